@@ -14,6 +14,12 @@ Before the warm-up the device is pre-heated for a fixed WALL TIME with real fram
 engine clock needs a few hundred milliseconds of load to reach its steady state, and `--steps 20` on a
 cold device times 2.6 ms of it.  `--steps` / `--warmup` are honoured exactly as passed.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, pre-heats, warms up, times the steps and prints the line: `value` and `ms_per_step` plus what follows
+from the timed region itself (per-launch statistics, roofline from the launch times).  `--full` adds everything that
+takes work of its own: the frame checked against the golden hashes, the counting pass (`rays_traced`), the serial and
+moving-camera passes, the host-buffer path, the profile-stamped `traffic` / `valu` figures and the CPU baseline.
+`--dump-outputs DIR` writes the last timed step's outputs (uint8 frame and float32 pre-clip RGB) as float32 .npy files.
 """
 import argparse
 import hashlib
@@ -45,6 +51,24 @@ PRICE_CLASS = {"add_f64": "v_add_f64", "mul_f64": "v_mul_f64", "fma_f64": "v_fma
                "cvt": "v_cvt_f32_f64", "int32": "v_and_b32", "int64": "v_lshlrev_b64"}
 UNCATEGORISED_FLOOR = "v_mov_b32"                   # the cheapest VALU class measured: prices the lower bound
 UNCATEGORISED_TYPICAL = "v_cmp_lt_f64_e64->sgpr"    # compares, selects, readlanes, 64-bit moves all measure 4.1-4.2 cycles
+DUMP_BYTES = 64_000_000     # --dump-outputs writes at most this much array data
+
+
+def dump_outputs(path, planes):
+    """--dump-outputs: every (3, w, h) array of `planes` as float32 `<path>/<name>.npy`.  If they exceed DUMP_BYTES together,
+    each is cut to the same seeded sample of pixels, (3, k), and the sample's flat pixel indices (column * h + row) go to
+    `pixel_index.npy` as float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    planes = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in planes.items() if v is not None}
+    if sum(v.nbytes for v in planes.values()) > DUMP_BYTES:
+        npix = next(iter(planes.values())).size // 3
+        keep = (DUMP_BYTES - 4096) // (12 * len(planes) + 8)
+        idx = np.sort(np.random.default_rng(0).choice(npix, keep, replace=False))
+        planes = {k: np.ascontiguousarray(v.reshape(3, npix)[:, idx]) for k, v in planes.items()}
+        planes["pixel_index"] = idx.astype(np.float64)
+    for k, v in planes.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
 
 
 def cpu_baseline(wl, rays_per_frame, min_wall_s=2.5):
@@ -175,6 +199,11 @@ def main():
     ap.add_argument("--frames-per-gather", type=int, default=8, help="N > 1: frames whose slabs travel to rank 0 in one gather")
     ap.add_argument("--frames-per-launch", type=int, default=16, help="frames one kernel launch renders (rt_render_sequence); with a gather: = --frames-per-gather; 0 = one Python call and one launch per frame, as in round 2")
     ap.add_argument("--gather", choices=("u8", "f32"), default="u8", help="N > 1: assemble the uint8 frames only, or the float32 pre-clip planes as well (a second gather per batch)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: golden-hash check, counting pass, "
+                    "serial / moving-camera / host-path passes, profile-stamped traffic and VALU figures, CPU baseline (the --no-* options below "
+                    "drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's uint8 frame and float32 pre-clip RGB "
+                    "as float32 DIR/frame_u8.npy, DIR/rgb_f32.npy (rank 0; a seeded pixel sample above 64 MB)")
     ap.add_argument("--no-dynamic", action="store_true", help="skip the moving-camera pass behind the timed region (dynamic)")
     ap.add_argument("--force-gather", action="store_true", help="run the N > 1 exchange structure on one GPU (world-size-1 RCCL group)")
     ap.add_argument("--preheat-ms", type=float, default=300.0, help="wall time of real frames rendered before the warm-up (clock ramp)")
@@ -441,14 +470,16 @@ def main():
         so_sha = hashlib.sha256(open(_lib.SO_PATH, "rb").read()).hexdigest()
         headline1 = world == 1 and name == workloads.HEADLINE
         suffix = "" if name == workloads.HEADLINE else f"_{name}"
-        tr = stamped(os.path.join(REPO, "profiles", f"traffic_{ROUND}{suffix}.json"), so_sha) if world == 1 else None
+        tr = stamped(os.path.join(REPO, "profiles", f"traffic_{ROUND}{suffix}.json"), so_sha) if world == 1 and a.full else None
         traffic = tr.get("hbm_bytes_per_launch") if tr else None
-        frame_host = frame.cpu().numpy()
+        if a.dump_outputs:                              # before anything else renders into the pipeline's buffers
+            dump_outputs(a.dump_outputs, {"frame_u8": frame.cpu().numpy(),
+                                          "rgb_f32": frame32.cpu().numpy() if frame32 is not None else None})
         check = check32 = None
         gpath = os.path.join(REPO, "tests", "golden", "frame_c2_1080p.npz")
-        if name == workloads.HEADLINE and os.path.exists(gpath):
+        if a.full and name == workloads.HEADLINE and os.path.exists(gpath):
             gold = np.load(gpath)
-            check = hashlib.sha256(frame_host.tobytes()).hexdigest() == str(gold["sha256_u8"])
+            check = hashlib.sha256(frame.cpu().numpy().tobytes()).hexdigest() == str(gold["sha256_u8"])
             # the float32 pre-clip planes (north_star's tolerance is stated on them): this rank's own at N = 1, the ASSEMBLED
             # frame with --gather f32
             if frame32 is not None and tuple(frame32.shape) == (3, w, h):
@@ -456,7 +487,7 @@ def main():
 
         # -- what the kernel really traced (counting instantiation, one frame, outside the timed region)
         traced = None
-        if world == 1:
+        if world == 1 and a.full:
             r.reset_stats()
             pc = r.params(wl["amb"], wl["lamb"], wl["refl"], wl["depth"], wl["aa"], spp=wl["spp"], seed=wl["seed"],
                           flags=_lib.RT_FLAG_COUNT_RAYS)
@@ -470,7 +501,7 @@ def main():
         # -- the same frames on ONE stream, strictly one after another: per-launch duration = frame period, so the
         # roofline fraction follows from the plain formula (bytes / duration / peak)
         serial = None
-        if world == 1 and not a.no_serial:
+        if world == 1 and a.full and not a.no_serial:
             ns = max(a.steps, 200)
             sh = pipe.stream_handle(0)
             u8p, f32p = pipe.u8v[0][0].data_ptr(), pipe.f32v[0][0].data_ptr()
@@ -497,7 +528,7 @@ def main():
         # the cull tables are rebuilt per camera position on the launching stream.  Same timing discipline as the main
         # region (fence, K steps, fence); never `value`.
         dynamic = None
-        if world == 1 and not a.no_dynamic:
+        if world == 1 and a.full and not a.no_dynamic:
             DNS = 3                                     # one launch per frame: three streams let consecutive frames overlap
             dstreams = pipe.streams if NS >= DNS else [torch.cuda.Stream(device=dev) for _ in range(DNS)]
             chunk = 8 * len(dstreams)                   # frames per call; frame i of a chunk always lands on stream i % DNS
@@ -536,7 +567,7 @@ def main():
 
         # -- the host-buffer entry point (what an unchanged main.py sees: launch + copy_to_host); never `value`
         host_path = None
-        if world == 1 and not a.no_host_path:
+        if world == 1 and a.full and not a.no_host_path:
             host_path = host_path_ms(r, wl, np)
 
         out = {
@@ -601,7 +632,7 @@ def main():
         # pass of THIS library build (profiles/valu_<round>[_<workload>].json carries the build's SHA-256; another build ->
         # null), priced with the cycles per wave-instruction tools/valu_prices.hip measured (profiles/r03_valu_prices.json;
         # MI355X_MICROARCH.md, "Per-instruction cycle constants": wave64 v_fma_f32 2 cycles with co-resident waves, 4 alone).
-        v = stamped(os.path.join(REPO, "profiles", f"valu_{ROUND}{suffix}.json"), so_sha) if world == 1 else None
+        v = stamped(os.path.join(REPO, "profiles", f"valu_{ROUND}{suffix}.json"), so_sha) if world == 1 and a.full else None
         ppath = os.path.join(REPO, "profiles", PRICES)
         if v and os.path.exists(ppath):
             info = r.kernel_info()
@@ -636,7 +667,7 @@ def main():
                 out["valu"]["reference_equivalent_flop_per_frame"] = int(rays_per_frame * (18 * S + 14 * P) + traced["hits"] * (51 + 24 * L))
         else:
             out["valu"] = None
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, rays_per_frame)
             # SURVEY.md section 8(d) / BASELINE.md section 2: the reference's own Python (numba.cuda kernels run as plain Python
             # under an identity-decorator stand-in, the arithmetic NUMBA_ENABLE_CUDASIM=1 runs) cannot travel to the GPU box; its

@@ -60,7 +60,7 @@ def test_bench_runs_under_torchrun_world1():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29544", os.path.join(REPO, "bench.py"),
-                          "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+                          "--gpus", "1", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -73,7 +73,7 @@ def test_bench_exchange_structure_on_one_gpu(extra):
     """The N > 1 choreography of bench.py (frames round-robin on render streams, slabs of F frames per RCCL gather
     on a separate stream, two exchanges in flight, last batch partly filled) on a world-size-1 RCCL group."""
     import json
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-gather", "--warmup", "5", "--no-cpu-baseline"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-gather", "--warmup", "5", "--full", "--no-cpu-baseline"] + extra,
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29546"))
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -86,7 +86,7 @@ def test_bench_force_gather_float32_assembly():
     assembled frame's hash is still the reference's (the uint8 one); bench.py's line carries the batched-launch fields."""
     import json
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-gather", "--gather", "f32", "--warmup", "5", "--steps", "20",
-                          "--no-cpu-baseline", "--no-host-path", "--no-serial", "--no-dynamic"],
+                          "--full", "--no-cpu-baseline", "--no-host-path", "--no-serial", "--no-dynamic"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29547"))
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -99,7 +99,7 @@ def test_bench_default_line_fields():
     """The default single-GPU line under the driver's flags: batched launches (host submit cost far below a frame), the
     moving-camera block, the priced issue bound when the profile constants match this build."""
     import json
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-host-path"],
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-host-path"],
                          capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -113,6 +113,27 @@ def test_bench_default_line_fields():
         assert j["valu"]["issue_frac"] <= 1.0 and j["valu"]["issue_bound_ms"] < j["valu"]["issue_estimate_ms"]
 
 
+def test_bench_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields without the extra passes, and --dump-outputs writes the last timed
+    frame: the uint8 frame and the float32 pre-clip planes, as float32, bit-equal to the reference's (golden hashes)."""
+    import hashlib
+    import json
+    import numpy as np
+    from conftest import load_frame
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "37", "--warmup", "5",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 37 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "Mrays/s" and j["dtype"] == "f64"
+    assert j["dynamic"] is None and j["rays_traced"] is None and "cpu_baseline" not in j
+    u8, f32 = np.load(tmp_path / "out" / "frame_u8.npy"), np.load(tmp_path / "out" / "rgb_f32.npy")
+    assert u8.dtype == f32.dtype == np.float32 and u8.shape == f32.shape == (3, 1920, 1080)
+    gold = load_frame("c2_1080p")
+    assert hashlib.sha256(u8.astype(np.uint8).tobytes()).hexdigest() == str(gold["sha256_u8"])
+    assert hashlib.sha256(f32.tobytes()).hexdigest() == str(gold["sha256_rgb32"])
+
+
 def test_bench_spawns_its_rank_for_config5_spp4():
     """`python bench.py --gpus 1 --workload c5_..._spp4` through torch.distributed.run (the launcher the driver uses for
     N > 1), a few steps of the largest BASELINE configuration: one JSON line with the workload's ray counts."""
@@ -121,7 +142,7 @@ def test_bench_spawns_its_rank_for_config5_spp4():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29548", os.path.join(REPO, "bench.py"),
                           "--gpus", "1", "--workload", "c5_7680x4320_s256_d8_spp4", "--steps", "4", "--warmup", "1", "--preheat-ms", "0",
-                          "--no-cpu-baseline", "--no-host-path", "--no-serial", "--no-dynamic"],
+                          "--full", "--no-cpu-baseline", "--no-host-path", "--no-serial", "--no-dynamic"],
                          capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -141,7 +162,7 @@ def test_bench_multi_rank_rehearsal_on_one_gpu(n, extra):
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
                           "--master-addr", "127.0.0.1", "--master-port", str(29560 + n), os.path.join(REPO, "bench.py"),
                           "--gpus", str(n), "--rehearse-gloo", "--steps", "24", "--warmup", "4", "--preheat-ms", "20", "--balance-rounds", "2",
-                          "--no-cpu-baseline", "--no-serial", "--no-dynamic"] + extra,
+                          "--full", "--no-cpu-baseline", "--no-serial", "--no-dynamic"] + extra,
                          capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]

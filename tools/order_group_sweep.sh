@@ -22,7 +22,7 @@ cd /tmp && export TMPDIR=/tmp
 for mode in "1 16" "3 0"; do set -- $mode; ST=$1; FPL=$2; DIV=$(( FPL > 0 ? FPL : 1 ))
 for g in 0 2 3 4 5; do
   export MI355RT_ORDER_GROUP=$g
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/ws_tmp -- python3 $ROOT/bench.py --steps 64 --warmup 16 --preheat-ms 0 --no-serial --no-host-path --no-cpu-baseline --no-dynamic --streams $ST --frames-per-launch $FPL > $OUT/ws_tmp.log 2>&1 || { tail -5 $OUT/ws_tmp.log; exit 1; }
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/ws_tmp -- python3 $ROOT/bench.py --steps 64 --warmup 16 --preheat-ms 0 --full --no-serial --no-host-path --no-cpu-baseline --no-dynamic --streams $ST --frames-per-launch $FPL > $OUT/ws_tmp.log 2>&1 || { tail -5 $OUT/ws_tmp.log; exit 1; }
   python3 - <<PY | tee -a $LOG
 import csv,glob
 f=glob.glob("$OUT/ws_tmp/**/*counter_collection.csv",recursive=True)[0]

@@ -8,7 +8,7 @@ for LIB in "$@"; do
   OUT=$ROOT/gpurun_out/pmcv_$TAG
   mkdir -p $OUT
   export MI355RT_SO=$ROOT/$LIB
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 12 --warmup 3 --no-cpu-baseline --streams 1 > $OUT/log.txt 2>&1 || exit 1
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 12 --warmup 3 --full --no-cpu-baseline --streams 1 > $OUT/log.txt 2>&1 || exit 1
   python3 - <<PY
 import csv, glob, collections
 f=glob.glob('$OUT/*/*counter_collection.csv')[0]

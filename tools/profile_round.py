@@ -67,7 +67,7 @@ def main():
     shutil.rmtree(out, ignore_errors=True)
     os.makedirs(out)
     bench = os.path.join(REPO, "bench.py")
-    common = ["--streams", str(a.streams), "--no-cpu-baseline", "--no-dynamic"] + (["--workload", a.workload] if a.workload else []) + (["--flags", str(a.flags)] if a.flags else [])
+    common = ["--streams", str(a.streams), "--full", "--no-cpu-baseline", "--no-dynamic"] + (["--workload", a.workload] if a.workload else []) + (["--flags", str(a.flags)] if a.flags else [])
 
     # 1. kernel trace of the bench command, without its serial pass and host-path timing: every render launch in the
     #    trace is then of the kind the timed region times (pre-heat, warm-up and timed steps on --streams streams), so
