@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Render a frame with the `Renderer` API and save it as a PNG.
 
-    python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa] [--frames 50] [--out output/render.png]
+    python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa] [--frames 50] [--materials] [--out output/render.png]
+
+--materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -16,7 +18,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import python_ray_tracer_amd as pkg
 from python_ray_tracer_amd import _lib as L
-from python_ray_tracer_amd.scene import Scene, Camera
+from python_ray_tracer_amd.scene import Scene, Camera, Material
 from python_ray_tracer_amd.viewer import convert_array_to_image
 
 
@@ -26,12 +28,19 @@ def main():
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--aa", action="store_true", help="the reference's 9-tap anti-aliasing")
     ap.add_argument("--frames", type=int, default=50)
+    ap.add_argument("--materials", action="store_true", help="mirror floor, matte spheres (per-object materials)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
     cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=[0, -30, 0])
     with pkg.Renderer(0) as r:
-        r.set_scene(*Scene.default_scene().generate_scene())
+        scene = Scene.default_scene()
+        mats = None
+        if a.materials:
+            for p in scene.planes:
+                p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
+            mats = scene.generate_materials(Material(0.05, 0.8, 0.0))   # matte spheres: no reflection
+        r.set_scene(*scene.generate_scene(), materials=mats)
         r.set_camera(cam.position, cam.rotation)
         r.set_raygen(w, h, *cam.raygen())
         image = r.host_array((h, w, 3), np.uint8)
@@ -48,7 +57,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} materials={a.materials}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -35,11 +35,12 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 6
+#define RT_ABI_VERSION 7
 #define RT_MAX_DEPTH 16      /* entries of rt_params.refl_pow (reflection bounces) */
 #define RT_MAX_SPHERES 1024  /* scene limits: the packed scene must fit one workgroup's LDS */
 #define RT_MAX_PLANES 64
 #define RT_MAX_LIGHTS 64
+#define RT_MAX_MATERIALS 256  /* entries of a scene's material table (rt_set_scene_materials) */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -87,7 +88,9 @@ typedef enum rt_status {
                                 with 161 spheres or more; rt_device.h).  Same pixels; for A/B timing.  (The name dates from round 2's
                                 bundle pre-cull, which the flag also switched off; that variant was removed in round 3.) */
 #define RT_FLAG_COUNT_RAYS 16 /* run the counting instantiation of the kernel (slower: registers instead of LDS-parked
-                                state): adds this launch's ray counts to the context's rt_stats.  Same pixels. */
+                                state): adds this launch's ray counts to the context's rt_stats.  Same pixels.
+                                Refused (RT_ERR_BAD_ARG) for a scene with materials: the counting instantiations exist
+                                for the shading scalars of rt_params only. */
 
 typedef struct rt_ctx rt_ctx;
 
@@ -160,6 +163,23 @@ const char *rt_last_error(const rt_ctx *ctx);
  * Any of S, L, P may be 0 (the pointer is then ignored). */
 int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
                  const float *planes, int P, int flags);
+
+/* The same scene with per-object materials (the reference's "more robust way of defining materials", README to-do list).
+ *   materials        float64 (M,3) C-order, rows (amb, lamb, refl); finite; 0 <= M <= RT_MAX_MATERIALS
+ *   sphere_material  int32 (S,), plane_material int32 (P,): each object's row of the table, in [0, M)
+ * A launch on such a scene ignores rt_params.amb, lamb and refl_pow.  Trace k of a sample (k = 0 the primary ray, 1..depth
+ * the bounces) that hits an object of material (amb_k, lamb_k, refl_k) is the reference's trace() (trace.py:44-112) with
+ * ambient_int = amb_k and lambert_int = lamb_k, and its colour is added with the weight W_k = ((refl_0 * refl_1) * ...) *
+ * refl_{k-1} (float64, left to right) in place of reflection_int ** k (trace.py:131); a trace that misses ends the path.
+ * With one material (amb, lamb, r) for every object and r = 0, 1 or a power of two the frame is byte-identical to
+ * rt_set_scene and the scalars (amb, lamb, r); for other r, r*r*r may differ from the host's r**3 in the last bit.
+ * M == 0 is rt_set_scene (the id arrays are then ignored).  Invalid ids, coefficients or NULL arrays: RT_ERR_BAD_ARG, and
+ * the previous scene stays current.  Table and ids travel with the scene (see "Streams" above).  RT_FLAG_COUNT_RAYS is
+ * refused for such a scene. */
+int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                           const float *planes, int P, int flags,
+                           const double *materials, int M,
+                           const int32_t *sphere_material, const int32_t *plane_material);
 
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);

@@ -5,9 +5,10 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MI355RT_SO") or os.path.join(HERE, "libmi355rt.so")   # env override: A/B profiling of other builds
 
-RT_ABI_VERSION = 6
+RT_ABI_VERSION = 7
 RT_MAX_DEPTH = 16
 RT_MAX_SPHERES, RT_MAX_PLANES, RT_MAX_LIGHTS = 1024, 64, 64
+RT_MAX_MATERIALS = 256
 RT_OK, RT_ERR_BAD_ARG, RT_ERR_HIP, RT_ERR_NO_DEVICE, RT_ERR_STATE, RT_ERR_ALLOC = 0, -1, -2, -3, -4, -5
 RT_AA_NONE, RT_AA_REFERENCE, RT_AA_STOCHASTIC = 0, 1, 2
 RT_MAX_SPP = 64
@@ -42,6 +43,8 @@ PROTOTYPES = {
     "rt_destroy": (C.c_int, [_vp]),
     "rt_last_error": (C.c_char_p, [_vp]),
     "rt_set_scene": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int]),
+    "rt_set_scene_materials": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "rt_set_pixel_loc": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),

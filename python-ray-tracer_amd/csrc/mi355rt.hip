@@ -72,6 +72,8 @@ struct rt_ctx {
     Buf pixel_loc, u8, f32;
     int S = 0, P = 0, L = 0;
     int NC = 0;                   // sphere clusters (0 = flat scene)
+    int M = 0;                    // materials of the current scene (rt_set_scene_materials; 0 = the launch's shading scalars)
+    size_t mat_lds_limit_set = 0; // hipFuncAttributeMaxDynamicSharedMemorySize of the material kernels (lds_limit_set: the others)
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
@@ -186,6 +188,8 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
         if (ctx->explicit_grid) return fail(ctx, RT_ERR_STATE, "RT_AA_STOCHASTIC needs the closed-form ray grid (rt_set_raygen)");
     }
     if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
+    if (ctx->M > 0 && (p->flags & RT_FLAG_COUNT_RAYS))
+        return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_COUNT_RAYS is not available for a scene with materials");
     return RT_OK;
 }
 
@@ -217,6 +221,30 @@ const void *kernel_variant(bool aa, bool park, int wpw, bool count = false, bool
                   : (park ? (const void *)rt::render_kernel<false, true, 2> : (const void *)rt::render_kernel<false, false, 2>);
     return aa ? (park ? (const void *)rt::render_kernel<true, true, 4> : (const void *)rt::render_kernel<true, false, 4>)
               : (park ? (const void *)rt::render_kernel<false, true, 4> : (const void *)rt::render_kernel<false, false, 4>);
+}
+
+// The instantiations for scenes with materials (rt_device.h: MAT), one for every variant the dispatcher picks for a scene
+// without them except the counting ones (RT_FLAG_COUNT_RAYS is refused for such scenes): same arguments as lanes_variant
+// (lanes), lattice_variant (lattice) and kernel_variant.
+const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
+{
+    if (lanes) {
+        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true>;
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true>);
+    }
+    if (lattice) {
+        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true>;
+        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true>;
+    }
+    if (norec && wpw == 4 && !aa)
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true>;
+    if (wpw == 2)
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true>);
+    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true>)
+              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true>);
 }
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
@@ -383,18 +411,29 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // variant runs 7 per CU if they fit and needs 6, the register variant 5.  Config 4 (64 spheres): 6 -> 7 workgroups, -5 %;
     // 100 spheres: register variant at 5 -> parked at 6, -7 %; where the count stays (36, 49, 144 spheres) it costs 0...2 %
     // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
+    // a scene with materials runs the material twins of the same variants; their LDS images hold the material data too
+    // (matd doubles), and the parked ones one more per-thread slot
+    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P);   // (the block is in the launch's scene buffer: rt::mat_offset)
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr);
+        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd);
         if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
-        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr));
+        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec);
+    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec);
-    const void *fn = lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (lds > 48 * 1024 && lds > ctx->lds_limit_set) {
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd);
+    const void *fn = matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
+                          : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
+    if (matd) {
+        if (lds > 48 * 1024 && lds > ctx->mat_lds_limit_set) {
+            for (int v = 0; v < 64; ++v)
+                RT_HIP(ctx, hipFuncSetAttribute(material_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ctx->mat_lds_limit_set = lds;
+        }
+    } else if (lds > 48 * 1024 && lds > ctx->lds_limit_set) {
         for (int v = 0; v < 8; ++v)
             RT_HIP(ctx, hipFuncSetAttribute(kernel_variant(v & 1, v & 2, (v & 4) ? 4 : 2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         for (int v = 0; v < 2; ++v) {
@@ -640,10 +679,30 @@ const char *rt_last_error(const rt_ctx *ctx) { return ctx ? ctx->err.c_str() : g
 
 int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags)
 {
+    return rt_set_scene_materials(ctx, spheres, S, lights, L, planes, P, flags, nullptr, 0, nullptr, nullptr);
+}
+
+int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
+                           const double *materials, int M, const int32_t *sphere_material, const int32_t *plane_material)
+{
     if (!ctx) return RT_ERR_BAD_ARG;
     if (S < 0 || S > RT_MAX_SPHERES || L < 0 || L > RT_MAX_LIGHTS || P < 0 || P > RT_MAX_PLANES)
         return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
     if ((S && !spheres) || (L && !lights) || (P && !planes)) return fail(ctx, RT_ERR_BAD_ARG, "NULL scene array with non-zero count");
+    if (M < 0 || M > RT_MAX_MATERIALS) return fail(ctx, RT_ERR_BAD_ARG, "material count outside 0..RT_MAX_MATERIALS");
+    if (M > 0) {
+        if (!materials) return fail(ctx, RT_ERR_BAD_ARG, "materials is NULL with M > 0");
+        if ((S && !sphere_material) || (P && !plane_material)) return fail(ctx, RT_ERR_BAD_ARG, "NULL material id array with non-zero count");
+        for (int i = 0; i < 3 * M; ++i)
+            if (!std::isfinite(materials[i]))
+                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(i / 3) + " has a coefficient that is not finite");
+        for (int k = 0; k < S; ++k)
+            if (sphere_material[k] < 0 || sphere_material[k] >= M)
+                return fail(ctx, RT_ERR_BAD_ARG, "sphere_material[" + std::to_string(k) + "] outside 0..M-1");
+        for (int k = 0; k < P; ++k)
+            if (plane_material[k] < 0 || plane_material[k] >= M)
+                return fail(ctx, RT_ERR_BAD_ARG, "plane_material[" + std::to_string(k) + "] outside 0..M-1");
+    }
     int nclusters = 0;
     try {
         // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
@@ -688,8 +747,8 @@ int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, 
             NC = (S + rt::CLUSTER - 1) / rt::CLUSTER;
         }
         nclusters = NC;
-        std::vector<double> rec((size_t)S * rt::SPH_STRIDE + (size_t)P * rt::PL_STRIDE + (size_t)L * rt::LT_STRIDE +
-                                (size_t)(NC + rt::supers(NC)) * rt::CL_STRIDE + 1, 0.0);
+        const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
+        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -749,6 +808,14 @@ int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, 
             bound(c * rt::CLUSTER, std::min(S, (c + 1) * rt::CLUSTER), sp);
         for (int g = 0; g < rt::supers(NC); ++g, sp += rt::CL_STRIDE)      // groups of rt::SUPER clusters
             bound(g * rt::SUPER * rt::CLUSTER, std::min(S, (g + 1) * rt::SUPER * rt::CLUSTER), sp);
+        if (M > 0) {   // the material block (rt::mat_offset): M, the table, the ids of the sphere SLOTS (the order above) and of the planes
+            rec[mat_off] = (double)M;
+            std::memcpy(rec.data() + mat_off + 1, materials, (size_t)3 * M * sizeof(double));
+            std::vector<int32_t> ids((size_t)S + P);
+            for (int slot = 0; slot < S; ++slot) ids[slot] = sphere_material[order[slot]];
+            for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
+            if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)3 * M, ids.data(), ids.size() * sizeof(int32_t));
+        }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
         // the next buffer of the ring: launches in flight keep reading the buffers they were queued with.  Whatever
@@ -777,6 +844,7 @@ int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, 
     }
     ctx->scene_extent2 = ext2;
     ctx->S = S; ctx->P = P; ctx->L = L; ctx->NC = nclusters;
+    ctx->M = M;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

@@ -316,6 +316,33 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
     }
 };
 
+// Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
+// its running reflection weight W.  An empty struct, and every use a no-op, in the kernels of scenes without materials.
+// Three per-thread LDS slots from WSLOT on (lds_slots) hold W, and the Lambert coefficient and reflectivity of the lane's current
+// hit, copied there from the table entry once per hit: no VGPR holds a coefficient or the entry's address across the light
+// loop (with them in registers seven of the 22 material kernels spilled more than their default twins).  The slots are addressed
+// off the same base as the parked colour (an immediate offset) or, FRESH (register variants, REMAT), re-derived from the lane's
+// number.  The table and the ids are wave-uniform LDS byte addresses, kept scalar until a hit reads them (see opaque()).
+template <bool MAT, int WSLOT, bool FRESH> struct MatState {};
+template <int WSLOT, bool FRESH> struct MatState<true, WSLOT, FRESH> {
+    unsigned tab;              // LDS: M x {amb, lamb, refl}
+    unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
+    enum { W = 0, LAMB = 1, REFL = 2 };
+    template <int WGT, int k> __device__ __forceinline__ volatile lds_f64 *at(const double *acc, int wave) const
+    {
+        if constexpr (FRESH) return (volatile lds_f64 *)acc + (WSLOT + k) * WGT + wave * 64 + fresh_lane();
+        else return (volatile lds_f64 *)acc + (WSLOT + k) * WGT + threadIdx.x;
+    }
+    __device__ __forceinline__ volatile const lds_f64 *entry(int slot) const   // the material of slot `slot`
+    {
+        unsigned t = tab, i = ids;
+        asm volatile("" : "+s"(t), "+s"(i));
+        typedef __attribute__((address_space(3))) const int lds_ci32;
+        const int m = ((lds_ci32 *)(size_t)i)[slot];
+        return (volatile const lds_f64 *)(size_t)t + 3 * m;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // Conservative float32 cull.  For a ray (o, R) and sphere (c, r2) the reference computes, in
 // float64, D = s² - a·(|L|² - r2) with L = o - c, s = L·R, and reports a miss when D < 0, or when
@@ -1160,9 +1187,10 @@ template <> struct RayCount<true> {
 
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
-template <bool PARK, int WGT, bool COUNT, int MODE>
+// MAT: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
+template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
-                                             V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt)
+                                             V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms)
 {
     constexpr bool NOREC = MODE >= 1;         // no float64 sphere records in LDS (sphere_hot)
     const int S = p.S, P = p.P, L = opaque(p.L);
@@ -1195,6 +1223,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             else if constexpr (PARK) return colp[c];
             else return c == 0 ? colr.x : (c == 1 ? colr.y : colr.z);
         };
+        volatile const lds_f64 *mp = nullptr;
         V3 N, bN;
         if (type == HIT_SPHERE) {                                             // :63-66
             const SphHot g = sphere_hot<NOREC>(lds, idx);
@@ -1205,6 +1234,15 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             N = V3{g[6], g[7], g[8]};                                         // float32-renormalised, host-side
             bN = V3{g[9], g[10], g[11]};                                      // BIAS*N as the reference rounds it
         }
+        if constexpr (MAT) {
+            // the object's entry of the LDS material table (looked up after the normal: its address is live only here);
+            // Lambert coefficient and reflectivity go to the lane's slots
+            mp = ms.entry((type == HIT_SPHERE) ? idx : S + idx);
+            *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) = mp[1];
+            *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = mp[2];
+            const double amb = mp[0];
+            rgb = V3{0.0 + amb * col(0), 0.0 + amb * col(1), 0.0 + amb * col(2)};   // :77 as the reference rounds it (+0 for a negative amb)
+        } else
         rgb = V3{p.amb * col(0), p.amb * col(1), p.amb * col(2)};             // :77 (0 + amb*col)
         Pt = V3{Pt.x + bN.x, Pt.y + bN.y, Pt.z + bN.z};                       // :82-83
         const int self = (type == HIT_SPHERE) ? idx : -1;
@@ -1216,7 +1254,9 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         for (int m = 0; m < L; ++m) {                                         // :86-102
             const double *g = lt + m * LT_STRIDE;
             const V3 Ld = normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});   // common.py:84-91
-            const double k = p.lamb * dot3(Ld, N);                            // :99
+            double lamb;
+            if constexpr (MAT) lamb = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave); else lamb = p.lamb;
+            const double k = lamb * dot3(Ld, N);                              // :99
             // :92-102 — the shadow query's answer is only used when k > 0; it has no other effect,
             // so lanes with k <= 0 (light behind the surface) do not ask.
             cnt.shadow(true, k > 0.0);
@@ -1240,11 +1280,15 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 
 
 // trace.py:115-133.  Bounce 0 rays all start at the camera (cull anchor 0); later bounces have none.
-template <bool PARK, int WGT, bool COUNT, int MODE>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
-__device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt)
+// MAT (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
+// of the surfaces the ray was reflected off, in place of p.refl_pow[b-1].  W stops changing where the path ends: the missed
+// bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
+template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
+__device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms)
 {
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
+    if constexpr (MAT) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
     for (int b = 0; b <= p.depth; ++b) {
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;                                   // wave-uniform exit
         if constexpr (COUNT) {                                                // lane utilisation per bounce: waves entering, lanes alive
@@ -1258,12 +1302,19 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt);
+        trace_bounce<PARK, WGT, COUNT, MODE, MAT, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0)
-            const double wgt = p.refl_pow[b - 1];
+            double wgt;
+            if constexpr (MAT) wgt = *ms.template at<WGT, MS::W>(lds.acc, lds.wave); else wgt = p.refl_pow[b - 1];
             const V3 a = acc.get();
             acc.set(V3{a.x + wgt * rgb.x, a.y + wgt * rgb.y, a.z + wgt * rgb.z});
+        }
+        if constexpr (MAT) {                                                  // W_{b+1} = W_b * refl_b (W_1 = 1 * refl_0 = refl_0)
+            if (alive) {
+                volatile lds_f64 *w = ms.template at<WGT, MS::W>(lds.acc, lds.wave);
+                *w = *w * *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave);
+            }
         }
     }
     return acc.get();
@@ -1347,7 +1398,12 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
 
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
-__host__ __device__ inline int lds_slots(bool aa, bool park, bool mode2 = false) { return park ? ((aa && !mode2) ? 9 : 6) : 0; }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers)
+__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl)
+// The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
+// M, then the M x 3 table {amb, lamb, refl}, then S + P int32 material ids of the slots (padded to a double).  Material kernels
+// stage it at the end of their LDS image.
+__host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
+__host__ __device__ inline size_t mat_doubles(int M, int S, int P) { return M > 0 ? 1 + 3 * (size_t)M + ((size_t)S + P + 1) / 2 : 0; }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
@@ -1379,9 +1435,11 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
     return col ? t.total_col : (lanes ? t.total_lanes : t.total);
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
-__host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false)
+// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise.
+__host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
+                                            size_t matd = 0)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2) * wgt) * sizeof(double) +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0) * wgt + matd) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
            + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
@@ -1500,9 +1558,19 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
     }
 }
 
+// The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
+template <bool MAT, int WSLOT, bool FRESH>
+__device__ __forceinline__ MatState<MAT, WSLOT, FRESH> mat_state(double *matl, int M)
+{
+    typedef __attribute__((address_space(3))) double lds_d;
+    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + 3 * M)};
+    else return {};
+}
+
 // AA = false: aliasing off — instantiated separately so that the common case does not carry the tap loop's
 // live state (registers decide occupancy here).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0>
+// MAT: the scene has a material table (per-object shading coefficients, rt_set_scene_materials).
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false>
 #ifndef RT_W_PARK
 #define RT_W_PARK 7
 #endif
@@ -1520,7 +1588,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
     double *accum = lds_raw + nrec;
-    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2) * WG_THREADS);
+    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
@@ -1542,6 +1610,19 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         f4 *dst = reinterpret_cast<f4 *>(sph32);
         for (int i = threadIdx.x; i < nf4; i += WG_THREADS) dst[i] = src[i];
 #endif
+    }
+    // MAT: the material block (mat_offset) behind the workgroup words (and the region counters of the measurement build)
+#ifdef RT_REGION_STATS
+    double *matl = reinterpret_cast<double *>(wgstat + 4 + WPW * 32);
+#else
+    double *matl = reinterpret_cast<double *>(wgstat + 4);
+#endif
+    int nmat = 0;
+    if constexpr (MAT) {
+        const double *msrc = p.scene + mat_offset(p.S, p.P, p.L, p.NC);
+        nmat = (int)msrc[0];
+        const int nm = (int)mat_doubles(nmat, p.S, p.P);
+        for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
     }
     __syncthreads();
     // two-wave workgroups serve the small flat scenes only (the host sends every clustered scene to workgroups of 4): with
@@ -1604,9 +1685,11 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
 
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
+    constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
+    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3>(matl, nmat);
     double R, G, B;
     if constexpr (!AA) {
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt);   // kernels.py:19-26
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -1634,7 +1717,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
                 const V3 Pn = pixel_P(p, interior ? x + ddx : xc, interior ? y + ddy : yc);
                 Pt = V3{0.5 * Pp.x + 0.5 * Pn.x, 0.5 * Pp.y + 0.5 * Pn.y, 0.5 * Pp.z + 0.5 * Pn.z};   // :43-50
             }
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

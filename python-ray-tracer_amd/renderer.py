@@ -95,12 +95,27 @@ class Renderer:
         self.close()
 
     # -- inputs -----------------------------------------------------------------------------
-    def set_scene(self, spheres, lights, planes, flags=0):
-        """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97)."""
+    def set_scene(self, spheres, lights, planes, flags=0, materials=None):
+        """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
+        materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
+        sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
+        the launches' amb, lamb and refl are then ignored (rt_set_scene_materials)."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
-        self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
-                                           p.ctypes.data_as(fp), p.shape[1], int(flags)))
+        if materials is None:
+            self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
+                                               p.ctypes.data_as(fp), p.shape[1], int(flags)))
+        else:
+            table, sid, pid = materials
+            t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 3)
+            si = np.ascontiguousarray(sid, dtype=np.int32).reshape(-1)
+            pi = np.ascontiguousarray(pid, dtype=np.int32).reshape(-1)
+            if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
+                raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
+            ip = C.POINTER(C.c_int32)
+            self._check(self._lib.rt_set_scene_materials(
+                self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp), p.shape[1],
+                int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
         self.counts = (s.shape[1], l.shape[1], p.shape[1])
         self.generation["scene"] += 1
 

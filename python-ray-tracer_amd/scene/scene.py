@@ -1,12 +1,26 @@
 """Scene description -> the float32 arrays the kernel consumes, reference scene/scene.py:9-115:
 spheres (7,S) rows cx,cy,cz,r,R,G,B; lights (3,L); planes (9,P) rows ox,oy,oz,nx,ny,nz,R,G,B with the
-normal normalised in float64 before the float32 store (scene.py:50)."""
+normal normalised in float64 before the float32 store (scene.py:50).
+Per-object materials (not in the reference, whose README lists them as a to-do) are an optional `material=` of a sphere or
+plane; Scene.generate_materials() turns them into the table and ids of Renderer.set_scene(..., materials=...)."""
 from dataclasses import dataclass
-from typing import ClassVar, List
+from typing import ClassVar, List, Optional
 
 import numpy as np
 
 from .colors import RED, BLUE, MAGENTA, YELLOW, GREEN, GREY
+
+
+@dataclass(frozen=True)
+class Material:
+    """Shading coefficients of one object: the reference's ambient_int, lambert_int and reflection_int (trace.py:44, :115),
+    per object instead of per frame.  float64; any finite value."""
+    amb: float
+    lamb: float
+    refl: float
+
+    def key(self):
+        return (float(self.amb), float(self.lamb), float(self.refl))
 
 
 @dataclass
@@ -14,6 +28,7 @@ class Sphere:
     origin: object
     radius: float
     color: object
+    material: Optional[Material] = None
     data_length: ClassVar[int] = 7
 
     def to_array(self):
@@ -35,6 +50,7 @@ class Plane:
     origin: object
     normal: object
     color: object
+    material: Optional[Material] = None
     data_length: ClassVar[int] = 9
 
     def to_array(self):
@@ -65,6 +81,25 @@ class Scene:
 
     def generate_scene(self):
         return self.get_spheres(), self.get_lights(), self.get_planes()
+
+    def generate_materials(self, default: Material):
+        """(table float64 (M,3) rows amb, lamb, refl; sphere_ids int32 (S,); plane_ids int32 (P,)) for
+        Renderer.set_scene(..., materials=...).  Objects without a material get `default`; equal materials share one row,
+        in the order of first use (spheres, then planes)."""
+        rows, index = [], {}
+
+        def ids(objs):
+            out = np.zeros(len(objs), dtype=np.int32)
+            for i, o in enumerate(objs):
+                k = (o.material if o.material is not None else default).key()
+                if k not in index:
+                    index[k] = len(rows)
+                    rows.append(k)
+                out[i] = index[k]
+            return out
+
+        sphere_ids, plane_ids = ids(self.spheres), ids(self.planes)
+        return np.array(rows, dtype=np.float64).reshape(-1, 3), sphere_ids, plane_ids
 
     @staticmethod
     def default_scene():

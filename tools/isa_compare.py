@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 ISA and resource usage of the kernels of two source trees (CPU only, no GPU).
+
+    python tools/isa_compare.py [--base REV] [--twins]
+
+Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and once for REV (default HEAD, extracted with
+`git archive` into a temporary directory), then, for every kernel of REV:
+  * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
+    kernel's own symbol renumbered, must be identical in the working tree;
+  * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
+A render_kernel instantiation is matched by its template arguments; a trailing `false` (the MAT parameter, rt_device.h) of the
+working tree's names is ignored, so the default kernels of a tree with material kernels match those of a tree without.
+--twins also prints each material kernel (MAT = true) next to its default twin.  Exit status 1 if any kernel differs.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join("python-ray-tracer_amd", "csrc")
+
+
+def build(tree):
+    r = subprocess.run(["make", "-s", "-C", os.path.join(tree, CSRC), "-B", "asm"], capture_output=True, text=True)
+    if r.returncode:
+        sys.exit(r.stdout + r.stderr)
+    return open(os.path.join(tree, CSRC, "rt_kernel.gfx950.s")).read(), r.stderr
+
+
+def key(name):
+    """Kernel symbol -> (kernel, template arguments without a trailing MAT = false), and whether it is a MAT = true kernel."""
+    m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
+    if not m:
+        return name, False
+    args = re.findall(r"L[bi](\d+)E", m.group(2))
+    mat = len(args) == 7 and args[-1] == "1"
+    if len(args) == 7:
+        args = args[:-1]
+    return (m.group(1),) + tuple(args), mat
+
+
+def functions(asm):
+    out = {}
+    for m in re.finditer(r"^\t\.type\t(\S+),@function\n(.*?)^\.Lfunc_end\d+:", asm, flags=re.S | re.M):
+        name, body = m.group(1), m.group(2)
+        lines = []
+        for ln in body.split("\n"):
+            ln = ln.split(";")[0].rstrip()
+            if not ln.strip() or ln.lstrip().startswith(".") and not ln.startswith(".L"):
+                continue
+            lines.append(ln.replace(name, "<fn>"))
+        text = "\n".join(lines)
+        labels = {}
+        text = re.sub(r"\.(LBB|Lfunc_end)\d+_?\d*", lambda x: labels.setdefault(x.group(0), f".L{len(labels)}"), text)
+        out[name] = text
+    return out
+
+
+def resources(log):
+    out, cur = {}, None
+    for ln in log.split("\n"):
+        m = re.search(r"remark: Function Name: (\S+)", ln)
+        if m:
+            cur = m.group(1); out[cur] = {}
+            continue
+        m = re.search(r"remark:\s+([^:]+): (\S+) \[-Rpass-analysis", ln)
+        if m and cur:
+            out[cur][m.group(1).strip()] = m.group(2)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--base", default="HEAD")
+    ap.add_argument("--twins", action="store_true")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        arch = subprocess.run(["git", "-C", REPO, "archive", a.base, CSRC, "include"], capture_output=True, check=True).stdout
+        subprocess.run(["tar", "-x", "-C", tmp], input=arch, check=True)
+        base_asm, base_log = build(tmp)
+    new_asm, new_log = build(REPO)
+    bf, nf = functions(base_asm), functions(new_asm)
+    br, nr = resources(base_log), resources(new_log)
+    new_by_key = {}
+    for n in nf:
+        k, mat = key(n)
+        new_by_key[(k, mat)] = n
+    bad = 0
+    for b in sorted(bf):
+        k, _ = key(b)
+        n = new_by_key.get((k, False))
+        if n is None:
+            print(f"MISSING  {b}"); bad += 1; continue
+        same_isa = bf[b] == nf[n]
+        same_res = br.get(b) == nr.get(n)
+        print(f"{'same' if same_isa and same_res else 'DIFF'}  isa={'=' if same_isa else '!'} res={'=' if same_res else '!'} "
+              f"{len(bf[b].splitlines()):6d} lines  {k}")
+        bad += not (same_isa and same_res)
+    print(f"{len(bf)} kernels of {a.base} compared, {bad} differ")
+    if a.twins:
+        cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
+        print("\nmaterial kernel (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   default twin")
+        for (k, mat), n in sorted(new_by_key.items(), key=str):
+            if not mat:
+                continue
+            t = new_by_key.get((k, False))
+            m_, d_ = nr.get(n, {}), nr.get(t, {})
+            print(f"  {','.join(k[1:]):20s}  " + " ".join(f"{m_.get(c, '?'):>5s}" for c in cols) + "   " +
+                  " ".join(f"{d_.get(c, '?'):>5s}" for c in cols))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
