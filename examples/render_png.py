@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--aa", action="store_true", help="the reference's 9-tap anti-aliasing")
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--materials", action="store_true", help="mirror floor, matte spheres (per-object materials)")
+    ap.add_argument("--glass", action="store_true",
+                    help="two glass spheres (ior 1.5 and 2.4) over the --materials mirror floor (refraction)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -36,9 +38,12 @@ def main():
     with pkg.Renderer(0) as r:
         scene = Scene.default_scene()
         mats = None
-        if a.materials:
+        if a.materials or a.glass:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
+            if a.glass:                                             # clear glass; ior 2.4 (diamond) shows total internal reflection
+                scene.spheres[0].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=1.5)
+                scene.spheres[5].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=2.4)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))   # matte spheres: no reflection
         r.set_scene(*scene.generate_scene(), materials=mats)
         r.set_camera(cam.position, cam.rotation)
@@ -57,7 +62,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} materials={a.materials}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} materials={a.materials} glass={a.glass}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

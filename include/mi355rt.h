@@ -181,6 +181,33 @@ int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float
                            const double *materials, int M,
                            const int32_t *sphere_material, const int32_t *plane_material);
 
+/* The same with transparent materials (refraction; the reference's README to-do list).  ncols is 3 or 5:
+ *   ncols == 3   exactly rt_set_scene_materials.
+ *   ncols == 5   materials float64 (M,5) C-order, rows (amb, lamb, refl, trans, ior): trans finite and >= 0, ior finite and
+ *                > 0, and a row with trans > 0 must have refl == 0 (one continuation cannot carry both).  A table without a
+ *                row trans > 0 is the 3-column table of its first three columns (same kernels, same bytes); only a scene
+ *                with a transparent row runs the refraction kernels.
+ * A transparent hit (trans > 0) is shaded exactly like an opaque one (ambient, Lambert, full shadows; a sphere hit from the
+ * inside with the outward normal N and P + BIAS*N), but the ray continues through the surface instead of being reflected.
+ * float64, no fused multiply-add, in this order, with P = o + t*d the unbiased hit point, N the outward normal (trace.py:63-71),
+ * BIAS = 0.0002 and linear_comb / normalize of common.py:
+ *   c = dot(d, N); c < 0 (entering): eta = 1.0/ior, ci = -c, n = N; otherwise (leaving): eta = ior, ci = c, n = -N.
+ *   sphere: k = 1.0 - (eta*eta)*(1.0 - ci*ci).
+ *     k >= 0: T = normalize(linear_comb(d, n, eta, eta*ci - sqrt(k))), next origin
+ *             linear_comb(linear_comb(P, n, 1.0, -BIAS), T, 1.0, BIAS)   (the far side of the surface);
+ *     k < 0 (total internal reflection): R = get_reflection(d, N), next origin
+ *             linear_comb(linear_comb(P, n, 1.0, BIAS), R, 1.0, BIAS)    (the incoming side).
+ *   plane (a thin sheet, ior ignored): direction d, next origin linear_comb(linear_comb(P, n, 1.0, -BIAS), d, 1.0, BIAS), with
+ *     BIAS*N rounded as trace.py:82-83 rounds it (RT_FLAG_TYPED_BIAS applies).
+ * Bounce k+1 is weighted with W_{k+1} = W_k * c_k, c_k = trans_k for a transparent hit (total internal reflection included)
+ * and refl_k otherwise; a miss ends the path.  Transparent objects cast full shadows.  Invalid input (a bad id, a NULL array,
+ * ncols not 3 or 5, a coefficient outside the rules above): RT_ERR_BAD_ARG, and the previous scene stays current.
+ * RT_FLAG_COUNT_RAYS is refused for such a scene.  RT_ABI_VERSION is unchanged: callers detect this entry point by its symbol. */
+int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                              const float *planes, int P, int flags,
+                              const double *materials, int M, int ncols,
+                              const int32_t *sphere_material, const int32_t *plane_material);
+
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);
 

@@ -73,7 +73,9 @@ struct rt_ctx {
     int S = 0, P = 0, L = 0;
     int NC = 0;                   // sphere clusters (0 = flat scene)
     int M = 0;                    // materials of the current scene (rt_set_scene_materials; 0 = the launch's shading scalars)
+    int mat_cols = 3;             // doubles per row of its table: 5 with a transparent row (the refraction kernels), else 3
     size_t mat_lds_limit_set = 0; // hipFuncAttributeMaxDynamicSharedMemorySize of the material kernels (lds_limit_set: the others)
+    size_t refr_lds_limit_set = 0;   // (the same, refraction kernels)
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
@@ -247,6 +249,29 @@ const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int w
               : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true>);
 }
 
+// The refraction kernels (rt_device.h: REFR): the material twins for a scene whose table has a transparent row
+// (rt_set_scene_materials_ex), same arguments.
+const void *refraction_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
+{
+    if (lanes) {
+        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true>;
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true>);
+    }
+    if (lattice) {
+        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true>;
+        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true>;
+    }
+    if (norec && wpw == 4 && !aa)
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true>;
+    if (wpw == 2)
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true>);
+    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true>)
+              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true>);
+}
+
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
 int acquire_tables(rt_ctx *ctx, const rt::KParams &k, hipStream_t stream, const float **out)
 {
@@ -413,20 +438,30 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
     // a scene with materials runs the material twins of the same variants; their LDS images hold the material data too
     // (matd doubles), and the parked ones one more per-thread slot
-    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P);   // (the block is in the launch's scene buffer: rt::mat_offset)
+    // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots)
+    const bool refr = ctx->M > 0 && ctx->mat_cols == 5;
+    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, ctx->mat_cols);   // (the block is in the launch's scene buffer: rt::mat_offset)
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd);
+        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr);
         if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
-        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd));
+        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd);
+    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd);
-    const void *fn = matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr);
+    const void *fn = refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
+                   : matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
                           : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (matd) {
+    if (refr) {
+        if (lds > 48 * 1024 && lds > ctx->refr_lds_limit_set) {
+            for (int v = 0; v < 64; ++v)
+                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ctx->refr_lds_limit_set = lds;
+        }
+    } else if (matd) {
         if (lds > 48 * 1024 && lds > ctx->mat_lds_limit_set) {
             for (int v = 0; v < 64; ++v)
                 RT_HIP(ctx, hipFuncSetAttribute(material_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
@@ -685,7 +720,45 @@ int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, 
 int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                            const double *materials, int M, const int32_t *sphere_material, const int32_t *plane_material)
 {
+    return rt_set_scene_materials_ex(ctx, spheres, S, lights, L, planes, P, flags, materials, M, 3, sphere_material, plane_material);
+}
+
+int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
+                              const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material)
+{
     if (!ctx) return RT_ERR_BAD_ARG;
+    if (ncols != 3 && ncols != 5) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3 or 5");
+    // a 5-column table: validated here; without a transparent row it is the 3-column table of its first three columns
+    // (the material kernels), with one the rows travel whole (the refraction kernels)
+    std::vector<double> packed;
+    int cols = 3;
+    if (ncols == 5 && M > 0 && M <= RT_MAX_MATERIALS && materials) {
+        bool glass = false;
+        for (int m = 0; m < M; ++m) {
+            const double *r = materials + (size_t)5 * m;
+            for (int i = 0; i < 5; ++i)
+                if (!std::isfinite(r[i]))
+                    return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + " has a coefficient that is not finite");
+            if (!(r[3] >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": trans must be >= 0");
+            if (!(r[4] > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": ior must be > 0");
+            if (r[3] > 0.0 && r[2] != 0.0)
+                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have refl == 0");
+            glass = glass || r[3] > 0.0;
+        }
+        try {
+            if (glass) {
+                packed.assign(materials, materials + (size_t)5 * M);
+                cols = 5;
+            } else {
+                packed.resize((size_t)3 * M);
+                for (int m = 0; m < M; ++m)
+                    for (int i = 0; i < 3; ++i) packed[(size_t)3 * m + i] = materials[(size_t)5 * m + i];
+            }
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, RT_ERR_ALLOC, "out of host memory");
+        }
+        materials = packed.data();
+    }
     if (S < 0 || S > RT_MAX_SPHERES || L < 0 || L > RT_MAX_LIGHTS || P < 0 || P > RT_MAX_PLANES)
         return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
     if ((S && !spheres) || (L && !lights) || (P && !planes)) return fail(ctx, RT_ERR_BAD_ARG, "NULL scene array with non-zero count");
@@ -693,9 +766,9 @@ int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float
     if (M > 0) {
         if (!materials) return fail(ctx, RT_ERR_BAD_ARG, "materials is NULL with M > 0");
         if ((S && !sphere_material) || (P && !plane_material)) return fail(ctx, RT_ERR_BAD_ARG, "NULL material id array with non-zero count");
-        for (int i = 0; i < 3 * M; ++i)
+        for (int i = 0; i < cols * M; ++i)
             if (!std::isfinite(materials[i]))
-                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(i / 3) + " has a coefficient that is not finite");
+                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(i / cols) + " has a coefficient that is not finite");
         for (int k = 0; k < S; ++k)
             if (sphere_material[k] < 0 || sphere_material[k] >= M)
                 return fail(ctx, RT_ERR_BAD_ARG, "sphere_material[" + std::to_string(k) + "] outside 0..M-1");
@@ -748,7 +821,7 @@ int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float
         }
         nclusters = NC;
         const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
-        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P), 0.0);
+        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -810,11 +883,11 @@ int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float
             bound(g * rt::SUPER * rt::CLUSTER, std::min(S, (g + 1) * rt::SUPER * rt::CLUSTER), sp);
         if (M > 0) {   // the material block (rt::mat_offset): M, the table, the ids of the sphere SLOTS (the order above) and of the planes
             rec[mat_off] = (double)M;
-            std::memcpy(rec.data() + mat_off + 1, materials, (size_t)3 * M * sizeof(double));
+            std::memcpy(rec.data() + mat_off + 1, materials, (size_t)cols * M * sizeof(double));
             std::vector<int32_t> ids((size_t)S + P);
             for (int slot = 0; slot < S; ++slot) ids[slot] = sphere_material[order[slot]];
             for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
-            if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)3 * M, ids.data(), ids.size() * sizeof(int32_t));
+            if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
         }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
@@ -845,6 +918,7 @@ int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float
     ctx->scene_extent2 = ext2;
     ctx->S = S; ctx->P = P; ctx->L = L; ctx->NC = nclusters;
     ctx->M = M;
+    ctx->mat_cols = cols;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

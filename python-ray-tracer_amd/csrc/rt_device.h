@@ -323,11 +323,17 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // loop (with them in registers seven of the 22 material kernels spilled more than their default twins).  The slots are addressed
 // off the same base as the parked colour (an immediate offset) or, FRESH (register variants, REMAT), re-derived from the lane's
 // number.  The table and the ids are wave-uniform LDS byte addresses, kept scalar until a hit reads them (see opaque()).
-template <bool MAT, int WSLOT, bool FRESH> struct MatState {};
-template <int WSLOT, bool FRESH> struct MatState<true, WSLOT, FRESH> {
-    unsigned tab;              // LDS: M x {amb, lamb, refl}
+// REFR (refraction kernels, rt_set_scene_materials_ex with a transparent row): rows of 5, {amb, lamb, refl, trans, ior}, and four
+// more slots: REFL then holds the hit's continuation weight c (trans for a transparent hit, refl otherwise), Q the unbiased hit
+// point moved BIAS against the outward normal (P - BIAS*N, the far side of the surface) and ETA what the continuation after the
+// light loop is: 0 a reflection, ior > 0 a refraction through a sphere, -1 a pass through a plane.
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false> struct MatState { static constexpr bool refr = false; };
+template <int WSLOT, bool FRESH, bool REFR> struct MatState<true, WSLOT, FRESH, REFR> {
+    static constexpr bool refr = REFR;
+    static constexpr int COLS = REFR ? 5 : 3;   // doubles per table row
+    unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior})
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
-    enum { W = 0, LAMB = 1, REFL = 2 };
+    enum { W = 0, LAMB = 1, REFL = 2, QX = 3, QY = 4, QZ = 5, ETA = 6 };
     template <int WGT, int k> __device__ __forceinline__ volatile lds_f64 *at(const double *acc, int wave) const
     {
         if constexpr (FRESH) return (volatile lds_f64 *)acc + (WSLOT + k) * WGT + wave * 64 + fresh_lane();
@@ -339,7 +345,7 @@ template <int WSLOT, bool FRESH> struct MatState<true, WSLOT, FRESH> {
         asm volatile("" : "+s"(t), "+s"(i));
         typedef __attribute__((address_space(3))) const int lds_ci32;
         const int m = ((lds_ci32 *)(size_t)i)[slot];
-        return (volatile const lds_f64 *)(size_t)t + 3 * m;
+        return (volatile const lds_f64 *)(size_t)t + COLS * m;
     }
 };
 
@@ -1185,6 +1191,49 @@ template <> struct RayCount<true> {
     __device__ __forceinline__ void shadow(bool alive, bool traced) { n_issued += (alive && traced) ? 1u : 0u; n_skipped += (alive && !traced) ? 1u : 0u; }
 };
 
+// The continuation of a REFR kernel's hit (MatState: ETA, Q), in place of trace.py:105-110.  d: the incoming direction,
+// N: the outward normal at the hit, Pt = P + BIAS*N (:82-83).  float64 throughout, in the order rt_set_scene_materials_ex
+// documents (mi355rt.h): c = d.N; entering (c < 0): eta = 1/ior, ci = -c, n = N; leaving: eta = ior, ci = c, n = -N.
+//   sphere, k = 1 - eta^2 (1 - ci^2) >= 0:  T = normalize(eta d + (eta ci - sqrt(k)) n), from P - BIAS*n
+//   sphere, k < 0 (total internal reflection):  the reflection, from P + BIAS*n
+//   plane (thin sheet, ior ignored):  d, from P - BIAS*n
+// and the next origin is that point + BIAS * the new direction.  P - BIAS*n is Q entering and Pt leaving, P + BIAS*n the
+// other way round (-BIAS*n = -+bN exactly: negation is exact).
+template <int WGT, class MS>
+__device__ __forceinline__ void refract_continue(const Lds &lds, const MS &ms, const V3 &N, const V3 &Pt, V3 &o, V3 &d)
+{
+    const double eta_slot = *ms.template at<WGT, MS::ETA>(lds.acc, lds.wave);
+    V3 nd;
+    bool from_q = false, reflect = true;
+    if (eta_slot != 0.0) {
+        const double c = dot3(d, N);
+        const bool enter = c < 0.0;
+        from_q = enter;
+        if (eta_slot < 0.0) { nd = d; reflect = false; }                     // a transparent plane
+        else {
+            const double eta = enter ? 1.0 / eta_slot : eta_slot;
+            const double ci = enter ? -c : c;
+            const double k = 1.0 - (eta * eta) * (1.0 - ci * ci);
+            if (k >= 0.0) {
+                const double cn = eta * ci - __builtin_sqrt(k);
+                const V3 n = enter ? N : V3{-N.x, -N.y, -N.z};
+                // |T| = 1 up to rounding for unit d, N (renormalize_unit falls back to sqrt-and-divide otherwise)
+                nd = renormalize_unit(V3{eta * d.x + cn * n.x, eta * d.y + cn * n.y, eta * d.z + cn * n.z});
+                reflect = false;
+            } else from_q = !enter;                                           // total internal reflection: stays on the incoming side
+        }
+    }
+    if (reflect) {                                                            // common.py:113-120
+        const double c2 = -2.0 * dot3(d, N);
+        nd = renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
+    }
+    V3 b = Pt;
+    if (from_q) b = V3{*ms.template at<WGT, MS::QX>(lds.acc, lds.wave), *ms.template at<WGT, MS::QY>(lds.acc, lds.wave),
+                       *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave)};
+    o = V3{b.x + 0.0002 * nd.x, b.y + 0.0002 * nd.y, b.z + 0.0002 * nd.z};
+    d = nd;
+}
+
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
 // MAT: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
@@ -1239,6 +1288,19 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             // Lambert coefficient and reflectivity go to the lane's slots
             mp = ms.entry((type == HIT_SPHERE) ? idx : S + idx);
             *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) = mp[1];
+            if constexpr (MS::refr) {
+                // a transparent hit: its weight is trans, and Q = P - BIAS*N (the unbiased P is gone after :82-83) is kept for
+                // the continuation; a plane's BIAS*N is its stored bN, rounded as the reference rounds it
+                const double tr = mp[3];
+                const bool glass = tr > 0.0;
+                *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = glass ? tr : mp[2];
+                *ms.template at<WGT, MS::ETA>(lds.acc, lds.wave) = glass ? ((type == HIT_SPHERE) ? mp[4] : -1.0) : 0.0;
+                if (glass) {
+                    *ms.template at<WGT, MS::QX>(lds.acc, lds.wave) = Pt.x - bN.x;
+                    *ms.template at<WGT, MS::QY>(lds.acc, lds.wave) = Pt.y - bN.y;
+                    *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave) = Pt.z - bN.z;
+                }
+            } else
             *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = mp[2];
             const double amb = mp[0];
             rgb = V3{0.0 + amb * col(0), 0.0 + amb * col(1), 0.0 + amb * col(2)};   // :77 as the reference rounds it (+0 for a negative amb)
@@ -1268,12 +1330,16 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             }
         }
         d = dpark.get();
+        if constexpr (MS::refr) {
+            refract_continue<WGT>(lds, ms, N, Pt, o, d);
+        } else {
         const double c2 = -2.0 * dot3(d, N);                                  // common.py:113-120
         // |d - 2(d.N)N| = 1 up to rounding for unit d, N: the exact unit-vector path applies (it falls
         // back to sqrt-and-divide by itself otherwise)
         const V3 Rd = renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
         o = V3{Pt.x + 0.0002 * Rd.x, Pt.y + 0.0002 * Rd.y, Pt.z + 0.0002 * Rd.z};   // :110
         d = Rd;
+        }
         RT_MARK(10);
     }
 }
@@ -1398,12 +1464,12 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
 
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
-__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl)
+__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta)
 // The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
-// M, then the M x 3 table {amb, lamb, refl}, then S + P int32 material ids of the slots (padded to a double).  Material kernels
-// stage it at the end of their LDS image.
+// M, then the M x cols table {amb, lamb, refl} (cols = 5, refraction kernels: {amb, lamb, refl, trans, ior}), then S + P int32
+// material ids of the slots (padded to a double).  Material kernels stage it at the end of their LDS image.
 __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
-__host__ __device__ inline size_t mat_doubles(int M, int S, int P) { return M > 0 ? 1 + 3 * (size_t)M + ((size_t)S + P + 1) / 2 : 0; }
+__host__ __device__ inline size_t mat_doubles(int M, int S, int P, int cols = 3) { return M > 0 ? 1 + (size_t)cols * M + ((size_t)S + P + 1) / 2 : 0; }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
@@ -1435,11 +1501,11 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
     return col ? t.total_col : (lanes ? t.total_lanes : t.total);
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
-// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise.
+// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise; refr: the refraction kernels.
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
-                                            size_t matd = 0)
+                                            size_t matd = 0, bool refr = false)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0) * wgt + matd) * sizeof(double) +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr) * wgt + matd) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
            + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
@@ -1559,18 +1625,19 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
 }
 
 // The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
-template <bool MAT, int WSLOT, bool FRESH>
-__device__ __forceinline__ MatState<MAT, WSLOT, FRESH> mat_state(double *matl, int M)
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false>
+__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR> mat_state(double *matl, int M)
 {
     typedef __attribute__((address_space(3))) double lds_d;
-    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + 3 * M)};
+    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + (REFR ? 5 : 3) * M)};
     else return {};
 }
 
 // AA = false: aliasing off — instantiated separately so that the common case does not carry the tap loop's
 // live state (registers decide occupancy here).
 // MAT: the scene has a material table (per-object shading coefficients, rt_set_scene_materials).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false>
+// REFR (with MAT only): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false>
 #ifndef RT_W_PARK
 #define RT_W_PARK 7
 #endif
@@ -1588,7 +1655,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
     double *accum = lds_raw + nrec;
-    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT) * WG_THREADS);
+    static_assert(MAT || !REFR, "refraction kernels are material kernels");
+    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
@@ -1621,7 +1689,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     if constexpr (MAT) {
         const double *msrc = p.scene + mat_offset(p.S, p.P, p.L, p.NC);
         nmat = (int)msrc[0];
-        const int nm = (int)mat_doubles(nmat, p.S, p.P);
+        const int nm = (int)mat_doubles(nmat, p.S, p.P, REFR ? 5 : 3);
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
     }
     __syncthreads();
@@ -1686,7 +1754,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
     constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
-    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3>(matl, nmat);
+    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR>(matl, nmat);
     double R, G, B;
     if constexpr (!AA) {
         const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms);   // kernels.py:19-26

@@ -99,7 +99,8 @@ class Renderer:
         """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
-        the launches' amb, lamb and refl are then ignored (rt_set_scene_materials)."""
+        the launches' amb, lamb and refl are then ignored (rt_set_scene_materials).  A table of shape (M,5), rows
+        amb, lamb, refl, trans, ior, has transparent materials (rt_set_scene_materials_ex)."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
         if materials is None:
@@ -107,15 +108,23 @@ class Renderer:
                                                p.ctypes.data_as(fp), p.shape[1], int(flags)))
         else:
             table, sid, pid = materials
-            t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 3)
+            t = np.ascontiguousarray(table, dtype=np.float64)
+            ncols = 5 if (t.ndim == 2 and t.shape[1] == 5) else 3
+            t = t.reshape(-1, ncols)
             si = np.ascontiguousarray(sid, dtype=np.int32).reshape(-1)
             pi = np.ascontiguousarray(pid, dtype=np.int32).reshape(-1)
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            self._check(self._lib.rt_set_scene_materials(
-                self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp), p.shape[1],
-                int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
+            if ncols == 5:
+                self._check(self._lib.rt_set_scene_materials_ex(
+                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
+                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], 5, si.ctypes.data_as(ip),
+                    pi.ctypes.data_as(ip)))
+            else:
+                self._check(self._lib.rt_set_scene_materials(
+                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp), p.shape[1],
+                    int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
         self.counts = (s.shape[1], l.shape[1], p.shape[1])
         self.generation["scene"] += 1
 

@@ -14,13 +14,34 @@ from .colors import RED, BLUE, MAGENTA, YELLOW, GREEN, GREY
 @dataclass(frozen=True)
 class Material:
     """Shading coefficients of one object: the reference's ambient_int, lambert_int and reflection_int (trace.py:44, :115),
-    per object instead of per frame.  float64; any finite value."""
+    per object instead of per frame.  float64; any finite value.
+    transparency > 0 makes the object transparent: the ray continues through it (refracted by a sphere with index of
+    refraction `ior`, straight through a plane) with weight `transparency` instead of being reflected; such a material must
+    have refl == 0.  transparency finite and >= 0, ior finite and > 0 (include/mi355rt.h: rt_set_scene_materials_ex)."""
     amb: float
     lamb: float
     refl: float
+    transparency: float = 0.0
+    ior: float = 1.0
+
+    def __post_init__(self):
+        # (amb, lamb and refl are checked where the table is set, as before: rt_set_scene_materials refuses non-finite ones)
+        if not (np.isfinite(float(self.transparency)) and float(self.transparency) >= 0.0):
+            raise ValueError(f"transparency must be finite and >= 0, got {self.transparency}")
+        if not (np.isfinite(float(self.ior)) and float(self.ior) > 0.0):
+            raise ValueError(f"ior must be finite and > 0, got {self.ior}")
+        if float(self.transparency) > 0.0 and float(self.refl) != 0.0:
+            raise ValueError("a transparent material (transparency > 0) must have refl == 0")
+
+    @property
+    def transparent(self):
+        return float(self.transparency) > 0.0
 
     def key(self):
         return (float(self.amb), float(self.lamb), float(self.refl))
+
+    def key5(self):
+        return (float(self.amb), float(self.lamb), float(self.refl), float(self.transparency), float(self.ior))
 
 
 @dataclass
@@ -85,13 +106,17 @@ class Scene:
     def generate_materials(self, default: Material):
         """(table float64 (M,3) rows amb, lamb, refl; sphere_ids int32 (S,); plane_ids int32 (P,)) for
         Renderer.set_scene(..., materials=...).  Objects without a material get `default`; equal materials share one row,
-        in the order of first use (spheres, then planes)."""
+        in the order of first use (spheres, then planes).  If any material is transparent the table is (M,5), rows
+        amb, lamb, refl, transparency, ior."""
         rows, index = [], {}
+        mats = [o.material if o.material is not None else default for o in list(self.spheres) + list(self.planes)]
+        wide = any(m.transparent for m in mats)
 
         def ids(objs):
             out = np.zeros(len(objs), dtype=np.int32)
             for i, o in enumerate(objs):
-                k = (o.material if o.material is not None else default).key()
+                m = o.material if o.material is not None else default
+                k = m.key5() if wide else m.key()
                 if k not in index:
                     index[k] = len(rows)
                     rows.append(k)
@@ -99,7 +124,7 @@ class Scene:
             return out
 
         sphere_ids, plane_ids = ids(self.spheres), ids(self.planes)
-        return np.array(rows, dtype=np.float64).reshape(-1, 3), sphere_ids, plane_ids
+        return np.array(rows, dtype=np.float64).reshape(-1, 5 if wide else 3), sphere_ids, plane_ids
 
     @staticmethod
     def default_scene():

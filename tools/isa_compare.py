@@ -8,9 +8,11 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
   * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
     kernel's own symbol renumbered, must be identical in the working tree;
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
-A render_kernel instantiation is matched by its template arguments; a trailing `false` (the MAT parameter, rt_device.h) of the
-working tree's names is ignored, so the default kernels of a tree with material kernels match those of a tree without.
---twins also prints each material kernel (MAT = true) next to its default twin.  Exit status 1 if any kernel differs.
+A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT and REFR
+parameters, rt_device.h) are ignored, so the default kernels of a tree with material or refraction kernels match those of a
+tree without, and the material kernels (MAT = true, REFR = false) match those of a tree without refraction kernels.
+--twins also prints each material kernel (MAT = true) next to its default twin, and each refraction kernel (REFR = true) next
+to its material twin.  Exit status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -31,15 +33,14 @@ def build(tree):
 
 
 def key(name):
-    """Kernel symbol -> (kernel, template arguments without a trailing MAT = false), and whether it is a MAT = true kernel."""
+    """Kernel symbol -> (kernel, template arguments without trailing false ones past the sixth), and its family:
+    "" (default), "mat" (MAT = true) or "refr" (REFR = true)."""
     m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
     if not m:
-        return name, False
+        return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
-    mat = len(args) == 7 and args[-1] == "1"
-    if len(args) == 7:
-        args = args[:-1]
-    return (m.group(1),) + tuple(args), mat
+    fam = "refr" if len(args) >= 8 and args[7] == "1" else ("mat" if len(args) >= 7 and args[6] == "1" else "")
+    return (m.group(1),) + tuple(args[:6]), fam
 
 
 def functions(asm):
@@ -86,30 +87,30 @@ def main():
     br, nr = resources(base_log), resources(new_log)
     new_by_key = {}
     for n in nf:
-        k, mat = key(n)
-        new_by_key[(k, mat)] = n
+        new_by_key[key(n)] = n
     bad = 0
     for b in sorted(bf):
-        k, _ = key(b)
-        n = new_by_key.get((k, False))
+        n = new_by_key.get(key(b))
         if n is None:
             print(f"MISSING  {b}"); bad += 1; continue
         same_isa = bf[b] == nf[n]
         same_res = br.get(b) == nr.get(n)
         print(f"{'same' if same_isa and same_res else 'DIFF'}  isa={'=' if same_isa else '!'} res={'=' if same_res else '!'} "
-              f"{len(bf[b].splitlines()):6d} lines  {k}")
+              f"{len(bf[b].splitlines()):6d} lines  {key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}")
         bad += not (same_isa and same_res)
     print(f"{len(bf)} kernels of {a.base} compared, {bad} differ")
     if a.twins:
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
-        print("\nmaterial kernel (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   default twin")
-        for (k, mat), n in sorted(new_by_key.items(), key=str):
-            if not mat:
-                continue
-            t = new_by_key.get((k, False))
-            m_, d_ = nr.get(n, {}), nr.get(t, {})
-            print(f"  {','.join(k[1:]):20s}  " + " ".join(f"{m_.get(c, '?'):>5s}" for c in cols) + "   " +
-                  " ".join(f"{d_.get(c, '?'):>5s}" for c in cols))
+        for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel")):
+            print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   "
+                  f"{'default' if twin == '' else 'material'} twin")
+            for (k, f_), n in sorted(new_by_key.items(), key=str):
+                if f_ != fam:
+                    continue
+                t = new_by_key.get((k, twin))
+                m_, d_ = nr.get(n, {}), nr.get(t, {})
+                print(f"  {','.join(k[1:]):20s}  " + " ".join(f"{m_.get(c, '?'):>5s}" for c in cols) + "   " +
+                      " ".join(f"{d_.get(c, '?'):>5s}" for c in cols))
     sys.exit(1 if bad else 0)
 
 
