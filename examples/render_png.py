@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Render a frame with the `Renderer` API and save it as a PNG.
 
-    python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa] [--frames 50] [--materials] [--out output/render.png]
+    python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
+                                  [--out output/render.png]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
+--scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
+(stochastic anti-aliasing, N samples per pixel) the scattered reflections average out.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -31,6 +34,9 @@ def main():
     ap.add_argument("--materials", action="store_true", help="mirror floor, matte spheres (per-object materials)")
     ap.add_argument("--glass", action="store_true",
                     help="two glass spheres (ior 1.5 and 2.4) over the --materials mirror floor (refraction)")
+    ap.add_argument("--scatter", action="store_true",
+                    help="brushed-metal spheres (roughness 0.1 and 0.3) and a satin floor (roughness 0.2): rough reflections")
+    ap.add_argument("--spp", type=int, default=0, help="stochastic anti-aliasing with this many samples per pixel")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -38,7 +44,14 @@ def main():
     with pkg.Renderer(0) as r:
         scene = Scene.default_scene()
         mats = None
-        if a.materials or a.glass:
+        if a.scatter:
+            for p in scene.planes:
+                p.material = Material(0.0, 0.3, 0.7, roughness=0.2)                  # a satin floor
+            scene.spheres[0].material = Material(0.05, 0.3, 0.8, roughness=0.1)     # brushed metal
+            scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
+            scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
+            mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
+        elif a.materials or a.glass:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
             if a.glass:                                             # clear glass; ior 2.4 (diamond) shows total internal reflection
@@ -50,9 +63,10 @@ def main():
         r.set_raygen(w, h, *cam.raygen())
         image = r.host_array((h, w, 3), np.uint8)
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
-        r.render_into(0.0, 0.6, 0.3, a.depth, a.aa, image, flags=flags)
+        aa = 2 if a.spp > 0 else a.aa
+        r.render_into(0.0, 0.6, 0.3, a.depth, aa, image, flags=flags, spp=a.spp)
         dev = r.malloc(3 * w * h)
-        p = r.params(0.0, 0.6, 0.3, a.depth, a.aa, flags=flags)
+        p = r.params(0.0, 0.6, 0.3, a.depth, aa, flags=flags, spp=a.spp)
         for _ in range(3):
             r.render_device(p, 0, w, dev, None, w)
         r.timer_begin()
@@ -62,7 +76,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} materials={a.materials} glass={a.glass}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

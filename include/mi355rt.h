@@ -104,7 +104,7 @@ typedef struct rt_params {
     int32_t aa_mode; /* RT_AA_* */
     int32_t flags;   /* RT_FLAG_* */
     int32_t spp;     /* RT_AA_STOCHASTIC: samples per pixel, 1..RT_MAX_SPP (ignored otherwise) */
-    uint32_t seed;   /* RT_AA_STOCHASTIC: hash seed */
+    uint32_t seed;   /* RT_AA_STOCHASTIC: hash seed (and, in every mode, of rt_set_scene_materials_scatter's rough rows) */
     int32_t reserved;
 } rt_params;
 
@@ -207,6 +207,34 @@ int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const fl
                               const float *planes, int P, int flags,
                               const double *materials, int M, int ncols,
                               const int32_t *sphere_material, const int32_t *plane_material);
+
+/* The same with rough materials (scatter; the reference's README to-do list).  ncols is 3, 5 or 6:
+ *   ncols == 3 or 5   exactly rt_set_scene_materials_ex.
+ *   ncols == 6        materials float64 (M,6) C-order, rows (amb, lamb, refl, trans, ior, rough): the rules of ncols == 5, and
+ *                     rough finite and in [0, 1]; a row with trans > 0 must have rough == 0 (frosted glass is not supported).
+ *                     A table without a row rough > 0 is the 5-column table of its first five columns (same kernels, same
+ *                     bytes); only a scene with a rough row runs the scatter kernels.
+ * A hit on a rough object (rough > 0) is shaded exactly like any other (ambient, Lambert, shadows; the weights W_k do not
+ * change), but for trace b < depth (b = 0: the primary ray) its next ray leaves along the mirror direction R perturbed by
+ * rough times a point in the unit ball.  float64, no fused multiply-add, in this order, with R = get_reflection(d, N)
+ * (common.py:113-120), N the outward normal, Pt the biased hit point of trace.py:82-83, linear_comb / normalize / dot of
+ * common.py and jitter_hash the 32-bit counter hash of rt_params.seed (rt_device.h):
+ *   key of a sample (X, Y, s): X, Y on the half-pixel lattice, pixel (x, y) at (2x, 2y) with x the absolute column, the
+ *     RT_AA_REFERENCE tap towards neighbour (dx, dy) at (2x+dx, 2y+dy); s the RT_AA_STOCHASTIC sample index, else 0.  (The
+ *     lattice path, RT_FLAG_AA_PER_PIXEL, an explicit grid and column slabs give the same bytes.)
+ *   candidate j = 0..7, component c = 0..2:  h = jitter_hash(X, Y, ((s*16 + b)*8 + j)*4 + c, seed ^ 0x5CA77E12),
+ *     q_c = (double)(h >> 8) * 2^-23 + (2^-24 - 1)   (exact); q is the first candidate with dot(q, q) < 1 (exact).
+ *   D = normalize(linear_comb(R, q, 1.0, rough)), or D = R if none of the eight candidates is inside the ball.
+ *   sR = dot(R, N), sD = dot(D, N): unless both are > 0 or both < 0 (NaN included) the path ends after this trace, like a
+ *     miss (absorption).
+ *   next origin linear_comb(Pt, D, 1.0, BIAS), weight W_{k+1} = W_k * refl_k as for a mirror.
+ * rt_params.seed is read in every aa_mode for such a scene.  Invalid input (as rt_set_scene_materials_ex, ncols not 3, 5 or
+ * 6, rough outside [0, 1] or NaN, a rough transparent row): RT_ERR_BAD_ARG, and the previous scene stays current.
+ * RT_FLAG_COUNT_RAYS is refused for such a scene.  RT_ABI_VERSION is unchanged: callers detect this entry point by its symbol. */
+int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                                   const float *planes, int P, int flags,
+                                   const double *materials, int M, int ncols,
+                                   const int32_t *sphere_material, const int32_t *plane_material);
 
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);

@@ -47,6 +47,8 @@ PROTOTYPES = {
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_set_scene_materials_ex": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rt_set_scene_materials_scatter": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int,
+                                                 C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "rt_set_pixel_loc": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),

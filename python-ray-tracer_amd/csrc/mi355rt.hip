@@ -73,9 +73,11 @@ struct rt_ctx {
     int S = 0, P = 0, L = 0;
     int NC = 0;                   // sphere clusters (0 = flat scene)
     int M = 0;                    // materials of the current scene (rt_set_scene_materials; 0 = the launch's shading scalars)
-    int mat_cols = 3;             // doubles per row of its table: 5 with a transparent row (the refraction kernels), else 3
+    int mat_cols = 3;             // doubles per row of its table: 6 with a rough row (the scatter kernels), else 5 with a
+                                  // transparent row (the refraction kernels), else 3
     size_t mat_lds_limit_set = 0; // hipFuncAttributeMaxDynamicSharedMemorySize of the material kernels (lds_limit_set: the others)
     size_t refr_lds_limit_set = 0;   // (the same, refraction kernels)
+    size_t scat_lds_limit_set = 0;   // (the same, scatter kernels)
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
@@ -250,26 +252,28 @@ const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int w
 }
 
 // The refraction kernels (rt_device.h: REFR): the material twins for a scene whose table has a transparent row
-// (rt_set_scene_materials_ex), same arguments.
+// (rt_set_scene_materials_ex), same arguments.  SC: their scatter twins (rt_device.h: SCAT), for a table with a rough row
+// (rt_set_scene_materials_scatter).
+template <bool SC = false>
 const void *refraction_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
 {
     if (lanes) {
-        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true>;
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true>);
+        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC>;
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC>);
     }
     if (lattice) {
-        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true>;
-        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true>;
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true>;
+        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC>;
+        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC>;
     }
     if (norec && wpw == 4 && !aa)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC>;
     if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true>);
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC>);
+    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC>)
+              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC>);
 }
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
@@ -438,23 +442,33 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
     // a scene with materials runs the material twins of the same variants; their LDS images hold the material data too
     // (matd doubles), and the parked ones one more per-thread slot
-    // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots)
-    const bool refr = ctx->M > 0 && ctx->mat_cols == 5;
+    // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots; with a rough row
+    // their scatter twins, with rows of 6 and two more slots)
+    const bool scat = ctx->M > 0 && ctx->mat_cols == 6;
+    const bool refr = ctx->M > 0 && ctx->mat_cols >= 5;
     const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, ctx->mat_cols);   // (the block is in the launch's scene buffer: rt::mat_offset)
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr);
+        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr, scat);
         if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
-        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr));
+        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr, scat));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr);
+    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr, scat);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr);
-    const void *fn = refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr, scat);
+    const void *fn = scat ? refraction_variant<true>(lanes, aa, lattice, park, wpw, norec)
+                   : refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
                    : matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
                           : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (refr) {
+    if (scat) {
+        if (lds > 48 * 1024 && lds > ctx->scat_lds_limit_set) {
+            for (int v = 0; v < 64; ++v)
+                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ctx->scat_lds_limit_set = lds;
+        }
+    } else if (refr) {
         if (lds > 48 * 1024 && lds > ctx->refr_lds_limit_set) {
             for (int v = 0; v < 64; ++v)
                 RT_HIP(ctx, hipFuncSetAttribute(refraction_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
@@ -728,32 +742,43 @@ int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const fl
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (ncols != 3 && ncols != 5) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3 or 5");
-    // a 5-column table: validated here; without a transparent row it is the 3-column table of its first three columns
-    // (the material kernels), with one the rows travel whole (the refraction kernels)
+    return rt_set_scene_materials_scatter(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+}
+
+int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
+                                   int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
+                                   const int32_t *plane_material)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (ncols != 3 && ncols != 5 && ncols != 6) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3, 5 or 6");
+    // a 5- or 6-column table: validated here; it travels with the columns its rows use: all six with a rough row (the scatter
+    // kernels), else the first five with a transparent row (the refraction kernels), else the first three (the material kernels)
     std::vector<double> packed;
     int cols = 3;
-    if (ncols == 5 && M > 0 && M <= RT_MAX_MATERIALS && materials) {
-        bool glass = false;
+    if (ncols >= 5 && M > 0 && M <= RT_MAX_MATERIALS && materials) {
+        bool glass = false, rough = false;
         for (int m = 0; m < M; ++m) {
-            const double *r = materials + (size_t)5 * m;
-            for (int i = 0; i < 5; ++i)
+            const double *r = materials + (size_t)ncols * m;
+            for (int i = 0; i < ncols; ++i)
                 if (!std::isfinite(r[i]))
                     return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + " has a coefficient that is not finite");
             if (!(r[3] >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": trans must be >= 0");
             if (!(r[4] > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": ior must be > 0");
             if (r[3] > 0.0 && r[2] != 0.0)
                 return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have refl == 0");
+            if (ncols == 6) {
+                if (!(r[5] >= 0.0 && r[5] <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": rough must be in [0, 1]");
+                if (r[3] > 0.0 && r[5] > 0.0)
+                    return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have rough == 0");
+                rough = rough || r[5] > 0.0;
+            }
             glass = glass || r[3] > 0.0;
         }
+        cols = rough ? 6 : (glass ? 5 : 3);
         try {
-            if (glass) {
-                packed.assign(materials, materials + (size_t)5 * M);
-                cols = 5;
-            } else {
-                packed.resize((size_t)3 * M);
-                for (int m = 0; m < M; ++m)
-                    for (int i = 0; i < 3; ++i) packed[(size_t)3 * m + i] = materials[(size_t)5 * m + i];
-            }
+            packed.resize((size_t)cols * M);
+            for (int m = 0; m < M; ++m)
+                for (int i = 0; i < cols; ++i) packed[(size_t)cols * m + i] = materials[(size_t)ncols * m + i];
         } catch (const std::bad_alloc &) {
             return fail(ctx, RT_ERR_ALLOC, "out of host memory");
         }

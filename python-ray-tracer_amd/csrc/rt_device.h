@@ -327,13 +327,18 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // more slots: REFL then holds the hit's continuation weight c (trans for a transparent hit, refl otherwise), Q the unbiased hit
 // point moved BIAS against the outward normal (P - BIAS*N, the far side of the surface) and ETA what the continuation after the
 // light loop is: 0 a reflection, ior > 0 a refraction through a sphere, -1 a pass through a plane.
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false> struct MatState { static constexpr bool refr = false; };
-template <int WSLOT, bool FRESH, bool REFR> struct MatState<true, WSLOT, FRESH, REFR> {
-    static constexpr bool refr = REFR;
-    static constexpr int COLS = REFR ? 5 : 3;   // doubles per table row
-    unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior})
+// SCAT (scatter kernels, rt_set_scene_materials_scatter with a rough row; REFR too): rows of 6, {amb, lamb, refl, trans, ior,
+// rough}, and two more slots: ROUGH, the hit's roughness, and KEY, the sample's pre-hashed key (scatter_key), written once per
+// sample and read by the scatter after the light loop (scatter_continue).
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false> struct MatState {
+    static constexpr bool refr = false, scat = false;
+};
+template <int WSLOT, bool FRESH, bool REFR, bool SCAT> struct MatState<true, WSLOT, FRESH, REFR, SCAT> {
+    static constexpr bool refr = REFR, scat = SCAT;
+    static constexpr int COLS = SCAT ? 6 : (REFR ? 5 : 3);   // doubles per table row
+    unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
-    enum { W = 0, LAMB = 1, REFL = 2, QX = 3, QY = 4, QZ = 5, ETA = 6 };
+    enum { W = 0, LAMB = 1, REFL = 2, QX = 3, QY = 4, QZ = 5, ETA = 6, ROUGH = 7, KEY = 8 };
     template <int WGT, int k> __device__ __forceinline__ volatile lds_f64 *at(const double *acc, int wave) const
     {
         if constexpr (FRESH) return (volatile lds_f64 *)acc + (WSLOT + k) * WGT + wave * 64 + fresh_lane();
@@ -1191,6 +1196,48 @@ template <> struct RayCount<true> {
     __device__ __forceinline__ void shadow(bool alive, bool traced) { n_issued += (alive && traced) ? 1u : 0u; n_skipped += (alive && !traced) ? 1u : 0u; }
 };
 
+// The scatter hash (rt_set_scene_materials_scatter, mi355rt.h): jitter_hash(X, Y, ((s*16 + b)*8 + j)*4 + c, seed ^ 0x5CA77E12)
+// in two parts.  scatter_key is its first two rounds, on (X, Y), with s folded in: for b <= 15 the third argument is the bit
+// pattern s << 9 | b << 5 | j << 2 | c, so XOR-ing s << 9 into the state before the third round is the same as XOR-ing it in
+// there.  scatter_hash finishes it for the low nine bits t = b << 5 | j << 2 | c.
+__device__ __forceinline__ unsigned scatter_key(unsigned x, unsigned y, unsigned s, unsigned seed)
+{
+    unsigned h = (seed ^ 0x5CA77E12u) ^ 0x9E3779B9u;
+    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
+    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
+    return h ^ (s << 9);
+}
+__device__ __forceinline__ unsigned scatter_hash(unsigned key, unsigned t)
+{
+    unsigned h = (key ^ t) * 0x27D4EB2Fu; h ^= h >> 15;
+    h *= 0x165667B1u; h ^= h >> 13;
+    return h;
+}
+
+// The scatter of a SCAT kernel's hit on a rough surface (rough > 0, trace b < depth), in place of the mirror direction R:
+// the first of eight hashed candidates q in the unit ball (q_c = (h >> 8) 2^-23 + 2^-24 - 1, and q.q, are exact), then
+// D = normalize(R + rough*q) (R itself if none of the eight is inside).  Returns false if D leaves on the other side of the
+// surface from R (or either is on it, or NaN): the path ends after this trace (absorption).
+template <int WGT, class MS>
+__device__ __forceinline__ bool scatter_continue(const Lds &lds, const MS &ms, const V3 &N, int b, double rough, V3 &nd)
+{
+    const unsigned key = (unsigned)*ms.template at<WGT, MS::KEY>(lds.acc, lds.wave);
+    const V3 R = nd;
+    bool found = false;
+    V3 q{0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int j = 0; j < 8 && !found; ++j) {
+        const unsigned t = ((unsigned)b << 5) | ((unsigned)j << 2);
+        const V3 c{(double)(scatter_hash(key, t) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
+                   (double)(scatter_hash(key, t | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
+                   (double)(scatter_hash(key, t | 2u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0)};
+        if (dot3(c, c) < 1.0) { q = c; found = true; }
+    }
+    if (found) nd = normalize3(V3{R.x + rough * q.x, R.y + rough * q.y, R.z + rough * q.z});   // linear_comb(R, q, 1.0, rough)
+    const double sR = dot3(R, N), sD = dot3(nd, N);
+    return (sR > 0.0 && sD > 0.0) || (sR < 0.0 && sD < 0.0);
+}
+
 // The continuation of a REFR kernel's hit (MatState: ETA, Q), in place of trace.py:105-110.  d: the incoming direction,
 // N: the outward normal at the hit, Pt = P + BIAS*N (:82-83).  float64 throughout, in the order rt_set_scene_materials_ex
 // documents (mi355rt.h): c = d.N; entering (c < 0): eta = 1/ior, ci = -c, n = N; leaving: eta = ior, ci = c, n = -N.
@@ -1199,8 +1246,10 @@ template <> struct RayCount<true> {
 //   plane (thin sheet, ior ignored):  d, from P - BIAS*n
 // and the next origin is that point + BIAS * the new direction.  P - BIAS*n is Q entering and Pt leaving, P + BIAS*n the
 // other way round (-BIAS*n = -+bN exactly: negation is exact).
+// SCAT: a reflection off a rough surface is scattered (scatter_continue; sb: the trace index, -1 for the last trace, whose
+// continuation is never used); returns false where the path ends (absorption).  Otherwise always true.
 template <int WGT, class MS>
-__device__ __forceinline__ void refract_continue(const Lds &lds, const MS &ms, const V3 &N, const V3 &Pt, V3 &o, V3 &d)
+__device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, const V3 &N, const V3 &Pt, V3 &o, V3 &d, int sb = -1)
 {
     const double eta_slot = *ms.template at<WGT, MS::ETA>(lds.acc, lds.wave);
     V3 nd;
@@ -1223,23 +1272,31 @@ __device__ __forceinline__ void refract_continue(const Lds &lds, const MS &ms, c
             } else from_q = !enter;                                           // total internal reflection: stays on the incoming side
         }
     }
+    bool keep = true;
     if (reflect) {                                                            // common.py:113-120
         const double c2 = -2.0 * dot3(d, N);
         nd = renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
+        if constexpr (MS::scat) {                                             // (a transparent row is never rough)
+            const double rough = *ms.template at<WGT, MS::ROUGH>(lds.acc, lds.wave);
+            if (rough > 0.0 && sb >= 0) keep = scatter_continue<WGT>(lds, ms, N, sb, rough, nd);
+        }
     }
     V3 b = Pt;
     if (from_q) b = V3{*ms.template at<WGT, MS::QX>(lds.acc, lds.wave), *ms.template at<WGT, MS::QY>(lds.acc, lds.wave),
                        *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave)};
     o = V3{b.x + 0.0002 * nd.x, b.y + 0.0002 * nd.y, b.z + 0.0002 * nd.z};
     d = nd;
+    return keep;
 }
 
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
 // MAT: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
+// b: the trace index (0: the primary ray); SCAT kernels scatter off rough surfaces with it, and clear `alive` where a scattered
+// path ends (absorption) after this trace's colour.
 template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
-                                             V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms)
+                                             V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
     constexpr bool NOREC = MODE >= 1;         // no float64 sphere records in LDS (sphere_hot)
     const int S = p.S, P = p.P, L = opaque(p.L);
@@ -1300,6 +1357,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                     *ms.template at<WGT, MS::QY>(lds.acc, lds.wave) = Pt.y - bN.y;
                     *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave) = Pt.z - bN.z;
                 }
+                if constexpr (MS::scat) *ms.template at<WGT, MS::ROUGH>(lds.acc, lds.wave) = mp[5];
             } else
             *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = mp[2];
             const double amb = mp[0];
@@ -1330,7 +1388,9 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             }
         }
         d = dpark.get();
-        if constexpr (MS::refr) {
+        if constexpr (MS::scat) {
+            alive = refract_continue<WGT>(lds, ms, N, Pt, o, d, b < p.depth ? b : -1);   // (alive is true here)
+        } else if constexpr (MS::refr) {
             refract_continue<WGT>(lds, ms, N, Pt, o, d);
         } else {
         const double c2 = -2.0 * dot3(d, N);                                  // common.py:113-120
@@ -1349,12 +1409,15 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 // MAT (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
 // of the surfaces the ray was reflected off, in place of p.refl_pow[b-1].  W stops changing where the path ends: the missed
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
+// SCAT: key is the sample's scatter_key, kept in its slot for the scatter.
 template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
-__device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms)
+__device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
+                                     unsigned key = 0u)
 {
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
     if constexpr (MAT) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
+    if constexpr (MS::scat) *ms.template at<WGT, MS::KEY>(lds.acc, lds.wave) = (double)key;
     for (int b = 0; b <= p.depth; ++b) {
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;                                   // wave-uniform exit
         if constexpr (COUNT) {                                                // lane utilisation per bounce: waves entering, lanes alive
@@ -1368,7 +1431,7 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE, MAT, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms);
+        trace_bounce<PARK, WGT, COUNT, MODE, MAT, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0)
             double wgt;
@@ -1464,9 +1527,10 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
 
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
-__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta)
+__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false, bool scat = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0) + (scat ? 2 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key)
 // The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
-// M, then the M x cols table {amb, lamb, refl} (cols = 5, refraction kernels: {amb, lamb, refl, trans, ior}), then S + P int32
+// M, then the M x cols table {amb, lamb, refl} (cols = 5, refraction kernels: {amb, lamb, refl, trans, ior}; cols = 6, scatter
+// kernels: ..., rough), then S + P int32
 // material ids of the slots (padded to a double).  Material kernels stage it at the end of their LDS image.
 __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
 __host__ __device__ inline size_t mat_doubles(int M, int S, int P, int cols = 3) { return M > 0 ? 1 + (size_t)cols * M + ((size_t)S + P + 1) / 2 : 0; }
@@ -1501,11 +1565,12 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
     return col ? t.total_col : (lanes ? t.total_lanes : t.total);
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
-// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise; refr: the refraction kernels.
+// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise; refr: the refraction kernels;
+// scat: the scatter kernels.
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
-                                            size_t matd = 0, bool refr = false)
+                                            size_t matd = 0, bool refr = false, bool scat = false)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr) * wgt + matd) * sizeof(double) +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr, scat) * wgt + matd) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
            + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
@@ -1625,11 +1690,11 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
 }
 
 // The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false>
-__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR> mat_state(double *matl, int M)
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false>
+__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT> mat_state(double *matl, int M)
 {
     typedef __attribute__((address_space(3))) double lds_d;
-    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + (REFR ? 5 : 3) * M)};
+    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR, SCAT>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MatState<MAT, WSLOT, FRESH, REFR, SCAT>::COLS * M)};
     else return {};
 }
 
@@ -1637,7 +1702,8 @@ __device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR> mat_state(double *m
 // live state (registers decide occupancy here).
 // MAT: the scene has a material table (per-object shading coefficients, rt_set_scene_materials).
 // REFR (with MAT only): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false>
+// SCAT (with REFR only): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false, bool SCAT = false>
 #ifndef RT_W_PARK
 #define RT_W_PARK 7
 #endif
@@ -1656,7 +1722,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
     double *accum = lds_raw + nrec;
     static_assert(MAT || !REFR, "refraction kernels are material kernels");
-    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR) * WG_THREADS);
+    static_assert(REFR || !SCAT, "scatter kernels are refraction kernels");
+    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR, SCAT) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
@@ -1689,7 +1756,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     if constexpr (MAT) {
         const double *msrc = p.scene + mat_offset(p.S, p.P, p.L, p.NC);
         nmat = (int)msrc[0];
-        const int nm = (int)mat_doubles(nmat, p.S, p.P, REFR ? 5 : 3);
+        const int nm = (int)mat_doubles(nmat, p.S, p.P, SCAT ? 6 : (REFR ? 5 : 3));
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
     }
     __syncthreads();
@@ -1754,10 +1821,15 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
     constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
-    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR>(matl, nmat);
+    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT>(matl, nmat);
+    // SCAT: the scatter key of a sample is (X, Y, s) on the half-pixel lattice, pixel centres at (2x, 2y), absolute columns
+    // (the lattice kernels' own coordinates); s the stochastic sample, else 0
+    const unsigned sseed = SCAT ? p.seed : 0u;
     double R, G, B;
     if constexpr (!AA) {
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms);   // kernels.py:19-26
+        unsigned key = 0u;
+        if constexpr (SCAT) key = LAT ? scatter_key((unsigned)xc, (unsigned)yc, 0u, sseed) : scatter_key(2u * xc, 2u * yc, 0u, sseed);
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms, key);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -1774,6 +1846,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         for (int tap = 0; tap < ntaps; ++tap) {
             const V3 Pp = pixel_P(p, xc, yc);                                 // :19
             V3 Pt = Pp;
+            unsigned key = 0u;
+            if constexpr (SCAT) key = scatter_key(2u * xc, 2u * yc, stoch ? (unsigned)tap : 0u, sseed);
             if (stoch) {
                 const unsigned hh = jitter_hash((unsigned)xc, (unsigned)yc, (unsigned)tap, p.seed);
                 const double u = (double)(hh & 0xFFFFu) * 0x1p-16 + (0x1p-17 - 0.5);
@@ -1784,8 +1858,9 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
                 const int ddx = (int)((NBX >> (2 * k)) & 3u) - 1, ddy = (int)((NBY >> (2 * k)) & 3u) - 1;
                 const V3 Pn = pixel_P(p, interior ? x + ddx : xc, interior ? y + ddy : yc);
                 Pt = V3{0.5 * Pp.x + 0.5 * Pn.x, 0.5 * Pp.y + 0.5 * Pn.y, 0.5 * Pp.z + 0.5 * Pn.z};   // :43-50
+                if constexpr (SCAT) key = scatter_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
             }
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms, key);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

@@ -100,7 +100,9 @@ class Renderer:
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
         the launches' amb, lamb and refl are then ignored (rt_set_scene_materials).  A table of shape (M,5), rows
-        amb, lamb, refl, trans, ior, has transparent materials (rt_set_scene_materials_ex)."""
+        amb, lamb, refl, trans, ior, has transparent materials (rt_set_scene_materials_ex); one of shape (M,6), rows
+        amb, lamb, refl, trans, ior, rough, rough ones as well (rt_set_scene_materials_scatter).  The width of a 2-D table
+        is its number of columns (the library refuses any but 3, 5 and 6); a 1-D table is read as rows of 3."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
         if materials is None:
@@ -109,14 +111,20 @@ class Renderer:
         else:
             table, sid, pid = materials
             t = np.ascontiguousarray(table, dtype=np.float64)
-            ncols = 5 if (t.ndim == 2 and t.shape[1] == 5) else 3
-            t = t.reshape(-1, ncols)
+            ncols = t.shape[1] if t.ndim == 2 else 3
+            if ncols == 3:
+                t = t.reshape(-1, 3)
             si = np.ascontiguousarray(sid, dtype=np.int32).reshape(-1)
             pi = np.ascontiguousarray(pid, dtype=np.int32).reshape(-1)
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            if ncols == 5:
+            if ncols not in (3, 5):
+                self._check(self._lib.rt_set_scene_materials_scatter(
+                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
+                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
+                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
+            elif ncols == 5:
                 self._check(self._lib.rt_set_scene_materials_ex(
                     self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
                     p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], 5, si.ctypes.data_as(ip),

@@ -17,12 +17,16 @@ class Material:
     per object instead of per frame.  float64; any finite value.
     transparency > 0 makes the object transparent: the ray continues through it (refracted by a sphere with index of
     refraction `ior`, straight through a plane) with weight `transparency` instead of being reflected; such a material must
-    have refl == 0.  transparency finite and >= 0, ior finite and > 0 (include/mi355rt.h: rt_set_scene_materials_ex)."""
+    have refl == 0.  transparency finite and >= 0, ior finite and > 0 (include/mi355rt.h: rt_set_scene_materials_ex).
+    roughness > 0 makes the reflection rough: the reflected ray is scattered around the mirror direction by up to `roughness`
+    (a "fuzzy metal"), reproducibly per sample and seed; finite and in [0, 1], and 0 for a transparent material
+    (include/mi355rt.h: rt_set_scene_materials_scatter)."""
     amb: float
     lamb: float
     refl: float
     transparency: float = 0.0
     ior: float = 1.0
+    roughness: float = 0.0
 
     def __post_init__(self):
         # (amb, lamb and refl are checked where the table is set, as before: rt_set_scene_materials refuses non-finite ones)
@@ -32,6 +36,10 @@ class Material:
             raise ValueError(f"ior must be finite and > 0, got {self.ior}")
         if float(self.transparency) > 0.0 and float(self.refl) != 0.0:
             raise ValueError("a transparent material (transparency > 0) must have refl == 0")
+        if not (np.isfinite(float(self.roughness)) and 0.0 <= float(self.roughness) <= 1.0):
+            raise ValueError(f"roughness must be finite and in [0, 1], got {self.roughness}")
+        if float(self.transparency) > 0.0 and float(self.roughness) > 0.0:
+            raise ValueError("a transparent material (transparency > 0) cannot be rough (roughness > 0)")
 
     @property
     def transparent(self):
@@ -40,8 +48,15 @@ class Material:
     def key(self):
         return (float(self.amb), float(self.lamb), float(self.refl))
 
+    @property
+    def rough(self):
+        return float(self.roughness) > 0.0
+
     def key5(self):
         return (float(self.amb), float(self.lamb), float(self.refl), float(self.transparency), float(self.ior))
+
+    def key6(self):
+        return self.key5() + (float(self.roughness),)
 
 
 @dataclass
@@ -106,17 +121,17 @@ class Scene:
     def generate_materials(self, default: Material):
         """(table float64 (M,3) rows amb, lamb, refl; sphere_ids int32 (S,); plane_ids int32 (P,)) for
         Renderer.set_scene(..., materials=...).  Objects without a material get `default`; equal materials share one row,
-        in the order of first use (spheres, then planes).  If any material is transparent the table is (M,5), rows
-        amb, lamb, refl, transparency, ior."""
+        in the order of first use (spheres, then planes).  If any material is rough the table is (M,6), rows
+        amb, lamb, refl, transparency, ior, roughness; else if any is transparent it is (M,5), the first five of those."""
         rows, index = [], {}
         mats = [o.material if o.material is not None else default for o in list(self.spheres) + list(self.planes)]
-        wide = any(m.transparent for m in mats)
+        ncols = 6 if any(m.rough for m in mats) else (5 if any(m.transparent for m in mats) else 3)
 
         def ids(objs):
             out = np.zeros(len(objs), dtype=np.int32)
             for i, o in enumerate(objs):
                 m = o.material if o.material is not None else default
-                k = m.key5() if wide else m.key()
+                k = {3: m.key, 5: m.key5, 6: m.key6}[ncols]()
                 if k not in index:
                     index[k] = len(rows)
                     rows.append(k)
@@ -124,7 +139,7 @@ class Scene:
             return out
 
         sphere_ids, plane_ids = ids(self.spheres), ids(self.planes)
-        return np.array(rows, dtype=np.float64).reshape(-1, 5 if wide else 3), sphere_ids, plane_ids
+        return np.array(rows, dtype=np.float64).reshape(-1, ncols), sphere_ids, plane_ids
 
     @staticmethod
     def default_scene():

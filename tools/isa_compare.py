@@ -8,11 +8,12 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
   * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
     kernel's own symbol renumbered, must be identical in the working tree;
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
-A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT and REFR
-parameters, rt_device.h) are ignored, so the default kernels of a tree with material or refraction kernels match those of a
-tree without, and the material kernels (MAT = true, REFR = false) match those of a tree without refraction kernels.
---twins also prints each material kernel (MAT = true) next to its default twin, and each refraction kernel (REFR = true) next
-to its material twin.  Exit status 1 if any kernel differs.
+A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT, REFR
+and SCAT parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction or scatter kernels
+match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without refraction kernels, and
+the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels.
+--twins also prints each material kernel (MAT = true) next to its default twin, each refraction kernel (REFR = true) next to
+its material twin and each scatter kernel (SCAT = true) next to its refraction twin.  Exit status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -34,12 +35,13 @@ def build(tree):
 
 def key(name):
     """Kernel symbol -> (kernel, template arguments without trailing false ones past the sixth), and its family:
-    "" (default), "mat" (MAT = true) or "refr" (REFR = true)."""
+    "" (default), "mat" (MAT = true), "refr" (REFR = true) or "scat" (SCAT = true)."""
     m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
     if not m:
         return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
-    fam = "refr" if len(args) >= 8 and args[7] == "1" else ("mat" if len(args) >= 7 and args[6] == "1" else "")
+    fam = ("scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
+           "mat" if len(args) >= 7 and args[6] == "1" else "")
     return (m.group(1),) + tuple(args[:6]), fam
 
 
@@ -101,9 +103,10 @@ def main():
     print(f"{len(bf)} kernels of {a.base} compared, {bad} differ")
     if a.twins:
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
-        for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel")):
+        for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"),
+                                 ("scat", "refr", "scatter kernel")):
             print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   "
-                  f"{'default' if twin == '' else 'material'} twin")
+                  f"{dict(mat='material', refr='refraction').get(twin, 'default')} twin")
             for (k, f_), n in sorted(new_by_key.items(), key=str):
                 if f_ != fam:
                     continue
