@@ -64,6 +64,7 @@ typedef enum rt_status {
                              samples' (R,G,B).  Needs the closed-form ray grid (rt_set_raygen).  Each sample is
                              the reference's sample() (trace.py:115-133) on that direction. */
 #define RT_MAX_SPP 64
+#define RT_MAX_SHADOW_SAMPLES 16 /* rt_set_scene_area_lights: shadow samples per light and trace */
 
 /* flags */
 #define RT_FLAG_TYPED_BIAS 1 /* evaluate BIAS*N of a plane hit (trace.py:82-83) in float64 (numba
@@ -104,7 +105,8 @@ typedef struct rt_params {
     int32_t aa_mode; /* RT_AA_* */
     int32_t flags;   /* RT_FLAG_* */
     int32_t spp;     /* RT_AA_STOCHASTIC: samples per pixel, 1..RT_MAX_SPP (ignored otherwise) */
-    uint32_t seed;   /* RT_AA_STOCHASTIC: hash seed (and, in every mode, of rt_set_scene_materials_scatter's rough rows) */
+    uint32_t seed;   /* RT_AA_STOCHASTIC: hash seed (and, in every mode, of rt_set_scene_materials_scatter's rough rows and
+                        rt_set_scene_area_lights' shadow samples) */
     int32_t reserved;
 } rt_params;
 
@@ -235,6 +237,33 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
                                    const float *planes, int P, int flags,
                                    const double *materials, int M, int ncols,
                                    const int32_t *sphere_material, const int32_t *plane_material);
+
+/* The same with area lights: soft shadows from spherical lights with a radius.  light_radius float32 (L,), radius rho_m of
+ * light m (finite, >= 0; the (3,L) lights array is unchanged and holds the centres c_m); shadow_samples n, 1..RT_MAX_SHADOW_SAMPLES.
+ *   Every rho_m == 0:  exactly rt_set_scene_materials_scatter (the same kernels and bytes, whatever n is).
+ *   Some rho_m > 0:    every light is sampled n times per trace, lights of radius 0 included.  For trace b (b = 0: the primary
+ *     ray) of sample (X, Y, s) (the key of rt_set_scene_materials_scatter), light m and shadow sample i = 0..n-1:
+ *       candidate j = 0..7, component c = 0..2:  h = jitter_hash(X, Y, t, seed ^ 0x50F7117E) with
+ *         t = ((((s*32 + b)*64 + m)*16 + i)*8 + j)*4 + c   (injective for s < 64, b <= 16, m < 64, i < 16; below 2^26),
+ *         q_c = (double)(h >> 8) * 2^-23 + (2^-24 - 1)   (exact); q is the first candidate with dot(q, q) < 1 (exact).
+ *       Q = c_m + rho_m * q, float64 with c_m the float32 centre widened and rho_m the float32 radius widened, no fused
+ *         multiply-add; Q = c_m if none of the eight candidates is inside the ball.
+ *     Trace b is the reference's trace() (trace.py:44-112) with two changes: its lights array is the L*n points Q in the order
+ *     (m, i), m-major, and lambert_int is lamb_b / n (a float64 division, exact for a power-of-two n).  Everything else is as
+ *     before: the ambient term, get_vector_to_light(Pt, Q), the shadow query's 0 < t < 999 any-hit (an occluder beyond Q
+ *     counts), no query where the Lambert term is <= 0, refraction, scatter and the weights W_k.  Every AA mode, the lattice
+ *     path, RT_FLAG_AA_PER_PIXEL, an explicit grid and column slabs give the same bytes.  rt_params.seed is read in every
+ *     aa_mode for such a scene.
+ *   Soft lights need a material table (M >= 1; ncols 3, 5 or 6, the rules of rt_set_scene_materials_scatter): scalar-only
+ *   shading has no area-light kernels.  Invalid input (as rt_set_scene_materials_scatter, a radius > 0 with M == 0, a NULL
+ *   light_radius with L > 0, a radius NaN, infinite or < 0, shadow_samples outside 1..RT_MAX_SHADOW_SAMPLES): RT_ERR_BAD_ARG,
+ *   and the previous scene stays current.  RT_FLAG_COUNT_RAYS is refused for such a scene.  RT_ABI_VERSION is unchanged:
+ *   callers detect this entry point by its symbol. */
+int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                             const float *planes, int P, int flags,
+                             const double *materials, int M, int ncols,
+                             const int32_t *sphere_material, const int32_t *plane_material,
+                             const float *light_radius, int shadow_samples);
 
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);

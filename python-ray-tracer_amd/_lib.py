@@ -12,6 +12,7 @@ RT_MAX_MATERIALS = 256
 RT_OK, RT_ERR_BAD_ARG, RT_ERR_HIP, RT_ERR_NO_DEVICE, RT_ERR_STATE, RT_ERR_ALLOC = 0, -1, -2, -3, -4, -5
 RT_AA_NONE, RT_AA_REFERENCE, RT_AA_STOCHASTIC = 0, 1, 2
 RT_MAX_SPP = 64
+RT_MAX_SHADOW_SAMPLES = 16
 RT_RENDER_SLOTS = 4
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
@@ -49,6 +50,8 @@ PROTOTYPES = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_set_scene_materials_scatter": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int,
                                                  C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rt_set_scene_area_lights": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "rt_set_pixel_loc": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),

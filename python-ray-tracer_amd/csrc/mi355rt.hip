@@ -78,6 +78,8 @@ struct rt_ctx {
     size_t mat_lds_limit_set = 0; // hipFuncAttributeMaxDynamicSharedMemorySize of the material kernels (lds_limit_set: the others)
     size_t refr_lds_limit_set = 0;   // (the same, refraction kernels)
     size_t scat_lds_limit_set = 0;   // (the same, scatter kernels)
+    size_t soft_lds_limit_set = 0;   // (the same, area-light kernels)
+    int soft_n = 0;               // shadow samples per light of a scene with a light radius > 0 (the area-light kernels), else 0
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
@@ -253,27 +255,28 @@ const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int w
 
 // The refraction kernels (rt_device.h: REFR): the material twins for a scene whose table has a transparent row
 // (rt_set_scene_materials_ex), same arguments.  SC: their scatter twins (rt_device.h: SCAT), for a table with a rough row
-// (rt_set_scene_materials_scatter).
-template <bool SC = false>
+// (rt_set_scene_materials_scatter).  SO (with SC): the area-light twins of those (rt_device.h: SOFT), for a scene with a light
+// radius > 0 (rt_set_scene_area_lights).
+template <bool SC = false, bool SO = false>
 const void *refraction_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
 {
     if (lanes) {
-        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC>;
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC>);
+        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC, SO>;
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC, SO>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC, SO>);
     }
     if (lattice) {
-        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC>;
-        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC>;
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC>;
+        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC, SO>;
+        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC, SO>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC, SO>;
     }
     if (norec && wpw == 4 && !aa)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC, SO>;
     if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC>);
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC, SO>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC, SO>);
+    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC, SO>)
+              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC, SO>);
 }
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
@@ -444,24 +447,34 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // (matd doubles), and the parked ones one more per-thread slot
     // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots; with a rough row
     // their scatter twins, with rows of 6 and two more slots)
+    // (a scene with a light radius > 0: the scatter kernels' area-light twins, rows of 6, one more slot and n behind the block)
+    const bool soft = ctx->M > 0 && ctx->soft_n > 0;
     const bool scat = ctx->M > 0 && ctx->mat_cols == 6;
     const bool refr = ctx->M > 0 && ctx->mat_cols >= 5;
-    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, ctx->mat_cols);   // (the block is in the launch's scene buffer: rt::mat_offset)
+    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, ctx->mat_cols, soft);   // (the block is in the launch's scene buffer: rt::mat_offset)
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr, scat);
+        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr, scat, soft);
         if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
-        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr, scat));
+        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr, scat, soft));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr, scat);
+    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr, scat, soft);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr, scat);
-    const void *fn = scat ? refraction_variant<true>(lanes, aa, lattice, park, wpw, norec)
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr, scat, soft);
+    const void *fn = soft ? refraction_variant<true, true>(lanes, aa, lattice, park, wpw, norec)
+                   : scat ? refraction_variant<true>(lanes, aa, lattice, park, wpw, norec)
                    : refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
                    : matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
                           : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (scat) {
+    if (soft) {
+        if (lds > 48 * 1024 && lds > ctx->soft_lds_limit_set) {
+            for (int v = 0; v < 64; ++v)
+                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ctx->soft_lds_limit_set = lds;
+        }
+    } else if (scat) {
         if (lds > 48 * 1024 && lds > ctx->scat_lds_limit_set) {
             for (int v = 0; v < 64; ++v)
                 RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
@@ -745,12 +758,50 @@ int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const fl
     return rt_set_scene_materials_scatter(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
 }
 
+static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
+                     const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
+                     const float *light_radius, int shadow_samples);
+
 int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                                    int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
                                    const int32_t *plane_material)
 {
+    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material, nullptr, 1);
+}
+
+int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
+                             int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
+                             const int32_t *plane_material, const float *light_radius, int shadow_samples)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
+    static const float none = 0.0f;
+    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
+                     light_radius ? light_radius : &none, shadow_samples);
+}
+
+// Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights.
+static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
+                     const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
+                     const float *light_radius, int shadow_samples)
+{
     if (!ctx) return RT_ERR_BAD_ARG;
     if (ncols != 3 && ncols != 5 && ncols != 6) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3, 5 or 6");
+    // area lights (light_radius: nullptr from rt_set_scene_materials_scatter): validated here; a scene with every radius 0 is
+    // exactly rt_set_scene_materials_scatter's (soft stays false), one with a radius > 0 runs the area-light kernels
+    bool soft = false;
+    if (light_radius) {
+        if (shadow_samples < 1 || shadow_samples > RT_MAX_SHADOW_SAMPLES)
+            return fail(ctx, RT_ERR_BAD_ARG, "shadow_samples outside 1..RT_MAX_SHADOW_SAMPLES");
+        if (L < 0 || L > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
+        for (int k = 0; k < L; ++k) {
+            if (!(std::isfinite(light_radius[k]) && light_radius[k] >= 0.0f))
+                return fail(ctx, RT_ERR_BAD_ARG, "light_radius[" + std::to_string(k) + "] must be finite and >= 0");
+            soft = soft || light_radius[k] > 0.0f;
+        }
+        if (soft && !(M > 0 && materials))
+            return fail(ctx, RT_ERR_BAD_ARG, "a light radius > 0 needs a material table (M >= 1)");
+    }
     // a 5- or 6-column table: validated here; it travels with the columns its rows use: all six with a rough row (the scatter
     // kernels), else the first five with a transparent row (the refraction kernels), else the first three (the material kernels)
     std::vector<double> packed;
@@ -783,6 +834,22 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
             return fail(ctx, RT_ERR_ALLOC, "out of host memory");
         }
         materials = packed.data();
+    }
+    // the area-light kernels are scatter kernels: their table travels with all six columns (a 3- or 5-column table padded with
+    // trans 0, ior 1, rough 0), and with lamb / n in place of lamb (the reference's lambert_int of a trace with n points per light)
+    std::vector<double> soft_table;
+    if (soft && M <= RT_MAX_MATERIALS) {
+        static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        try {
+            soft_table.resize((size_t)6 * M);
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, RT_ERR_ALLOC, "out of host memory");
+        }
+        for (int m = 0; m < M; ++m)
+            for (int i = 0; i < 6; ++i) soft_table[(size_t)6 * m + i] = i < cols ? materials[(size_t)cols * m + i] : pad[i];
+        for (int m = 0; m < M; ++m) soft_table[(size_t)6 * m + 1] = soft_table[(size_t)6 * m + 1] / (double)shadow_samples;
+        materials = soft_table.data();
+        cols = 6;
     }
     if (S < 0 || S > RT_MAX_SPHERES || L < 0 || L > RT_MAX_LIGHTS || P < 0 || P > RT_MAX_PLANES)
         return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
@@ -846,7 +913,7 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
         }
         nclusters = NC;
         const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
-        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols), 0.0);
+        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols, soft), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -878,6 +945,7 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
         }
         for (int k = 0; k < L; ++k, sp += rt::LT_STRIDE) {
             sp[0] = lights[0 * L + k]; sp[1] = lights[1 * L + k]; sp[2] = lights[2 * L + k];
+            if (soft) sp[3] = light_radius[k];                      // (the pad slot: the area-light kernels' radius)
         }
         // bounding sphere (float64, inflated) of the spheres in slots [j0, j1): around the centroid of the centres or the centre of
         // their bounding box, whichever gives the smaller sphere
@@ -913,6 +981,7 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
             for (int slot = 0; slot < S; ++slot) ids[slot] = sphere_material[order[slot]];
             for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
             if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
+            if (soft) rec.back() = (double)shadow_samples;          // (rt::mat_doubles: the block's last double)
         }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
@@ -938,12 +1007,17 @@ int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, con
     }
     for (int k = 0; k < L; ++k) {
         const double x = lights[0 * L + k], y = lights[1 * L + k], z = lights[2 * L + k];
+        if (soft) {                                                 // (the light's ball)
+            const double e = std::sqrt(x * x + y * y + z * z) + (double)light_radius[k];
+            if (e * e > ext2) ext2 = e * e;
+        } else
         if (x * x + y * y + z * z > ext2) ext2 = x * x + y * y + z * z;
     }
     ctx->scene_extent2 = ext2;
     ctx->S = S; ctx->P = P; ctx->L = L; ctx->NC = nclusters;
     ctx->M = M;
     ctx->mat_cols = cols;
+    ctx->soft_n = soft ? shadow_samples : 0;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

@@ -330,15 +330,19 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // SCAT (scatter kernels, rt_set_scene_materials_scatter with a rough row; REFR too): rows of 6, {amb, lamb, refl, trans, ior,
 // rough}, and two more slots: ROUGH, the hit's roughness, and KEY, the sample's pre-hashed key (scatter_key), written once per
 // sample and read by the scatter after the light loop (scatter_continue).
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false> struct MatState {
-    static constexpr bool refr = false, scat = false;
+// SOFT (area-light kernels, rt_set_scene_area_lights with a radius > 0; SCAT too): one more slot, LKEY, the sample's pre-hashed
+// light key (soft_key), read inside the light loop where each shadow sample's point on its light is formed (soft_light_point);
+// nsh is the scene's shadow_samples n (the last double of the material block).
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false> struct MatState {
+    static constexpr bool refr = false, scat = false, soft = false;
 };
-template <int WSLOT, bool FRESH, bool REFR, bool SCAT> struct MatState<true, WSLOT, FRESH, REFR, SCAT> {
-    static constexpr bool refr = REFR, scat = SCAT;
+template <int WSLOT, bool FRESH, bool REFR, bool SCAT, bool SOFT> struct MatState<true, WSLOT, FRESH, REFR, SCAT, SOFT> {
+    static constexpr bool refr = REFR, scat = SCAT, soft = SOFT;
     static constexpr int COLS = SCAT ? 6 : (REFR ? 5 : 3);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
-    enum { W = 0, LAMB = 1, REFL = 2, QX = 3, QY = 4, QZ = 5, ETA = 6, ROUGH = 7, KEY = 8 };
+    int nsh;                   // SOFT: shadow samples per light (1 otherwise, unused)
+    enum { W = 0, LAMB = 1, REFL = 2, QX = 3, QY = 4, QZ = 5, ETA = 6, ROUGH = 7, KEY = 8, LKEY = 9 };
     template <int WGT, int k> __device__ __forceinline__ volatile lds_f64 *at(const double *acc, int wave) const
     {
         if constexpr (FRESH) return (volatile lds_f64 *)acc + (WSLOT + k) * WGT + wave * 64 + fresh_lane();
@@ -1214,6 +1218,34 @@ __device__ __forceinline__ unsigned scatter_hash(unsigned key, unsigned t)
     return h;
 }
 
+// The area-light hash (rt_set_scene_area_lights, mi355rt.h): jitter_hash(X, Y, t, seed ^ 0x50F7117E) with
+// t = ((((s*32 + b)*64 + m)*16 + i)*8 + j)*4 + c, the bit pattern s << 20 | b << 15 | m << 9 | i << 5 | j << 2 | c (s < 64,
+// b <= 16, m < 64, i < 16).  soft_key is its first two rounds on (X, Y) with s folded in (as scatter_key); scatter_hash
+// finishes it for t without s.
+__device__ __forceinline__ unsigned soft_key(unsigned x, unsigned y, unsigned s, unsigned seed)
+{
+    unsigned h = (seed ^ 0x50F7117Eu) ^ 0x9E3779B9u;
+    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
+    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
+    return h ^ (s << 20);
+}
+
+// Shadow sample point Q of a light record g = {cx, cy, cz, rho} for the hash key `key` (soft_key with t = b << 15 | m << 9 |
+// i << 5 folded in): the first of eight hashed candidates q in the unit ball (as scatter_continue's), Q = c + rho*q (float64,
+// no fused multiply-add: -ffp-contract=off), or c itself if none of the eight is inside.
+__device__ __forceinline__ V3 soft_light_point(unsigned key, const double *g)
+{
+#pragma unroll 1
+    for (int j = 0; j < 8; ++j) {
+        const unsigned t = (unsigned)j << 2;
+        const V3 c{(double)(scatter_hash(key, t) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
+                   (double)(scatter_hash(key, t | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
+                   (double)(scatter_hash(key, t | 2u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0)};
+        if (dot3(c, c) < 1.0) { const double rho = g[3]; return V3{g[0] + rho * c.x, g[1] + rho * c.y, g[2] + rho * c.z}; }
+    }
+    return V3{g[0], g[1], g[2]};
+}
+
 // The scatter of a SCAT kernel's hit on a rough surface (rough > 0, trace b < depth), in place of the mirror direction R:
 // the first of eight hashed candidates q in the unit ball (q_c = (h >> 8) 2^-23 + 2^-24 - 1, and q.q, are exact), then
 // D = normalize(R + rough*q) (R itself if none of the eight is inside).  Returns false if D leaves on the other side of the
@@ -1371,6 +1403,27 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         RT_MARK(4);
 
         const double *lt = lds.recs() + plb + opaque(P) * PL_STRIDE;
+        if constexpr (MS::soft) {
+        // SOFT: the lights array of :86 is the L*n shadow sample points Q, (m, i) m-major (soft_light_point), and lamb (the
+        // table's, host-divided by n) is lamb_b / n.  The rays do not pass through a light's centre: the shadow query takes the
+        // origin form of the cull (no anchor; the lane-owned kernels' lanes_any<false>), never the light-anchored tables.
+        for (int m = 0; m < L; ++m) {
+            const double *g = lt + m * LT_STRIDE;
+#pragma unroll 1
+            for (int i = 0; i < ms.nsh; ++i) {
+                // (the key is re-read from its slot per sample: no VGPR holds it across the light loop)
+                const unsigned key = (unsigned)*ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) ^ (((unsigned)b << 15) | ((unsigned)m << 9) | ((unsigned)i << 5));
+                const V3 Q = soft_light_point(key, g);
+                const V3 Ld = normalize3(V3{Q.x - Pt.x, Q.y - Pt.y, Q.z - Pt.z});   // common.py:84-91
+                const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * dot3(Ld, N);   // :99
+                RT_MARK(5);
+                if (k > 0.0) {
+                    const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
+                    if (!occluded) rgb = V3{rgb.x + k * col(0), rgb.y + k * col(1), rgb.z + k * col(2)};
+                }
+            }
+        }
+        } else
         for (int m = 0; m < L; ++m) {                                         // :86-102
             const double *g = lt + m * LT_STRIDE;
             const V3 Ld = normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});   // common.py:84-91
@@ -1409,15 +1462,17 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 // MAT (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
 // of the surfaces the ray was reflected off, in place of p.refl_pow[b-1].  W stops changing where the path ends: the missed
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
-// SCAT: key is the sample's scatter_key, kept in its slot for the scatter.
+// SCAT: key is the sample's scatter_key, kept in its slot for the scatter.  SOFT: lkey is its soft_key, kept in its slot for
+// the light loop.
 template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
 __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
-                                     unsigned key = 0u)
+                                     unsigned key = 0u, unsigned lkey = 0u)
 {
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
     if constexpr (MAT) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
     if constexpr (MS::scat) *ms.template at<WGT, MS::KEY>(lds.acc, lds.wave) = (double)key;
+    if constexpr (MS::soft) *ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) = (double)lkey;
     for (int b = 0; b <= p.depth; ++b) {
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;                                   // wave-uniform exit
         if constexpr (COUNT) {                                                // lane utilisation per bounce: waves entering, lanes alive
@@ -1527,13 +1582,14 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
 
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
-__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false, bool scat = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0) + (scat ? 2 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key)
+__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false, bool scat = false, bool soft = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0) + (scat ? 2 : 0) + (soft ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
 // The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
 // M, then the M x cols table {amb, lamb, refl} (cols = 5, refraction kernels: {amb, lamb, refl, trans, ior}; cols = 6, scatter
 // kernels: ..., rough), then S + P int32
-// material ids of the slots (padded to a double).  Material kernels stage it at the end of their LDS image.
+// material ids of the slots (padded to a double), and (soft: a scene of the area-light kernels) its shadow_samples n.  Material
+// kernels stage it at the end of their LDS image.
 __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
-__host__ __device__ inline size_t mat_doubles(int M, int S, int P, int cols = 3) { return M > 0 ? 1 + (size_t)cols * M + ((size_t)S + P + 1) / 2 : 0; }
+__host__ __device__ inline size_t mat_doubles(int M, int S, int P, int cols = 3, bool soft = false) { return M > 0 ? 1 + (size_t)cols * M + ((size_t)S + P + 1) / 2 + (soft ? 1 : 0) : 0; }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
@@ -1566,11 +1622,11 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
 // matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise; refr: the refraction kernels;
-// scat: the scatter kernels.
+// scat: the scatter kernels; soft: the area-light kernels.
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
-                                            size_t matd = 0, bool refr = false, bool scat = false)
+                                            size_t matd = 0, bool refr = false, bool scat = false, bool soft = false)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr, scat) * wgt + matd) * sizeof(double) +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr, scat, soft) * wgt + matd) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
            + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
@@ -1690,11 +1746,12 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
 }
 
 // The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false>
-__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT> mat_state(double *matl, int M)
+// SOFT: nsh is the scene's shadow_samples (the block's last double).
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false>
+__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT> mat_state(double *matl, int M, int nsh = 1)
 {
     typedef __attribute__((address_space(3))) double lds_d;
-    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR, SCAT>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MatState<MAT, WSLOT, FRESH, REFR, SCAT>::COLS * M)};
+    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT>::COLS * M), nsh};
     else return {};
 }
 
@@ -1703,7 +1760,9 @@ __device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT> mat_state(dou
 // MAT: the scene has a material table (per-object shading coefficients, rt_set_scene_materials).
 // REFR (with MAT only): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
 // SCAT (with REFR only): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false, bool SCAT = false>
+// SOFT (with SCAT only): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false, bool SCAT = false,
+          bool SOFT = false>
 #ifndef RT_W_PARK
 #define RT_W_PARK 7
 #endif
@@ -1723,7 +1782,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     double *accum = lds_raw + nrec;
     static_assert(MAT || !REFR, "refraction kernels are material kernels");
     static_assert(REFR || !SCAT, "scatter kernels are refraction kernels");
-    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR, SCAT) * WG_THREADS);
+    static_assert(SCAT || !SOFT, "area-light kernels are scatter kernels");
+    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR, SCAT, SOFT) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
@@ -1752,12 +1812,13 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
 #else
     double *matl = reinterpret_cast<double *>(wgstat + 4);
 #endif
-    int nmat = 0;
+    int nmat = 0, nsh = 1;
     if constexpr (MAT) {
         const double *msrc = p.scene + mat_offset(p.S, p.P, p.L, p.NC);
         nmat = (int)msrc[0];
-        const int nm = (int)mat_doubles(nmat, p.S, p.P, SCAT ? 6 : (REFR ? 5 : 3));
+        const int nm = (int)mat_doubles(nmat, p.S, p.P, SCAT ? 6 : (REFR ? 5 : 3), SOFT);
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
+        if constexpr (SOFT) nsh = (int)msrc[nm - 1];
     }
     __syncthreads();
     // two-wave workgroups serve the small flat scenes only (the host sends every clustered scene to workgroups of 4): with
@@ -1821,15 +1882,17 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
     constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
-    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT>(matl, nmat);
+    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT, SOFT>(matl, nmat, nsh);
     // SCAT: the scatter key of a sample is (X, Y, s) on the half-pixel lattice, pixel centres at (2x, 2y), absolute columns
     // (the lattice kernels' own coordinates); s the stochastic sample, else 0
+    // SOFT: the light key (soft_key) of the same (X, Y, s)
     const unsigned sseed = SCAT ? p.seed : 0u;
     double R, G, B;
     if constexpr (!AA) {
-        unsigned key = 0u;
+        unsigned key = 0u, lkey = 0u;
         if constexpr (SCAT) key = LAT ? scatter_key((unsigned)xc, (unsigned)yc, 0u, sseed) : scatter_key(2u * xc, 2u * yc, 0u, sseed);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms, key);   // kernels.py:19-26
+        if constexpr (SOFT) lkey = LAT ? soft_key((unsigned)xc, (unsigned)yc, 0u, sseed) : soft_key(2u * xc, 2u * yc, 0u, sseed);
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -1846,8 +1909,9 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         for (int tap = 0; tap < ntaps; ++tap) {
             const V3 Pp = pixel_P(p, xc, yc);                                 // :19
             V3 Pt = Pp;
-            unsigned key = 0u;
+            unsigned key = 0u, lkey = 0u;
             if constexpr (SCAT) key = scatter_key(2u * xc, 2u * yc, stoch ? (unsigned)tap : 0u, sseed);
+            if constexpr (SOFT) lkey = soft_key(2u * xc, 2u * yc, stoch ? (unsigned)tap : 0u, sseed);
             if (stoch) {
                 const unsigned hh = jitter_hash((unsigned)xc, (unsigned)yc, (unsigned)tap, p.seed);
                 const double u = (double)(hh & 0xFFFFu) * 0x1p-16 + (0x1p-17 - 0.5);
@@ -1859,8 +1923,9 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
                 const V3 Pn = pixel_P(p, interior ? x + ddx : xc, interior ? y + ddy : yc);
                 Pt = V3{0.5 * Pp.x + 0.5 * Pn.x, 0.5 * Pp.y + 0.5 * Pn.y, 0.5 * Pp.z + 0.5 * Pn.z};   // :43-50
                 if constexpr (SCAT) key = scatter_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
+                if constexpr (SOFT) lkey = soft_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
             }
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms, key);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

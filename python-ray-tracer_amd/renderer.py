@@ -95,16 +95,29 @@ class Renderer:
         self.close()
 
     # -- inputs -----------------------------------------------------------------------------
-    def set_scene(self, spheres, lights, planes, flags=0, materials=None):
+    def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1):
         """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
         the launches' amb, lamb and refl are then ignored (rt_set_scene_materials).  A table of shape (M,5), rows
         amb, lamb, refl, trans, ior, has transparent materials (rt_set_scene_materials_ex); one of shape (M,6), rows
         amb, lamb, refl, trans, ior, rough, rough ones as well (rt_set_scene_materials_scatter).  The width of a 2-D table
-        is its number of columns (the library refuses any but 3, 5 and 6); a 1-D table is read as rows of 3."""
+        is its number of columns (the library refuses any but 3, 5 and 6); a 1-D table is read as rows of 3.
+        light_radius: None, or float32 (L,) radii as Scene.get_light_radii() returns them; with a radius > 0 the lights are
+        area lights with soft shadows, shadow_samples (1..RT_MAX_SHADOW_SAMPLES) points per light and trace
+        (rt_set_scene_area_lights).  Area lights need a material table."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
+        rad = None
+        if light_radius is not None:
+            rad = np.ascontiguousarray(light_radius, dtype=np.float32).reshape(-1)
+            if rad.shape[0] != l.shape[1]:
+                raise ValueError(f"light_radius: {rad.shape[0]} radii for {l.shape[1]} lights")
+            if materials is None and not (np.isfinite(rad) & (rad == 0.0)).all():
+                raise ValueError("area lights (a light radius > 0) need a material table: pass materials=... "
+                                 "(scalar-only shading has no soft shadows)")
+            if materials is None:
+                rad = None
         if materials is None:
             self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
                                                p.ctypes.data_as(fp), p.shape[1], int(flags)))
@@ -119,7 +132,12 @@ class Renderer:
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            if ncols not in (3, 5):
+            if rad is not None:
+                self._check(self._lib.rt_set_scene_area_lights(
+                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
+                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
+                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip), rad.ctypes.data_as(fp), int(shadow_samples)))
+            elif ncols not in (3, 5):
                 self._check(self._lib.rt_set_scene_materials_scatter(
                     self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
                     p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,

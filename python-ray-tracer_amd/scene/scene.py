@@ -74,8 +74,17 @@ class Sphere:
 
 @dataclass
 class Light:
+    """A light at `origin`.  radius > 0 makes it an area light, a ball of that radius: shadows from it are soft (penumbrae),
+    sampled at Renderer.set_scene's shadow_samples points per light (include/mi355rt.h: rt_set_scene_area_lights).  The radius
+    is float32, finite and >= 0; 0 (the default) is the reference's point light."""
     origin: object
+    radius: float = 0.0
     data_length: ClassVar[int] = 3
+
+    def __post_init__(self):
+        r = float(self.radius)
+        if not (np.isfinite(r) and 0.0 <= r <= float(np.finfo(np.float32).max)):
+            raise ValueError(f"light radius must be finite and >= 0, got {self.radius}")
 
     def to_array(self):
         return np.asarray(self.origin, dtype=np.float64).astype(np.float32)
@@ -114,6 +123,10 @@ class Scene:
 
     def get_lights(self):
         return _columns(self.lights, Light.data_length)
+
+    def get_light_radii(self):
+        """float32 (L,): the lights' radii, for Renderer.set_scene(..., light_radius=...)."""
+        return np.array([float(li.radius) for li in self.lights], dtype=np.float32)
 
     def generate_scene(self):
         return self.get_spheres(), self.get_lights(), self.get_planes()

@@ -8,12 +8,15 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
   * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
     kernel's own symbol renumbered, must be identical in the working tree;
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
-A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT, REFR
-and SCAT parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction or scatter kernels
-match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without refraction kernels, and
-the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels.
+A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT, REFR,
+SCAT and SOFT parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction, scatter or
+area-light kernels match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without
+refraction kernels, the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels, and the scatter
+kernels (SCAT = true, SOFT = false) those of a tree without area-light kernels.  Kernels of the working tree that the base does
+not have are listed as NEW.
 --twins also prints each material kernel (MAT = true) next to its default twin, each refraction kernel (REFR = true) next to
-its material twin and each scatter kernel (SCAT = true) next to its refraction twin.  Exit status 1 if any kernel differs.
+its material twin, each scatter kernel (SCAT = true) next to its refraction twin and each area-light kernel (SOFT = true) next
+to its scatter twin.  Exit status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -35,12 +38,12 @@ def build(tree):
 
 def key(name):
     """Kernel symbol -> (kernel, template arguments without trailing false ones past the sixth), and its family:
-    "" (default), "mat" (MAT = true), "refr" (REFR = true) or "scat" (SCAT = true)."""
+    "" (default), "mat" (MAT = true), "refr" (REFR = true), "scat" (SCAT = true) or "soft" (SOFT = true)."""
     m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
     if not m:
         return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
-    fam = ("scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
+    fam = ("soft" if len(args) >= 10 and args[9] == "1" else "scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
            "mat" if len(args) >= 7 and args[6] == "1" else "")
     return (m.group(1),) + tuple(args[:6]), fam
 
@@ -100,13 +103,17 @@ def main():
         print(f"{'same' if same_isa and same_res else 'DIFF'}  isa={'=' if same_isa else '!'} res={'=' if same_res else '!'} "
               f"{len(bf[b].splitlines()):6d} lines  {key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}")
         bad += not (same_isa and same_res)
-    print(f"{len(bf)} kernels of {a.base} compared, {bad} differ")
+    base_keys = {key(b) for b in bf}
+    new = sorted(n for n in nf if key(n) not in base_keys)
+    for n in new:
+        print(f"NEW   {key(n)[0]} {key(n)[1]}")
+    print(f"{len(bf)} kernels of {a.base} compared, {bad} differ; {len(new)} new")
     if a.twins:
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
         for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"),
-                                 ("scat", "refr", "scatter kernel")):
+                                 ("scat", "refr", "scatter kernel"), ("soft", "scat", "area-light kernel")):
             print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   "
-                  f"{dict(mat='material', refr='refraction').get(twin, 'default')} twin")
+                  f"{dict(mat='material', refr='refraction', scat='scatter').get(twin, 'default')} twin")
             for (k, f_), n in sorted(new_by_key.items(), key=str):
                 if f_ != fam:
                     continue
