@@ -2,13 +2,16 @@
 """Render a frame with the `Renderer` API and save it as a PNG.
 
     python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
-                                  [--soft [--shadow-samples 4]] [--out output/render.png]
+                                  [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]] [--out output/render.png]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
 (stochastic anti-aliasing, N samples per pixel) the scattered reflections average out.
 --soft makes the default scene's lights area lights of radius 0.5 (rt_set_scene_area_lights): soft shadows, --shadow-samples
 points per light and trace, over the --materials scene unless --glass or --scatter is given; --spp N averages the penumbrae.
+--dof APERTURE gives the camera a thin lens of that radius (rt_set_lens: depth of field), focused on the centre of sphere K
+(--focus-on-sphere, default 0), over the --materials scene unless --glass or --scatter is given: that sphere is sharp, the floor
+in front of it and behind it blurred.  Use it with --spp 16, which averages the lens samples.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--soft", action="store_true", help="area lights of radius 0.5: soft shadows")
     ap.add_argument("--shadow-samples", type=int, default=4, help="--soft: shadow samples per light and trace")
     ap.add_argument("--spp", type=int, default=0, help="stochastic anti-aliasing with this many samples per pixel")
+    ap.add_argument("--dof", type=float, default=0.0, metavar="APERTURE", help="depth of field: a thin lens of this radius")
+    ap.add_argument("--focus-on-sphere", type=int, default=0, metavar="K", help="--dof: focus on the centre of sphere K")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -55,7 +60,7 @@ def main():
             scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
             scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
-        elif a.materials or a.glass or a.soft:
+        elif a.materials or a.glass or a.soft or a.dof > 0:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
             if a.glass:                                             # clear glass; ior 2.4 (diamond) shows total internal reflection
@@ -69,6 +74,10 @@ def main():
             radii = scene.get_light_radii()
         r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples)
         r.set_camera(cam.position, cam.rotation)
+        if a.dof > 0:
+            focus = cam.focus_on(scene.spheres[a.focus_on_sphere].origin)
+            cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=[0, -30, 0], aperture=a.dof, focus_distance=focus)
+            r.set_lens(*cam.lens)
         r.set_raygen(w, h, *cam.raygen())
         image = r.host_array((h, w, 3), np.uint8)
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
@@ -85,7 +94,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -18,8 +18,8 @@
  *
  * Threading: a context is not thread-safe; use one context per host thread / per GPU.
  * Streams: rt_render_device may be called for one context on several streams (frames of a sequence in flight
- * together); the scheduler feedback inside the context is safe under that use.  rt_set_camera, rt_set_raygen and
- * rt_set_scene apply to LATER launches only: camera and ray grid travel with every launch by value, and the scene
+ * together); the scheduler feedback inside the context is safe under that use.  rt_set_camera, rt_set_lens, rt_set_raygen and
+ * rt_set_scene apply to LATER launches only: camera, lens and ray grid travel with every launch by value, and the scene
  * lives in a ring of device buffers — a launch keeps reading the buffer that was current when it was queued, so frames
  * in flight on any stream finish with the scene they were launched with.  rt_set_pixel_loc (the explicit grid of the
  * literal drop-in) rewrites ONE device buffer: it waits for the whole device before it does.
@@ -106,7 +106,7 @@ typedef struct rt_params {
     int32_t flags;   /* RT_FLAG_* */
     int32_t spp;     /* RT_AA_STOCHASTIC: samples per pixel, 1..RT_MAX_SPP (ignored otherwise) */
     uint32_t seed;   /* RT_AA_STOCHASTIC: hash seed (and, in every mode, of rt_set_scene_materials_scatter's rough rows and
-                        rt_set_scene_area_lights' shadow samples) */
+                        rt_set_scene_area_lights' shadow samples and rt_set_lens' lens samples) */
     int32_t reserved;
 } rt_params;
 
@@ -267,6 +267,32 @@ int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const flo
 
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);
+
+/* Depth of field: a thin-lens camera.  aperture a: the lens radius in world units (finite, >= 0); focus_distance f: the distance
+ * from cam_o to the plane of sharp focus along the camera's forward axis R e_x (finite, > 0).  Invalid values: RT_ERR_BAD_ARG,
+ * and the previous lens stays.  A new context has a = 0.  Like the camera, the lens applies to LATER launches only and travels
+ * with every launch by value (frames in flight keep theirs); a changed lens starts dispatch-order measuring again, the same lens
+ * again changes nothing.  rt_render_sequence uses the context's lens for every frame (cameras != NULL included).
+ *   a == 0:  the pinhole camera, exactly as without this call (the same kernels and bytes, whatever f is).
+ *   a > 0:   the primary ray of every sample is a lens ray; shading, bounces, refraction, scatter and shadow rays are unchanged.
+ *     float64, no fused multiply-add, in this order, with linear_comb / normalize / vector_difference of common.py, O = cam_o,
+ *     R = cam_R and jitter_hash the 32-bit counter hash of rt_params.seed (rt_device.h):
+ *       P: the sample's pixel point as without a lens (pixel_loc / the closed-form grid, the RT_AA_REFERENCE midpoint, the
+ *         RT_AA_STOCHASTIC jittered point); v = R P with the products and sums of kernels.py:22, before its normalize.
+ *       focal point F = linear_comb(O, v, 1.0, f / P.x)  (P.x = px on the closed-form grid; an explicit grid's own first row).
+ *       key (X, Y, s): the key of rt_set_scene_materials_scatter (half-pixel lattice, s the stochastic sample index, else 0).
+ *       candidate j = 0..7, component c = 0..1:  h = jitter_hash(X, Y, (s*8 + j)*2 + c, seed ^ 0x1E45D0F5),
+ *         u_c = (double)(h >> 8) * 2^-23 + (2^-24 - 1)   (exact); u is the first candidate with u_0*u_0 + u_1*u_1 < 1 (exact),
+ *         u = (0, 0) if none of the eight is inside the disk.
+ *       lens point L = (O + (a*u_0)*ey) + (a*u_1)*ez per component, ey = (R[1], R[4], R[7]) and ez = (R[2], R[5], R[8]) the
+ *         images of the camera's y and z axes.
+ *       primary ray (L, normalize(vector_difference(L, F))).
+ *     Every AA mode, the lattice path, RT_FLAG_AA_PER_PIXEL, an explicit grid and column slabs give the same bytes.
+ *     rt_params.seed is read in every aa_mode.  With RT_AA_NONE every pixel gets one lens sample; RT_AA_STOCHASTIC averages.
+ *     A lens needs a scene with a material table (M >= 1): a launch with a > 0 on a scene without one fails with RT_ERR_STATE.
+ *     RT_FLAG_COUNT_RAYS stays refused (as for every scene with materials).  RT_ABI_VERSION is unchanged: callers detect this
+ *     entry point by its symbol. */
+int rt_set_lens(rt_ctx *ctx, double aperture, double focus_distance);
 
 /* The pixel grid of Camera.generate_pixel_locations() (scene/camera.py:18-26) in closed form:
  *   pixel_loc[:, x, y] = (px, x*dy + y0, y*dz + z0)      (one multiply, one add, as np.mgrid does)

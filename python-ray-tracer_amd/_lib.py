@@ -53,6 +53,7 @@ PROTOTYPES = {
     "rt_set_scene_area_lights": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
+    "rt_set_lens": (C.c_int, [_vp, C.c_double, C.c_double]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "rt_set_pixel_loc": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
     "rt_render": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, _vp, _vp]),

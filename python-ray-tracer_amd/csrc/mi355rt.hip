@@ -80,6 +80,9 @@ struct rt_ctx {
     size_t scat_lds_limit_set = 0;   // (the same, scatter kernels)
     size_t soft_lds_limit_set = 0;   // (the same, area-light kernels)
     int soft_n = 0;               // shadow samples per light of a scene with a light radius > 0 (the area-light kernels), else 0
+    size_t lens_lds_limit_set[2] = {0, 0};   // (the same, lens kernels: scatter twins, area-light twins)
+    long long lens_mat = 0;       // offset (doubles) in the scene buffer of its material block with rows of 6 (the lens kernels')
+    double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
@@ -196,6 +199,8 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
     if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
     if (ctx->M > 0 && (p->flags & RT_FLAG_COUNT_RAYS))
         return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_COUNT_RAYS is not available for a scene with materials");
+    if (ctx->lens_a > 0.0 && ctx->M == 0)
+        return fail(ctx, RT_ERR_STATE, "a lens with aperture > 0 needs a scene with a material table (M >= 1)");
     return RT_OK;
 }
 
@@ -256,27 +261,28 @@ const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int w
 // The refraction kernels (rt_device.h: REFR): the material twins for a scene whose table has a transparent row
 // (rt_set_scene_materials_ex), same arguments.  SC: their scatter twins (rt_device.h: SCAT), for a table with a rough row
 // (rt_set_scene_materials_scatter).  SO (with SC): the area-light twins of those (rt_device.h: SOFT), for a scene with a light
-// radius > 0 (rt_set_scene_area_lights).
-template <bool SC = false, bool SO = false>
+// radius > 0 (rt_set_scene_area_lights).  LE (with SC): the lens twins of the scatter or area-light kernels (rt_device.h: LENS),
+// for a launch with an aperture > 0 (rt_set_lens).
+template <bool SC = false, bool SO = false, bool LE = false>
 const void *refraction_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
 {
     if (lanes) {
-        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC, SO>;
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC, SO>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC, SO>);
+        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC, SO, LE>;
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC, SO, LE>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC, SO, LE>);
     }
     if (lattice) {
-        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC, SO>;
-        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC, SO>;
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC, SO>;
+        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC, SO, LE>;
+        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC, SO, LE>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC, SO, LE>;
     }
     if (norec && wpw == 4 && !aa)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC, SO>;
+        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC, SO, LE>;
     if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC, SO>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC, SO>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC, SO>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC, SO> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC, SO>);
+        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC, SO, LE>)
+                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC, SO, LE>);
+    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC, SO, LE>)
+              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC, SO, LE>);
 }
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
@@ -367,13 +373,18 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
     k.amb = p->amb; k.lamb = p->lamb;
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
+    // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
+    // the lens travels in its place, by value with this launch
+    const bool lens = ctx->lens_a > 0.0 && ctx->M > 0;
+    if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
     const size_t table = (size_t)(ctx->L + 1) * (rt::padS(ctx->S, ctx->NC) + rt::pad4(ctx->NC)) * rt::CULL_STRIDE * sizeof(float);
     k.anchors = (table <= (size_t)rt::MAX_CULL_TABLE_BYTES) ? ctx->L + 1 : 0;
-    const double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
+    double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
+    if (lens) { const double e = std::sqrt(cam2) + ctx->lens_a; cam2 = e * e; }   // (primary rays start on the lens, |L - cam| <= a)
     k.extent2 = (float)(1.0001 * (cam2 > ctx->scene_extent2 ? cam2 : ctx->scene_extent2));
-    {   // every ray origin of the launch lies within |cam| + 999 (depth + 1) of the world origin
+    {   // every ray origin of the launch lies within |cam| (+ a with a lens) + 999 (depth + 1) of the world origin
         const double reach = std::sqrt(cam2) + 999.0 * (p->depth + 1) + std::sqrt(ctx->scene_extent2);
         k.floor_anch = (float)(0x1p-39 * reach * reach);
     }
@@ -448,10 +459,13 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots; with a rough row
     // their scatter twins, with rows of 6 and two more slots)
     // (a scene with a light radius > 0: the scatter kernels' area-light twins, rows of 6, one more slot and n behind the block)
+    // (a launch with a lens: the lens twins of the scatter or area-light kernels, rows of 6 (the scene's own block or its padded
+    // copy, rt_ctx::lens_mat) and no more slots)
+    const bool lens = ctx->M > 0 && ctx->lens_a > 0.0;
     const bool soft = ctx->M > 0 && ctx->soft_n > 0;
-    const bool scat = ctx->M > 0 && ctx->mat_cols == 6;
-    const bool refr = ctx->M > 0 && ctx->mat_cols >= 5;
-    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, ctx->mat_cols, soft);   // (the block is in the launch's scene buffer: rt::mat_offset)
+    const bool scat = ctx->M > 0 && (ctx->mat_cols == 6 || lens);
+    const bool refr = ctx->M > 0 && (ctx->mat_cols >= 5 || lens);
+    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, lens ? 6 : ctx->mat_cols, soft);   // (the block is in the launch's scene buffer: rt::mat_offset)
     auto per_cu = [&](bool nr) {
         const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr, scat, soft);
         if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
@@ -462,12 +476,22 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
     const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr, scat, soft);
-    const void *fn = soft ? refraction_variant<true, true>(lanes, aa, lattice, park, wpw, norec)
+    const void *fn = lens ? (soft ? refraction_variant<true, true, true>(lanes, aa, lattice, park, wpw, norec)
+                                  : refraction_variant<true, false, true>(lanes, aa, lattice, park, wpw, norec))
+                   : soft ? refraction_variant<true, true>(lanes, aa, lattice, park, wpw, norec)
                    : scat ? refraction_variant<true>(lanes, aa, lattice, park, wpw, norec)
                    : refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
                    : matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
                           : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (soft) {
+    if (lens) {
+        if (lds > 48 * 1024 && lds > ctx->lens_lds_limit_set[soft]) {
+            for (int v = 0; v < 64; ++v)
+                RT_HIP(ctx, hipFuncSetAttribute(soft ? refraction_variant<true, true, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32)
+                                                     : refraction_variant<true, false, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            ctx->lens_lds_limit_set[soft] = lds;
+        }
+    } else if (soft) {
         if (lds > 48 * 1024 && lds > ctx->soft_lds_limit_set) {
             for (int v = 0; v < 64; ++v)
                 RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
@@ -869,6 +893,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                 return fail(ctx, RT_ERR_BAD_ARG, "plane_material[" + std::to_string(k) + "] outside 0..M-1");
     }
     int nclusters = 0;
+    size_t lens_off = 0;
     try {
         // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
         // are evaluated here, once, in float32: r*r (intersections.py:21), the plane shading normal
@@ -913,7 +938,10 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         }
         nclusters = NC;
         const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
-        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols, soft), 0.0);
+        // the lens kernels are scatter kernels: a table of 3 or 5 columns gets a copy padded to six (trans 0, ior 1, rough 0)
+        // behind its block, with the same ids; a 6-column one (an area-light scene's included) serves them as it is
+        lens_off = (M > 0 && cols < 6) ? mat_off + rt::mat_doubles(M, S, P, cols, soft) : mat_off;
+        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols, soft) + ((M > 0 && cols < 6) ? rt::mat_doubles(M, S, P, 6) : 0), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -982,6 +1010,13 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
             for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
             if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
             if (soft) rec.back() = (double)shadow_samples;          // (rt::mat_doubles: the block's last double)
+            if (lens_off != mat_off) {
+                static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+                rec[lens_off] = (double)M;
+                for (int m = 0; m < M; ++m)
+                    for (int i = 0; i < 6; ++i) rec[lens_off + 1 + (size_t)6 * m + i] = i < cols ? materials[(size_t)cols * m + i] : pad[i];
+                if (!ids.empty()) std::memcpy(rec.data() + lens_off + 1 + (size_t)6 * M, ids.data(), ids.size() * sizeof(int32_t));
+            }
         }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
@@ -1018,6 +1053,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
     ctx->M = M;
     ctx->mat_cols = cols;
     ctx->soft_n = soft ? shadow_samples : 0;
+    ctx->lens_mat = (long long)lens_off;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;
@@ -1035,6 +1071,21 @@ int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9])
     std::memcpy(ctx->cam_o, origin, sizeof ctx->cam_o);
     std::memcpy(ctx->cam_R, rotation, sizeof ctx->cam_R);
     ctx->have_cam = true;
+    ctx->epoch++;
+    return RT_OK;
+}
+
+int rt_set_lens(rt_ctx *ctx, double aperture, double focus_distance)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!(std::isfinite(aperture) && aperture >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "aperture must be finite and >= 0");
+    if (!(std::isfinite(focus_distance) && focus_distance > 0.0))
+        return fail(ctx, RT_ERR_BAD_ARG, "focus_distance must be finite and > 0");
+    // the same lens again changes nothing (as rt_set_camera), nor does a new focus without an aperture (the pinhole camera
+    // ignores it); a new lens starts dispatch-order measuring again
+    if (aperture == ctx->lens_a && (focus_distance == ctx->lens_f || aperture == 0.0)) { ctx->lens_f = focus_distance; return RT_OK; }
+    ctx->lens_a = aperture;
+    ctx->lens_f = focus_distance;
     ctx->epoch++;
     return RT_OK;
 }

@@ -132,7 +132,14 @@ struct KParams {
     double cam_o[3];
     double cam_R[9];
     double amb, lamb;
-    double refl_pow[16];
+    union {
+        double refl_pow[16];   // kernels without a material table: refl ** (b+1) (the MAT kernels weigh bounces with the table)
+        struct {               // LENS kernels (MAT kernels: refl_pow is unused there), rt_set_lens
+            double aperture;   // lens radius a > 0
+            double focus;      // distance f of the plane of focus along R e_x
+            long long mat;     // offset (doubles) in `scene` of the material block with rows of 6 (mat_offset, or a padded copy)
+        } lens;
+    };
 };
 
 // Division of n < 2^31 by a launch constant d without the backend's 20-instruction sequence (v_rcp_iflag_f32 and two
@@ -333,11 +340,13 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // SOFT (area-light kernels, rt_set_scene_area_lights with a radius > 0; SCAT too): one more slot, LKEY, the sample's pre-hashed
 // light key (soft_key), read inside the light loop where each shadow sample's point on its light is formed (soft_light_point);
 // nsh is the scene's shadow_samples n (the last double of the material block).
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false> struct MatState {
-    static constexpr bool refr = false, scat = false, soft = false;
+// LENS (depth-of-field kernels, rt_set_lens with an aperture > 0; SCAT too): no slot; the primary ray does not start at the
+// camera, so trace 0's closest-hit query takes the origin form of the cull (trace_bounce).
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false, bool LENS = false> struct MatState {
+    static constexpr bool refr = false, scat = false, soft = false, lens = false;
 };
-template <int WSLOT, bool FRESH, bool REFR, bool SCAT, bool SOFT> struct MatState<true, WSLOT, FRESH, REFR, SCAT, SOFT> {
-    static constexpr bool refr = REFR, scat = SCAT, soft = SOFT;
+template <int WSLOT, bool FRESH, bool REFR, bool SCAT, bool SOFT, bool LENS> struct MatState<true, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> {
+    static constexpr bool refr = REFR, scat = SCAT, soft = SOFT, lens = LENS;
     static constexpr int COLS = SCAT ? 6 : (REFR ? 5 : 3);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
@@ -1336,7 +1345,9 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
     double t = 999.0; int idx = -1, type = HIT_NONE;
     cnt.closest(alive);
     RT_MARK(11);
-    if (alive) closest_hit<MODE>(lds, p, o, d, anchor, t, idx, type);   // :53 (idle lanes masked off)
+    // (LENS: a primary ray starts on the lens, not at the camera: no anchor for its closest hit.  `anchor` itself still says
+    // which trace this is for the shadow rays below.)
+    if (alive) closest_hit<MODE>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
     alive = alive && (type != HIT_NONE);                                      // :56-57
     cnt.hit(alive);
     if (alive) {
@@ -1458,7 +1469,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 }
 
 
-// trace.py:115-133.  Bounce 0 rays all start at the camera (cull anchor 0); later bounces have none.
+// trace.py:115-133.  Bounce 0 rays all start at the camera (cull anchor 0; LENS kernels: on the lens, none); later bounces have none.
 // MAT (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
 // of the surfaces the ray was reflected off, in place of p.refl_pow[b-1].  W stops changing where the path ends: the missed
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
@@ -1542,6 +1553,42 @@ __device__ __forceinline__ unsigned jitter_hash(unsigned x, unsigned y, unsigned
     h = (h ^ s) * 0x27D4EB2Fu; h ^= h >> 15;
     h *= 0x165667B1u; h ^= h >> 13;
     return h;
+}
+
+// The lens hash (rt_set_lens, mi355rt.h): jitter_hash(X, Y, (s*8 + j)*2 + c, seed ^ 0x1E45D0F5), the bit pattern s << 4 | j << 1 | c.
+// lens_key is its first two rounds on (X, Y) with s folded in (as scatter_key); scatter_hash finishes it for t = j << 1 | c.
+__device__ __forceinline__ unsigned lens_key(unsigned x, unsigned y, unsigned s, unsigned seed)
+{
+    unsigned h = (seed ^ 0x1E45D0F5u) ^ 0x9E3779B9u;
+    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
+    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
+    return h ^ (s << 4);
+}
+
+// The thin-lens primary ray (o, d) of sample (X, Y, s) through the pixel point P (rt_set_lens, mi355rt.h), float64 without
+// fused multiply-add: v = R P as primary_dir forms it, the focal point F = O + (f / P.x) v (linear_comb(O, v, 1.0, f / P.x);
+// 1.0*O is exact), u the first of eight hashed candidates in the unit disk (u_c and u.u exact) or (0, 0),
+// o = (O + (a u0) ey) + (a u1) ez with ey, ez the columns 1 and 2 of R, d = normalize(F - o).
+__device__ __forceinline__ void lens_ray(const KParams &p, unsigned x, unsigned y, unsigned s, const V3 &P, V3 &o, V3 &d)
+{
+    const V3 v{p.cam_R[0] * P.x + p.cam_R[1] * P.y + p.cam_R[2] * P.z,
+               p.cam_R[3] * P.x + p.cam_R[4] * P.y + p.cam_R[5] * P.z,
+               p.cam_R[6] * P.x + p.cam_R[7] * P.y + p.cam_R[8] * P.z};
+    const double t = p.lens.focus / P.x;
+    const V3 F{p.cam_o[0] + t * v.x, p.cam_o[1] + t * v.y, p.cam_o[2] + t * v.z};
+    const unsigned key = lens_key(x, y, s, p.seed);
+    double u0 = 0.0, u1 = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < 8; ++j) {
+        const unsigned tj = (unsigned)j << 1;
+        const double c0 = (double)(scatter_hash(key, tj) >> 8) * 0x1p-23 + (0x1p-24 - 1.0);
+        const double c1 = (double)(scatter_hash(key, tj | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0);
+        if (c0 * c0 + c1 * c1 < 1.0) { u0 = c0; u1 = c1; break; }
+    }
+    const double a0 = p.lens.aperture * u0, a1 = p.lens.aperture * u1;
+    o = V3{(p.cam_o[0] + a0 * p.cam_R[1]) + a1 * p.cam_R[2], (p.cam_o[1] + a0 * p.cam_R[4]) + a1 * p.cam_R[5],
+           (p.cam_o[2] + a0 * p.cam_R[7]) + a1 * p.cam_R[8]};
+    d = normalize3(V3{F.x - o.x, F.y - o.y, F.z - o.z});                     // common.py:28-32 of vector_difference(o, F)
 }
 
 // common.py:52-57: min(max(0, int(round(c))), 255), round half to even (v_rndne_f64).
@@ -1747,11 +1794,12 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
 
 // The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
 // SOFT: nsh is the scene's shadow_samples (the block's last double).
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false>
-__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT> mat_state(double *matl, int M, int nsh = 1)
+template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false, bool LENS = false>
+__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> mat_state(double *matl, int M, int nsh = 1)
 {
     typedef __attribute__((address_space(3))) double lds_d;
-    if constexpr (MAT) return MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT>{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT>::COLS * M), nsh};
+    typedef MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> MS;
+    if constexpr (MAT) return MS{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MS::COLS * M), nsh};
     else return {};
 }
 
@@ -1761,8 +1809,9 @@ __device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT> mat_sta
 // REFR (with MAT only): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
 // SCAT (with REFR only): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
 // SOFT (with SCAT only): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
+// LENS (with SCAT only): the camera has an aperture (rt_set_lens): thin-lens primary rays (lens_ray).
 template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false, bool SCAT = false,
-          bool SOFT = false>
+          bool SOFT = false, bool LENS = false>
 #ifndef RT_W_PARK
 #define RT_W_PARK 7
 #endif
@@ -1783,6 +1832,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     static_assert(MAT || !REFR, "refraction kernels are material kernels");
     static_assert(REFR || !SCAT, "scatter kernels are refraction kernels");
     static_assert(SCAT || !SOFT, "area-light kernels are scatter kernels");
+    static_assert(SCAT || !LENS, "lens kernels are scatter kernels");
     int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR, SCAT, SOFT) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
@@ -1814,7 +1864,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
 #endif
     int nmat = 0, nsh = 1;
     if constexpr (MAT) {
-        const double *msrc = p.scene + mat_offset(p.S, p.P, p.L, p.NC);
+        // (LENS: the block with rows of 6 the host names, a padded copy behind the scene's own for a table of 3 or 5 columns)
+        const double *msrc = p.scene + (LENS ? (size_t)p.lens.mat : mat_offset(p.S, p.P, p.L, p.NC));
         nmat = (int)msrc[0];
         const int nm = (int)mat_doubles(nmat, p.S, p.P, SCAT ? 6 : (REFR ? 5 : 3), SOFT);
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
@@ -1882,17 +1933,22 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
     constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
-    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT, SOFT>(matl, nmat, nsh);
+    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT, SOFT, LENS>(matl, nmat, nsh);
     // SCAT: the scatter key of a sample is (X, Y, s) on the half-pixel lattice, pixel centres at (2x, 2y), absolute columns
     // (the lattice kernels' own coordinates); s the stochastic sample, else 0
     // SOFT: the light key (soft_key) of the same (X, Y, s)
+    // LENS: the primary ray is lens_ray's for the same (X, Y, s); its origin is the lane's own
     const unsigned sseed = SCAT ? p.seed : 0u;
     double R, G, B;
     if constexpr (!AA) {
         unsigned key = 0u, lkey = 0u;
         if constexpr (SCAT) key = LAT ? scatter_key((unsigned)xc, (unsigned)yc, 0u, sseed) : scatter_key(2u * xc, 2u * yc, 0u, sseed);
         if constexpr (SOFT) lkey = LAT ? soft_key((unsigned)xc, (unsigned)yc, 0u, sseed) : soft_key(2u * xc, 2u * yc, 0u, sseed);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, o, primary_dir(p, LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc)), cnt, ms, key, lkey);   // kernels.py:19-26
+        const V3 P0 = LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc);
+        V3 ro = o, rd;
+        if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
+        else rd = primary_dir(p, P0);
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -1910,6 +1966,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             const V3 Pp = pixel_P(p, xc, yc);                                 // :19
             V3 Pt = Pp;
             unsigned key = 0u, lkey = 0u;
+            unsigned lx = 2u * xc, ly = 2u * yc;                              // LENS: the sample's (X, Y)
             if constexpr (SCAT) key = scatter_key(2u * xc, 2u * yc, stoch ? (unsigned)tap : 0u, sseed);
             if constexpr (SOFT) lkey = soft_key(2u * xc, 2u * yc, stoch ? (unsigned)tap : 0u, sseed);
             if (stoch) {
@@ -1924,8 +1981,12 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
                 Pt = V3{0.5 * Pp.x + 0.5 * Pn.x, 0.5 * Pp.y + 0.5 * Pn.y, 0.5 * Pp.z + 0.5 * Pn.z};   // :43-50
                 if constexpr (SCAT) key = scatter_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
                 if constexpr (SOFT) lkey = soft_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
+                if constexpr (LENS) { lx = (unsigned)(2 * xc + ddx); ly = (unsigned)(2 * yc + ddy); }
             }
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, o, primary_dir(p, Pt), cnt, ms, key, lkey);   // :26 / :56
+            V3 ro = o, rd;
+            if constexpr (LENS) lens_ray(p, lx, ly, stoch ? (unsigned)tap : 0u, Pt, ro, rd);
+            else rd = primary_dir(p, Pt);
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

@@ -56,6 +56,16 @@ class _PinnedBlock:
             pass
 
 
+def check_lens(aperture, focus_distance):
+    """(aperture, focus_distance) as floats, or ValueError: aperture finite and >= 0, focus_distance finite and > 0."""
+    a, f = float(aperture), float(focus_distance)
+    if not (np.isfinite(a) and a >= 0.0):
+        raise ValueError(f"aperture must be finite and >= 0, not {aperture!r}")
+    if not (np.isfinite(f) and f > 0.0):
+        raise ValueError(f"focus_distance must be finite and > 0, not {focus_distance!r}")
+    return a, f
+
+
 class Renderer:
     def __init__(self, device=0, lib=None):
         self.serial = next(_serials)     # process-unique (id() values are reused after garbage collection)
@@ -161,6 +171,14 @@ class Renderer:
         r = np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
         dp = C.POINTER(C.c_double)
         self._check(self._lib.rt_set_camera(self._ctx, o.ctypes.data_as(dp), r.ctypes.data_as(dp)))
+        self.generation["camera"] += 1
+
+    def set_lens(self, aperture, focus_distance):
+        """Depth of field (rt_set_lens): a thin lens of radius `aperture` (finite, >= 0; 0 is the pinhole camera) focused at
+        `focus_distance` (finite, > 0) along the camera's forward axis, as Camera.lens returns them.  Applies to later launches;
+        an aperture > 0 needs a scene with a material table."""
+        a, f = check_lens(aperture, focus_distance)
+        self._check(self._lib.rt_set_lens(self._ctx, a, f))
         self.generation["camera"] += 1
 
     def set_raygen(self, w, h, px, y0, dy, z0, dz):

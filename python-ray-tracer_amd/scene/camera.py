@@ -22,16 +22,36 @@ class PixelGrid(np.ndarray):
 
 
 class Camera:
-    def __init__(self, resolution, position, euler, fov=45.0, true_aspect=False):
+    """aperture, focus_distance: a thin lens (depth of field, Renderer.set_lens): its radius in world units (0: the pinhole
+    camera of the reference) and the distance of the plane of sharp focus along the forward axis rotation[:, 0]."""
+
+    def __init__(self, resolution, position, euler, fov=45.0, true_aspect=False, aperture=0.0, focus_distance=1.0):
         self.resolution = resolution
         self._position = position
         self.rotation = euler_rotation(euler[0], euler[1], euler[2])
         self.field_of_view = fov
         self.true_aspect = true_aspect      # False: the reference's AR = int(w/h); True: AR = w/h
+        a, f = float(aperture), float(focus_distance)
+        if not (np.isfinite(a) and a >= 0.0):
+            raise ValueError(f"aperture must be finite and >= 0, not {aperture!r}")
+        if not (np.isfinite(f) and f > 0.0):
+            raise ValueError(f"focus_distance must be finite and > 0, not {focus_distance!r}")
+        self.aperture, self.focus_distance = a, f
 
     @property
     def position(self):
         return np.array(self._position)
+
+    @property
+    def lens(self):
+        """(aperture, focus_distance), the arguments of Renderer.set_lens."""
+        return self.aperture, self.focus_distance
+
+    def focus_on(self, point):
+        """The focus_distance that puts `point` in focus: its distance from the camera along the forward axis,
+        dot(point - position, rotation[:, 0])."""
+        d = np.asarray(point, dtype=np.float64).reshape(3) - np.asarray(self.position, dtype=np.float64).reshape(3)
+        return float(np.dot(d, np.asarray(self.rotation, dtype=np.float64)[:, 0]))
 
     def raygen(self):
         """(px, y0, dy, z0, dz).  AR = int(width/height) truncates as the reference does

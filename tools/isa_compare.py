@@ -9,14 +9,15 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
     kernel's own symbol renumbered, must be identical in the working tree;
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
 A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT, REFR,
-SCAT and SOFT parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction, scatter or
-area-light kernels match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without
-refraction kernels, the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels, and the scatter
-kernels (SCAT = true, SOFT = false) those of a tree without area-light kernels.  Kernels of the working tree that the base does
-not have are listed as NEW.
+SCAT, SOFT and LENS parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction, scatter,
+area-light or lens kernels match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without
+refraction kernels, the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels, the scatter
+kernels (SCAT = true, SOFT = false) those of a tree without area-light kernels, and the area-light kernels (SOFT = true,
+LENS = false) those of a tree without lens kernels.  Kernels of the working tree that the base does not have are listed as NEW.
 --twins also prints each material kernel (MAT = true) next to its default twin, each refraction kernel (REFR = true) next to
 its material twin, each scatter kernel (SCAT = true) next to its refraction twin and each area-light kernel (SOFT = true) next
-to its scatter twin.  Exit status 1 if any kernel differs.
+to its scatter twin, and each lens kernel (LENS = true) next to its scatter or area-light twin.  Exit status 1 if any kernel
+differs.
 """
 import argparse
 import os
@@ -38,12 +39,14 @@ def build(tree):
 
 def key(name):
     """Kernel symbol -> (kernel, template arguments without trailing false ones past the sixth), and its family:
-    "" (default), "mat" (MAT = true), "refr" (REFR = true), "scat" (SCAT = true) or "soft" (SOFT = true)."""
+    "" (default), "mat" (MAT = true), "refr" (REFR = true), "scat" (SCAT = true), "soft" (SOFT = true), "lens" (LENS = true,
+    SOFT = false) or "lens_soft" (LENS = true, SOFT = true)."""
     m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
     if not m:
         return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
-    fam = ("soft" if len(args) >= 10 and args[9] == "1" else "scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
+    lens = len(args) >= 11 and args[10] == "1"
+    fam = ("lens_soft" if lens and args[9] == "1" else "lens" if lens else "soft" if len(args) >= 10 and args[9] == "1" else "scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
            "mat" if len(args) >= 7 and args[6] == "1" else "")
     return (m.group(1),) + tuple(args[:6]), fam
 
@@ -111,9 +114,10 @@ def main():
     if a.twins:
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
         for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"),
-                                 ("scat", "refr", "scatter kernel"), ("soft", "scat", "area-light kernel")):
+                                 ("scat", "refr", "scatter kernel"), ("soft", "scat", "area-light kernel"),
+                                 ("lens", "scat", "lens kernel"), ("lens_soft", "soft", "lens area-light kernel")):
             print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   "
-                  f"{dict(mat='material', refr='refraction', scat='scatter').get(twin, 'default')} twin")
+                  f"{dict(mat='material', refr='refraction', scat='scatter', soft='area-light').get(twin, 'default')} twin")
             for (k, f_), n in sorted(new_by_key.items(), key=str):
                 if f_ != fam:
                     continue
