@@ -14,6 +14,10 @@ SO = os.path.join(HERE, "librt_oracle.so")
 
 FLAG_TYPED_BIAS = 1
 
+# Deliberately wrong restatements of the feature path (rt_oracle.c ORC_WRONG_*): test-only, for showing that the fixtures
+# catch each of them (tests/test_oracle_features.py).
+WRONG = dict(key_pixel=1, pow_weight=2, soft_i_major=4, lamb_whole=8, tir_far=16, no_bounce=32, focus_f=64, no_absorb=128)
+
 _lib = None
 
 
@@ -27,6 +31,12 @@ def build(force=False):
 class _RayGen(C.Structure):
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("pixel_loc", C.c_void_p),
                 ("px", C.c_double), ("y0", C.c_double), ("dy", C.c_double), ("z0", C.c_double), ("dz", C.c_double)]
+
+
+class _Features(C.Structure):
+    _fields_ = [("M", C.c_int), ("ncols", C.c_int), ("materials", C.c_void_p), ("sphere_material", C.c_void_p),
+                ("plane_material", C.c_void_p), ("light_radius", C.c_void_p), ("shadow_samples", C.c_int),
+                ("aperture", C.c_double), ("focus", C.c_double), ("wrong", C.c_int)]
 
 
 def lib():
@@ -55,6 +65,10 @@ def lib():
                                         C.c_double, C.c_double, dp, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]
         L.orc_render_pixels.restype = C.c_int
+        L.orc_render_ex.argtypes = list(L.orc_render.argtypes) + [C.POINTER(_Features)]
+        L.orc_render_ex.restype = C.c_int
+        L.orc_render_pixels_ex.argtypes = list(L.orc_render_pixels.argtypes) + [C.POINTER(_Features)]
+        L.orc_render_pixels_ex.restype = C.c_int
         L.orc_max_threads.restype = C.c_int
         _lib = L
     return _lib
@@ -148,14 +162,47 @@ def sample(spheres, lights, planes, o, d, amb, lamb, refl, depth, flags=0):
     return out
 
 
+def _features(S, L, P, materials, light_radius, shadow_samples, lens, wrong):
+    """(struct, arrays it points into) for the keyword arguments of render / render_pixels, or (None, None) when none is given:
+    then the plain entry points run."""
+    if materials is None and light_radius is None and lens is None and not wrong:
+        return None, None
+    fe = _Features()
+    keep = []
+    if materials is not None:
+        table, sid, pid = materials
+        table = _d(table)
+        table = table.reshape(-1, table.shape[-1]) if table.ndim == 2 else table.reshape(-1, 3)
+        sid = np.ascontiguousarray(sid, dtype=np.int32).reshape(-1)
+        pid = np.ascontiguousarray(pid, dtype=np.int32).reshape(-1)
+        assert sid.shape == (S,) and pid.shape == (P,)
+        keep += [table, sid, pid]
+        fe.M, fe.ncols = table.shape
+        fe.materials, fe.sphere_material, fe.plane_material = table.ctypes.data, sid.ctypes.data, pid.ctypes.data
+    if light_radius is not None:
+        rad = _f(light_radius).reshape(-1)
+        assert rad.shape == (L,)
+        keep.append(rad)
+        fe.light_radius = rad.ctypes.data if L else None
+    fe.shadow_samples = int(shadow_samples)
+    fe.aperture, fe.focus = (0.0, 1.0) if lens is None else (float(lens[0]), float(lens[1]))
+    fe.wrong = int(wrong)
+    return fe, keep
+
+
 def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, depth, aa=False, *,
            pixel_loc=None, raygen=None, x0=0, x1=None, flags=0, want=("u8", "f64"), nthreads=0, refl_pow=None,
-           spp=0, seed=1):
+           spp=0, seed=1, materials=None, light_radius=None, shadow_samples=1, lens=None, wrong=0):
     """Run the restated `render` (kernels.py:6-73) for columns [x0,x1).
 
     raygen = (px, y0, dy, z0, dz) closed form, or pixel_loc = explicit float64 (3,w,h) array.
     Returns dict with any of 'u8' (3,w,h) uint8 [R,B,G], 'f64' (3,w,h), 'f32' (3,w,h) and 'counters'.
     Columns outside [x0,x1) are left zero.
+
+    The features of include/mi355rt.h (rt_oracle.c orc_render_ex): materials = (table (M,3|5|6) float64, sphere ids (S,),
+    plane ids (P,)) as rt_set_scene_materials_scatter takes them (amb, lamb and refl are then ignored); light_radius (L,)
+    and shadow_samples as rt_set_scene_area_lights; lens = (aperture, focus_distance) as rt_set_lens.  wrong: WRONG bits
+    (test-only).  Input the header refuses raises ValueError.
     """
     L = lib()
     x1 = w if x1 is None else x1
@@ -177,12 +224,15 @@ def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, 
     f64 = np.zeros((3, w, h), np.float64) if "f64" in want else None
     f32 = np.zeros((3, w, h), np.float32) if "f32" in want else None
     cnt = (C.c_longlong * 3)()
-    rc = L.orc_render(C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
-                      _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp), int(flags),
-                      int(x0), int(x1),
-                      u8.ctypes.data if u8 is not None else None,
-                      f64.ctypes.data if f64 is not None else None,
-                      f32.ctypes.data if f32 is not None else None, cnt, int(nthreads), int(seed) & 0xFFFFFFFF)
+    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong)
+    args = (C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
+            _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp), int(flags),
+            int(x0), int(x1),
+            u8.ctypes.data if u8 is not None else None,
+            f64.ctypes.data if f64 is not None else None,
+            f32.ctypes.data if f32 is not None else None, cnt, int(nthreads), int(seed) & 0xFFFFFFFF)
+    rc = L.orc_render(*args) if fe is None else L.orc_render_ex(*args, C.byref(fe))
+    del fkeep
     if rc != 0:
         raise ValueError("orc_render: bad arguments")
     if u8 is not None: out["u8"] = u8
@@ -193,8 +243,9 @@ def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, 
 
 
 def render_pixels(w, h, coords, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, depth, aa=False, *,
-                  pixel_loc=None, raygen=None, flags=0, nthreads=0, refl_pow=None, spp=0, seed=1):
-    """The same per-pixel path for an explicit (n,2) list of (x,y) pixels.
+                  pixel_loc=None, raygen=None, flags=0, nthreads=0, refl_pow=None, spp=0, seed=1, materials=None,
+                  light_radius=None, shadow_samples=1, lens=None, wrong=0):
+    """The same per-pixel path for an explicit (n,2) list of (x,y) pixels (the feature keywords of render()).
     Returns (u8 (n,3) in stored order [R,B,G], f64 (n,3) = pre-clip (R,G,B))."""
     L = lib()
     rg = _RayGen()
@@ -214,9 +265,12 @@ def render_pixels(w, h, coords, cam_origin, cam_rot, spheres, lights, planes, am
     n = co.shape[0]
     u8 = np.zeros((n, 3), np.uint8)
     f64 = np.zeros((n, 3), np.float64)
-    rc = L.orc_render_pixels(C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
-                             _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp),
-                             int(flags), co.ctypes.data, n, u8.ctypes.data, f64.ctypes.data, int(nthreads), int(seed) & 0xFFFFFFFF)
+    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong)
+    args = (C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
+            _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp),
+            int(flags), co.ctypes.data, n, u8.ctypes.data, f64.ctypes.data, int(nthreads), int(seed) & 0xFFFFFFFF)
+    rc = L.orc_render_pixels(*args) if fe is None else L.orc_render_pixels_ex(*args, C.byref(fe))
+    del fkeep
     if rc != 0:
         raise ValueError("orc_render_pixels: bad arguments")
     return u8, f64

@@ -34,8 +34,9 @@ def test_in_range_division_and_sqrt_are_bit_identical(tmp_path):
 
 def test_oracle_under_asan_ubsan(tmp_path):
     """the CPU restatement under AddressSanitizer + UndefinedBehaviorSanitizer (the GPU side cannot run
-    sanitizers on this pool).  Two scenes (a golden's, and an empty one) through every oracle entry point; the
-    sanitized build must finish without a report and produce the bytes of the regular build."""
+    sanitizers on this pool).  Two scenes (a golden's, and an empty one) through every oracle entry point, the feature
+    path's (orc_render_ex, orc_render_pixels_ex) included; the sanitized build must finish without a report and produce the
+    bytes of the regular build."""
     import struct
     import numpy as np
     from conftest import load_frame, raygen_closed_form
@@ -59,6 +60,13 @@ def test_oracle_under_asan_ubsan(tmp_path):
             f.write(np.asarray([0.1, 0.5, 0.45] + [0.45 ** (k + 1) for k in range(depth)], np.float64).tobytes())
             for a in (sp, li, pl):
                 f.write(np.ascontiguousarray(a, np.float32).tobytes())
+            # the feature path: a 6-column table with glass and rough rows, area lights with radii 0 and > 0, n = 3, a lens
+            table = np.array([[0.05, 0.6, 0.5, 0.0, 1.0, 0.0], [0.0, 0.1, 0.0, 0.9, 1.5, 0.0], [-0.02, 0.5, 0.7, 0.0, 1.0, 0.4]])
+            f.write(struct.pack("3i", table.shape[0], table.shape[1], 3))
+            f.write(table.tobytes())
+            f.write((np.arange(sp.shape[1]) % 3).astype(np.int32).tobytes()); f.write((np.arange(pl.shape[1]) % 3).astype(np.int32).tobytes())
+            f.write((0.4 * (np.arange(li.shape[1]) % 2)).astype(np.float32).tobytes())
+            f.write(np.array([0.1, 3.0]).tobytes())
         outs = []
         for exe in (plain, san):
             out = str(tmp_path / (os.path.basename(exe) + f"{i}.out"))
@@ -66,6 +74,6 @@ def test_oracle_under_asan_ubsan(tmp_path):
             assert res.returncode == 0 and "ok" in res.stdout, res.stdout + res.stderr
             assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
             outs.append(open(out, "rb").read())
-        assert outs[0] == outs[1] and len(outs[0]) > 3 * w * h * 5
+        assert outs[0] == outs[1] and len(outs[0]) > 3 * w * h * 10
         if i == 0:
             assert any(outs[0][:3 * w * h])                           # the golden's scene renders something

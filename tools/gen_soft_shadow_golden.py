@@ -291,6 +291,28 @@ def main():
             sr = gg.sph(gg.DEFAULT_SPHERES[:3] + [([2.5, -1.7, 3.0], 0.12, gg.GREY)])
             c("rim_48_d2", 48, 48, sr, L3, [0.5, 0.0, 0.0], 4, P1, *CAM, MATTE_TABLE, [0, 1, 2, 0], [3], 2, seed=6,
               point=True)
+        if want("many_lights"):   # L = 12 (light indices m up to 11), zero and nonzero radii mixed, n = 16
+            L12 = gg.lig(gg.DEFAULT_LIGHTS + [[0.0, -3.0, 2.5], [0.0, 3.0, 2.5], [4.0, -1.0, 1.5], [-1.0, 0.0, 4.0], [3.0, 3.0, 0.8],
+                                              [1.0, -1.5, 3.5], [6.0, 2.0, 2.0], [-0.5, 2.0, 1.2], [2.0, 0.0, 5.0]])
+            R12 = [0.5, 0.0, 0.3, 0.0, 0.6, 0.2, 0.0, 0.4, 0.25, 0.0, 0.35, 0.5]
+            c("many_lights_24_n16_d2", 24, 24, S6, L12, R12, 16, P1, *CAM, MATTE_TABLE, [0, 1, 2, 0, 1, 2], [3], 2, seed=15)
+        if want("table256"):      # a 256-row table with ids over every row, 324 spheres (clustered, lane-owned traversal)
+            rng = np.random.default_rng(256)
+            T = np.zeros((256, 6))
+            T[:, 0], T[:, 1], T[:, 2], T[:, 4] = rng.uniform(0, 0.15, 256), rng.uniform(0.2, 0.9, 256), rng.uniform(0, 0.9, 256), 1.0
+            T[5::7, 2], T[5::7, 3], T[5::7, 4] = 0.0, 0.85, 1.5                       # glass rows
+            T[3::7, 5] = 0.3                                                          # rough rows
+            G = grid(18, 357)
+            c("table256_s324_32x24_d3", 32, 24, G, L3, R3, 2, P1, *CAM, T, [(i * 37) % 256 for i in range(G.shape[1])], [255], 3,
+              seed=17)
+        if want("deep16"):        # depth 16 between a mirror floor and a mirror ceiling (refl = 1), glass and rough spheres
+            DEEP = [(0.0, 0.1, 0.0, 0.9, 1.5, 0.0), (0.02, 0.3, 1.0, 0.0, 1.0, 0.0), (0.0, 0.4, 0.9, 0.0, 1.0, 0.2),
+                    (0.1, 0.6, 0.2, 0.0, 1.0, 0.0), (0.0, 0.3, 1.0, 0.0, 1.0, 0.05)]
+            P2 = gg.pla([gg.DEFAULT_PLANE, ([0, 0, 3.2], [0, 0.1, -1], gg.GREY)])
+            c("deep16_32_d16", 32, 32, S6, L3, [0.4, 0.0, 0.5], 2, P2, *CAM, DEEP, [1, 0, 2, 1, 0, 1], [4, 1], 16, seed=19)
+        if want("spp64"):         # 64 stochastic samples (the key's s up to 63) on a small frame
+            c("spp64_16x12_d2", 16, 12, S8, L3, R3, 2, P1, *CAM, DEFAULT_TABLE, [0, 1, 2, 3, 4, 5, 3, 5], [6], 2, aa=2, spp=64,
+              seed=23)
         if want("c4"):        # 64 spheres (clustered), 3840x2160 on the sub32 lattice
             cs = [(x, y) for x in range(16, 3840, 32) for y in range(16, 2160, 32)]
             c("c4_s64_d5_sub32", 3840, 2160, grid(8, 355), L3, R3, 2, P1, *CAM, GRID_TABLE, grid_ids(64), [6], 5, coords=cs,
