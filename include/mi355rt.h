@@ -296,7 +296,12 @@ int rt_set_lens(rt_ctx *ctx, double aperture, double focus_distance);
 
 /* The pixel grid of Camera.generate_pixel_locations() (scene/camera.py:18-26) in closed form:
  *   pixel_loc[:, x, y] = (px, x*dy + y0, y*dz + z0)      (one multiply, one add, as np.mgrid does)
- * The kernel generates primary rays from this; no (3,w,h) array is read.   replaces main.py:29 */
+ * The kernel generates primary rays from this; no (3,w,h) array is read.   replaces main.py:29
+ * Frame size (here and in rt_set_pixel_loc): 1 <= w <= 2^31 - 8, 1 <= h <= 2^29 - 32 and w*h <= 2^31, else RT_ERR_BAD_ARG.
+ * (The kernel forms a tile's columns x0 + 8 tx + 7, up to w + 6, as a signed 32-bit int; and a dispatch holds at most 2^32 - 1
+ * work-items: launches wider than that go out as column slabs, and one column of 8x8 tiles must fit.)  Every such frame renders
+ * with every entry point; RT_AA_REFERENCE traces the half-pixel lattice while (2w-1)(2h-1) < 2^31, 2w-1 <= 2^31 - 8 and
+ * 2h-1 <= 2^29 - 32, else nine taps per pixel (RT_FLAG_AA_PER_PIXEL): the same bytes. */
 int rt_set_raygen(rt_ctx *ctx, int w, int h, double px, double y0, double dy, double z0, double dz);
 
 /* Drop-in alternative: an explicit float64 (3,w,h) C-order pixel_loc array (host pointer), uploaded

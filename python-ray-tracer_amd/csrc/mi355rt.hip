@@ -3,6 +3,7 @@
 // rt_create fails and nothing renders.
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
+#include "rt_geometry.h"
 
 #include <cmath>
 #include <cstdio>
@@ -365,9 +366,8 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     k.aa = p->aa_mode; k.u8_rgb = (p->flags & RT_FLAG_U8_RGB) ? 1 : 0; k.u8_hwc = (p->flags & RT_FLAG_U8_HWC) ? 1 : 0;
     k.spp = p->spp; k.seed = p->seed;
     k.lanes_primary = ctx->lanes_primary;
-    k.tiles_y = (ctx->h + rt::TILE - 1) / rt::TILE;
-    const int tiles_x = (x1 - x0 + rt::TILE - 1) / rt::TILE;
-    k.ntiles = tiles_x * k.tiles_y;
+    k.tiles_y = (int)rt_geo_tiles(ctx->h);
+    k.ntiles = (int)(rt_geo_tiles(x1 - x0) * k.tiles_y);      // (rt_geo_frame_ok: below 2^28)
     k.px = ctx->px; k.y0 = ctx->y0; k.dy = ctx->dy; k.z0 = ctx->z0; k.dz = ctx->dz;
     std::memcpy(k.cam_o, ctx->cam_o, sizeof k.cam_o);
     std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
@@ -400,17 +400,18 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     // the reference's order (kernels.py:53-65, including its G/B swap).  Explicit pixel_loc grids are not separable
     // in general and keep the nine-taps-per-pixel kernel.
     const long long LW = 2ll * ctx->w - 1, LH = 2ll * ctx->h - 1;
-    if (k.aa == RT_AA_REFERENCE && !ctx->explicit_grid && LW * LH < (1ll << 31) && !(p->flags & RT_FLAG_AA_PER_PIXEL)) {
-        const int li0 = std::max(0, 2 * x0 - 1), li1 = (int)std::min(LW - 1, 2ll * x1 - 1);       // lattice columns, inclusive
+    long long li0 = 0, li1 = 0;                                 // lattice columns [li0, li1)
+    if (k.aa == RT_AA_REFERENCE && !ctx->explicit_grid && rt_geo_lattice(ctx->w, ctx->h, x0, x1, &li0, &li1) &&
+        !(p->flags & RT_FLAG_AA_PER_PIXEL)) {
         double *lat = nullptr;
-        int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0 + 1) * (size_t)LH * 3 * sizeof(double), &lat);
+        int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0) * (size_t)LH * 3 * sizeof(double), &lat);
         if (rc != RT_OK) return rc;
         rt::KParams kl = k;
         kl.aa = 0; kl.lattice = 1; kl.out_u8 = nullptr; kl.out_f32 = nullptr; kl.out_f64 = lat; kl.tile_cycles = nullptr;   // (rt_set_tile_stats: pixel launches only)
-        kl.w = (int)LW; kl.h = (int)LH; kl.x0 = li0; kl.x1 = li1 + 1; kl.plane_stride = 0;
-        kl.tiles_y = ((int)LH + rt::TILE - 1) / rt::TILE;
-        kl.ntiles = ((li1 + 1 - li0 + rt::TILE - 1) / rt::TILE) * kl.tiles_y;
-        k.out_f64 = lat; k.lat_x0 = li0; k.lat_h = (int)LH;
+        kl.w = (int)LW; kl.h = (int)LH; kl.x0 = (int)li0; kl.x1 = (int)li1; kl.plane_stride = 0;
+        kl.tiles_y = (int)rt_geo_tiles(LH);
+        kl.ntiles = (int)(rt_geo_tiles(li1 - li0) * kl.tiles_y);
+        k.out_f64 = lat; k.lat_x0 = (int)li0; k.lat_h = (int)LH;
         const long long npx = (long long)(x1 - x0) * ctx->h;
         for (int f = 0; f < nframes; ++f) {                    // the stream's one lattice buffer serves the frames in turn
             rc = dispatch(ctx, p, kl, true, stream, 1, 0);
@@ -543,7 +544,27 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
         }
         k.ray_counts = (unsigned long long *)ctx->counts.p;
     }
-    const unsigned grid = (unsigned)((k.ntiles + wpw - 1) / wpw);
+    // At most RT_GEO_MAX_ITEMS work-items per dispatch (rt_geometry.h): a frame beyond that alone goes out as column slabs
+    // (they assemble bit-identically), one dispatch each; a sequence as batches of frames.
+    const rt_geo_plan g = rt_geo_plan_of(x0, x1, k.h, wpw, nframes);
+    auto frame_of = [&](int fr) { rt::KParams kf = k; if (kf.out_u8) kf.out_u8 += (size_t)fr * frame_stride; if (kf.out_f32) kf.out_f32 += (size_t)fr * frame_stride; return kf; };
+    if (g.nslabs > 1) {
+        for (int fr = 0; fr < nframes; ++fr)
+            for (long long s = 0; s < g.nslabs; ++s) {
+                const long long sx0 = x0 + s * g.slab_tiles * rt::TILE, sx1 = std::min<long long>(x1, sx0 + g.slab_tiles * rt::TILE);
+                const long long dx = sx0 - x0;
+                rt::KParams kf = frame_of(fr);
+                kf.x0 = (int)sx0; kf.x1 = (int)sx1; kf.ntiles = (int)(rt_geo_tiles(sx1 - sx0) * k.tiles_y);
+                if (kf.out_u8) kf.out_u8 += k.u8_hwc ? 3 * dx : dx * k.h;       // (element [c, x, y] of rt_render_device)
+                if (kf.out_f32) kf.out_f32 += dx * k.h;
+                if (kf.out_f64) kf.out_f64 += 3 * dx * k.h;                      // (lattice samples, [column - x0][row][3])
+                if (kf.tile_cycles) kf.tile_cycles += dx / rt::TILE * k.tiles_y;
+                int rc = dispatch(ctx, p, kf, lattice, stream, 1, 0);
+                if (rc != RT_OK) return rc;
+            }
+        return RT_OK;
+    }
+    const unsigned grid = (unsigned)g.blocks;
     // Scheduler feedback (longest-first dispatch): a launch files its tile blocks by cost and dispatches in the
     // order built from the previous measured launch of the same range, depth and AA mode.
     // RT_FLAG_NO_FEEDBACK renders in plain tile order.  Any order renders every tile exactly once.
@@ -610,11 +631,11 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     const bool settled = feedback && f.have && (same_epoch ? f.builds >= 2 : f.since < ctx->remeasure);
     // A launch of several frames (rt_render_sequence) is ONE launch only in a settled order; until then its frames go
     // through this function one by one (a measuring launch stores the costs of one frame).
-    auto frame_of = [&](int fr) { rt::KParams kf = k; if (kf.out_u8) kf.out_u8 += (size_t)fr * frame_stride; if (kf.out_f32) kf.out_f32 += (size_t)fr * frame_stride; return kf; };
-    if (nframes > 1 && (long long)grid * nframes >= (1ll << 31)) {            // (a grid beyond 2^31 workgroups: frame by frame)
-        for (int fr = 0; fr < nframes; ++fr) {
+    if (nframes > g.frames_per_dispatch) {                    // (more work-items than one dispatch holds: batches of frames)
+        const int fpd = (int)g.frames_per_dispatch;
+        for (int fr = 0; fr < nframes; fr += fpd) {
             rt::KParams kf = frame_of(fr);
-            int rc = dispatch(ctx, p, kf, lattice, stream, 1, 0);
+            int rc = dispatch(ctx, p, kf, lattice, stream, std::min(fpd, nframes - fr), frame_stride);
             if (rc != RT_OK) return rc;
         }
         return RT_OK;
@@ -1093,7 +1114,7 @@ int rt_set_lens(rt_ctx *ctx, double aperture, double focus_distance)
 int rt_set_raygen(rt_ctx *ctx, int w, int h, double px, double y0, double dy, double z0, double dz)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (w < 1 || h < 1 || (long long)w * h > (1ll << 31)) return fail(ctx, RT_ERR_BAD_ARG, "frame size out of range");
+    if (!rt_geo_frame_ok(w, h)) return fail(ctx, RT_ERR_BAD_ARG, "frame size out of range (1 <= w <= 2^31 - 8, 1 <= h <= 2^29 - 32, w*h <= 2^31)");
     {
         const double now[5] = {px, y0, dy, z0, dz}, was[5] = {ctx->px, ctx->y0, ctx->dy, ctx->z0, ctx->dz};
         if (ctx->have_grid && !ctx->explicit_grid && ctx->w == w && ctx->h == h && std::memcmp(now, was, sizeof now) == 0)
@@ -1110,7 +1131,7 @@ int rt_set_pixel_loc(rt_ctx *ctx, const double *pixel_loc, int w, int h)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (!pixel_loc) return fail(ctx, RT_ERR_BAD_ARG, "pixel_loc is NULL");
-    if (w < 1 || h < 1 || (long long)w * h > (1ll << 31)) return fail(ctx, RT_ERR_BAD_ARG, "frame size out of range");
+    if (!rt_geo_frame_ok(w, h)) return fail(ctx, RT_ERR_BAD_ARG, "frame size out of range (1 <= w <= 2^31 - 8, 1 <= h <= 2^29 - 32, w*h <= 2^31)");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bytes = (size_t)3 * w * h * sizeof(double);
     // one buffer, read by every launch of an explicit grid on any stream: nothing may be in flight while it is rewritten
@@ -1203,7 +1224,7 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
     // launches overlap), and every chunk's planes start their way to the host (third stream, behind an
     // event) while the following chunks still render: the copy of a 1080p frame costs about as much as rendering it,
     // and this hides all of it but the last chunk's.  (main.py:41-51: launch, then copy_to_host.)
-    const int tiles = (x1 - x0 + rt::TILE - 1) / rt::TILE;
+    const long long tiles = rt_geo_tiles(x1 - x0);
     const int NCH = ctx->render_chunks;
     if (hwc || NCH < 2 || npx < (1u << 19) || tiles < 4 * NCH) {
         rc = launch(ctx, params, x0, x1, out_u8 ? ctx->u8.p : nullptr, out_f32 ? ctx->f32.p : nullptr,
@@ -1239,10 +1260,28 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
     int cx[RT_RENDER_CHUNKS + 1];
     // the first and the last chunk are half as wide as the others: the copies start sooner, and the one copy that
     // nothing overlaps (the last chunk's) is short
-    for (int c = 0; c <= NCH; ++c) {
-        const int num = (c == 0) ? 0 : (c == NCH ? 2 * (NCH - 1) : 2 * c - 1);          // of 2 (NCH - 1) half-units
-        cx[c] = std::min(x1, x0 + (int)((long long)tiles * num / (2 * (NCH - 1))) * rt::TILE);
-    }
+    for (int c = 0; c <= NCH; ++c) cx[c] = (int)rt_geo_chunk_x(x0, x1, NCH, c);
+    // a chunk's three planes = one 2-D copy (3 rows, pitch = plane) while the pitch stays within RT_GEO_MAX_PITCH, else
+    // three copies, plane by plane
+    auto copy_chunk = [&](size_t off, size_t n, hipStream_t s) -> int {
+        if (out_u8) {
+            if (rt_geo_copy_2d((long long)npx, 1))
+                RT_HIP(ctx, hipMemcpy2DAsync(out_u8 + off, npx, (uint8_t *)ctx->u8.p + off, npx, n, 3, hipMemcpyDeviceToHost, s));
+            else
+                for (size_t c = 0; c < 3; ++c)
+                    RT_HIP(ctx, hipMemcpyAsync(out_u8 + c * npx + off, (uint8_t *)ctx->u8.p + c * npx + off, n, hipMemcpyDeviceToHost, s));
+        }
+        if (out_f32) {
+            if (rt_geo_copy_2d((long long)npx, sizeof(float)))
+                RT_HIP(ctx, hipMemcpy2DAsync(out_f32 + off, npx * sizeof(float), (float *)ctx->f32.p + off, npx * sizeof(float),
+                                             n * sizeof(float), 3, hipMemcpyDeviceToHost, s));
+            else
+                for (size_t c = 0; c < 3; ++c)
+                    RT_HIP(ctx, hipMemcpyAsync(out_f32 + c * npx + off, (float *)ctx->f32.p + c * npx + off, n * sizeof(float),
+                                               hipMemcpyDeviceToHost, s));
+        }
+        return RT_OK;
+    };
     unsigned *const tile_stats = ctx->tile_stats;
     const int tiles_y = (ctx->h + rt::TILE - 1) / rt::TILE;
     for (int c = 0; c < NCH; ++c) {
@@ -1255,21 +1294,17 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
         ctx->tile_stats = tile_stats;
         if (rc != RT_OK) return rc;
         if (instream) {
-            if (out_u8) RT_HIP(ctx, hipMemcpy2DAsync(out_u8 + off, npx, (uint8_t *)ctx->u8.p + off, npx, n, 3, hipMemcpyDeviceToHost, s));
-            if (out_f32) RT_HIP(ctx, hipMemcpy2DAsync(out_f32 + off, npx * sizeof(float), (float *)ctx->f32.p + off, npx * sizeof(float),
-                                                      n * sizeof(float), 3, hipMemcpyDeviceToHost, s));
+            if ((rc = copy_chunk(off, n, s)) != RT_OK) return rc;
         } else RT_HIP(ctx, hipEventRecord(ctx->chunk_ev[c], s));
     }
     if (instream) {
         for (int c = 0; c < NCH; ++c) RT_HIP(ctx, hipStreamSynchronize(ctx->chunk_stream[c]));
         return RT_OK;
     }
-    for (int c = 0; c < NCH; ++c) {                             // a chunk's three planes = one 2-D copy (3 rows, pitch = plane)
+    for (int c = 0; c < NCH; ++c) {
         const size_t off = (size_t)(cx[c] - x0) * ctx->h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->h;
         RT_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->chunk_ev[c], 0));
-        if (out_u8) RT_HIP(ctx, hipMemcpy2DAsync(out_u8 + off, npx, (uint8_t *)ctx->u8.p + off, npx, n, 3, hipMemcpyDeviceToHost, ctx->copy_stream));
-        if (out_f32) RT_HIP(ctx, hipMemcpy2DAsync(out_f32 + off, npx * sizeof(float), (float *)ctx->f32.p + off, npx * sizeof(float),
-                                                  n * sizeof(float), 3, hipMemcpyDeviceToHost, ctx->copy_stream));
+        if ((rc = copy_chunk(off, n, ctx->copy_stream)) != RT_OK) return rc;
     }
     RT_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
     return RT_OK;

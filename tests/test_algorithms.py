@@ -77,3 +77,36 @@ def test_oracle_under_asan_ubsan(tmp_path):
         assert outs[0] == outs[1] and len(outs[0]) > 3 * w * h * 10
         if i == 0:
             assert any(outs[0][:3 * w * h])                           # the golden's scene renders something
+
+
+def test_launch_geometry_under_ubsan(tmp_path):
+    """python-ray-tracer_amd/csrc/rt_geometry.h, the library's launch arithmetic, under UndefinedBehaviorSanitizer on the frame
+    limits of include/mi355rt.h: 2^31-pixel frames, thin frames and their transposes, both sides of the lattice switch, slabs
+    near w, long sequences.  Every dispatch at most 2^32 - 1 work-items, tiles / slabs / batches covering their range exactly
+    once, every int of the launch and of the kernel's index arithmetic in range, the shapes beyond the limits refused."""
+    exe = str(tmp_path / "geometry_check")
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "geometry_check.c")])
+    res = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.startswith("shapes=") and res.stdout.strip().endswith("ok"), res.stdout
+    assert int(res.stdout.split()[1].split("=")[1]) > 1000000, res.stdout    # (every slab and batch of every shape)
+
+
+def test_python_frame_rule_is_the_header_rule():
+    """renderer.check_frame states rt_geometry.h's frame rule (rt_set_raygen / rt_set_pixel_loc) with the same constants."""
+    import re
+    import pytest
+    from python_ray_tracer_amd.renderer import MAX_FRAME_H, MAX_FRAME_PIXELS, MAX_FRAME_W, check_frame
+    src = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "rt_geometry.h")).read()
+    consts = {}
+    for name in ("RT_GEO_MAX_W", "RT_GEO_MAX_H", "RT_GEO_MAX_PIXELS"):
+        m = re.search(r"#define " + name + r" \(\(?1ll << (\d+)\)(?: - (\d+)\))?", src)
+        consts[name] = (1 << int(m.group(1))) - int(m.group(2) or 0)
+    assert (MAX_FRAME_W, MAX_FRAME_H, MAX_FRAME_PIXELS) == (consts["RT_GEO_MAX_W"], consts["RT_GEO_MAX_H"], consts["RT_GEO_MAX_PIXELS"])
+    for w, h in [(65536, 32768), (2 ** 31 - 8, 1), (1, 2 ** 29 - 32), (2 ** 30, 2), (4, 2 ** 29 - 32), (1, 1)]:
+        assert check_frame(w, h) == (w, h)
+    for w, h in [(2 ** 31 - 7, 1), (2 ** 31 - 1, 1), (1, 2 ** 29 - 31), (2, 2 ** 29 + 8), (65536, 32769), (0, 5), (5, 0),
+                 (2 ** 31, 1), (2 ** 30 + 1, 2)]:
+        with pytest.raises(ValueError):
+            check_frame(w, h)
