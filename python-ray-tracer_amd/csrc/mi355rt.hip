@@ -9,11 +9,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <numeric>
 #include <new>
 #include <string>
 #include <functional>
+#include <utility>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -76,12 +78,7 @@ struct rt_ctx {
     int M = 0;                    // materials of the current scene (rt_set_scene_materials; 0 = the launch's shading scalars)
     int mat_cols = 3;             // doubles per row of its table: 6 with a rough row (the scatter kernels), else 5 with a
                                   // transparent row (the refraction kernels), else 3
-    size_t mat_lds_limit_set = 0; // hipFuncAttributeMaxDynamicSharedMemorySize of the material kernels (lds_limit_set: the others)
-    size_t refr_lds_limit_set = 0;   // (the same, refraction kernels)
-    size_t scat_lds_limit_set = 0;   // (the same, scatter kernels)
-    size_t soft_lds_limit_set = 0;   // (the same, area-light kernels)
     int soft_n = 0;               // shadow samples per light of a scene with a light radius > 0 (the area-light kernels), else 0
-    size_t lens_lds_limit_set[2] = {0, 0};   // (the same, lens kernels: scatter twins, area-light twins)
     long long lens_mat = 0;       // offset (doubles) in the scene buffer of its material block with rows of 6 (the lens kernels')
     double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
@@ -89,7 +86,7 @@ struct rt_ctx {
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
     int w = 0, h = 0;
     double px = 0, y0 = 0, dy = 0, z0 = 0, dz = 0;
-    size_t lds_limit_set = 0;
+    size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
     unsigned plane_codes = 0;         // axis codes of planes 0..3 (rt_device.h: KParams::plane_codes)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback: a MEASURING launch stores its tile blocks' costs; a small kernel behind it (same stream) turns
@@ -184,6 +181,15 @@ void plane_normal_f32(const float n[3], float out[3])
     out[0] = n[0] / norm; out[1] = n[1] / norm; out[2] = n[2] / norm;
 }
 
+// M rows of `cols` columns of a material table into dst, from a table of `ncols` columns: its first columns, and where it has
+// fewer, trans 0, ior 1 and rough 0.
+void put_rows(double *dst, int cols, const double *src, int ncols, int M)
+{
+    static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    for (int m = 0; m < M; ++m)
+        for (int i = 0; i < cols; ++i) dst[(size_t)cols * m + i] = i < ncols ? src[(size_t)ncols * m + i] : pad[i];
+}
+
 int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
 {
     if (!p) return fail(ctx, RT_ERR_BAD_ARG, "params is NULL");
@@ -205,85 +211,109 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
     return RT_OK;
 }
 
-// instantiations with the lane-owned traversal (MODE 2: clustered scenes from lanes_min_spheres spheres on); workgroups of
-// 4.  They keep no float64 sphere records in LDS (rt_device.h: sphere_hot), which leaves room for the parked state.
-const void *lanes_variant(bool aa, bool lattice, bool park)
+// The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
+// have.  From the scene (M materials in a table of mat_cols columns, soft_n shadow samples per light) and the lens aperture.
+rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a)
 {
-    if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2> : (const void *)rt::render_kernel<false, false, 4, false, true, 2>;
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3> : (const void *)rt::render_kernel<true, false, 4, false, false, 2>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2> : (const void *)rt::render_kernel<false, false, 4, false, false, 2>);
+    using F = rt::Family;
+    if (M <= 0) return F::PLAIN;
+    if (lens_a > 0.0) return soft_n > 0 ? F::LENS_SOFT : F::LENS;    // (check_params: a lens needs a material table)
+    return soft_n > 0 ? F::SOFT : mat_cols == 6 ? F::SCAT : mat_cols == 5 ? F::REFR : F::MAT;
 }
 
-const void *lattice_variant(bool park, int wpw, bool count = false, bool norec = false)     // the plain kernel over the half-pixel lattice (RT_AA_REFERENCE)
+// The shape of a launch (dispatch()): render_kernel's first six template arguments.
+struct Shape {
+    bool aa, park;
+    int wpw;
+    bool count, lat;
+    int mode;    // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS; 2: lane-owned traversal; 3: its AA + parked variant
+    constexpr bool operator==(const Shape &o) const
+    {
+        return aa == o.aa && park == o.park && wpw == o.wpw && count == o.count && lat == o.lat && mode == o.mode;
+    }
+};
+
+// Every shape dispatch() can produce.
+constexpr Shape SHAPES[] = {
+    // wave-uniform cull, workgroups of 2 or 4 (flat scenes up to rt::CLUSTER_MIN spheres may take 2), with AA or without, register
+    // or parked variant; MODE 1: workgroups of 4 without AA that keep no float64 sphere records in LDS (rt_device.h: sphere_hot)
+    {false, false, 2, false, false, 0}, {false, true, 2, false, false, 0}, {true, false, 2, false, false, 0}, {true, true, 2, false, false, 0},
+    {false, false, 4, false, false, 0}, {false, true, 4, false, false, 0}, {true, false, 4, false, false, 0}, {true, true, 4, false, false, 0},
+    {false, false, 4, false, false, 1}, {false, true, 4, false, false, 1},
+    // the same over the half-pixel lattice (RT_AA_REFERENCE on the closed-form grid: no AA of their own)
+    {false, false, 2, false, true, 0}, {false, true, 2, false, true, 0}, {false, false, 4, false, true, 0}, {false, true, 4, false, true, 0},
+    {false, false, 4, false, true, 1}, {false, true, 4, false, true, 1},
+    // lane-owned traversal (MODE 2, clustered scenes from lanes_min_spheres spheres on), workgroups of 4; with AA and parked: MODE 3
+    {false, false, 4, false, false, 2}, {false, true, 4, false, false, 2}, {true, false, 4, false, false, 2}, {true, true, 4, false, false, 3},
+    {false, false, 4, false, true, 2}, {false, true, 4, false, true, 2},
+    // rt_get_stats: the register variants with workgroups of 4 carry the ray counters
+    {false, false, 4, true, false, 0}, {true, false, 4, true, false, 0}, {false, false, 4, true, true, 0},
+};
+constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
+
+// A family has one render kernel per shape, except
+//  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
+//  * the parked wave-uniform shapes (MODE 0 and 1) from REFR on, which the parking rule never picks (the static_assert below).
+// So PLAIN has 25 kernels, MAT 22 and every later family 14.  Nothing else names a render kernel of a family other than
+// PLAIN, so the kernels a family does not have are not compiled.
+constexpr bool has_kernel(rt::Family f, const Shape &s)
 {
-    if (count) return (const void *)rt::render_kernel<false, false, 4, true, true>;
-    if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1> : (const void *)rt::render_kernel<false, false, 4, false, true, 1>;
-    if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true> : (const void *)rt::render_kernel<false, false, 2, false, true>;
-    return park ? (const void *)rt::render_kernel<false, true, 4, false, true> : (const void *)rt::render_kernel<false, false, 4, false, true>;
+    return (!s.count || f == rt::Family::PLAIN) && !(rt::has_refr(f) && s.park && s.mode < 2);
 }
 
-const void *kernel_variant(bool aa, bool park, int wpw, bool count = false, bool norec = false)
+// The parking rule of the wave-uniform kernels (dispatch()): their state parks in LDS while PARK_WAVES wavefronts per CU still
+// fit their workgroups' LDS images.
+constexpr int PARK_WAVES = 24;
+constexpr size_t CU_LDS = 160 * 1024;
+
+// A kernel a family does not have (counting kernels aside) is one that no scene lets park: its per-thread slots, pixel offsets
+// and workgroup words alone (rt::lds_bytes of an empty scene) take more than CU_LDS at PARK_WAVES wavefronts.  For REFR without
+// AA that is 13 slots: 13 840 B x 12 workgroups of 2 = 166 080 B and 27 664 B x 6 workgroups of 4 = 165 984 B against 163 840 B.
+constexpr bool missing_kernels_never_park()
 {
-    if (count)      // rt_get_stats: the register variant with workgroups of 4 carries the ray counters
-        return aa ? (const void *)rt::render_kernel<true, false, 4, true> : (const void *)rt::render_kernel<false, false, 4, true>;
-    if (norec && wpw == 4 && !aa)   // MODE 1: four-wave workgroups without float64 sphere records in LDS (rt_device.h: sphere_hot)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1> : (const void *)rt::render_kernel<false, false, 4, false, false, 1>;
-    if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2> : (const void *)rt::render_kernel<true, false, 2>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2> : (const void *)rt::render_kernel<false, false, 2>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4> : (const void *)rt::render_kernel<true, false, 4>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4> : (const void *)rt::render_kernel<false, false, 4>);
+    for (int fi = 0; fi < rt::FAMILIES; ++fi)
+        for (const Shape &s : SHAPES) {
+            const rt::Family f = (rt::Family)fi;
+            if (s.count || has_kernel(f, s)) continue;
+            const size_t wgt = 64 * s.wpw;
+            const size_t least = rt::lds_slots(s.aa, true, s.mode >= 2, rt::has_mat(f), rt::has_refr(f), rt::has_scat(f), rt::has_soft(f)) * wgt * sizeof(double) +
+                                 wgt * sizeof(int) + 16;
+            if (!s.park || s.mode >= 2 || least * (PARK_WAVES / s.wpw) <= CU_LDS) return false;
+        }
+    return true;
+}
+static_assert(missing_kernels_never_park(), "the parking rule can pick a render kernel that is not compiled");
+
+template <rt::Family F, int I>
+const void *kernel_at()
+{
+    constexpr Shape s = SHAPES[I];
+    if constexpr (has_kernel(F, s))
+        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, rt::has_mat(F), rt::has_refr(F), rt::has_scat(F),
+                                               rt::has_soft(F), rt::has_lens(F)>;
+    else
+        return nullptr;
+}
+template <rt::Family F, int... I>
+std::array<const void *, NSHAPES> family_kernels(std::integer_sequence<int, I...>)
+{
+    return {kernel_at<F, I>()...};
 }
 
-// The instantiations for scenes with materials (rt_device.h: MAT), one for every variant the dispatcher picks for a scene
-// without them except the counting ones (RT_FLAG_COUNT_RAYS is refused for such scenes): same arguments as lanes_variant
-// (lanes), lattice_variant (lattice) and kernel_variant.
-const void *material_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
-{
-    if (lanes) {
-        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true>;
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true>);
-    }
-    if (lattice) {
-        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true>;
-        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true>;
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true>;
-    }
-    if (norec && wpw == 4 && !aa)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true>;
-    if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true>);
-}
+// KERNELS[f][i]: family f's render kernel of shape SHAPES[i] (nullptr: it has none)
+constexpr std::make_integer_sequence<int, NSHAPES> ALL_SHAPES{};
+const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
+    family_kernels<rt::Family::PLAIN>(ALL_SHAPES), family_kernels<rt::Family::MAT>(ALL_SHAPES),
+    family_kernels<rt::Family::REFR>(ALL_SHAPES),  family_kernels<rt::Family::SCAT>(ALL_SHAPES),
+    family_kernels<rt::Family::SOFT>(ALL_SHAPES),  family_kernels<rt::Family::LENS>(ALL_SHAPES),
+    family_kernels<rt::Family::LENS_SOFT>(ALL_SHAPES),
+};
 
-// The refraction kernels (rt_device.h: REFR): the material twins for a scene whose table has a transparent row
-// (rt_set_scene_materials_ex), same arguments.  SC: their scatter twins (rt_device.h: SCAT), for a table with a rough row
-// (rt_set_scene_materials_scatter).  SO (with SC): the area-light twins of those (rt_device.h: SOFT), for a scene with a light
-// radius > 0 (rt_set_scene_area_lights).  LE (with SC): the lens twins of the scatter or area-light kernels (rt_device.h: LENS),
-// for a launch with an aperture > 0 (rt_set_lens).
-template <bool SC = false, bool SO = false, bool LE = false>
-const void *refraction_variant(bool lanes, bool aa, bool lattice, bool park, int wpw, bool norec)
+const void *kernel_of(rt::Family f, const Shape &s)
 {
-    if (lanes) {
-        if (lattice) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 2, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 2, true, true, SC, SO, LE>;
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 3, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 4, false, false, 2, true, true, SC, SO, LE>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 2, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 2, true, true, SC, SO, LE>);
-    }
-    if (lattice) {
-        if (norec && wpw == 4) return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 1, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 1, true, true, SC, SO, LE>;
-        if (wpw == 2) return park ? (const void *)rt::render_kernel<false, true, 2, false, true, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 2, false, true, 0, true, true, SC, SO, LE>;
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, true, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, true, 0, true, true, SC, SO, LE>;
-    }
-    if (norec && wpw == 4 && !aa)
-        return park ? (const void *)rt::render_kernel<false, true, 4, false, false, 1, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 1, true, true, SC, SO, LE>;
-    if (wpw == 2)
-        return aa ? (park ? (const void *)rt::render_kernel<true, true, 2, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 2, false, false, 0, true, true, SC, SO, LE>)
-                  : (park ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 2, false, false, 0, true, true, SC, SO, LE>);
-    return aa ? (park ? (const void *)rt::render_kernel<true, true, 4, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<true, false, 4, false, false, 0, true, true, SC, SO, LE>)
-              : (park ? (const void *)rt::render_kernel<false, true, 4, false, false, 0, true, true, SC, SO, LE> : (const void *)rt::render_kernel<false, false, 4, false, false, 0, true, true, SC, SO, LE>);
+    for (int i = 0; i < NSHAPES; ++i)
+        if (SHAPES[i] == s) return KERNELS[(int)f][i];
+    return nullptr;
 }
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
@@ -375,7 +405,7 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const bool lens = ctx->lens_a > 0.0 && ctx->M > 0;
+    const bool lens = rt::has_lens(family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a));
     if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
@@ -434,8 +464,9 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     const int x0 = k.x0, x1 = k.x1;
     // Workgroup size: 2 tiles (wavefronts) for scenes whose LDS image (records + cull tables) is small, 4 otherwise
     // (every workgroup stages its own copy; rt_device.h has the measurements).
-    // Kernel variant: state parked in LDS (7 waves/SIMD, no scratch) while at least 24 wavefronts per CU still
+    // Kernel variant: state parked in LDS (7 waves/SIMD, no scratch) while at least PARK_WAVES wavefronts per CU still
     // fit their workgroups' LDS images; otherwise the register variant (its occupancy is then LDS-bound anyway).
+    // The kernel is the family's of the launch's shape (kernel_of).
     const bool aa = k.aa != 0;
     const bool count = (p->flags & RT_FLAG_COUNT_RAYS) != 0;
     const size_t image = rt::lds_doubles(ctx->S, ctx->P, ctx->L) * sizeof(double) + rt::table_floats(ctx->S, ctx->NC, k.anchors) * sizeof(float);
@@ -455,86 +486,28 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // variant runs 7 per CU if they fit and needs 6, the register variant 5.  Config 4 (64 spheres): 6 -> 7 workgroups, -5 %;
     // 100 spheres: register variant at 5 -> parked at 6, -7 %; where the count stays (36, 49, 144 spheres) it costs 0...2 %
     // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
-    // a scene with materials runs the material twins of the same variants; their LDS images hold the material data too
-    // (matd doubles), and the parked ones one more per-thread slot
-    // (a scene with a transparent row: the refraction twins, with rows of 5 and four more per-thread slots; with a rough row
-    // their scatter twins, with rows of 6 and two more slots)
-    // (a scene with a light radius > 0: the scatter kernels' area-light twins, rows of 6, one more slot and n behind the block)
-    // (a launch with a lens: the lens twins of the scatter or area-light kernels, rows of 6 (the scene's own block or its padded
-    // copy, rt_ctx::lens_mat) and no more slots)
-    const bool lens = ctx->M > 0 && ctx->lens_a > 0.0;
-    const bool soft = ctx->M > 0 && ctx->soft_n > 0;
-    const bool scat = ctx->M > 0 && (ctx->mat_cols == 6 || lens);
-    const bool refr = ctx->M > 0 && (ctx->mat_cols >= 5 || lens);
-    const size_t matd = rt::mat_doubles(ctx->M, ctx->S, ctx->P, lens ? 6 : ctx->mat_cols, soft);   // (the block is in the launch's scene buffer: rt::mat_offset)
+    // The feature family (family_of) picks the twins of these variants: their LDS images hold the material block too
+    // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt_ctx::lens_mat), and their parked variants the
+    // family's per-thread slots (rt::lds_slots).
+    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a);
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, matd, refr, scat, soft);
-        if (lp * 6 <= 160 * 1024) return (int)std::min<size_t>(7, 160 * 1024 / lp);
-        return (int)std::min<size_t>(5, 160 * 1024 / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, matd, refr, scat, soft));
+        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->M);
+        if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
+        return (int)std::min<size_t>(5, CU_LDS / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, fam, ctx->M));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, matd, refr, scat, soft);
+    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, fam, ctx->M);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
-    const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= 160 * 1024 && ctx->lanes_park) : lds_park * (24 / wpw) <= 160 * 1024);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, matd, refr, scat, soft);
-    const void *fn = lens ? (soft ? refraction_variant<true, true, true>(lanes, aa, lattice, park, wpw, norec)
-                                  : refraction_variant<true, false, true>(lanes, aa, lattice, park, wpw, norec))
-                   : soft ? refraction_variant<true, true>(lanes, aa, lattice, park, wpw, norec)
-                   : scat ? refraction_variant<true>(lanes, aa, lattice, park, wpw, norec)
-                   : refr ? refraction_variant(lanes, aa, lattice, park, wpw, norec)
-                   : matd ? material_variant(lanes, aa, lattice, park, wpw, norec)
-                          : lanes ? lanes_variant(aa, lattice, park) : (lattice ? lattice_variant(park, wpw, count, norec) : kernel_variant(aa, park, wpw, count, norec));
-    if (lens) {
-        if (lds > 48 * 1024 && lds > ctx->lens_lds_limit_set[soft]) {
-            for (int v = 0; v < 64; ++v)
-                RT_HIP(ctx, hipFuncSetAttribute(soft ? refraction_variant<true, true, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32)
-                                                     : refraction_variant<true, false, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->lens_lds_limit_set[soft] = lds;
-        }
-    } else if (soft) {
-        if (lds > 48 * 1024 && lds > ctx->soft_lds_limit_set) {
-            for (int v = 0; v < 64; ++v)
-                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true, true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->soft_lds_limit_set = lds;
-        }
-    } else if (scat) {
-        if (lds > 48 * 1024 && lds > ctx->scat_lds_limit_set) {
-            for (int v = 0; v < 64; ++v)
-                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant<true>(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->scat_lds_limit_set = lds;
-        }
-    } else if (refr) {
-        if (lds > 48 * 1024 && lds > ctx->refr_lds_limit_set) {
-            for (int v = 0; v < 64; ++v)
-                RT_HIP(ctx, hipFuncSetAttribute(refraction_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->refr_lds_limit_set = lds;
-        }
-    } else if (matd) {
-        if (lds > 48 * 1024 && lds > ctx->mat_lds_limit_set) {
-            for (int v = 0; v < 64; ++v)
-                RT_HIP(ctx, hipFuncSetAttribute(material_variant(v & 1, v & 2, v & 4, v & 8, (v & 16) ? 4 : 2, v & 32),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->mat_lds_limit_set = lds;
-        }
-    } else if (lds > 48 * 1024 && lds > ctx->lds_limit_set) {
-        for (int v = 0; v < 8; ++v)
-            RT_HIP(ctx, hipFuncSetAttribute(kernel_variant(v & 1, v & 2, (v & 4) ? 4 : 2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int v = 0; v < 2; ++v) {
-            RT_HIP(ctx, hipFuncSetAttribute(kernel_variant(false, v & 1, 4, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            RT_HIP(ctx, hipFuncSetAttribute(lattice_variant(v & 1, 4, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        for (int v = 0; v < 2; ++v)
-            RT_HIP(ctx, hipFuncSetAttribute(kernel_variant(v & 1, false, 4, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int v = 0; v < 4; ++v)
-            RT_HIP(ctx, hipFuncSetAttribute(lattice_variant(v & 1, (v & 2) ? 4 : 2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        RT_HIP(ctx, hipFuncSetAttribute(lattice_variant(false, 4, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int v = 0; v < 6; ++v)
-            RT_HIP(ctx, hipFuncSetAttribute(lanes_variant(v % 3 == 1, v % 3 == 2, v >= 3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->lds_limit_set = lds;
+    const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= CU_LDS && ctx->lanes_park) : lds_park * (PARK_WAVES / wpw) <= CU_LDS);
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, fam, ctx->M);
+    const void *fn = kernel_of(fam, Shape{aa, park, wpw, count, lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0)});
+    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: missing_kernels_never_park)
+    // more than the default 48 KiB of dynamic LDS: raised on all of the family's kernels at once
+    const int fi = (int)fam;
+    if (lds > 48 * 1024 && lds > ctx->lds_limit_set[fi]) {
+        for (const void *kf : KERNELS[fi])
+            if (kf) RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->lds_limit_set[fi] = lds;
     }
     if (count) {
         if (!ctx->counts.p) {
@@ -873,26 +846,23 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         cols = rough ? 6 : (glass ? 5 : 3);
         try {
             packed.resize((size_t)cols * M);
-            for (int m = 0; m < M; ++m)
-                for (int i = 0; i < cols; ++i) packed[(size_t)cols * m + i] = materials[(size_t)ncols * m + i];
         } catch (const std::bad_alloc &) {
             return fail(ctx, RT_ERR_ALLOC, "out of host memory");
         }
+        put_rows(packed.data(), cols, materials, ncols, M);
         materials = packed.data();
     }
     // the area-light kernels are scatter kernels: their table travels with all six columns (a 3- or 5-column table padded with
     // trans 0, ior 1, rough 0), and with lamb / n in place of lamb (the reference's lambert_int of a trace with n points per light)
     std::vector<double> soft_table;
     if (soft && M <= RT_MAX_MATERIALS) {
-        static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
         try {
             soft_table.resize((size_t)6 * M);
         } catch (const std::bad_alloc &) {
             return fail(ctx, RT_ERR_ALLOC, "out of host memory");
         }
-        for (int m = 0; m < M; ++m)
-            for (int i = 0; i < 6; ++i) soft_table[(size_t)6 * m + i] = i < cols ? materials[(size_t)cols * m + i] : pad[i];
-        for (int m = 0; m < M; ++m) soft_table[(size_t)6 * m + 1] = soft_table[(size_t)6 * m + 1] / (double)shadow_samples;
+        put_rows(soft_table.data(), 6, materials, cols, M);
+        for (int m = 0; m < M; ++m) soft_table[(size_t)6 * m + 1] /= (double)shadow_samples;
         materials = soft_table.data();
         cols = 6;
     }
@@ -961,8 +931,9 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
         // the lens kernels are scatter kernels: a table of 3 or 5 columns gets a copy padded to six (trans 0, ior 1, rough 0)
         // behind its block, with the same ids; a 6-column one (an area-light scene's included) serves them as it is
-        lens_off = (M > 0 && cols < 6) ? mat_off + rt::mat_doubles(M, S, P, cols, soft) : mat_off;
-        std::vector<double> rec(mat_off + rt::mat_doubles(M, S, P, cols, soft) + ((M > 0 && cols < 6) ? rt::mat_doubles(M, S, P, 6) : 0), 0.0);
+        const size_t matd = rt::mat_doubles(M, S, P, family_of(M, cols, soft ? shadow_samples : 0, 0.0));
+        lens_off = (M > 0 && cols < 6) ? mat_off + matd : mat_off;
+        std::vector<double> rec(mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -1032,10 +1003,8 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
             if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
             if (soft) rec.back() = (double)shadow_samples;          // (rt::mat_doubles: the block's last double)
             if (lens_off != mat_off) {
-                static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
                 rec[lens_off] = (double)M;
-                for (int m = 0; m < M; ++m)
-                    for (int i = 0; i < 6; ++i) rec[lens_off + 1 + (size_t)6 * m + i] = i < cols ? materials[(size_t)cols * m + i] : pad[i];
+                put_rows(rec.data() + lens_off + 1, 6, materials, cols, M);
                 if (!ids.empty()) std::memcpy(rec.data() + lens_off + 1 + (size_t)6 * M, ids.data(), ids.size() * sizeof(int32_t));
             }
         }

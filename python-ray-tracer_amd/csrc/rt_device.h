@@ -1627,16 +1627,33 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
     }
 }
 
+// The feature family of a render kernel: which of its MAT, REFR, SCAT, SOFT and LENS arguments are set.  Each family's kernels
+// are the twins of the family before it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host
+// derives a launch's family from its scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
+enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT };
+constexpr int FAMILIES = 7;
+__host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
+__host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
+__host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
+__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT; }
+__host__ __device__ constexpr bool has_lens(Family f) { return f >= Family::LENS; }
+__host__ __device__ constexpr Family family(bool mat, bool refr, bool scat, bool soft, bool lens)
+{
+    return !mat ? Family::PLAIN : lens ? (soft ? Family::LENS_SOFT : Family::LENS) : soft ? Family::SOFT : scat ? Family::SCAT
+                                : refr ? Family::REFR : Family::MAT;
+}
+__host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
+
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
 __host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false, bool scat = false, bool soft = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0) + (scat ? 2 : 0) + (soft ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
 // The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
-// M, then the M x cols table {amb, lamb, refl} (cols = 5, refraction kernels: {amb, lamb, refl, trans, ior}; cols = 6, scatter
-// kernels: ..., rough), then S + P int32
-// material ids of the slots (padded to a double), and (soft: a scene of the area-light kernels) its shadow_samples n.  Material
+// M, then the M x table_cols(f) table {amb, lamb, refl} (5 columns, refraction kernels: {amb, lamb, refl, trans, ior}; 6, scatter
+// kernels and their twins: ..., rough), then S + P int32
+// material ids of the slots (padded to a double), and (has_soft(f): a scene of the area-light kernels) its shadow_samples n.  Material
 // kernels stage it at the end of their LDS image.
 __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
-__host__ __device__ inline size_t mat_doubles(int M, int S, int P, int cols = 3, bool soft = false) { return M > 0 ? 1 + (size_t)cols * M + ((size_t)S + P + 1) / 2 + (soft ? 1 : 0) : 0; }
+__host__ __device__ inline size_t mat_doubles(int M, int S, int P, Family f) { return M > 0 ? 1 + (size_t)table_cols(f) * M + ((size_t)S + P + 1) / 2 + (has_soft(f) ? 1 : 0) : 0; }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
@@ -1668,12 +1685,12 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
     return col ? t.total_col : (lanes ? t.total_lanes : t.total);
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
-// matd: mat_doubles() of a scene with materials (the image of the material kernels), 0 otherwise; refr: the refraction kernels;
-// scat: the scatter kernels; soft: the area-light kernels.
+// f, M: the kernels' family and the scene's material count (their image holds the material block, mat_doubles)
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
-                                            size_t matd = 0, bool refr = false, bool scat = false, bool soft = false)
+                                            Family f = Family::PLAIN, int M = 0)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, matd > 0, refr, scat, soft) * wgt + matd) * sizeof(double) +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, has_mat(f), has_refr(f), has_scat(f), has_soft(f)) * wgt +
+            mat_doubles(M, S, P, f)) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
            + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
@@ -1867,7 +1884,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         // (LENS: the block with rows of 6 the host names, a padded copy behind the scene's own for a table of 3 or 5 columns)
         const double *msrc = p.scene + (LENS ? (size_t)p.lens.mat : mat_offset(p.S, p.P, p.L, p.NC));
         nmat = (int)msrc[0];
-        const int nm = (int)mat_doubles(nmat, p.S, p.P, SCAT ? 6 : (REFR ? 5 : 3), SOFT);
+        const int nm = (int)mat_doubles(nmat, p.S, p.P, family(MAT, REFR, SCAT, SOFT, LENS));
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
         if constexpr (SOFT) nsh = (int)msrc[nm - 1];
     }
