@@ -276,7 +276,7 @@ constexpr bool missing_kernels_never_park()
             const rt::Family f = (rt::Family)fi;
             if (s.count || has_kernel(f, s)) continue;
             const size_t wgt = 64 * s.wpw;
-            const size_t least = rt::lds_slots(s.aa, true, s.mode >= 2, rt::has_mat(f), rt::has_refr(f), rt::has_scat(f), rt::has_soft(f)) * wgt * sizeof(double) +
+            const size_t least = rt::lds_slots(s.aa, true, s.mode >= 2, f) * wgt * sizeof(double) +
                                  wgt * sizeof(int) + 16;
             if (!s.park || s.mode >= 2 || least * (PARK_WAVES / s.wpw) <= CU_LDS) return false;
         }
@@ -289,8 +289,7 @@ const void *kernel_at()
 {
     constexpr Shape s = SHAPES[I];
     if constexpr (has_kernel(F, s))
-        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, rt::has_mat(F), rt::has_refr(F), rt::has_scat(F),
-                                               rt::has_soft(F), rt::has_lens(F)>;
+        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F>;
     else
         return nullptr;
 }
@@ -549,7 +548,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     const int gshift = ctx->order_group >= 0 ? ctx->order_group : (wpw == 2 ? 3 : 2);
     // Four-wave kernels: the order's items are TILES, not blocks of four neighbouring tiles (rt_device.h: KParams::order_tiles) —
     // a workgroup's four waves are then tiles of equal cost, end together and free their slots together.
-    const bool otiles = wpw >= RT_TILE_ORDER_MIN_WPW && ctx->order_tiles && feedback;
+    const bool otiles = wpw >= rt::TILE_ORDER_MIN_WPW && ctx->order_tiles && feedback;
     const int wshift = wpw == 4 ? 2 : 1;
     const unsigned items = otiles ? grid * (unsigned)wpw : grid;          // entries of one permutation
     rt_ctx::Feedback::Key key;

@@ -35,34 +35,26 @@
 #pragma clang fp contract(off)
 
 // Build-time knobs (A/B builds for tools/ab_bench.py); the defaults are the measured best on MI355X:
-//   RT_PREFILTER        float32 cull in front of the float64 sphere tests            (C2 -23 %, C4 -63 %)
 //   RT_FAST_NORMALIZE   shared-reciprocal normalize instead of sqrt + three divisions (C2 -10 %)
 //   RT_FAST_DIVSQRT     0 = the backend's full f64 division / sqrt in the scene queries (div_inrange, sqrt_inrange)
 //   RT_CLUSTER_MIN      sphere count above which the scene is stored in clusters of 8
-//   RT_W_PARK, RT_W_AAPARK  waves/SIMD the LDS-parked variants are compiled for
-#ifndef RT_PREFILTER
-#define RT_PREFILTER 1
-#endif
+//   RT_MAX_CULL_TABLE_BYTES  LDS budget of a workgroup's anchored cull table
+//   RT_W_PARK, RT_W_AAPARK, RT_W_LANES  waves/SIMD the LDS-parked, parked AA and lane-owned variants are compiled for
+// and two measurement builds: RT_REGION_STATS (tools/region_stats.py) and RT_LANE_STATS (tools/lane_stats.py).
 #ifndef RT_FAST_DIVSQRT
 #define RT_FAST_DIVSQRT 1
-#endif
-#ifndef RT_CULL_PAIRS_WPW2
-#define RT_CULL_PAIRS_WPW2 1   // the two-wave kernels too: 16 spheres -3 %, the headline -0.6 %
-#endif
-#ifndef RT_SHADOW_EXIT_CHECKS
-#define RT_SHADOW_EXIT_CHECKS 0
 #endif
 #ifndef RT_FAST_NORMALIZE
 #define RT_FAST_NORMALIZE 1
 #endif
-#ifndef RT_OPAQUE_ARGS
-#define RT_OPAQUE_ARGS 1
+#ifndef RT_W_PARK
+#define RT_W_PARK 7
 #endif
-#ifndef RT_OPAQUE_PLANE_CODE
-#define RT_OPAQUE_PLANE_CODE 1
+#ifndef RT_W_AAPARK
+#define RT_W_AAPARK 7   // 72 VGPRs with a few spills (76 B/lane of scratch) still beat 5 waves/SIMD without: -9 %
 #endif
-#ifndef RT_LAZY_RENORM
-#define RT_LAZY_RENORM 0
+#ifndef RT_W_LANES
+#define RT_W_LANES 4    // lane-owned traversal (clustered scenes: the LDS image bounds the occupancy at about 4 anyway) wants registers
 #endif
 
 namespace rt {
@@ -71,6 +63,7 @@ constexpr int TILE = 8;            // 8x8 pixels per wavefront
 // Tiles (wavefronts) per workgroup: a template parameter of the kernel, chosen per scene by the host.  Small
 // workgroups start and retire at a finer grain (C2: 2 waves beat 4 by 3 %); every workgroup stages its own copy
 // of the scene and its cull tables, so bigger scenes want bigger workgroups (C4: 4 waves beat 2 by 24 %, C5 by 69 %).
+constexpr int TILE_ORDER_MIN_WPW = 4;   // workgroups of this many waves or more may be dispatched tile by tile (render_kernel, dispatch)
 constexpr int TABLE_THREADS = 256; // tables_kernel's workgroup
 constexpr int SPH_STRIDE = 8;      // doubles per sphere record: cx,cy,cz,r2, R,G,B, caller's index
 constexpr int PL_STRIDE = 16;      // ox,oy,oz,nx,ny,nz, Nx,Ny,Nz, bNx,bNy,bNz, R,G,B, axis code (0 general, +-1/2/3 = +-e_x/y/z)
@@ -323,8 +316,20 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
     }
 };
 
+// The feature family of a render kernel (its last template argument).  Each family's kernels are the twins of the family before
+// it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host derives a launch's family from its
+// scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
+enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT };
+constexpr int FAMILIES = 7;
+__host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
+__host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
+__host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
+__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT; }
+__host__ __device__ constexpr bool has_lens(Family f) { return f >= Family::LENS; }
+__host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
+
 // Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
-// its running reflection weight W.  An empty struct, and every use a no-op, in the kernels of scenes without materials.
+// its running reflection weight W.  An empty struct, and every use a no-op, in the kernels of scenes without materials (PLAIN).
 // Three per-thread LDS slots from WSLOT on (lds_slots) hold W, and the Lambert coefficient and reflectivity of the lane's current
 // hit, copied there from the table entry once per hit: no VGPR holds a coefficient or the entry's address across the light
 // loop (with them in registers seven of the 22 material kernels spilled more than their default twins).  The slots are addressed
@@ -342,12 +347,9 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // nsh is the scene's shadow_samples n (the last double of the material block).
 // LENS (depth-of-field kernels, rt_set_lens with an aperture > 0; SCAT too): no slot; the primary ray does not start at the
 // camera, so trace 0's closest-hit query takes the origin form of the cull (trace_bounce).
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false, bool LENS = false> struct MatState {
-    static constexpr bool refr = false, scat = false, soft = false, lens = false;
-};
-template <int WSLOT, bool FRESH, bool REFR, bool SCAT, bool SOFT, bool LENS> struct MatState<true, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> {
-    static constexpr bool refr = REFR, scat = SCAT, soft = SOFT, lens = LENS;
-    static constexpr int COLS = SCAT ? 6 : (REFR ? 5 : 3);   // doubles per table row
+template <Family F, int WSLOT, bool FRESH> struct MatState {
+    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F);
+    static constexpr int COLS = table_cols(F);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
     int nsh;                   // SOFT: shadow samples per light (1 otherwise, unused)
@@ -365,6 +367,9 @@ template <int WSLOT, bool FRESH, bool REFR, bool SCAT, bool SOFT, bool LENS> str
         const int m = ((lds_ci32 *)(size_t)i)[slot];
         return (volatile const lds_f64 *)(size_t)t + COLS * m;
     }
+};
+template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
+    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -743,27 +748,21 @@ __device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, i
 // A wave-uniform kernel argument made opaque at its point of use: the value stays where it is (a scalar register), but
 // what is derived from it (a comparison, a select) is re-derived there with scalar instructions instead of being hoisted
 // out of the bounce loop into scalar registers the kernel does not have — hoisted values come back as v_readlane, a VALU
-// slot each, at every use (RT_OPAQUE_ARGS = 0 leaves it to the compiler).
+// slot each, at every use.
 __device__ __forceinline__ int opaque(int x)
 {
-#if RT_OPAQUE_ARGS
     asm volatile("" : "+s"(x));
-#endif
     return x;
 }
 
 __device__ __forceinline__ int plane_code(const KParams &p, int k)
 {
-#if RT_OPAQUE_PLANE_CODE
     // the decoded code and the booleans derived from it are loop-invariant, and the compiler hoists them out of the bounce
     // loop — into scalar registers it does not have: they come back as v_readlane (a VALU slot each) at every use.
     // Re-deriving them from the one kernel-argument word costs scalar instructions only.
     unsigned c = p.plane_codes;
     asm volatile("" : "+s"(c));
     return k < 4 ? (int)(signed char)(c >> (8 * k)) : 0;
-#else
-    return k < 4 ? (int)(signed char)(p.plane_codes >> (8 * k)) : 0;
-#endif
 }
 
 __device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int code, const V3 &o, const V3 &d, double &den, double &num)
@@ -1024,7 +1023,7 @@ __device__ __forceinline__ bool lanes_any(const Lds &lds, const KParams &p, int 
     } else add_origin(q, o, p.extent2);
     bool occ = false;
     for (int cb = 0; cb < lds.NC; cb += 32) {
-        if ((RT_SHADOW_EXIT_CHECKS || cb > 0) && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // (nothing is occluded before the first block)
+        if (cb > 0 && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // (nothing is occluded before the first block)
         const int nc = lds.NC - cb < 32 ? lds.NC - cb : 32;
         unsigned cm = lane_cluster_bits<ANCH>(lds, anchor, cb, nc, q, p.extent2);
         RT_MARK(7);
@@ -1073,9 +1072,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(0);
-#if RT_PREFILTER
     const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-#endif
     double bestn = __builtin_inf();
     int bidx = -1;
     constexpr bool F32 = MODE >= 1;                           // sphere records: the float32 LDS table (see sphere_hot)
@@ -1087,14 +1084,9 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     } else
     for (int k0 = 0; k0 < S; k0 += 64) {
       const int n = (S - k0 < 64) ? S - k0 : 64;
-#if RT_PREFILTER
-      unsigned long long mask;
       // the float32 ray is rebuilt per chunk so that it is not live during the float64 phase
-      mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, -1);
+      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, -1);
       mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);       // padding slots certify themselves, except to a NaN ray
-#else
-      unsigned long long mask = (n == 64) ? ~0ull : ((1ull << n) - 1ull);
-#endif
       RT_MARK(1);
       while (mask) {                                          // spheres some live lane might hit, ascending
         const int k = k0 + __builtin_ctzll(mask);
@@ -1132,49 +1124,34 @@ __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const 
 {
     const int P = opaque(p.P);
     const int S = p.S;
-    V3 R{0.0, 0.0, 0.0};
-    double a = 1.0;
-    // RT_LAZY_RENORM: the float32 cull runs on d itself (within 2^-52 of R: the same float32 values up to the
-    // rounding the margins already budget for) and R, a are formed only if some lane's mask is not empty
-    constexpr bool LAZY = RT_LAZY_RENORM && MODE == 0;
-    if (!LAZY) { R = renormalize_unit(d); a = dot3(R, R); }  // R == normalize(d), intersections.py:13
+    const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
+    const double a = dot3(R, R);
     RT_MARK(6);
-    bool a_sane = (a > 0.999999 && a < 1.000001);
-    bool haveR = !LAZY;
+    const bool a_sane = (a > 0.999999 && a < 1.000001);
     bool occ = false;
-#if RT_PREFILTER
     const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-#endif
     if (MODE >= 2 && lds.NC > 0 && lanes) {
         occ = (canchor >= 0) ? lanes_any<true>(lds, p, canchor, o, R, a, self) : lanes_any<false>(lds, p, -1, o, R, a, self);
     } else
     for (int k0 = 0; k0 < S; k0 += 64) {
       // "is any live lane still unoccluded" compiles to a v_cndmask + v_cmp pair (the bool lives as a lane mask that may hold
       // stale bits of inactive lanes): asked only where the answer can be no and skipping pays — not before the first chunk,
-      // not before the first sphere of the first chunk, not before a plane (RT_SHADOW_EXIT_CHECKS = 1: everywhere, as before)
-      if ((RT_SHADOW_EXIT_CHECKS || k0 > 0) && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;
+      // not before the first sphere of the first chunk, not before a plane (an empty exec mask skips a plane's test anyway)
+      if (k0 > 0 && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;
       const int n = (S - k0 < 64) ? S - k0 : 64;
-#if RT_PREFILTER
-      unsigned long long mask;
-      mask = cull_mask(lds, S, canchor, k0, n, o, LAZY ? d : R, p.extent2, self);
+      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, self);
       mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);
-#else
-      unsigned long long mask = (n == 64) ? ~0ull : ((1ull << n) - 1ull);
-#endif
-      if (LAZY && mask && !haveR) { R = renormalize_unit(d); a = dot3(R, R); a_sane = (a > 0.999999 && a < 1.000001); haveR = true; }
       RT_MARK(7);
       while (mask) {
-        if (RT_SHADOW_EXIT_CHECKS && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // every live lane already occluded
         const int k = k0 + __builtin_ctzll(mask);
         mask &= mask - 1ull;
         if (!occ) occ = sphere_any<(MODE >= 1)>(lds, k, o, R, a, a_sane);
-        if (!RT_SHADOW_EXIT_CHECKS && mask && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // (only if spheres remain)
+        if (mask && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // every live lane already occluded (only if spheres remain)
       }
       RT_MARK(8);
     }
     const double *pl = lds.recs() + (MODE >= 1 ? 0 : opaque(p.S) * SPH_STRIDE);
     for (int k = 0; k < P; ++k) {
-        if (RT_SHADOW_EXIT_CHECKS && __builtin_amdgcn_ballot_w64(!occ) == 0ull) break;   // (an empty exec mask skips the test below anyway)
         if (!occ) {
             const double *g = pl + k * PL_STRIDE;
             double den, num;
@@ -1332,10 +1309,10 @@ __device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, c
 
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
-// MAT: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
+// MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
 // b: the trace index (0: the primary ray); SCAT kernels scatter off rough surfaces with it, and clear `alive` where a scattered
 // path ends (absorption) after this trace's colour.
-template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
                                              V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
@@ -1383,7 +1360,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             N = V3{g[6], g[7], g[8]};                                         // float32-renormalised, host-side
             bN = V3{g[9], g[10], g[11]};                                      // BIAS*N as the reference rounds it
         }
-        if constexpr (MAT) {
+        if constexpr (MS::mat) {
             // the object's entry of the LDS material table (looked up after the normal: its address is live only here);
             // Lambert coefficient and reflectivity go to the lane's slots
             mp = ms.entry((type == HIT_SPHERE) ? idx : S + idx);
@@ -1439,7 +1416,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             const double *g = lt + m * LT_STRIDE;
             const V3 Ld = normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});   // common.py:84-91
             double lamb;
-            if constexpr (MAT) lamb = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave); else lamb = p.lamb;
+            if constexpr (MS::mat) lamb = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave); else lamb = p.lamb;
             const double k = lamb * dot3(Ld, N);                              // :99
             // :92-102 — the shadow query's answer is only used when k > 0; it has no other effect,
             // so lanes with k <= 0 (light behind the surface) do not ask.
@@ -1470,18 +1447,18 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 
 
 // trace.py:115-133.  Bounce 0 rays all start at the camera (cull anchor 0; LENS kernels: on the lens, none); later bounces have none.
-// MAT (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
+// MS::mat (per-object materials): bounce b >= 1 is weighted with W_b = ((refl_0 * refl_1) * ...) * refl_{b-1}, the reflectivities
 // of the surfaces the ray was reflected off, in place of p.refl_pow[b-1].  W stops changing where the path ends: the missed
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
 // SCAT: key is the sample's scatter_key, kept in its slot for the scatter.  SOFT: lkey is its soft_key, kept in its slot for
 // the light loop.
-template <bool PARK, int WGT, bool COUNT, int MODE, bool MAT, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
 __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
                                      unsigned key = 0u, unsigned lkey = 0u)
 {
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
-    if constexpr (MAT) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
+    if constexpr (MS::mat) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
     if constexpr (MS::scat) *ms.template at<WGT, MS::KEY>(lds.acc, lds.wave) = (double)key;
     if constexpr (MS::soft) *ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) = (double)lkey;
     for (int b = 0; b <= p.depth; ++b) {
@@ -1497,15 +1474,15 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE, MAT, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
+        trace_bounce<PARK, WGT, COUNT, MODE, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0)
             double wgt;
-            if constexpr (MAT) wgt = *ms.template at<WGT, MS::W>(lds.acc, lds.wave); else wgt = p.refl_pow[b - 1];
+            if constexpr (MS::mat) wgt = *ms.template at<WGT, MS::W>(lds.acc, lds.wave); else wgt = p.refl_pow[b - 1];
             const V3 a = acc.get();
             acc.set(V3{a.x + wgt * rgb.x, a.y + wgt * rgb.y, a.z + wgt * rgb.z});
         }
-        if constexpr (MAT) {                                                  // W_{b+1} = W_b * refl_b (W_1 = 1 * refl_0 = refl_0)
+        if constexpr (MS::mat) {                                              // W_{b+1} = W_b * refl_b (W_1 = 1 * refl_0 = refl_0)
             if (alive) {
                 volatile lds_f64 *w = ms.template at<WGT, MS::W>(lds.acc, lds.wave);
                 *w = *w * *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave);
@@ -1627,26 +1604,9 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
     }
 }
 
-// The feature family of a render kernel: which of its MAT, REFR, SCAT, SOFT and LENS arguments are set.  Each family's kernels
-// are the twins of the family before it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host
-// derives a launch's family from its scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
-enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT };
-constexpr int FAMILIES = 7;
-__host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
-__host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
-__host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
-__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT; }
-__host__ __device__ constexpr bool has_lens(Family f) { return f >= Family::LENS; }
-__host__ __device__ constexpr Family family(bool mat, bool refr, bool scat, bool soft, bool lens)
-{
-    return !mat ? Family::PLAIN : lens ? (soft ? Family::LENS_SOFT : Family::LENS) : soft ? Family::SOFT : scat ? Family::SCAT
-                                : refr ? Family::REFR : Family::MAT;
-}
-__host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
-
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
 __host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
-__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2 = false, bool mat = false, bool refr = false, bool scat = false, bool soft = false) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (mat ? 3 : 0) + (refr ? 4 : 0) + (scat ? 2 : 0) + (soft ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
+__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2, Family f) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (has_mat(f) ? 3 : 0) + (has_refr(f) ? 4 : 0) + (has_scat(f) ? 2 : 0) + (has_soft(f) ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
 // The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
 // M, then the M x table_cols(f) table {amb, lamb, refl} (5 columns, refraction kernels: {amb, lamb, refl, trans, ior}; 6, scatter
 // kernels and their twins: ..., rough), then S + P int32
@@ -1689,7 +1649,7 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
                                             Family f = Family::PLAIN, int M = 0)
 {
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, has_mat(f), has_refr(f), has_scat(f), has_soft(f)) * wgt +
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, f) * wgt +
             mat_doubles(M, S, P, f)) * sizeof(double) +
            ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
 #ifdef RT_REGION_STATS
@@ -1811,46 +1771,34 @@ __global__ __launch_bounds__(TABLE_THREADS) void tables_kernel(const KParams p, 
 
 // The MatState of a workgroup's material block matl (staged: M, table, ids) with W in the per-thread slot wslot.
 // SOFT: nsh is the scene's shadow_samples (the block's last double).
-template <bool MAT, int WSLOT, bool FRESH, bool REFR = false, bool SCAT = false, bool SOFT = false, bool LENS = false>
-__device__ __forceinline__ MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> mat_state(double *matl, int M, int nsh = 1)
+template <Family F, int WSLOT, bool FRESH>
+__device__ __forceinline__ MatState<F, WSLOT, FRESH> mat_state(double *matl, int M, int nsh = 1)
 {
     typedef __attribute__((address_space(3))) double lds_d;
-    typedef MatState<MAT, WSLOT, FRESH, REFR, SCAT, SOFT, LENS> MS;
-    if constexpr (MAT) return MS{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MS::COLS * M), nsh};
+    typedef MatState<F, WSLOT, FRESH> MS;
+    if constexpr (MS::mat) return MS{(unsigned)(size_t)(lds_d *)(matl + 1), (unsigned)(size_t)(lds_d *)(matl + 1 + MS::COLS * M), nsh};
     else return {};
 }
 
 // AA = false: aliasing off — instantiated separately so that the common case does not carry the tap loop's
 // live state (registers decide occupancy here).
+// F: the kernel's feature family (Family; PLAIN has none of these features).
 // MAT: the scene has a material table (per-object shading coefficients, rt_set_scene_materials).
-// REFR (with MAT only): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
-// SCAT (with REFR only): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
-// SOFT (with SCAT only): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
-// LENS (with SCAT only): the camera has an aperture (rt_set_lens): thin-lens primary rays (lens_ray).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, bool MAT = false, bool REFR = false, bool SCAT = false,
-          bool SOFT = false, bool LENS = false>
-#ifndef RT_W_PARK
-#define RT_W_PARK 7
-#endif
-#ifndef RT_W_AAPARK
-#define RT_W_AAPARK 7   // 72 VGPRs with a few spills (76 B/lane of scratch) still beat 5 waves/SIMD without: -9 %
-#endif
-#ifndef RT_W_LANES
-#define RT_W_LANES 4    // lane-owned traversal (clustered scenes: the LDS image bounds the occupancy at about 4 anyway) wants registers
-#endif
+// REFR (with MAT): the table has transparent rows (rt_set_scene_materials_ex): refraction continuations (refract_continue).
+// SCAT (with REFR): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
+// SOFT (with SCAT): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
+// LENS (with SCAT, and LENS_SOFT with SOFT): the camera has an aperture (rt_set_lens): thin-lens primary rays (lens_ray).
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, Family F = Family::PLAIN>
 __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT_W_AAPARK : 4) : (PARK ? RT_W_PARK : 5))) void render_kernel(const KParams p)
 {
     constexpr int WG_THREADS = 64 * WPW, WAVES_PER_WG = WPW;
     constexpr bool M2 = MODE >= 2;
     constexpr bool NOREC = MODE >= 1;
+    constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F);
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
     double *accum = lds_raw + nrec;
-    static_assert(MAT || !REFR, "refraction kernels are material kernels");
-    static_assert(REFR || !SCAT, "scatter kernels are refraction kernels");
-    static_assert(SCAT || !SOFT, "area-light kernels are scatter kernels");
-    static_assert(SCAT || !LENS, "lens kernels are scatter kernels");
-    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, MAT, REFR, SCAT, SOFT) * WG_THREADS);
+    int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, F) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
     const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
@@ -1866,12 +1814,10 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     {   // stage the packed scene and its float32 cull tables once per workgroup: two straight copies.  (The tables
         // used to be computed here, by every workgroup: 3 % of the frame's VALU instructions and a second barrier.)
         for (int i = threadIdx.x; i < nrec; i += WG_THREADS) lds_raw[i] = rec_src[i];
-#if RT_PREFILTER
         const int nf4 = (int)(ntab / 4);
         const f4 *src = reinterpret_cast<const f4 *>(p.ftab);
         f4 *dst = reinterpret_cast<f4 *>(sph32);
         for (int i = threadIdx.x; i < nf4; i += WG_THREADS) dst[i] = src[i];
-#endif
     }
     // MAT: the material block (mat_offset) behind the workgroup words (and the region counters of the measurement build)
 #ifdef RT_REGION_STATS
@@ -1884,7 +1830,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         // (LENS: the block with rows of 6 the host names, a padded copy behind the scene's own for a table of 3 or 5 columns)
         const double *msrc = p.scene + (LENS ? (size_t)p.lens.mat : mat_offset(p.S, p.P, p.L, p.NC));
         nmat = (int)msrc[0];
-        const int nm = (int)mat_doubles(nmat, p.S, p.P, family(MAT, REFR, SCAT, SOFT, LENS));
+        const int nm = (int)mat_doubles(nmat, p.S, p.P, F);
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];
         if constexpr (SOFT) nsh = (int)msrc[nm - 1];
     }
@@ -1893,11 +1839,11 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     // NC a constant 0 there, none of the cluster code is compiled into those kernels (the headline kernel sits in a narrow
     // register optimum)
 #ifdef RT_REGION_STATS
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2 && (WPW >= 4 || RT_CULL_PAIRS_WPW2), MODE >= 2, wgstat + 4, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, wgstat + 4, accum};
     for (int i = threadIdx.x & 63; i < 32; i += 64) lds.reg[(threadIdx.x >> 6) * 32 + i] = 0u;
     if ((threadIdx.x & 63) == 0) lds.reg[(threadIdx.x >> 6) * 32 + 31] = (unsigned)__builtin_amdgcn_s_memtime();
 #else
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2 && (WPW >= 4 || RT_CULL_PAIRS_WPW2), MODE >= 2, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, accum};
 #endif
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1919,17 +1865,14 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     // Four-wave kernels may dispatch TILE by tile (p.order_tiles): a workgroup holds its LDS image and — by the time three of its
     // waves have ended — three idle wave slots until its last wave ends, so its waves should be tiles of EQUAL cost, not
     // neighbours (measured on config 5: 3.26 of 4 wave slots per SIMD occupied on average with neighbours).
-#ifndef RT_TILE_ORDER_MIN_WPW
-#define RT_TILE_ORDER_MIN_WPW 4
-#endif
-    const bool by_tile = WPW >= RT_TILE_ORDER_MIN_WPW && p.order_tiles;
+    const bool by_tile = WPW >= TILE_ORDER_MIN_WPW && p.order_tiles;
     const int block = by_tile ? bid : (ord ? (int)ord[bid] : bid);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int tile_v = by_tile ? (ord ? (int)ord[bid * WAVES_PER_WG + wave_u] : bid * WAVES_PER_WG + wave_u) : block * WAVES_PER_WG + wave;
     // (wave-uniform, but loaded through a vector register: as a scalar it does not occupy a VGPR until the cost is recorded
     // at the end — the MODE 1 kernel spilled it, 8 bytes of scratch written per lane; the two-wave kernels keep their register
     // allocation as it is)
-    const int tile = WPW >= RT_TILE_ORDER_MIN_WPW ? __builtin_amdgcn_readfirstlane(tile_v) : tile_v;
+    const int tile = WPW >= TILE_ORDER_MIN_WPW ? __builtin_amdgcn_readfirstlane(tile_v) : tile_v;
     if (tile >= p.ntiles) return;                                             // whole wave, after the barriers
     const unsigned long long t_begin = (p.tile_cycles || p.cost) ? __builtin_amdgcn_s_memtime() : 0ull;
     const int tx = div_by(tile, p.tiles_y, p.tiles_y_magic, p.tiles_y_shift), ty = tile - tx * p.tiles_y;
@@ -1949,8 +1892,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
 
     const V3 o{p.cam_o[0], p.cam_o[1], p.cam_o[2]};                           // kernels.py:16
     RayCount<COUNT> cnt;
-    constexpr int WSLOT = lds_slots(AA, PARK, M2);                           // MAT: the slot of W
-    auto ms = mat_state<MAT, WSLOT, !PARK || MODE == 3, REFR, SCAT, SOFT, LENS>(matl, nmat, nsh);
+    constexpr int WSLOT = lds_slots(AA, PARK, M2, Family::PLAIN);            // MAT: the slot of W
+    auto ms = mat_state<F, WSLOT, !PARK || MODE == 3>(matl, nmat, nsh);
     // SCAT: the scatter key of a sample is (X, Y, s) on the half-pixel lattice, pixel centres at (2x, 2y), absolute columns
     // (the lattice kernels' own coordinates); s the stochastic sample, else 0
     // SOFT: the light key (soft_key) of the same (X, Y, s)
@@ -1965,7 +1908,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         V3 ro = o, rd;
         if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
         else rd = primary_dir(p, P0);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms)>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -2003,7 +1946,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             V3 ro = o, rd;
             if constexpr (LENS) lens_ray(p, lx, ly, stoch ? (unsigned)tap : 0u, Pt, ro, rd);
             else rd = primary_dir(p, Pt);
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, MAT, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

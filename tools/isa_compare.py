@@ -8,16 +8,14 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
   * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
     kernel's own symbol renumbered, must be identical in the working tree;
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
-A render_kernel instantiation is matched by its template arguments; trailing `false` arguments past the sixth (the MAT, REFR,
-SCAT, SOFT and LENS parameters, rt_device.h) are ignored, so the default kernels of a tree with material, refraction, scatter,
-area-light or lens kernels match those of a tree without, the material kernels (MAT = true, REFR = false) those of a tree without
-refraction kernels, the refraction kernels (REFR = true, SCAT = false) those of a tree without scatter kernels, the scatter
-kernels (SCAT = true, SOFT = false) those of a tree without area-light kernels, and the area-light kernels (SOFT = true,
-LENS = false) those of a tree without lens kernels.  Kernels of the working tree that the base does not have are listed as NEW.
---twins also prints each material kernel (MAT = true) next to its default twin, each refraction kernel (REFR = true) next to
-its material twin, each scatter kernel (SCAT = true) next to its refraction twin and each area-light kernel (SOFT = true) next
-to its scatter twin, and each lens kernel (LENS = true) next to its scatter or area-light twin.  Exit status 1 if any kernel
-differs.
+A render_kernel instantiation is matched by its first six template arguments (AA, PARK, WPW, COUNT, LAT, MODE) and its feature
+family (rt::Family, rt_device.h), whichever way the tree spells the family: as the seventh argument `Family F` (mangled
+`LNS_6FamilyE<n>E`), or, in trees from before that parameter, as up to five trailing bool arguments MAT, REFR, SCAT, SOFT and
+LENS, of which a missing one counts as false.  So a tree of either form compares with one of the other, and a tree with more
+families with one with fewer.  Kernels of the working tree that the base does not have are listed as NEW.
+--twins also prints each MAT kernel next to its PLAIN twin, each REFR kernel next to its MAT twin, each SCAT kernel next to its
+REFR twin, each SOFT kernel next to its SCAT twin, and each LENS and LENS_SOFT kernel next to its SCAT and SOFT twin.  Exit
+status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -37,17 +35,21 @@ def build(tree):
     return open(os.path.join(tree, CSRC, "rt_kernel.gfx950.s")).read(), r.stderr
 
 
+FAMILIES = ("", "mat", "refr", "scat", "soft", "lens", "lens_soft")   # rt::Family in enum order; "" is PLAIN
+
+
 def key(name):
-    """Kernel symbol -> (kernel, template arguments without trailing false ones past the sixth), and its family:
-    "" (default), "mat" (MAT = true), "refr" (REFR = true), "scat" (SCAT = true), "soft" (SOFT = true), "lens" (LENS = true,
-    SOFT = false) or "lens_soft" (LENS = true, SOFT = true)."""
-    m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)EEvNS_7KParamsE$", name)
+    """Kernel symbol -> ((kernel, its first six template arguments), its family: one of FAMILIES)."""
+    m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)(?:LNS_6FamilyE(\d+)E)?EEvNS_7KParamsE$", name)
     if not m:
         return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
-    lens = len(args) >= 11 and args[10] == "1"
-    fam = ("lens_soft" if lens and args[9] == "1" else "lens" if lens else "soft" if len(args) >= 10 and args[9] == "1" else "scat" if len(args) >= 9 and args[8] == "1" else "refr" if len(args) >= 8 and args[7] == "1" else
-           "mat" if len(args) >= 7 and args[6] == "1" else "")
+    if m.group(3) is not None:
+        fam = FAMILIES[int(m.group(3))]
+    else:
+        mat, refr, scat, soft, lens = ((args[6:] + ["0"] * 5)[i] == "1" for i in range(5))
+        fam = (("lens_soft" if soft else "lens") if lens else "soft" if soft else "scat" if scat else "refr" if refr else
+               "mat" if mat else "")
     return (m.group(1),) + tuple(args[:6]), fam
 
 
