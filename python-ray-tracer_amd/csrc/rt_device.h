@@ -424,6 +424,9 @@ struct Lds {
     int wave;              // this wave's index in its workgroup (scalar)
     bool pairs;            // a compile-time constant per kernel: the wave-uniform cull keeps two table entries in flight (cull4)
     bool groups;           // a compile-time constant per kernel: test a chunk's group of clusters before its clusters (MODE 2 kernels)
+    bool trim;             // a compile-time constant per kernel: the instruction trims measured on the two-wave kernels without a material
+                           // table — shadow queries keep their occlusion flag as one scalar lane mask (any_hit_masks), and a plane with
+                           // normal -e_i is tested without negating den and num (plane_den_num)
 #ifdef RT_REGION_STATS
     unsigned *reg;         // measurement build: 32 words per wave — cycles per code region [0, 24), bounce class [30], last stamp [31]
 #endif
@@ -765,7 +768,13 @@ __device__ __forceinline__ int plane_code(const KParams &p, int k)
     return k < 4 ? (int)(signed char)(c >> (8 * k)) : 0;
 }
 
-__device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int code, const V3 &o, const V3 &d, double &den, double &num)
+// no_negate (Lds::trim): for a normal -e_i both den and num are negated, and everything a query does with the pair is the same for
+// (-den, -num) as for (den, num) — |den| < 0.001, |num| against |den|, whether the signs agree, and the quotient bit for bit
+// (IEEE division, and div_inrange: rcp is odd and each of its steps negates exactly; only a ZERO quotient may change sign, and
+// t > 0 fails for both).  Leaving the negation out saves two v_xor and two v_cndmask per test, for either sign of the code.
+// tests/algo/plane_sign_check.c replays it.
+__device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int code, const V3 &o, const V3 &d, double &den, double &num,
+                                              bool no_negate = false)
 {
     if (code == 0) {
         const V3 n{g[3], g[4], g[5]};
@@ -778,7 +787,7 @@ __device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int 
         if (a == 1)      { dc = d.x; lp = g[0] - o.x; }
         else if (a == 2) { dc = d.y; lp = g[1] - o.y; }
         else             { dc = d.z; lp = g[2] - o.z; }
-        if (code > 0) { den = dc; num = lp; } else { den = -dc; num = -lp; }
+        if (code > 0 || no_negate) { den = dc; num = lp; } else { den = -dc; num = -lp; }
     }
 }
 
@@ -864,6 +873,48 @@ __device__ __forceinline__ bool sphere_any(const Lds &lds, int k, const V3 &o, c
         }
     }
     return false;
+}
+
+// The lanes of a scalar lane mask, back as a per-lane bool (one v_cndmask; only where a rare per-lane path is entered).
+__device__ __forceinline__ bool lane_of(lanemask m)
+{
+    unsigned x; asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(x) : "s"(m)); return x != 0u;
+}
+__device__ __forceinline__ lanemask lanes_where(bool c) { return __builtin_amdgcn_ballot_w64(c); }   // of a plain compare: the v_cmp itself
+
+// sphere_any for the whole wave at once: the live lanes for which the sphere reports 0 < t < 999, as a lane mask.  The same
+// compares, each written straight into a scalar register pair and combined on the scalar unit: as nested per-lane conditions
+// every level is an exec-mask region (s_and_saveexec, a branch, s_or exec) and the bool that leaves them a v_cndmask + v_cmp
+// pair at every use.  D >= 0 rules out a NaN s (it would have made D a NaN), so under it !(s >= 0) is s < 0.
+// a_sane: the lanes whose a is within 1e-6 of 1.  The exact path (origin inside the sphere, a far hit) is entered by the
+// wave only if some lane needs it.
+template <bool F32>
+__device__ __forceinline__ lanemask sphere_any_mask(const Lds &lds, int k, const V3 &o, const V3 &R, double a, lanemask a_sane)
+{
+    const SphHot g = sphere_hot<F32>(lds, k);
+    const V3 Lv{o.x - g.x, o.y - g.y, o.z - g.z};
+    const double s = dot3(Lv, R);
+    const double cc = dot3(Lv, Lv) - g.r2;
+    const double D = s * s - a * cc;
+    const lanemask dpos = lanes_where(D >= 0.0), sneg = lanes_where(s < 0.0);
+    const lanemask cand = dpos & (sneg | lanes_where(!(cc >= 0.0)));          // D >= 0 && !(s >= 0 && cc >= 0)
+    const lanemask fast = dpos & sneg & lanes_where(-s < 499.0) & lanes_where(D < 249001.0) & a_sane;   // see sphere_any
+    lanemask hit = fast;
+    const lanemask slow = cand & ~fast;
+    if (slow != 0ull) {
+        bool h = false;
+        if (lane_of(slow)) {
+            const double q = __builtin_sqrt(D);
+            double n = -s - q;
+            if (!(n > 0.0)) n = -s + q;
+            if (n > 0.0) {
+                const double t = n / a;
+                h = 999.0 > t && t > 0.0;
+            }
+        }
+        hit |= lanes_where(h);
+    }
+    return hit;
 }
 
 
@@ -1105,7 +1156,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     for (int k = 0; k < P; ++k) {                             // intersections.py:41-68
         const double *g = pl + k * PL_STRIDE;
         double den, num;
-        plane_den_num(g, plane_code(p, k), o, d, den, num);   // :52, :59-61
+        plane_den_num(g, plane_code(p, k), o, d, den, num, lds.trim);   // :52, :59-61
         if (!(__builtin_fabs(den) < 0.001)) {                 // :55
             const double t = div_inrange(num, den);           // :63
             if (best > t && t > 0.0) { best = t; idx = k; type = HIT_PLANE; }
@@ -1115,6 +1166,60 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     RT_MARK(3);
 }
 
+// any_hit's sphere and plane loops with the occlusion flag as ONE lane mask in a scalar register pair (Lds::trim: the
+// two-wave kernels without a material table): "is any live lane still unoccluded" is then two scalar instructions wherever
+// it is asked, no test runs under a per-lane condition, and the flag becomes a per-lane bool once, at the end.  Same compares
+// on the same values as any_hit's loops below; a lane that is already occluded is tested again (its answer can only stay).
+__device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self)
+{
+    const int P = opaque(p.P);
+    const int S = p.S;
+    const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
+    const double a = dot3(R, R);
+    RT_MARK(6);
+    const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
+    const lanemask live = lanes_where(true);
+    const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
+    lanemask occ = 0ull;
+    for (int k0 = 0; k0 < S; k0 += 64) {
+      if (k0 > 0 && (live & ~occ) == 0ull) break;
+      const int n = (S - k0 < 64) ? S - k0 : 64;
+      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, self);
+      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);
+      RT_MARK(7);
+      while (mask) {
+        const int k = k0 + __builtin_ctzll(mask);
+        mask &= mask - 1ull;
+        occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
+        if (mask && (live & ~occ) == 0ull) break;
+      }
+      RT_MARK(8);
+    }
+    const double *pl = lds.recs() + opaque(p.S) * SPH_STRIDE;
+    for (int k = 0; k < P; ++k) {
+        if ((live & ~occ) == 0ull) break;
+        const double *g = pl + k * PL_STRIDE;
+        double den, num;
+        plane_den_num(g, plane_code(p, k), o, d, den, num, true);
+        const double an = __builtin_fabs(num), ad = __builtin_fabs(den);
+        // the signs agree (any_hit: num > 0 && den > 0 || num < 0 && den < 0) where the sign bits do and neither is zero; den is
+        // not zero under !(|den| < 0.001); a NaN num fails |num| > 0, a NaN den every test of the quotient below
+        int sx = (int)(__builtin_bit_cast(unsigned long long, num) >> 32) ^ (int)(__builtin_bit_cast(unsigned long long, den) >> 32);
+        asm("" : "+v"(sx));                                                   // (a 32-bit compare of the high words' xor, not a 64-bit one of both words')
+        const lanemask ahead = lanes_where(!(ad < 0.001)) & lanes_where(sx >= 0) & lanes_where(an > 0.0);   // t = num/den > 0
+        const lanemask sure = lanes_where(an < 998.0 * ad);                   // t < 999 for certain (see any_hit)
+        occ |= ahead & sure;
+        const lanemask edge = ahead & ~sure & ~occ;
+        if (edge != 0ull) {                                                   // far along a grazing ray: the rounded quotient decides
+            bool h = false;
+            if (lane_of(edge) && !(an > 1000.0 * ad)) { const double t = num / den; h = 999.0 > t && t > 0.0; }
+            occ |= lanes_where(h);
+        }
+    }
+    RT_MARK(9);
+    return lane_of(occ);
+}
+
 // trace.py:92-96: the shadow query only asks "does anything report 0 < t < 999" (any hit).
 // Called with the lanes that need the answer active; returns true if occluded.
 // anchor = cull-table index of the light the ray points at; self = index of the sphere the ray
@@ -1122,6 +1227,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
 template <int MODE>
 __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self, bool lanes = true)
 {
+    if (MODE == 0 && lds.trim) return any_hit_masks(lds, p, o, d, anchor, self);
     const int P = opaque(p.P);
     const int S = p.S;
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
@@ -1839,11 +1945,11 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     // NC a constant 0 there, none of the cluster code is compiled into those kernels (the headline kernel sits in a narrow
     // register optimum)
 #ifdef RT_REGION_STATS
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, wgstat + 4, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, wgstat + 4, accum};
     for (int i = threadIdx.x & 63; i < 32; i += 64) lds.reg[(threadIdx.x >> 6) * 32 + i] = 0u;
     if ((threadIdx.x & 63) == 0) lds.reg[(threadIdx.x >> 6) * 32 + 31] = (unsigned)__builtin_amdgcn_s_memtime();
 #else
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, accum};
 #endif
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -1,0 +1,117 @@
+/* CPU replay of two restatements in rt_device.h's plane tests (Lds::trim kernels).
+ *
+ * 1. plane_den_num(no_negate): for a plane whose stored normal is -e_i the straightforward form negates both den and num.
+ *    Everything a query does with the pair must be the same for (den, num) and (-den, -num):
+ *      closest_hit:  !(|den| < 0.001), t = div_inrange(num, den), best > t && t > 0
+ *      any_hit:      !(|den| < 0.001), the signs agree, |num| < 998 |den|, |num| > 1000 |den|, t = num / den, 999 > t && t > 0
+ *    t is compared bit for bit (NaNs: both NaN; zeros: both zero — div_inrange's last fma gives a zero quotient the sign of
+ *    r, not of num/den, and a zero t of either sign is no hit: t > 0 fails).  div_inrange is replayed with a reciprocal
+ *    seed that is odd in its operand, as v_rcp_f64 is, and up to 2^-24 off.
+ * 2. any_hit_masks: "num > 0 && den > 0 || num < 0 && den < 0" restated as "the sign bits agree, |num| > 0" under
+ *    !(|den| < 0.001); the whole occlusion decision of the straightforward form (any_hit) against the restated one.
+ *
+ * Operands: every pair from a list of special values (zeros, denormals, the 0.001 and 998/999/1000 boundaries and their
+ * neighbours, huge values, infinities, NaN), then random pairs over many magnitudes.  Built and run by tests/test_algorithms_trim.py. */
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+static uint64_t s[2] = {0x9E3779B97F4A7C15ull, 0xD1B54A32D192ED03ull};
+static inline uint64_t rnd(void) { uint64_t a = s[0], b = s[1]; s[0] = b; a ^= a << 23; s[1] = a ^ b ^ (a >> 17) ^ (b >> 26); return s[1] + b; }
+static inline double urand(void) { return (double)(rnd() >> 11) * (1.0 / 9007199254740992.0); }
+static inline uint64_t bits(double x) { uint64_t u; memcpy(&u, &x, 8); return u; }
+static inline int same_bits(double a, double b) { return bits(a) == bits(b) || (a != a && b != b) || (a == 0.0 && b == 0.0); }
+
+static double rcp_seed(double b)                          /* odd in b; relative error up to 2^-24, a function of |b| */
+{
+    const double m = fabs(b);
+    const double e = ((double)((bits(m) * 0x9E3779B97F4A7C15ull) >> 40) * 0x1p-24 * 2 - 1) * 0x1p-24;
+    return copysign((1.0 / m) * (1.0 + e), b);
+}
+static double div_inrange(double a, double b)
+{
+    double r = rcp_seed(b);
+    double e = fma(-b, r, 1.0); r = fma(r, e, r);
+    e = fma(-b, r, 1.0); r = fma(r, e, r);
+    const double q = a * r;
+    return fma(fma(-b, q, a), r, q);
+}
+
+/* closest_hit's use of one plane: returns 1 and *t if the plane is a candidate (before the comparison with `best`) */
+static int closest_use(double den, double num, double *t)
+{
+    if (!(fabs(den) < 0.001)) { *t = div_inrange(num, den); return 1; }
+    return 0;
+}
+/* any_hit's plane test, as written there */
+static int any_straight(double den, double num)
+{
+    if (!(fabs(den) < 0.001)) {
+        const double an = fabs(num), ad = fabs(den);
+        const int same_sign = (num > 0.0 && den > 0.0) || (num < 0.0 && den < 0.0);
+        if (same_sign) {
+            if (an < 998.0 * ad) return 1;
+            else if (!(an > 1000.0 * ad)) { const double t = num / den; if (999.0 > t && t > 0.0) return 1; }
+        }
+    }
+    return 0;
+}
+/* any_hit_masks' plane test: flat conditions, sign bits */
+static int any_masks(double den, double num)
+{
+    const double an = fabs(num), ad = fabs(den);
+    const int32_t sx = (int32_t)(bits(num) >> 32) ^ (int32_t)(bits(den) >> 32);
+    const int ahead = !(ad < 0.001) & (sx >= 0) & (an > 0.0);
+    const int sure = an < 998.0 * ad;
+    if (ahead & sure) return 1;
+    if (ahead & !sure) {
+        if (!(an > 1000.0 * ad)) { const double t = num / den; return 999.0 > t && t > 0.0; }
+    }
+    return 0;
+}
+
+static long bad = 0;
+static void check(double den, double num)
+{
+    double t1 = 0, t2 = 0;
+    const int c1 = closest_use(den, num, &t1), c2 = closest_use(-den, -num, &t2);
+    if (c1 != c2 || (c1 && !same_bits(t1, t2))) { if (bad++ < 5) fprintf(stderr, "CLOSEST den=%a num=%a: %d %a / %d %a\n", den, num, c1, t1, c2, t2); }
+    const int a0 = any_straight(den, num), a1 = any_straight(-den, -num), a2 = any_masks(den, num), a3 = any_masks(-den, -num);
+    if (a0 != a1 || a0 != a2 || a0 != a3) { if (bad++ < 5) fprintf(stderr, "ANY den=%a num=%a: %d %d %d %d\n", den, num, a0, a1, a2, a3); }
+    if (!same_bits(num / den, (-num) / (-den))) { if (bad++ < 5) fprintf(stderr, "DIV den=%a num=%a\n", den, num); }
+}
+
+int main(int argc, char **argv)
+{
+    const long n = argc > 1 ? atol(argv[1]) : 5000000;
+    double sp[256];
+    int ns = 0;
+    const double base[] = {0.0, 0x1p-1074, 0x1p-1040, 0x1p-1022, 1e-300, 1e-30, 0.000999, 0.001, 0.0010000001, 0.5, 1.0, 3.0,
+                           997.0, 998.0, 999.0, 1000.0, 1001.0, 1e6, 1e30, 1e300, 0x1.fffffffffffffp1023, INFINITY, NAN};
+    for (unsigned i = 0; i < sizeof base / sizeof *base; ++i)
+        for (int sg = 0; sg < 2; ++sg) {
+            const double v = sg ? -base[i] : base[i];
+            sp[ns++] = v;
+            if (v == v && fabs(v) > 0 && fabs(v) < INFINITY) { sp[ns++] = nextafter(v, INFINITY); sp[ns++] = nextafter(v, -INFINITY); }
+        }
+    long checked = 0;
+    for (int i = 0; i < ns; ++i)
+        for (int j = 0; j < ns; ++j) {
+            check(sp[i], sp[j]); ++checked;
+            /* num on the 998 / 999 / 1000 |den| boundaries of this den */
+            const double m[] = {997.9999999, 998.0, 998.0000001, 999.0, 999.0000001, 1000.0, 1000.0000001};
+            for (unsigned k = 0; k < sizeof m / sizeof *m; ++k) { check(sp[i], sp[i] * m[k]); check(sp[i], -sp[i] * m[k]); checked += 2; }
+        }
+    for (long it = 0; it < n; ++it) {
+        const int mode = it & 7;
+        double den = (urand() * 2 - 1) * exp((urand() - 0.5) * (mode & 1 ? 400.0 : 30.0));
+        double num = (urand() * 2 - 1) * exp((urand() - 0.5) * (mode & 2 ? 400.0 : 30.0));
+        if (mode == 4) den = copysign(0.001 + (urand() - 0.5) * 1e-12, den);                 /* around |den| = 0.001 */
+        if (mode >= 5) num = den * (mode == 5 ? 998.0 : mode == 6 ? 999.0 : 1000.0) * (1.0 + (urand() - 0.5) * 0x1p-48) * (urand() < 0.5 ? -1 : 1);
+        check(den, num); ++checked;
+    }
+    printf("checked=%ld mismatches=%ld\n", checked, bad);
+    return bad ? 1 : 0;
+}
