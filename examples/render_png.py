@@ -2,7 +2,8 @@
 """Render a frame with the `Renderer` API and save it as a PNG.
 
     python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
-                                  [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]] [--out output/render.png]
+                                  [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]]
+                                  [--checker [--texture IMAGE]] [--out output/render.png]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -12,6 +13,9 @@ points per light and trace, over the --materials scene unless --glass or --scatt
 --dof APERTURE gives the camera a thin lens of that radius (rt_set_lens: depth of field), focused on the centre of sphere K
 (--focus-on-sphere, default 0), over the --materials scene unless --glass or --scatter is given: that sphere is sharp, the floor
 in front of it and behind it blurred.  Use it with --spp 16, which averages the lens samples.
+--checker gives the floor a checkerboard of 0.5 x 0.5 squares and sphere 0 a solid checker (rt_set_scene_textures), over the
+--materials scene unless --glass or --scatter is given; --texture IMAGE also lays that picture (read with PIL) on the floor in
+front of the camera, 2 units wide.  --spp N averages the texel edges.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -26,7 +30,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import python_ray_tracer_amd as pkg
 from python_ray_tracer_amd import _lib as L
-from python_ray_tracer_amd.scene import Scene, Camera, Material
+from python_ray_tracer_amd.scene import Scene, Camera, Material, Plane, Texture
 from python_ray_tracer_amd.viewer import convert_array_to_image
 
 
@@ -46,6 +50,8 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="stochastic anti-aliasing with this many samples per pixel")
     ap.add_argument("--dof", type=float, default=0.0, metavar="APERTURE", help="depth of field: a thin lens of this radius")
     ap.add_argument("--focus-on-sphere", type=int, default=0, metavar="K", help="--dof: focus on the centre of sphere K")
+    ap.add_argument("--checker", action="store_true", help="a checkered floor and a solid checker on sphere 0 (textures)")
+    ap.add_argument("--texture", default=None, metavar="IMAGE", help="--checker: also lay this picture on the floor")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -60,7 +66,7 @@ def main():
             scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
             scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
-        elif a.materials or a.glass or a.soft or a.dof > 0:
+        elif a.materials or a.glass or a.soft or a.dof > 0 or a.checker:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
             if a.glass:                                             # clear glass; ior 2.4 (diamond) shows total internal reflection
@@ -72,7 +78,19 @@ def main():
             for li in scene.lights:
                 li.radius = 0.5
             radii = scene.get_light_radii()
-        r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples)
+        textures = None
+        if a.checker:
+            scene.planes[0].texture = Texture.checker((230, 230, 230), (40, 40, 40), 0.5)
+            scene.spheres[0].texture = Texture.checker((230, 60, 40), (250, 220, 120), 0.25, solid=True)
+            if a.texture:                                       # a poster on a second plane just above the floor: the picture 2 units
+                from PIL import Image                           # wide in front of the camera, repeating beyond it
+                img = np.asarray(Image.open(a.texture).convert("RGB"), dtype=np.float32)
+                hgt = 2.0 * img.shape[0] / img.shape[1]
+                poster = Texture.image(img, (1.0 + hgt, 1.0, 0.0), (0.0, -2.0, 0.0), (-hgt, 0.0, 0.0))
+                scene.planes.append(Plane([0, 0, 0.001], [0, 0, 1], [125, 125, 125], material=scene.planes[0].material, texture=poster))
+                mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
+            textures = scene.generate_textures()
+        r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples, textures=textures)
         r.set_camera(cam.position, cam.rotation)
         if a.dof > 0:
             focus = cam.focus_on(scene.spheres[a.focus_on_sphere].origin)
@@ -94,7 +112,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -265,6 +265,58 @@ int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const flo
                              const int32_t *sphere_material, const int32_t *plane_material,
                              const float *light_radius, int shadow_samples);
 
+/* The same with textures: a hit object's colour looked up at the hit point in a wrapped, nearest-neighbour grid of texels
+ * projected along up to three world-space axes (a checkered floor is a 2x2x1 grid, a solid checker 2x2x2, stripes 2x1x1, an
+ * image on a plane or projected onto a sphere like a slide W x H x 1).
+ *   textures        rt_texture (T,), 0 <= T <= RT_MAX_TEXTURES
+ *   sphere_texture  int32 (S,), plane_texture int32 (P,): the object's texture, or -1 for none; a NULL array means all -1
+ *   texels          float32 (n_texels, 3) C-order, true (R,G,B), finite; 0 <= n_texels <= RT_MAX_TEXELS.  Texture k owns texels
+ *                   first .. first + nx*ny*nz - 1, x fastest, then y, then z; the range must lie inside the array.  Ranges may
+ *                   overlap (two textures may share texels).
+ * T == 0, or every id -1:  exactly rt_set_scene_area_lights (the same kernels and bytes).  Only a scene with a textured object
+ * runs the texture kernels.
+ * A trace whose closest hit is an object with texture k uses, in place of the object's colour (RGB_obj, trace.py:65/70) for the
+ * ambient term and for every Lambert term of that trace, the texel chosen as follows.  Pt is the unbiased hit point of
+ * trace.py:60.  float64, no fused multiply-add, in this order:
+ *   for a = 0..2 with dim[a] > 1:
+ *       d   = (Pt.x - origin.x, Pt.y - origin.y, Pt.z - origin.z)
+ *       g   = ((d.x * axis[a][0]) + (d.y * axis[a][1])) + (d.z * axis[a][2])
+ *       f   = floor(g)
+ *       i_a = -2^30 if f is NaN or f < -2^30;  2^30 - 1 if f > 2^30 - 1;  else (integer) f
+ *       j_a = i_a mod dim[a], Euclidean (0 <= j_a < dim[a])
+ *   for an axis with dim[a] == 1:  j_a = 0, and g is not evaluated
+ *   texel index = first + (j_2 * ny + j_1) * nx + j_0
+ *   colour      = the three float32 of that texel, widened to float64
+ * Everything else is unchanged: normals, bias, shadows, refraction, scatter, area lights, the lens, the weights W_k.  A
+ * transparent or rough object may be textured.  Every AA mode, the lattice path, RT_FLAG_AA_PER_PIXEL, an explicit grid, column
+ * slabs, rt_render, rt_render_begin/end, rt_render_device and rt_render_sequence give the same bytes.
+ * Textures need a material table (M >= 1), like area lights and the lens.  Invalid input (as rt_set_scene_area_lights, an id
+ * outside [-1, T), a dimension outside 1..RT_MAX_TEXTURE_DIM, reserved != 0, a non-finite origin, axis or texel, a texel range outside the
+ * array, T > RT_MAX_TEXTURES, n_texels > RT_MAX_TEXELS, T > 0 with M == 0, NULL where an array is needed): RT_ERR_BAD_ARG, and the
+ * previous scene stays current.  Textures and texels travel with the scene (see "Streams" at the top): a frame in flight keeps
+ * the textures it was launched with.  Every call uploads its texels again.  RT_FLAG_COUNT_RAYS is refused for such a scene.
+ * RT_ABI_VERSION is unchanged: callers detect this entry point by its symbol. */
+#define RT_MAX_TEXTURES     64
+#define RT_MAX_TEXTURE_DIM  4096
+#define RT_MAX_TEXELS       (1 << 22)   /* four 1024 x 1024 images; 64 MB on the device */
+
+typedef struct rt_texture {
+    double  origin[3];   /* world point that maps to grid coordinate (0,0,0)        */
+    double  axis[3][3];  /* U, V, W: grid cells per world unit along each axis       */
+    int32_t dim[3];      /* nx, ny, nz, each 1..RT_MAX_TEXTURE_DIM                   */
+    int32_t reserved;    /* 0                                                        */
+    int64_t first;       /* index of texel (0,0,0) in the texel array                */
+} rt_texture;
+
+int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                          const float *planes, int P, int flags,
+                          const double *materials, int M, int ncols,
+                          const int32_t *sphere_material, const int32_t *plane_material,
+                          const float *light_radius, int shadow_samples,
+                          const rt_texture *textures, int T,
+                          const int32_t *sphere_texture, const int32_t *plane_texture,
+                          const float *texels, int64_t n_texels);
+
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);
 

@@ -14,6 +14,7 @@ RT_AA_NONE, RT_AA_REFERENCE, RT_AA_STOCHASTIC = 0, 1, 2
 RT_MAX_SPP = 64
 RT_MAX_SHADOW_SAMPLES = 16
 RT_RENDER_SLOTS = 4
+RT_MAX_TEXTURES, RT_MAX_TEXTURE_DIM, RT_MAX_TEXELS = 64, 4096, 1 << 22
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -35,6 +36,11 @@ class rt_stats(C.Structure):
                [("bounce_waves", C.c_uint64 * (RT_MAX_DEPTH + 1)), ("bounce_lanes", C.c_uint64 * (RT_MAX_DEPTH + 1))]
 
 
+class rt_texture(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("axis", (C.c_double * 3) * 3), ("dim", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("first", C.c_int64)]
+
+
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
 _dp, _fp, _vp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p
 PROTOTYPES = {
@@ -52,6 +58,9 @@ PROTOTYPES = {
                                                  C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_set_scene_area_lights": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int]),
+    "rt_set_scene_textures": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
+                                        C.POINTER(rt_texture), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int64]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_lens": (C.c_int, [_vp, C.c_double, C.c_double]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),

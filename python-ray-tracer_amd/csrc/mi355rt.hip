@@ -58,6 +58,7 @@ struct rt_ctx {
     int order_tiles = 1;              // MI355RT_ORDER_TILES=0: the four-wave kernels' dispatch order per block of four neighbouring tiles (A/B)
     int lanes_park = 1;               // MI355RT_LANES_PARK=0: register variants of the lane-owned kernels (A/B; with workgroups of equal-cost tiles the
                                       // parked variants win: config 5 6.88 against 7.16 ms — with neighbouring tiles they lost, 8.20 against 7.95)
+    int log_kernels = 0;              // MI355RT_LOG_KERNELS=1: every render launch names its kernel on stderr (its shape and family number)
     int remeasure = 24;               // MI355RT_REMEASURE: launches a dispatch order measured under an older camera is kept for before
                                       // the tile costs are measured again (a moving camera; any order renders the same frame)
     struct Slot {                     // rt_render_begin / rt_render_end: a frame in flight to host memory
@@ -80,6 +81,10 @@ struct rt_ctx {
                                   // transparent row (the refraction kernels), else 3
     int soft_n = 0;               // shadow samples per light of a scene with a light radius > 0 (the area-light kernels), else 0
     long long lens_mat = 0;       // offset (doubles) in the scene buffer of its material block with rows of 6 (the lens kernels')
+    int T = 0;                    // texture records of a scene with a textured object (the texture kernels), else 0
+    long long tex_off = 0;        // offset (doubles) in the scene buffer of its texture block (rt::tex_doubles)
+    Buf texels[RT_SCENE_RING];    // per scene buffer of the ring: {R,G,B, texture id} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels;
+                                  // allocated by the first textured scene that lands in the slot, grown when one needs more
     double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
@@ -213,10 +218,12 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
 // have.  From the scene (M materials in a table of mat_cols columns, soft_n shadow samples per light) and the lens aperture.
-rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a)
+rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0)
 {
     using F = rt::Family;
     if (M <= 0) return F::PLAIN;
+    if (T > 0)                                                       // (set_scene: T > 0 only with a textured object, and M >= 1)
+        return lens_a > 0.0 ? (soft_n > 0 ? F::TEX_LENS_SOFT : F::TEX_LENS) : (soft_n > 0 ? F::TEX_SOFT : F::TEX_SCAT);
     if (lens_a > 0.0) return soft_n > 0 ? F::LENS_SOFT : F::LENS;    // (check_params: a lens needs a material table)
     return soft_n > 0 ? F::SOFT : mat_cols == 6 ? F::SCAT : mat_cols == 5 ? F::REFR : F::MAT;
 }
@@ -254,7 +261,7 @@ constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
 // A family has one render kernel per shape, except
 //  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
 //  * the parked wave-uniform shapes (MODE 0 and 1) from REFR on, which the parking rule never picks (the static_assert below).
-// So PLAIN has 25 kernels, MAT 22 and every later family 14.  Nothing else names a render kernel of a family other than
+// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture families included) 14.  Nothing else names a render kernel of a family other than
 // PLAIN, so the kernels a family does not have are not compiled.
 constexpr bool has_kernel(rt::Family f, const Shape &s)
 {
@@ -306,7 +313,10 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
     family_kernels<rt::Family::REFR>(ALL_SHAPES),  family_kernels<rt::Family::SCAT>(ALL_SHAPES),
     family_kernels<rt::Family::SOFT>(ALL_SHAPES),  family_kernels<rt::Family::LENS>(ALL_SHAPES),
     family_kernels<rt::Family::LENS_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::TEX_SCAT>(ALL_SHAPES), family_kernels<rt::Family::TEX_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::TEX_LENS>(ALL_SHAPES), family_kernels<rt::Family::TEX_LENS_SOFT>(ALL_SHAPES),
 };
+static_assert(rt::FAMILIES == 11 && (int)rt::Family::TEX_LENS_SOFT == 10, "KERNELS lists the families in enum order");
 
 const void *kernel_of(rt::Family f, const Shape &s)
 {
@@ -404,8 +414,12 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const bool lens = rt::has_lens(family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a));
+    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T);
+    const bool lens = rt::has_lens(lfam);
     if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
+    // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
+    // scene buffer that is current now travel in its place
+    if (rt::has_tex(lfam)) { k.lens.mat = ctx->lens_mat; k.lens.tex = ctx->tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
     const size_t table = (size_t)(ctx->L + 1) * (rt::padS(ctx->S, ctx->NC) + rt::pad4(ctx->NC)) * rt::CULL_STRIDE * sizeof(float);
@@ -488,7 +502,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // The feature family (family_of) picks the twins of these variants: their LDS images hold the material block too
     // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt_ctx::lens_mat), and their parked variants the
     // family's per-thread slots (rt::lds_slots).
-    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a);
+    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T);
     auto per_cu = [&](bool nr) {
         const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->M);
         if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
@@ -501,6 +515,9 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, fam, ctx->M);
     const void *fn = kernel_of(fam, Shape{aa, park, wpw, count, lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0)});
     if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: missing_kernels_never_park)
+    if (ctx->log_kernels)
+        std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>\n", (int)aa, (int)park, wpw, (int)count,
+                     (int)lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0), (int)fam);
     // more than the default 48 KiB of dynamic LDS: raised on all of the family's kernels at once
     const int fi = (int)fam;
     if (lds > 48 * 1024 && lds > ctx->lds_limit_set[fi]) {
@@ -705,6 +722,7 @@ int rt_create(rt_ctx **out, int device)
     if (const char *e = std::getenv("MI355RT_WPW2_MAX_IMAGE")) ctx->wpw2_max_image = (size_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("MI355RT_ORDER_TILES")) ctx->order_tiles = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LANES_PARK")) ctx->lanes_park = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_LOG_KERNELS")) ctx->log_kernels = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_SEQ_ORDER")) ctx->seq_order = std::atoi(e) != 0 ? 1 : 0;
     if (const char *e = std::getenv("MI355RT_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= RT_RENDER_CHUNKS) ctx->render_chunks = v; }
     hipError_t s;
@@ -731,6 +749,7 @@ int rt_destroy(rt_ctx *ctx)
     for (Buf *b : {&ctx->pixel_loc, &ctx->u8, &ctx->f32, &ctx->counts})
         if (b->p) (void)hipFree(b->p);
     for (Buf &b : ctx->scene) if (b.p) (void)hipFree(b.p);
+    for (Buf &b : ctx->texels) if (b.p) (void)hipFree(b.p);
     for (auto &e : ctx->lattice) if (e.second.p) (void)hipFree(e.second.p);
     for (auto &f : ctx->fbs) {
         for (Buf *b : {&f.cost, &f.gtmp, &f.btmp, &f.order[0], &f.order[1]}) if (b->p) (void)hipFree(b->p);
@@ -777,7 +796,9 @@ int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const fl
 
 static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
-                     const float *light_radius, int shadow_samples);
+                     const float *light_radius, int shadow_samples, const rt_texture *textures = nullptr, int T = 0,
+                     const int32_t *sphere_texture = nullptr, const int32_t *plane_texture = nullptr, const float *texels = nullptr,
+                     int64_t n_texels = 0);
 
 int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                                    int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
@@ -797,10 +818,25 @@ int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const flo
                      light_radius ? light_radius : &none, shadow_samples);
 }
 
-// Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights.
+int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
+                          int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
+                          const int32_t *plane_material, const float *light_radius, int shadow_samples,
+                          const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
+                          const float *texels, int64_t n_texels)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
+    static const float none = 0.0f;
+    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
+                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels);
+}
+
+// Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights; textures ...
+// n_texels: the arguments of rt_set_scene_textures (T == 0: none).
 static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
-                     const float *light_radius, int shadow_samples)
+                     const float *light_radius, int shadow_samples, const rt_texture *textures, int T,
+                     const int32_t *sphere_texture, const int32_t *plane_texture, const float *texels, int64_t n_texels)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (ncols != 3 && ncols != 5 && ncols != 6) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3, 5 or 6");
@@ -882,8 +918,44 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
             if (plane_material[k] < 0 || plane_material[k] >= M)
                 return fail(ctx, RT_ERR_BAD_ARG, "plane_material[" + std::to_string(k) + "] outside 0..M-1");
     }
+    // textures: validated here; a scene without a textured object (T == 0, or every id -1) is exactly rt_set_scene_area_lights'
+    // (textured stays false), one with a textured object runs the texture kernels
+    bool textured = false;
+    if (T < 0 || T > RT_MAX_TEXTURES) return fail(ctx, RT_ERR_BAD_ARG, "texture count outside 0..RT_MAX_TEXTURES");
+    if (n_texels < 0 || n_texels > RT_MAX_TEXELS) return fail(ctx, RT_ERR_BAD_ARG, "texel count outside 0..RT_MAX_TEXELS");
+    if (T > 0) {
+        if (!(M > 0)) return fail(ctx, RT_ERR_BAD_ARG, "textures need a material table (M >= 1)");
+        if (!textures) return fail(ctx, RT_ERR_BAD_ARG, "textures is NULL with T > 0");
+        if (!texels) return fail(ctx, RT_ERR_BAD_ARG, "texels is NULL with T > 0");
+        for (int t = 0; t < T; ++t) {
+            const rt_texture &x = textures[t];
+            long long cells = 1;
+            if (x.reserved != 0) return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": reserved must be 0");
+            for (int a = 0; a < 3; ++a) {
+                if (x.dim[a] < 1 || x.dim[a] > RT_MAX_TEXTURE_DIM)
+                    return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": a dimension outside 1..RT_MAX_TEXTURE_DIM");
+                cells *= x.dim[a];
+                if (!std::isfinite(x.origin[a]) || !std::isfinite(x.axis[a][0]) || !std::isfinite(x.axis[a][1]) || !std::isfinite(x.axis[a][2]))
+                    return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": origin or axis not finite");
+            }
+            if (x.first < 0 || x.first > n_texels || cells > n_texels - x.first)
+                return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": texel range outside the texel array");
+        }
+        for (int64_t i = 0; i < 3 * n_texels; ++i)
+            if (!std::isfinite(texels[i])) return fail(ctx, RT_ERR_BAD_ARG, "texel " + std::to_string(i / 3) + " is not finite");
+    }
+    for (int k = 0; k < S && sphere_texture; ++k) {
+        if (sphere_texture[k] < -1 || sphere_texture[k] >= T)
+            return fail(ctx, RT_ERR_BAD_ARG, "sphere_texture[" + std::to_string(k) + "] outside -1..T-1");
+        textured = textured || sphere_texture[k] >= 0;
+    }
+    for (int k = 0; k < P && plane_texture; ++k) {
+        if (plane_texture[k] < -1 || plane_texture[k] >= T)
+            return fail(ctx, RT_ERR_BAD_ARG, "plane_texture[" + std::to_string(k) + "] outside -1..T-1");
+        textured = textured || plane_texture[k] >= 0;
+    }
     int nclusters = 0;
-    size_t lens_off = 0;
+    size_t lens_off = 0, tex_off = 0;
     try {
         // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
         // are evaluated here, once, in float32: r*r (intersections.py:21), the plane shading normal
@@ -932,7 +1004,9 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         // behind its block, with the same ids; a 6-column one (an area-light scene's included) serves them as it is
         const size_t matd = rt::mat_doubles(M, S, P, family_of(M, cols, soft ? shadow_samples : 0, 0.0));
         lens_off = (M > 0 && cols < 6) ? mat_off + matd : mat_off;
-        std::vector<double> rec(mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0), 0.0);
+        // the texture block (rt::tex_doubles) behind everything else
+        tex_off = mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0);
+        std::vector<double> rec(tex_off + (textured ? rt::tex_doubles(T) : 0), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -1000,12 +1074,42 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
             for (int slot = 0; slot < S; ++slot) ids[slot] = sphere_material[order[slot]];
             for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
             if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
-            if (soft) rec.back() = (double)shadow_samples;          // (rt::mat_doubles: the block's last double)
+            if (soft) rec[mat_off + matd - 1] = (double)shadow_samples;   // (rt::mat_doubles: the block's last double)
             if (lens_off != mat_off) {
                 rec[lens_off] = (double)M;
                 put_rows(rec.data() + lens_off + 1, 6, materials, cols, M);
                 if (!ids.empty()) std::memcpy(rec.data() + lens_off + 1 + (size_t)6 * M, ids.data(), ids.size() * sizeof(int32_t));
             }
+        }
+        // textures: the records with what texel_of reads (dimensions and their reciprocals as doubles, the first texel's entry of
+        // the texel array); the texel array starts with the S + P slots' own colours (exact: the scene is float32) and texture
+        // ids (-1: none), so that a hit without a texture reads its colour the same way
+        std::vector<float> tx;
+        if (textured) {
+            double *tb = rec.data() + tex_off;
+            tb[0] = (double)T;
+            for (int t = 0; t < T; ++t) {
+                double *r = tb + 1 + (size_t)rt::TEX_STRIDE * t;
+                const rt_texture &x = textures[t];
+                for (int a = 0; a < 3; ++a) {
+                    r[a] = x.origin[a];
+                    for (int i = 0; i < 3; ++i) r[3 + 3 * a + i] = x.axis[a][i];
+                    r[12 + a] = (double)x.dim[a];
+                    r[15 + a] = 1.0 / (double)x.dim[a];
+                }
+                r[18] = (double)((long long)S + P + x.first);
+            }
+            tx.assign(4 * ((size_t)S + P + (size_t)n_texels), 0.0f);
+            for (int slot = 0; slot < S; ++slot) {
+                for (int c = 0; c < 3; ++c) tx[4 * (size_t)slot + c] = spheres[(4 + c) * S + order[slot]];
+                tx[4 * (size_t)slot + 3] = sphere_texture ? (float)sphere_texture[order[slot]] : -1.0f;
+            }
+            for (int k = 0; k < P; ++k) {
+                for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + k) + c] = planes[(6 + c) * P + k];
+                tx[4 * ((size_t)S + k) + 3] = plane_texture ? (float)plane_texture[k] : -1.0f;
+            }
+            for (int64_t i = 0; i < n_texels; ++i)
+                for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + P + (size_t)i) + c] = texels[3 * i + c];
         }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
@@ -1016,6 +1120,11 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         ctx->scene_readers[next].clear();
         int rc = ensure(ctx, ctx->scene[next], bytes);
         if (rc != RT_OK) return rc;
+        if (textured) {
+            rc = ensure(ctx, ctx->texels[next], tx.size() * sizeof(float));
+            if (rc != RT_OK) return rc;
+            RT_HIP(ctx, hipMemcpyAsync(ctx->texels[next].p, tx.data(), tx.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        }
         RT_HIP(ctx, hipMemcpyAsync(ctx->scene[next].p, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // rec is about to go out of scope; other streams may launch at once
         ctx->scene_cur = next;
@@ -1043,6 +1152,8 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
     ctx->mat_cols = cols;
     ctx->soft_n = soft ? shadow_samples : 0;
     ctx->lens_mat = (long long)lens_off;
+    ctx->T = textured ? T : 0;
+    ctx->tex_off = (long long)tex_off;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

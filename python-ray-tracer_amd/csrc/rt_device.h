@@ -131,6 +131,9 @@ struct KParams {
             double aperture;   // lens radius a > 0
             double focus;      // distance f of the plane of focus along R e_x
             long long mat;     // offset (doubles) in `scene` of the material block with rows of 6 (mat_offset, or a padded copy)
+            // TEX kernels (rt_set_scene_textures with a textured object; lens or not, they read `mat` too):
+            long long tex;     // offset (doubles) in `scene` of the texture block (tex_doubles)
+            const float *texels;   // 16 B per entry: {R,G,B, texture id or -1} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels
         } lens;
     };
 };
@@ -319,13 +322,16 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // The feature family of a render kernel (its last template argument).  Each family's kernels are the twins of the family before
 // it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host derives a launch's family from its
 // scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
-enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT };
-constexpr int FAMILIES = 7;
+// TEX_*: the texture twins of SCAT, SOFT, LENS and LENS_SOFT (rt_set_scene_textures with a textured object): the hit's colour is a
+// texel chosen at the hit point (texel_of).  They are appended: tools/isa_compare.py matches kernels by the family's number.
+enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT, TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT };
+constexpr int FAMILIES = 11;
 __host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
 __host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
 __host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
-__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT; }
-__host__ __device__ constexpr bool has_lens(Family f) { return f >= Family::LENS; }
+__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT; }
+__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT; }
+__host__ __device__ constexpr bool has_tex(Family f) { return f >= Family::TEX_SCAT; }
 __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
 
 // Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
@@ -347,8 +353,10 @@ __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 
 // nsh is the scene's shadow_samples n (the last double of the material block).
 // LENS (depth-of-field kernels, rt_set_lens with an aperture > 0; SCAT too): no slot; the primary ray does not start at the
 // camera, so trace 0's closest-hit query takes the origin form of the cull (trace_bounce).
+// TEX (texture kernels, rt_set_scene_textures with a textured object; SCAT too, and SOFT / LENS as their twins): no slot and no
+// LDS: texture records, ids and texels are read from global memory where a hit needs them (texel_of).
 template <Family F, int WSLOT, bool FRESH> struct MatState {
-    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F);
+    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F);
     static constexpr int COLS = table_cols(F);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
@@ -369,7 +377,7 @@ template <Family F, int WSLOT, bool FRESH> struct MatState {
     }
 };
 template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
-    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false;
+    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1413,6 +1421,49 @@ __device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, c
     return keep;
 }
 
+// The texel a TEX kernel's hit takes its colour from (rt_set_scene_textures, mi355rt.h): the entry of KParams::lens.texels for the
+// object in slot `slot` (spheres in slot order, then planes) hit at the unbiased point Pt.  The slot's own entry holds its colour
+// and, in the fourth float, its texture id k (-1: none — the entry is then the answer).  With a texture, its record
+// r = {origin[3], axis[3][3], n[3], 1/n[3], base} (TEX_STRIDE doubles in the scene buffer's texture block, KParams::lens.tex; read
+// per lane from global memory: a wave's hits share a few records, which stay in the cache) gives, per axis a:
+// g = ((d.x*U.x) + (d.y*U.y)) + d.z*U.z with d = Pt - origin (float64, no fused multiply-add), f = floor(g) clamped to
+// [-2^30, 2^30 - 1] (NaN: -2^30), j = f mod n; entry base + (j_2*ny + j_1)*nx + j_0 (base = S + P + first).
+// Nothing of this is staged in LDS: the images of a family's kernels, and with them every choice the dispatcher makes from
+// their sizes (workgroups per CU, parking), are those of the family's twin.
+// f mod n without an integer division (20 instructions on the vector unit, three times per hit): q = floor(f * rn) with
+// rn = RN(1/n) (the host's division), j = f - n*q, and one correction step into [0, n).  Exact for integral |f| <= 2^30 and
+// 1 <= n <= 4096:  n*q < 2^43 and f - n*q are integers below 2^53, so neither rounds;  f*rn is within 2^-52 |f/n| <= 2^-22 of f/n
+// (rn within 2^-53 relative, one more rounding);  a quotient f/n that is not an integer is at least 1/n >= 2^-12 from the
+// nearest one, so its floor is the true floor and 0 <= j < n;  an integral quotient k may come out as k or k - 1, j as 0 or n:
+// the correction maps n to 0.  (The other direction, j < 0, cannot occur; it is corrected too, for one compare and one add.)
+// An axis with n = 1 needs no case of its own: j = f - floor(f) = 0 whatever g is.
+// tests/test_textures.py replays this against integer arithmetic on dimensions 3, 5, 7 and 4096 and coordinates on exact multiples.
+constexpr int TEX_STRIDE = 20;     // doubles per texture record: origin[3], axis[3][3], n[3], 1/n[3], base, pad
+__host__ __device__ inline double texel_wrap(double g, double n, double rn)
+{
+    double f = __builtin_floor(g);
+    f = f >= -0x1p30 ? f : -0x1p30;                                           // (a NaN fails the compare)
+    f = f > 0x1p30 - 1.0 ? 0x1p30 - 1.0 : f;
+    double j = f - n * __builtin_floor(f * rn);
+    if (j < 0.0) j += n;
+    if (j >= n) j -= n;
+    return j;
+}
+__device__ __forceinline__ unsigned texel_of(const KParams &p, int slot, const V3 &Pt)
+{
+    const int k = (int)p.lens.texels[4 * (size_t)slot + 3];
+    unsigned ti = (unsigned)slot;
+    if (k >= 0) {
+        const double *r = p.scene + (size_t)p.lens.tex + 1 + TEX_STRIDE * k;
+        const V3 dd{Pt.x - r[0], Pt.y - r[1], Pt.z - r[2]};
+        const double j0 = texel_wrap(((dd.x * r[3]) + (dd.y * r[4])) + (dd.z * r[5]), r[12], r[15]);
+        const double j1 = texel_wrap(((dd.x * r[6]) + (dd.y * r[7])) + (dd.z * r[8]), r[13], r[16]);
+        const double j2 = texel_wrap(((dd.x * r[9]) + (dd.y * r[10])) + (dd.z * r[11]), r[14], r[17]);
+        ti = (unsigned)(r[18] + ((j2 * r[13] + j1) * r[12] + j0));            // (integers below 2^53: exact)
+    }
+    return ti;
+}
+
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
@@ -1447,10 +1498,21 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         typedef __attribute__((address_space(3))) float lds_f32;
         volatile const lds_f32 *col1 = nullptr;
         if constexpr (MODE == 1) col1 = (volatile const lds_f32 *)lds.col32 + 4 * ((type == HIT_SPHERE) ? idx : (int)padS(S, lds.NC) + idx);
+        // TEX: the colour is a float32 texel in global memory (the object's own colour is one too: texel_of), chosen here from the
+        // unbiased Pt.  What stays live across the shadow queries is its 32-bit index; parked kernels read the texel again at
+        // each point of use (an L2 hit), as they re-read a record's colour
+        unsigned texi = 0u;
+        if constexpr (MS::tex) texi = texel_of(p, (type == HIT_SPHERE) ? idx : S + idx, Pt);
+        auto texel = [&](int c) -> double { return (double)((volatile const float *)p.lens.texels)[4 * (size_t)texi + c]; };
         V3 colr{0.0, 0.0, 0.0};
-        if constexpr (!PARK) colr = (MODE == 1) ? V3{(double)col1[0], (double)col1[1], (double)col1[2]} : V3{colf[0], colf[1], colf[2]};
+        if constexpr (!PARK && MS::tex) {                                      // register variants: the 16-byte entry, one aligned load
+            const f4 tc = reinterpret_cast<const f4 *>(p.lens.texels)[texi];
+            colr = V3{(double)tc[0], (double)tc[1], (double)tc[2]};
+        }
+        else if constexpr (!PARK) colr = (MODE == 1) ? V3{(double)col1[0], (double)col1[1], (double)col1[2]} : V3{colf[0], colf[1], colf[2]};
         auto col = [&](int c) -> double {
-            if constexpr (PARK && MODE == 1) return (double)col1[c];
+            if constexpr (PARK && MS::tex) return texel(c);
+            else if constexpr (PARK && MODE == 1) return (double)col1[c];
             else if constexpr (PARK && NOREC) return colf[c];
             else if constexpr (PARK) return colp[c];
             else return c == 0 ? colr.x : (c == 1 ? colr.y : colr.z);
@@ -1720,6 +1782,8 @@ __host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2, Fami
 // kernels stage it at the end of their LDS image.
 __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
 __host__ __device__ inline size_t mat_doubles(int M, int S, int P, Family f) { return M > 0 ? 1 + (size_t)table_cols(f) * M + ((size_t)S + P + 1) / 2 + (has_soft(f) ? 1 : 0) : 0; }
+// The texture block of a scene with a textured object (KParams::lens.tex): T, then the T records of TEX_STRIDE doubles (texel_of).
+__host__ __device__ inline size_t tex_doubles(int T) { return T > 0 ? 1 + (size_t)TEX_STRIDE * T : 0; }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
@@ -1751,6 +1815,8 @@ __host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool 
     return col ? t.total_col : (lanes ? t.total_lanes : t.total);
 }
 // mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
+// (TEX kernels keep their twins' image, unread parts included: they take every colour from KParams::lens.texels, so the MODE 1
+// colour table and the colours of the float64 records are dead weight in theirs — the price of sharing the twins' layout.)
 // f, M: the kernels' family and the scene's material count (their image holds the material block, mat_doubles)
 __host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
                                             Family f = Family::PLAIN, int M = 0)
@@ -1900,7 +1966,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     constexpr int WG_THREADS = 64 * WPW, WAVES_PER_WG = WPW;
     constexpr bool M2 = MODE >= 2;
     constexpr bool NOREC = MODE >= 1;
-    constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F);
+    constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F), TEX = has_tex(F);
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
     double *accum = lds_raw + nrec;
@@ -1933,8 +1999,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
 #endif
     int nmat = 0, nsh = 1;
     if constexpr (MAT) {
-        // (LENS: the block with rows of 6 the host names, a padded copy behind the scene's own for a table of 3 or 5 columns)
-        const double *msrc = p.scene + (LENS ? (size_t)p.lens.mat : mat_offset(p.S, p.P, p.L, p.NC));
+        // (LENS, TEX: the block with rows of 6 the host names, a padded copy behind the scene's own for a table of 3 or 5 columns)
+        const double *msrc = p.scene + ((LENS || TEX) ? (size_t)p.lens.mat : mat_offset(p.S, p.P, p.L, p.NC));
         nmat = (int)msrc[0];
         const int nm = (int)mat_doubles(nmat, p.S, p.P, F);
         for (int i = threadIdx.x; i < nm; i += WG_THREADS) matl[i] = msrc[i];

@@ -119,7 +119,7 @@ class Renderer:
         self.close()
 
     # -- inputs -----------------------------------------------------------------------------
-    def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1):
+    def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1, textures=None):
         """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
@@ -129,7 +129,10 @@ class Renderer:
         is its number of columns (the library refuses any but 3, 5 and 6); a 1-D table is read as rows of 3.
         light_radius: None, or float32 (L,) radii as Scene.get_light_radii() returns them; with a radius > 0 the lights are
         area lights with soft shadows, shadow_samples (1..RT_MAX_SHADOW_SAMPLES) points per light and trace
-        (rt_set_scene_area_lights).  Area lights need a material table."""
+        (rt_set_scene_area_lights).  Area lights need a material table.
+        textures: None, or (records, sphere_ids int32 (S,), plane_ids int32 (P,), texels float32 (N,3)) as
+        Scene.generate_textures() returns them: records a list of (origin (3,), axes (3,3), (nx, ny, nz), first); an id of -1
+        means no texture (rt_set_scene_textures).  Textures need a material table."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
         rad = None
@@ -142,6 +145,8 @@ class Renderer:
                                  "(scalar-only shading has no soft shadows)")
             if materials is None:
                 rad = None
+        if textures is not None and materials is None:
+            raise ValueError("textures need a material table: pass materials=...")
         if materials is None:
             self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
                                                p.ctypes.data_as(fp), p.shape[1], int(flags)))
@@ -156,7 +161,31 @@ class Renderer:
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            if rad is not None:
+            if textures is not None:
+                records, tsid, tpid, texels = textures
+                T = len(records)
+                recs = (L.rt_texture * max(T, 1))()
+                for k, (o, ax, dims, first) in enumerate(records):
+                    o = np.asarray(o, dtype=np.float64).reshape(3)
+                    ax = np.asarray(ax, dtype=np.float64).reshape(3, 3)
+                    for a in range(3):
+                        recs[k].origin[a] = o[a]
+                        recs[k].dim[a] = int(dims[a])
+                        for i in range(3):
+                            recs[k].axis[a][i] = ax[a, i]
+                    recs[k].first = int(first)
+                tsi = np.ascontiguousarray(tsid, dtype=np.int32).reshape(-1)
+                tpi = np.ascontiguousarray(tpid, dtype=np.int32).reshape(-1)
+                if tsi.shape[0] != s.shape[1] or tpi.shape[0] != p.shape[1]:
+                    raise ValueError(f"texture ids: {tsi.shape[0]} for {s.shape[1]} spheres, {tpi.shape[0]} for {p.shape[1]} planes")
+                tx = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1, 3)
+                zr = rad if rad is not None else np.zeros(l.shape[1], dtype=np.float32)
+                self._check(self._lib.rt_set_scene_textures(
+                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
+                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
+                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip), zr.ctypes.data_as(fp), int(shadow_samples),
+                    recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip), tx.ctypes.data_as(fp), tx.shape[0]))
+            elif rad is not None:
                 self._check(self._lib.rt_set_scene_area_lights(
                     self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
                     p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,

@@ -9,6 +9,7 @@ from typing import ClassVar, List, Optional
 import numpy as np
 
 from .colors import RED, BLUE, MAGENTA, YELLOW, GREEN, GREY
+from .texture import Texture, RT_MAX_TEXTURES, RT_MAX_TEXELS
 
 
 @dataclass(frozen=True)
@@ -65,6 +66,7 @@ class Sphere:
     radius: float
     color: object
     material: Optional[Material] = None
+    texture: Optional[Texture] = None
     data_length: ClassVar[int] = 7
 
     def to_array(self):
@@ -96,6 +98,7 @@ class Plane:
     normal: object
     color: object
     material: Optional[Material] = None
+    texture: Optional[Texture] = None
     data_length: ClassVar[int] = 9
 
     def to_array(self):
@@ -153,6 +156,38 @@ class Scene:
 
         sphere_ids, plane_ids = ids(self.spheres), ids(self.planes)
         return np.array(rows, dtype=np.float64).reshape(-1, ncols), sphere_ids, plane_ids
+
+    def generate_textures(self):
+        """(records, sphere_ids int32 (S,), plane_ids int32 (P,), texels float32 (N, 3)) for
+        Renderer.set_scene(..., textures=...).  records: a list of (origin (3,), axes (3, 3), dims (nx, ny, nz), first), one per
+        distinct texture in the order of first use (spheres, then planes): equal textures share one record and its texels.
+        Objects without a texture get id -1."""
+        records, index, chunks, n = [], {}, [], 0
+
+        def ids(objs):
+            nonlocal n
+            out = np.full(len(objs), -1, dtype=np.int32)
+            for i, o in enumerate(objs):
+                t = o.texture
+                if t is None:
+                    continue
+                if not isinstance(t, Texture):
+                    raise TypeError(f"texture must be a Texture, got {type(t).__name__}")
+                if t not in index:
+                    if len(records) >= RT_MAX_TEXTURES:
+                        raise ValueError(f"a scene holds at most {RT_MAX_TEXTURES} textures")
+                    index[t] = len(records)
+                    records.append((t.origin.copy(), t.axes.copy(), t.dims, n))
+                    chunks.append(t.texels.reshape(-1, 3))
+                    n += chunks[-1].shape[0]
+                    if n > RT_MAX_TEXELS:
+                        raise ValueError(f"a scene holds at most {RT_MAX_TEXELS} texels")
+                out[i] = index[t]
+            return out
+
+        sphere_ids, plane_ids = ids(self.spheres), ids(self.planes)
+        texels = np.concatenate(chunks).astype(np.float32) if chunks else np.zeros((0, 3), dtype=np.float32)
+        return records, sphere_ids, plane_ids, texels
 
     @staticmethod
     def default_scene():

@@ -14,8 +14,9 @@ family (rt::Family, rt_device.h), whichever way the tree spells the family: as t
 LENS, of which a missing one counts as false.  So a tree of either form compares with one of the other, and a tree with more
 families with one with fewer.  Kernels of the working tree that the base does not have are listed as NEW.
 --twins also prints each MAT kernel next to its PLAIN twin, each REFR kernel next to its MAT twin, each SCAT kernel next to its
-REFR twin, each SOFT kernel next to its SCAT twin, and each LENS and LENS_SOFT kernel next to its SCAT and SOFT twin.  Exit
-status 1 if any kernel differs.
+REFR twin, each SOFT kernel next to its SCAT twin, each LENS and LENS_SOFT kernel next to its SCAT and SOFT twin, and each
+texture kernel (TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT) next to its SCAT, SOFT, LENS and LENS_SOFT twin.  Exit status 1
+if any kernel differs.
 """
 import argparse
 import os
@@ -35,7 +36,8 @@ def build(tree):
     return open(os.path.join(tree, CSRC, "rt_kernel.gfx950.s")).read(), r.stderr
 
 
-FAMILIES = ("", "mat", "refr", "scat", "soft", "lens", "lens_soft")   # rt::Family in enum order; "" is PLAIN
+FAMILIES = ("", "mat", "refr", "scat", "soft", "lens", "lens_soft",    # rt::Family in enum order; "" is PLAIN
+            "tex_scat", "tex_soft", "tex_lens", "tex_lens_soft")
 
 
 def key(name):
@@ -117,9 +119,12 @@ def main():
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
         for fam, twin, title in (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"),
                                  ("scat", "refr", "scatter kernel"), ("soft", "scat", "area-light kernel"),
-                                 ("lens", "scat", "lens kernel"), ("lens_soft", "soft", "lens area-light kernel")):
+                                 ("lens", "scat", "lens kernel"), ("lens_soft", "soft", "lens area-light kernel"),
+                                 ("tex_scat", "scat", "texture kernel"), ("tex_soft", "soft", "texture area-light kernel"),
+                                 ("tex_lens", "lens", "texture lens kernel"),
+                                 ("tex_lens_soft", "lens_soft", "texture lens area-light kernel")):
             print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   "
-                  f"{dict(mat='material', refr='refraction', scat='scatter', soft='area-light').get(twin, 'default')} twin")
+                  f"{dict(mat='material', refr='refraction', scat='scatter', soft='area-light', lens='lens', lens_soft='lens area-light').get(twin, 'default')} twin")
             for (k, f_), n in sorted(new_by_key.items(), key=str):
                 if f_ != fam:
                     continue
