@@ -3,7 +3,7 @@
 
     python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
                                   [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]]
-                                  [--checker [--texture IMAGE]] [--out output/render.png]
+                                  [--checker [--texture IMAGE]] [--lights] [--out output/render.png]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -16,6 +16,8 @@ in front of it and behind it blurred.  Use it with --spp 16, which averages the 
 --checker gives the floor a checkerboard of 0.5 x 0.5 squares and sphere 0 a solid checker (rt_set_scene_textures), over the
 --materials scene unless --glass or --scatter is given; --texture IMAGE also lays that picture (read with PIL) on the floor in
 front of the camera, 2 units wide.  --spp N averages the texel edges.
+--lights lights the default scene with one warm light, one cool light and one dim light, and gives it glossy spheres and glass
+with a highlight (rt_set_scene_lighting), over the --glass scene unless --scatter is given.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -30,7 +32,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import python_ray_tracer_amd as pkg
 from python_ray_tracer_amd import _lib as L
-from python_ray_tracer_amd.scene import Scene, Camera, Material, Plane, Texture
+from python_ray_tracer_amd.scene import Scene, Camera, Light, Material, Plane, Texture
 from python_ray_tracer_amd.viewer import convert_array_to_image
 
 
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--focus-on-sphere", type=int, default=0, metavar="K", help="--dof: focus on the centre of sphere K")
     ap.add_argument("--checker", action="store_true", help="a checkered floor and a solid checker on sphere 0 (textures)")
     ap.add_argument("--texture", default=None, metavar="IMAGE", help="--checker: also lay this picture on the floor")
+    ap.add_argument("--lights", action="store_true", help="a warm, a cool and a dim light; glossy spheres and glass (lighting)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -66,13 +69,27 @@ def main():
             scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
             scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
-        elif a.materials or a.glass or a.soft or a.dof > 0 or a.checker:
+        elif a.materials or a.glass or a.soft or a.dof > 0 or a.checker or a.lights:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
-            if a.glass:                                             # clear glass; ior 2.4 (diamond) shows total internal reflection
+            if a.glass or a.lights:                                 # clear glass; ior 2.4 (diamond) shows total internal reflection
                 scene.spheres[0].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=1.5)
                 scene.spheres[5].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=2.4)
+            if a.lights:                                            # a highlight on the glass, and two glossy spheres
+                scene.spheres[0].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=1.5, specular=220.0, shininess=256)
+                scene.spheres[5].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=2.4, specular=220.0, shininess=256)
+                scene.spheres[1].material = Material(0.05, 0.7, 0.1, specular=160.0, shininess=64)
+                scene.spheres[2].material = Material(0.05, 0.7, 0.1, specular=90.0, shininess=8)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))   # matte spheres: no reflection
+        colors = None
+        if a.lights:                                                # a warm key light, a cool fill, a dim third
+            if a.scatter:
+                scene.spheres[1].material = Material(0.05, 0.7, 0.1, specular=160.0, shininess=64)
+                mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
+            for li, (color, intensity) in zip(scene.lights, (((1.0, 0.8, 0.55), 1.3), ((0.5, 0.7, 1.0), 0.7), ((1.0, 1.0, 1.0), 0.25))):
+                li.color, li.intensity = color, intensity
+            scene.lights = [Light(li.origin, li.radius, li.color, li.intensity) for li in scene.lights]   # (validated)
+            colors = scene.get_light_colors()
         radii = None
         if a.soft:
             for li in scene.lights:
@@ -90,7 +107,8 @@ def main():
                 scene.planes.append(Plane([0, 0, 0.001], [0, 0, 1], [125, 125, 125], material=scene.planes[0].material, texture=poster))
                 mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
             textures = scene.generate_textures()
-        r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples, textures=textures)
+        r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples, textures=textures,
+                    light_rgb=colors)
         r.set_camera(cam.position, cam.rotation)
         if a.dof > 0:
             focus = cam.focus_on(scene.spheres[a.focus_on_sphere].origin)
@@ -112,7 +130,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -317,6 +317,51 @@ int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float 
                           const int32_t *sphere_texture, const int32_t *plane_texture,
                           const float *texels, int64_t n_texels);
 
+/* The same with lighting: a colour and strength per light, and a Blinn-Phong highlight per material.
+ *   light_rgb  float32 (L, 3) C-order: e_m = (e_r, e_g, e_b), the colour times the strength of light m; every component finite
+ *              and >= 0.  NULL: every light is (1, 1, 1).
+ *   ncols      3, 5, 6 or 8.  Rows of 8 are (amb, lamb, refl, trans, ior, rough, spec, shin): spec finite and >= 0, in colour
+ *              units (the 0..255 scale of the objects' colours); shin, the Blinn-Phong exponent, one of 1, 2, 4, ..., 1024, so
+ *              that the power is log2(shin) exact squarings and no pow() is involved.  Every rule for the first six columns holds.
+ * ncols 3, 5 or 6 with light_rgb NULL is exactly rt_set_scene_textures.
+ * A scene runs the lighting kernels when some e_m is not bitwise (1, 1, 1) or some table row has spec > 0 (by row, whether or not
+ * an object uses it, as the rough and transparent tests).  Every other scene is exactly rt_set_scene_textures': the same kernels
+ * and bytes.  In a scene that runs them, trace b adds per light m (and per shadow sample under area lights), float64, no fused
+ * multiply-add, in this order; d is the incoming unit direction, N the outward normal, Pt the biased point of trace.py:82-83, col
+ * the object's colour or its texel, Ld the unit vector from Pt to light m (to the sample point Q under area lights), n the scene's
+ * shadow_samples with area lights and 1 without, lamb_n = lamb / n as before and spec_n = spec / n (a float64 division):
+ *   cN = dot(Ld, N)
+ *   k  = lamb_n * cN                                                       (trace.py:99)
+ *   wantL = k > 0;  wantS = spec > 0 and cN > 0
+ *   neither: no shadow query, next light
+ *   occluded (the same shadow ray and any-hit rule as before): next light
+ *   wantL:  rgb_c = rgb_c + ((k * e_c) * col_c)                            c = r, g, b
+ *   wantS:  Hs = (Ld.x + (-d.x), Ld.y + (-d.y), Ld.z + (-d.z));  H = normalize(Hs);  s = dot(N, H)
+ *           s > 0:  q = s;  log2(shin) times q = q * q;  a = spec_n * q
+ *                   rgb_c = rgb_c + (a * e_c)                              c = r, g, b, after this light's Lambert term
+ * A NaN compares false everywhere: Hs == 0 gives s = NaN and no highlight.  (The kernels decide wantS on spec_n > 0.  That differs
+ * from spec > 0 only where spec / n underflows to 0, and there the bytes are the same: a = 0 * q is +0, e_c >= 0, and rgb_c, which
+ * starts as 0 + amb * col_c, is never -0, so adding a * e_c changes nothing, nor does the shadow query that is not asked.)
+ * The highlight has the light's colour, not the
+ * texel's.  Everything else is unchanged: ambient, bias, the continuation rays and the weights W_k, the scatter, light and lens
+ * hashes, the texel lookup.  A transparent or rough object may have spec > 0.  Every AA mode, the lattice path,
+ * RT_FLAG_AA_PER_PIXEL, an explicit grid, column slabs, rt_render, rt_render_begin/end, rt_render_device and rt_render_sequence
+ * give the same bytes.
+ * Lighting needs a material table (M >= 1).  Invalid input (as rt_set_scene_textures, a light_rgb component that is negative or not
+ * finite, a spec that is negative or not finite, a shin that is not one of the eleven values, a coloured light or spec > 0 with
+ * M == 0): RT_ERR_BAD_ARG, and the previous scene stays current.  Light colours travel with the scene, as texture records do: a
+ * frame in flight keeps the lights it was launched with.  RT_FLAG_COUNT_RAYS is refused for such a scene.  RT_ABI_VERSION is
+ * unchanged: callers detect this entry point by its symbol. */
+int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                          const float *planes, int P, int flags,
+                          const double *materials, int M, int ncols,
+                          const int32_t *sphere_material, const int32_t *plane_material,
+                          const float *light_radius, int shadow_samples,
+                          const rt_texture *textures, int T,
+                          const int32_t *sphere_texture, const int32_t *plane_texture,
+                          const float *texels, int64_t n_texels,
+                          const float *light_rgb);
+
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);
 

@@ -61,6 +61,10 @@ PROTOTYPES = {
     "rt_set_scene_textures": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
                                         C.POINTER(rt_texture), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int64]),
+    "rt_set_scene_lighting": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
+                                        C.POINTER(rt_texture), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int64,
+                                        _fp]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_lens": (C.c_int, [_vp, C.c_double, C.c_double]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),

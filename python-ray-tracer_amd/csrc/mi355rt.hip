@@ -83,8 +83,10 @@ struct rt_ctx {
     long long lens_mat = 0;       // offset (doubles) in the scene buffer of its material block with rows of 6 (the lens kernels')
     int T = 0;                    // texture records of a scene with a textured object (the texture kernels), else 0
     long long tex_off = 0;        // offset (doubles) in the scene buffer of its texture block (rt::tex_doubles)
+    bool lit = false;             // the scene runs the lighting kernels (a light colour that is not (1, 1, 1), or a row with spec > 0)
+    long long lit_off = 0;        // offset (doubles) in the scene buffer of its lighting block (rt::lit_doubles)
     Buf texels[RT_SCENE_RING];    // per scene buffer of the ring: {R,G,B, texture id} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels;
-                                  // allocated by the first textured scene that lands in the slot, grown when one needs more
+                                  // allocated by the first textured (or lit) scene that lands in the slot, grown when one needs more
     double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
     double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
@@ -218,10 +220,12 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
 // have.  From the scene (M materials in a table of mat_cols columns, soft_n shadow samples per light) and the lens aperture.
-rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0)
+rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0, bool lit = false)
 {
     using F = rt::Family;
     if (M <= 0) return F::PLAIN;
+    if (lit)                                                         // (set_scene: lit only with M >= 1; textured or not)
+        return lens_a > 0.0 ? (soft_n > 0 ? F::LIT_LENS_SOFT : F::LIT_LENS) : (soft_n > 0 ? F::LIT_SOFT : F::LIT_SCAT);
     if (T > 0)                                                       // (set_scene: T > 0 only with a textured object, and M >= 1)
         return lens_a > 0.0 ? (soft_n > 0 ? F::TEX_LENS_SOFT : F::TEX_LENS) : (soft_n > 0 ? F::TEX_SOFT : F::TEX_SCAT);
     if (lens_a > 0.0) return soft_n > 0 ? F::LENS_SOFT : F::LENS;    // (check_params: a lens needs a material table)
@@ -261,7 +265,7 @@ constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
 // A family has one render kernel per shape, except
 //  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
 //  * the parked wave-uniform shapes (MODE 0 and 1) from REFR on, which the parking rule never picks (the static_assert below).
-// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture families included) 14.  Nothing else names a render kernel of a family other than
+// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture and the four lighting families included) 14.  Nothing else names a render kernel of a family other than
 // PLAIN, so the kernels a family does not have are not compiled.
 constexpr bool has_kernel(rt::Family f, const Shape &s)
 {
@@ -315,8 +319,11 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
     family_kernels<rt::Family::LENS_SOFT>(ALL_SHAPES),
     family_kernels<rt::Family::TEX_SCAT>(ALL_SHAPES), family_kernels<rt::Family::TEX_SOFT>(ALL_SHAPES),
     family_kernels<rt::Family::TEX_LENS>(ALL_SHAPES), family_kernels<rt::Family::TEX_LENS_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::LIT_SCAT>(ALL_SHAPES), family_kernels<rt::Family::LIT_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::LIT_LENS>(ALL_SHAPES), family_kernels<rt::Family::LIT_LENS_SOFT>(ALL_SHAPES),
 };
-static_assert(rt::FAMILIES == 11 && (int)rt::Family::TEX_LENS_SOFT == 10, "KERNELS lists the families in enum order");
+static_assert(rt::FAMILIES == 15 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14,
+              "KERNELS lists the families in enum order");
 
 const void *kernel_of(rt::Family f, const Shape &s)
 {
@@ -414,12 +421,13 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T);
+    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit);
     const bool lens = rt::has_lens(lfam);
     if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
     // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
     // scene buffer that is current now travel in its place
     if (rt::has_tex(lfam)) { k.lens.mat = ctx->lens_mat; k.lens.tex = ctx->tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
+    if (rt::has_lit(lfam)) k.lens.lit = ctx->lit_off;                // (the lighting kernels are texture kernels: the above too)
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
     const size_t table = (size_t)(ctx->L + 1) * (rt::padS(ctx->S, ctx->NC) + rt::pad4(ctx->NC)) * rt::CULL_STRIDE * sizeof(float);
@@ -502,7 +510,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // The feature family (family_of) picks the twins of these variants: their LDS images hold the material block too
     // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt_ctx::lens_mat), and their parked variants the
     // family's per-thread slots (rt::lds_slots).
-    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T);
+    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit);
     auto per_cu = [&](bool nr) {
         const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->M);
         if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
@@ -798,7 +806,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
                      const float *light_radius, int shadow_samples, const rt_texture *textures = nullptr, int T = 0,
                      const int32_t *sphere_texture = nullptr, const int32_t *plane_texture = nullptr, const float *texels = nullptr,
-                     int64_t n_texels = 0);
+                     int64_t n_texels = 0, const float *light_rgb = nullptr, bool lighting = false);
 
 int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                                    int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
@@ -831,15 +839,45 @@ int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float 
                      light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels);
 }
 
+int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
+                          int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
+                          const int32_t *plane_material, const float *light_radius, int shadow_samples,
+                          const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
+                          const float *texels, int64_t n_texels, const float *light_rgb)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
+    static const float none = 0.0f;
+    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
+                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels,
+                     light_rgb, true);
+}
+
 // Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights; textures ...
-// n_texels: the arguments of rt_set_scene_textures (T == 0: none).
+// n_texels: the arguments of rt_set_scene_textures (T == 0: none); light_rgb: nullptr or the (L, 3) colours of
+// rt_set_scene_lighting, the one entry (lighting) that takes a table of 8 columns.
 static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
                      const float *light_radius, int shadow_samples, const rt_texture *textures, int T,
-                     const int32_t *sphere_texture, const int32_t *plane_texture, const float *texels, int64_t n_texels)
+                     const int32_t *sphere_texture, const int32_t *plane_texture, const float *texels, int64_t n_texels,
+                     const float *light_rgb, bool lighting)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (ncols != 3 && ncols != 5 && ncols != 6) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3, 5 or 6");
+    if (ncols != 3 && ncols != 5 && ncols != 6 && !(lighting && ncols == 8))
+        return fail(ctx, RT_ERR_BAD_ARG, lighting ? "ncols must be 3, 5, 6 or 8" : "ncols must be 3, 5 or 6");
+    // lighting: validated here and below (the spec and shin columns); a scene whose lights are all bitwise (1, 1, 1) and whose rows
+    // all have spec 0 is exactly rt_set_scene_textures' (lit stays false), any other runs the lighting kernels
+    bool lit = false;
+    if (light_rgb) {
+        if (L < 0 || L > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
+        static const float one = 1.0f;
+        for (int i = 0; i < 3 * L; ++i) {
+            if (!(std::isfinite(light_rgb[i]) && light_rgb[i] >= 0.0f))
+                return fail(ctx, RT_ERR_BAD_ARG, "light_rgb[" + std::to_string(i / 3) + "] must be finite and >= 0");
+            lit = lit || std::memcmp(&light_rgb[i], &one, sizeof one) != 0;
+        }
+    }
+    std::vector<double> spec_shin;                                  // ncols == 8: {spec, log2(shin)} per row
     // area lights (light_radius: nullptr from rt_set_scene_materials_scatter): validated here; a scene with every radius 0 is
     // exactly rt_set_scene_materials_scatter's (soft stays false), one with a radius > 0 runs the area-light kernels
     bool soft = false;
@@ -870,16 +908,30 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
             if (!(r[4] > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": ior must be > 0");
             if (r[3] > 0.0 && r[2] != 0.0)
                 return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have refl == 0");
-            if (ncols == 6) {
+            if (ncols >= 6) {
                 if (!(r[5] >= 0.0 && r[5] <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": rough must be in [0, 1]");
                 if (r[3] > 0.0 && r[5] > 0.0)
                     return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have rough == 0");
                 rough = rough || r[5] > 0.0;
             }
             glass = glass || r[3] > 0.0;
+            if (ncols == 8) {
+                if (!(r[6] >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": spec must be >= 0");
+                int lg = -1;
+                for (int i = 0; i <= 10; ++i) if (r[7] == (double)(1 << i)) lg = i;
+                if (lg < 0) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": shin must be one of 1, 2, 4, ..., 1024");
+                lit = lit || r[6] > 0.0;
+            }
         }
         cols = rough ? 6 : (glass ? 5 : 3);
         try {
+            if (ncols == 8) {
+                spec_shin.resize((size_t)2 * M);
+                for (int m = 0; m < M; ++m) {
+                    spec_shin[(size_t)2 * m] = materials[(size_t)8 * m + 6];
+                    spec_shin[(size_t)2 * m + 1] = std::log2(materials[(size_t)8 * m + 7]);   // (exact: a power of two)
+                }
+            }
             packed.resize((size_t)cols * M);
         } catch (const std::bad_alloc &) {
             return fail(ctx, RT_ERR_ALLOC, "out of host memory");
@@ -905,6 +957,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
     if ((S && !spheres) || (L && !lights) || (P && !planes)) return fail(ctx, RT_ERR_BAD_ARG, "NULL scene array with non-zero count");
     if (M < 0 || M > RT_MAX_MATERIALS) return fail(ctx, RT_ERR_BAD_ARG, "material count outside 0..RT_MAX_MATERIALS");
+    if (lit && !(M > 0 && materials)) return fail(ctx, RT_ERR_BAD_ARG, "lighting needs a material table (M >= 1)");
     if (M > 0) {
         if (!materials) return fail(ctx, RT_ERR_BAD_ARG, "materials is NULL with M > 0");
         if ((S && !sphere_material) || (P && !plane_material)) return fail(ctx, RT_ERR_BAD_ARG, "NULL material id array with non-zero count");
@@ -955,7 +1008,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         textured = textured || plane_texture[k] >= 0;
     }
     int nclusters = 0;
-    size_t lens_off = 0, tex_off = 0;
+    size_t lens_off = 0, tex_off = 0, lit_off = 0;
     try {
         // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
         // are evaluated here, once, in float32: r*r (intersections.py:21), the plane shading normal
@@ -1006,7 +1059,9 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         lens_off = (M > 0 && cols < 6) ? mat_off + matd : mat_off;
         // the texture block (rt::tex_doubles) behind everything else
         tex_off = mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0);
-        std::vector<double> rec(tex_off + (textured ? rt::tex_doubles(T) : 0), 0.0);
+        // and the lighting block (rt::lit_doubles) behind that
+        lit_off = tex_off + (textured ? rt::tex_doubles(T) : 0);
+        std::vector<double> rec(lit_off + (lit ? rt::lit_doubles(S, P, L) : 0), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -1084,11 +1139,12 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         // textures: the records with what texel_of reads (dimensions and their reciprocals as doubles, the first texel's entry of
         // the texel array); the texel array starts with the S + P slots' own colours (exact: the scene is float32) and texture
         // ids (-1: none), so that a hit without a texture reads its colour the same way
+        // (a lit scene without a textured object has the array too, every id -1: the lighting kernels are texture kernels)
         std::vector<float> tx;
-        if (textured) {
+        if (textured || lit) {
             double *tb = rec.data() + tex_off;
-            tb[0] = (double)T;
-            for (int t = 0; t < T; ++t) {
+            if (textured) tb[0] = (double)T;
+            for (int t = 0; t < T && textured; ++t) {
                 double *r = tb + 1 + (size_t)rt::TEX_STRIDE * t;
                 const rt_texture &x = textures[t];
                 for (int a = 0; a < 3; ++a) {
@@ -1099,17 +1155,31 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                 }
                 r[18] = (double)((long long)S + P + x.first);
             }
-            tx.assign(4 * ((size_t)S + P + (size_t)n_texels), 0.0f);
+            tx.assign(4 * ((size_t)S + P + (size_t)(textured ? n_texels : 0)), 0.0f);
             for (int slot = 0; slot < S; ++slot) {
                 for (int c = 0; c < 3; ++c) tx[4 * (size_t)slot + c] = spheres[(4 + c) * S + order[slot]];
-                tx[4 * (size_t)slot + 3] = sphere_texture ? (float)sphere_texture[order[slot]] : -1.0f;
+                tx[4 * (size_t)slot + 3] = (textured && sphere_texture) ? (float)sphere_texture[order[slot]] : -1.0f;
             }
             for (int k = 0; k < P; ++k) {
                 for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + k) + c] = planes[(6 + c) * P + k];
-                tx[4 * ((size_t)S + k) + 3] = plane_texture ? (float)plane_texture[k] : -1.0f;
+                tx[4 * ((size_t)S + k) + 3] = (textured && plane_texture) ? (float)plane_texture[k] : -1.0f;
             }
-            for (int64_t i = 0; i < n_texels; ++i)
+            for (int64_t i = 0; i < n_texels && textured; ++i)
                 for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + P + (size_t)i) + c] = texels[3 * i + c];
+        }
+        // lighting: the lights' colours (widened: exact), then per object slot its row's spec / n (n: the shadow samples of an
+        // area-light scene, else 1; a float64 division, as lamb / n) and log2(shin)
+        if (lit) {
+            double *lb = rec.data() + lit_off;
+            for (int k = 0; k < L; ++k)
+                for (int c = 0; c < 3; ++c) lb[(size_t)rt::LT_STRIDE * k + c] = light_rgb ? (double)light_rgb[3 * k + c] : 1.0;
+            double *ob = lb + (size_t)rt::LT_STRIDE * L;
+            const double n = soft ? (double)shadow_samples : 1.0;
+            for (size_t j = 0; j < (size_t)S + P; ++j) {
+                const int m = j < (size_t)S ? sphere_material[order[j]] : plane_material[j - S];
+                ob[2 * j] = spec_shin.empty() ? 0.0 : spec_shin[(size_t)2 * m] / n;
+                ob[2 * j + 1] = spec_shin.empty() ? 0.0 : spec_shin[(size_t)2 * m + 1];
+            }
         }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
@@ -1120,7 +1190,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         ctx->scene_readers[next].clear();
         int rc = ensure(ctx, ctx->scene[next], bytes);
         if (rc != RT_OK) return rc;
-        if (textured) {
+        if (textured || lit) {
             rc = ensure(ctx, ctx->texels[next], tx.size() * sizeof(float));
             if (rc != RT_OK) return rc;
             RT_HIP(ctx, hipMemcpyAsync(ctx->texels[next].p, tx.data(), tx.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -1154,6 +1224,8 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
     ctx->lens_mat = (long long)lens_off;
     ctx->T = textured ? T : 0;
     ctx->tex_off = (long long)tex_off;
+    ctx->lit = lit;
+    ctx->lit_off = (long long)lit_off;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

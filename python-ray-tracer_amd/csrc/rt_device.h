@@ -134,6 +134,8 @@ struct KParams {
             // TEX kernels (rt_set_scene_textures with a textured object; lens or not, they read `mat` too):
             long long tex;     // offset (doubles) in `scene` of the texture block (tex_doubles)
             const float *texels;   // 16 B per entry: {R,G,B, texture id or -1} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels
+            // LIT kernels (rt_set_scene_lighting with a coloured light or a specular row; they are TEX kernels too):
+            long long lit;     // offset (doubles) in `scene` of the lighting block (lit_doubles)
         } lens;
     };
 };
@@ -324,14 +326,18 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
 // TEX_*: the texture twins of SCAT, SOFT, LENS and LENS_SOFT (rt_set_scene_textures with a textured object): the hit's colour is a
 // texel chosen at the hit point (texel_of).  They are appended: tools/isa_compare.py matches kernels by the family's number.
-enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT, TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT };
-constexpr int FAMILIES = 11;
+// LIT_*: the lighting twins of the four TEX families (rt_set_scene_lighting with a light that is not (1, 1, 1) or a row with
+// spec > 0): every light has a colour and a hit a Blinn-Phong highlight (trace_bounce).  Appended too, for the same reason.
+enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT, TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT,
+                    LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT };
+constexpr int FAMILIES = 15;
 __host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
 __host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
 __host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
-__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT; }
-__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT; }
+__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT || f == Family::LIT_SOFT || f == Family::LIT_LENS_SOFT; }
+__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT || f == Family::LIT_LENS || f == Family::LIT_LENS_SOFT; }
 __host__ __device__ constexpr bool has_tex(Family f) { return f >= Family::TEX_SCAT; }
+__host__ __device__ constexpr bool has_lit(Family f) { return f >= Family::LIT_SCAT; }
 __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
 
 // Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
@@ -355,8 +361,10 @@ __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 
 // camera, so trace 0's closest-hit query takes the origin form of the cull (trace_bounce).
 // TEX (texture kernels, rt_set_scene_textures with a textured object; SCAT too, and SOFT / LENS as their twins): no slot and no
 // LDS: texture records, ids and texels are read from global memory where a hit needs them (texel_of).
+// LIT (lighting kernels, rt_set_scene_lighting; TEX too): no slot and no LDS either: the lights' colours and the hit's spec / n
+// and log2(shin) are read from the scene's lighting block in global memory inside the light loop (trace_bounce, lit_doubles).
 template <Family F, int WSLOT, bool FRESH> struct MatState {
-    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F);
+    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F), lit = has_lit(F);
     static constexpr int COLS = table_cols(F);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
@@ -377,7 +385,7 @@ template <Family F, int WSLOT, bool FRESH> struct MatState {
     }
 };
 template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
-    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false;
+    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false, lit = false;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1559,6 +1567,75 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         RT_MARK(4);
 
         const double *lt = lds.recs() + plb + opaque(P) * PL_STRIDE;
+        if constexpr (MS::lit) {
+        // LIT (rt_set_scene_lighting, mi355rt.h): light m has a colour e_m and the hit a Blinn-Phong highlight of strength spec / n
+        // and exponent shin.  e_m, spec / n and log2(shin) come from the scene's lighting block in global memory (lit_doubles): e_m
+        // by a wave-uniform address, the hit's pair by its slot, the one 32-bit value this keeps live across the shadow queries.
+        // The shadow query is asked when the Lambert term (k > 0) or the highlight (spec > 0 and Ld.N > 0) wants it; spec > 0 is
+        // read off the stored spec / n, which gives the same bytes where the quotient underflows to 0 (mi355rt.h).  Ld is not
+        // held across the query either: a lane that is lit and whose hit has spec > 0 forms it again, the same way from the same operands (the soft key
+        // comes from its slot again, the light's record through an opaque index: again()), and reads -d for the half vector back from dpark.
+        const unsigned lslot = (unsigned)((type == HIT_SPHERE) ? idx : S + idx);
+        auto lit_row = [&]() { return (volatile const double *)(p.scene + (size_t)p.lens.lit + (size_t)LT_STRIDE * L) + 2 * (size_t)lslot; };
+        auto again = [](int m) { asm volatile("" : "+v"(m)); return m; };   // the light's index, opaque: what is read through it is read again
+        auto point_Ld = [&](int m) {
+            const double *g = lt + m * LT_STRIDE;
+            return normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});     // common.py:84-91
+        };
+        auto soft_Ld = [&](int m, int i) {
+            const double *g = lt + m * LT_STRIDE;
+            const unsigned key = (unsigned)*ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) ^ (((unsigned)b << 15) | ((unsigned)m << 9) | ((unsigned)i << 5));
+            const V3 Q = soft_light_point(key, g);
+            return normalize3(V3{Q.x - Pt.x, Q.y - Pt.y, Q.z - Pt.z});
+        };
+        auto lit_add = [&](int m, double k, auto &&form_Ld) {                 // light m, not occluded
+            const double *e = p.scene + (size_t)p.lens.lit + LT_STRIDE * m;
+            const double er = e[0], eg = e[1], eb = e[2];
+            if (k > 0.0) rgb = V3{rgb.x + (k * er) * col(0), rgb.y + (k * eg) * col(1), rgb.z + (k * eb) * col(2)};
+            volatile const double *lr = lit_row();
+            const double spec = lr[0];
+            if (spec > 0.0) {                                                 // (Ld again only for a hit that can have a highlight)
+              const V3 Ld = form_Ld();
+              if (dot3(Ld, N) > 0.0) {
+                const V3 dd = dpark.get();
+                const V3 H = normalize3(V3{Ld.x - dd.x, Ld.y - dd.y, Ld.z - dd.z});   // Ld + (-d); a zero sum: NaN, no highlight
+                const double s = dot3(N, H);
+                if (s > 0.0) {
+                    double q = s;
+                    const int nsq = (int)lr[1];
+#pragma unroll 1
+                    for (int i = 0; i < nsq; ++i) q = q * q;                  // s ** shin, log2(shin) squarings
+                    const double a = spec * q;
+                    rgb = V3{rgb.x + a * er, rgb.y + a * eg, rgb.z + a * eb};
+                }
+              }
+            }
+        };
+        for (int m = 0; m < L; ++m) {
+            if constexpr (MS::soft) {
+#pragma unroll 1
+                for (int i = 0; i < ms.nsh; ++i) {
+                    const V3 Ld = soft_Ld(m, i);
+                    const double cN = dot3(Ld, N);
+                    const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * cN;   // :99
+                    RT_MARK(5);
+                    if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
+                        const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
+                        if (!occluded) lit_add(m, k, [&]() { return soft_Ld(again(m), i); });
+                    }
+                }
+            } else {
+                const V3 Ld = point_Ld(m);
+                const double cN = dot3(Ld, N);
+                const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * cN;       // :99
+                RT_MARK(5);
+                if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
+                    const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                    if (!occluded) lit_add(m, k, [&]() { return point_Ld(again(m)); });
+                }
+            }
+        }
+        } else
         if constexpr (MS::soft) {
         // SOFT: the lights array of :86 is the L*n shadow sample points Q, (m, i) m-major (soft_light_point), and lamb (the
         // table's, host-divided by n) is lamb_b / n.  The rays do not pass through a light's centre: the shadow query takes the
@@ -1784,6 +1861,9 @@ __host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { retu
 __host__ __device__ inline size_t mat_doubles(int M, int S, int P, Family f) { return M > 0 ? 1 + (size_t)table_cols(f) * M + ((size_t)S + P + 1) / 2 + (has_soft(f) ? 1 : 0) : 0; }
 // The texture block of a scene with a textured object (KParams::lens.tex): T, then the T records of TEX_STRIDE doubles (texel_of).
 __host__ __device__ inline size_t tex_doubles(int T) { return T > 0 ? 1 + (size_t)TEX_STRIDE * T : 0; }
+// The lighting block of a scene that runs the LIT kernels (KParams::lens.lit): {e_r, e_g, e_b, -} per light (LT_STRIDE doubles),
+// then {spec / n, log2(shin)} per object slot (S spheres in slot order, then P planes).
+__host__ __device__ inline size_t lit_doubles(int S, int P, int L) { return (size_t)LT_STRIDE * L + 2 * ((size_t)S + P); }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours

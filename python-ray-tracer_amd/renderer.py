@@ -119,7 +119,8 @@ class Renderer:
         self.close()
 
     # -- inputs -----------------------------------------------------------------------------
-    def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1, textures=None):
+    def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1, textures=None,
+                  light_rgb=None):
         """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
@@ -132,7 +133,11 @@ class Renderer:
         (rt_set_scene_area_lights).  Area lights need a material table.
         textures: None, or (records, sphere_ids int32 (S,), plane_ids int32 (P,), texels float32 (N,3)) as
         Scene.generate_textures() returns them: records a list of (origin (3,), axes (3,3), (nx, ny, nz), first); an id of -1
-        means no texture (rt_set_scene_textures).  Textures need a material table."""
+        means no texture (rt_set_scene_textures).  Textures need a material table.
+        light_rgb: None (every light white, (1, 1, 1)), or float32 (L,3) colours times strengths as Scene.get_light_colors()
+        returns them.  A table of shape (M,8), rows amb, lamb, refl, trans, ior, rough, spec, shin, gives materials a
+        Blinn-Phong highlight of strength spec (colour units) and exponent shin (1, 2, 4, ..., 1024).  Either goes through
+        rt_set_scene_lighting and needs a material table."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
         rad = None
@@ -147,6 +152,13 @@ class Renderer:
                 rad = None
         if textures is not None and materials is None:
             raise ValueError("textures need a material table: pass materials=...")
+        rgb = None
+        if light_rgb is not None:
+            rgb = np.ascontiguousarray(light_rgb, dtype=np.float32).reshape(-1, 3)
+            if rgb.shape[0] != l.shape[1]:
+                raise ValueError(f"light_rgb: {rgb.shape[0]} colours for {l.shape[1]} lights")
+            if materials is None:
+                raise ValueError("light colours need a material table: pass materials=...")
         if materials is None:
             self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
                                                p.ctypes.data_as(fp), p.shape[1], int(flags)))
@@ -161,8 +173,9 @@ class Renderer:
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            if textures is not None:
-                records, tsid, tpid, texels = textures
+            if textures is not None or rgb is not None or ncols == 8:
+                records, tsid, tpid, texels = textures if textures is not None else (
+                    [], np.full(s.shape[1], -1, np.int32), np.full(p.shape[1], -1, np.int32), np.zeros((0, 3), np.float32))
                 T = len(records)
                 recs = (L.rt_texture * max(T, 1))()
                 for k, (o, ax, dims, first) in enumerate(records):
@@ -180,11 +193,14 @@ class Renderer:
                     raise ValueError(f"texture ids: {tsi.shape[0]} for {s.shape[1]} spheres, {tpi.shape[0]} for {p.shape[1]} planes")
                 tx = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1, 3)
                 zr = rad if rad is not None else np.zeros(l.shape[1], dtype=np.float32)
-                self._check(self._lib.rt_set_scene_textures(
-                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
-                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
-                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip), zr.ctypes.data_as(fp), int(shadow_samples),
-                    recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip), tx.ctypes.data_as(fp), tx.shape[0]))
+                args = (self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
+                        p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
+                        si.ctypes.data_as(ip), pi.ctypes.data_as(ip), zr.ctypes.data_as(fp), int(shadow_samples),
+                        recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip), tx.ctypes.data_as(fp), tx.shape[0])
+                if rgb is not None or ncols == 8:
+                    self._check(self._lib.rt_set_scene_lighting(*args, rgb.ctypes.data_as(fp) if rgb is not None else None))
+                else:
+                    self._check(self._lib.rt_set_scene_textures(*args))
             elif rad is not None:
                 self._check(self._lib.rt_set_scene_area_lights(
                     self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),

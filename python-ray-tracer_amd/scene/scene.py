@@ -10,6 +10,7 @@ import numpy as np
 
 from .colors import RED, BLUE, MAGENTA, YELLOW, GREEN, GREY
 from .texture import Texture, RT_MAX_TEXTURES, RT_MAX_TEXELS
+from .lighting import squarings
 
 
 @dataclass(frozen=True)
@@ -21,13 +22,18 @@ class Material:
     have refl == 0.  transparency finite and >= 0, ior finite and > 0 (include/mi355rt.h: rt_set_scene_materials_ex).
     roughness > 0 makes the reflection rough: the reflected ray is scattered around the mirror direction by up to `roughness`
     (a "fuzzy metal"), reproducibly per sample and seed; finite and in [0, 1], and 0 for a transparent material
-    (include/mi355rt.h: rt_set_scene_materials_scatter)."""
+    (include/mi355rt.h: rt_set_scene_materials_scatter).
+    specular > 0 gives the object a Blinn-Phong highlight in the lights' colours: its strength in colour units (the 0..255 scale
+    of the objects' colours), finite and >= 0; shininess is the exponent, one of 1, 2, 4, ..., 1024
+    (include/mi355rt.h: rt_set_scene_lighting)."""
     amb: float
     lamb: float
     refl: float
     transparency: float = 0.0
     ior: float = 1.0
     roughness: float = 0.0
+    specular: float = 0.0
+    shininess: int = 1
 
     def __post_init__(self):
         # (amb, lamb and refl are checked where the table is set, as before: rt_set_scene_materials refuses non-finite ones)
@@ -41,6 +47,9 @@ class Material:
             raise ValueError(f"roughness must be finite and in [0, 1], got {self.roughness}")
         if float(self.transparency) > 0.0 and float(self.roughness) > 0.0:
             raise ValueError("a transparent material (transparency > 0) cannot be rough (roughness > 0)")
+        if not (np.isfinite(float(self.specular)) and float(self.specular) >= 0.0):
+            raise ValueError(f"specular must be finite and >= 0, got {self.specular}")
+        squarings(self.shininess)                                 # (ValueError unless one of 1, 2, 4, ..., 1024)
 
     @property
     def transparent(self):
@@ -58,6 +67,13 @@ class Material:
 
     def key6(self):
         return self.key5() + (float(self.roughness),)
+
+    @property
+    def glossy(self):
+        return float(self.specular) > 0.0
+
+    def key8(self):
+        return self.key6() + (float(self.specular), float(self.shininess))
 
 
 @dataclass
@@ -78,15 +94,30 @@ class Sphere:
 class Light:
     """A light at `origin`.  radius > 0 makes it an area light, a ball of that radius: shadows from it are soft (penumbrae),
     sampled at Renderer.set_scene's shadow_samples points per light (include/mi355rt.h: rt_set_scene_area_lights).  The radius
-    is float32, finite and >= 0; 0 (the default) is the reference's point light."""
+    is float32, finite and >= 0; 0 (the default) is the reference's point light.
+    color (three components) times intensity is the light's colour and strength e, float32, every component finite and >= 0;
+    the default (1, 1, 1) is the reference's white light of unit strength (include/mi355rt.h: rt_set_scene_lighting)."""
     origin: object
     radius: float = 0.0
+    color: object = (1.0, 1.0, 1.0)
+    intensity: float = 1.0
     data_length: ClassVar[int] = 3
 
     def __post_init__(self):
         r = float(self.radius)
         if not (np.isfinite(r) and 0.0 <= r <= float(np.finfo(np.float32).max)):
             raise ValueError(f"light radius must be finite and >= 0, got {self.radius}")
+        c = np.asarray(self.color, dtype=np.float64)
+        if c.shape != (3,):
+            raise ValueError(f"light color must have three components, got {self.color!r}")
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = self.rgb()
+        if not (np.isfinite(e).all() and (e >= 0.0).all()):
+            raise ValueError(f"light color times intensity must be finite and >= 0, got {self.color!r} x {self.intensity}")
+
+    def rgb(self):
+        """e = float32(intensity * color), (3,)."""
+        return (float(self.intensity) * np.asarray(self.color, dtype=np.float64)).astype(np.float32)
 
     def to_array(self):
         return np.asarray(self.origin, dtype=np.float64).astype(np.float32)
@@ -131,6 +162,10 @@ class Scene:
         """float32 (L,): the lights' radii, for Renderer.set_scene(..., light_radius=...)."""
         return np.array([float(li.radius) for li in self.lights], dtype=np.float32)
 
+    def get_light_colors(self):
+        """float32 (L, 3): the lights' colours times strengths, for Renderer.set_scene(..., light_rgb=...)."""
+        return np.array([li.rgb() for li in self.lights], dtype=np.float32).reshape(-1, 3)
+
     def generate_scene(self):
         return self.get_spheres(), self.get_lights(), self.get_planes()
 
@@ -138,16 +173,17 @@ class Scene:
         """(table float64 (M,3) rows amb, lamb, refl; sphere_ids int32 (S,); plane_ids int32 (P,)) for
         Renderer.set_scene(..., materials=...).  Objects without a material get `default`; equal materials share one row,
         in the order of first use (spheres, then planes).  If any material is rough the table is (M,6), rows
-        amb, lamb, refl, transparency, ior, roughness; else if any is transparent it is (M,5), the first five of those."""
+        amb, lamb, refl, transparency, ior, roughness; else if any is transparent it is (M,5), the first five of those.  If any
+        material has specular > 0 the table is (M,8): those six, then specular and shininess."""
         rows, index = [], {}
         mats = [o.material if o.material is not None else default for o in list(self.spheres) + list(self.planes)]
-        ncols = 6 if any(m.rough for m in mats) else (5 if any(m.transparent for m in mats) else 3)
+        ncols = 8 if any(m.glossy for m in mats) else 6 if any(m.rough for m in mats) else (5 if any(m.transparent for m in mats) else 3)
 
         def ids(objs):
             out = np.zeros(len(objs), dtype=np.int32)
             for i, o in enumerate(objs):
                 m = o.material if o.material is not None else default
-                k = {3: m.key, 5: m.key5, 6: m.key6}[ncols]()
+                k = {3: m.key, 5: m.key5, 6: m.key6, 8: m.key8}[ncols]()
                 if k not in index:
                     index[k] = len(rows)
                     rows.append(k)
