@@ -3,7 +3,7 @@
 
     python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
                                   [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]]
-                                  [--checker [--texture IMAGE]] [--lights] [--out output/render.png]
+                                  [--checker [--texture IMAGE]] [--lights] [--sky] [--out output/render.png]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -18,6 +18,8 @@ in front of it and behind it blurred.  Use it with --spp 16, which averages the 
 front of the camera, 2 units wide.  --spp N averages the texel edges.
 --lights lights the default scene with one warm light, one cool light and one dim light, and gives it glossy spheres and glass
 with a highlight (rt_set_scene_lighting), over the --glass scene unless --scatter is given.
+--sky puts the default scene with a mirror floor, two glass spheres and two of brushed metal under a blue gradient with a low sun
+and its halo (rt_set_scene_sky), and raises the camera so that the horizon is in the picture; --spp N smooths the sun's edge.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -32,7 +34,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import python_ray_tracer_amd as pkg
 from python_ray_tracer_amd import _lib as L
-from python_ray_tracer_amd.scene import Scene, Camera, Light, Material, Plane, Texture
+from python_ray_tracer_amd.scene import Scene, Camera, Light, Material, Plane, Sky, Texture
 from python_ray_tracer_amd.viewer import convert_array_to_image
 
 
@@ -55,10 +57,12 @@ def main():
     ap.add_argument("--checker", action="store_true", help="a checkered floor and a solid checker on sphere 0 (textures)")
     ap.add_argument("--texture", default=None, metavar="IMAGE", help="--checker: also lay this picture on the floor")
     ap.add_argument("--lights", action="store_true", help="a warm, a cool and a dim light; glossy spheres and glass (lighting)")
+    ap.add_argument("--sky", action="store_true", help="a blue gradient with a low sun behind a mirror floor, glass and metal (sky)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=[0, -30, 0])
+    euler = [0, -12, 0] if a.sky else [0, -30, 0]                   # --sky: the horizon a third of the way down the picture
+    cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=euler)
     with pkg.Renderer(0) as r:
         scene = Scene.default_scene()
         mats = None
@@ -69,10 +73,10 @@ def main():
             scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
             scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
-        elif a.materials or a.glass or a.soft or a.dof > 0 or a.checker or a.lights:
+        elif a.materials or a.glass or a.soft or a.dof > 0 or a.checker or a.lights or a.sky:
             for p in scene.planes:
                 p.material = Material(0.0, 0.3, 0.8)                # a mirror floor
-            if a.glass or a.lights:                                 # clear glass; ior 2.4 (diamond) shows total internal reflection
+            if a.glass or a.lights or a.sky:                        # clear glass; ior 2.4 (diamond) shows total internal reflection
                 scene.spheres[0].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=1.5)
                 scene.spheres[5].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=2.4)
             if a.lights:                                            # a highlight on the glass, and two glossy spheres
@@ -80,6 +84,9 @@ def main():
                 scene.spheres[5].material = Material(0.0, 0.0, 0.0, transparency=0.9, ior=2.4, specular=220.0, shininess=256)
                 scene.spheres[1].material = Material(0.05, 0.7, 0.1, specular=160.0, shininess=64)
                 scene.spheres[2].material = Material(0.05, 0.7, 0.1, specular=90.0, shininess=8)
+            if a.sky:                                               # brushed metal, as --scatter's
+                scene.spheres[2].material = Material(0.05, 0.3, 0.8, roughness=0.3)
+                scene.spheres[4].material = Material(0.0, 0.2, 0.9, roughness=0.05)
             mats = scene.generate_materials(Material(0.05, 0.8, 0.0))   # matte spheres: no reflection
         colors = None
         if a.lights:                                                # a warm key light, a cool fill, a dim third
@@ -90,6 +97,10 @@ def main():
                 li.color, li.intensity = color, intensity
             scene.lights = [Light(li.origin, li.radius, li.color, li.intensity) for li in scene.lights]   # (validated)
             colors = scene.get_light_colors()
+        if a.sky:                                                   # the sky lights nothing: the scene keeps its three lights
+            scene.sky = Sky(zenith=(25, 70, 190), horizon=(190, 215, 240), nadir=(70, 65, 60), sharpness=2,
+                            sun_direction=(1.0, 0.25, 0.12), sun_angle_deg=2.5, sun_color=(255, 240, 200),
+                            halo_color=(130, 100, 50), halo_shininess=64)
         radii = None
         if a.soft:
             for li in scene.lights:
@@ -108,11 +119,11 @@ def main():
                 mats = scene.generate_materials(Material(0.05, 0.8, 0.0))
             textures = scene.generate_textures()
         r.set_scene(*scene.generate_scene(), materials=mats, light_radius=radii, shadow_samples=a.shadow_samples, textures=textures,
-                    light_rgb=colors)
+                    light_rgb=colors, sky=scene.get_sky())
         r.set_camera(cam.position, cam.rotation)
         if a.dof > 0:
             focus = cam.focus_on(scene.spheres[a.focus_on_sphere].origin)
-            cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=[0, -30, 0], aperture=a.dof, focus_distance=focus)
+            cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=euler, aperture=a.dof, focus_distance=focus)
             r.set_lens(*cam.lens)
         r.set_raygen(w, h, *cam.raygen())
         image = r.host_array((h, w, 3), np.uint8)
@@ -130,7 +141,7 @@ def main():
         r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky}: {ms:.4f} ms per frame on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -362,6 +362,53 @@ int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float 
                           const float *texels, int64_t n_texels,
                           const float *light_rgb);
 
+/* The same with a sky: the colour of a ray that hits nothing, a gradient with a sun disc and a halo around it.
+ *   sky   NULL, or RT_SKY_DOUBLES = 24 float64:
+ *           0..2    up         unit vector towards the zenith
+ *           3..5    zenith     RGB in colour units (the 0..255 scale of the objects' colours)
+ *           6..8    horizon    RGB
+ *           9..11   nadir      RGB
+ *           12      sharp      1, 2, 4, 8 or 16: how fast the gradient leaves the horizon colour
+ *           13..15  sun_dir    unit vector towards the sun
+ *           16      sun_cos    the disc is where dot(d, sun_dir) >= sun_cos; a value > 1 means no disc
+ *           17..19  sun_rgb    colour added inside the disc
+ *           20..22  halo_rgb   colour of the glow around the sun
+ *           23      halo_shin  1, 2, 4, ..., 1024: the halo's exponent
+ * A scene has a sky when sky != NULL and some component of the five colours is not zero.  Every other scene is exactly
+ * rt_set_scene_lighting's: the same kernels and bytes.  In a scene with a sky, a trace that is made and finds nothing
+ * (get_intersection reports 404, trace.py:56-57) returns sky(d) instead of (0, 0, 0).  It still returns the 404 sentinels for point
+ * and direction, so the path ends as before and its colour is weighted like any other trace's: trace 0 sets the sample to sky(d),
+ * trace b >= 1 adds W_b * sky(d).  d is the direction the trace was called with: the primary or lens ray, the reflected, refracted
+ * or scattered direction, or the straight continuation through a window; it is unit to rounding and is not normalised again.
+ * float64, no fused multiply-add, in this order, per channel c (dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, common.py:35-37):
+ *   h   = dot(d, up)
+ *   a   = h < 0 ? -h : h;   t = a > 1 ? 1 : a;   far = h < 0 ? nadir : zenith      (h = -0.0 takes zenith with t = 0)
+ *   sharp = 2^j, j > 0:     q = 1 - t;  j times q = q * q;  t = 1 - q               (j = 0: t as it is)
+ *   g_c = horizon_c + (t * (far_c - horizon_c))
+ *   s   = dot(d, sun_dir)
+ *   s > 0:          q = s;  log2(halo_shin) times q = q * q;   g_c = g_c + (halo_c * q)
+ *   s >= sun_cos:   g_c = g_c + sun_c
+ * (far_c - horizon_c is a float64 subtraction; the library forms it once per scene, which gives the same bits.)  There is no
+ * pow(), no atan2 and no image lookup.  A uniform sky (zenith == horizon == nadir, black sun and halo) is exactly its colour in
+ * every direction.  The sky is seen through glass and in mirrors.  It gives no light: shadow rays, the ambient and Lambert terms
+ * and the highlights are unchanged (a caller who wants sunlight adds a light along sun_dir).  A ray that scatter sends through its
+ * surface traces nothing, so it adds nothing, as before.  Every AA mode, the lattice path, RT_FLAG_AA_PER_PIXEL, an explicit grid,
+ * column slabs, rt_render, rt_render_begin/end, rt_render_device and rt_render_sequence give the same bytes.
+ * Invalid input (anything rt_set_scene_lighting refuses, a sky component that is not finite, a negative colour, |up|^2 or
+ * |sun_dir|^2 outside 1 +- 1e-6, a sharp or halo_shin that is not one of the listed values, a sky with M == 0): RT_ERR_BAD_ARG, and
+ * the previous scene stays current.  The sky travels with the scene: a frame in flight keeps the sky it was launched with.
+ * RT_FLAG_COUNT_RAYS is refused for such a scene.  RT_ABI_VERSION is unchanged: callers detect this entry point by its symbol. */
+#define RT_SKY_DOUBLES 24
+int rt_set_scene_sky(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L,
+                     const float *planes, int P, int flags,
+                     const double *materials, int M, int ncols,
+                     const int32_t *sphere_material, const int32_t *plane_material,
+                     const float *light_radius, int shadow_samples,
+                     const rt_texture *textures, int T,
+                     const int32_t *sphere_texture, const int32_t *plane_texture,
+                     const float *texels, int64_t n_texels,
+                     const float *light_rgb, const double *sky);
+
 /* camera_origin float64 (3,) and camera_rotation float64 (3,3) C-order   main.py:27-28 */
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9]);
 

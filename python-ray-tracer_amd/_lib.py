@@ -15,6 +15,7 @@ RT_MAX_SPP = 64
 RT_MAX_SHADOW_SAMPLES = 16
 RT_RENDER_SLOTS = 4
 RT_MAX_TEXTURES, RT_MAX_TEXTURE_DIM, RT_MAX_TEXELS = 64, 4096, 1 << 22
+RT_SKY_DOUBLES = 24
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -65,6 +66,10 @@ PROTOTYPES = {
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
                                         C.POINTER(rt_texture), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int64,
                                         _fp]),
+    "rt_set_scene_sky": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
+                                   C.POINTER(rt_texture), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int64,
+                                   _fp, _dp]),
     "rt_set_camera": (C.c_int, [_vp, _dp, _dp]),
     "rt_set_lens": (C.c_int, [_vp, C.c_double, C.c_double]),
     "rt_set_raygen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),

@@ -85,6 +85,8 @@ struct rt_ctx {
     long long tex_off = 0;        // offset (doubles) in the scene buffer of its texture block (rt::tex_doubles)
     bool lit = false;             // the scene runs the lighting kernels (a light colour that is not (1, 1, 1), or a row with spec > 0)
     long long lit_off = 0;        // offset (doubles) in the scene buffer of its lighting block (rt::lit_doubles)
+    bool sky = false;             // the scene runs the sky kernels (rt_set_scene_sky with a colour that is not zero); lit is set too
+    long long sky_off = 0;        // offset (doubles) in the scene buffer of its sky block (rt::SKY_DOUBLES)
     Buf texels[RT_SCENE_RING];    // per scene buffer of the ring: {R,G,B, texture id} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels;
                                   // allocated by the first textured (or lit) scene that lands in the slot, grown when one needs more
     double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
@@ -220,10 +222,12 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
 // have.  From the scene (M materials in a table of mat_cols columns, soft_n shadow samples per light) and the lens aperture.
-rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0, bool lit = false)
+rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0, bool lit = false, bool sky = false)
 {
     using F = rt::Family;
     if (M <= 0) return F::PLAIN;
+    if (sky)                                                         // (set_scene: a sky only with M >= 1; it sets lit too)
+        return lens_a > 0.0 ? (soft_n > 0 ? F::SKY_LENS_SOFT : F::SKY_LENS) : (soft_n > 0 ? F::SKY_SOFT : F::SKY_SCAT);
     if (lit)                                                         // (set_scene: lit only with M >= 1; textured or not)
         return lens_a > 0.0 ? (soft_n > 0 ? F::LIT_LENS_SOFT : F::LIT_LENS) : (soft_n > 0 ? F::LIT_SOFT : F::LIT_SCAT);
     if (T > 0)                                                       // (set_scene: T > 0 only with a textured object, and M >= 1)
@@ -265,7 +269,7 @@ constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
 // A family has one render kernel per shape, except
 //  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
 //  * the parked wave-uniform shapes (MODE 0 and 1) from REFR on, which the parking rule never picks (the static_assert below).
-// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture and the four lighting families included) 14.  Nothing else names a render kernel of a family other than
+// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture, the four lighting and the four sky families included) 14.  Nothing else names a render kernel of a family other than
 // PLAIN, so the kernels a family does not have are not compiled.
 constexpr bool has_kernel(rt::Family f, const Shape &s)
 {
@@ -321,8 +325,11 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
     family_kernels<rt::Family::TEX_LENS>(ALL_SHAPES), family_kernels<rt::Family::TEX_LENS_SOFT>(ALL_SHAPES),
     family_kernels<rt::Family::LIT_SCAT>(ALL_SHAPES), family_kernels<rt::Family::LIT_SOFT>(ALL_SHAPES),
     family_kernels<rt::Family::LIT_LENS>(ALL_SHAPES), family_kernels<rt::Family::LIT_LENS_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::SKY_SCAT>(ALL_SHAPES), family_kernels<rt::Family::SKY_SOFT>(ALL_SHAPES),
+    family_kernels<rt::Family::SKY_LENS>(ALL_SHAPES), family_kernels<rt::Family::SKY_LENS_SOFT>(ALL_SHAPES),
 };
-static_assert(rt::FAMILIES == 15 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14,
+static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14 &&
+              (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
               "KERNELS lists the families in enum order");
 
 const void *kernel_of(rt::Family f, const Shape &s)
@@ -421,13 +428,14 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit);
+    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit, ctx->sky);
     const bool lens = rt::has_lens(lfam);
     if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
     // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
     // scene buffer that is current now travel in its place
     if (rt::has_tex(lfam)) { k.lens.mat = ctx->lens_mat; k.lens.tex = ctx->tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
     if (rt::has_lit(lfam)) k.lens.lit = ctx->lit_off;                // (the lighting kernels are texture kernels: the above too)
+    if (rt::has_sky(lfam)) k.lens.sky = ctx->sky_off;                // (and the sky kernels lighting kernels)
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
     const size_t table = (size_t)(ctx->L + 1) * (rt::padS(ctx->S, ctx->NC) + rt::pad4(ctx->NC)) * rt::CULL_STRIDE * sizeof(float);
@@ -510,7 +518,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // The feature family (family_of) picks the twins of these variants: their LDS images hold the material block too
     // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt_ctx::lens_mat), and their parked variants the
     // family's per-thread slots (rt::lds_slots).
-    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit);
+    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit, ctx->sky);
     auto per_cu = [&](bool nr) {
         const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->M);
         if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
@@ -806,7 +814,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
                      const float *light_radius, int shadow_samples, const rt_texture *textures = nullptr, int T = 0,
                      const int32_t *sphere_texture = nullptr, const int32_t *plane_texture = nullptr, const float *texels = nullptr,
-                     int64_t n_texels = 0, const float *light_rgb = nullptr, bool lighting = false);
+                     int64_t n_texels = 0, const float *light_rgb = nullptr, bool lighting = false, const double *sky = nullptr);
 
 int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                                    int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
@@ -853,16 +861,52 @@ int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float 
                      light_rgb, true);
 }
 
+int rt_set_scene_sky(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
+                     int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
+                     const int32_t *plane_material, const float *light_radius, int shadow_samples,
+                     const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
+                     const float *texels, int64_t n_texels, const float *light_rgb, const double *sky)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
+    static const float none = 0.0f;
+    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
+                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels,
+                     light_rgb, true, sky);
+}
+
 // Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights; textures ...
 // n_texels: the arguments of rt_set_scene_textures (T == 0: none); light_rgb: nullptr or the (L, 3) colours of
-// rt_set_scene_lighting, the one entry (lighting) that takes a table of 8 columns.
+// rt_set_scene_lighting, the one entry (lighting) that takes a table of 8 columns; sky: nullptr or the RT_SKY_DOUBLES of rt_set_scene_sky.
 static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                      const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
                      const float *light_radius, int shadow_samples, const rt_texture *textures, int T,
                      const int32_t *sphere_texture, const int32_t *plane_texture, const float *texels, int64_t n_texels,
-                     const float *light_rgb, bool lighting)
+                     const float *light_rgb, bool lighting, const double *sky)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
+    // the sky: validated here; one whose five colours are all zero is no sky (has_sky stays false: exactly rt_set_scene_lighting),
+    // any other runs the sky kernels, which are lighting kernels (lit is set below)
+    bool has_sky = false;
+    int sky_sharp = 0, sky_shin = 0;                                // log2(sharp), log2(halo_shin)
+    if (sky) {
+        for (int i = 0; i < RT_SKY_DOUBLES; ++i)
+            if (!std::isfinite(sky[i])) return fail(ctx, RT_ERR_BAD_ARG, "sky[" + std::to_string(i) + "] is not finite");
+        for (int i : {3, 4, 5, 6, 7, 8, 9, 10, 11, 17, 18, 19, 20, 21, 22}) {
+            if (sky[i] < 0.0) return fail(ctx, RT_ERR_BAD_ARG, "sky[" + std::to_string(i) + "]: a colour must be >= 0");
+            has_sky = has_sky || sky[i] != 0.0;
+        }
+        for (int v : {0, 13}) {
+            const double n2 = sky[v] * sky[v] + sky[v + 1] * sky[v + 1] + sky[v + 2] * sky[v + 2];
+            if (!(n2 >= 1.0 - 1e-6 && n2 <= 1.0 + 1e-6))
+                return fail(ctx, RT_ERR_BAD_ARG, v == 0 ? "sky: up must be a unit vector" : "sky: sun_dir must be a unit vector");
+        }
+        sky_sharp = sky_shin = -1;
+        for (int i = 0; i <= 4; ++i) if (sky[12] == (double)(1 << i)) sky_sharp = i;
+        for (int i = 0; i <= 10; ++i) if (sky[23] == (double)(1 << i)) sky_shin = i;
+        if (sky_sharp < 0) return fail(ctx, RT_ERR_BAD_ARG, "sky: sharp must be one of 1, 2, 4, 8, 16");
+        if (sky_shin < 0) return fail(ctx, RT_ERR_BAD_ARG, "sky: halo_shin must be one of 1, 2, 4, ..., 1024");
+    }
     if (ncols != 3 && ncols != 5 && ncols != 6 && !(lighting && ncols == 8))
         return fail(ctx, RT_ERR_BAD_ARG, lighting ? "ncols must be 3, 5, 6 or 8" : "ncols must be 3, 5 or 6");
     // lighting: validated here and below (the spec and shin columns); a scene whose lights are all bitwise (1, 1, 1) and whose rows
@@ -958,6 +1002,8 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
     if ((S && !spheres) || (L && !lights) || (P && !planes)) return fail(ctx, RT_ERR_BAD_ARG, "NULL scene array with non-zero count");
     if (M < 0 || M > RT_MAX_MATERIALS) return fail(ctx, RT_ERR_BAD_ARG, "material count outside 0..RT_MAX_MATERIALS");
     if (lit && !(M > 0 && materials)) return fail(ctx, RT_ERR_BAD_ARG, "lighting needs a material table (M >= 1)");
+    if (has_sky && !(M > 0 && materials)) return fail(ctx, RT_ERR_BAD_ARG, "a sky needs a material table (M >= 1)");
+    lit = lit || has_sky;                                           // (white lights and spec 0 where the scene gave none)
     if (M > 0) {
         if (!materials) return fail(ctx, RT_ERR_BAD_ARG, "materials is NULL with M > 0");
         if ((S && !sphere_material) || (P && !plane_material)) return fail(ctx, RT_ERR_BAD_ARG, "NULL material id array with non-zero count");
@@ -1008,7 +1054,7 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         textured = textured || plane_texture[k] >= 0;
     }
     int nclusters = 0;
-    size_t lens_off = 0, tex_off = 0, lit_off = 0;
+    size_t lens_off = 0, tex_off = 0, lit_off = 0, sky_off = 0;
     try {
         // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
         // are evaluated here, once, in float32: r*r (intersections.py:21), the plane shading normal
@@ -1061,7 +1107,9 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
         tex_off = mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0);
         // and the lighting block (rt::lit_doubles) behind that
         lit_off = tex_off + (textured ? rt::tex_doubles(T) : 0);
-        std::vector<double> rec(lit_off + (lit ? rt::lit_doubles(S, P, L) : 0), 0.0);
+        // and the sky block (rt::SKY_DOUBLES) last
+        sky_off = lit_off + (lit ? rt::lit_doubles(S, P, L) : 0);
+        std::vector<double> rec(sky_off + (has_sky ? rt::SKY_DOUBLES : 0), 0.0);
         double *sp = rec.data();
         unsigned codes = 0;
         for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
@@ -1181,6 +1229,24 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                 ob[2 * j + 1] = spec_shin.empty() ? 0.0 : spec_shin[(size_t)2 * m + 1];
             }
         }
+        // the sky, laid out for rt::sky_color: the gradient as the horizon's colour and the two differences from it, the two
+        // exponents as numbers of squarings (int64)
+        if (has_sky) {
+            double *kb = rec.data() + sky_off;
+            for (int c = 0; c < 3; ++c) {
+                kb[c] = sky[c];
+                kb[3 + c] = sky[6 + c];
+                kb[6 + c] = sky[3 + c] - sky[6 + c];
+                kb[9 + c] = sky[9 + c] - sky[6 + c];
+                kb[13 + c] = sky[13 + c];
+                kb[17 + c] = sky[17 + c];
+                kb[20 + c] = sky[20 + c];
+            }
+            kb[16] = sky[16];
+            const long long nsq[2] = {sky_sharp, sky_shin};         // the two counts are int64 words: scalar loop counters
+            std::memcpy(&kb[12], &nsq[0], sizeof(double));
+            std::memcpy(&kb[23], &nsq[1], sizeof(double));
+        }
         RT_HIP(ctx, hipSetDevice(ctx->device));
         const size_t bytes = rec.size() * sizeof(double);
         // the next buffer of the ring: launches in flight keep reading the buffers they were queued with.  Whatever
@@ -1226,6 +1292,8 @@ static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *ligh
     ctx->tex_off = (long long)tex_off;
     ctx->lit = lit;
     ctx->lit_off = (long long)lit_off;
+    ctx->sky = has_sky;
+    ctx->sky_off = (long long)sky_off;
     ctx->have_scene = true;
     ctx->epoch++;
     ctx->scene_epoch++;

@@ -136,6 +136,8 @@ struct KParams {
             const float *texels;   // 16 B per entry: {R,G,B, texture id or -1} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels
             // LIT kernels (rt_set_scene_lighting with a coloured light or a specular row; they are TEX kernels too):
             long long lit;     // offset (doubles) in `scene` of the lighting block (lit_doubles)
+            // SKY kernels (rt_set_scene_sky with a sky that is not black; they are LIT kernels too):
+            long long sky;     // offset (doubles) in `scene` of the sky block (SKY_DOUBLES)
         } lens;
     };
 };
@@ -328,16 +330,19 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // texel chosen at the hit point (texel_of).  They are appended: tools/isa_compare.py matches kernels by the family's number.
 // LIT_*: the lighting twins of the four TEX families (rt_set_scene_lighting with a light that is not (1, 1, 1) or a row with
 // spec > 0): every light has a colour and a hit a Blinn-Phong highlight (trace_bounce).  Appended too, for the same reason.
+// SKY_*: the sky twins of the four LIT families (rt_set_scene_sky with a sky that is not black): a trace that finds nothing
+// returns sky_color(d) in place of (0, 0, 0) (trace_bounce).  Appended too, for the same reason.
 enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT, TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT,
-                    LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT };
-constexpr int FAMILIES = 15;
+                    LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT, SKY_SCAT, SKY_SOFT, SKY_LENS, SKY_LENS_SOFT };
+constexpr int FAMILIES = 19;
 __host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
 __host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
 __host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
-__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT || f == Family::LIT_SOFT || f == Family::LIT_LENS_SOFT; }
-__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT || f == Family::LIT_LENS || f == Family::LIT_LENS_SOFT; }
+__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT || f == Family::LIT_SOFT || f == Family::LIT_LENS_SOFT || f == Family::SKY_SOFT || f == Family::SKY_LENS_SOFT; }
+__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT || f == Family::LIT_LENS || f == Family::LIT_LENS_SOFT || f == Family::SKY_LENS || f == Family::SKY_LENS_SOFT; }
 __host__ __device__ constexpr bool has_tex(Family f) { return f >= Family::TEX_SCAT; }
 __host__ __device__ constexpr bool has_lit(Family f) { return f >= Family::LIT_SCAT; }
+__host__ __device__ constexpr bool has_sky(Family f) { return f >= Family::SKY_SCAT; }
 __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
 
 // Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
@@ -363,8 +368,10 @@ __host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 
 // LDS: texture records, ids and texels are read from global memory where a hit needs them (texel_of).
 // LIT (lighting kernels, rt_set_scene_lighting; TEX too): no slot and no LDS either: the lights' colours and the hit's spec / n
 // and log2(shin) are read from the scene's lighting block in global memory inside the light loop (trace_bounce, lit_doubles).
+// SKY (sky kernels, rt_set_scene_sky; LIT too): no slot and no LDS: the lanes of a trace that missed read the scene's sky block
+// from global memory through wave-uniform addresses (sky_color, SKY_DOUBLES).
 template <Family F, int WSLOT, bool FRESH> struct MatState {
-    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F), lit = has_lit(F);
+    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F), lit = has_lit(F), sky = has_sky(F);
     static constexpr int COLS = table_cols(F);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
@@ -385,7 +392,7 @@ template <Family F, int WSLOT, bool FRESH> struct MatState {
     }
 };
 template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
-    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false, lit = false;
+    static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false, lit = false, sky = false;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1472,6 +1479,48 @@ __device__ __forceinline__ unsigned texel_of(const KParams &p, int slot, const V
     return ti;
 }
 
+// The sky (rt_set_scene_sky, mi355rt.h): the colour of a trace with direction d that found nothing, float64 without fused
+// multiply-add in the header's order.  k is the scene's sky block (SKY_DOUBLES 8-byte words), which the host lays out for this
+// function:
+//   0..2 up | 3..5 horizon | 6..8 zenith - horizon | 9..11 nadir - horizon | 12 log2(sharp), an int64 | 13..15 sun_dir |
+//   16 sun_cos | 17..19 sun_rgb | 20..22 halo_rgb | 23 log2(halo_shin), an int64
+// (the two differences are float64 subtractions, the same bits wherever they are formed).  The block is read through a pointer
+// to the constant address space: the kernel never writes the scene buffer and the address is made of kernel arguments alone, so
+// every read is an s_load into SGPRs and no VGPR holds a constant of the sky; the two counts are integers so that the squaring
+// loops run on the scalar unit.  Both gradient differences are loaded and the value is selected, not the address.
+constexpr int SKY_DOUBLES = 24;
+typedef __attribute__((address_space(4))) const double sky_f64;
+typedef __attribute__((address_space(4))) const long long sky_i64;
+__device__ __forceinline__ V3 sky_color(const double *block, const V3 &d)
+{
+    sky_f64 *k = (sky_f64 *)(size_t)block;
+    const double h = dot3(d, V3{k[0], k[1], k[2]});
+    const bool below = h < 0.0;
+    const double a = below ? -h : h;
+    double one = 1.0;
+    asm volatile("" : "+s"(one));                             // (a scalar 1.0 made here: see DESIGN.md, Sky)
+    double t = a > 1.0 ? one : a;
+    const int nsharp = (int)((sky_i64 *)k)[12];
+    if (nsharp > 0) {                                                         // (wave-uniform: a scalar branch)
+        double q = 1.0 - t;
+#pragma unroll 1
+        for (int i = 0; i < nsharp; ++i) q = q * q;
+        t = 1.0 - q;
+    }
+    const double zx = k[6], zy = k[7], zz = k[8], nx = k[9], ny = k[10], nz = k[11];
+    V3 g{k[3] + t * (below ? nx : zx), k[4] + t * (below ? ny : zy), k[5] + t * (below ? nz : zz)};
+    const double s = dot3(d, V3{k[13], k[14], k[15]});
+    if (s > 0.0) {
+        double q = s;
+        const int nhalo = (int)((sky_i64 *)k)[23];
+#pragma unroll 1
+        for (int i = 0; i < nhalo; ++i) q = q * q;
+        g = V3{g.x + k[20] * q, g.y + k[21] * q, g.z + k[22] * q};
+    }
+    if (s >= k[16]) g = V3{g.x + k[17], g.y + k[18], g.z + k[19]};
+    return g;
+}
+
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
@@ -1490,6 +1539,12 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
     // (LENS: a primary ray starts on the lens, not at the camera: no anchor for its closest hit.  `anchor` itself still says
     // which trace this is for the shadow rays below.)
     if (alive) closest_hit<MODE>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
+    // SKY: the lanes that entered alive and missed return the sky's colour for their direction instead of (0, 0, 0); they end
+    // as before.  d is still in registers here, parked kernels included (the hit lanes park it below), so it is neither held
+    // longer nor read back; the branch is skipped when no lane of the wave missed (s_cbranch_execz).
+    if constexpr (MS::sky) {
+        if (alive && type == HIT_NONE) rgb = sky_color(p.scene + (size_t)p.lens.sky, d);
+    }
     alive = alive && (type != HIT_NONE);                                      // :56-57
     cnt.hit(alive);
     if (alive) {
@@ -1721,7 +1776,7 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #endif
         trace_bounce<PARK, WGT, COUNT, MODE, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
-        else {                                                                // :131 (a missed bounce adds pow*0)
+        else {                                                                // :131 (a missed bounce adds pow*0; SKY: W * sky(d))
             double wgt;
             if constexpr (MS::mat) wgt = *ms.template at<WGT, MS::W>(lds.acc, lds.wave); else wgt = p.refl_pow[b - 1];
             const V3 a = acc.get();

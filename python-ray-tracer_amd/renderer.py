@@ -120,7 +120,7 @@ class Renderer:
 
     # -- inputs -----------------------------------------------------------------------------
     def set_scene(self, spheres, lights, planes, flags=0, materials=None, light_radius=None, shadow_samples=1, textures=None,
-                  light_rgb=None):
+                  light_rgb=None, sky=None):
         """float32 (7,S), (3,L), (9,P) as Scene.generate_scene() returns them (scene/scene.py:96-97).
         materials: None (launches shade with their amb, lamb, refl) or (table float64 (M,3) rows amb, lamb, refl,
         sphere_ids int32 (S,), plane_ids int32 (P,)) as Scene.generate_materials() returns them — per-object shading;
@@ -137,7 +137,9 @@ class Renderer:
         light_rgb: None (every light white, (1, 1, 1)), or float32 (L,3) colours times strengths as Scene.get_light_colors()
         returns them.  A table of shape (M,8), rows amb, lamb, refl, trans, ior, rough, spec, shin, gives materials a
         Blinn-Phong highlight of strength spec (colour units) and exponent shin (1, 2, 4, ..., 1024).  Either goes through
-        rt_set_scene_lighting and needs a material table."""
+        rt_set_scene_lighting and needs a material table.
+        sky: None (a ray that hits nothing is black), or a scene.Sky or its 24 packed float64 as Scene.get_sky() returns them:
+        such a ray sees the sky's gradient, sun disc and halo (rt_set_scene_sky).  A sky needs a material table."""
         s, l, p = _f32(spheres, 7, "spheres"), _f32(lights, 3, "lights"), _f32(planes, 9, "planes")
         fp = C.POINTER(C.c_float)
         rad = None
@@ -159,6 +161,13 @@ class Renderer:
                 raise ValueError(f"light_rgb: {rgb.shape[0]} colours for {l.shape[1]} lights")
             if materials is None:
                 raise ValueError("light colours need a material table: pass materials=...")
+        sk = None
+        if sky is not None:
+            sk = np.ascontiguousarray(sky.pack() if hasattr(sky, "pack") else sky, dtype=np.float64).reshape(-1)
+            if sk.shape[0] != L.RT_SKY_DOUBLES:
+                raise ValueError(f"sky: {sk.shape[0]} doubles, a packed sky has {L.RT_SKY_DOUBLES}")
+            if materials is None:
+                raise ValueError("a sky needs a material table: pass materials=...")
         if materials is None:
             self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
                                                p.ctypes.data_as(fp), p.shape[1], int(flags)))
@@ -173,7 +182,7 @@ class Renderer:
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
             ip = C.POINTER(C.c_int32)
-            if textures is not None or rgb is not None or ncols == 8:
+            if textures is not None or rgb is not None or ncols == 8 or sk is not None:
                 records, tsid, tpid, texels = textures if textures is not None else (
                     [], np.full(s.shape[1], -1, np.int32), np.full(p.shape[1], -1, np.int32), np.zeros((0, 3), np.float32))
                 T = len(records)
@@ -197,7 +206,10 @@ class Renderer:
                         p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
                         si.ctypes.data_as(ip), pi.ctypes.data_as(ip), zr.ctypes.data_as(fp), int(shadow_samples),
                         recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip), tx.ctypes.data_as(fp), tx.shape[0])
-                if rgb is not None or ncols == 8:
+                if sk is not None:
+                    self._check(self._lib.rt_set_scene_sky(*args, rgb.ctypes.data_as(fp) if rgb is not None else None,
+                                                           sk.ctypes.data_as(C.POINTER(C.c_double))))
+                elif rgb is not None or ncols == 8:
                     self._check(self._lib.rt_set_scene_lighting(*args, rgb.ctypes.data_as(fp) if rgb is not None else None))
                 else:
                     self._check(self._lib.rt_set_scene_textures(*args))

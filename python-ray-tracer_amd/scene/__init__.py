@@ -4,5 +4,6 @@ pinned byte-for-byte by tests/golden/host_helpers.npz."""
 from .scene import Scene, Light, Plane, Sphere, Material  # noqa: F401
 from .texture import Texture, texel_index  # noqa: F401
 from .lighting import light_terms  # noqa: F401
+from .sky import Sky, sky_color  # noqa: F401
 from .rotation import euler_rotation  # noqa: F401
 from .camera import Camera, PixelGrid  # noqa: F401

@@ -146,8 +146,9 @@ def _columns(items, rows):
 
 
 class Scene:
-    def __init__(self, lights: List[Light], spheres: List[Sphere], planes: List[Plane]):
+    def __init__(self, lights: List[Light], spheres: List[Sphere], planes: List[Plane], sky=None):
         self.lights, self.spheres, self.planes = lights, spheres, planes
+        self.sky = sky                                  # a scene.sky.Sky, or None: a ray that hits nothing is black
 
     def get_spheres(self):
         return _columns(self.spheres, Sphere.data_length)
@@ -165,6 +166,10 @@ class Scene:
     def get_light_colors(self):
         """float32 (L, 3): the lights' colours times strengths, for Renderer.set_scene(..., light_rgb=...)."""
         return np.array([li.rgb() for li in self.lights], dtype=np.float32).reshape(-1, 3)
+
+    def get_sky(self):
+        """float64 (24,), the packed sky for Renderer.set_scene(..., sky=...), or None for a scene without one."""
+        return None if self.sky is None else self.sky.pack()
 
     def generate_scene(self):
         return self.get_spheres(), self.get_lights(), self.get_planes()

@@ -175,3 +175,17 @@ def live(orc, sc, u8=None):
         o8 = oracle_frame(orc, strip(sc, what))[0]
         out[what] = int((o8 != u8).any(axis=0).sum())
     return out
+
+
+def bench_sky(way="full"):
+    """The packed sky (rt_set_scene_sky, 24 float64) of tools/sky_bench.py: "full", a blue gradient with a low sun and its halo
+    in front of the camera, or "unreachable", a black gradient and halo whose sun no ray can see (sun_cos = 2), which makes a scene
+    run the sky kernels and leaves its bytes alone."""
+    from python_ray_tracer_amd.scene import Sky
+    k = Sky(zenith=(25, 70, 190), horizon=(190, 215, 240), nadir=(70, 65, 60), sharpness=2, sun_direction=(1.0, 0.25, 0.12),
+            sun_angle_deg=2.5, sun_color=(255, 240, 200), halo_color=(130, 100, 50), halo_shininess=64).pack()
+    if way == "unreachable":
+        k[3:12] = 0.0
+        k[20:23] = 0.0
+        k[16] = 2.0
+    return k

@@ -64,7 +64,8 @@ def lit_trace(o, d, spheres, Qs, planes, amb, lamb_n, eQ, spec, spec_n, shin, gl
     trace, common = _W["mods"][1], _W["mods"][2]
     t, idx, typ = trace.get_intersection(o, d, spheres, planes)                 # :53
     if typ == 404:
-        return MISS
+        # (tools/gen_sky_golden.py: under a sky a trace that finds nothing returns the sky's colour with the same sentinels)
+        return MISS if _W.get("miss") is None else (_W["miss"](d), MISS[1], MISS[2])
     P = common.linear_comb(o, d, 1.0, t)                                        # :60
     if typ == 0:
         col = common.get_sphere_color(idx, spheres)
@@ -142,6 +143,7 @@ def _sample(o, d, spheres, lights, radius, n, planes, table, sid, pid, depth, ke
                 cont = _W["scatter"](res[2], N, common.linear_comb(P, N, 1.0, BIAS), m[5], key, b, common)
         return res, m, cont
 
+    _W["ray"] = "primary"                           # what the next trace's ray is (read by the miss hook of gen_sky_golden.py)
     (RGB, POINT, RD), m, cont = run(o, d, 0)
     W = None
     dead = False
@@ -156,6 +158,7 @@ def _sample(o, d, spheres, lights, radius, n, planes, table, sid, pid, depth, ke
             if fallback is not None and not keep:
                 dead = True
                 continue
+        _W["ray"] = "reflected" if cont is None else ("refracted" if cont[2] is None else "scattered")
         (RGB_refl, POINT, RD), m, cont = run(POINT, RD, i + 1)
         RGB = common.linear_comb(RGB, RGB_refl, 1.0, W)
     return RGB

@@ -16,7 +16,8 @@ families with one with fewer.  Kernels of the working tree that the base does no
 --twins also prints each MAT kernel next to its PLAIN twin, each REFR kernel next to its MAT twin, each SCAT kernel next to its
 REFR twin, each SOFT kernel next to its SCAT twin, each LENS and LENS_SOFT kernel next to its SCAT and SOFT twin, and each
 texture kernel (TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT) next to its SCAT, SOFT, LENS and LENS_SOFT twin, and each lighting
-kernel (LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT) next to its texture twin.  Exit status 1 if any kernel differs.
+kernel (LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT) next to its texture twin, and each sky kernel (SKY_SCAT, SKY_SOFT, SKY_LENS,
+SKY_LENS_SOFT) next to its lighting twin.  Exit status 1 if any kernel differs.
 """
 import argparse
 import os
@@ -37,17 +38,21 @@ def build(tree):
 
 
 FAMILIES = ("", "mat", "refr", "scat", "soft", "lens", "lens_soft",    # rt::Family in enum order; "" is PLAIN
-            "tex_scat", "tex_soft", "tex_lens", "tex_lens_soft", "lit_scat", "lit_soft", "lit_lens", "lit_lens_soft")
+            "tex_scat", "tex_soft", "tex_lens", "tex_lens_soft", "lit_scat", "lit_soft", "lit_lens", "lit_lens_soft",
+            "sky_scat", "sky_soft", "sky_lens", "sky_lens_soft")
 # --twins: (family, its twin, the family's title), and how a twin is called in the heading ("" is PLAIN: "default")
 TWINS = (("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"), ("scat", "refr", "scatter kernel"),
          ("soft", "scat", "area-light kernel"), ("lens", "scat", "lens kernel"), ("lens_soft", "soft", "lens area-light kernel"),
          ("tex_scat", "scat", "texture kernel"), ("tex_soft", "soft", "texture area-light kernel"),
          ("tex_lens", "lens", "texture lens kernel"), ("tex_lens_soft", "lens_soft", "texture lens area-light kernel"),
          ("lit_scat", "tex_scat", "lighting kernel"), ("lit_soft", "tex_soft", "lighting area-light kernel"),
-         ("lit_lens", "tex_lens", "lighting lens kernel"), ("lit_lens_soft", "tex_lens_soft", "lighting lens area-light kernel"))
+         ("lit_lens", "tex_lens", "lighting lens kernel"), ("lit_lens_soft", "tex_lens_soft", "lighting lens area-light kernel"),
+         ("sky_scat", "lit_scat", "sky kernel"), ("sky_soft", "lit_soft", "sky area-light kernel"),
+         ("sky_lens", "lit_lens", "sky lens kernel"), ("sky_lens_soft", "lit_lens_soft", "sky lens area-light kernel"))
 TWIN_NAMES = {"": "default", "mat": "material", "refr": "refraction", "scat": "scatter", "soft": "area-light", "lens": "lens",
               "lens_soft": "lens area-light", "tex_scat": "texture", "tex_soft": "texture area-light", "tex_lens": "texture lens",
-              "tex_lens_soft": "texture lens area-light"}
+              "tex_lens_soft": "texture lens area-light", "lit_scat": "lighting", "lit_soft": "lighting area-light",
+              "lit_lens": "lighting lens", "lit_lens_soft": "lighting lens area-light"}
 
 
 def key(name):
@@ -126,9 +131,9 @@ def main():
         print(f"NEW   {key(n)[0]} {key(n)[1]}")
     print(f"{len(bf)} kernels of {a.base} compared, {bad} differ; {len(new)} new")
     if a.twins:
-        cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
+        cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "LDS Size [bytes/block]")
         for fam, twin, title in TWINS:
-            print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy   {TWIN_NAMES[twin]} twin")
+            print(f"\n{title} (AA, PARK, WPW, COUNT, LAT, MODE)  VGPRs SGPRs scratch occupancy spill LDS   {TWIN_NAMES[twin]} twin")
             for (k, f_), n in sorted(new_by_key.items(), key=str):
                 if f_ != fam:
                     continue
