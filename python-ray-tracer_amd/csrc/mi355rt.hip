@@ -4,6 +4,7 @@
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_geometry.h"
+#include "rt_scene.h"
 
 #include <cmath>
 #include <cstdio>
@@ -11,10 +12,8 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
-#include <numeric>
 #include <new>
 #include <string>
-#include <functional>
 #include <utility>
 #include <vector>
 
@@ -74,29 +73,15 @@ struct rt_ctx {
     std::vector<hipStream_t> scene_readers[RT_SCENE_RING];
     int scene_cur = 0;
     Buf pixel_loc, u8, f32;
-    int S = 0, P = 0, L = 0;
-    int NC = 0;                   // sphere clusters (0 = flat scene)
-    int M = 0;                    // materials of the current scene (rt_set_scene_materials; 0 = the launch's shading scalars)
-    int mat_cols = 3;             // doubles per row of its table: 6 with a rough row (the scatter kernels), else 5 with a
-                                  // transparent row (the refraction kernels), else 3
-    int soft_n = 0;               // shadow samples per light of a scene with a light radius > 0 (the area-light kernels), else 0
-    long long lens_mat = 0;       // offset (doubles) in the scene buffer of its material block with rows of 6 (the lens kernels')
-    int T = 0;                    // texture records of a scene with a textured object (the texture kernels), else 0
-    long long tex_off = 0;        // offset (doubles) in the scene buffer of its texture block (rt::tex_doubles)
-    bool lit = false;             // the scene runs the lighting kernels (a light colour that is not (1, 1, 1), or a row with spec > 0)
-    long long lit_off = 0;        // offset (doubles) in the scene buffer of its lighting block (rt::lit_doubles)
-    bool sky = false;             // the scene runs the sky kernels (rt_set_scene_sky with a colour that is not zero); lit is set too
-    long long sky_off = 0;        // offset (doubles) in the scene buffer of its sky block (rt::SKY_DOUBLES)
+    rt::SceneLayout lay;          // the current scene (rt_scene.h): counts, families' flags, block offsets, plane codes, extent
     Buf texels[RT_SCENE_RING];    // per scene buffer of the ring: {R,G,B, texture id} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels;
                                   // allocated by the first textured (or lit) scene that lands in the slot, grown when one needs more
     double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
-    double scene_extent2 = 0.0;   // max squared distance of lights / sphere surfaces from the world origin
     bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
     double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
     int w = 0, h = 0;
     double px = 0, y0 = 0, dy = 0, z0 = 0, dz = 0;
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
-    unsigned plane_codes = 0;         // axis codes of planes 0..3 (rt_device.h: KParams::plane_codes)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback: a MEASURING launch stores its tile blocks' costs; a small kernel behind it (same stream) turns
     // them into a dispatch order (rt::order_kernel).  The order lives in two buffers: launches dispatch in order[cur]
@@ -181,24 +166,6 @@ int ensure(rt_ctx *ctx, Buf &b, size_t bytes)
     return RT_OK;
 }
 
-// common.py:104-110 on float32 inputs (float32 squares/sum, sqrt of that sum rounded to float32,
-// float32 divisions) — the shading normal of a plane, hoisted to scene-upload time.
-void plane_normal_f32(const float n[3], float out[3])
-{
-    const float s = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-    const float norm = (float)std::sqrt((double)s);
-    out[0] = n[0] / norm; out[1] = n[1] / norm; out[2] = n[2] / norm;
-}
-
-// M rows of `cols` columns of a material table into dst, from a table of `ncols` columns: its first columns, and where it has
-// fewer, trans 0, ior 1 and rough 0.
-void put_rows(double *dst, int cols, const double *src, int ncols, int M)
-{
-    static const double pad[6] = {0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-    for (int m = 0; m < M; ++m)
-        for (int i = 0; i < cols; ++i) dst[(size_t)cols * m + i] = i < ncols ? src[(size_t)ncols * m + i] : pad[i];
-}
-
 int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
 {
     if (!p) return fail(ctx, RT_ERR_BAD_ARG, "params is NULL");
@@ -213,27 +180,29 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
         if (ctx->explicit_grid) return fail(ctx, RT_ERR_STATE, "RT_AA_STOCHASTIC needs the closed-form ray grid (rt_set_raygen)");
     }
     if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
-    if (ctx->M > 0 && (p->flags & RT_FLAG_COUNT_RAYS))
+    if (ctx->lay.M > 0 && (p->flags & RT_FLAG_COUNT_RAYS))
         return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_COUNT_RAYS is not available for a scene with materials");
-    if (ctx->lens_a > 0.0 && ctx->M == 0)
+    if (ctx->lens_a > 0.0 && ctx->lay.M == 0)
         return fail(ctx, RT_ERR_STATE, "a lens with aperture > 0 needs a scene with a material table (M >= 1)");
     return RT_OK;
 }
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
-// have.  From the scene (M materials in a table of mat_cols columns, soft_n shadow samples per light) and the lens aperture.
-rt::Family family_of(int M, int mat_cols, int soft_n, double lens_a, int T = 0, bool lit = false, bool sky = false)
+// have.  From the scene (rt::SceneLayout: M materials in a table of mat_cols columns, soft_n shadow samples per light, ...) and the
+// lens aperture.
+rt::Family family_of(const rt::SceneLayout &s, double lens_a)
 {
     using F = rt::Family;
-    if (M <= 0) return F::PLAIN;
-    if (sky)                                                         // (set_scene: a sky only with M >= 1; it sets lit too)
-        return lens_a > 0.0 ? (soft_n > 0 ? F::SKY_LENS_SOFT : F::SKY_LENS) : (soft_n > 0 ? F::SKY_SOFT : F::SKY_SCAT);
-    if (lit)                                                         // (set_scene: lit only with M >= 1; textured or not)
-        return lens_a > 0.0 ? (soft_n > 0 ? F::LIT_LENS_SOFT : F::LIT_LENS) : (soft_n > 0 ? F::LIT_SOFT : F::LIT_SCAT);
-    if (T > 0)                                                       // (set_scene: T > 0 only with a textured object, and M >= 1)
-        return lens_a > 0.0 ? (soft_n > 0 ? F::TEX_LENS_SOFT : F::TEX_LENS) : (soft_n > 0 ? F::TEX_SOFT : F::TEX_SCAT);
-    if (lens_a > 0.0) return soft_n > 0 ? F::LENS_SOFT : F::LENS;    // (check_params: a lens needs a material table)
-    return soft_n > 0 ? F::SOFT : mat_cols == 6 ? F::SCAT : mat_cols == 5 ? F::REFR : F::MAT;
+    const bool lens = lens_a > 0.0, soft = s.soft_n > 0;
+    if (s.M <= 0) return F::PLAIN;
+    if (s.sky)                                                       // (rt_scene.h: a sky only with M >= 1; it sets lit too)
+        return lens ? (soft ? F::SKY_LENS_SOFT : F::SKY_LENS) : (soft ? F::SKY_SOFT : F::SKY_SCAT);
+    if (s.lit)                                                       // (rt_scene.h: lit only with M >= 1; textured or not)
+        return lens ? (soft ? F::LIT_LENS_SOFT : F::LIT_LENS) : (soft ? F::LIT_SOFT : F::LIT_SCAT);
+    if (s.T > 0)                                                     // (rt_scene.h: T > 0 only with a textured object, and M >= 1)
+        return lens ? (soft ? F::TEX_LENS_SOFT : F::TEX_LENS) : (soft ? F::TEX_SOFT : F::TEX_SCAT);
+    if (lens) return soft ? F::LENS_SOFT : F::LENS;                  // (check_params: a lens needs a material table)
+    return rt::block_family(s.M, s.mat_cols, soft);                  // SOFT, SCAT, REFR or MAT: the family of the scene's own material block
 }
 
 // The shape of a launch (dispatch()): render_kernel's first six template arguments.
@@ -376,7 +345,7 @@ int acquire_tables(rt_ctx *ctx, const rt::KParams &k, hipStream_t stream, const 
     return RT_OK;
 }
 
-int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride);
+int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride);
 
 // The lattice buffer of a stream (RT_AA_REFERENCE with the closed-form grid renders the half-pixel lattice once into
 // float64 samples, then sums nine of them per pixel): one buffer per launching stream, so that frames in flight on
@@ -415,7 +384,7 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     k.tile_cycles = ctx->tile_stats;
     k.plane_stride = plane_stride;
     k.w = ctx->w; k.h = ctx->h; k.x0 = x0; k.x1 = x1;
-    k.S = ctx->S; k.P = ctx->P; k.L = ctx->L; k.depth = p->depth; k.NC = ctx->NC; k.plane_codes = ctx->plane_codes;
+    k.S = ctx->lay.S; k.P = ctx->lay.P; k.L = ctx->lay.L; k.depth = p->depth; k.NC = ctx->lay.NC; k.plane_codes = ctx->lay.plane_codes;
     k.aa = p->aa_mode; k.u8_rgb = (p->flags & RT_FLAG_U8_RGB) ? 1 : 0; k.u8_hwc = (p->flags & RT_FLAG_U8_HWC) ? 1 : 0;
     k.spp = p->spp; k.seed = p->seed;
     k.lanes_primary = ctx->lanes_primary;
@@ -428,23 +397,23 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const rt::Family lfam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit, ctx->sky);
+    const rt::Family lfam = family_of(ctx->lay, ctx->lens_a);
     const bool lens = rt::has_lens(lfam);
-    if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lens_mat; }
+    if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lay.lens_mat; }
     // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
     // scene buffer that is current now travel in its place
-    if (rt::has_tex(lfam)) { k.lens.mat = ctx->lens_mat; k.lens.tex = ctx->tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
-    if (rt::has_lit(lfam)) k.lens.lit = ctx->lit_off;                // (the lighting kernels are texture kernels: the above too)
-    if (rt::has_sky(lfam)) k.lens.sky = ctx->sky_off;                // (and the sky kernels lighting kernels)
+    if (rt::has_tex(lfam)) { k.lens.mat = ctx->lay.lens_mat; k.lens.tex = ctx->lay.tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
+    if (rt::has_lit(lfam)) k.lens.lit = ctx->lay.lit_off;                // (the lighting kernels are texture kernels: the above too)
+    if (rt::has_sky(lfam)) k.lens.sky = ctx->lay.sky_off;                // (and the sky kernels lighting kernels)
 
     // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
-    const size_t table = (size_t)(ctx->L + 1) * (rt::padS(ctx->S, ctx->NC) + rt::pad4(ctx->NC)) * rt::CULL_STRIDE * sizeof(float);
-    k.anchors = (table <= (size_t)rt::MAX_CULL_TABLE_BYTES) ? ctx->L + 1 : 0;
+    const size_t table = (size_t)(ctx->lay.L + 1) * (rt::padS(ctx->lay.S, ctx->lay.NC) + rt::pad4(ctx->lay.NC)) * rt::CULL_STRIDE * sizeof(float);
+    k.anchors = (table <= (size_t)rt::MAX_CULL_TABLE_BYTES) ? ctx->lay.L + 1 : 0;
     double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
     if (lens) { const double e = std::sqrt(cam2) + ctx->lens_a; cam2 = e * e; }   // (primary rays start on the lens, |L - cam| <= a)
-    k.extent2 = (float)(1.0001 * (cam2 > ctx->scene_extent2 ? cam2 : ctx->scene_extent2));
+    k.extent2 = (float)(1.0001 * (cam2 > ctx->lay.extent2 ? cam2 : ctx->lay.extent2));
     {   // every ray origin of the launch lies within |cam| (+ a with a lens) + 999 (depth + 1) of the world origin
-        const double reach = std::sqrt(cam2) + 999.0 * (p->depth + 1) + std::sqrt(ctx->scene_extent2);
+        const double reach = std::sqrt(cam2) + 999.0 * (p->depth + 1) + std::sqrt(ctx->lay.extent2);
         k.floor_anch = (float)(0x1p-39 * reach * reach);
     }
     {
@@ -473,7 +442,7 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
         k.out_f64 = lat; k.lat_x0 = (int)li0; k.lat_h = (int)LH;
         const long long npx = (long long)(x1 - x0) * ctx->h;
         for (int f = 0; f < nframes; ++f) {                    // the stream's one lattice buffer serves the frames in turn
-            rc = dispatch(ctx, p, kl, true, stream, 1, 0);
+            rc = dispatch(ctx, p, kl, lfam, true, stream, 1, 0);
             if (rc != RT_OK) return rc;
             rt::KParams kf = k;
             if (kf.out_u8) kf.out_u8 += (size_t)f * frame_stride;
@@ -483,12 +452,12 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
         }
         return RT_OK;
     }
-    return dispatch(ctx, p, k, false, stream, nframes, frame_stride);
+    return dispatch(ctx, p, k, lfam, false, stream, nframes, frame_stride);
 }
 
 // Chooses the kernel instantiation and the dispatch order for one launch of the render kernel over the tiles k
 // describes, and launches it.
-int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride)
+int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride)
 {
     const int x0 = k.x0, x1 = k.x1;
     // Workgroup size: 2 tiles (wavefronts) for scenes whose LDS image (records + cull tables) is small, 4 otherwise
@@ -498,7 +467,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // The kernel is the family's of the launch's shape (kernel_of).
     const bool aa = k.aa != 0;
     const bool count = (p->flags & RT_FLAG_COUNT_RAYS) != 0;
-    const size_t image = rt::lds_doubles(ctx->S, ctx->P, ctx->L) * sizeof(double) + rt::table_floats(ctx->S, ctx->NC, k.anchors) * sizeof(float);
+    const size_t image = rt::lds_doubles(ctx->lay.S, ctx->lay.P, ctx->lay.L) * sizeof(double) + rt::table_floats(ctx->lay.S, ctx->lay.NC, k.anchors) * sizeof(float);
     // Scenes with more than rt::CLUSTER_MIN spheres are clustered (rt_set_scene) and culled cluster by cluster; from 161
     // spheres on with the lane-owned traversal and its groups of clusters (rt_device.h, MODE 2; compiled for 128 VGPRs,
     // 4 waves/SIMD).  Measured against the plain wave-uniform cull of the same clusters
@@ -506,8 +475,8 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // but 144 +6 %, 100 +17 %.
     // (Round 2's bundle pre-cull, MODE 1/3, lost against these clusters at every measured size and was removed in round 3:
     // profiles/r02_variant_thresholds.txt.)
-    const bool lanes = ctx->NC > 0 && ctx->S >= ctx->lanes_min_spheres && !count && !(p->flags & RT_FLAG_NO_BUNDLES);
-    const int wpw = (image <= ctx->wpw2_max_image && !count && ctx->NC == 0) ? 2 : 4;   // flat scenes only (up to rt::CLUSTER_MIN spheres); measured at 1080p, depth 3 on flat scenes: 2 wins up to 25 spheres (4.1 KB), 4 from 36 (5.4 KB)
+    const bool lanes = ctx->lay.NC > 0 && ctx->lay.S >= ctx->lanes_min_spheres && !count && !(p->flags & RT_FLAG_NO_BUNDLES);
+    const int wpw = (image <= ctx->wpw2_max_image && !count && ctx->lay.NC == 0) ? 2 : 4;   // flat scenes only (up to rt::CLUSTER_MIN spheres); measured at 1080p, depth 3 on flat scenes: 2 wins up to 25 spheres (4.1 KB), 4 from 36 (5.4 KB)
     const int wgt = 64 * wpw;
     const bool ltab = lanes && k.anchors > 0;                     // lane-owned kernels with anchored tables leave the clusters' origin-form spheres out of LDS
     // MODE 1 (wave-uniform cull, four-wave workgroups, no float64 sphere records in LDS: sphere_hot widens the float32 table
@@ -515,20 +484,19 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
     // variant runs 7 per CU if they fit and needs 6, the register variant 5.  Config 4 (64 spheres): 6 -> 7 workgroups, -5 %;
     // 100 spheres: register variant at 5 -> parked at 6, -7 %; where the count stays (36, 49, 144 spheres) it costs 0...2 %
     // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
-    // The feature family (family_of) picks the twins of these variants: their LDS images hold the material block too
-    // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt_ctx::lens_mat), and their parked variants the
+    // The feature family (fam: launch() derives it from the scene and the lens) picks the twins of these variants: their LDS images hold the material block too
+    // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt::SceneLayout::lens_mat), and their parked variants the
     // family's per-thread slots (rt::lds_slots).
-    const rt::Family fam = family_of(ctx->M, ctx->mat_cols, ctx->soft_n, ctx->lens_a, ctx->T, ctx->lit, ctx->sky);
     auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->M);
+        const size_t lp = rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->lay.M);
         if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
-        return (int)std::min<size_t>(5, CU_LDS / rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, nr, fam, ctx->M));
+        return (int)std::min<size_t>(5, CU_LDS / rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, false, wgt, ltab, lanes, nr, fam, ctx->lay.M));
     };
     const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, true, wgt, ltab, lanes, norec, fam, ctx->M);
+    const size_t lds_park = rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, true, wgt, ltab, lanes, norec, fam, ctx->lay.M);
     // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
     const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= CU_LDS && ctx->lanes_park) : lds_park * (PARK_WAVES / wpw) <= CU_LDS);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->S, ctx->P, ctx->L, ctx->NC, k.anchors, aa, false, wgt, ltab, lanes, norec, fam, ctx->M);
+    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, false, wgt, ltab, lanes, norec, fam, ctx->lay.M);
     const void *fn = kernel_of(fam, Shape{aa, park, wpw, count, lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0)});
     if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: missing_kernels_never_park)
     if (ctx->log_kernels)
@@ -564,7 +532,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
                 if (kf.out_f32) kf.out_f32 += dx * k.h;
                 if (kf.out_f64) kf.out_f64 += 3 * dx * k.h;                      // (lattice samples, [column - x0][row][3])
                 if (kf.tile_cycles) kf.tile_cycles += dx / rt::TILE * k.tiles_y;
-                int rc = dispatch(ctx, p, kf, lattice, stream, 1, 0);
+                int rc = dispatch(ctx, p, kf, fam, lattice, stream, 1, 0);
                 if (rc != RT_OK) return rc;
             }
         return RT_OK;
@@ -640,7 +608,7 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
         const int fpd = (int)g.frames_per_dispatch;
         for (int fr = 0; fr < nframes; fr += fpd) {
             rt::KParams kf = frame_of(fr);
-            int rc = dispatch(ctx, p, kf, lattice, stream, std::min(fpd, nframes - fr), frame_stride);
+            int rc = dispatch(ctx, p, kf, fam, lattice, stream, std::min(fpd, nframes - fr), frame_stride);
             if (rc != RT_OK) return rc;
         }
         return RT_OK;
@@ -650,11 +618,11 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, bool lattice, hipS
         // frames singly while the order is being built — wait for the build (a fraction of a millisecond, twice per new
         // geometry) and hand the rest back: at most two single frames before whole batches go out in the settled order
         rt::KParams kf = frame_of(0);
-        int rc = dispatch(ctx, p, kf, lattice, stream, 1, 0);
+        int rc = dispatch(ctx, p, kf, fam, lattice, stream, 1, 0);
         if (rc != RT_OK) return rc;
         if (f.building) RT_HIP(ctx, hipEventSynchronize(f.done));
         rt::KParams kr = frame_of(1);
-        return dispatch(ctx, p, kr, lattice, stream, nframes - 1, frame_stride);
+        return dispatch(ctx, p, kr, fam, lattice, stream, nframes - 1, frame_stride);
     }
     const bool measure = feedback && !settled && !f.building;  // one measurement in flight at a time (one cost buffer)
     if (settled && !same_epoch) f.since++;
@@ -791,15 +759,67 @@ int rt_destroy(rt_ctx *ctx)
 
 const char *rt_last_error(const rt_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+// Every rt_set_scene* entry: pack the scene on the host (rt_scene.h), upload it into the next buffer of the ring, and make its
+// layout the context's.  A scene that fails validation leaves the context as it was.
+static int set_scene(rt_ctx *ctx, const rt::SceneDesc &desc)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    const rt::PackedScene ps = rt::pack_scene(desc, ctx->cluster_min, ctx->lanes_min_spheres);
+    if (ps.status != RT_OK) return fail(ctx, ps.status, ps.error);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = ps.rec.size() * sizeof(double);
+    // the next buffer of the ring: launches in flight keep reading the buffers they were queued with.  Whatever
+    // launched with THIS buffer did so RT_SCENE_RING scene changes ago; its streams are drained before it is rewritten.
+    const int next = (ctx->scene_cur + 1) % RT_SCENE_RING;
+    for (hipStream_t st : ctx->scene_readers[next]) RT_HIP(ctx, hipStreamSynchronize(st));
+    ctx->scene_readers[next].clear();
+    int rc = ensure(ctx, ctx->scene[next], bytes);
+    if (rc != RT_OK) return rc;
+    if (ps.layout.T > 0 || ps.layout.lit) {                 // (the texture and lighting kernels' texel array)
+        rc = ensure(ctx, ctx->texels[next], ps.texels.size() * sizeof(float));
+        if (rc != RT_OK) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(ctx->texels[next].p, ps.texels.data(), ps.texels.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    RT_HIP(ctx, hipMemcpyAsync(ctx->scene[next].p, ps.rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // ps is about to go out of scope; other streams may launch at once
+    ctx->scene_cur = next;
+    ctx->lay = ps.layout;
+    ctx->have_scene = true;
+    ctx->epoch++;
+    ctx->scene_epoch++;
+    return RT_OK;
+}
+
+// What the entries from rt_set_scene_materials on share.
+static rt::SceneDesc scene_desc(const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
+                                const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material)
+{
+    rt::SceneDesc d;
+    d.spheres = spheres; d.S = S; d.lights = lights; d.L = L; d.planes = planes; d.P = P; d.flags = flags;
+    d.materials = materials; d.M = M; d.ncols = ncols; d.sphere_material = sphere_material; d.plane_material = plane_material;
+    return d;
+}
+
+// The entries from rt_set_scene_area_lights on: the radii may be NULL only where there is no light.
+static int set_scene_radii(rt_ctx *ctx, rt::SceneDesc &d, const float *light_radius, int shadow_samples)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (d.L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
+    static const float none = 0.0f;
+    d.light_radius = light_radius ? light_radius : &none;
+    d.shadow_samples = shadow_samples;
+    return set_scene(ctx, d);
+}
+
 int rt_set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags)
 {
-    return rt_set_scene_materials(ctx, spheres, S, lights, L, planes, P, flags, nullptr, 0, nullptr, nullptr);
+    return set_scene(ctx, scene_desc(spheres, S, lights, L, planes, P, flags, nullptr, 0, 3, nullptr, nullptr));
 }
 
 int rt_set_scene_materials(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
                            const double *materials, int M, const int32_t *sphere_material, const int32_t *plane_material)
 {
-    return rt_set_scene_materials_ex(ctx, spheres, S, lights, L, planes, P, flags, materials, M, 3, sphere_material, plane_material);
+    return set_scene(ctx, scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, 3, sphere_material, plane_material));
 }
 
 int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
@@ -807,31 +827,22 @@ int rt_set_scene_materials_ex(rt_ctx *ctx, const float *spheres, int S, const fl
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (ncols != 3 && ncols != 5) return fail(ctx, RT_ERR_BAD_ARG, "ncols must be 3 or 5");
-    return rt_set_scene_materials_scatter(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+    return set_scene(ctx, scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material));
 }
-
-static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
-                     const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
-                     const float *light_radius, int shadow_samples, const rt_texture *textures = nullptr, int T = 0,
-                     const int32_t *sphere_texture = nullptr, const int32_t *plane_texture = nullptr, const float *texels = nullptr,
-                     int64_t n_texels = 0, const float *light_rgb = nullptr, bool lighting = false, const double *sky = nullptr);
 
 int rt_set_scene_materials_scatter(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                                    int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
                                    const int32_t *plane_material)
 {
-    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material, nullptr, 1);
+    return set_scene(ctx, scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material));
 }
 
 int rt_set_scene_area_lights(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
                              int flags, const double *materials, int M, int ncols, const int32_t *sphere_material,
                              const int32_t *plane_material, const float *light_radius, int shadow_samples)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
-    static const float none = 0.0f;
-    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
-                     light_radius ? light_radius : &none, shadow_samples);
+    rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+    return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
 
 int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
@@ -840,11 +851,10 @@ int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float 
                           const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
                           const float *texels, int64_t n_texels)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
-    static const float none = 0.0f;
-    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
-                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels);
+    rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
+    d.texels = texels; d.n_texels = n_texels;
+    return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
 
 int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
@@ -853,12 +863,11 @@ int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float 
                           const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
                           const float *texels, int64_t n_texels, const float *light_rgb)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
-    static const float none = 0.0f;
-    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
-                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels,
-                     light_rgb, true);
+    rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
+    d.texels = texels; d.n_texels = n_texels;
+    d.light_rgb = light_rgb; d.lighting = true;
+    return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
 
 int rt_set_scene_sky(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P,
@@ -867,437 +876,11 @@ int rt_set_scene_sky(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                      const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
                      const float *texels, int64_t n_texels, const float *light_rgb, const double *sky)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (L > 0 && !light_radius) return fail(ctx, RT_ERR_BAD_ARG, "light_radius is NULL with L > 0");
-    static const float none = 0.0f;
-    return set_scene(ctx, spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material,
-                     light_radius ? light_radius : &none, shadow_samples, textures, T, sphere_texture, plane_texture, texels, n_texels,
-                     light_rgb, true, sky);
-}
-
-// Every rt_set_scene* entry.  light_radius: nullptr (no area lights) or the (L,) radii of rt_set_scene_area_lights; textures ...
-// n_texels: the arguments of rt_set_scene_textures (T == 0: none); light_rgb: nullptr or the (L, 3) colours of
-// rt_set_scene_lighting, the one entry (lighting) that takes a table of 8 columns; sky: nullptr or the RT_SKY_DOUBLES of rt_set_scene_sky.
-static int set_scene(rt_ctx *ctx, const float *spheres, int S, const float *lights, int L, const float *planes, int P, int flags,
-                     const double *materials, int M, int ncols, const int32_t *sphere_material, const int32_t *plane_material,
-                     const float *light_radius, int shadow_samples, const rt_texture *textures, int T,
-                     const int32_t *sphere_texture, const int32_t *plane_texture, const float *texels, int64_t n_texels,
-                     const float *light_rgb, bool lighting, const double *sky)
-{
-    if (!ctx) return RT_ERR_BAD_ARG;
-    // the sky: validated here; one whose five colours are all zero is no sky (has_sky stays false: exactly rt_set_scene_lighting),
-    // any other runs the sky kernels, which are lighting kernels (lit is set below)
-    bool has_sky = false;
-    int sky_sharp = 0, sky_shin = 0;                                // log2(sharp), log2(halo_shin)
-    if (sky) {
-        for (int i = 0; i < RT_SKY_DOUBLES; ++i)
-            if (!std::isfinite(sky[i])) return fail(ctx, RT_ERR_BAD_ARG, "sky[" + std::to_string(i) + "] is not finite");
-        for (int i : {3, 4, 5, 6, 7, 8, 9, 10, 11, 17, 18, 19, 20, 21, 22}) {
-            if (sky[i] < 0.0) return fail(ctx, RT_ERR_BAD_ARG, "sky[" + std::to_string(i) + "]: a colour must be >= 0");
-            has_sky = has_sky || sky[i] != 0.0;
-        }
-        for (int v : {0, 13}) {
-            const double n2 = sky[v] * sky[v] + sky[v + 1] * sky[v + 1] + sky[v + 2] * sky[v + 2];
-            if (!(n2 >= 1.0 - 1e-6 && n2 <= 1.0 + 1e-6))
-                return fail(ctx, RT_ERR_BAD_ARG, v == 0 ? "sky: up must be a unit vector" : "sky: sun_dir must be a unit vector");
-        }
-        sky_sharp = sky_shin = -1;
-        for (int i = 0; i <= 4; ++i) if (sky[12] == (double)(1 << i)) sky_sharp = i;
-        for (int i = 0; i <= 10; ++i) if (sky[23] == (double)(1 << i)) sky_shin = i;
-        if (sky_sharp < 0) return fail(ctx, RT_ERR_BAD_ARG, "sky: sharp must be one of 1, 2, 4, 8, 16");
-        if (sky_shin < 0) return fail(ctx, RT_ERR_BAD_ARG, "sky: halo_shin must be one of 1, 2, 4, ..., 1024");
-    }
-    if (ncols != 3 && ncols != 5 && ncols != 6 && !(lighting && ncols == 8))
-        return fail(ctx, RT_ERR_BAD_ARG, lighting ? "ncols must be 3, 5, 6 or 8" : "ncols must be 3, 5 or 6");
-    // lighting: validated here and below (the spec and shin columns); a scene whose lights are all bitwise (1, 1, 1) and whose rows
-    // all have spec 0 is exactly rt_set_scene_textures' (lit stays false), any other runs the lighting kernels
-    bool lit = false;
-    if (light_rgb) {
-        if (L < 0 || L > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
-        static const float one = 1.0f;
-        for (int i = 0; i < 3 * L; ++i) {
-            if (!(std::isfinite(light_rgb[i]) && light_rgb[i] >= 0.0f))
-                return fail(ctx, RT_ERR_BAD_ARG, "light_rgb[" + std::to_string(i / 3) + "] must be finite and >= 0");
-            lit = lit || std::memcmp(&light_rgb[i], &one, sizeof one) != 0;
-        }
-    }
-    std::vector<double> spec_shin;                                  // ncols == 8: {spec, log2(shin)} per row
-    // area lights (light_radius: nullptr from rt_set_scene_materials_scatter): validated here; a scene with every radius 0 is
-    // exactly rt_set_scene_materials_scatter's (soft stays false), one with a radius > 0 runs the area-light kernels
-    bool soft = false;
-    if (light_radius) {
-        if (shadow_samples < 1 || shadow_samples > RT_MAX_SHADOW_SAMPLES)
-            return fail(ctx, RT_ERR_BAD_ARG, "shadow_samples outside 1..RT_MAX_SHADOW_SAMPLES");
-        if (L < 0 || L > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
-        for (int k = 0; k < L; ++k) {
-            if (!(std::isfinite(light_radius[k]) && light_radius[k] >= 0.0f))
-                return fail(ctx, RT_ERR_BAD_ARG, "light_radius[" + std::to_string(k) + "] must be finite and >= 0");
-            soft = soft || light_radius[k] > 0.0f;
-        }
-        if (soft && !(M > 0 && materials))
-            return fail(ctx, RT_ERR_BAD_ARG, "a light radius > 0 needs a material table (M >= 1)");
-    }
-    // a 5- or 6-column table: validated here; it travels with the columns its rows use: all six with a rough row (the scatter
-    // kernels), else the first five with a transparent row (the refraction kernels), else the first three (the material kernels)
-    std::vector<double> packed;
-    int cols = 3;
-    if (ncols >= 5 && M > 0 && M <= RT_MAX_MATERIALS && materials) {
-        bool glass = false, rough = false;
-        for (int m = 0; m < M; ++m) {
-            const double *r = materials + (size_t)ncols * m;
-            for (int i = 0; i < ncols; ++i)
-                if (!std::isfinite(r[i]))
-                    return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + " has a coefficient that is not finite");
-            if (!(r[3] >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": trans must be >= 0");
-            if (!(r[4] > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": ior must be > 0");
-            if (r[3] > 0.0 && r[2] != 0.0)
-                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have refl == 0");
-            if (ncols >= 6) {
-                if (!(r[5] >= 0.0 && r[5] <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": rough must be in [0, 1]");
-                if (r[3] > 0.0 && r[5] > 0.0)
-                    return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": a transparent row must have rough == 0");
-                rough = rough || r[5] > 0.0;
-            }
-            glass = glass || r[3] > 0.0;
-            if (ncols == 8) {
-                if (!(r[6] >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": spec must be >= 0");
-                int lg = -1;
-                for (int i = 0; i <= 10; ++i) if (r[7] == (double)(1 << i)) lg = i;
-                if (lg < 0) return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(m) + ": shin must be one of 1, 2, 4, ..., 1024");
-                lit = lit || r[6] > 0.0;
-            }
-        }
-        cols = rough ? 6 : (glass ? 5 : 3);
-        try {
-            if (ncols == 8) {
-                spec_shin.resize((size_t)2 * M);
-                for (int m = 0; m < M; ++m) {
-                    spec_shin[(size_t)2 * m] = materials[(size_t)8 * m + 6];
-                    spec_shin[(size_t)2 * m + 1] = std::log2(materials[(size_t)8 * m + 7]);   // (exact: a power of two)
-                }
-            }
-            packed.resize((size_t)cols * M);
-        } catch (const std::bad_alloc &) {
-            return fail(ctx, RT_ERR_ALLOC, "out of host memory");
-        }
-        put_rows(packed.data(), cols, materials, ncols, M);
-        materials = packed.data();
-    }
-    // the area-light kernels are scatter kernels: their table travels with all six columns (a 3- or 5-column table padded with
-    // trans 0, ior 1, rough 0), and with lamb / n in place of lamb (the reference's lambert_int of a trace with n points per light)
-    std::vector<double> soft_table;
-    if (soft && M <= RT_MAX_MATERIALS) {
-        try {
-            soft_table.resize((size_t)6 * M);
-        } catch (const std::bad_alloc &) {
-            return fail(ctx, RT_ERR_ALLOC, "out of host memory");
-        }
-        put_rows(soft_table.data(), 6, materials, cols, M);
-        for (int m = 0; m < M; ++m) soft_table[(size_t)6 * m + 1] /= (double)shadow_samples;
-        materials = soft_table.data();
-        cols = 6;
-    }
-    if (S < 0 || S > RT_MAX_SPHERES || L < 0 || L > RT_MAX_LIGHTS || P < 0 || P > RT_MAX_PLANES)
-        return fail(ctx, RT_ERR_BAD_ARG, "scene size outside RT_MAX_SPHERES / RT_MAX_LIGHTS / RT_MAX_PLANES");
-    if ((S && !spheres) || (L && !lights) || (P && !planes)) return fail(ctx, RT_ERR_BAD_ARG, "NULL scene array with non-zero count");
-    if (M < 0 || M > RT_MAX_MATERIALS) return fail(ctx, RT_ERR_BAD_ARG, "material count outside 0..RT_MAX_MATERIALS");
-    if (lit && !(M > 0 && materials)) return fail(ctx, RT_ERR_BAD_ARG, "lighting needs a material table (M >= 1)");
-    if (has_sky && !(M > 0 && materials)) return fail(ctx, RT_ERR_BAD_ARG, "a sky needs a material table (M >= 1)");
-    lit = lit || has_sky;                                           // (white lights and spec 0 where the scene gave none)
-    if (M > 0) {
-        if (!materials) return fail(ctx, RT_ERR_BAD_ARG, "materials is NULL with M > 0");
-        if ((S && !sphere_material) || (P && !plane_material)) return fail(ctx, RT_ERR_BAD_ARG, "NULL material id array with non-zero count");
-        for (int i = 0; i < cols * M; ++i)
-            if (!std::isfinite(materials[i]))
-                return fail(ctx, RT_ERR_BAD_ARG, "material " + std::to_string(i / cols) + " has a coefficient that is not finite");
-        for (int k = 0; k < S; ++k)
-            if (sphere_material[k] < 0 || sphere_material[k] >= M)
-                return fail(ctx, RT_ERR_BAD_ARG, "sphere_material[" + std::to_string(k) + "] outside 0..M-1");
-        for (int k = 0; k < P; ++k)
-            if (plane_material[k] < 0 || plane_material[k] >= M)
-                return fail(ctx, RT_ERR_BAD_ARG, "plane_material[" + std::to_string(k) + "] outside 0..M-1");
-    }
-    // textures: validated here; a scene without a textured object (T == 0, or every id -1) is exactly rt_set_scene_area_lights'
-    // (textured stays false), one with a textured object runs the texture kernels
-    bool textured = false;
-    if (T < 0 || T > RT_MAX_TEXTURES) return fail(ctx, RT_ERR_BAD_ARG, "texture count outside 0..RT_MAX_TEXTURES");
-    if (n_texels < 0 || n_texels > RT_MAX_TEXELS) return fail(ctx, RT_ERR_BAD_ARG, "texel count outside 0..RT_MAX_TEXELS");
-    if (T > 0) {
-        if (!(M > 0)) return fail(ctx, RT_ERR_BAD_ARG, "textures need a material table (M >= 1)");
-        if (!textures) return fail(ctx, RT_ERR_BAD_ARG, "textures is NULL with T > 0");
-        if (!texels) return fail(ctx, RT_ERR_BAD_ARG, "texels is NULL with T > 0");
-        for (int t = 0; t < T; ++t) {
-            const rt_texture &x = textures[t];
-            long long cells = 1;
-            if (x.reserved != 0) return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": reserved must be 0");
-            for (int a = 0; a < 3; ++a) {
-                if (x.dim[a] < 1 || x.dim[a] > RT_MAX_TEXTURE_DIM)
-                    return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": a dimension outside 1..RT_MAX_TEXTURE_DIM");
-                cells *= x.dim[a];
-                if (!std::isfinite(x.origin[a]) || !std::isfinite(x.axis[a][0]) || !std::isfinite(x.axis[a][1]) || !std::isfinite(x.axis[a][2]))
-                    return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": origin or axis not finite");
-            }
-            if (x.first < 0 || x.first > n_texels || cells > n_texels - x.first)
-                return fail(ctx, RT_ERR_BAD_ARG, "texture " + std::to_string(t) + ": texel range outside the texel array");
-        }
-        for (int64_t i = 0; i < 3 * n_texels; ++i)
-            if (!std::isfinite(texels[i])) return fail(ctx, RT_ERR_BAD_ARG, "texel " + std::to_string(i / 3) + " is not finite");
-    }
-    for (int k = 0; k < S && sphere_texture; ++k) {
-        if (sphere_texture[k] < -1 || sphere_texture[k] >= T)
-            return fail(ctx, RT_ERR_BAD_ARG, "sphere_texture[" + std::to_string(k) + "] outside -1..T-1");
-        textured = textured || sphere_texture[k] >= 0;
-    }
-    for (int k = 0; k < P && plane_texture; ++k) {
-        if (plane_texture[k] < -1 || plane_texture[k] >= T)
-            return fail(ctx, RT_ERR_BAD_ARG, "plane_texture[" + std::to_string(k) + "] outside -1..T-1");
-        textured = textured || plane_texture[k] >= 0;
-    }
-    int nclusters = 0;
-    size_t lens_off = 0, tex_off = 0, lit_off = 0, sky_off = 0;
-    try {
-        // Packed float64 records (layout: rt_device.h).  All float32 sub-expressions of the reference
-        // are evaluated here, once, in float32: r*r (intersections.py:21), the plane shading normal
-        // (common.py:104-110) and BIAS*N of a plane hit (trace.py:82-83).
-        // Scenes with more than rt::CLUSTER_MIN spheres are stored in clusters of rt::CLUSTER spatially close
-        // spheres (Morton order of the centres), each with a bounding sphere the kernel culls first.  Slot
-        // order is a permutation of the caller's order; every record keeps the caller's index so that the
-        // reference's tie rule (the lower index wins an exact tie, trace.py:26) is unaffected.
-        std::vector<int> order(S);
-        std::iota(order.begin(), order.end(), 0);
-        int NC = 0;
-        if (S > ctx->cluster_min) {
-            // Recursive median split of the centres along the longest axis of their bounding box, the left part always a
-            // whole number of clusters: every cluster but the last has exactly rt::CLUSTER spheres and is a compact block
-            // of neighbours.  (Until late in round 2: Morton order cut into runs of 8 — first with every axis scaled to its own
-            // span, which sorted a flat layer of spheres by radius; then with one scale; the split is tighter still.)
-            // Ties are broken by the caller's index, so the order is the same on every host.
-            const bool group_aligned = S >= ctx->lanes_min_spheres;
-            std::function<void(int, int)> split = [&](int a, int b) {
-                const int n = b - a;
-                if (n <= rt::CLUSTER) return;
-                double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-                for (int j = a; j < b; ++j)
-                    for (int i = 0; i < 3; ++i) { const double v = spheres[i * S + order[j]]; lo[i] = std::min(lo[i], v); hi[i] = std::max(hi[i], v); }
-                int ax = 0;
-                for (int i = 1; i < 3; ++i) if (hi[i] - lo[i] > hi[ax] - lo[ax]) ax = i;
-                const int nc = (n + rt::CLUSTER - 1) / rt::CLUSTER;
-                // scenes whose kernels test GROUPS of rt::SUPER consecutive clusters first (the lane-owned traversal's): the left
-                // part is a whole number of groups as well, so that every group is a subtree of this split
-                const int left = (group_aligned && nc > rt::SUPER) ? rt::SUPER * ((nc / rt::SUPER + 1) / 2) : (nc + 1) / 2;
-                const int mid = a + left * rt::CLUSTER;
-                auto key = [&](int x) { const float v = spheres[ax * S + x]; return v == v ? v : 3.0e38f; };   // (a NaN sorts last)
-                std::sort(order.begin() + a, order.begin() + b, [&](int x, int y) {
-                    const float vx = key(x), vy = key(y);
-                    return vx < vy || (vx == vy && x < y);
-                });
-                split(a, mid);
-                split(mid, b);
-            };
-            split(0, S);
-            NC = (S + rt::CLUSTER - 1) / rt::CLUSTER;
-        }
-        nclusters = NC;
-        const size_t mat_off = rt::mat_offset(S, P, L, NC);      // (records, cluster records, one spare double)
-        // the lens kernels are scatter kernels: a table of 3 or 5 columns gets a copy padded to six (trans 0, ior 1, rough 0)
-        // behind its block, with the same ids; a 6-column one (an area-light scene's included) serves them as it is
-        const size_t matd = rt::mat_doubles(M, S, P, family_of(M, cols, soft ? shadow_samples : 0, 0.0));
-        lens_off = (M > 0 && cols < 6) ? mat_off + matd : mat_off;
-        // the texture block (rt::tex_doubles) behind everything else
-        tex_off = mat_off + matd + (lens_off != mat_off ? rt::mat_doubles(M, S, P, rt::Family::LENS) : 0);
-        // and the lighting block (rt::lit_doubles) behind that
-        lit_off = tex_off + (textured ? rt::tex_doubles(T) : 0);
-        // and the sky block (rt::SKY_DOUBLES) last
-        sky_off = lit_off + (lit ? rt::lit_doubles(S, P, L) : 0);
-        std::vector<double> rec(sky_off + (has_sky ? rt::SKY_DOUBLES : 0), 0.0);
-        double *sp = rec.data();
-        unsigned codes = 0;
-        for (int slot = 0; slot < S; ++slot, sp += rt::SPH_STRIDE) {
-            const int k = order[slot];
-            sp[7] = (double)k;                                   // the caller's index of this sphere
-            const float r = spheres[3 * S + k];
-            const float r2 = r * r;
-            sp[0] = spheres[0 * S + k]; sp[1] = spheres[1 * S + k]; sp[2] = spheres[2 * S + k]; sp[3] = (double)r2;
-            sp[4] = spheres[4 * S + k]; sp[5] = spheres[5 * S + k]; sp[6] = spheres[6 * S + k];
-        }
-        for (int k = 0; k < P; ++k, sp += rt::PL_STRIDE) {
-            for (int i = 0; i < 6; ++i) sp[i] = planes[i * P + k];
-            const float nraw[3] = {planes[3 * P + k], planes[4 * P + k], planes[5 * P + k]};
-            float nf[3];
-            plane_normal_f32(nraw, nf);
-            const double BIAS = 0.0002;
-            const float bf = (float)BIAS;
-            {   // axis code: the stored normal is exactly +-e_i (intersection shortcut in rt_device.h:plane_den_num)
-                int axis = -1, nonzero = 0;
-                for (int i = 0; i < 3; ++i) if (nraw[i] != 0.0f) { ++nonzero; axis = i; }
-                sp[15] = (nonzero == 1 && (nraw[axis] == 1.0f || nraw[axis] == -1.0f)) ? (double)(axis + 1) * (double)nraw[axis] : 0.0;
-                if (k < 4) codes |= (unsigned)(unsigned char)(signed char)sp[15] << (8 * k);
-            }
-            for (int i = 0; i < 3; ++i) {
-                sp[6 + i] = (double)nf[i];
-                sp[9 + i] = (flags & RT_FLAG_TYPED_BIAS) ? BIAS * (double)nf[i] : (double)(bf * nf[i]);
-                sp[12 + i] = planes[(6 + i) * P + k];
-            }
-        }
-        for (int k = 0; k < L; ++k, sp += rt::LT_STRIDE) {
-            sp[0] = lights[0 * L + k]; sp[1] = lights[1 * L + k]; sp[2] = lights[2 * L + k];
-            if (soft) sp[3] = light_radius[k];                      // (the pad slot: the area-light kernels' radius)
-        }
-        // bounding sphere (float64, inflated) of the spheres in slots [j0, j1): around the centroid of the centres or the centre of
-        // their bounding box, whichever gives the smaller sphere
-        auto bound = [&](int j0, int j1, double *out) {
-            double Cc[2][3] = {{0, 0, 0}, {0, 0, 0}}, blo[3] = {1e300, 1e300, 1e300}, bhi[3] = {-1e300, -1e300, -1e300};
-            for (int j = j0; j < j1; ++j)
-                for (int i = 0; i < 3; ++i) {
-                    const double v = spheres[i * S + order[j]], rr = std::fabs((double)spheres[3 * S + order[j]]);
-                    Cc[0][i] += v; blo[i] = std::min(blo[i], v - rr); bhi[i] = std::max(bhi[i], v + rr);
-                }
-            for (int i = 0; i < 3; ++i) { Cc[0][i] /= (j1 - j0); Cc[1][i] = 0.5 * (blo[i] + bhi[i]); }
-            double C[3] = {0, 0, 0}, R = 1e300;
-            for (int t = 0; t < 2; ++t) {
-                double Rt = 0;
-                for (int j = j0; j < j1; ++j) {
-                    const int k = order[j];
-                    const double dx = spheres[0 * S + k] - Cc[t][0], dy = spheres[1 * S + k] - Cc[t][1], dz = spheres[2 * S + k] - Cc[t][2];
-                    Rt = std::max(Rt, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs((double)spheres[3 * S + k]));
-                }
-                if (Rt < R || t == 0) { R = Rt; for (int i = 0; i < 3; ++i) C[i] = Cc[t][i]; }   // (NaN: keeps the centroid's)
-            }
-            R = R * (1.0 + 1e-6) + 1e-9;
-            out[0] = C[0]; out[1] = C[1]; out[2] = C[2]; out[3] = R * R;
-        };
-        for (int c = 0; c < NC; ++c, sp += rt::CL_STRIDE)                   // clusters of rt::CLUSTER spheres
-            bound(c * rt::CLUSTER, std::min(S, (c + 1) * rt::CLUSTER), sp);
-        for (int g = 0; g < rt::supers(NC); ++g, sp += rt::CL_STRIDE)      // groups of rt::SUPER clusters
-            bound(g * rt::SUPER * rt::CLUSTER, std::min(S, (g + 1) * rt::SUPER * rt::CLUSTER), sp);
-        if (M > 0) {   // the material block (rt::mat_offset): M, the table, the ids of the sphere SLOTS (the order above) and of the planes
-            rec[mat_off] = (double)M;
-            std::memcpy(rec.data() + mat_off + 1, materials, (size_t)cols * M * sizeof(double));
-            std::vector<int32_t> ids((size_t)S + P);
-            for (int slot = 0; slot < S; ++slot) ids[slot] = sphere_material[order[slot]];
-            for (int k = 0; k < P; ++k) ids[(size_t)S + k] = plane_material[k];
-            if (!ids.empty()) std::memcpy(rec.data() + mat_off + 1 + (size_t)cols * M, ids.data(), ids.size() * sizeof(int32_t));
-            if (soft) rec[mat_off + matd - 1] = (double)shadow_samples;   // (rt::mat_doubles: the block's last double)
-            if (lens_off != mat_off) {
-                rec[lens_off] = (double)M;
-                put_rows(rec.data() + lens_off + 1, 6, materials, cols, M);
-                if (!ids.empty()) std::memcpy(rec.data() + lens_off + 1 + (size_t)6 * M, ids.data(), ids.size() * sizeof(int32_t));
-            }
-        }
-        // textures: the records with what texel_of reads (dimensions and their reciprocals as doubles, the first texel's entry of
-        // the texel array); the texel array starts with the S + P slots' own colours (exact: the scene is float32) and texture
-        // ids (-1: none), so that a hit without a texture reads its colour the same way
-        // (a lit scene without a textured object has the array too, every id -1: the lighting kernels are texture kernels)
-        std::vector<float> tx;
-        if (textured || lit) {
-            double *tb = rec.data() + tex_off;
-            if (textured) tb[0] = (double)T;
-            for (int t = 0; t < T && textured; ++t) {
-                double *r = tb + 1 + (size_t)rt::TEX_STRIDE * t;
-                const rt_texture &x = textures[t];
-                for (int a = 0; a < 3; ++a) {
-                    r[a] = x.origin[a];
-                    for (int i = 0; i < 3; ++i) r[3 + 3 * a + i] = x.axis[a][i];
-                    r[12 + a] = (double)x.dim[a];
-                    r[15 + a] = 1.0 / (double)x.dim[a];
-                }
-                r[18] = (double)((long long)S + P + x.first);
-            }
-            tx.assign(4 * ((size_t)S + P + (size_t)(textured ? n_texels : 0)), 0.0f);
-            for (int slot = 0; slot < S; ++slot) {
-                for (int c = 0; c < 3; ++c) tx[4 * (size_t)slot + c] = spheres[(4 + c) * S + order[slot]];
-                tx[4 * (size_t)slot + 3] = (textured && sphere_texture) ? (float)sphere_texture[order[slot]] : -1.0f;
-            }
-            for (int k = 0; k < P; ++k) {
-                for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + k) + c] = planes[(6 + c) * P + k];
-                tx[4 * ((size_t)S + k) + 3] = (textured && plane_texture) ? (float)plane_texture[k] : -1.0f;
-            }
-            for (int64_t i = 0; i < n_texels && textured; ++i)
-                for (int c = 0; c < 3; ++c) tx[4 * ((size_t)S + P + (size_t)i) + c] = texels[3 * i + c];
-        }
-        // lighting: the lights' colours (widened: exact), then per object slot its row's spec / n (n: the shadow samples of an
-        // area-light scene, else 1; a float64 division, as lamb / n) and log2(shin)
-        if (lit) {
-            double *lb = rec.data() + lit_off;
-            for (int k = 0; k < L; ++k)
-                for (int c = 0; c < 3; ++c) lb[(size_t)rt::LT_STRIDE * k + c] = light_rgb ? (double)light_rgb[3 * k + c] : 1.0;
-            double *ob = lb + (size_t)rt::LT_STRIDE * L;
-            const double n = soft ? (double)shadow_samples : 1.0;
-            for (size_t j = 0; j < (size_t)S + P; ++j) {
-                const int m = j < (size_t)S ? sphere_material[order[j]] : plane_material[j - S];
-                ob[2 * j] = spec_shin.empty() ? 0.0 : spec_shin[(size_t)2 * m] / n;
-                ob[2 * j + 1] = spec_shin.empty() ? 0.0 : spec_shin[(size_t)2 * m + 1];
-            }
-        }
-        // the sky, laid out for rt::sky_color: the gradient as the horizon's colour and the two differences from it, the two
-        // exponents as numbers of squarings (int64)
-        if (has_sky) {
-            double *kb = rec.data() + sky_off;
-            for (int c = 0; c < 3; ++c) {
-                kb[c] = sky[c];
-                kb[3 + c] = sky[6 + c];
-                kb[6 + c] = sky[3 + c] - sky[6 + c];
-                kb[9 + c] = sky[9 + c] - sky[6 + c];
-                kb[13 + c] = sky[13 + c];
-                kb[17 + c] = sky[17 + c];
-                kb[20 + c] = sky[20 + c];
-            }
-            kb[16] = sky[16];
-            const long long nsq[2] = {sky_sharp, sky_shin};         // the two counts are int64 words: scalar loop counters
-            std::memcpy(&kb[12], &nsq[0], sizeof(double));
-            std::memcpy(&kb[23], &nsq[1], sizeof(double));
-        }
-        RT_HIP(ctx, hipSetDevice(ctx->device));
-        const size_t bytes = rec.size() * sizeof(double);
-        // the next buffer of the ring: launches in flight keep reading the buffers they were queued with.  Whatever
-        // launched with THIS buffer did so RT_SCENE_RING scene changes ago; its streams are drained before it is rewritten.
-        const int next = (ctx->scene_cur + 1) % RT_SCENE_RING;
-        for (hipStream_t st : ctx->scene_readers[next]) RT_HIP(ctx, hipStreamSynchronize(st));
-        ctx->scene_readers[next].clear();
-        int rc = ensure(ctx, ctx->scene[next], bytes);
-        if (rc != RT_OK) return rc;
-        if (textured || lit) {
-            rc = ensure(ctx, ctx->texels[next], tx.size() * sizeof(float));
-            if (rc != RT_OK) return rc;
-            RT_HIP(ctx, hipMemcpyAsync(ctx->texels[next].p, tx.data(), tx.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        }
-        RT_HIP(ctx, hipMemcpyAsync(ctx->scene[next].p, rec.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // rec is about to go out of scope; other streams may launch at once
-        ctx->scene_cur = next;
-        ctx->plane_codes = codes;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, RT_ERR_ALLOC, "out of host memory");
-    }
-    double ext2 = 0.0;
-    for (int k = 0; k < S; ++k) {
-        const double cx = spheres[0 * S + k], cy = spheres[1 * S + k], cz = spheres[2 * S + k], r = std::fabs((double)spheres[3 * S + k]);
-        const double e = std::sqrt(cx * cx + cy * cy + cz * cz) + r;
-        if (e * e > ext2) ext2 = e * e;
-    }
-    for (int k = 0; k < L; ++k) {
-        const double x = lights[0 * L + k], y = lights[1 * L + k], z = lights[2 * L + k];
-        if (soft) {                                                 // (the light's ball)
-            const double e = std::sqrt(x * x + y * y + z * z) + (double)light_radius[k];
-            if (e * e > ext2) ext2 = e * e;
-        } else
-        if (x * x + y * y + z * z > ext2) ext2 = x * x + y * y + z * z;
-    }
-    ctx->scene_extent2 = ext2;
-    ctx->S = S; ctx->P = P; ctx->L = L; ctx->NC = nclusters;
-    ctx->M = M;
-    ctx->mat_cols = cols;
-    ctx->soft_n = soft ? shadow_samples : 0;
-    ctx->lens_mat = (long long)lens_off;
-    ctx->T = textured ? T : 0;
-    ctx->tex_off = (long long)tex_off;
-    ctx->lit = lit;
-    ctx->lit_off = (long long)lit_off;
-    ctx->sky = has_sky;
-    ctx->sky_off = (long long)sky_off;
-    ctx->have_scene = true;
-    ctx->epoch++;
-    ctx->scene_epoch++;
-    return RT_OK;
+    rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
+    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
+    d.texels = texels; d.n_texels = n_texels;
+    d.light_rgb = light_rgb; d.lighting = true; d.sky = sky;
+    return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
 
 int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9])

@@ -8,7 +8,7 @@
 // How it is organised is not the reference's one-thread-per-pixel translation:
 //   * a 64-lane wavefront owns an 8x8 tile (8 consecutive y per x-row = the contiguous
 //     direction of the (3,w,h) frame); the 2 or 4 waves of a workgroup take tiles consecutive in y;
-//   * the scene (float64-widened sphere/plane/light/material records, packed by the host) and its float32 cull
+//   * the scene (float64-widened sphere/plane/light/material records, packed by the host: rt_scene.h) and its float32 cull
 //     tables (built once per scene/camera by tables_kernel) are copied once per workgroup into LDS and read
 //     with wave-uniform (broadcast) ds_reads;
 //   * every scene query normalises its direction ONCE (the reference re-normalises per sphere,
@@ -31,6 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets: shared with the host's scene packer (rt_scene.h)
 
 #pragma clang fp contract(off)
 
@@ -65,17 +66,6 @@ constexpr int TILE = 8;            // 8x8 pixels per wavefront
 // of the scene and its cull tables, so bigger scenes want bigger workgroups (C4: 4 waves beat 2 by 24 %, C5 by 69 %).
 constexpr int TILE_ORDER_MIN_WPW = 4;   // workgroups of this many waves or more may be dispatched tile by tile (render_kernel, dispatch)
 constexpr int TABLE_THREADS = 256; // tables_kernel's workgroup
-constexpr int SPH_STRIDE = 8;      // doubles per sphere record: cx,cy,cz,r2, R,G,B, caller's index
-constexpr int PL_STRIDE = 16;      // ox,oy,oz,nx,ny,nz, Nx,Ny,Nz, bNx,bNy,bNz, R,G,B, axis code (0 general, +-1/2/3 = +-e_x/y/z)
-constexpr int LT_STRIDE = 4;       // x,y,z,pad
-constexpr int CL_STRIDE = 4;       // cluster bounding sphere: cx,cy,cz,R2 (global memory only; LDS holds the float32 tables)
-constexpr int CLUSTER = 8;         // spheres per cluster
-#ifndef RT_CLUSTER_MIN
-#define RT_CLUSTER_MIN 20   // measured (median-split clusters) against the flat scene: 16 spheres +3 % (the two-wave kernels, flat
-                            // scenes only, are faster there), 25 -7 %, 36 -20 %, 49 -17 %, 64 -13 %
-#endif
-constexpr int CLUSTER_MIN = RT_CLUSTER_MIN;   // scenes with at most this many spheres stay flat
-constexpr int SUPER = 8;           // clusters per group of clusters (one more box each: the lane-owned traversal skips whole groups)
 constexpr int BOX_STRIDE = 8;      // floats per cluster box: lo.xyz, -, hi.xyz, - (two ds_read_b128)
 constexpr int CULL_STRIDE = 4;     // floats per (anchor, sphere) cull entry: Lx,Ly,Lz, tau (one ds_read_b128)
 #ifndef RT_MAX_CULL_TABLE_BYTES
@@ -323,27 +313,6 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
     }
 };
 
-// The feature family of a render kernel (its last template argument).  Each family's kernels are the twins of the family before
-// it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host derives a launch's family from its
-// scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
-// TEX_*: the texture twins of SCAT, SOFT, LENS and LENS_SOFT (rt_set_scene_textures with a textured object): the hit's colour is a
-// texel chosen at the hit point (texel_of).  They are appended: tools/isa_compare.py matches kernels by the family's number.
-// LIT_*: the lighting twins of the four TEX families (rt_set_scene_lighting with a light that is not (1, 1, 1) or a row with
-// spec > 0): every light has a colour and a hit a Blinn-Phong highlight (trace_bounce).  Appended too, for the same reason.
-// SKY_*: the sky twins of the four LIT families (rt_set_scene_sky with a sky that is not black): a trace that finds nothing
-// returns sky_color(d) in place of (0, 0, 0) (trace_bounce).  Appended too, for the same reason.
-enum class Family { PLAIN, MAT, REFR, SCAT, SOFT, LENS, LENS_SOFT, TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT,
-                    LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT, SKY_SCAT, SKY_SOFT, SKY_LENS, SKY_LENS_SOFT };
-constexpr int FAMILIES = 19;
-__host__ __device__ constexpr bool has_mat(Family f) { return f != Family::PLAIN; }
-__host__ __device__ constexpr bool has_refr(Family f) { return f >= Family::REFR; }
-__host__ __device__ constexpr bool has_scat(Family f) { return f >= Family::SCAT; }
-__host__ __device__ constexpr bool has_soft(Family f) { return f == Family::SOFT || f == Family::LENS_SOFT || f == Family::TEX_SOFT || f == Family::TEX_LENS_SOFT || f == Family::LIT_SOFT || f == Family::LIT_LENS_SOFT || f == Family::SKY_SOFT || f == Family::SKY_LENS_SOFT; }
-__host__ __device__ constexpr bool has_lens(Family f) { return f == Family::LENS || f == Family::LENS_SOFT || f == Family::TEX_LENS || f == Family::TEX_LENS_SOFT || f == Family::LIT_LENS || f == Family::LIT_LENS_SOFT || f == Family::SKY_LENS || f == Family::SKY_LENS_SOFT; }
-__host__ __device__ constexpr bool has_tex(Family f) { return f >= Family::TEX_SCAT; }
-__host__ __device__ constexpr bool has_lit(Family f) { return f >= Family::LIT_SCAT; }
-__host__ __device__ constexpr bool has_sky(Family f) { return f >= Family::SKY_SCAT; }
-__host__ __device__ constexpr int table_cols(Family f) { return has_scat(f) ? 6 : (has_refr(f) ? 5 : 3); }   // doubles per material row its kernels read
 
 // Per-object materials (MAT kernels, rt_set_scene_materials): where a sample finds the hit object's coefficients and keeps
 // its running reflection weight W.  An empty struct, and every use a no-op, in the kernels of scenes without materials (PLAIN).
@@ -577,8 +546,6 @@ __device__ __forceinline__ unsigned push_any(unsigned acc, lanemask m)
     asm volatile("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(acc) : "s"(m) : "scc");
     return acc;
 }
-__host__ __device__ inline int pad4(int n) { return (n + 3) & ~3; }
-__host__ __device__ inline int supers(int NC) { return (NC + SUPER - 1) / SUPER; }   // groups of SUPER clusters
 
 // logarithmic cost key for the dispatch-order feedback: monotone in c, < 1024
 __device__ __forceinline__ int order_bucket(unsigned c)
@@ -1446,14 +1413,13 @@ __device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, c
 // Nothing of this is staged in LDS: the images of a family's kernels, and with them every choice the dispatcher makes from
 // their sizes (workgroups per CU, parking), are those of the family's twin.
 // f mod n without an integer division (20 instructions on the vector unit, three times per hit): q = floor(f * rn) with
-// rn = RN(1/n) (the host's division), j = f - n*q, and one correction step into [0, n).  Exact for integral |f| <= 2^30 and
+// rn = RN(1/n) (the host's division, rt_scene.h: texture_block), j = f - n*q, and one correction step into [0, n).  Exact for integral |f| <= 2^30 and
 // 1 <= n <= 4096:  n*q < 2^43 and f - n*q are integers below 2^53, so neither rounds;  f*rn is within 2^-52 |f/n| <= 2^-22 of f/n
 // (rn within 2^-53 relative, one more rounding);  a quotient f/n that is not an integer is at least 1/n >= 2^-12 from the
 // nearest one, so its floor is the true floor and 0 <= j < n;  an integral quotient k may come out as k or k - 1, j as 0 or n:
 // the correction maps n to 0.  (The other direction, j < 0, cannot occur; it is corrected too, for one compare and one add.)
 // An axis with n = 1 needs no case of its own: j = f - floor(f) = 0 whatever g is.
 // tests/test_textures.py replays this against integer arithmetic on dimensions 3, 5, 7 and 4096 and coordinates on exact multiples.
-constexpr int TEX_STRIDE = 20;     // doubles per texture record: origin[3], axis[3][3], n[3], 1/n[3], base, pad
 __host__ __device__ inline double texel_wrap(double g, double n, double rn)
 {
     double f = __builtin_floor(g);
@@ -1480,7 +1446,7 @@ __device__ __forceinline__ unsigned texel_of(const KParams &p, int slot, const V
 }
 
 // The sky (rt_set_scene_sky, mi355rt.h): the colour of a trace with direction d that found nothing, float64 without fused
-// multiply-add in the header's order.  k is the scene's sky block (SKY_DOUBLES 8-byte words), which the host lays out for this
+// multiply-add in the header's order.  k is the scene's sky block (SKY_DOUBLES 8-byte words), which the host (rt_scene.h: sky_block) lays out for this
 // function:
 //   0..2 up | 3..5 horizon | 6..8 zenith - horizon | 9..11 nadir - horizon | 12 log2(sharp), an int64 | 13..15 sun_dir |
 //   16 sun_cos | 17..19 sun_rgb | 20..22 halo_rgb | 23 log2(halo_shin), an int64
@@ -1488,7 +1454,6 @@ __device__ __forceinline__ unsigned texel_of(const KParams &p, int slot, const V
 // to the constant address space: the kernel never writes the scene buffer and the address is made of kernel arguments alone, so
 // every read is an s_load into SGPRs and no VGPR holds a constant of the sky; the two counts are integers so that the squaring
 // loops run on the scalar unit.  Both gradient differences are loaded and the value is selected, not the address.
-constexpr int SKY_DOUBLES = 24;
 typedef __attribute__((address_space(4))) const double sky_f64;
 typedef __attribute__((address_space(4))) const long long sky_i64;
 __device__ __forceinline__ V3 sky_color(const double *block, const V3 &d)
@@ -1905,20 +1870,7 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
 }
 
 // LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
-__host__ __device__ inline size_t lds_doubles(int S, int P, int L) { return (size_t)S * SPH_STRIDE + (size_t)P * PL_STRIDE + (size_t)L * LT_STRIDE; }
 __host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2, Family f) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (has_mat(f) ? 3 : 0) + (has_refr(f) ? 4 : 0) + (has_scat(f) ? 2 : 0) + (has_soft(f) ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
-// The material block of a scene with materials, behind the packed records (and the cluster records and one spare double):
-// M, then the M x table_cols(f) table {amb, lamb, refl} (5 columns, refraction kernels: {amb, lamb, refl, trans, ior}; 6, scatter
-// kernels and their twins: ..., rough), then S + P int32
-// material ids of the slots (padded to a double), and (has_soft(f): a scene of the area-light kernels) its shadow_samples n.  Material
-// kernels stage it at the end of their LDS image.
-__host__ __device__ inline size_t mat_offset(int S, int P, int L, int NC) { return lds_doubles(S, P, L) + (size_t)(NC + supers(NC)) * CL_STRIDE + 1; }
-__host__ __device__ inline size_t mat_doubles(int M, int S, int P, Family f) { return M > 0 ? 1 + (size_t)table_cols(f) * M + ((size_t)S + P + 1) / 2 + (has_soft(f) ? 1 : 0) : 0; }
-// The texture block of a scene with a textured object (KParams::lens.tex): T, then the T records of TEX_STRIDE doubles (texel_of).
-__host__ __device__ inline size_t tex_doubles(int T) { return T > 0 ? 1 + (size_t)TEX_STRIDE * T : 0; }
-// The lighting block of a scene that runs the LIT kernels (KParams::lens.lit): {e_r, e_g, e_b, -} per light (LT_STRIDE doubles),
-// then {spec / n, log2(shin)} per object slot (S spheres in slot order, then P planes).
-__host__ __device__ inline size_t lit_doubles(int S, int P, int L) { return (size_t)LT_STRIDE * L + 2 * ((size_t)S + P); }
 __host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
 // The float32 tables of a scene, offsets in floats (every one a multiple of 4):
 //   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours

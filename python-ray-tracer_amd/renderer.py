@@ -80,6 +80,13 @@ def check_frame(w, h):
     return w, h
 
 
+# The rt_set_scene* entries (include/mi355rt.h; _lib.PROTOTYPES): each takes the leading arguments of the next, up to
+# rt_set_scene_sky's 23 (rt_set_scene_materials: those of rt_set_scene_materials_ex without ncols).
+_SCENE_ENTRIES = {"rt_set_scene": 8, "rt_set_scene_materials": 13, "rt_set_scene_materials_ex": 13,
+                  "rt_set_scene_materials_scatter": 13, "rt_set_scene_area_lights": 15, "rt_set_scene_textures": 21,
+                  "rt_set_scene_lighting": 22, "rt_set_scene_sky": 23}
+
+
 class Renderer:
     def __init__(self, device=0, lib=None):
         self.serial = next(_serials)     # process-unique (id() values are reused after garbage collection)
@@ -168,10 +175,12 @@ class Renderer:
                 raise ValueError(f"sky: {sk.shape[0]} doubles, a packed sky has {L.RT_SKY_DOUBLES}")
             if materials is None:
                 raise ValueError("a sky needs a material table: pass materials=...")
-        if materials is None:
-            self._check(self._lib.rt_set_scene(self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1],
-                                               p.ctypes.data_as(fp), p.shape[1], int(flags)))
-        else:
+        # every entry's arguments are the leading ones of rt_set_scene_sky's (_SCENE_ENTRIES): marshal those once, then call the
+        # entry of the highest feature in use
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        t = si = pi = None
+        ncols = 3
+        if materials is not None:
             table, sid, pid = materials
             t = np.ascontiguousarray(table, dtype=np.float64)
             ncols = t.shape[1] if t.ndim == 2 else 3
@@ -181,57 +190,48 @@ class Renderer:
             pi = np.ascontiguousarray(pid, dtype=np.int32).reshape(-1)
             if si.shape[0] != s.shape[1] or pi.shape[0] != p.shape[1]:
                 raise ValueError(f"material ids: {si.shape[0]} for {s.shape[1]} spheres, {pi.shape[0]} for {p.shape[1]} planes")
-            ip = C.POINTER(C.c_int32)
-            if textures is not None or rgb is not None or ncols == 8 or sk is not None:
-                records, tsid, tpid, texels = textures if textures is not None else (
-                    [], np.full(s.shape[1], -1, np.int32), np.full(p.shape[1], -1, np.int32), np.zeros((0, 3), np.float32))
-                T = len(records)
-                recs = (L.rt_texture * max(T, 1))()
-                for k, (o, ax, dims, first) in enumerate(records):
-                    o = np.asarray(o, dtype=np.float64).reshape(3)
-                    ax = np.asarray(ax, dtype=np.float64).reshape(3, 3)
-                    for a in range(3):
-                        recs[k].origin[a] = o[a]
-                        recs[k].dim[a] = int(dims[a])
-                        for i in range(3):
-                            recs[k].axis[a][i] = ax[a, i]
-                    recs[k].first = int(first)
-                tsi = np.ascontiguousarray(tsid, dtype=np.int32).reshape(-1)
-                tpi = np.ascontiguousarray(tpid, dtype=np.int32).reshape(-1)
-                if tsi.shape[0] != s.shape[1] or tpi.shape[0] != p.shape[1]:
-                    raise ValueError(f"texture ids: {tsi.shape[0]} for {s.shape[1]} spheres, {tpi.shape[0]} for {p.shape[1]} planes")
-                tx = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1, 3)
-                zr = rad if rad is not None else np.zeros(l.shape[1], dtype=np.float32)
-                args = (self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
-                        p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
-                        si.ctypes.data_as(ip), pi.ctypes.data_as(ip), zr.ctypes.data_as(fp), int(shadow_samples),
-                        recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip), tx.ctypes.data_as(fp), tx.shape[0])
-                if sk is not None:
-                    self._check(self._lib.rt_set_scene_sky(*args, rgb.ctypes.data_as(fp) if rgb is not None else None,
-                                                           sk.ctypes.data_as(C.POINTER(C.c_double))))
-                elif rgb is not None or ncols == 8:
-                    self._check(self._lib.rt_set_scene_lighting(*args, rgb.ctypes.data_as(fp) if rgb is not None else None))
-                else:
-                    self._check(self._lib.rt_set_scene_textures(*args))
-            elif rad is not None:
-                self._check(self._lib.rt_set_scene_area_lights(
-                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
-                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
-                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip), rad.ctypes.data_as(fp), int(shadow_samples)))
-            elif ncols not in (3, 5):
-                self._check(self._lib.rt_set_scene_materials_scatter(
-                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
-                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], ncols,
-                    si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
-            elif ncols == 5:
-                self._check(self._lib.rt_set_scene_materials_ex(
-                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp),
-                    p.shape[1], int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], 5, si.ctypes.data_as(ip),
-                    pi.ctypes.data_as(ip)))
-            else:
-                self._check(self._lib.rt_set_scene_materials(
-                    self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp), p.shape[1],
-                    int(flags), t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], si.ctypes.data_as(ip), pi.ctypes.data_as(ip)))
+        records, tsid, tpid, texels = textures if textures is not None else (
+            [], np.full(s.shape[1], -1, np.int32), np.full(p.shape[1], -1, np.int32), np.zeros((0, 3), np.float32))
+        T = len(records)
+        recs = (L.rt_texture * max(T, 1))()
+        for k, (o, ax, dims, first) in enumerate(records):
+            o = np.asarray(o, dtype=np.float64).reshape(3)
+            ax = np.asarray(ax, dtype=np.float64).reshape(3, 3)
+            for a in range(3):
+                recs[k].origin[a] = o[a]
+                recs[k].dim[a] = int(dims[a])
+                for i in range(3):
+                    recs[k].axis[a][i] = ax[a, i]
+            recs[k].first = int(first)
+        tsi = np.ascontiguousarray(tsid, dtype=np.int32).reshape(-1)
+        tpi = np.ascontiguousarray(tpid, dtype=np.int32).reshape(-1)
+        if tsi.shape[0] != s.shape[1] or tpi.shape[0] != p.shape[1]:
+            raise ValueError(f"texture ids: {tsi.shape[0]} for {s.shape[1]} spheres, {tpi.shape[0]} for {p.shape[1]} planes")
+        tx = np.ascontiguousarray(texels, dtype=np.float32).reshape(-1, 3)
+        zr = rad if rad is not None else np.zeros(l.shape[1], dtype=np.float32)
+        ptr = lambda a, ty: a.ctypes.data_as(ty) if a is not None else None
+        args = (self._ctx, s.ctypes.data_as(fp), s.shape[1], l.ctypes.data_as(fp), l.shape[1], p.ctypes.data_as(fp), p.shape[1],
+                int(flags), ptr(t, dp), t.shape[0] if t is not None else 0, ncols, ptr(si, ip), ptr(pi, ip),
+                zr.ctypes.data_as(fp), int(shadow_samples), recs, T, tsi.ctypes.data_as(ip), tpi.ctypes.data_as(ip),
+                tx.ctypes.data_as(fp), tx.shape[0], ptr(rgb, fp), ptr(sk, dp))
+        if materials is None:
+            entry = "rt_set_scene"
+        elif sk is not None:
+            entry = "rt_set_scene_sky"
+        elif rgb is not None or ncols == 8:
+            entry = "rt_set_scene_lighting"
+        elif textures is not None:
+            entry = "rt_set_scene_textures"
+        elif rad is not None:
+            entry = "rt_set_scene_area_lights"
+        elif ncols not in (3, 5):
+            entry = "rt_set_scene_materials_scatter"
+        else:
+            entry = "rt_set_scene_materials_ex" if ncols == 5 else "rt_set_scene_materials"
+        args = args[:_SCENE_ENTRIES[entry]]
+        if entry == "rt_set_scene_materials":
+            args = args[:10] + args[11:]                     # (the one entry without ncols)
+        self._check(getattr(self._lib, entry)(*args))
         self.counts = (s.shape[1], l.shape[1], p.shape[1])
         self.generation["scene"] += 1
 

@@ -3,6 +3,9 @@ straightforward evaluation on tens of millions of inputs.  The shortcuts are alg
 features, so they can be validated here without a GPU; the GPU parity tests then confirm the device code."""
 import os
 import subprocess
+import sys
+
+import pytest
 
 from conftest import REPO
 
@@ -110,3 +113,128 @@ def test_python_frame_rule_is_the_header_rule():
                  (2 ** 31, 1), (2 ** 30 + 1, 2)]:
         with pytest.raises(ValueError):
             check_frame(w, h)
+
+
+@pytest.fixture(scope="module")
+def scene_pack_shim(tmp_path_factory):
+    """(path, env): tests/algo/scene_pack_check.cpp (the library's scene packer, rt_scene.h, without HIP) as a shared object built with
+    AddressSanitizer and UndefinedBehaviorSanitizer, and the environment a Python that loads it needs (the sanitizer's
+    runtime in front of everything else)."""
+    so = str(tmp_path_factory.mktemp("scene_pack") / "scene_pack_check.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so,
+                           os.path.join(ALGO, "scene_pack_check.cpp")])
+    asan = subprocess.check_output(["g++", "-print-file-name=libasan.so"], text=True).strip()
+    pre = os.environ.get("LD_PRELOAD")
+    env = dict(os.environ, LD_PRELOAD=asan + (":" + pre if pre else ""), UBSAN_OPTIONS="print_stacktrace=1",
+               ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0")    # (leaks: the interpreter's own)
+    return so, env
+
+
+def test_scene_pack_is_bit_identical_to_the_recorded_one(scene_pack_shim, tmp_path):
+    """python-ray-tracer_amd/csrc/rt_scene.h, everything an rt_set_scene* entry does before it touches the device, under
+    AddressSanitizer and UndefinedBehaviorSanitizer on the scenes of tests/algo/scene_pack_cases.py: every branch of the table
+    widths, area lights, textures, lighting, the sky, flat and clustered scenes, RT_FLAG_TYPED_BIAS.  The scene buffer, the texel
+    array and every field of the layout must be, bit for bit, what tests/golden/scene_pack.npz holds: the output of the
+    library's set_scene as it was before the packer became a header of its own, recorded from a build of that commit patched to
+    write its buffers and context fields to a file.  Invalid inputs (one per rule, and several that break two rules at once)
+    must give the recorded status and the recorded error text.  The degenerate inputs (textures with every id -1, white
+    lights with spec 0, a black sky, radii all zero) must pack exactly like the lower entry."""
+    import json
+    import numpy as np
+    so, env = scene_pack_shim
+    got_path = str(tmp_path / "got.npz")
+    res = subprocess.run([sys.executable, os.path.join(ALGO, "scene_pack_cases.py"), so, got_path], env=env, capture_output=True, text=True)
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    got, want = np.load(got_path), np.load(os.path.join(REPO, "tests", "golden", "scene_pack.npz"))
+    assert sorted(got.files) == sorted(want.files)
+    for k in want.files:
+        if k == "errors":
+            continue
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert got[k].tobytes() == want[k].tobytes(), k
+    ge, we = json.loads(str(got["errors"])), json.loads(str(want["errors"]))
+    assert sorted(ge) == sorted(we) and len(we) > 50
+    for name in we:
+        assert ge[name] == we[name], (name, ge[name], we[name])
+        assert we[name][0] == -1 and we[name][1], name                        # (RT_ERR_BAD_ARG with a text)
+    sys.path.insert(0, ALGO)
+    try:
+        from scene_pack_cases import EQUAL
+    finally:
+        sys.path.remove(ALGO)
+    for a, b in EQUAL:
+        for k in ("rec", "texels", "layout", "extent2"):
+            assert got[f"{a}/{k}"].tobytes() == got[f"{b}/{k}"].tobytes(), (a, b, k)
+    # every branch the cases are there for was taken (layout: S, P, L, NC, M, mat_cols, soft_n, T, lit, sky, four offsets, codes)
+    lay = {n[:-len("/layout")]: dict(zip(["S", "P", "L", "NC", "M", "mat_cols", "soft_n", "T", "lit", "sky"], got[n][:10]))
+           for n in got.files if n.endswith("/layout")}
+    assert lay["flat"]["M"] == 0 and lay["flat"]["NC"] == 0
+    assert [lay[n]["mat_cols"] for n in ("mat3", "refr5", "scat6", "soft6", "soft3")] == [3, 5, 6, 6, 6]
+    assert lay["soft6"]["soft_n"] > 0 and lay["soft3"]["soft_n"] == 4 and lay["radii_zero"]["soft_n"] == 0
+    assert lay["tex"]["T"] == 2 and not lay["tex"]["lit"] and lay["tex_none"]["T"] == 0
+    assert lay["lit"]["lit"] and not lay["lit"]["sky"] and not lay["lit_white"]["lit"]
+    assert lay["sky"]["sky"] and lay["sky"]["lit"] and lay["sky"]["T"] == 2 and lay["sky"]["soft_n"] > 0 and not lay["sky_black"]["sky"]
+    assert lay["sky_s64"]["NC"] == 8 and lay["sky_s256"]["NC"] == 32
+    assert got["typed_bias/rec"].tobytes() != got["flat/rec"].tobytes()
+
+
+def test_scene_layout_offsets_follow_rt_layout(scene_pack_shim):
+    """The four block offsets of a packed scene's layout, and the length of its buffer, are the ones rt_layout.h's mat_offset,
+    mat_doubles, tex_doubles and lit_doubles give (the kernels find the blocks through the same functions): for made-up scenes of
+    0 to 170 spheres with every combination of table width, area lights, a texture, a coloured light and a sky."""
+    so, env = scene_pack_shim
+    res = subprocess.run([sys.executable, "-c", _OFFSETS_CHECK, ALGO, so], env=env, capture_output=True, text=True)
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == "scenes=245 ok", res.stdout    # (5 sizes x (no table + 3 widths x 16 feature combinations))
+
+
+_OFFSETS_CHECK = r'''
+import itertools, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import scene_pack_cases as spc
+lib = spc.bind(sys.argv[2])
+LENS, n = 5, 0                                                           # (rt::Family::LENS)
+for S, ncols, soft, tex, rgb, sky in itertools.product((0, 5, 21, 64, 170), (0, 3, 5, 6), (0, 1), (0, 1), (0, 1), (0, 1)):
+    if ncols == 0 and (soft or tex or rgb or sky):
+        continue                                                         # (every feature needs a material table)
+    P, L, M = 2, 3, 4
+    i = np.arange(7 * S, dtype=np.float32).reshape(7, S)
+    spheres = np.cos(i) * 9.0
+    spheres[3] = 0.5 + 0.01 * np.arange(S)
+    planes = np.array([[0, 0], [0, 0], [-1, 5], [0, 0], [0, 1], [1, 0], [.5, .5], [.5, .5], [.5, .5]], np.float32)
+    table = np.tile(np.array([0.1, 0.6, 0.0, 0.0, 1.0, 0.0]), (M, 1))
+    if ncols >= 5:
+        table[1, 3], table[1, 4] = 0.8, 1.5                              # a transparent row
+    if ncols == 6:
+        table[2, 5] = 0.3                                                # a rough row
+    c = dict(entry="sky" if sky else "lighting" if rgb else "textures" if tex else "area_lights" if soft else "scatter" if ncols else "scene",
+             flags=0, spheres=spheres, lights=np.eye(3, dtype=np.float32) * 7, planes=planes,
+             materials=table[:, :ncols] if ncols else None, sphere_material=np.arange(S) % M, plane_material=np.arange(P) % M,
+             light_radius=np.array([0.2, 0, 0], np.float32) if soft else None, shadow_samples=3,
+             tex_origin=np.zeros((tex, 3)), tex_axes=np.tile(np.eye(3), (tex, 1, 1)), tex_dims=np.full((tex, 3), 2, np.int32),
+             tex_first=np.zeros(tex, np.int64), texels=np.full((8 * tex, 3), 0.5, np.float32),
+             sphere_texture=np.full(S, -1, np.int32), plane_texture=np.array([0 if tex else -1, -1], np.int32),
+             light_rgb=np.full((3, 3), 0.5, np.float32) if rgb else None,
+             sky=np.array([0, 0, 1, .1, .2, .3, .4, .5, .6, .1, .1, .1, 2, 0, 1, 0, .99, 1, 1, 1, .2, .2, .2, 8.0]) if sky else None)
+    r = spc.pack(lib, c)
+    assert r["status"] == 0, (c["entry"], r["error"])
+    lay = dict(zip(spc.LAYOUT, (int(v) for v in r["layout"])))
+    Mm = M if ncols else 0
+    assert (lay["S"], lay["P"], lay["L"], lay["M"]) == (S, P, L, Mm)
+    assert lay["NC"] == ((S + 7) // 8 if S > spc.CLUSTER_MIN else 0)
+    assert lay["mat_cols"] == (6 if soft and ncols else ncols or 3) and lay["soft_n"] == 3 * soft
+    assert lay["T"] == tex and lay["lit"] == (rgb or sky) and lay["sky"] == sky
+    mat_off = lib.scene_mat_offset(S, P, L, lay["NC"])
+    matd = lib.scene_mat_doubles(Mm, S, P, lib.scene_block_family(Mm, lay["mat_cols"], soft))
+    lens = mat_off + matd if Mm > 0 and lay["mat_cols"] < 6 else mat_off
+    tex_off = mat_off + matd + (lib.scene_mat_doubles(Mm, S, P, LENS) if lens != mat_off else 0)
+    lit_off = tex_off + lib.scene_tex_doubles(lay["T"])
+    sky_off = lit_off + (lib.scene_lit_doubles(S, P, L) if lay["lit"] else 0)
+    assert (lay["lens_mat"], lay["tex_off"], lay["lit_off"], lay["sky_off"]) == (lens, tex_off, lit_off, sky_off), (c["entry"], S, ncols, lay)
+    assert len(r["rec"]) == sky_off + (lib.scene_sky_doubles() if sky else 0)
+    assert len(r["texels"]) == (4 * (S + P + 8 * tex) if lay["T"] or lay["lit"] else 0)
+    n += 1
+print(f"scenes={n} ok")
+'''
