@@ -16,7 +16,9 @@ FLAG_TYPED_BIAS = 1
 
 # Deliberately wrong restatements of the feature path (rt_oracle.c ORC_WRONG_*): test-only, for showing that the fixtures
 # catch each of them (tests/test_oracle_features.py).
-WRONG = dict(key_pixel=1, pow_weight=2, soft_i_major=4, lamb_whole=8, tir_far=16, no_bounce=32, focus_f=64, no_absorb=128)
+WRONG = dict(key_pixel=1, pow_weight=2, soft_i_major=4, lamb_whole=8, tir_far=16, no_bounce=32, focus_f=64, no_absorb=128,
+             tex_biased=256, tex_trunc=512, spec_texel=1024, spec_whole=2048, sun_first=4096, sky_flat=8192, lamb_order=16384)
+SKY_DOUBLES = 24
 
 _lib = None
 
@@ -36,7 +38,15 @@ class _RayGen(C.Structure):
 class _Features(C.Structure):
     _fields_ = [("M", C.c_int), ("ncols", C.c_int), ("materials", C.c_void_p), ("sphere_material", C.c_void_p),
                 ("plane_material", C.c_void_p), ("light_radius", C.c_void_p), ("shadow_samples", C.c_int),
-                ("aperture", C.c_double), ("focus", C.c_double), ("wrong", C.c_int)]
+                ("aperture", C.c_double), ("focus", C.c_double), ("wrong", C.c_int),
+                ("T", C.c_int), ("textures", C.c_void_p), ("sphere_texture", C.c_void_p), ("plane_texture", C.c_void_p),
+                ("texels", C.c_void_p), ("n_texels", C.c_int64), ("light_rgb", C.c_void_p), ("sky", C.c_void_p)]
+
+
+class _Texture(C.Structure):
+    """rt_oracle.c orc_texture: the layout of include/mi355rt.h's rt_texture."""
+    _fields_ = [("origin", C.c_double * 3), ("axis", (C.c_double * 3) * 3), ("dim", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("first", C.c_int64)]
 
 
 def lib():
@@ -70,6 +80,12 @@ def lib():
         L.orc_render_pixels_ex.argtypes = list(L.orc_render_pixels.argtypes) + [C.POINTER(_Features)]
         L.orc_render_pixels_ex.restype = C.c_int
         L.orc_max_threads.restype = C.c_int
+        L.orc_texel_index.argtypes = [dp, C.POINTER(_Texture), C.c_int]
+        L.orc_texel_index.restype = C.c_int64
+        L.orc_light_terms.argtypes = [dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
+        L.orc_light_terms.restype = None
+        L.orc_sky_color.argtypes = [dp, dp, dp]
+        L.orc_sky_color.restype = None
         _lib = L
     return _lib
 
@@ -162,10 +178,69 @@ def sample(spheres, lights, planes, o, d, amb, lamb, refl, depth, flags=0):
     return out
 
 
-def _features(S, L, P, materials, light_radius, shadow_samples, lens, wrong):
+def _texture_records(records):
+    """A ctypes array of orc_texture from records (origin (3,), axes (3,3), (nx, ny, nz), first)."""
+    recs = (_Texture * max(len(records), 1))()
+    for k, (o, ax, dims, first) in enumerate(records):
+        o, ax = _d(o).reshape(3), _d(ax).reshape(3, 3)
+        for a in range(3):
+            recs[k].origin[a] = o[a]
+            recs[k].dim[a] = int(dims[a])
+            for i in range(3):
+                recs[k].axis[a][i] = ax[a, i]
+        recs[k].first = int(first)
+    return recs
+
+
+def texel_index(points, origin, axes, dims, first=0, wrong=0):
+    """rt_oracle.c orc_texel_index for points (..., 3): int64 of shape points.shape[:-1] (scene.texel_index's arguments)."""
+    p = _d(points)
+    recs = _texture_records([(origin, axes, dims, first)])
+    flat = p.reshape(-1, 3)
+    out = np.empty(len(flat), np.int64)
+    fn = lib().orc_texel_index
+    for i in range(len(flat)):
+        out[i] = fn(_dp(flat[i]), recs, int(wrong))
+    return out.reshape(p.shape[:-1])
+
+
+def light_terms(rgb, d, N, Ld, col, e, lamb_n, spec, spec_n, shin, occluded, wrong=0):
+    """rt_oracle.c orc_light_terms for arrays (..., 3) (scene.lighting.light_terms' arguments): (..., 3) float64."""
+    rgb = np.array(_d(rgb))
+    shape = rgb.shape[:-1]
+    b3 = lambda a: np.ascontiguousarray(np.broadcast_to(_d(a), rgb.shape)).reshape(-1, 3)
+    b1 = lambda a, dt=np.float64: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=dt), shape)).reshape(-1)
+    d, N, Ld, col = b3(d), b3(N), b3(Ld), b3(col)
+    e = _d(e).reshape(3)
+    lamb_n, spec, spec_n, shin, occ = b1(lamb_n), b1(spec), b1(spec_n), b1(shin), b1(occluded, bool)
+    flat = rgb.reshape(-1, 3)
+    fn = lib().orc_light_terms
+    for i in range(len(flat)):
+        nsq = int(shin[i]).bit_length() - 1
+        assert float(1 << nsq) == shin[i] and 0 <= nsq <= 10
+        fn(_dp(flat[i]), _dp(d[i]), _dp(N[i]), _dp(Ld[i]), _dp(col[i]), _dp(e), float(lamb_n[i]), float(spec[i]), float(spec_n[i]),
+           nsq, int(occ[i]), int(wrong))
+    return flat.reshape(rgb.shape)
+
+
+def sky_color(d, packed):
+    """rt_oracle.c orc_sky_color for directions (..., 3) and a packed sky (24 float64; not checked here): (..., 3) float64."""
+    d = _d(d)
+    k = _d(packed).reshape(-1)
+    assert k.shape == (SKY_DOUBLES,)
+    flat = d.reshape(-1, 3)
+    out = np.empty_like(flat)
+    fn = lib().orc_sky_color
+    for i in range(len(flat)):
+        fn(_dp(flat[i]), _dp(k), _dp(out[i]))
+    return out.reshape(d.shape)
+
+
+def _features(S, L, P, materials, light_radius, shadow_samples, lens, wrong, textures=None, light_rgb=None, sky=None):
     """(struct, arrays it points into) for the keyword arguments of render / render_pixels, or (None, None) when none is given:
     then the plain entry points run."""
-    if materials is None and light_radius is None and lens is None and not wrong:
+    if materials is None and light_radius is None and lens is None and not wrong and textures is None and light_rgb is None \
+            and sky is None:
         return None, None
     fe = _Features()
     keep = []
@@ -187,22 +262,47 @@ def _features(S, L, P, materials, light_radius, shadow_samples, lens, wrong):
     fe.shadow_samples = int(shadow_samples)
     fe.aperture, fe.focus = (0.0, 1.0) if lens is None else (float(lens[0]), float(lens[1]))
     fe.wrong = int(wrong)
+    if textures is not None:
+        records, tsid, tpid, texels = textures
+        recs = _texture_records(records)
+        tsid = np.ascontiguousarray(tsid, dtype=np.int32).reshape(-1)
+        tpid = np.ascontiguousarray(tpid, dtype=np.int32).reshape(-1)
+        tx = _f(texels).reshape(-1, 3)
+        assert tsid.shape == (S,) and tpid.shape == (P,)
+        keep += [recs, tsid, tpid, tx]
+        fe.T, fe.textures = len(records), C.addressof(recs)
+        fe.sphere_texture, fe.plane_texture = tsid.ctypes.data, tpid.ctypes.data
+        fe.texels, fe.n_texels = tx.ctypes.data, tx.shape[0]
+    if light_rgb is not None:
+        rgb = _f(light_rgb).reshape(-1, 3)
+        assert rgb.shape == (L, 3)
+        keep.append(rgb)
+        fe.light_rgb = rgb.ctypes.data if L else None
+    if sky is not None:
+        k = _d(sky.pack() if hasattr(sky, "pack") else sky).reshape(-1)
+        if k.shape != (SKY_DOUBLES,):
+            raise ValueError(f"sky: {k.shape[0]} doubles, a packed sky has {SKY_DOUBLES}")
+        keep.append(k)
+        fe.sky = k.ctypes.data
     return fe, keep
 
 
 def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, depth, aa=False, *,
            pixel_loc=None, raygen=None, x0=0, x1=None, flags=0, want=("u8", "f64"), nthreads=0, refl_pow=None,
-           spp=0, seed=1, materials=None, light_radius=None, shadow_samples=1, lens=None, wrong=0):
+           spp=0, seed=1, materials=None, light_radius=None, shadow_samples=1, lens=None, wrong=0, textures=None,
+           light_rgb=None, sky=None):
     """Run the restated `render` (kernels.py:6-73) for columns [x0,x1).
 
     raygen = (px, y0, dy, z0, dz) closed form, or pixel_loc = explicit float64 (3,w,h) array.
     Returns dict with any of 'u8' (3,w,h) uint8 [R,B,G], 'f64' (3,w,h), 'f32' (3,w,h) and 'counters'.
     Columns outside [x0,x1) are left zero.
 
-    The features of include/mi355rt.h (rt_oracle.c orc_render_ex): materials = (table (M,3|5|6) float64, sphere ids (S,),
-    plane ids (P,)) as rt_set_scene_materials_scatter takes them (amb, lamb and refl are then ignored); light_radius (L,)
-    and shadow_samples as rt_set_scene_area_lights; lens = (aperture, focus_distance) as rt_set_lens.  wrong: WRONG bits
-    (test-only).  Input the header refuses raises ValueError.
+    The features of include/mi355rt.h (rt_oracle.c orc_render_ex): materials = (table (M,3|5|6|8) float64, sphere ids (S,),
+    plane ids (P,)) as rt_set_scene_lighting takes them (amb, lamb and refl are then ignored); light_radius (L,)
+    and shadow_samples as rt_set_scene_area_lights; lens = (aperture, focus_distance) as rt_set_lens; textures = (records,
+    sphere ids (S,), plane ids (P,), texels (N,3)), light_rgb (L,3) float32 and sky (a scene.Sky or its 24 packed float64)
+    with the shapes Renderer.set_scene takes (rt_set_scene_textures, _lighting, _sky).  wrong: WRONG bits (test-only).
+    Input the header refuses raises ValueError.
     """
     L = lib()
     x1 = w if x1 is None else x1
@@ -224,7 +324,8 @@ def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, 
     f64 = np.zeros((3, w, h), np.float64) if "f64" in want else None
     f32 = np.zeros((3, w, h), np.float32) if "f32" in want else None
     cnt = (C.c_longlong * 3)()
-    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong)
+    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong,
+                            textures, light_rgb, sky)
     args = (C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
             _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp), int(flags),
             int(x0), int(x1),
@@ -244,7 +345,7 @@ def render(w, h, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, 
 
 def render_pixels(w, h, coords, cam_origin, cam_rot, spheres, lights, planes, amb, lamb, refl, depth, aa=False, *,
                   pixel_loc=None, raygen=None, flags=0, nthreads=0, refl_pow=None, spp=0, seed=1, materials=None,
-                  light_radius=None, shadow_samples=1, lens=None, wrong=0):
+                  light_radius=None, shadow_samples=1, lens=None, wrong=0, textures=None, light_rgb=None, sky=None):
     """The same per-pixel path for an explicit (n,2) list of (x,y) pixels (the feature keywords of render()).
     Returns (u8 (n,3) in stored order [R,B,G], f64 (n,3) = pre-clip (R,G,B))."""
     L = lib()
@@ -265,7 +366,8 @@ def render_pixels(w, h, coords, cam_origin, cam_rot, spheres, lights, planes, am
     n = co.shape[0]
     u8 = np.zeros((n, 3), np.uint8)
     f64 = np.zeros((n, 3), np.float64)
-    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong)
+    fe, fkeep = _features(spheres.shape[1], lights.shape[1], planes.shape[1], materials, light_radius, shadow_samples, lens, wrong,
+                            textures, light_rgb, sky)
     args = (C.byref(rg), _dp(o), _dp(R), _fp(spheres), spheres.shape[1], _fp(lights), lights.shape[1],
             _fp(planes), planes.shape[1], float(amb), float(lamb), _dp(rp), int(depth), _aa_code(aa, spp),
             int(flags), co.ctypes.data, n, u8.ctypes.data, f64.ctypes.data, int(nthreads), int(seed) & 0xFFFFFFFF)

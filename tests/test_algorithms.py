@@ -38,8 +38,9 @@ def test_in_range_division_and_sqrt_are_bit_identical(tmp_path):
 def test_oracle_under_asan_ubsan(tmp_path):
     """the CPU restatement under AddressSanitizer + UndefinedBehaviorSanitizer (the GPU side cannot run
     sanitizers on this pool).  Two scenes (a golden's, and an empty one) through every oracle entry point, the feature
-    path's (orc_render_ex, orc_render_pixels_ex) included; the sanitized build must finish without a report and produce the
-    bytes of the regular build."""
+    path's (orc_render_ex, orc_render_pixels_ex) included, with texture records, ids and texels, light colours, an 8-column
+    table and a sky, and the input it refuses (a texel range one past the array's end among it); the sanitized build must
+    finish without a report and produce the bytes of the regular build."""
     import struct
     import numpy as np
     from conftest import load_frame, raygen_closed_form
@@ -70,6 +71,27 @@ def test_oracle_under_asan_ubsan(tmp_path):
             f.write((np.arange(sp.shape[1]) % 3).astype(np.int32).tobytes()); f.write((np.arange(pl.shape[1]) % 3).astype(np.int32).tobytes())
             f.write((0.4 * (np.arange(li.shape[1]) % 2)).astype(np.float32).tobytes())
             f.write(np.array([0.1, 3.0]).tobytes())
+            # textures, lighting and the sky: three records over 40 texels (skewed axes; axes of 1e12 cells per unit, so that
+            # the frame's hit points take both clamps; a 2 x 3 x 4 grid whose range overlaps the second's and ends exactly at the
+            # array's end), ids with -1 among them, coloured lights with a zero and a value above 1, an 8-column table, a sky
+            S, P, NL = sp.shape[1], pl.shape[1], li.shape[1]
+            recs = [((0.1, -0.2, 0.3), [[1.5, 0.25, 0.0], [-0.5, 2.0, 0.125], [0.0, 0.0, 1.0]], (5, 3, 1), 0),
+                    ((0.0, 0.0, 0.0), [[1e12, 0.0, 0.0], [0.0, -1e12, 0.0], [0.0, 0.0, 1e12]], (3, 2, 2), 15),
+                    ((0.0, 0.0, -1.0), [[0.7, 0.7, 0.0], [0.0, 0.9, -0.4], [0.3, 0.0, 1.1]], (2, 3, 4), 16)]
+            n_texels = 40
+            f.write(struct.pack("i", len(recs)))
+            for o, ax, dims, first in recs:
+                f.write(np.asarray(o, np.float64).tobytes()); f.write(np.asarray(ax, np.float64).tobytes())
+                f.write(struct.pack("4i", *dims, 0)); f.write(struct.pack("q", first))
+            f.write(struct.pack("q", n_texels))
+            f.write(((np.arange(S) % 4) - 1).astype(np.int32).tobytes()); f.write((2 - (np.arange(P) % 4)).astype(np.int32).tobytes())
+            f.write(np.random.default_rng(3).integers(0, 256, (n_texels, 3)).astype(np.float32).tobytes())
+            f.write(np.array([[1.5, 0.0, 0.25], [1.0, 1.0, 1.0], [0.0, 0.0, 0.0], [0.3, 2.0, 1.0]] * NL, np.float32)[:NL].tobytes())
+            table8 = np.array([[0.05, 0.6, 0.5, 0.0, 1.0, 0.0, 120.0, 64.0], [0.0, 0.1, 0.0, 0.9, 1.5, 0.0, 200.0, 1024.0],
+                               [-0.02, 0.0, 0.7, 0.0, 1.0, 0.4, 80.0, 1.0]])
+            f.write(struct.pack("i", len(table8))); f.write(table8.tobytes())
+            sky = np.array([0.0, 0.6, 0.8, 20, 60, 200, 210, 220, 240, 70, 60, 50, 4.0, 0.8, 0.0, 0.6, 0.999, 255, 240, 200, 90, 70, 30, 32.0])
+            f.write(sky.tobytes())
         outs = []
         for exe in (plain, san):
             out = str(tmp_path / (os.path.basename(exe) + f"{i}.out"))

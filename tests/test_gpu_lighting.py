@@ -1,5 +1,5 @@
 """Lighting on the GPU (rt_set_scene_lighting, the lighting kernels): every lighting_* fixture through every entry point, all
-56 lighting kernels through the dispatcher's environment overrides with the same bytes, fixtures against restated scenes (white
+56 lighting kernels through the dispatcher's environment overrides with the same bytes and the bytes of the CPU oracle's frames, fixtures against restated scenes (white
 lights without a spec row, an unused spec row, doubled lights with lamb halved, a black light, a red light), frames in flight
 across a scene change, column slabs, the error paths and the example."""
 import ctypes as C
@@ -16,6 +16,8 @@ from conftest import REPO, load_frame, raygen_closed_form
 from test_lighting import CASES, fixture_textures, load_lighting
 from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
 from test_gpu_textures import _scene_textures
+from test_gpu_features_vs_oracle import _same
+from test_gpu_lit_vs_oracle import kernel_table_refs
 
 pytestmark = pytest.mark.gpu
 IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
@@ -153,7 +155,7 @@ def _glossy(table):
 
 
 @pytest.mark.parametrize("kind", list(LIT_FAMILIES))
-def test_every_lighting_kernel_same_bytes(monkeypatch, capfd, kind):
+def test_every_lighting_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
     import python_ray_tracer_amd as pkg
     from python_ray_tracer_amd import _lib as L
     soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
@@ -174,6 +176,8 @@ def test_every_lighting_kernel_same_bytes(monkeypatch, capfd, kind):
         rgb = np.array([[1.0, 0.7, 0.4], [0.3, 0.5, 1.5], [0.0, 0.3, 0.2]][:NL], np.float32)
         tex = _scene_textures(src) if case != "tiny" else None    # (tiny: a lit scene without textures)
         rg = raygen_closed_form(w, h, float(src["fov"]))
+        refs = kernel_table_refs(oracle, src, w, h, modes, "lighting", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
+                                 textures=tex, light_rgb=rgb)
         first = plain = None
         for env in _VARIANTS[case]:
             for k in _VARIANT_KEYS:
@@ -200,6 +204,8 @@ def test_every_lighting_kernel_same_bytes(monkeypatch, capfd, kind):
             names = KERNEL_LINE.findall(capfd.readouterr().err)
             assert names and all(int(n[6]) == LIT_FAMILIES[kind] for n in names), (case, env, names)
             seen.update(names)
+            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
+                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
             if first is None:
                 first = outs
                 assert all(u8.any() for u8, _ in outs)

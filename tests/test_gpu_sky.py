@@ -1,5 +1,5 @@
 """The sky on the GPU (rt_set_scene_sky, the sky kernels): every sky_* fixture through every entry point, all 56 sky kernels
-through the dispatcher's environment overrides with the same bytes, fixtures against restated scenes (no sky, a black sky, an
+through the dispatcher's environment overrides with the same bytes and the bytes of the CPU oracle's frames, fixtures against restated scenes (no sky, a black sky, an
 unreachable sun, the sun everywhere, a uniform sky over an empty scene, the sky turned upside down), frames in flight across a
 change of sky, column slabs, the error paths and the example."""
 import ctypes as C
@@ -16,6 +16,8 @@ from test_sky import CASES, load_sky, packed
 from test_lighting import fixture_textures, load_lighting
 from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
 from test_gpu_textures import _scene_textures
+from test_gpu_features_vs_oracle import _same
+from test_gpu_lit_vs_oracle import kernel_table_refs
 from test_gpu_lighting import IGNORED, KERNEL_LINE, LIT_FAMILIES, _check, _glossy, _kw, _mats, _render_host, _frames, _same_frames
 
 pytestmark = pytest.mark.gpu
@@ -130,7 +132,7 @@ SKY = packed(up=(0.0, 0.6, 0.8), zenith=(30.0, 80.0, 210.0), horizon=(230.0, 210
 
 
 @pytest.mark.parametrize("kind", list(SKY_FAMILIES))
-def test_every_sky_kernel_same_bytes(monkeypatch, capfd, kind):
+def test_every_sky_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
     import python_ray_tracer_amd as pkg
     from python_ray_tracer_amd import _lib as L
     soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
@@ -151,6 +153,8 @@ def test_every_sky_kernel_same_bytes(monkeypatch, capfd, kind):
         rgb = np.array([[1.0, 0.7, 0.4], [0.3, 0.5, 1.5], [0.0, 0.3, 0.2]][:NL], np.float32)
         tex = _scene_textures(src) if case != "tiny" else None    # (tiny: a sky scene without textures)
         rg = raygen_closed_form(w, h, float(src["fov"]))
+        refs = kernel_table_refs(oracle, src, w, h, modes, "sky", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
+                                 textures=tex, light_rgb=rgb, sky=SKY)
         first = plain = None
         for env in _VARIANTS[case]:
             for k in _VARIANT_KEYS:
@@ -178,6 +182,8 @@ def test_every_sky_kernel_same_bytes(monkeypatch, capfd, kind):
             names = KERNEL_LINE.findall(capfd.readouterr().err)
             assert names and all(int(n[6]) == SKY_FAMILIES[kind] for n in names), (case, env, names)
             seen.update(names)
+            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
+                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
             if first is None:
                 first = outs
                 assert all(u8.any() for u8, _ in outs)

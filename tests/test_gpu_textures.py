@@ -1,5 +1,6 @@
 """Textures on the GPU (rt_set_scene_textures, the texture kernels): every texture_* fixture through every entry point, the
-large fixtures on every traversal, all 56 texture kernels through the dispatcher's environment overrides with the same bytes,
+large fixtures on every traversal, all 56 texture kernels through the dispatcher's environment overrides with the same bytes and
+the bytes of the CPU oracle's frames (which restates the lookup: tests/test_gpu_lit_vs_oracle.py has its edges),
 uniform textures against the CPU oracle of the untextured scene (every kernel shape, random scenes, the scene sizes), depth 0
 per pixel against the oracle with the texel as the hit object's colour, ids -1 and T == 0 against rt_set_scene_area_lights,
 frames in flight across a scene change, column slabs, the error paths and the example."""
@@ -18,6 +19,7 @@ from conftest import REPO, load_frame, raygen_closed_form
 from test_textures import CASES, fixture_textures, load_texture
 from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
 from test_gpu_features_vs_oracle import _ENVS, _ENV_KEYS, _MODES, _family_scene, _oracle_modes, _same, _same_pixels
+from test_gpu_lit_vs_oracle import kernel_table_refs
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402
@@ -177,7 +179,7 @@ def _scene_textures(src):
 
 
 @pytest.mark.parametrize("kind", list(TEX_FAMILIES))
-def test_every_texture_kernel_same_bytes(monkeypatch, capfd, kind):
+def test_every_texture_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
     import python_ray_tracer_amd as pkg
     from python_ray_tracer_amd import _lib as L
     soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
@@ -196,6 +198,8 @@ def test_every_texture_kernel_same_bytes(monkeypatch, capfd, kind):
         radius = np.array([0.5, 0.0, 0.3][:NL], np.float32) if soft else np.zeros(NL, np.float32)
         tex = _scene_textures(src)
         rg = raygen_closed_form(w, h, float(src["fov"]))
+        refs = kernel_table_refs(oracle, src, w, h, modes, "textures", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
+                                 textures=tex)
         first = plain = None
         for env in _VARIANTS[case]:
             for k in _VARIANT_KEYS:
@@ -221,6 +225,8 @@ def test_every_texture_kernel_same_bytes(monkeypatch, capfd, kind):
             names = KERNEL_LINE.findall(capfd.readouterr().err)
             assert names and all(int(n[6]) == TEX_FAMILIES[kind] for n in names), (case, env, names)
             seen.update(names)
+            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
+                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
             if first is None:
                 first = outs
                 assert all(u8.any() for u8, _ in outs)

@@ -237,19 +237,21 @@ def test_fixture_is_self_consistent(case, oracle):
         assert len(g["tex_first"]) > 0
     size = os.path.getsize(os.path.join(GOLDEN, f"lighting_{case}.npz"))
     assert size <= os.path.getsize(os.path.join(GOLDEN, "lens_c4_s64_d5_sub32.npz")) and size < 1 << 20
-    # white lights and spec = 0: the CPU oracle's frame of the scene, every sampled pixel.  (The oracle has no textures: the two
-    # textured fixtures are recomputed by test_regenerate_sampled_pixels below.)
+    # white lights and spec = 0: the CPU oracle's frame of the scene, every sampled pixel, the two textured fixtures included
+    # (test_regenerate_sampled_pixels below recomputes them with the reference as well).
     assert (len(g["tex_first"]) > 0) == (case in TEXTURED)
-    if case not in TEXTURED:
-        pick = np.arange(n)
-        w, h = int(g["w"]), int(g["h"])
-        u8, _ = oracle.render_pixels(w, h, g["coords"][pick], g["cam_origin"], g["cam_rot"], g["spheres"], g["lights"], g["planes"],
-                                     0.0, 0.0, 0.0, int(g["depth"]), int(g["aa"]), raygen=raygen_closed_form(w, h, float(g["fov"])),
-                                     spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]),
-                                     materials=(np.ascontiguousarray(t[:, :6]), g["sphere_material"], g["plane_material"]),
-                                     light_radius=g["light_radius"], shadow_samples=int(g["shadow_samples"]),
-                                     lens=(float(g["aperture"]), float(g["focus_distance"])))
-        assert np.array_equal(u8, g["u8_plain"][pick])
+    tex = None
+    if case in TEXTURED:
+        tex = ([(g["tex_origin"][k], g["tex_axes"][k], g["tex_dims"][k], int(g["tex_first"][k])) for k in range(len(g["tex_first"]))],
+               g["sphere_texture"], g["plane_texture"], g["texels"])
+    w, h = int(g["w"]), int(g["h"])
+    u8, _ = oracle.render_pixels(w, h, g["coords"], g["cam_origin"], g["cam_rot"], g["spheres"], g["lights"], g["planes"],
+                                 0.0, 0.0, 0.0, int(g["depth"]), int(g["aa"]), raygen=raygen_closed_form(w, h, float(g["fov"])),
+                                 spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]),
+                                 materials=(np.ascontiguousarray(t[:, :6]), g["sphere_material"], g["plane_material"]),
+                                 light_radius=g["light_radius"], shadow_samples=int(g["shadow_samples"]),
+                                 lens=(float(g["aperture"]), float(g["focus_distance"])), textures=tex)
+    assert np.array_equal(u8, g["u8_plain"])
 
 
 from test_textures import REFERENCE  # noqa: E402  (where the reference checkout lies, as the texture test has it)

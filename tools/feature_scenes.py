@@ -1,13 +1,17 @@
 """TEST INFRASTRUCTURE ONLY — seeded random scenes with every feature of include/mi355rt.h (per-object materials, glass,
-rough surfaces, area lights, a thin lens), for tests/test_gpu_features_vs_oracle.py and the soak tools/fuzz_features.py.
+rough surfaces, area lights, a thin lens; with draw_lit also textures, coloured lights, highlights and a sky), for
+tests/test_gpu_features_vs_oracle.py, tests/test_gpu_lit_vs_oracle.py and the soak tools/fuzz_features.py.
 
 draw(seed) returns one scene as a dict; every key of it is plain data (numpy arrays and numbers).  Scenes are biased toward
 what the feature paths get wrong: cameras, lights and lens points inside glass spheres, touching and nested spheres, total
 internal reflection and grazing absorption, glass windows (transparent planes), negative ambient, refl = 1 at depth 16 and
 scales from 1e-3 to 1e3.
 
+draw_lit(seed) is draw(seed) with non-uniform textures, coloured lights, spec / shin columns and a sky added from a random
+stream of its own (draw(seed) itself never changes: the seed lists of the tests depend on it).
+
 oracle_kwargs(sc) / oracle_frame(orc, sc) give the CPU oracle's arguments and frame; strip(sc, what) the same scene with one
-feature turned off ("materials", "glass", "rough", "soft", "lens"), for the tests' liveness checks."""
+feature turned off ("materials", "glass", "rough", "soft", "lens", "textures", "lighting", "sky"), for the tests' liveness checks."""
 import numpy as np
 
 KINDS = ("plain", "touching", "camera_in_glass", "lens_in_glass", "light_in_glass", "tir", "grazing", "window", "mirror16",
@@ -123,9 +127,78 @@ def draw(seed, w=None, h=None, kind=None):
                 hseed=int(rng.integers(0, 2 ** 32)), typed=typed)
 
 
+SHININESS = tuple(float(1 << i) for i in range(11))
+SHARPNESS = (1.0, 2.0, 4.0, 8.0, 16.0)
+LIT = ("textures", "lighting", "sky")
+
+
+def _unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+
+
+def draw_lit(seed, w=None, h=None, kind=None):
+    """draw(seed, w, h, kind) plus, from a random stream of its own:
+      textures   1 to 4 records of random dimensions along up to three axes (non-uniform texels), skewed axes, texel ranges
+                 that overlap, most objects textured and some left at -1;
+      light_rgb  a colour times strength per light, zeros and values above 1 among them;
+      table      8 columns: spec 0 on some rows, shin through all eleven exponents over the seeds, and now and then lamb <= 0
+                 on the matte row with spec > 0;
+      sky        random unit up and sun_dir, every sharp over the seeds, the sun near the camera's forward axis so that some ray
+                 sees its disc."""
+    sc = draw(seed, w, h, kind)
+    rng = np.random.default_rng([int(seed), 0x11D])
+    S, P, NL = sc["spheres"].shape[1], sc["planes"].shape[1], sc["lights"].shape[1]
+    scale = float(sc["spheres"][3].mean()) / 0.7
+    # textures
+    T = int(rng.integers(1, 5))
+    recs, need = [], 0
+    for k in range(T):
+        dims = [int(rng.choice([2, 3, 5, 8])) if a < int(rng.integers(1, 4)) else 1 for a in range(3)]
+        rng.shuffle(dims)
+        recs.append([rng.uniform(-2, 2, 3) * scale, rng.normal(size=(3, 3)) * float(rng.choice([0.3, 2.0, 40.0])) / scale, tuple(dims), 0])
+        need = max(need, dims[0] * dims[1] * dims[2])
+    N = need + int(rng.integers(0, 24))
+    for r in recs:                                                 # shared texels: every range somewhere inside one short array
+        r[3] = int(rng.integers(0, N - r[2][0] * r[2][1] * r[2][2] + 1))
+    texels = rng.integers(0, 256, (N, 3)).astype(np.float32)
+    st = np.where(rng.uniform(size=S) < 0.7, rng.integers(0, T, S), -1).astype(np.int32)
+    pt = np.where(rng.uniform(size=P) < 0.85, rng.integers(0, T, P), -1).astype(np.int32)
+    st[0] = int(rng.integers(0, T))
+    if S > 1:
+        st[1] = -1
+    # lighting
+    rgb = (rng.uniform(0.0, 2.5, (NL, 3)) * (rng.uniform(size=(NL, 3)) < 0.8)).astype(np.float32)
+    rgb[0] = np.maximum(rgb[0], np.float32(0.4))                   # (the first light, the one with a radius, stays on)
+    if NL > 2 and rng.uniform() < 0.5:
+        rgb[NL - 1] = 0.0                                          # a black light among the coloured ones
+    t6 = np.asarray(sc["table"], np.float64)
+    table = np.zeros((len(t6), 8))
+    table[:, :6] = t6
+    table[:, 6] = rng.uniform(20.0, 300.0, len(t6)) * (rng.uniform(size=len(t6)) < 0.75)
+    table[:, 7] = [SHININESS[(int(seed) + 3 * i) % 11] for i in range(len(t6))]
+    table[0, 6] = float(rng.uniform(40.0, 200.0))
+    if rng.uniform() < 0.3:
+        table[0, 1] = float(rng.choice([0.0, -0.2]))               # lamb <= 0 with spec > 0
+    # the sky: the sun close to where the camera looks
+    fwd = np.asarray(sc["cam_rot"], np.float64)[:, 0]
+    sun = _unit(_unit(fwd) + rng.normal(size=3) * 0.25)
+    sky = np.zeros(24)
+    sky[0:3] = _unit(rng.normal(size=3) + np.array([0.0, 0.0, 1.5]))
+    sky[3:12] = rng.uniform(0.0, 255.0, 9)
+    sky[12] = SHARPNESS[int(seed) % 5]
+    sky[13:16] = sun
+    sky[16] = float(np.cos(np.radians(rng.uniform(3.0, 25.0))))
+    sky[17:20] = rng.uniform(50.0, 300.0, 3)
+    sky[20:23] = rng.uniform(0.0, 150.0, 3)
+    sky[23] = SHININESS[int(rng.integers(0, 11))]
+    sc.update(table=table, textures=([tuple(r) for r in recs], st, pt, texels), light_rgb=rgb, sky=sky)
+    return sc
+
+
 def strip(sc, what):
     """The same scene with one feature off: 'glass' (trans 0), 'rough' (rough 0), 'soft' (radii 0), 'lens' (aperture 0),
-    'materials' (one table row for every object)."""
+    'materials' (one table row for every object), 'textures' (none), 'lighting' (white lights and spec 0), 'sky' (none)."""
     sc = dict(sc)
     t = np.array(sc["table"])
     if what == "glass":
@@ -139,13 +212,27 @@ def strip(sc, what):
     elif what == "materials":
         sc["sid"] = np.zeros_like(sc["sid"])
         sc["pid"] = np.zeros_like(sc["pid"])
+    elif what == "textures":
+        sc["textures"] = None
+    elif what == "lighting":
+        sc["light_rgb"] = None
+        if t.shape[1] == 8:
+            t[:, 6] = 0.0
+    elif what == "sky":
+        sc["sky"] = None
     sc["table"] = t
     return sc
 
 
+def _lit_kwargs(sc):
+    """The textures=, light_rgb= and sky= keywords of a draw_lit scene; none for a scene of draw(), whose calls stay as they were."""
+    return {k: sc[k] for k in ("textures", "light_rgb", "sky") if sc.get(k) is not None}
+
+
 def oracle_kwargs(sc):
     return dict(raygen=sc["raygen"], flags=int(sc["typed"]), spp=sc["spp"], seed=sc["hseed"],
-                materials=(sc["table"], sc["sid"], sc["pid"]), light_radius=sc["radius"], shadow_samples=sc["n"], lens=sc["lens"])
+                materials=(sc["table"], sc["sid"], sc["pid"]), light_radius=sc["radius"], shadow_samples=sc["n"], lens=sc["lens"],
+                **_lit_kwargs(sc))
 
 
 def oracle_frame(orc, sc, **kw):
@@ -155,10 +242,16 @@ def oracle_frame(orc, sc, **kw):
     return ref["u8"], ref["f32"]
 
 
+def oracle_pixels(orc, sc, coords, **kw):
+    """The oracle's (u8 (n,3) in stored order, f64 (n,3)) at the sampled pixels coords (n,2) of the scene's frame."""
+    return orc.render_pixels(sc["w"], sc["h"], coords, sc["cam_origin"], sc["cam_rot"], sc["spheres"], sc["lights"], sc["planes"],
+                             0.0, 0.0, 0.0, sc["depth"], sc["aa"], **{**oracle_kwargs(sc), **kw})
+
+
 def gpu_frame(r, sc, **kw):
     """The library's frames for the scene on Renderer r (scene, camera, lens and grid set here)."""
     r.set_scene(sc["spheres"], sc["lights"], sc["planes"], flags=int(sc["typed"]), materials=(sc["table"], sc["sid"], sc["pid"]),
-                light_radius=sc["radius"], shadow_samples=sc["n"])
+                light_radius=sc["radius"], shadow_samples=sc["n"], **_lit_kwargs(sc))
     r.set_camera(sc["cam_origin"], sc["cam_rot"])
     r.set_lens(*sc["lens"])
     r.set_raygen(sc["w"], sc["h"], *sc["raygen"])
@@ -171,7 +264,8 @@ def live(orc, sc, u8=None):
     if u8 is None:
         u8 = oracle_frame(orc, sc)[0]
     out = {}
-    for what in ("materials", "glass", "rough", "soft", "lens"):
+    for what in ("materials", "glass", "rough", "soft", "lens") + tuple(k for k in LIT if sc.get("textures" if k == "textures" else
+                                                                                                 ("light_rgb" if k == "lighting" else "sky")) is not None):
         o8 = oracle_frame(orc, strip(sc, what))[0]
         out[what] = int((o8 != u8).any(axis=0).sum())
     return out
