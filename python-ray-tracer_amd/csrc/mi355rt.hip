@@ -4,6 +4,7 @@
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_geometry.h"
+#include "rt_plan.h"
 #include "rt_scene.h"
 
 #include <cmath>
@@ -43,20 +44,10 @@ struct rt_ctx {
     hipStream_t chunk_stream[RT_RENDER_CHUNKS] = {};
     int chunk_mode = -1;              // -1 = by destination memory type
     int cluster_min = rt::CLUSTER_MIN;            // scenes with more spheres are stored in clusters (MI355RT_CLUSTER_MINS overrides)
-    int lanes_primary = 1, lanes_min_spheres = 161;   // MI355RT_LANES_MINS: the lane-owned traversal from that size on; MI355RT_LANES_PRIMARY=0: from bounce 1 on only
-                                                      // (primary rays and their shadow rays wave-uniform: +2..3 % since the group level exists)
+    int lanes_primary = 1;            // MI355RT_LANES_PRIMARY=0: the lane-owned traversal from bounce 1 on only (primary rays and their shadow
+                                      // rays wave-uniform: +2..3 % since the group level exists)
+    rt::PlanKnobs knobs;              // what steers the choice of a launch's kernel and order shape (rt_plan.h)
     int render_chunks = 4;            // MI355RT_CHUNKS overrides (1 = one launch, one copy)
-    int order_group = -1;             // MI355RT_ORDER_GROUP: log2 of the blocks per XCD-affine dispatch group (0..6; 0 = every block on its
-                                      // own; default -1 = groups of 16 tiles)
-    int seq_order = -1;               // MI355RT_SEQ_ORDER: 1 / 0 = all but the last frame of a multi-frame launch in the XCD's tile order / every
-                                      // frame longest-first; default -1 = tile order for the two-wave kernels (small flat scenes: headline
-                                      // 0.1050 ms either way, writes 31.8 instead of 38.7 MB per frame), longest-first for the four-wave ones
-                                      // (config 4: 0.734 against 0.785 ms — runs of cheap sky tiles starve the dispatcher in tile order)
-    int f32_records = 1;              // MI355RT_F32_RECORDS: four-wave wave-uniform kernels keep no float64 sphere records in LDS (MODE 1)
-    size_t wpw2_max_image = 4608;     // MI355RT_WPW2_MAX_IMAGE: flat scenes whose LDS image is at most this many bytes run two-wave workgroups
-    int order_tiles = 1;              // MI355RT_ORDER_TILES=0: the four-wave kernels' dispatch order per block of four neighbouring tiles (A/B)
-    int lanes_park = 1;               // MI355RT_LANES_PARK=0: register variants of the lane-owned kernels (A/B; with workgroups of equal-cost tiles the
-                                      // parked variants win: config 5 6.88 against 7.16 ms — with neighbouring tiles they lost, 8.20 against 7.95)
     int log_kernels = 0;              // MI355RT_LOG_KERNELS=1: every render launch names its kernel on stderr (its shape and family number)
     int remeasure = 24;               // MI355RT_REMEASURE: launches a dispatch order measured under an older camera is kept for before
                                       // the tile costs are measured again (a moving camera; any order renders the same frame)
@@ -187,86 +178,7 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
     return RT_OK;
 }
 
-// The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
-// have.  From the scene (rt::SceneLayout: M materials in a table of mat_cols columns, soft_n shadow samples per light, ...) and the
-// lens aperture.
-rt::Family family_of(const rt::SceneLayout &s, double lens_a)
-{
-    using F = rt::Family;
-    const bool lens = lens_a > 0.0, soft = s.soft_n > 0;
-    if (s.M <= 0) return F::PLAIN;
-    if (s.sky)                                                       // (rt_scene.h: a sky only with M >= 1; it sets lit too)
-        return lens ? (soft ? F::SKY_LENS_SOFT : F::SKY_LENS) : (soft ? F::SKY_SOFT : F::SKY_SCAT);
-    if (s.lit)                                                       // (rt_scene.h: lit only with M >= 1; textured or not)
-        return lens ? (soft ? F::LIT_LENS_SOFT : F::LIT_LENS) : (soft ? F::LIT_SOFT : F::LIT_SCAT);
-    if (s.T > 0)                                                     // (rt_scene.h: T > 0 only with a textured object, and M >= 1)
-        return lens ? (soft ? F::TEX_LENS_SOFT : F::TEX_LENS) : (soft ? F::TEX_SOFT : F::TEX_SCAT);
-    if (lens) return soft ? F::LENS_SOFT : F::LENS;                  // (check_params: a lens needs a material table)
-    return rt::block_family(s.M, s.mat_cols, soft);                  // SOFT, SCAT, REFR or MAT: the family of the scene's own material block
-}
-
-// The shape of a launch (dispatch()): render_kernel's first six template arguments.
-struct Shape {
-    bool aa, park;
-    int wpw;
-    bool count, lat;
-    int mode;    // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS; 2: lane-owned traversal; 3: its AA + parked variant
-    constexpr bool operator==(const Shape &o) const
-    {
-        return aa == o.aa && park == o.park && wpw == o.wpw && count == o.count && lat == o.lat && mode == o.mode;
-    }
-};
-
-// Every shape dispatch() can produce.
-constexpr Shape SHAPES[] = {
-    // wave-uniform cull, workgroups of 2 or 4 (flat scenes up to rt::CLUSTER_MIN spheres may take 2), with AA or without, register
-    // or parked variant; MODE 1: workgroups of 4 without AA that keep no float64 sphere records in LDS (rt_device.h: sphere_hot)
-    {false, false, 2, false, false, 0}, {false, true, 2, false, false, 0}, {true, false, 2, false, false, 0}, {true, true, 2, false, false, 0},
-    {false, false, 4, false, false, 0}, {false, true, 4, false, false, 0}, {true, false, 4, false, false, 0}, {true, true, 4, false, false, 0},
-    {false, false, 4, false, false, 1}, {false, true, 4, false, false, 1},
-    // the same over the half-pixel lattice (RT_AA_REFERENCE on the closed-form grid: no AA of their own)
-    {false, false, 2, false, true, 0}, {false, true, 2, false, true, 0}, {false, false, 4, false, true, 0}, {false, true, 4, false, true, 0},
-    {false, false, 4, false, true, 1}, {false, true, 4, false, true, 1},
-    // lane-owned traversal (MODE 2, clustered scenes from lanes_min_spheres spheres on), workgroups of 4; with AA and parked: MODE 3
-    {false, false, 4, false, false, 2}, {false, true, 4, false, false, 2}, {true, false, 4, false, false, 2}, {true, true, 4, false, false, 3},
-    {false, false, 4, false, true, 2}, {false, true, 4, false, true, 2},
-    // rt_get_stats: the register variants with workgroups of 4 carry the ray counters
-    {false, false, 4, true, false, 0}, {true, false, 4, true, false, 0}, {false, false, 4, true, true, 0},
-};
-constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
-
-// A family has one render kernel per shape, except
-//  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
-//  * the parked wave-uniform shapes (MODE 0 and 1) from REFR on, which the parking rule never picks (the static_assert below).
-// So PLAIN has 25 kernels, MAT 22 and every later family (the four texture, the four lighting and the four sky families included) 14.  Nothing else names a render kernel of a family other than
-// PLAIN, so the kernels a family does not have are not compiled.
-constexpr bool has_kernel(rt::Family f, const Shape &s)
-{
-    return (!s.count || f == rt::Family::PLAIN) && !(rt::has_refr(f) && s.park && s.mode < 2);
-}
-
-// The parking rule of the wave-uniform kernels (dispatch()): their state parks in LDS while PARK_WAVES wavefronts per CU still
-// fit their workgroups' LDS images.
-constexpr int PARK_WAVES = 24;
-constexpr size_t CU_LDS = 160 * 1024;
-
-// A kernel a family does not have (counting kernels aside) is one that no scene lets park: its per-thread slots, pixel offsets
-// and workgroup words alone (rt::lds_bytes of an empty scene) take more than CU_LDS at PARK_WAVES wavefronts.  For REFR without
-// AA that is 13 slots: 13 840 B x 12 workgroups of 2 = 166 080 B and 27 664 B x 6 workgroups of 4 = 165 984 B against 163 840 B.
-constexpr bool missing_kernels_never_park()
-{
-    for (int fi = 0; fi < rt::FAMILIES; ++fi)
-        for (const Shape &s : SHAPES) {
-            const rt::Family f = (rt::Family)fi;
-            if (s.count || has_kernel(f, s)) continue;
-            const size_t wgt = 64 * s.wpw;
-            const size_t least = rt::lds_slots(s.aa, true, s.mode >= 2, f) * wgt * sizeof(double) +
-                                 wgt * sizeof(int) + 16;
-            if (!s.park || s.mode >= 2 || least * (PARK_WAVES / s.wpw) <= CU_LDS) return false;
-        }
-    return true;
-}
-static_assert(missing_kernels_never_park(), "the parking rule can pick a render kernel that is not compiled");
+using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel;
 
 template <rt::Family F, int I>
 const void *kernel_at()
@@ -300,13 +212,6 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
 static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14 &&
               (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
               "KERNELS lists the families in enum order");
-
-const void *kernel_of(rt::Family f, const Shape &s)
-{
-    for (int i = 0; i < NSHAPES; ++i)
-        if (SHAPES[i] == s) return KERNELS[(int)f][i];
-    return nullptr;
-}
 
 // The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
 int acquire_tables(rt_ctx *ctx, const rt::KParams &k, hipStream_t stream, const float **out)
@@ -345,7 +250,7 @@ int acquire_tables(rt_ctx *ctx, const rt::KParams &k, hipStream_t stream, const 
     return RT_OK;
 }
 
-int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride);
+int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPlan &plan, hipStream_t stream, int nframes, int64_t frame_stride);
 
 // The lattice buffer of a stream (RT_AA_REFERENCE with the closed-form grid renders the half-pixel lattice once into
 // float64 samples, then sums nine of them per pixel): one buffer per launching stream, so that frames in flight on
@@ -395,9 +300,18 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
     k.amb = p->amb; k.lamb = p->lamb;
     std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
+    // (RT_AA_REFERENCE on the closed-form grid renders the half-pixel lattice, below: lattice columns [li0, li1))
+    long long li0 = 0, li1 = 0;
+    const bool lattice = k.aa == RT_AA_REFERENCE && !ctx->explicit_grid && rt_geo_lattice(ctx->w, ctx->h, x0, x1, &li0, &li1) &&
+                         !(p->flags & RT_FLAG_AA_PER_PIXEL);
+    // the launch's family, kernel and LDS size (rt_plan.h), decided once: every slab and frame of the launch runs the same kernel
+    k.anchors = rt::anchors_of(ctx->lay);
+    const rt::LaunchPlan plan = rt::plan_launch(ctx->lay, ctx->knobs, ctx->lens_a, !lattice && k.aa != 0, p->flags, lattice, k.anchors);
+    if (plan.index < 0 || !KERNELS[(int)plan.family][plan.index])
+        return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: rt_plan.h, missing_kernels_never_park)
     // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
     // the lens travels in its place, by value with this launch
-    const rt::Family lfam = family_of(ctx->lay, ctx->lens_a);
+    const rt::Family lfam = plan.family;
     const bool lens = rt::has_lens(lfam);
     if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lay.lens_mat; }
     // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
@@ -406,9 +320,6 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     if (rt::has_lit(lfam)) k.lens.lit = ctx->lay.lit_off;                // (the lighting kernels are texture kernels: the above too)
     if (rt::has_sky(lfam)) k.lens.sky = ctx->lay.sky_off;                // (and the sky kernels lighting kernels)
 
-    // anchored cull table (camera + one anchor per light) if it fits its LDS budget, else origin-form culling only
-    const size_t table = (size_t)(ctx->lay.L + 1) * (rt::padS(ctx->lay.S, ctx->lay.NC) + rt::pad4(ctx->lay.NC)) * rt::CULL_STRIDE * sizeof(float);
-    k.anchors = (table <= (size_t)rt::MAX_CULL_TABLE_BYTES) ? ctx->lay.L + 1 : 0;
     double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
     if (lens) { const double e = std::sqrt(cam2) + ctx->lens_a; cam2 = e * e; }   // (primary rays start on the lens, |L - cam| <= a)
     k.extent2 = (float)(1.0001 * (cam2 > ctx->lay.extent2 ? cam2 : ctx->lay.extent2));
@@ -428,9 +339,7 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     // the reference's order (kernels.py:53-65, including its G/B swap).  Explicit pixel_loc grids are not separable
     // in general and keep the nine-taps-per-pixel kernel.
     const long long LW = 2ll * ctx->w - 1, LH = 2ll * ctx->h - 1;
-    long long li0 = 0, li1 = 0;                                 // lattice columns [li0, li1)
-    if (k.aa == RT_AA_REFERENCE && !ctx->explicit_grid && rt_geo_lattice(ctx->w, ctx->h, x0, x1, &li0, &li1) &&
-        !(p->flags & RT_FLAG_AA_PER_PIXEL)) {
+    if (lattice) {
         double *lat = nullptr;
         int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0) * (size_t)LH * 3 * sizeof(double), &lat);
         if (rc != RT_OK) return rc;
@@ -442,7 +351,7 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
         k.out_f64 = lat; k.lat_x0 = (int)li0; k.lat_h = (int)LH;
         const long long npx = (long long)(x1 - x0) * ctx->h;
         for (int f = 0; f < nframes; ++f) {                    // the stream's one lattice buffer serves the frames in turn
-            rc = dispatch(ctx, p, kl, lfam, true, stream, 1, 0);
+            rc = dispatch(ctx, p, kl, plan, stream, 1, 0);
             if (rc != RT_OK) return rc;
             rt::KParams kf = k;
             if (kf.out_u8) kf.out_u8 += (size_t)f * frame_stride;
@@ -452,74 +361,36 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
         }
         return RT_OK;
     }
-    return dispatch(ctx, p, k, lfam, false, stream, nframes, frame_stride);
+    return dispatch(ctx, p, k, plan, stream, nframes, frame_stride);
 }
 
-// Chooses the kernel instantiation and the dispatch order for one launch of the render kernel over the tiles k
-// describes, and launches it.
-int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bool lattice, hipStream_t stream, int nframes, int64_t frame_stride)
+using Feedback = rt_ctx::Feedback;
+int feedback_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out);
+int switch_order(rt_ctx *ctx, Feedback &f);
+int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt_geo_plan &g, const rt::OrderShape &os,
+               Feedback &f, hipStream_t stream, int nframes, int64_t frame_stride);
+
+// An order built for this launch geometry is a valid permutation whatever has happened to scene and camera since: only
+// how well it balances the end of the launch depends on them.
+//  * Nothing that decides a tile's cost has changed since the order was rebuilt twice (once from plain tile order, once
+//    from longest-first order): the costs are the same again, so launches neither measure nor rebuild — they dispatch
+//    in that order, on any stream.
+//  * Something has changed (rt_set_* bumped the epoch — a moving camera does so with every frame): launches still
+//    dispatch in the order there is, and only every `remeasure`-th of them measures its tiles again (under that order)
+//    and rebuilds.  Round 2 measured and rebuilt with every frame of a moving camera: +11 us per frame.
+bool order_settled(const rt_ctx *ctx, const Feedback &f)
+{
+    return f.have && (f.epoch == ctx->epoch ? f.builds >= 2 : f.since < ctx->remeasure);
+}
+
+// One launch of the planned kernel over the tiles k describes, cut into pieces that one dispatch holds and one dispatch order
+// serves; each piece finds its feedback slot, switches to a finished order and goes out (launch_one).
+int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPlan &plan, hipStream_t stream, int nframes, int64_t frame_stride)
 {
     const int x0 = k.x0, x1 = k.x1;
-    // Workgroup size: 2 tiles (wavefronts) for scenes whose LDS image (records + cull tables) is small, 4 otherwise
-    // (every workgroup stages its own copy; rt_device.h has the measurements).
-    // Kernel variant: state parked in LDS (7 waves/SIMD, no scratch) while at least PARK_WAVES wavefronts per CU still
-    // fit their workgroups' LDS images; otherwise the register variant (its occupancy is then LDS-bound anyway).
-    // The kernel is the family's of the launch's shape (kernel_of).
-    const bool aa = k.aa != 0;
-    const bool count = (p->flags & RT_FLAG_COUNT_RAYS) != 0;
-    const size_t image = rt::lds_doubles(ctx->lay.S, ctx->lay.P, ctx->lay.L) * sizeof(double) + rt::table_floats(ctx->lay.S, ctx->lay.NC, k.anchors) * sizeof(float);
-    // Scenes with more than rt::CLUSTER_MIN spheres are clustered (rt_set_scene) and culled cluster by cluster; from 161
-    // spheres on with the lane-owned traversal and its groups of clusters (rt_device.h, MODE 2; compiled for 128 VGPRs,
-    // 4 waves/SIMD).  Measured against the plain wave-uniform cull of the same clusters
-    // (profiles/r02_variant_thresholds.txt): 256 spheres -25 %, 196 spheres -4 % (depth 3) .. -9 % (depth 8), 169 -8 %,
-    // but 144 +6 %, 100 +17 %.
-    // (Round 2's bundle pre-cull, MODE 1/3, lost against these clusters at every measured size and was removed in round 3:
-    // profiles/r02_variant_thresholds.txt.)
-    const bool lanes = ctx->lay.NC > 0 && ctx->lay.S >= ctx->lanes_min_spheres && !count && !(p->flags & RT_FLAG_NO_BUNDLES);
-    const int wpw = (image <= ctx->wpw2_max_image && !count && ctx->lay.NC == 0) ? 2 : 4;   // flat scenes only (up to rt::CLUSTER_MIN spheres); measured at 1080p, depth 3 on flat scenes: 2 wins up to 25 spheres (4.1 KB), 4 from 36 (5.4 KB)
-    const int wgt = 64 * wpw;
-    const bool ltab = lanes && k.anchors > 0;                     // lane-owned kernels with anchored tables leave the clusters' origin-form spheres out of LDS
-    // MODE 1 (wave-uniform cull, four-wave workgroups, no float64 sphere records in LDS: sphere_hot widens the float32 table
-    // and a hit's colour comes from global memory) where the smaller image lets a CU hold one workgroup more — the parked
-    // variant runs 7 per CU if they fit and needs 6, the register variant 5.  Config 4 (64 spheres): 6 -> 7 workgroups, -5 %;
-    // 100 spheres: register variant at 5 -> parked at 6, -7 %; where the count stays (36, 49, 144 spheres) it costs 0...2 %
-    // (four conversions per sphere test), and the AA kernels lose 1.5 % with it: those keep MODE 0.
-    // The feature family (fam: launch() derives it from the scene and the lens) picks the twins of these variants: their LDS images hold the material block too
-    // (rt::mat_doubles: rows of rt::table_cols, the lens kernels' from rt::SceneLayout::lens_mat), and their parked variants the
-    // family's per-thread slots (rt::lds_slots).
-    auto per_cu = [&](bool nr) {
-        const size_t lp = rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, true, wgt, ltab, lanes, nr, fam, ctx->lay.M);
-        if (lp * 6 <= CU_LDS) return (int)std::min<size_t>(7, CU_LDS / lp);
-        return (int)std::min<size_t>(5, CU_LDS / rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, false, wgt, ltab, lanes, nr, fam, ctx->lay.M));
-    };
-    const bool norec = !lanes && !count && !aa && wpw == 4 && ctx->f32_records && per_cu(true) > per_cu(false);
-    const size_t lds_park = rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, true, wgt, ltab, lanes, norec, fam, ctx->lay.M);
-    // (lane-owned kernels are compiled for 4 waves per SIMD = 4 workgroups per CU: parked state while those still fit)
-    const bool park = !count && (lanes ? (lds_park * RT_W_LANES <= CU_LDS && ctx->lanes_park) : lds_park * (PARK_WAVES / wpw) <= CU_LDS);
-    const size_t lds = park ? lds_park : rt::lds_bytes(ctx->lay.S, ctx->lay.P, ctx->lay.L, ctx->lay.NC, k.anchors, aa, false, wgt, ltab, lanes, norec, fam, ctx->lay.M);
-    const void *fn = kernel_of(fam, Shape{aa, park, wpw, count, lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0)});
-    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: missing_kernels_never_park)
-    if (ctx->log_kernels)
-        std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>\n", (int)aa, (int)park, wpw, (int)count,
-                     (int)lattice, lanes ? (aa && park ? 3 : 2) : (norec ? 1 : 0), (int)fam);
-    // more than the default 48 KiB of dynamic LDS: raised on all of the family's kernels at once
-    const int fi = (int)fam;
-    if (lds > 48 * 1024 && lds > ctx->lds_limit_set[fi]) {
-        for (const void *kf : KERNELS[fi])
-            if (kf) RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->lds_limit_set[fi] = lds;
-    }
-    if (count) {
-        if (!ctx->counts.p) {
-            int rc0 = ensure(ctx, ctx->counts, RT_COUNT_WORDS * sizeof(unsigned long long));
-            if (rc0 != RT_OK) return rc0;
-            RT_HIP(ctx, hipMemsetAsync(ctx->counts.p, 0, RT_COUNT_WORDS * sizeof(unsigned long long), stream));
-        }
-        k.ray_counts = (unsigned long long *)ctx->counts.p;
-    }
     // At most RT_GEO_MAX_ITEMS work-items per dispatch (rt_geometry.h): a frame beyond that alone goes out as column slabs
     // (they assemble bit-identically), one dispatch each; a sequence as batches of frames.
-    const rt_geo_plan g = rt_geo_plan_of(x0, x1, k.h, wpw, nframes);
+    const rt_geo_plan g = rt_geo_plan_of(x0, x1, k.h, plan.shape.wpw, nframes);
     auto frame_of = [&](int fr) { rt::KParams kf = k; if (kf.out_u8) kf.out_u8 += (size_t)fr * frame_stride; if (kf.out_f32) kf.out_f32 += (size_t)fr * frame_stride; return kf; };
     if (g.nslabs > 1) {
         for (int fr = 0; fr < nframes; ++fr)
@@ -532,106 +403,141 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bo
                 if (kf.out_f32) kf.out_f32 += dx * k.h;
                 if (kf.out_f64) kf.out_f64 += 3 * dx * k.h;                      // (lattice samples, [column - x0][row][3])
                 if (kf.tile_cycles) kf.tile_cycles += dx / rt::TILE * k.tiles_y;
-                int rc = dispatch(ctx, p, kf, fam, lattice, stream, 1, 0);
+                int rc = dispatch(ctx, p, kf, plan, stream, 1, 0);
                 if (rc != RT_OK) return rc;
             }
         return RT_OK;
     }
-    const unsigned grid = (unsigned)g.blocks;
-    // Scheduler feedback (longest-first dispatch): a launch files its tile blocks by cost and dispatches in the
-    // order built from the previous measured launch of the same range, depth and AA mode.
-    // RT_FLAG_NO_FEEDBACK renders in plain tile order.  Any order renders every tile exactly once.
-    const bool feedback = !(p->flags & RT_FLAG_NO_FEEDBACK) && grid > 1 && grid < (1u << 20);
-    // XCD-affine block groups (rt::order_kernel): runs of 2^gshift consecutive blocks (neighbours in y, which share 128-byte
-    // lines of the output planes) are rendered by ONE XCD, so that its L2 completes those lines before they leave for HBM;
-    // inside every XCD the order is block-level longest-first.  Default: groups of 16 tiles.  MI355RT_ORDER_GROUP overrides
-    // (0 = every block on its own: round 2's order, 1.39x the algorithmic write traffic on the headline frame).
-    const int gshift = ctx->order_group >= 0 ? ctx->order_group : (wpw == 2 ? 3 : 2);
-    // Four-wave kernels: the order's items are TILES, not blocks of four neighbouring tiles (rt_device.h: KParams::order_tiles) —
-    // a workgroup's four waves are then tiles of equal cost, end together and free their slots together.
-    const bool otiles = wpw >= rt::TILE_ORDER_MIN_WPW && ctx->order_tiles && feedback;
-    const int wshift = wpw == 4 ? 2 : 1;
-    const unsigned items = otiles ? grid * (unsigned)wpw : grid;          // entries of one permutation
-    rt_ctx::Feedback::Key key;
-    key.valid = true; key.x0 = x0; key.x1 = x1; key.h = k.h; key.aa = lattice ? 3 : k.aa; key.depth = k.depth;
-    key.spp = (k.aa == RT_AA_STOCHASTIC) ? k.spp : 0; key.wpw = wpw + (lanes ? 32 : 0) + (otiles ? 64 : 0);
-    rt_ctx::Feedback *fsel = nullptr;
-    for (auto &c : ctx->fbs) if (c.key == key) { fsel = &c; break; }
-    if (!fsel && feedback) {                                   // a free slot, else the least recently used geometry
-        for (auto &c : ctx->fbs) if (!fsel || (!c.key.valid && fsel->key.valid) || (c.key.valid == fsel->key.valid && c.stamp < fsel->stamp)) fsel = &c;
-        if (fsel->key.valid) RT_HIP(ctx, hipDeviceSynchronize());   // launches of the evicted geometry may still read its orders (rare: > 8 geometries)
-        for (auto &e : fsel->fence) fsel->spare.push_back(e.second);
-        fsel->fence.clear(); fsel->users.clear();
-        fsel->have = fsel->building = false; fsel->builds = 0; fsel->since = 0; fsel->cur = 0;
-        fsel->key = key;
-    }
-    static rt_ctx::Feedback none;                              // RT_FLAG_NO_FEEDBACK / one-block launches: no order, no measuring
-    rt_ctx::Feedback &f = (feedback && fsel) ? *fsel : none;
-    if (feedback) f.stamp = ++ctx->fb_stamp;
-    if (feedback && !f.done) RT_HIP(ctx, hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
-    // the order being built is complete: switch to it.  Launches queued so far on the streams that used the old order may
-    // still read it; an event per such stream, recorded now, is what the measurement after next waits for before it
-    // overwrites that buffer.
-    if (feedback && f.building) {
-        const hipError_t q = hipEventQuery(f.done);
-        if (q == hipSuccess) {
-            f.cur ^= 1;
-            f.have = true;
-            f.building = false;
-            f.builds = (f.build_epoch == f.epoch) ? f.builds + 1 : 1;
-            f.epoch = f.build_epoch;
-            for (auto &e : f.fence) f.spare.push_back(e.second);
-            f.fence.clear();
-            for (hipStream_t us : f.users) {
-                hipEvent_t ev = nullptr;
-                if (!f.spare.empty()) { ev = f.spare.back(); f.spare.pop_back(); }
-                else RT_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                RT_HIP(ctx, hipEventRecord(ev, us));
-                f.fence.emplace_back(us, ev);
-            }
-            f.users.clear();
-        } else (void)hipGetLastError();                        // hipErrorNotReady is an answer, not a failure
-    }
-    // An order built for this launch geometry is a valid permutation whatever has happened to scene and camera since: only
-    // how well it balances the end of the launch depends on them.
-    //  * Nothing that decides a tile's cost has changed since the order was rebuilt twice (once from plain tile order, once
-    //    from longest-first order): the costs are the same again, so launches neither measure nor rebuild — they dispatch
-    //    in that order, on any stream.
-    //  * Something has changed (rt_set_* bumped the epoch — a moving camera does so with every frame): launches still
-    //    dispatch in the order there is, and only every `remeasure`-th of them measures its tiles again (under that order)
-    //    and rebuilds.  Round 2 measured and rebuilt with every frame of a moving camera: +11 us per frame.
-    const bool same_epoch = f.epoch == ctx->epoch;
-    const bool settled = feedback && f.have && (same_epoch ? f.builds >= 2 : f.since < ctx->remeasure);
-    // A launch of several frames (rt_render_sequence) is ONE launch only in a settled order; until then its frames go
-    // through this function one by one (a measuring launch stores the costs of one frame).
     if (nframes > g.frames_per_dispatch) {                    // (more work-items than one dispatch holds: batches of frames)
         const int fpd = (int)g.frames_per_dispatch;
         for (int fr = 0; fr < nframes; fr += fpd) {
             rt::KParams kf = frame_of(fr);
-            int rc = dispatch(ctx, p, kf, fam, lattice, stream, std::min(fpd, nframes - fr), frame_stride);
+            int rc = dispatch(ctx, p, kf, plan, stream, std::min(fpd, nframes - fr), frame_stride);
             if (rc != RT_OK) return rc;
         }
         return RT_OK;
     }
-    if (nframes > 1 && feedback && !settled) {
+    const rt::OrderShape os = rt::order_shape(plan, ctx->knobs, p->flags, g);
+    static Feedback none;                                      // RT_FLAG_NO_FEEDBACK / one-block launches: no order, no measuring
+    Feedback *f = &none;
+    if (os.feedback) {
+        Feedback::Key key;
+        key.valid = true; key.x0 = x0; key.x1 = x1; key.h = k.h; key.aa = plan.shape.lat ? 3 : k.aa; key.depth = k.depth;
+        key.spp = (k.aa == RT_AA_STOCHASTIC) ? k.spp : 0; key.wpw = os.code;
+        int rc = feedback_slot(ctx, key, &f);
+        if (rc == RT_OK) rc = switch_order(ctx, *f);
+        if (rc != RT_OK) return rc;
+    }
+    // A launch of several frames (rt_render_sequence) is ONE launch only in a settled order; until then its frames go
+    // through this function one by one (a measuring launch stores the costs of one frame).
+    if (nframes > 1 && os.feedback && !order_settled(ctx, *f)) {
         // the first frame on its own (it measures, if no measurement is in flight), then — rather than rendering more
         // frames singly while the order is being built — wait for the build (a fraction of a millisecond, twice per new
         // geometry) and hand the rest back: at most two single frames before whole batches go out in the settled order
         rt::KParams kf = frame_of(0);
-        int rc = dispatch(ctx, p, kf, fam, lattice, stream, 1, 0);
+        int rc = dispatch(ctx, p, kf, plan, stream, 1, 0);
         if (rc != RT_OK) return rc;
-        if (f.building) RT_HIP(ctx, hipEventSynchronize(f.done));
+        if (f->building) RT_HIP(ctx, hipEventSynchronize(f->done));
         rt::KParams kr = frame_of(1);
-        return dispatch(ctx, p, kr, fam, lattice, stream, nframes - 1, frame_stride);
+        return dispatch(ctx, p, kr, plan, stream, nframes - 1, frame_stride);
     }
-    const bool measure = feedback && !settled && !f.building;  // one measurement in flight at a time (one cost buffer)
+    return launch_one(ctx, k, plan, g, os, *f, stream, nframes, frame_stride);
+}
+
+// The feedback slot of a launch geometry none of the slots holds: a free slot, else the least recently used geometry's.
+int evict_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out)
+{
+    Feedback *fsel = nullptr;
+    for (auto &c : ctx->fbs) if (!fsel || (!c.key.valid && fsel->key.valid) || (c.key.valid == fsel->key.valid && c.stamp < fsel->stamp)) fsel = &c;
+    if (fsel->key.valid) RT_HIP(ctx, hipDeviceSynchronize());   // launches of the evicted geometry may still read its orders (rare: > 8 geometries)
+    for (auto &e : fsel->fence) fsel->spare.push_back(e.second);
+    fsel->fence.clear(); fsel->users.clear();
+    fsel->have = fsel->building = false; fsel->builds = 0; fsel->since = 0; fsel->cur = 0;
+    fsel->key = key;
+    *out = fsel;
+    return RT_OK;
+}
+
+// The feedback slot of a launch geometry: the one that holds it, else evict_slot's.
+int feedback_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out)
+{
+    Feedback *f = nullptr;
+    for (auto &c : ctx->fbs) if (c.key == key) { f = &c; break; }
+    if (!f) {
+        int rc = evict_slot(ctx, key, &f);
+        if (rc != RT_OK) return rc;
+    }
+    f->stamp = ++ctx->fb_stamp;
+    if (!f->done) RT_HIP(ctx, hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
+    *out = f;
+    return RT_OK;
+}
+
+// the order being built is complete: switch to it.  Launches queued so far on the streams that used the old order may
+// still read it; an event per such stream, recorded now, is what the measurement after next waits for before it
+// overwrites that buffer.
+int switch_order(rt_ctx *ctx, Feedback &f)
+{
+    if (!f.building) return RT_OK;
+    const hipError_t q = hipEventQuery(f.done);
+    if (q != hipSuccess) {
+        (void)hipGetLastError();                               // hipErrorNotReady is an answer, not a failure
+        return RT_OK;
+    }
+    f.cur ^= 1;
+    f.have = true;
+    f.building = false;
+    f.builds = (f.build_epoch == f.epoch) ? f.builds + 1 : 1;
+    f.epoch = f.build_epoch;
+    for (auto &e : f.fence) f.spare.push_back(e.second);
+    f.fence.clear();
+    for (hipStream_t us : f.users) {
+        hipEvent_t ev = nullptr;
+        if (!f.spare.empty()) { ev = f.spare.back(); f.spare.pop_back(); }
+        else RT_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        RT_HIP(ctx, hipEventRecord(ev, us));
+        f.fence.emplace_back(us, ev);
+    }
+    f.users.clear();
+    return RT_OK;
+}
+
+// One dispatch of the planned kernel: nframes frames of g.blocks workgroups each, in f's order (os.feedback: f is the geometry's
+// slot, else an empty one), measuring the tiles' costs behind it if the order is not settled.
+int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt_geo_plan &g, const rt::OrderShape &os,
+               Feedback &f, hipStream_t stream, int nframes, int64_t frame_stride)
+{
+    const Shape &sh = plan.shape;
+    const int fi = (int)plan.family;
+    const void *fn = KERNELS[fi][plan.index];
+    const unsigned grid = (unsigned)g.blocks;
+    if (ctx->log_kernels)
+        std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
+                     (int)sh.lat, sh.mode, fi);
+    // more than the default 48 KiB of dynamic LDS: raised on all of the family's kernels at once
+    if (plan.lds > 48 * 1024 && plan.lds > ctx->lds_limit_set[fi]) {
+        for (const void *kf : KERNELS[fi])
+            if (kf) RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+        ctx->lds_limit_set[fi] = plan.lds;
+    }
+    if (sh.count) {
+        if (!ctx->counts.p) {
+            int rc0 = ensure(ctx, ctx->counts, RT_COUNT_WORDS * sizeof(unsigned long long));
+            if (rc0 != RT_OK) return rc0;
+            RT_HIP(ctx, hipMemsetAsync(ctx->counts.p, 0, RT_COUNT_WORDS * sizeof(unsigned long long), stream));
+        }
+        k.ray_counts = (unsigned long long *)ctx->counts.p;
+    }
+    const bool same_epoch = f.epoch == ctx->epoch;
+    const bool settled = order_settled(ctx, f);
+    const bool measure = os.feedback && !settled && !f.building;  // one measurement in flight at a time (one cost buffer)
     if (settled && !same_epoch) f.since++;
     if (f.have) {
         k.order = (const unsigned *)f.order[f.cur].p;
         if (std::find(f.users.begin(), f.users.end(), stream) == f.users.end()) f.users.push_back(stream);
     }
     if (measure) {
-        const size_t words = (size_t)items * sizeof(unsigned);
+        const size_t words = (size_t)os.items * sizeof(unsigned);
         int rc = ensure(ctx, f.cost, words);
         if (rc == RT_OK) rc = ensure(ctx, f.btmp, words);
         if (rc == RT_OK) rc = ensure(ctx, f.order[0], 2 * words);     // longest-first order, then the tile-order one (order_kernel)
@@ -645,20 +551,20 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, rt::Family fam, bo
         f.fence.clear();
         k.cost = (unsigned *)f.cost.p;
     }
-    k.nframes = nframes; k.bpf = (int)grid; k.frame_stride = frame_stride; k.order_tiles = otiles ? 1 : 0;
+    k.nframes = nframes; k.bpf = (int)grid; k.frame_stride = frame_stride; k.order_tiles = os.otiles ? 1 : 0;
     rt::div_magic((unsigned)k.bpf, k.bpf_magic, k.bpf_shift);
     rt::div_magic((unsigned)k.tiles_y, k.tiles_y_magic, k.tiles_y_shift);
-    k.seq_offset = (ctx->seq_order < 0 ? wpw == 2 : ctx->seq_order != 0) ? (int)items : 0;
+    k.seq_offset = os.seq_offset;
     void *args[] = {(void *)&k};
-    RT_HIP(ctx, hipLaunchKernel(fn, dim3(grid * (unsigned)nframes), dim3(wgt), args, lds, stream));
+    RT_HIP(ctx, hipLaunchKernel(fn, dim3(grid * (unsigned)nframes), dim3(64 * sh.wpw), args, plan.lds, stream));
     ctx->stats.launches++;
     ctx->stats.frames += (uint64_t)nframes;
     if (settled) ctx->stats.launches_settled++;
     if (measure) ctx->stats.launches_measuring++;
     if (measure) {
         hipLaunchKernelGGL(rt::order_kernel, dim3(1), dim3(rt::ORDER_THREADS), 0, stream, (const unsigned *)f.cost.p,
-                           (unsigned *)f.gtmp.p, (unsigned *)f.btmp.p, (unsigned *)f.order[f.cur ^ 1].p, (int)items, otiles ? gshift + wshift : gshift,
-                           otiles ? wshift : 0, otiles ? k.ntiles : (int)grid);
+                           (unsigned *)f.gtmp.p, (unsigned *)f.btmp.p, (unsigned *)f.order[f.cur ^ 1].p, (int)os.items, os.otiles ? os.gshift + os.wshift : os.gshift,
+                           os.otiles ? os.wshift : 0, os.otiles ? k.ntiles : (int)grid);
         RT_HIP(ctx, hipEventRecord(f.done, stream));
         f.building = true;
         f.build_epoch = ctx->epoch;
@@ -697,17 +603,17 @@ int rt_create(rt_ctx **out, int device)
     if (!ctx) return fail(nullptr, RT_ERR_ALLOC, "out of host memory");
     ctx->device = device;
     if (const char *e = std::getenv("MI355RT_LANES_PRIMARY")) ctx->lanes_primary = std::atoi(e);
-    if (const char *e = std::getenv("MI355RT_LANES_MINS")) ctx->lanes_min_spheres = std::atoi(e);
+    if (const char *e = std::getenv("MI355RT_LANES_MINS")) ctx->knobs.lanes_min_spheres = std::atoi(e);
     if (const char *e = std::getenv("MI355RT_CLUSTER_MINS")) ctx->cluster_min = std::max(8, std::atoi(e));
     if (const char *e = std::getenv("MI355RT_CHUNK_MODE")) ctx->chunk_mode = std::atoi(e);
-    if (const char *e = std::getenv("MI355RT_ORDER_GROUP")) { const int v = std::atoi(e); if (v >= 0 && v <= 6) ctx->order_group = v; }
+    if (const char *e = std::getenv("MI355RT_ORDER_GROUP")) { const int v = std::atoi(e); if (v >= 0 && v <= 6) ctx->knobs.order_group = v; }
     if (const char *e = std::getenv("MI355RT_REMEASURE")) ctx->remeasure = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("MI355RT_F32_RECORDS")) ctx->f32_records = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MI355RT_WPW2_MAX_IMAGE")) ctx->wpw2_max_image = (size_t)std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("MI355RT_ORDER_TILES")) ctx->order_tiles = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MI355RT_LANES_PARK")) ctx->lanes_park = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_F32_RECORDS")) ctx->knobs.f32_records = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_WPW2_MAX_IMAGE")) ctx->knobs.wpw2_max_image = (size_t)std::max(0, std::atoi(e));
+    if (const char *e = std::getenv("MI355RT_ORDER_TILES")) ctx->knobs.order_tiles = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_LANES_PARK")) ctx->knobs.lanes_park = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LOG_KERNELS")) ctx->log_kernels = std::atoi(e) != 0;
-    if (const char *e = std::getenv("MI355RT_SEQ_ORDER")) ctx->seq_order = std::atoi(e) != 0 ? 1 : 0;
+    if (const char *e = std::getenv("MI355RT_SEQ_ORDER")) ctx->knobs.seq_order = std::atoi(e) != 0 ? 1 : 0;
     if (const char *e = std::getenv("MI355RT_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= RT_RENDER_CHUNKS) ctx->render_chunks = v; }
     hipError_t s;
     if ((s = hipSetDevice(device)) != hipSuccess || (s = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -764,7 +670,7 @@ const char *rt_last_error(const rt_ctx *ctx) { return ctx ? ctx->err.c_str() : g
 static int set_scene(rt_ctx *ctx, const rt::SceneDesc &desc)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    const rt::PackedScene ps = rt::pack_scene(desc, ctx->cluster_min, ctx->lanes_min_spheres);
+    const rt::PackedScene ps = rt::pack_scene(desc, ctx->cluster_min, ctx->knobs.lanes_min_spheres);
     if (ps.status != RT_OK) return fail(ctx, ps.status, ps.error);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bytes = ps.rec.size() * sizeof(double);

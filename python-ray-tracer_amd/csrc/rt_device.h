@@ -31,13 +31,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets: shared with the host's scene packer (rt_scene.h)
+#include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets, the LDS image's arithmetic (lds_bytes, table_layout, ...), TILE, div_magic:
+                         // shared with the host's scene packer (rt_scene.h) and launch plan (rt_plan.h)
 
 #pragma clang fp contract(off)
 
 // Build-time knobs (A/B builds for tools/ab_bench.py); the defaults are the measured best on MI355X:
 //   RT_FAST_NORMALIZE   shared-reciprocal normalize instead of sqrt + three divisions (C2 -10 %)
 //   RT_FAST_DIVSQRT     0 = the backend's full f64 division / sqrt in the scene queries (div_inrange, sqrt_inrange)
+// and, with their defaults in rt_layout.h (the host's launch plan reads them too):
 //   RT_CLUSTER_MIN      sphere count above which the scene is stored in clusters of 8
 //   RT_MAX_CULL_TABLE_BYTES  LDS budget of a workgroup's anchored cull table
 //   RT_W_PARK, RT_W_AAPARK, RT_W_LANES  waves/SIMD the LDS-parked, parked AA and lane-owned variants are compiled for
@@ -48,30 +50,10 @@
 #ifndef RT_FAST_NORMALIZE
 #define RT_FAST_NORMALIZE 1
 #endif
-#ifndef RT_W_PARK
-#define RT_W_PARK 7
-#endif
-#ifndef RT_W_AAPARK
-#define RT_W_AAPARK 7   // 72 VGPRs with a few spills (76 B/lane of scratch) still beat 5 waves/SIMD without: -9 %
-#endif
-#ifndef RT_W_LANES
-#define RT_W_LANES 4    // lane-owned traversal (clustered scenes: the LDS image bounds the occupancy at about 4 anyway) wants registers
-#endif
 
 namespace rt {
 
-constexpr int TILE = 8;            // 8x8 pixels per wavefront
-// Tiles (wavefronts) per workgroup: a template parameter of the kernel, chosen per scene by the host.  Small
-// workgroups start and retire at a finer grain (C2: 2 waves beat 4 by 3 %); every workgroup stages its own copy
-// of the scene and its cull tables, so bigger scenes want bigger workgroups (C4: 4 waves beat 2 by 24 %, C5 by 69 %).
-constexpr int TILE_ORDER_MIN_WPW = 4;   // workgroups of this many waves or more may be dispatched tile by tile (render_kernel, dispatch)
 constexpr int TABLE_THREADS = 256; // tables_kernel's workgroup
-constexpr int BOX_STRIDE = 8;      // floats per cluster box: lo.xyz, -, hi.xyz, - (two ds_read_b128)
-constexpr int CULL_STRIDE = 4;     // floats per (anchor, sphere) cull entry: Lx,Ly,Lz, tau (one ds_read_b128)
-#ifndef RT_MAX_CULL_TABLE_BYTES
-#define RT_MAX_CULL_TABLE_BYTES (40 * 1024)
-#endif
-constexpr int MAX_CULL_TABLE_BYTES = RT_MAX_CULL_TABLE_BYTES;   // anchored cull table budget per workgroup (LDS)
 
 struct KParams {
     const double *scene;       // packed records: S spheres, then P planes, then L lights
@@ -132,20 +114,6 @@ struct KParams {
     };
 };
 
-// Division of n < 2^31 by a launch constant d without the backend's 20-instruction sequence (v_rcp_iflag_f32 and two
-// correction steps, on the VECTOR unit even for wave-uniform operands): q = mulhi(n, M) >> sh with M = floor(2^(31+l) / d) + 1,
-// l = ceil(log2 d), sh = l - 1 — exact because n d < 2^(31+l) (Granlund-Montgomery); d = 1 passes n through.  Every wave
-// divides its tile index by the tiles per column, and in multi-frame launches its block index by the blocks per frame,
-// twice: 31 of the headline kernel's vector instructions (and as many scalar ones) per wave, C2 -1.5 %, C4 -1.7 %.
-// tests/test_host_helpers.py checks the formula exhaustively on small ranges and on random operands.
-__host__ __device__ inline void div_magic(unsigned d, unsigned &M, unsigned &sh)
-{
-    if (d <= 1u) { M = 0u; sh = 0u; return; }
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    M = (unsigned)((1ull << (31 + l)) / d + 1ull);
-    sh = l - 1u;
-}
 __device__ __forceinline__ int div_by(int n, int d, unsigned M, unsigned sh)
 {
     return d == 1 ? n : (int)(__umulhi((unsigned)n, M) >> sh);
@@ -556,8 +524,6 @@ __device__ __forceinline__ int order_bucket(unsigned c)
 }
 // dispatch-order feedback (order_kernel)
 constexpr int ORDER_THREADS = 1024, ORDER_BUCKETS = 1024, ORDER_XCDS = 8;
-// sphere slots in the float32 tables: whole clusters when the scene is clustered, else a multiple of 4
-__host__ __device__ inline int padS(int S, int NC) { return NC > 0 ? NC * CLUSTER : pad4(S); }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1867,54 +1833,6 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
         o32[p.plane_stride + off] = (float)G;
         o32[2 * p.plane_stride + off] = (float)B;
     }
-}
-
-// LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
-__host__ __device__ constexpr int lds_slots(bool aa, bool park, bool mode2, Family f) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (has_mat(f) ? 3 : 0) + (has_refr(f) ? 4 : 0) + (has_scat(f) ? 2 : 0) + (has_soft(f) ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
-__host__ __device__ inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
-// The float32 tables of a scene, offsets in floats (every one a multiple of 4):
-//   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
-// (colours: {R,G,B,-} of the S spheres, padded to Sp entries, then of the P planes — exact, the scene is float32; only
-// the MODE 1 kernels, which keep no float64 sphere records, stage and read them: `total_col` floats instead of `total`)
-// The lane-owned traversal never reads the clusters' origin-form spheres (it tests boxes), so its kernels stage — and
-// reserve LDS for — everything but that last table (`lanes`): config 5's image stays under the 4-workgroups-per-CU line.
-struct TableLayout { size_t tab, ctab, cbox, gbox, gtab, csph32, total_lanes, total, col32, total_col; };
-__host__ __device__ inline TableLayout table_layout(int S, int NC, int anchors, int P = 0)
-{
-    const size_t Sp = padS(S, NC), NCp = pad4(NC), NG = supers(NC), NGp = pad4((int)NG);
-    TableLayout t;
-    size_t o = 4 * Sp;
-    t.tab = o;    o += (size_t)anchors * Sp * CULL_STRIDE;
-    t.ctab = o;   o += (size_t)anchors * NCp * CULL_STRIDE;
-    t.cbox = o;   o += NCp * BOX_STRIDE;
-    t.gbox = o;   o += NG * BOX_STRIDE;
-    t.gtab = o;   o += (size_t)anchors * NGp * CULL_STRIDE;
-    t.total_lanes = o;
-    t.csph32 = o; o += 4 * NCp;
-    t.total = o;
-    t.col32 = o;  o += 4 * (Sp + (size_t)pad4(P));
-    t.total_col = o;
-    return t;
-}
-__host__ __device__ inline size_t table_floats(int S, int NC, int anchors, bool lanes = false, bool col = false, int P = 0)
-{
-    const TableLayout t = table_layout(S, NC, anchors, P);
-    return col ? t.total_col : (lanes ? t.total_lanes : t.total);
-}
-// mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
-// (TEX kernels keep their twins' image, unread parts included: they take every colour from KParams::lens.texels, so the MODE 1
-// colour table and the colours of the float64 records are dead weight in theirs — the price of sharing the twins' layout.)
-// f, M: the kernels' family and the scene's material count (their image holds the material block, mat_doubles)
-__host__ __device__ inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
-                                            Family f = Family::PLAIN, int M = 0)
-{
-    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, f) * wgt +
-            mat_doubles(M, S, P, f)) * sizeof(double) +
-           ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
-#ifdef RT_REGION_STATS
-           + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
-#endif
-           ;
 }
 
 // The float32 cull tables (exact sphere table for the origin form; {A-c, tau} per anchor and sphere; the same two

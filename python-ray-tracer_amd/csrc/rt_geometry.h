@@ -10,7 +10,7 @@
 
 #include <stdint.h>
 
-#define RT_GEO_TILE 8                            /* tiles are 8x8 pixels, one wavefront each (rt_device.h: TILE) */
+#define RT_GEO_TILE 8                            /* tiles are 8x8 pixels, one wavefront each (rt_layout.h: TILE) */
 #define RT_GEO_MAX_PIXELS (1ll << 31)            /* w*h of a frame */
 #define RT_GEO_MAX_W ((1ll << 31) - 8)           /* the kernel forms x0 + 8 tx + 7 (up to w + 6) as a signed int */
 #define RT_GEO_MAX_H ((1ll << 29) - 32)          /* one column of tiles, ceil(h/8) <= 2^26 - 4, in whole workgroups of up to

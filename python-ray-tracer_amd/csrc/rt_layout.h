@@ -1,7 +1,9 @@
-// rt_layout.h — the layout of the scene buffer, shared by the host's scene packer (rt_scene.h) and the render kernels
-// (rt_device.h): record strides, the feature families and the sizes and offsets of the buffer's blocks.
-// HIP-free: hipcc and a plain C++17 host compiler both take it (tests/algo/scene_pack_check.cpp builds the packer without
-// HIP), so nothing here may name a HIP type or builtin.
+// rt_layout.h — the layout of the scene buffer and of a render kernel's LDS image, shared by the host's scene packer
+// (rt_scene.h), its launch plan (rt_plan.h) and the render kernels (rt_device.h): record strides, the feature families, the
+// sizes and offsets of the buffer's blocks, the float32 tables and the LDS image's size (table_layout, lds_bytes), the tile
+// size, the build-time knobs both sides read (RT_CLUSTER_MIN, RT_MAX_CULL_TABLE_BYTES, RT_W_*) and div_magic.
+// HIP-free: hipcc and a plain C++17 host compiler both take it (tests/algo/scene_pack_check.cpp and launch_plan_check.cpp
+// build the packer and the plan without HIP), so nothing here may name a HIP type or builtin.
 #pragma once
 #include <stddef.h>
 
@@ -12,8 +14,31 @@
 #define RT_HD
 #endif
 
+// waves/SIMD the LDS-parked, parked AA and lane-owned kernels are compiled for (render_kernel's __launch_bounds__; rt_plan.h's
+// parking rule reads RT_W_LANES)
+#ifndef RT_W_PARK
+#define RT_W_PARK 7
+#endif
+#ifndef RT_W_AAPARK
+#define RT_W_AAPARK 7   // 72 VGPRs with a few spills (76 B/lane of scratch) still beat 5 waves/SIMD without: -9 %
+#endif
+#ifndef RT_W_LANES
+#define RT_W_LANES 4    // lane-owned traversal (clustered scenes: the LDS image bounds the occupancy at about 4 anyway) wants registers
+#endif
+
 namespace rt {
 
+constexpr int TILE = 8;            // 8x8 pixels per wavefront
+// Tiles (wavefronts) per workgroup: a template parameter of the kernel, chosen per scene by the host.  Small
+// workgroups start and retire at a finer grain (C2: 2 waves beat 4 by 3 %); every workgroup stages its own copy
+// of the scene and its cull tables, so bigger scenes want bigger workgroups (C4: 4 waves beat 2 by 24 %, C5 by 69 %).
+constexpr int TILE_ORDER_MIN_WPW = 4;   // workgroups of this many waves or more may be dispatched tile by tile (render_kernel, dispatch)
+constexpr int BOX_STRIDE = 8;      // floats per cluster box: lo.xyz, -, hi.xyz, - (two ds_read_b128)
+constexpr int CULL_STRIDE = 4;     // floats per (anchor, sphere) cull entry: Lx,Ly,Lz, tau (one ds_read_b128)
+#ifndef RT_MAX_CULL_TABLE_BYTES
+#define RT_MAX_CULL_TABLE_BYTES (40 * 1024)
+#endif
+constexpr int MAX_CULL_TABLE_BYTES = RT_MAX_CULL_TABLE_BYTES;   // anchored cull table budget per workgroup (LDS)
 constexpr int SPH_STRIDE = 8;      // doubles per sphere record: cx,cy,cz,r2, R,G,B, caller's index
 constexpr int PL_STRIDE = 16;      // ox,oy,oz,nx,ny,nz, Nx,Ny,Nz, bNx,bNy,bNz, R,G,B, axis code (0 general, +-1/2/3 = +-e_x/y/z)
 constexpr int LT_STRIDE = 4;       // x,y,z,pad
@@ -30,7 +55,7 @@ constexpr int SKY_DOUBLES = 24;    // the sky block (rt_device.h: sky_color has 
 
 // The feature family of a render kernel (its last template argument).  Each family's kernels are the twins of the family before
 // it with one more feature; LENS and LENS_SOFT are the lens twins of SCAT and SOFT.  The host derives a launch's family from its
-// scene and lens (mi355rt.hip: family_of) and runs that family's kernels.
+// scene and lens (rt_plan.h: family_of) and runs that family's kernels.
 // TEX_*: the texture twins of SCAT, SOFT, LENS and LENS_SOFT (rt_set_scene_textures with a textured object): the hit's colour is a
 // texel chosen at the hit point (texel_of).  They are appended: tools/isa_compare.py matches kernels by the family's number.
 // LIT_*: the lighting twins of the four TEX families (rt_set_scene_lighting with a light that is not (1, 1, 1) or a row with
@@ -67,5 +92,71 @@ RT_HD inline size_t tex_doubles(int T) { return T > 0 ? 1 + (size_t)TEX_STRIDE *
 // The lighting block of a scene that runs the LIT kernels (KParams::lens.lit): {e_r, e_g, e_b, -} per light (LT_STRIDE doubles),
 // then {spec / n, log2(shin)} per object slot (S spheres in slot order, then P planes).
 RT_HD inline size_t lit_doubles(int S, int P, int L) { return (size_t)LT_STRIDE * L + 2 * ((size_t)S + P); }
+
+// sphere slots in the float32 tables: whole clusters when the scene is clustered, else a multiple of 4
+RT_HD inline int padS(int S, int NC) { return NC > 0 ? NC * CLUSTER : pad4(S); }
+
+// LDS image: [float64 records][per-thread slots 6|9 x 256 doubles][256 int32 pixel offsets][float32 sphere table S x 4][cull table anchors x S x CULL_STRIDE]
+RT_HD constexpr int lds_slots(bool aa, bool park, bool mode2, Family f) { return (park ? ((aa && !mode2) ? 9 : 6) : 0) + (has_mat(f) ? 3 : 0) + (has_refr(f) ? 4 : 0) + (has_scat(f) ? 2 : 0) + (has_soft(f) ? 1 : 0); }   // x workgroup-size doubles (MODE 2: the tap sums stay in registers; MAT: + W, lamb, refl; REFR: + Q, eta; SCAT: + rough, key; SOFT: + light key)
+RT_HD inline int lds_offset_words(bool park, int wgt) { return park ? wgt : 0; }    // + one int32 per thread: the pixel offset
+// The float32 tables of a scene, offsets in floats (every one a multiple of 4):
+//   sph32 | anchored table | cluster anchored table | cluster boxes | group boxes | group anchored table | cluster sph32 | colours
+// (colours: {R,G,B,-} of the S spheres, padded to Sp entries, then of the P planes — exact, the scene is float32; only
+// the MODE 1 kernels, which keep no float64 sphere records, stage and read them: `total_col` floats instead of `total`)
+// The lane-owned traversal never reads the clusters' origin-form spheres (it tests boxes), so its kernels stage — and
+// reserve LDS for — everything but that last table (`lanes`): config 5's image stays under the 4-workgroups-per-CU line.
+struct TableLayout { size_t tab, ctab, cbox, gbox, gtab, csph32, total_lanes, total, col32, total_col; };
+RT_HD inline TableLayout table_layout(int S, int NC, int anchors, int P = 0)
+{
+    const size_t Sp = padS(S, NC), NCp = pad4(NC), NG = supers(NC), NGp = pad4((int)NG);
+    TableLayout t;
+    size_t o = 4 * Sp;
+    t.tab = o;    o += (size_t)anchors * Sp * CULL_STRIDE;
+    t.ctab = o;   o += (size_t)anchors * NCp * CULL_STRIDE;
+    t.cbox = o;   o += NCp * BOX_STRIDE;
+    t.gbox = o;   o += NG * BOX_STRIDE;
+    t.gtab = o;   o += (size_t)anchors * NGp * CULL_STRIDE;
+    t.total_lanes = o;
+    t.csph32 = o; o += 4 * NCp;
+    t.total = o;
+    t.col32 = o;  o += 4 * (Sp + (size_t)pad4(P));
+    t.total_col = o;
+    return t;
+}
+RT_HD inline size_t table_floats(int S, int NC, int anchors, bool lanes = false, bool col = false, int P = 0)
+{
+    const TableLayout t = table_layout(S, NC, anchors, P);
+    return col ? t.total_col : (lanes ? t.total_lanes : t.total);
+}
+// mode2: the kernels of the large clustered scenes (lane-owned traversal) stage no float64 sphere records (sphere_hot)
+// (TEX kernels keep their twins' image, unread parts included: they take every colour from KParams::lens.texels, so the MODE 1
+// colour table and the colours of the float64 records are dead weight in theirs — the price of sharing the twins' layout.)
+// f, M: the kernels' family and the scene's material count (their image holds the material block, mat_doubles)
+RT_HD inline size_t lds_bytes(int S, int P, int L, int NC, int anchors, bool aa, bool park, int wgt, bool lanes = false, bool mode2 = false, bool norec = false,
+                              Family f = Family::PLAIN, int M = 0)
+{
+    return (lds_doubles((mode2 || norec) ? 0 : S, P, L) + (size_t)lds_slots(aa, park, mode2, f) * wgt +
+            mat_doubles(M, S, P, f)) * sizeof(double) +
+           ((size_t)lds_offset_words(park, wgt) + table_floats(S, NC, anchors, lanes, norec, P)) * sizeof(float) + 16   // + workgroup cost/arrival words
+#ifdef RT_REGION_STATS
+           + (size_t)(wgt / 64) * 32 * sizeof(unsigned)
+#endif
+           ;
+}
+
+// Division of n < 2^31 by a launch constant d without the backend's 20-instruction sequence (v_rcp_iflag_f32 and two
+// correction steps, on the VECTOR unit even for wave-uniform operands): q = mulhi(n, M) >> sh with M = floor(2^(31+l) / d) + 1,
+// l = ceil(log2 d), sh = l - 1 — exact because n d < 2^(31+l) (Granlund-Montgomery); d = 1 passes n through.  Every wave
+// divides its tile index by the tiles per column, and in multi-frame launches its block index by the blocks per frame,
+// twice: 31 of the headline kernel's vector instructions (and as many scalar ones) per wave, C2 -1.5 %, C4 -1.7 %.
+// tests/test_host_helpers.py checks the formula exhaustively on small ranges and on random operands.
+RT_HD inline void div_magic(unsigned d, unsigned &M, unsigned &sh)
+{
+    if (d <= 1u) { M = 0u; sh = 0u; return; }
+    unsigned l = 0;
+    while ((1ull << l) < d) ++l;
+    M = (unsigned)((1ull << (31 + l)) / d + 1ull);
+    sh = l - 1u;
+}
 
 }  // namespace rt

@@ -260,3 +260,57 @@ for S, ncols, soft, tex, rgb, sky in itertools.product((0, 5, 21, 64, 170), (0, 
     n += 1
 print(f"scenes={n} ok")
 '''
+
+
+LAUNCH_PLAN_COORDS = ("knobs", "S", "P", "L", "family", "aa", "count", "no_bundles")
+LAUNCH_PLAN_ROW = ("family", "aa", "park", "wpw", "count", "lat", "mode", "index", "lds", "anchors", "gshift", "code", "seq")
+
+
+def test_launch_plan_is_the_recorded_one(tmp_path):
+    """python-ray-tracer_amd/csrc/rt_plan.h, everything a launch decides before a HIP call (its family, which of the family's render
+    kernels runs, the dynamic LDS, the anchors, the shape of the dispatch order), under AddressSanitizer and
+    UndefinedBehaviorSanitizer over the table of tests/algo/launch_plan_check.cpp: 14 rows of MI355RT_* knobs x 15 sphere counts
+    x P in {0, 2} x L in {1, 3} x the 19 families x AA off / on / the lattice x RT_FLAG_COUNT_RAYS (PLAIN) x RT_FLAG_NO_BUNDLES,
+    100 800 cases.  Every row must be, exactly, what tests/golden/launch_plan.npz holds: the choice of the library's dispatch() as it
+    was before the plan became a header of its own, recorded by a program that included that commit's rt_device.h, held that
+    commit's launch() and dispatch() expressions copied verbatim, was built with hipcc for gfx950 and ran its host arithmetic on a
+    CPU.  No case may pick a shape its family has no kernel for, the picked (family, shape) pairs are exactly the 285 has_kernel
+    admits, the LDS size is lds_bytes of the picked shape (the program checks both), and both sides of each threshold occur."""
+    import numpy as np
+    exe, got_path = str(tmp_path / "launch_plan_check"), str(tmp_path / "got.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "launch_plan_check.cpp")])
+    res = subprocess.run([exe, got_path], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == "cases=100800 kernels=285 ok", res.stdout
+    want = np.load(os.path.join(REPO, "tests", "golden", "launch_plan.npz"))
+    got = np.fromfile(got_path, np.int32)
+    nk = want["knobs"].size
+    assert np.array_equal(got[:nk].reshape(-1, 8), want["knobs"])
+    got = got[nk:].reshape(-1, 21)
+    assert got.shape[0] == 100800 == want["rows"].shape[0]
+    assert np.array_equal(got[:, :8], want["coords"])
+    bad = np.flatnonzero((got[:, 8:] != want["rows"]).any(axis=1))
+    assert bad.size == 0, [(dict(zip(LAUNCH_PLAN_COORDS, got[i, :8])), got[i, 8:], want["rows"][i]) for i in bad[:5]]
+    co = {n: got[:, i] for i, n in enumerate(LAUNCH_PLAN_COORDS)}
+    ro = {n: got[:, 8 + i] for i, n in enumerate(LAUNCH_PLAN_ROW)}
+    # the picked (family, shape) pairs are all the kernels there are: PLAIN 25, MAT 22, 14 for each of the other 17
+    pairs = set(zip(ro["family"].tolist(), ro["index"].tolist()))
+    per_family = [sum(1 for f, _ in pairs if f == fam) for fam in range(19)]
+    assert per_family == [25, 22] + [14] * 17 and len(pairs) == 285, per_family
+    assert np.array_equal(ro["family"], co["family"])
+    # both sides of each threshold: clusters from 21 spheres, the lane-owned traversal from 161, two-wave workgroups up to 4608 bytes
+    nc = np.where(co["S"] > want["knobs"][co["knobs"], 0], (co["S"] + 7) // 8, 0)
+    default = co["knobs"] == 0
+    assert (nc[default & (co["S"] == 20)] == 0).all() and (nc[default & (co["S"] == 21)] == 3).all()
+    plain = default & (co["count"] == 0) & (co["no_bundles"] == 0)
+    assert (ro["mode"][plain & (co["S"] == 160)] < 2).all() and (ro["mode"][plain & (co["S"] == 161)] >= 2).all()
+    assert (ro["mode"][default & (co["S"] == 161) & (co["no_bundles"] == 1)] < 2).all()
+    flat = (co["knobs"] == 5) & (co["S"] == 36) & (co["P"] == 2) & (co["family"] == 0) & (co["count"] == 0)
+    assert (ro["wpw"][flat & (co["L"] == 1)] == 2).all() and (ro["wpw"][flat & (co["L"] == 3)] == 4).all()    # (images of 4320 and 5536 B)
+    # the order knobs reach the order's shape
+    four = ro["wpw"] == 4
+    assert (ro["gshift"][co["knobs"] == 10] == 0).all() and set(ro["gshift"][default]) == {2, 3}
+    assert (ro["code"][(co["knobs"] == 11) & four] & 64 == 0).all() and (ro["code"][default & four] & 64 == 64).all()
+    assert (ro["seq"][co["knobs"] == 12] == 0).all() and (ro["seq"][co["knobs"] == 13] == 1).all()
+    assert np.array_equal(ro["seq"][default], (ro["wpw"][default] == 2).astype(np.int32))

@@ -82,7 +82,7 @@ def test_true_aspect_option():
 
 
 def test_division_by_launch_constants():
-    """rt_device.h div_magic / div_by (tile index / tiles per column, block index / blocks per frame): q = mulhi(n, M) >> sh with
+    """rt_layout.h div_magic / rt_device.h div_by (tile index / tiles per column, block index / blocks per frame): q = mulhi(n, M) >> sh with
     M = floor(2^(31+l) / d) + 1, l = ceil(log2 d), sh = l - 1, must equal n // d for every n < 2^31 — restated here and checked
     exhaustively for small operands, at the edges, and on random ones (the GPU suite then runs the device code on odd frame sizes)."""
     import random
