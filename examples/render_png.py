@@ -4,6 +4,7 @@
     python examples/render_png.py [--size 1000x1000] [--depth 4] [--aa | --spp N] [--frames 50] [--materials | --glass | --scatter]
                                   [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]]
                                   [--checker [--texture IMAGE]] [--lights] [--sky] [--out output/render.png]
+                                  [--passes N [--exposure E] [--white W] [--gamma2]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -20,6 +21,10 @@ front of the camera, 2 units wide.  --spp N averages the texel edges.
 with a highlight (rt_set_scene_lighting), over the --glass scene unless --scatter is given.
 --sky puts the default scene with a mirror floor, two glass spheres and two of brushed metal under a blue gradient with a low sun
 and its halo (rt_set_scene_sky), and raises the camera so that the horizon is in the picture; --spp N smooths the sun's edge.
+--passes N renders the picture through a Film (rt_film_accumulate, rt_film_resolve): N passes with seeds 1, 2, ..., N summed on the
+device, each a frame of the launch the other options describe, and their mean resolved there with --exposure E (default 1),
+highlights compressed so that --white W (colour units; default 0: none, values clip at 255) maps to 255, and --gamma2 (a square
+root for display).  For example --sky --dof 0.1 --passes 64 --white 400: 64 lens samples per pixel and a sun that is not flat white.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -58,6 +63,10 @@ def main():
     ap.add_argument("--texture", default=None, metavar="IMAGE", help="--checker: also lay this picture on the floor")
     ap.add_argument("--lights", action="store_true", help="a warm, a cool and a dim light; glossy spheres and glass (lighting)")
     ap.add_argument("--sky", action="store_true", help="a blue gradient with a low sun behind a mirror floor, glass and metal (sky)")
+    ap.add_argument("--passes", type=int, default=0, metavar="N", help="accumulate N passes (seeds 1..N) in a film and resolve their mean")
+    ap.add_argument("--exposure", type=float, default=1.0, help="--passes: the mean is multiplied by this")
+    ap.add_argument("--white", type=float, default=0.0, help="--passes: compress highlights so that this value maps to 255 (0: clip)")
+    ap.add_argument("--gamma2", action="store_true", help="--passes: square-root display gamma")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
@@ -129,19 +138,28 @@ def main():
         image = r.host_array((h, w, 3), np.uint8)
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
         aa = 2 if a.spp > 0 else a.aa
-        r.render_into(0.0, 0.6, 0.3, a.depth, aa, image, flags=flags, spp=a.spp)
-        dev = r.malloc(3 * w * h)
         p = r.params(0.0, 0.6, 0.3, a.depth, aa, flags=flags, spp=a.spp)
-        for _ in range(3):
-            r.render_device(p, 0, w, dev, None, w)
-        r.timer_begin()
-        for _ in range(a.frames):
-            r.render_device(p, 0, w, dev, None, w)
-        ms = r.timer_end() / a.frames
-        r.free(dev)
+        if a.passes > 0:                                        # a film: the passes summed and resolved on the device
+            with pkg.Film(r) as film:
+                film.accumulate(p, a.passes)
+                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags)[0]
+                r.timer_begin()
+                for _ in range(a.frames):                       # (timed: one more pass into the sum, per pass)
+                    film.accumulate(p, 1)
+                ms = r.timer_end() / a.frames
+        else:
+            r.render_into(0.0, 0.6, 0.3, a.depth, aa, image, flags=flags, spp=a.spp)
+            dev = r.malloc(3 * w * h)
+            for _ in range(3):
+                r.render_device(p, 0, w, dev, None, w)
+            r.timer_begin()
+            for _ in range(a.frames):
+                r.render_device(p, 0, w, dev, None, w)
+            ms = r.timer_end() / a.frames
+            r.free(dev)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky}: {ms:.4f} ms per frame on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

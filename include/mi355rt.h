@@ -503,6 +503,58 @@ int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
                        int64_t plane_stride, int64_t frame_stride, const double *cameras, void *const *streams,
                        int n_streams, int frames_per_launch);
 
+/* The film: passes accumulated in device memory and resolved to a frame there (the device half of the reference's "real-time
+ * display" to-do item: progressive refinement).  One launch averages at most RT_MAX_SPP samples, and only under RT_AA_STOCHASTIC;
+ * a film takes any number of passes in any aa_mode, and its resolve compresses what clip_color would cut off.
+ *   d_sum   caller-owned device buffer of float64, true (R,G,B) planes: element [c, x, y] (x0 <= x < x1) at
+ *           d_sum[c * sum_stride + (x - x0) * h + y], the addressing of rt_render_device; a full-frame sum (sum_stride = w*h, d_sum
+ *           pointing at column x0) can be filled slab by slab in place.
+ * rt_film_accumulate: for pass i = 0..passes-1 let f_i be the float32 colours rt_render_device would store for *params with
+ * seed = (params->seed + i) mod 2^32, everything else unchanged (every aa_mode; the RT_FLAG_U8_* bits are ignored).  Per element e,
+ * float64, in this order:
+ *   s = reset ? +0.0 : sum[e];   for i in 0..passes-1:  s = s + (double)f_i[e];   sum[e] = s
+ * (reset != 0 does not read the buffer: it may hold anything.)  The library renders the passes with the unchanged render kernels
+ * into its own scratch and folds up to four of them into the sum per add kernel; the result does not depend on that grouping.
+ * Asynchronous on `stream` (NULL = the context's stream) like rt_render_device; scene, camera, lens and grid are those current
+ * at the call.  RT_ERR_BAD_ARG for passes < 1, d_sum NULL, sum_stride < (x1-x0)*h, (x1-x0)*h > RT_FILM_MAX_PIXELS, and whatever
+ * rt_render_device refuses (which keeps its status); the sum is then untouched.  Two accumulates into the same sum on different
+ * streams are the caller's race; into different sums on different streams they are safe (the scratch is per stream).
+ * rt_film_resolve: the sum of n >= 1 passes (the caller keeps n) of a ws x h frame or slab to a frame.  Per pixel and channel c,
+ * float64, no fused multiply-add, in this order, with s the sum:
+ *   v = (s / (double)n) * exposure
+ *   white > 0:   wn = white / 255.0 (once);  x = v / 255.0;
+ *                x > 0:  y = (x * (1.0 + x / (wn*wn))) / (1.0 + x);  v = y * 255.0      (x <= 0 or NaN: v unchanged)
+ *   gamma == 2:  t = v / 255.0;   t > 0:  v = sqrt(t) * 255.0                           (t <= 0 or NaN: v unchanged)
+ *   d_f32: (float)v        d_u8: clip_color(v), the rule of rt_device.h (NaN -> 0, round half to even, clamp)
+ * The compression is the extended Reinhard curve per channel: a value equal to white comes out as 255.  (In exact arithmetic; the
+ * float64 v is exactly 255.0 for white = 1e-3 and 255 and within two units in the last place of it for every white, so the float32
+ * output is exactly 255.0f and the byte 255: white = 1e6 gives v = 254.99999999999997.)  Gamma 2 is a square root: there is
+ * no pow(), so the bytes do not depend on a math library (as shin and sharp).  The outputs are laid out as rt_render_device's:
+ * planar (3, ws, h) with out_stride between planes, float32 in true (R,G,B) order, uint8 in the reference's (R,B,G) order unless
+ * RT_FLAG_U8_RGB; RT_FLAG_U8_HWC stores the uint8 frame as [y][x][3] with out_stride the row pitch in pixels, uint8 only (d_f32
+ * must then be NULL, as for rt_render_device).  Either output pointer may be NULL, but not both.
+ * With n = 1, exposure 1, white 0 and gamma 1 the float32 output is the pass's float32 frame bit for bit, and the uint8 output is
+ * clip_color of that float32 (a colour of -0.0, which no scene renders, comes out as +0.0 + -0.0 = +0.0).  rt_render_device's own uint8 frame clips the float64 colour before it is rounded to float32, so the
+ * two may differ by one at a rounding tie (a colour within float32 rounding of k + 0.5).
+ * RT_ERR_BAD_ARG for a NULL d_sum or tone, n < 1, exposure not finite or <= 0, white not 0 and not (finite and > 0), gamma not 1
+ * or 2, a flag bit other than the two above, ws < 1, h < 1, ws*h > RT_FILM_MAX_PIXELS, sum_stride < ws*h, out_stride < ws*h (with
+ * RT_FLAG_U8_HWC: < ws), both outputs NULL.  Asynchronous on `stream`; it needs no scene.
+ * RT_ABI_VERSION is unchanged: callers detect these entry points by their symbols. */
+#define RT_FILM_MAX_PIXELS (1 << 27)   /* (x1-x0)*h of one film call */
+
+int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset,
+                       void *d_sum, int64_t sum_stride, void *stream);
+
+typedef struct rt_film_tone {
+    double  exposure;  /* finite, > 0 */
+    double  white;     /* 0: no compression; else finite, > 0, colour units: the value that maps to 255 */
+    int32_t gamma;     /* 1 or 2 */
+    int32_t flags;     /* RT_FLAG_U8_RGB, RT_FLAG_U8_HWC; every other bit must be 0 */
+} rt_film_tone;
+
+int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n,
+                    const rt_film_tone *tone, void *d_u8, void *d_f32, int64_t out_stride, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

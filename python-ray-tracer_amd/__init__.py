@@ -13,5 +13,7 @@ importing works anywhere, rendering raises unless the library and an AMD GPU are
 from . import _lib            # noqa: F401  (ctypes loader; raises on use if the .so is missing)
 from . import cuda            # noqa: F401
 from .renderer import Renderer, RenderError   # noqa: F401
+from . import film            # noqa: F401
+from .film import Film        # noqa: F401
 
-__all__ = ["cuda", "Renderer", "RenderError"]
+__all__ = ["cuda", "film", "Film", "Renderer", "RenderError"]

@@ -16,6 +16,7 @@ RT_MAX_SHADOW_SAMPLES = 16
 RT_RENDER_SLOTS = 4
 RT_MAX_TEXTURES, RT_MAX_TEXTURE_DIM, RT_MAX_TEXELS = 64, 4096, 1 << 22
 RT_SKY_DOUBLES = 24
+RT_FILM_MAX_PIXELS = 1 << 27
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -40,6 +41,12 @@ class rt_stats(C.Structure):
 class rt_texture(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("axis", (C.c_double * 3) * 3), ("dim", C.c_int32 * 3), ("reserved", C.c_int32),
                 ("first", C.c_int64)]
+
+
+class rt_film_tone(C.Structure):
+    """rt_film_resolve's tone (include/mi355rt.h; the arithmetic in numpy: film.tone_reference): exposure finite and > 0; white 0 (no
+    compression) or finite and > 0, the colour that maps to 255; gamma 1 or 2; flags RT_FLAG_U8_RGB | RT_FLAG_U8_HWC only."""
+    _fields_ = [("exposure", C.c_double), ("white", C.c_double), ("gamma", C.c_int32), ("flags", C.c_int32)]
 
 
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
@@ -80,6 +87,8 @@ PROTOTYPES = {
     "rt_render_device": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "rt_render_sequence": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _dp,
                                      C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "rt_film_accumulate": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
+    "rt_film_resolve": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_film_tone), _vp, _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),

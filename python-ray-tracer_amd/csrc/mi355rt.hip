@@ -3,6 +3,7 @@
 // rt_create fails and nothing renders.
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
+#include "rt_film.h"
 #include "rt_geometry.h"
 #include "rt_plan.h"
 #include "rt_scene.h"
@@ -110,6 +111,7 @@ struct rt_ctx {
     rt_stats stats = {};              // host-side launch counters (the ray counters live in `counts`)
     Buf counts;                       // 4 x uint64 on the device: ray counters of RT_FLAG_COUNT_RAYS launches
     std::vector<std::pair<hipStream_t, Buf>> lattice;   // per launching stream: float64 lattice samples (RT_AA_REFERENCE)
+    std::vector<std::pair<hipStream_t, Buf>> film;      // per launching stream: float32 pass frames (rt_film_accumulate)
     int cu_count = 256;
     unsigned long long epoch = 1;     // bumped by every rt_set_*: scene, camera or ray grid changed
     unsigned long long scene_epoch = 1;   // bumped by rt_set_scene only
@@ -255,19 +257,24 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPl
 // The lattice buffer of a stream (RT_AA_REFERENCE with the closed-form grid renders the half-pixel lattice once into
 // float64 samples, then sums nine of them per pixel): one buffer per launching stream, so that frames in flight on
 // different streams keep their samples apart.
-int lattice_buffer(rt_ctx *ctx, hipStream_t stream, size_t bytes, double **out)
+int stream_buffer(rt_ctx *ctx, std::vector<std::pair<hipStream_t, Buf>> &bufs, hipStream_t stream, size_t bytes, void **out)
 {
-    for (auto &e : ctx->lattice)
+    for (auto &e : bufs)
         if (e.first == stream) {
             if (e.second.cap < bytes) RT_HIP(ctx, hipStreamSynchronize(stream));
             int rc = ensure(ctx, e.second, bytes);
-            *out = (double *)e.second.p;
+            *out = e.second.p;
             return rc;
         }
-    ctx->lattice.emplace_back(stream, Buf{});
-    int rc = ensure(ctx, ctx->lattice.back().second, bytes);
-    *out = (double *)ctx->lattice.back().second.p;
+    bufs.emplace_back(stream, Buf{});
+    int rc = ensure(ctx, bufs.back().second, bytes);
+    *out = bufs.back().second.p;
     return rc;
+}
+
+int lattice_buffer(rt_ctx *ctx, hipStream_t stream, size_t bytes, double **out)
+{
+    return stream_buffer(ctx, ctx->lattice, stream, bytes, (void **)out);
 }
 
 // nframes > 1 (rt_render_sequence): that many frames of the current scene and camera, frame f into the outputs +
@@ -641,6 +648,7 @@ int rt_destroy(rt_ctx *ctx)
     for (Buf &b : ctx->scene) if (b.p) (void)hipFree(b.p);
     for (Buf &b : ctx->texels) if (b.p) (void)hipFree(b.p);
     for (auto &e : ctx->lattice) if (e.second.p) (void)hipFree(e.second.p);
+    for (auto &e : ctx->film) if (e.second.p) (void)hipFree(e.second.p);
     for (auto &f : ctx->fbs) {
         for (Buf *b : {&f.cost, &f.gtmp, &f.btmp, &f.order[0], &f.order[1]}) if (b->p) (void)hipFree(b->p);
         for (auto &r : f.fence) (void)hipEventDestroy(r.second);
@@ -915,6 +923,83 @@ int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
     return RT_OK;
 }
 
+// The film: `passes` frames of the unchanged render path (launch(), float32 output, seed + i) into the stream's scratch, up to
+// rt::FILM_BATCH of them folded into the float64 sum by one add kernel.  Everything is queued on `stream`: a batch's renders write
+// the scratch only after the add kernel before them has read it.
+int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
+                       void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = check_params(ctx, params, x0, x1);
+    if (rc != RT_OK) return rc;
+    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: passes < 1");
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: d_sum is NULL");
+    const long long npx = (long long)(x1 - x0) * ctx->h;
+    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: (x1-x0)*h above RT_FILM_MAX_PIXELS");
+    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: sum_stride smaller than the slab");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    rt_params p = *params;
+    p.flags &= ~(RT_FLAG_U8_RGB | RT_FLAG_U8_HWC);
+    // pass planes padded to a multiple of four floats: every plane of the scratch is 16-byte aligned whatever npx is
+    const long long fplane = (npx + 3) & ~3ll;
+    const size_t pass_bytes = (size_t)fplane * 3 * sizeof(float);
+    int batch = passes < rt::FILM_BATCH ? passes : rt::FILM_BATCH;
+    if (batch * pass_bytes > rt::FILM_SCRATCH_MAX) batch = 1;
+    float *frames = nullptr;
+    rc = stream_buffer(ctx, ctx->film, st, batch * pass_bytes, (void **)&frames);
+    if (rc != RT_OK) return rc;
+    rt::FilmAddArgs a;
+    a.sum = (double *)d_sum; a.frames = frames; a.sum_stride = sum_stride; a.fplane = fplane; a.npx = npx;
+    const dim3 grid(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 3), 3);
+    for (int i = 0; i < passes; i += batch) {
+        const int nb = std::min(batch, passes - i);
+        for (int b = 0; b < nb; ++b) {
+            p.seed = params->seed + (uint32_t)(i + b);
+            rc = launch(ctx, &p, x0, x1, nullptr, frames + (size_t)b * 3 * fplane, fplane, st);
+            if (rc != RT_OK) return rc;
+        }
+        a.nb = nb; a.reset = (reset && i == 0) ? 1 : 0;
+        hipLaunchKernelGGL(rt::film_add_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a);
+        RT_HIP(ctx, hipGetLastError());
+    }
+    return RT_OK;
+}
+
+int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone,
+                    void *d_u8, void *d_f32, int64_t out_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: d_sum is NULL");
+    if (!tone) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: tone is NULL");
+    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: ws*h outside 1..RT_FILM_MAX_PIXELS");
+    if (n < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: n < 1");
+    if (!(std::isfinite(tone->exposure) && tone->exposure > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: exposure must be finite and > 0");
+    if (!(tone->white == 0.0 || (std::isfinite(tone->white) && tone->white > 0.0)))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: white must be 0, or finite and > 0");
+    if (tone->gamma != 1 && tone->gamma != 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: gamma must be 1 or 2");
+    if (tone->flags & ~(RT_FLAG_U8_RGB | RT_FLAG_U8_HWC)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: unknown flag bit");
+    if (!d_u8 && !d_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
+    const long long npx = (long long)ws * h;
+    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: sum_stride smaller than the frame");
+    const bool hwc = (tone->flags & RT_FLAG_U8_HWC) != 0;
+    if (hwc) {
+        if (d_f32) return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC re-uses out_stride as the image row pitch: resolve the float32 buffer in a separate call");
+        if (out_stride < (int64_t)ws) return fail(ctx, RT_ERR_BAD_ARG, "row pitch smaller than the frame width");
+    } else if (out_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "out_stride smaller than the frame");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rt::FilmResolveArgs a;
+    a.sum = (const double *)d_sum; a.u8 = (uint8_t *)d_u8; a.f32 = (float *)d_f32;
+    a.sum_stride = sum_stride; a.out_stride = out_stride; a.npx = npx;
+    a.h = h; a.rgb = (tone->flags & RT_FLAG_U8_RGB) ? 1 : 0; a.hwc = hwc ? 1 : 0;
+    a.tone = rt::film_tone_of(n, tone->exposure, tone->white, tone->gamma);
+    hipLaunchKernelGGL(rt::film_resolve_kernel, dim3(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
+                       stream ? (hipStream_t)stream : ctx->stream, a);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out_u8, float *out_f32)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
@@ -1138,6 +1223,10 @@ static int forget_stream(rt_ctx *ctx, hipStream_t stream)
     RT_HIP(ctx, hipStreamSynchronize(stream));
     for (size_t i = 0; i < ctx->lattice.size();) {
         if (ctx->lattice[i].first == stream) { if (ctx->lattice[i].second.p) (void)hipFree(ctx->lattice[i].second.p); ctx->lattice.erase(ctx->lattice.begin() + (long)i); }
+        else ++i;
+    }
+    for (size_t i = 0; i < ctx->film.size();) {
+        if (ctx->film[i].first == stream) { if (ctx->film[i].second.p) (void)hipFree(ctx->film[i].second.p); ctx->film.erase(ctx->film.begin() + (long)i); }
         else ++i;
     }
     for (auto &f : ctx->fbs) {                                  // (its work is complete: nothing of it reads an order any more)

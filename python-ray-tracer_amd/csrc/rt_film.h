@@ -1,0 +1,235 @@
+// rt_film.h — the film (include/mi355rt.h: rt_film_accumulate, rt_film_resolve): a float64 sum of float32 pass frames in device
+// memory, and its resolve to a frame (mean, exposure, highlight compression, display gamma, bytes).
+// The arithmetic of one element (film_add, film_tone, film_clip) is HIP-free, like rt_plan.h and rt_scene.h and for the same
+// reason: the two kernels below and tests/algo/film_check.cpp, a CPU program built under AddressSanitizer and UBSan, compile the
+// same text.  Everything here is evaluated without fused multiply-add (the Makefile's -ffp-contract=off; the CPU program's too).
+// The kernels (hipcc only) are memory-bound streams: 16-byte accesses per lane on planes whose base is 16-byte aligned, 8-, 4-
+// or 1-byte accesses on planes whose base is not (a caller's plane stride may be odd), a scalar tail for the last npx mod 4
+// elements, a grid capped near 8 blocks per CU with a grid-stride loop, no LDS, no scratch, 64-bit plane offsets.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define RT_FILM_HD __host__ __device__
+#else
+#define RT_FILM_HD
+#endif
+
+namespace rt {
+
+// One pass's float32 colour onto the float64 sum.
+RT_FILM_HD inline double film_add(double s, float f) { return s + (double)f; }
+
+// What a resolve evaluates once: n as a double, and the square of white / 255.
+struct FilmTone {
+    double n, exposure, white, wn2;
+    int gamma;
+};
+
+RT_FILM_HD inline FilmTone film_tone_of(int64_t n, double exposure, double white, int gamma)
+{
+    FilmTone t;
+    t.n = (double)n; t.exposure = exposure; t.white = white; t.gamma = gamma;
+    const double wn = white / 255.0;
+    t.wn2 = wn * wn;
+    return t;
+}
+
+// The sum s of n passes to a display value: mean, exposure, the extended Reinhard curve per channel (white maps to 255), a square
+// root for gamma 2.  The comparisons are false for a NaN, which passes through.
+RT_FILM_HD inline double film_tone(double s, const FilmTone &t)
+{
+    double v = (s / t.n) * t.exposure;
+    if (t.white > 0.0) {
+        const double x = v / 255.0;
+        if (x > 0.0) {
+            const double y = (x * (1.0 + x / t.wn2)) / (1.0 + x);
+            v = y * 255.0;
+        }
+    }
+    if (t.gamma == 2) {
+        const double q = v / 255.0;
+        if (q > 0.0) v = __builtin_sqrt(q) * 255.0;
+    }
+    return v;
+}
+
+// rt_device.h's clip_color (common.py:52-57): NaN -> 0, round half to even, clamp to 0..255.
+RT_FILM_HD inline uint8_t film_clip(double c)
+{
+    if (!(c == c)) return 0;
+    if (c <= -0.5) return 0;
+    if (c >= 255.5) return 255;
+    const int i = (int)__builtin_rint(c);
+    return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
+}
+
+#if defined(__HIPCC__)
+
+constexpr int FILM_THREADS = 256;
+constexpr int FILM_BATCH = 4;                       // passes one add kernel folds
+constexpr size_t FILM_SCRATCH_MAX = 256u << 20;      // bytes of pass frames beyond which passes go one by one
+
+// frames: `nb` (1..FILM_BATCH) float32 pass frames, pass b's plane c at frames[(b*3 + c) * fplane], fplane a multiple of 4 floats
+// and frames 16-byte aligned (the library's own scratch): every pass plane is 16-byte aligned.
+struct FilmAddArgs {
+    double *sum;
+    const float *frames;
+    long long sum_stride, fplane, npx;
+    int nb, reset;
+};
+
+struct FilmResolveArgs {
+    const double *sum;
+    uint8_t *u8;
+    float *f32;
+    long long sum_stride, out_stride, npx;
+    int h, rgb, hwc;
+    FilmTone tone;
+};
+
+// 16 bytes per lane as the compiler's own vector types: one global_load / global_store _dwordx4 each
+typedef double film_d2 __attribute__((ext_vector_type(2)));
+typedef float film_f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bool film_aligned(const void *p, unsigned a) { return ((unsigned long long)p & (a - 1)) == 0; }
+
+// four consecutive doubles: two 16-byte accesses where the plane allows (vec), else four of 8 bytes
+__device__ __forceinline__ void film_load4(const double *p, bool vec, double (&v)[4])
+{
+    if (vec) {
+        const film_d2 a = *reinterpret_cast<const film_d2 *>(p), b = *reinterpret_cast<const film_d2 *>(p + 2);
+        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+    } else {
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+    }
+}
+
+__device__ __forceinline__ void film_store4(double *p, bool vec, const double (&v)[4])
+{
+    if (vec) {
+        *reinterpret_cast<film_d2 *>(p) = film_d2{v[0], v[1]};
+        *reinterpret_cast<film_d2 *>(p + 2) = film_d2{v[2], v[3]};
+    } else {
+        p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
+    }
+}
+
+// sum[c][e] = (reset ? +0.0 : sum[c][e]) + f_0[c][e] + ... + f_{nb-1}[c][e], left to right.  blockIdx.y is the plane; a thread
+// takes groups of four elements in a grid-stride loop, and the first npx mod 4 threads of block 0 the elements behind the last group.
+__global__ __launch_bounds__(FILM_THREADS) void film_add_kernel(const FilmAddArgs a)
+{
+    const long long c = blockIdx.y;
+    double *const s = a.sum + c * a.sum_stride;
+    const float *const f = a.frames + c * a.fplane;
+    const long long pass = 3 * a.fplane;
+    const bool vec = film_aligned(s, 16);
+    const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
+    for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
+        const long long e = g << 2;
+        film_f4 v[FILM_BATCH];
+#pragma unroll
+        for (int b = 0; b < FILM_BATCH; ++b)
+            if (b < a.nb) v[b] = *reinterpret_cast<const film_f4 *>(f + b * pass + e);
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        if (!a.reset) film_load4(s + e, vec, acc);
+#pragma unroll
+        for (int b = 0; b < FILM_BATCH; ++b)
+            if (b < a.nb) {
+                acc[0] = film_add(acc[0], v[b].x); acc[1] = film_add(acc[1], v[b].y);
+                acc[2] = film_add(acc[2], v[b].z); acc[3] = film_add(acc[3], v[b].w);
+            }
+        film_store4(s + e, vec, acc);
+    }
+    if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
+        const long long e = (ngroups << 2) + threadIdx.x;
+        double acc = a.reset ? 0.0 : s[e];
+        for (int b = 0; b < a.nb; ++b) acc = film_add(acc, f[b * pass + e]);
+        s[e] = acc;
+    }
+}
+
+// One pixel's three bytes (the tail, and the image layout): e = (x - x0) h + y.
+__device__ __forceinline__ void film_store_u8_pixel(const FilmResolveArgs &a, long long e, double R, double G, double B)
+{
+    const uint8_t r8 = film_clip(R), g8 = film_clip(G), b8 = film_clip(B);
+    const uint8_t c1 = a.rgb ? g8 : b8, c2 = a.rgb ? b8 : g8;
+    if (a.hwc) {
+        const long long x = e / a.h, y = e - x * a.h;
+        uint8_t *px = a.u8 + (y * a.out_stride + x) * 3;
+        px[0] = r8; px[1] = c1; px[2] = c2;
+    } else {
+        a.u8[e] = r8;
+        a.u8[a.out_stride + e] = c1;
+        a.u8[2 * a.out_stride + e] = c2;
+    }
+}
+
+__device__ __forceinline__ void film_store_f32x4(float *p, bool vec, const double (&v)[4])
+{
+    if (vec) *reinterpret_cast<film_f4 *>(p) = film_f4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    else { p[0] = (float)v[0]; p[1] = (float)v[1]; p[2] = (float)v[2]; p[3] = (float)v[3]; }
+}
+
+__device__ __forceinline__ void film_store_u8x4(uint8_t *p, bool vec, const double (&v)[4])
+{
+    const uint8_t b0 = film_clip(v[0]), b1 = film_clip(v[1]), b2 = film_clip(v[2]), b3 = film_clip(v[3]);
+    if (vec) *reinterpret_cast<uint32_t *>(p) = (uint32_t)b0 | ((uint32_t)b1 << 8) | ((uint32_t)b2 << 16) | ((uint32_t)b3 << 24);
+    else { p[0] = b0; p[1] = b1; p[2] = b2; p[3] = b3; }
+}
+
+// A thread resolves groups of four consecutive elements of a column run (all three channels: the image layout interleaves them)
+// in a grid-stride loop; the first npx mod 4 threads of block 0 the pixels behind the last group.
+__global__ __launch_bounds__(FILM_THREADS) void film_resolve_kernel(const FilmResolveArgs a)
+{
+    const double *const s0 = a.sum, *const s1 = a.sum + a.sum_stride, *const s2 = a.sum + 2 * a.sum_stride;
+    const bool v0 = film_aligned(s0, 16), v1 = film_aligned(s1, 16), v2 = film_aligned(s2, 16);
+    // the uint8 planes in stored order: (R,B,G) unless RT_FLAG_U8_RGB
+    float *const f0 = a.f32, *const f1 = a.f32 + a.out_stride, *const f2 = a.f32 + 2 * a.out_stride;
+    const bool w0 = film_aligned(f0, 16), w1 = film_aligned(f1, 16), w2 = film_aligned(f2, 16);
+    uint8_t *const u0 = a.u8, *const u1 = a.u8 + a.out_stride, *const u2 = a.u8 + 2 * a.out_stride;
+    const bool b0 = film_aligned(u0, 4), b1 = film_aligned(u1, 4), b2 = film_aligned(u2, 4);
+    const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
+    for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
+        const long long e = g << 2;
+        double R[4], G[4], B[4];
+        film_load4(s0 + e, v0, R);
+        film_load4(s1 + e, v1, G);
+        film_load4(s2 + e, v2, B);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { R[i] = film_tone(R[i], a.tone); G[i] = film_tone(G[i], a.tone); B[i] = film_tone(B[i], a.tone); }
+        if (a.f32) {
+            film_store_f32x4(f0 + e, w0, R);
+            film_store_f32x4(f1 + e, w1, G);
+            film_store_f32x4(f2 + e, w2, B);
+        }
+        if (a.u8) {
+            if (a.hwc) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) film_store_u8_pixel(a, e + i, R[i], G[i], B[i]);
+            } else {
+                film_store_u8x4(u0 + e, b0, R);
+                film_store_u8x4(u1 + e, b1, a.rgb ? G : B);
+                film_store_u8x4(u2 + e, b2, a.rgb ? B : G);
+            }
+        }
+    }
+    if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
+        const long long e = (ngroups << 2) + threadIdx.x;
+        const double R = film_tone(s0[e], a.tone), G = film_tone(s1[e], a.tone), B = film_tone(s2[e], a.tone);
+        if (a.f32) { f0[e] = (float)R; f1[e] = (float)G; f2[e] = (float)B; }
+        if (a.u8) film_store_u8_pixel(a, e, R, G, B);
+    }
+}
+
+// blocks along x of a film kernel over `groups` groups of four elements: at most 8 per CU in all (`planes` rows of them)
+inline unsigned film_grid(long long groups, int cu_count, int planes)
+{
+    const long long want = (groups + FILM_THREADS - 1) / FILM_THREADS, cap = (long long)cu_count * 8 / planes;
+    const long long n = want < cap ? want : cap;
+    return (unsigned)(n < 1 ? 1 : n);
+}
+
+#endif  // __HIPCC__
+
+}  // namespace rt

@@ -391,6 +391,29 @@ class Renderer:
                                                  cam.ctypes.data_as(C.POINTER(C.c_double)) if cam is not None else None,
                                                  self._seq_streams, len(sv), int(frames_per_launch)))
 
+    def film_accumulate(self, params, x0, x1, passes, reset, d_sum, sum_stride=None, stream=None):
+        """`passes` frames of `params` with seeds seed, seed + 1, ... added to the float64 (3, x1-x0, h) sum at device address
+        d_sum (rt_film_accumulate); reset: start from zero instead of the buffer's content.  Asynchronous.  film.Film owns
+        such a sum and counts its passes."""
+        if sum_stride is None:
+            sum_stride = (int(x1) - int(x0)) * self.h
+        self._check(self._lib.rt_film_accumulate(self._ctx, C.byref(params), int(x0), int(x1), int(passes), int(bool(reset)),
+                                                 C.c_void_p(d_sum) if d_sum else None, int(sum_stride),
+                                                 C.c_void_p(stream) if stream else None))
+
+    def film_resolve(self, d_sum, ws, h, n, d_u8=None, d_f32=None, *, exposure=1.0, white=0.0, gamma=1, flags=0, sum_stride=None,
+                     out_stride=None, stream=None):
+        """The sum of n passes at d_sum to a uint8 and / or float32 frame in device memory (rt_film_resolve): mean, exposure,
+        highlight compression towards `white`, gamma 1 or 2.  Asynchronous."""
+        if sum_stride is None:
+            sum_stride = int(ws) * int(h)
+        if out_stride is None:
+            out_stride = int(ws) if int(flags) & L.RT_FLAG_U8_HWC else int(ws) * int(h)
+        tone = L.rt_film_tone(float(exposure), float(white), int(gamma), int(flags))
+        self._check(self._lib.rt_film_resolve(self._ctx, C.c_void_p(d_sum) if d_sum else None, int(sum_stride), int(ws), int(h), int(n),
+                                              C.byref(tone), C.c_void_p(d_u8) if d_u8 else None, C.c_void_p(d_f32) if d_f32 else None,
+                                              int(out_stride), C.c_void_p(stream) if stream else None))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
         if stream:

@@ -1,0 +1,280 @@
+"""The film on the CPU (rt_film_accumulate, rt_film_resolve): the header, the binding and the exported symbols; the arithmetic of
+python-ray-tracer_amd/csrc/rt_film.h, the text the two film kernels compile, run by tests/algo/film_check.cpp under AddressSanitizer
+and UBSan over a table of edge and random values and compared bit for bit with the numpy restatement of
+python-ray-tracer_amd/film.py; the white -> 255 and identity properties of that restatement; Film's ValueErrors."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+
+from python_ray_tracer_amd import Film, film as F
+from python_ray_tracer_amd import _lib as L
+
+ALGO = os.path.join(REPO, "tests", "algo")
+
+# Sums a resolve must get right: zeros of both signs, negatives, NaN, infinities, denormals, a value whose products overflow, and
+# the rounding ties of clip_color (0.5 -> 0, 1.5 -> 2, 254.5 -> 254, 255.5 -> 255, -0.5 -> 0).
+EDGE_SUMS = np.array([0.0, -0.0, -1.0, -254.5, -1e300, np.nan, np.inf, -np.inf, 5e-324, -5e-324, 2.2250738585072014e-308, 1e-310, 1e300,
+                      0.5, 1.5, 254.5, 255.5, -0.5, 2.5, 253.5, 0.49999999999999994, 0.5000000000000001, 254.99999999999997, 255.0, 256.0,
+                      1.0, 127.5, 128.5, 1e-3, 1e6, 1000.0, 400.0, 3.0, 764.9999999999999], dtype=np.float64)
+WHITES = (0.0, 1e-3, 255.0, 1e6, 1000.0)
+NS = (1, 3, 2 ** 31 - 1)
+EXPOSURES = (1.0, 0.37)
+GAMMAS = (1, 2)
+
+
+def random_sums(rng, n):
+    """Seeded sums in the ranges a film meets: colours, dim colours, sums of many passes, a few negatives."""
+    return np.concatenate([rng.uniform(0.0, 300.0, n // 2), rng.uniform(0.0, 1.0, n // 8), 10.0 ** rng.uniform(-12.0, 12.0, n // 4),
+                           -rng.uniform(0.0, 300.0, n - n // 2 - n // 8 - n // 4)])
+
+
+def tone_table():
+    """[(sums float64 (k,), n, exposure, white, gamma)]: every combination of NS x EXPOSURES x WHITES x GAMMAS over the edge sums and
+    100 random ones each, and s == white at n = 1, exposure 1 for every white > 0 (and 400) under both gammas."""
+    rng = np.random.default_rng(20261018)
+    rows = []
+    for n in NS:
+        for e in EXPOSURES:
+            for wh in WHITES:
+                for g in GAMMAS:
+                    with np.errstate(over="ignore"):
+                        rows.append((np.concatenate([EDGE_SUMS, EDGE_SUMS * n, random_sums(rng, 100) * n]), n, e, wh, g))
+    for wh in WHITES[1:] + (400.0,):
+        for g in GAMMAS:
+            rows.append((np.array([wh]), 1, 1.0, wh, g))
+    return rows
+
+
+def add_table():
+    """(sum float64 (k,), count int64 (k,), reset int64 (k,), addends float32 (k, 9))."""
+    rng = np.random.default_rng(7)
+    k = 3000
+    edges32 = np.array([0.0, -0.0, np.nan, np.inf, -np.inf, 1e-45, -1e-45, 3.4028235e38, 0.5, 254.5, 1e-20, 16777216.0], np.float32)
+    sums = np.concatenate([EDGE_SUMS, random_sums(rng, k - EDGE_SUMS.size) * rng.integers(1, 1000, k - EDGE_SUMS.size)])
+    add = rng.uniform(0.0, 400.0, (k, 9)).astype(np.float32)
+    pick = rng.random((k, 9)) < 0.1
+    add[pick] = rng.choice(edges32, int(pick.sum()))
+    count = rng.integers(0, 10, k).astype(np.int64)
+    count[:10] = np.arange(10)
+    reset = (rng.random(k) < 0.3).astype(np.int64)
+    reset[:EDGE_SUMS.size:2] = 1                                  # a reset over NaN, inf, ...: the old sum must not be read
+    return sums, count, reset, add
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    ut = {8: np.uint64, 4: np.uint32, 1: np.uint8}[a.dtype.itemsize]
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(ut), b.view(ut))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Header, binding, exported symbols
+
+def test_header_binding_and_exported_symbols(tmp_path):
+    hdr = open(os.path.join(REPO, "include", "mi355rt.h")).read()
+    assert "int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset," in hdr
+    assert "int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n," in hdr
+    assert "#define RT_FILM_MAX_PIXELS (1 << 27)" in hdr and "#define RT_ABI_VERSION 7" in hdr
+    assert L.RT_FILM_MAX_PIXELS == 1 << 27 and L.RT_ABI_VERSION == 7
+    for name in ("rt_film_accumulate", "rt_film_resolve"):
+        assert name in L.PROTOTYPES
+    acc, res = L.PROTOTYPES["rt_film_accumulate"], L.PROTOTYPES["rt_film_resolve"]
+    assert acc[0] is C.c_int and len(acc[1]) == 9 and acc[1][7] is C.c_int64
+    assert res[0] is C.c_int and len(res[1]) == 11 and res[1][2] is C.c_int64 and res[1][5] is C.c_int64 and res[1][9] is C.c_int64
+    assert C.sizeof(L.rt_film_tone) == 24
+    src = tmp_path / "size.c"
+    src.write_text('#include "mi355rt.h"\n_Static_assert(sizeof(rt_film_tone) == 24, "rt_film_tone is 24 bytes");\n'
+                   '_Static_assert(RT_FILM_MAX_PIXELS == 134217728, "2^27");\nint main(void) { return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)])
+    lib = L.load()                                               # the cross-compiled library
+    assert lib.rt_abi_version() == 7 and hasattr(lib, "rt_film_accumulate") and hasattr(lib, "rt_film_resolve")
+    # header, numpy restatement (and with them README and DESIGN.md) state the same arithmetic
+    for line in ("s = reset ? +0.0 : sum[e];   for i in 0..passes-1:  s = s + (double)f_i[e];   sum[e] = s",
+                 "v = (s / (double)n) * exposure",
+                 "white > 0:   wn = white / 255.0 (once);  x = v / 255.0;",
+                 "x > 0:  y = (x * (1.0 + x / (wn*wn))) / (1.0 + x);  v = y * 255.0      (x <= 0 or NaN: v unchanged)",
+                 "gamma == 2:  t = v / 255.0;   t > 0:  v = sqrt(t) * 255.0                           (t <= 0 or NaN: v unchanged)"):
+        assert line in hdr, line
+        assert line in (F.accumulate_reference.__doc__ + F.tone_reference.__doc__), line
+    for doc in ("README.md", "DESIGN.md"):
+        text = open(os.path.join(REPO, doc)).read()
+        assert "rt_film_accumulate" in text and "rt_film_resolve" in text and "y = (x * (1.0 + x / (wn*wn))) / (1.0 + x)" in text, doc
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# rt_film.h's arithmetic under the sanitizers against the numpy restatement
+
+def test_film_arithmetic_under_sanitizers_matches_numpy(tmp_path):
+    exe, table, got = str(tmp_path / "film_check"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "film_check.cpp")])
+    rows = tone_table()
+    tone_dt = np.dtype([("s", "<f8"), ("n", "<i8"), ("exposure", "<f8"), ("white", "<f8"), ("gamma", "<i8")])
+    tone = np.concatenate([np.array([(s, n, e, wh, g) for s in sums], dtype=tone_dt) for sums, n, e, wh, g in rows])
+    sums, count, reset, add = add_table()
+    add_dt = np.dtype([("sum", "<f8"), ("count", "<i8"), ("reset", "<i8"), ("addend", "<f4", (9,)), ("pad", "<f4")])
+    assert tone_dt.itemsize == 40 and add_dt.itemsize == 64
+    acc = np.zeros(sums.size, add_dt)
+    acc["sum"], acc["count"], acc["reset"], acc["addend"] = sums, count, reset, add
+    with open(table, "wb") as f:
+        f.write(np.array([tone.size, acc.size], "<i8").tobytes() + tone.tobytes() + acc.tobytes())
+    res = subprocess.run([exe, table, got], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == f"tone={tone.size} add={acc.size} ok", res.stdout
+    assert tone.size > 4000 and acc.size >= 3000
+    raw = open(got, "rb").read()
+    T, A = tone.size, acc.size
+    assert len(raw) == 13 * T + 8 * A
+    v = np.frombuffer(raw, "<f8", T, 0)
+    f32 = np.frombuffer(raw, "<f4", T, 8 * T)
+    u8 = np.frombuffer(raw, np.uint8, T, 12 * T)
+    s_out = np.frombuffer(raw, "<f8", A, 13 * T)
+    at = 0
+    for sums_, n, e, wh, g in rows:
+        want = F.tone_reference(sums_, n, e, wh, g)
+        k = sums_.size
+        what = f"n={n} exposure={e} white={wh} gamma={g}"
+        bad = np.flatnonzero(v[at:at + k].view(np.uint64) != want.view(np.uint64))
+        assert bad.size == 0, (what, sums_[bad][:4], v[at:at + k][bad][:4], want[bad][:4])
+        with np.errstate(all="ignore"):
+            assert same_bits(f32[at:at + k], want.astype(np.float32)), what
+        assert np.array_equal(u8[at:at + k], F.clip_reference(want)), what
+        if k == 1:                                                # s == white: 255.0 in the float32 output, the byte 255
+            assert sums_[0] == wh and f32[at] == np.float32(255.0) and u8[at] == 255 and abs(v[at] - 255.0) < 1e-13, what
+        at += k
+    assert at == T
+    for i in range(A):                                            # (the restatement folds whole frames: one case, one 1-element frame)
+        frames = [add[i, j:j + 1] for j in range(int(count[i]))]
+        want = F.accumulate_reference(None if reset[i] else sums[i:i + 1], frames) if (frames or not reset[i]) else np.zeros(1)
+        assert same_bits(s_out[i:i + 1], want), (i, sums[i], reset[i], add[i, :count[i]], s_out[i], want)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Properties of the restatement
+
+def test_clip_reference_is_clip_color():
+    v = np.array([np.nan, -np.inf, -1.0, -0.5, -0.49999, 0.0, -0.0, 0.5, 0.50001, 1.5, 2.5, 254.5, 254.50001, 255.0, 255.5, 256.0, 1e300, np.inf])
+    assert F.clip_reference(v).tolist() == [0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 2, 254, 255, 255, 255, 255, 255, 255]
+    assert F.clip_reference(v).dtype == np.uint8 and F.clip_reference(v.reshape(3, 6)).shape == (3, 6)
+
+
+@pytest.mark.parametrize("white", [1e-3, 255.0, 400.0, 1000.0, 1e6])
+def test_white_maps_to_255(white):
+    """A sum equal to white resolves to 255.0 in the float32 output and to the byte 255.  The float64 v behind them is exactly 255.0
+    for white = 1e-3 and 255; the contract's order of operations leaves it within two units in the last place of 255.0 for the
+    others (measured: 400 -> 255.00000000000006, 1000 -> 254.99999999999994, 1e6 -> 254.99999999999997), which is why the property
+    is asserted on the outputs a resolve writes and bounded, not asserted, on v."""
+    ulp = np.spacing(np.float64(255.0))
+    for n, exposure in ((1, 1.0), (4, 1.0), (1, 0.25), (8, 0.5)):
+        s = white * n / exposure                                  # exact: n and 1 / exposure are powers of two
+        for gamma in (1, 2):
+            v = F.tone_reference(np.array([s, 2.0 * s, 0.5 * s]), n, exposure, white, gamma)
+            assert v.astype(np.float32)[0] == np.float32(255.0) and F.clip_reference(v).tolist()[:2] == [255, 255], (white, float(v[0]))
+            assert abs(v[0] - 255.0) <= 2 * ulp and v[1] > 255.0 + 4 * ulp and v[2] < 255.0 - 4 * ulp, (white, float(v[0]))
+            if white in (1e-3, 255.0):
+                assert v[0] == 255.0
+    x = np.linspace(0.0, white, 1001)
+    v = F.tone_reference(x, 1, 1.0, white, 1)
+    assert (np.diff(v) > 0).all() and v[0] == 0.0                  # the curve rises from 0 to 255
+    if white >= 255.0:
+        assert (v <= x * (1.0 + 1e-15)).all()                      # and compresses: not above the input (to rounding)
+
+
+def test_identity_at_n_1():
+    rng = np.random.default_rng(3)
+    f = np.concatenate([rng.uniform(-10.0, 700.0, 3998), [0.0, -0.0, np.nan, np.inf, 0.5, 254.5, 255.5]]).astype(np.float32)
+    f = f.reshape(3, 5, 267)
+    s = F.accumulate_reference(None, [f])
+    assert s.dtype == np.float64 and same_bits(s, f.astype(np.float64) + 0.0)
+    v = F.tone_reference(s, 1)
+    assert same_bits(v.astype(np.float32), (f + np.float32(0.0)))            # the pass's float32 frame, bit for bit (-0 + +0 = +0)
+    assert np.array_equal(F.clip_reference(v), F.clip_reference(f.astype(np.float64)))
+    # the sum rule: left to right, float64, and not the float32 sum
+    a, b, c = (np.full((3, 1, 1), x, np.float32) for x in (1e8, 1.0, -1e8))
+    assert F.accumulate_reference(None, [a, b, c])[0, 0, 0] == 1.0
+    assert F.accumulate_reference(np.full((3, 1, 1), 0.1), [b])[0, 0, 0] == 0.1 + 1.0
+    assert F.accumulate_reference(None, [np.full((3, 1, 1), -0.0, np.float32)])[0, 0, 0].tobytes() == np.float64(0.0).tobytes()
+    with pytest.raises(ValueError, match="float32"):
+        F.accumulate_reference(None, [np.zeros((3, 1, 1))])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Film's argument checks, before the library sees anything
+
+class _NoDevice:
+    """What Film touches of a Renderer, with every device call recorded."""
+    closed = False
+
+    def __init__(self, w=8, h=4):
+        self.w, self.h, self.calls = w, h, []
+
+    def malloc(self, n):
+        self.calls.append(("malloc", n))
+        return 4096
+
+    def free(self, d):
+        self.calls.append(("free", d))
+
+    def film_accumulate(self, *a):
+        self.calls.append(("accumulate",) + a)
+
+    def film_resolve(self, *a, **kw):
+        self.calls.append(("resolve",) + a)
+
+
+def test_film_value_errors():
+    with pytest.raises(ValueError, match="ray grid"):
+        Film(_NoDevice(None, None))
+    for x0, x1 in ((-1, 4), (4, 4), (0, 9), (5, 3)):
+        with pytest.raises(ValueError, match="column range"):
+            Film(_NoDevice(), x0, x1)
+    with pytest.raises(ValueError, match="RT_FILM_MAX_PIXELS"):
+        Film(_NoDevice(1, 2 ** 27 + 1))
+    r = _NoDevice()
+    with Film(r, 2, 6) as film:
+        assert r.calls == [("malloc", 24 * 4 * 4)] and (film.ws, film.h, film.passes) == (4, 4, 0)
+        p = L.rt_params()
+        for bad in (0, -3):
+            with pytest.raises(ValueError, match="passes"):
+                film.accumulate(p, bad)
+        with pytest.raises(ValueError, match="no pass"):
+            film.resolve()
+        with pytest.raises(ValueError, match="no pass"):
+            film.resolve_device(d_u8=1)
+        assert len(r.calls) == 1                                  # nothing reached the library
+        film.accumulate(p, 3)
+        film.accumulate(p, 2)
+        assert film.passes == 5 and [c[0] for c in r.calls[1:]] == ["accumulate", "accumulate"]
+        assert r.calls[1][1:] == (p, 2, 6, 3, True, 4096, 16, None) and r.calls[2][1:] == (p, 2, 6, 2, False, 4096, 16, None)
+        n = len(r.calls)
+        for kw, match in ((dict(exposure=0.0), "exposure"), (dict(exposure=float("nan")), "exposure"), (dict(exposure=float("inf")), "exposure"),
+                          (dict(exposure=-1.0), "exposure"), (dict(white=-1.0), "white"), (dict(white=float("nan")), "white"),
+                          (dict(white=float("inf")), "white"), (dict(gamma=3), "gamma"), (dict(gamma=0), "gamma"), (dict(gamma=1.5), "gamma"),
+                          (dict(flags=L.RT_FLAG_TYPED_BIAS), "flags"), (dict(flags=L.RT_FLAG_U8_RGB | 64), "flags"),
+                          (dict(u8=False, f32=False), "neither")):
+            with pytest.raises(ValueError, match=match):
+                film.resolve(**kw)
+        with pytest.raises(ValueError, match="both outputs"):
+            film.resolve_device()
+        with pytest.raises(ValueError, match="RT_FLAG_U8_HWC"):
+            film.resolve_device(d_u8=1, d_f32=2, flags=L.RT_FLAG_U8_HWC)
+        assert len(r.calls) == n
+        r.h = 5                                                   # the renderer's grid changed under the film
+        with pytest.raises(ValueError, match="frame is now"):
+            film.accumulate(p)
+        r.h = 4
+        film.clear()
+        assert film.passes == 0
+        film.accumulate(p)
+        assert r.calls[-1][5] is True                             # the pass after clear() resets the sum
+    assert r.calls[-1] == ("free", 4096)
+    with pytest.raises(ValueError, match="closed"):
+        film.accumulate(p)
+    for n_, e, wh, g in ((0, 1.0, 0.0, 1), (1, 0.0, 0.0, 1), (1, 1.0, -2.0, 1), (1, 1.0, 0.0, 4)):
+        with pytest.raises(ValueError):
+            F.tone_reference(np.zeros(3), n_, e, wh, g)
