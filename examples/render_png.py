@@ -5,6 +5,7 @@
                                   [--soft [--shadow-samples 4]] [--dof APERTURE [--focus-on-sphere K]]
                                   [--checker [--texture IMAGE]] [--lights] [--sky] [--out output/render.png]
                                   [--passes N [--exposure E] [--white W] [--gamma2]]
+                                  [--denoise [--denoise-levels N]] [--guides PREFIX]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -25,6 +26,11 @@ and its halo (rt_set_scene_sky), and raises the camera so that the horizon is in
 device, each a frame of the launch the other options describe, and their mean resolved there with --exposure E (default 1),
 highlights compressed so that --white W (colour units; default 0: none, values clip at 255) maps to 255, and --gamma2 (a square
 root for display).  For example --sky --dof 0.1 --passes 64 --white 400: 64 lens samples per pixel and a sun that is not flat white.
+
+--denoise filters the film's mean before it is resolved (rt_render_guides, rt_film_denoise: an edge-stopping filter guided by
+what the pinhole camera hits first), with --denoise-levels N iterations (default 4); without --passes it takes four passes.  For
+example --sky --soft --shadow-samples 1 --passes 4 --denoise --white 400.  --guides PREFIX writes the guides as PREFIX_normal.png,
+PREFIX_depth.png, PREFIX_albedo.png and PREFIX_id.png.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -67,9 +73,14 @@ def main():
     ap.add_argument("--exposure", type=float, default=1.0, help="--passes: the mean is multiplied by this")
     ap.add_argument("--white", type=float, default=0.0, help="--passes: compress highlights so that this value maps to 255 (0: clip)")
     ap.add_argument("--gamma2", action="store_true", help="--passes: square-root display gamma")
+    ap.add_argument("--denoise", action="store_true", help="filter the film's mean with the edge-stopping denoiser (four passes unless --passes)")
+    ap.add_argument("--denoise-levels", type=int, default=4, metavar="N", help="--denoise: filter iterations, 0..6")
+    ap.add_argument("--guides", default=None, metavar="PREFIX", help="write the first-hit guides as PREFIX_normal/_depth/_albedo/_id.png")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
+    if a.denoise and a.passes <= 0:
+        a.passes = 4
     euler = [0, -12, 0] if a.sky else [0, -30, 0]                   # --sky: the horizon a third of the way down the picture
     cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=euler)
     with pkg.Renderer(0) as r:
@@ -142,7 +153,9 @@ def main():
         if a.passes > 0:                                        # a film: the passes summed and resolved on the device
             with pkg.Film(r) as film:
                 film.accumulate(p, a.passes)
-                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags)[0]
+                if a.denoise:
+                    film.denoise(levels=a.denoise_levels)
+                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags, denoised=a.denoise)[0]
                 r.timer_begin()
                 for _ in range(a.frames):                       # (timed: one more pass into the sum, per pass)
                     film.accumulate(p, 1)
@@ -157,9 +170,21 @@ def main():
                 r.render_device(p, 0, w, dev, None, w)
             ms = r.timer_end() / a.frames
             r.free(dev)
+        if a.guides:                                            # normal, depth, albedo and id of what the pinhole camera hits first
+            from PIL import Image
+            with pkg.Film(r) as film:
+                g = film.guides()                               # float32 (8, w, h)
+            hit = g[7] >= 0
+            far = float(g[3][hit].max()) if hit.any() else 1.0
+            ids = g[7].astype(np.int64) + 1                     # (0: nothing)
+            pictures = {"normal": np.where(hit, (g[0:3] * 0.5 + 0.5) * 255.0, 0.0), "depth": np.where(hit, (1.0 - g[3] / far) * 255.0, 0.0)[None].repeat(3, 0),
+                        "albedo": g[4:7], "id": np.stack([(ids * 97) % 256, (ids * 57) % 256, (ids * 181) % 256]) * (ids > 0)}
+            os.makedirs(os.path.dirname(os.path.abspath(a.guides)), exist_ok=True)
+            for kind, pic in pictures.items():
+                Image.fromarray(np.clip(np.rint(pic), 0, 255).astype(np.uint8).transpose(2, 1, 0)).save(f"{a.guides}_{kind}.png")
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

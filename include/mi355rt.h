@@ -555,6 +555,83 @@ typedef struct rt_film_tone {
 int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n,
                     const rt_film_tone *tone, void *d_u8, void *d_f32, int64_t out_stride, void *stream);
 
+/* The denoiser: a few passes, then a filter that knows where the geometry's edges are.  Two entry points: the first-hit guides of
+ * a frame (also useful on their own, as masks and for compositing), and an edge-stopping a-trous filter on a film's mean.
+ * RT_ABI_VERSION is unchanged: callers detect these entry points by their symbols.
+ *
+ * rt_render_guides: what the pinhole camera sees first.  The output is float32: element [g, x, y] (x0 <= x < x1) is at
+ * d_guides[g*plane_stride + (x-x0)*h + y], the addressing of rt_render_device, so a full-frame buffer can be filled slab by slab
+ * in place.  The call uses the scene, camera and grid that are current at the call (they travel by value, as in every launch);
+ * it needs no rt_params and no material table, and works on scenes set through every rt_set_scene* entry.
+ * For pixel (x, y) the ray is the RT_AA_NONE primary ray without a lens: P the pixel point (the closed form of rt_set_raygen or the
+ * explicit grid of rt_set_pixel_loc), d = normalize(R P), o = the camera origin.  A lens set with rt_set_lens is ignored: the
+ * guides are those of the sharp image.  (t, idx, type) = get_intersection(o, d) (trace.py:7-41), exactly as the render kernels
+ * evaluate it: the same query with the same culls, not a second intersection routine.
+ *   plane   hit                                      miss (404)
+ *   0..2    (float)N                                 +0.0f
+ *   3       (float)t                                 +0.0f
+ *   4..6    albedo                                   +0.0f
+ *   7       object id                                -1.0f
+ * N is the float64 normal trace() uses (trace.py:66/71): for a sphere normalize(Pt - c) with Pt = linear_comb(o, d, 1.0, t), for a
+ * plane the normalised float32 normal as the render kernels form it.  Albedo is the object's own float32 colour; when the scene
+ * has textures and the object's texture id is >= 0 it is the texel the render kernels' first trace would use: the same point Pt
+ * and the same texel index (rt_set_scene_textures).  Object id: a sphere has (float)k with k the caller's sphere index, a plane
+ * (float)(S + k); ids stay below 2^24, so they are exact in float32.
+ * Asynchronous on `stream` (NULL = the context's stream).  RT_ERR_BAD_ARG for a NULL buffer, plane_stride < (x1-x0)*h, and whatever
+ * rt_render_device refuses for x0, x1; RT_ERR_STATE without a scene, camera or grid; the buffer is then untouched.
+ * What the guides are not: a pixel that shows a mirror or glass carries the mirror's or the glass's own normal, albedo and id, not
+ * those of what is seen in or through it, and under a lens the guides stay those of the pinhole image.
+ *
+ * rt_film_denoise: an edge-stopping a-trous filter on the film's mean.  d_sum is a film sum of n passes of a ws x h frame;
+ * d_guides that frame's guides (planes 0..2 and 7 are always read, planes 4..6 when demodulate is set); d_out a float64 buffer of
+ * three planes laid out like a sum, which receives the filtered MEAN: the caller tone-maps it with rt_film_resolve and n = 1
+ * (filtering happens in linear colour, before compression).  d_work is a second such buffer, owned by the caller (the library
+ * allocates nothing); it may be NULL when levels <= 1.  Which of the two holds which level is the library's business; the result
+ * always ends in d_out.  d_out and d_work must not overlap d_sum, d_guides or each other: equal pointers are refused, partial
+ * overlap is the caller's error.
+ * Per pixel p in float64, no fused multiply-add, in this order (x is the slow axis of the layout, so taps at dy are neighbours in
+ * memory):
+ *   m_0[c][p] = s[c][p] / (double)n
+ *   demodulate:  a[c][p] = max((double)albedo_c[p], 1.0);   m_0[c][p] = m_0[c][p] / a[c][p]
+ *   levels == 0 (with or without demodulate):  out[c][p] = s[c][p] / (double)n, and nothing else is evaluated
+ *   for i = 0 .. levels-1:      step = 1 << i;   q_i = sigma / 2^i  (exact)
+ *       W = +0.0; A_c = +0.0
+ *       for dx = -2..2 (outer), dy = -2..2 (inner):   q = (p.x + step*dx, p.y + step*dy)
+ *           q outside [0,ws) x [0,h):  skip
+ *           id[q] != id[p]:            skip
+ *           id[p] >= 0:  cn = ((nx_p*nx_q) + (ny_p*ny_q)) + (nz_p*nz_q)   (float32 normals widened to double)
+ *                        !(cn > 0):  skip;    log2(normal_shin) times:  cn = cn*cn
+ *           id[p] <  0:  cn = 1.0                                          (sky pixels: the colour weight alone)
+ *           sigma > 0:   e_c = (m_i[c][q] - m_i[c][p]) / q_i;  d2 = (e_0*e_0 + e_1*e_1) + e_2*e_2;  wc = 1.0 / (1.0 + d2)
+ *           else:        wc = 1.0
+ *           w = ((k[dx] * k[dy]) * cn) * wc          k = (1/16, 1/4, 3/8, 1/4, 1/16)  (the B3 spline)
+ *           W = W + w;   A_c = A_c + w * m_i[c][q]
+ *       m_{i+1}[c][p] = A_c / W                       (the centre tap always contributes 9/64, so W > 0)
+ *   out[c][p] = demodulate ? m_levels[c][p] * a[c][p] : m_levels[c][p]
+ * max(v, 1.0) is v > 1.0 ? v : 1.0.  The colour weight is rational rather than exp(), and the normal weight is squarings rather than
+ * pow(): the bytes do not depend on a math library (as shin, sharp and gamma 2).  Sums are assumed finite: a non-finite sum (or
+ * guide) gives unspecified values but does not fault.
+ * The filter sees only the buffer it is given: taps do not cross a slab's edge, so a multi-rank caller denoises the assembled frame.
+ * RT_ERR_BAD_ARG for a NULL d_sum, d_guides, dn or d_out; n < 1; levels outside 0..6; a normal_shin that is not one of the eleven
+ * powers of two 1..1024; a sigma that is not 0 and not (finite and > 0); a demodulate that is not 0 or 1; a reserved that is not 0;
+ * ws < 1, h < 1 or ws*h > RT_FILM_MAX_PIXELS; any of the four strides < ws*h (work_stride counts when d_work is given);
+ * d_work == NULL with levels >= 2; equal buffers.  The outputs are then untouched.  Asynchronous on `stream`; it needs no scene. */
+#define RT_GUIDE_PLANES 8
+
+int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream);
+
+typedef struct rt_denoise {
+    int32_t levels;       /* 0..6: filter iterations; iteration i has taps step 2^i apart */
+    int32_t normal_shin;  /* 1, 2, 4, ..., 1024: exponent of the normal weight, as log2 exact squarings */
+    double  sigma;        /* 0: no colour weight; else finite, > 0, colour units at level 0, halved per level */
+    int32_t demodulate;   /* 0 or 1: filter colour / albedo and multiply back */
+    int32_t reserved;     /* must be 0 */
+} rt_denoise;
+
+int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n,
+                    const void *d_guides, int64_t guide_stride, const rt_denoise *dn,
+                    void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

@@ -17,6 +17,7 @@ RT_RENDER_SLOTS = 4
 RT_MAX_TEXTURES, RT_MAX_TEXTURE_DIM, RT_MAX_TEXELS = 64, 4096, 1 << 22
 RT_SKY_DOUBLES = 24
 RT_FILM_MAX_PIXELS = 1 << 27
+RT_GUIDE_PLANES = 8
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -47,6 +48,13 @@ class rt_film_tone(C.Structure):
     """rt_film_resolve's tone (include/mi355rt.h; the arithmetic in numpy: film.tone_reference): exposure finite and > 0; white 0 (no
     compression) or finite and > 0, the colour that maps to 255; gamma 1 or 2; flags RT_FLAG_U8_RGB | RT_FLAG_U8_HWC only."""
     _fields_ = [("exposure", C.c_double), ("white", C.c_double), ("gamma", C.c_int32), ("flags", C.c_int32)]
+
+
+class rt_denoise(C.Structure):
+    """rt_film_denoise's settings (include/mi355rt.h; the arithmetic in numpy: denoise.denoise_reference): levels 0..6; normal_shin
+    1, 2, 4, ..., 1024; sigma 0 (no colour weight) or finite and > 0; demodulate 0 or 1; reserved 0."""
+    _fields_ = [("levels", C.c_int32), ("normal_shin", C.c_int32), ("sigma", C.c_double), ("demodulate", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
@@ -89,6 +97,9 @@ PROTOTYPES = {
                                      C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "rt_film_accumulate": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
     "rt_film_resolve": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_film_tone), _vp, _vp, C.c_int64, _vp]),
+    "rt_render_guides": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
+    "rt_film_denoise": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, C.POINTER(rt_denoise), _vp, C.c_int64,
+                                  _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -108,6 +119,10 @@ PROTOTYPES = {
     "rt_memcpy_d2h": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
 }
 
+# Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
+# times such a build beside this one), and Renderer raises where one is called.
+LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise")
+
 _lib = None
 
 
@@ -118,6 +133,8 @@ def bind(path):
                           f"(or `make -C python-ray-tracer_amd/csrc`); there is no CPU fallback")
     lib = C.CDLL(path)
     for name, (res, args) in PROTOTYPES.items():
+        if name in LATER_ENTRIES and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
     if lib.rt_abi_version() != RT_ABI_VERSION:

@@ -3,8 +3,10 @@
 // rt_create fails and nothing renders.
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
+#include "rt_denoise.h"
 #include "rt_film.h"
 #include "rt_geometry.h"
+#include "rt_guides.h"
 #include "rt_plan.h"
 #include "rt_scene.h"
 
@@ -74,6 +76,7 @@ struct rt_ctx {
     int w = 0, h = 0;
     double px = 0, y0 = 0, dy = 0, z0 = 0, dz = 0;
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
+    size_t guides_lds_set = 0;                 // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback: a MEASURING launch stores its tile blocks' costs; a small kernel behind it (same stream) turns
     // them into a dispatch order (rt::order_kernel).  The order lives in two buffers: launches dispatch in order[cur]
@@ -997,6 +1000,123 @@ int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
     hipLaunchKernelGGL(rt::film_resolve_kernel, dim3(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
                        stream ? (hipStream_t)stream : ctx->stream, a);
     RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// The first-hit guides: one launch of the guides kernel (rt_guides.h) per dispatch the slab needs, in plain tile order.  Scene,
+// camera and grid travel by value as in launch(); the cull tables are the stream's own (acquire_tables), built for rays that start
+// at the camera and go no further than the first hit.
+int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: d_guides is NULL");
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
+    if (!ctx->have_cam) return fail(ctx, RT_ERR_STATE, "rt_set_camera has not been called");
+    if (!ctx->have_grid) return fail(ctx, RT_ERR_STATE, "rt_set_raygen / rt_set_pixel_loc has not been called");
+    if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
+    if (plane_stride < (int64_t)(x1 - x0) * ctx->h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    rt::KParams k;
+    std::memset(&k, 0, sizeof k);
+    k.scene = (const double *)ctx->scene[ctx->scene_cur].p;
+    {
+        auto &rd = ctx->scene_readers[ctx->scene_cur];
+        if (std::find(rd.begin(), rd.end(), st) == rd.end()) rd.push_back(st);
+    }
+    k.nframes = 1;
+    k.pixel_loc = ctx->explicit_grid ? (const double *)ctx->pixel_loc.p : nullptr;
+    k.out_f32 = (float *)d_guides;
+    k.plane_stride = plane_stride;
+    k.w = ctx->w; k.h = ctx->h; k.x0 = x0; k.x1 = x1;
+    k.S = ctx->lay.S; k.P = ctx->lay.P; k.L = ctx->lay.L; k.NC = ctx->lay.NC; k.plane_codes = ctx->lay.plane_codes;
+    k.lanes_primary = ctx->lanes_primary;
+    k.tiles_y = (int)rt_geo_tiles(ctx->h);
+    k.px = ctx->px; k.y0 = ctx->y0; k.dy = ctx->dy; k.z0 = ctx->z0; k.dz = ctx->dz;
+    std::memcpy(k.cam_o, ctx->cam_o, sizeof k.cam_o);
+    std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
+    const int textured = ctx->lay.T > 0 ? 1 : 0;
+    if (textured) { k.lens.tex = ctx->lay.tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
+    k.anchors = rt::anchors_of(ctx->lay);
+    const rt::GuidesPlan plan = rt::plan_guides(ctx->lay, ctx->knobs, k.anchors);
+    const double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
+    k.extent2 = (float)(1.0001 * (cam2 > ctx->lay.extent2 ? cam2 : ctx->lay.extent2));
+    {   // (as launch() with depth 0: every ray starts at the camera)
+        const double reach = std::sqrt(cam2) + 999.0 + std::sqrt(ctx->lay.extent2);
+        k.floor_anch = (float)(0x1p-39 * reach * reach);
+    }
+    int rc = acquire_tables(ctx, k, st, &k.ftab);
+    if (rc != RT_OK) return rc;
+    const void *fn = plan.mode == 2 ? (const void *)rt::guides_kernel<2> : (plan.mode == 1 ? (const void *)rt::guides_kernel<1> : (const void *)rt::guides_kernel<0>);
+    if (plan.lds > 48 * 1024 && plan.lds > ctx->guides_lds_set) {
+        for (const void *kf : {(const void *)rt::guides_kernel<0>, (const void *)rt::guides_kernel<1>, (const void *)rt::guides_kernel<2>})
+            RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+        ctx->guides_lds_set = plan.lds;
+    }
+    rt::div_magic((unsigned)k.tiles_y, k.tiles_y_magic, k.tiles_y_shift);
+    // at most RT_GEO_MAX_ITEMS work-items per dispatch: a slab beyond that goes out as narrower column slabs, as dispatch() cuts a frame
+    const rt_geo_plan g = rt_geo_plan_of(x0, x1, ctx->h, rt::GUIDE_WPW, 1);
+    for (long long s = 0; s < g.nslabs; ++s) {
+        const long long sx0 = x0 + s * g.slab_tiles * rt::TILE, sx1 = std::min<long long>(x1, sx0 + g.slab_tiles * rt::TILE);
+        rt::KParams ks = k;
+        ks.x0 = (int)sx0; ks.x1 = (int)sx1;
+        ks.ntiles = (int)(rt_geo_tiles(sx1 - sx0) * k.tiles_y);
+        ks.out_f32 += (sx0 - x0) * ctx->h;
+        int tex = textured;
+        void *args[] = {(void *)&ks, (void *)&tex};
+        const unsigned blocks = (unsigned)((ks.ntiles + rt::GUIDE_WPW - 1) / rt::GUIDE_WPW);
+        RT_HIP(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64 * rt::GUIDE_WPW), args, plan.lds, st));
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// The film's filter: one launch of the denoise kernel (rt_denoise.h) per level, ping-pong between d_out and d_work so that the last
+// level writes d_out; levels == 0 is one launch that writes the mean.
+int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const void *d_guides, int64_t guide_stride,
+                    const rt_denoise *dn, void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_sum is NULL");
+    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_guides is NULL");
+    if (!dn) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: dn is NULL");
+    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_out is NULL");
+    if (n < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: n < 1");
+    if (dn->levels < 0 || dn->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: levels outside 0..6");
+    int nsq = -1;
+    for (int i = 0; i <= 10; ++i) if (dn->normal_shin == (1 << i)) nsq = i;
+    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: normal_shin must be 1, 2, 4, ..., 1024");
+    if (!(dn->sigma == 0.0 || (std::isfinite(dn->sigma) && dn->sigma > 0.0)))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: sigma must be 0, or finite and > 0");
+    if (dn->demodulate != 0 && dn->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: demodulate must be 0 or 1");
+    if (dn->reserved != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: reserved must be 0");
+    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: ws*h outside 1..RT_FILM_MAX_PIXELS");
+    const long long npx = (long long)ws * h;
+    if (sum_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: a plane stride is smaller than the frame");
+    if (!d_work && dn->levels >= 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_work is NULL with levels >= 2");
+    if (d_out == d_sum || d_out == d_guides || (d_work && (d_work == d_sum || d_work == d_guides || d_work == d_out)))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_out and d_work must be buffers of their own");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    rt::DenoiseArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
+    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dn->demodulate; a.n = (double)n;
+    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
+    const int levels = dn->levels;
+    const double *src = (const double *)d_sum;
+    long long src_stride = sum_stride;
+    for (int i = 0; i < (levels ? levels : 1); ++i) {
+        const bool to_out = rt::denoise_to_out(levels, i);
+        a.src = src; a.src_stride = src_stride;
+        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
+        rt::denoise_level(a, levels, i, dn->sigma);
+        hipLaunchKernelGGL(rt::denoise_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
+        RT_HIP(ctx, hipGetLastError());
+        src = a.dst; src_stride = a.dst_stride;
+    }
     return RT_OK;
 }
 

@@ -184,6 +184,26 @@ inline LaunchPlan plan_launch(const SceneLayout &lay, const PlanKnobs &kn, doubl
     return pl;
 }
 
+// rt_render_guides (rt_guides.h: guides_kernel): the table mode of its closest_hit and the dynamic LDS of its four-wave workgroups.
+// The mode is the one plan_launch gives a launch of the same scene without a material table, AA or flags (0, 1 or 2: what keeps
+// the LDS image of a scene of RT_MAX_SPHERES small); the image is that of the register variant of that mode: no per-thread slots,
+// no pixel offsets, no material block.
+struct GuidesPlan {
+    int mode;
+    size_t lds;
+};
+
+inline GuidesPlan plan_guides(const SceneLayout &lay, const PlanKnobs &kn, int anchors)
+{
+    SceneLayout l = lay;
+    l.M = 0; l.soft_n = 0; l.T = 0; l.lit = false; l.sky = false;
+    const LaunchPlan pl = plan_launch(l, kn, 0.0, false, 0, false, anchors);
+    GuidesPlan g;
+    g.mode = pl.shape.mode >= 2 ? 2 : pl.shape.mode;
+    g.lds = lds_bytes(l, anchors, Family::PLAIN, Shape{false, false, 4, false, false, g.mode});
+    return g;
+}
+
 // The shape of the dispatch order of a planned launch over the grid g (rt_geo_plan_of with the plan's workgroup size; one dispatch).
 struct OrderShape {
     bool feedback;   // the launch dispatches in a measured order (and may measure)

@@ -5,10 +5,23 @@ the contract's second statement, as scene.texel_index, light_terms and sky_color
     with Film(renderer) as film:
         film.accumulate(params, passes=64)            # seeds params.seed, params.seed + 1, ...
         image, _ = film.resolve(white=400.0, gamma=2, flags=RT_FLAG_U8_HWC | RT_FLAG_U8_RGB)
+
+Film.guides, Film.denoise and resolve(denoised=True) put the denoiser behind the same object (rt_render_guides, rt_film_denoise;
+their arithmetic in numpy is in denoise.py):
+
+        film.accumulate(params, passes=4)
+        film.denoise()                                # first-hit guides, then the edge-stopping filter on the mean
+        image, _ = film.resolve(white=400.0, denoised=True)
 """
 import numpy as np
 
 from . import _lib as L
+from .denoise import check_denoise
+
+# Film.denoise's default sigma, in the units the filter sees: colour / albedo with demodulation, so about 0..1 and not 0..255.  The
+# best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 at levels 4, normal_shininess 32 with demodulation on four passes of the
+# soft_default_64_d4 scene (one shadow sample) against its 1024-pass mean (DESIGN.md, Denoiser)
+DENOISE_SIGMA = 0.125
 
 _TONE_FLAGS = L.RT_FLAG_U8_RGB | L.RT_FLAG_U8_HWC
 
@@ -98,12 +111,17 @@ class Film:
         self.ws = x1 - x0
         self.passes = 0
         self.d_sum = renderer.malloc(24 * self.ws * self.h)
+        self.d_guides = self.d_denoised = self.d_work = None      # allocated by guides() and denoise()
+        self.denoised_passes = 0                                  # the pass count the filtered mean in d_denoised belongs to (0: none)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
-        if d and not self.renderer.closed:
-            self.renderer.free(d)
+        extra = [getattr(self, n, None) for n in ("d_guides", "d_denoised", "d_work")]
+        self.d_guides = self.d_denoised = self.d_work = None
+        for e in extra + [d]:
+            if e and not self.renderer.closed:
+                self.renderer.free(e)
 
     def __enter__(self):
         return self
@@ -136,13 +154,64 @@ class Film:
         self.passes += passes
 
     def clear(self):
-        """Forget every pass: the next accumulate starts from zero."""
+        """Forget every pass: the next accumulate starts from zero.  The guides stay (they do not depend on the passes)."""
         self.passes = 0
+        self.denoised_passes = 0
+
+    # -- the denoiser -----------------------------------------------------------------------
+    def guides(self, stream=None):
+        """Render the first-hit guides of the film's slab (Renderer.render_guides) with the renderer's current scene, camera and
+        grid, keep them on the device for denoise(), and return them: float32 (8, ws, h).  clear() does not drop them; a scene,
+        camera or grid change is the caller's cue to call this again.  Waits for the stream."""
+        self._live()
+        if self.renderer.h != self.h or self.x1 > (self.renderer.w or 0):
+            raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
+                             f"[{self.x0}, {self.x1}) of height {self.h}")
+        r, n = self.renderer, self.ws * self.h
+        if not self.d_guides:
+            self.d_guides = r.malloc(4 * L.RT_GUIDE_PLANES * n)
+        r.render_guides(self.x0, self.x1, self.d_guides, n, stream)
+        r.sync(stream)
+        out = np.empty((L.RT_GUIDE_PLANES, self.ws, self.h), np.float32)
+        r.d2h(out, self.d_guides)
+        return out
+
+    def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None):
+        """Filter the mean of the passes so far (Renderer.film_denoise: an edge-stopping a-trous filter guided by guides(), which is
+        called first if it has not been) into the film's own buffers; resolve(denoised=True) shows the result.  levels 0..6,
+        normal_shininess 1, 2, 4, ..., 1024, sigma 0 (no colour weight) or > 0 in colour units, demodulate: filter colour / albedo.
+        sigma is measured in what the filter sees: colour units (0..255) without demodulation, colour / albedo (about 0..1) with it.
+        The default, DENOISE_SIGMA = 1/8, is the best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 recorded in DESIGN.md (Denoiser): four
+        passes of the soft_default_64_d4 scene with one shadow sample against its 1024-pass mean, RMSE x0.85; the values 4 to 64
+        switch the colour weight off under demodulation and make that frame worse (x2.7 to x2.9).  Asynchronous."""
+        self._live()
+        if self.passes < 1:
+            raise ValueError("the film holds no pass yet")
+        levels, shin, sigma, demodulate = check_denoise(levels, normal_shininess, sigma, demodulate)
+        r, n = self.renderer, self.ws * self.h
+        if not self.d_guides:
+            self.guides(stream)
+        if not self.d_denoised:
+            self.d_denoised = r.malloc(24 * n)
+        if levels >= 2 and not self.d_work:
+            self.d_work = r.malloc(24 * n)
+        r.film_denoise(self.d_sum, self.ws, self.h, self.passes, self.d_guides, self.d_denoised, self.d_work, levels=levels,
+                       normal_shin=shin, sigma=sigma, demodulate=demodulate, stream=stream)
+        self.denoised_passes = self.passes
+
+    def _source(self, denoised):
+        """(sum or filtered mean, its n) of a resolve."""
+        if not denoised:
+            return self.d_sum, self.passes
+        if not self.denoised_passes or self.denoised_passes != self.passes:
+            raise ValueError("the film has no filtered mean of its current passes: call denoise() first")
+        return self.d_denoised, 1
 
     # -- frames -----------------------------------------------------------------------------
-    def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None):
+    def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None,
+                       denoised=False):
         """The mean of the passes so far, tone-mapped, into caller-owned device memory (raw addresses), laid out as
-        Renderer.render_device's outputs.  Asynchronous."""
+        Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead.  Asynchronous."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
@@ -151,18 +220,20 @@ class Film:
             raise ValueError("both outputs are None")
         if int(flags) & L.RT_FLAG_U8_HWC and d_f32:
             raise ValueError("RT_FLAG_U8_HWC is a uint8 layout: resolve the float32 frame in a separate call")
-        self.renderer.film_resolve(self.d_sum, self.ws, self.h, self.passes, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
+        src, n = self._source(denoised)
+        self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
                                    flags=flags, out_stride=out_stride, stream=stream)
 
-    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0):
+    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False):
         """(uint8 or None, float32 or None) host arrays shaped like Renderer.render's: (3, ws, h), or (h, ws, 3) for the uint8
-        frame with RT_FLAG_U8_HWC.  Waits for the context's stream."""
+        frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered.  Waits for the context's stream."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         check_tone(self.passes, exposure, white, gamma, flags)
         if not u8 and not f32:
             raise ValueError("neither u8 nor f32 is asked for")
+        self._source(denoised)
         r, n = self.renderer, self.ws * self.h
         hwc = bool(int(flags) & L.RT_FLAG_U8_HWC)
         out8 = np.empty((self.h, self.ws, 3) if hwc else (3, self.ws, self.h), np.uint8) if u8 else None
@@ -170,7 +241,7 @@ class Film:
         d8 = r.malloc(3 * n) if u8 else None
         d32 = r.malloc(12 * n) if f32 else None
         try:
-            kw = dict(exposure=exposure, white=white, gamma=gamma)
+            kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised)
             if hwc:                                             # (the image layout is uint8 only: two calls)
                 self.resolve_device(d8, None, flags=flags, **kw)
                 if f32:

@@ -414,6 +414,33 @@ class Renderer:
                                               C.byref(tone), C.c_void_p(d_u8) if d_u8 else None, C.c_void_p(d_f32) if d_f32 else None,
                                               int(out_stride), C.c_void_p(stream) if stream else None))
 
+    def _later_entry(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise RenderError(L.RT_ERR_STATE, f"this build of the library has no {name}")
+        return fn
+
+    def render_guides(self, x0, x1, d_guides, plane_stride=None, stream=None):
+        """The first-hit guides of columns [x0, x1) into caller-owned device memory (rt_render_guides): float32
+        (RT_GUIDE_PLANES, x1-x0, h), planes normal (3), distance, albedo (3), object id, of the pinhole camera's RT_AA_NONE primary
+        ray (a lens is ignored); plane_stride elements between planes.  Asynchronous.  In numpy: denoise.guides_reference."""
+        if plane_stride is None:
+            plane_stride = (int(x1) - int(x0)) * (self.h or 0)
+        self._check(self._later_entry("rt_render_guides")(self._ctx, int(x0), int(x1), C.c_void_p(d_guides) if d_guides else None,
+                                                          int(plane_stride), C.c_void_p(stream) if stream else None))
+
+    def film_denoise(self, d_sum, ws, h, n, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, sigma=0.0, demodulate=1,
+                     sum_stride=None, guide_stride=None, out_stride=None, work_stride=None, stream=None, reserved=0):
+        """The edge-stopping a-trous filter on the mean of the sum of n passes at d_sum, guided by d_guides, into the float64
+        (3, ws, h) buffer d_out (rt_film_denoise); d_work is a second such buffer (None allowed for levels <= 1).  The result is a
+        mean: resolve it with film_resolve(..., n=1).  Asynchronous.  In numpy: denoise.denoise_reference."""
+        npx = int(ws) * int(h)
+        sum_stride, guide_stride, out_stride, work_stride = (npx if v is None else int(v) for v in (sum_stride, guide_stride, out_stride, work_stride))
+        dn = L.rt_denoise(int(levels), int(normal_shin), float(sigma), int(demodulate), int(reserved))
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_denoise")(self._ctx, vp(d_sum), sum_stride, int(ws), int(h), int(n), vp(d_guides), guide_stride,
+                                                         C.byref(dn), vp(d_out), out_stride, vp(d_work), work_stride, vp(stream)))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
         if stream:
