@@ -1,9 +1,12 @@
 // mi355rt.hip — host side of libmi355rt.so: the C ABI of include/mi355rt.h over the gfx950
 // render kernel in rt_device.h.  HIP only (no torch, no CPU fallback): without a HIP device
-// rt_create fails and nothing renders.
+// rt_create fails and nothing renders.  What a call decides before it touches the device lives in
+// HIP-free headers: the packed scene (rt_scene.h), the launch arithmetic (rt_geometry.h), the
+// launch's kernel and order shape (rt_plan.h), the dispatch-order feedback (rt_feedback.h).
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_denoise.h"
+#include "rt_feedback.h"
 #include "rt_film.h"
 #include "rt_geometry.h"
 #include "rt_guides.h"
@@ -18,6 +21,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -34,7 +38,6 @@ struct Buf {
 
 }  // namespace
 
-#define RT_FEEDBACK_SLOTS 8
 #define RT_SCENE_RING 4
 #define RT_COUNT_WORDS (4 + 2 * (RT_MAX_DEPTH + 1))   /* ray counters + per bounce {waves, alive lanes} */
 #define RT_RENDER_CHUNKS 8   /* upper bound; the pipeline uses ctx->render_chunks of them */
@@ -78,39 +81,12 @@ struct rt_ctx {
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
     size_t guides_lds_set = 0;                 // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
-    // Scheduler feedback: a MEASURING launch stores its tile blocks' costs; a small kernel behind it (same stream) turns
-    // them into a dispatch order (rt::order_kernel).  The order lives in two buffers: launches dispatch in order[cur]
-    // while a measuring launch's order kernel writes order[cur ^ 1]; the context switches to the new one when a later
-    // launch (on any stream) finds the order kernel's event complete — so no stream ever waits for another stream's
-    // measuring launch (round 2: the other streams' first launch in a new order waited for it, and a measuring launch
-    // waited for everything the other streams had queued; with a camera that moves every frame that was a pipeline
-    // bubble per measurement).  The buffer a measurement overwrites was last read by launches queued before the previous
-    // switch; events recorded on their streams AT that switch (complete long before they are waited on) fence them.
-    struct Feedback {
+    // Scheduler feedback (rt_feedback.h has the rules and the slots' host state; the device buffers stay here)
+    struct Feedback : rt::FeedbackSlot {
         Buf cost, gtmp, btmp, order[2]; // per-block costs of the measuring launch, order_kernel's scratch, the dispatch orders
-        struct Key {                  // launch geometry the orders were built for (valid = false: none)
-            bool valid = false;
-            int x0 = 0, x1 = 0, h = 0, aa = 0, depth = 0, spp = 0, wpw = 0;
-            bool operator==(const Key &o) const
-            {
-                return valid && o.valid && x0 == o.x0 && x1 == o.x1 && h == o.h && aa == o.aa && depth == o.depth &&
-                       spp == o.spp && wpw == o.wpw;
-            }
-        } key;
-        int cur = 0;
-        bool have = false;            // order[cur] holds a complete order
-        bool building = false;        // a measuring launch and its order kernel are in flight, writing order[cur ^ 1]
-        unsigned long long epoch = 0; // ctx->epoch the costs behind order[cur] were measured under
-        unsigned long long build_epoch = 0;   // ... behind the order being built
-        int builds = 0;               // consecutive orders built under `epoch`
-        int since = 0;                // launches that used the order under a LATER epoch (moving camera) since the last measurement
-        hipEvent_t done = nullptr;    // recorded behind every order kernel
-        std::vector<hipStream_t> users;                            // streams that launched in order[cur] since the last switch
-        std::vector<std::pair<hipStream_t, hipEvent_t>> fence;     // recorded at the last switch: what may still read order[cur ^ 1]
-        std::vector<hipEvent_t> spare;
-        unsigned long long stamp = 0; // last use (the least recently used geometry is replaced)
-    } fbs[RT_FEEDBACK_SLOTS];         // one per launch geometry in use: slabs, chunks and AA modes do not evict each other
-    unsigned long long fb_stamp = 0;
+    } fbs[RT_FEEDBACK_SLOTS];
+    rt::FeedbackBook book;
+    rt_ctx() { for (int i = 0; i < RT_FEEDBACK_SLOTS; ++i) book.slot[i] = &fbs[i]; }
     rt_stats stats = {};              // host-side launch counters (the ray counters live in `counts`)
     Buf counts;                       // 4 x uint64 on the device: ray counters of RT_FLAG_COUNT_RAYS launches
     std::vector<std::pair<hipStream_t, Buf>> lattice;   // per launching stream: float64 lattice samples (RT_AA_REFERENCE)
@@ -375,23 +351,12 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
 }
 
 using Feedback = rt_ctx::Feedback;
-int feedback_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out);
+static_assert(std::is_convertible<hipStream_t, void *>::value && std::is_convertible<hipEvent_t, void *>::value,
+              "rt_feedback.h keeps streams and events as opaque handles");
+int feedback_slot(rt_ctx *ctx, const rt::FeedbackKey &key, Feedback **out);
 int switch_order(rt_ctx *ctx, Feedback &f);
 int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt_geo_plan &g, const rt::OrderShape &os,
-               Feedback &f, hipStream_t stream, int nframes, int64_t frame_stride);
-
-// An order built for this launch geometry is a valid permutation whatever has happened to scene and camera since: only
-// how well it balances the end of the launch depends on them.
-//  * Nothing that decides a tile's cost has changed since the order was rebuilt twice (once from plain tile order, once
-//    from longest-first order): the costs are the same again, so launches neither measure nor rebuild — they dispatch
-//    in that order, on any stream.
-//  * Something has changed (rt_set_* bumped the epoch — a moving camera does so with every frame): launches still
-//    dispatch in the order there is, and only every `remeasure`-th of them measures its tiles again (under that order)
-//    and rebuilds.  Round 2 measured and rebuilt with every frame of a moving camera: +11 us per frame.
-bool order_settled(const rt_ctx *ctx, const Feedback &f)
-{
-    return f.have && (f.epoch == ctx->epoch ? f.builds >= 2 : f.since < ctx->remeasure);
-}
+               Feedback *f, hipStream_t stream, int nframes, int64_t frame_stride);
 
 // One launch of the planned kernel over the tiles k describes, cut into pieces that one dispatch holds and one dispatch order
 // serves; each piece finds its feedback slot, switches to a finished order and goes out (launch_one).
@@ -428,94 +393,67 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPl
         return RT_OK;
     }
     const rt::OrderShape os = rt::order_shape(plan, ctx->knobs, p->flags, g);
-    static Feedback none;                                      // RT_FLAG_NO_FEEDBACK / one-block launches: no order, no measuring
-    Feedback *f = &none;
+    Feedback *f = nullptr;                                     // RT_FLAG_NO_FEEDBACK / one-block launches: no slot
     if (os.feedback) {
-        Feedback::Key key;
-        key.valid = true; key.x0 = x0; key.x1 = x1; key.h = k.h; key.aa = plan.shape.lat ? 3 : k.aa; key.depth = k.depth;
-        key.spp = (k.aa == RT_AA_STOCHASTIC) ? k.spp : 0; key.wpw = os.code;
-        int rc = feedback_slot(ctx, key, &f);
+        int rc = feedback_slot(ctx, rt::feedback_key(x0, x1, k.h, k.aa, plan.shape.lat, k.depth, k.spp, os.code), &f);
         if (rc == RT_OK) rc = switch_order(ctx, *f);
         if (rc != RT_OK) return rc;
     }
     // A launch of several frames (rt_render_sequence) is ONE launch only in a settled order; until then its frames go
     // through this function one by one (a measuring launch stores the costs of one frame).
-    if (nframes > 1 && os.feedback && !order_settled(ctx, *f)) {
+    if (nframes > 1 && f && !rt::settled(*f, ctx->epoch, ctx->remeasure)) {
         // the first frame on its own (it measures, if no measurement is in flight), then — rather than rendering more
         // frames singly while the order is being built — wait for the build (a fraction of a millisecond, twice per new
         // geometry) and hand the rest back: at most two single frames before whole batches go out in the settled order
         rt::KParams kf = frame_of(0);
         int rc = dispatch(ctx, p, kf, plan, stream, 1, 0);
         if (rc != RT_OK) return rc;
-        if (f->building) RT_HIP(ctx, hipEventSynchronize(f->done));
+        if (f->building) RT_HIP(ctx, hipEventSynchronize((hipEvent_t)f->done));
         rt::KParams kr = frame_of(1);
         return dispatch(ctx, p, kr, plan, stream, nframes - 1, frame_stride);
     }
-    return launch_one(ctx, k, plan, g, os, *f, stream, nframes, frame_stride);
+    return launch_one(ctx, k, plan, g, os, f, stream, nframes, frame_stride);
 }
 
-// The feedback slot of a launch geometry none of the slots holds: a free slot, else the least recently used geometry's.
-int evict_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out)
+// The feedback slot of a launch geometry (rt_feedback.h: the one that holds it, else a free or the least recently used one).
+int feedback_slot(rt_ctx *ctx, const rt::FeedbackKey &key, Feedback **out)
 {
-    Feedback *fsel = nullptr;
-    for (auto &c : ctx->fbs) if (!fsel || (!c.key.valid && fsel->key.valid) || (c.key.valid == fsel->key.valid && c.stamp < fsel->stamp)) fsel = &c;
-    if (fsel->key.valid) RT_HIP(ctx, hipDeviceSynchronize());   // launches of the evicted geometry may still read its orders (rare: > 8 geometries)
-    for (auto &e : fsel->fence) fsel->spare.push_back(e.second);
-    fsel->fence.clear(); fsel->users.clear();
-    fsel->have = fsel->building = false; fsel->builds = 0; fsel->since = 0; fsel->cur = 0;
-    fsel->key = key;
-    *out = fsel;
-    return RT_OK;
-}
-
-// The feedback slot of a launch geometry: the one that holds it, else evict_slot's.
-int feedback_slot(rt_ctx *ctx, const Feedback::Key &key, Feedback **out)
-{
-    Feedback *f = nullptr;
-    for (auto &c : ctx->fbs) if (c.key == key) { f = &c; break; }
-    if (!f) {
-        int rc = evict_slot(ctx, key, &f);
-        if (rc != RT_OK) return rc;
+    bool live = false;
+    const int i = ctx->book.find(key, &live);
+    if (live) RT_HIP(ctx, hipDeviceSynchronize());             // launches of the evicted geometry may still read its orders (rare: > 8 geometries)
+    ctx->book.claim(i, key);
+    Feedback *f = &ctx->fbs[i];
+    if (!f->done) {
+        hipEvent_t ev = nullptr;
+        RT_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        f->done = ev;
     }
-    f->stamp = ++ctx->fb_stamp;
-    if (!f->done) RT_HIP(ctx, hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
     *out = f;
     return RT_OK;
 }
 
-// the order being built is complete: switch to it.  Launches queued so far on the streams that used the old order may
-// still read it; an event per such stream, recorded now, is what the measurement after next waits for before it
-// overwrites that buffer.
+// The order being built is complete: switch to it, and record the events that fence the old order's readers (rt_feedback.h).
 int switch_order(rt_ctx *ctx, Feedback &f)
 {
     if (!f.building) return RT_OK;
-    const hipError_t q = hipEventQuery(f.done);
+    const hipError_t q = hipEventQuery((hipEvent_t)f.done);
     if (q != hipSuccess) {
         (void)hipGetLastError();                               // hipErrorNotReady is an answer, not a failure
         return RT_OK;
     }
-    f.cur ^= 1;
-    f.have = true;
-    f.building = false;
-    f.builds = (f.build_epoch == f.epoch) ? f.builds + 1 : 1;
-    f.epoch = f.build_epoch;
-    for (auto &e : f.fence) f.spare.push_back(e.second);
-    f.fence.clear();
-    for (hipStream_t us : f.users) {
-        hipEvent_t ev = nullptr;
-        if (!f.spare.empty()) { ev = f.spare.back(); f.spare.pop_back(); }
-        else RT_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        RT_HIP(ctx, hipEventRecord(ev, us));
-        f.fence.emplace_back(us, ev);
+    for (void *us : rt::switch_order(f)) {
+        hipEvent_t ev = (hipEvent_t)rt::take_spare(f);
+        if (!ev) RT_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        RT_HIP(ctx, hipEventRecord(ev, (hipStream_t)us));
+        rt::add_fence(f, us, ev);
     }
-    f.users.clear();
     return RT_OK;
 }
 
 // One dispatch of the planned kernel: nframes frames of g.blocks workgroups each, in f's order (os.feedback: f is the geometry's
-// slot, else an empty one), measuring the tiles' costs behind it if the order is not settled.
+// slot, else nullptr), measuring the tiles' costs behind it if the order is not settled.
 int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt_geo_plan &g, const rt::OrderShape &os,
-               Feedback &f, hipStream_t stream, int nframes, int64_t frame_stride)
+               Feedback *f, hipStream_t stream, int nframes, int64_t frame_stride)
 {
     const Shape &sh = plan.shape;
     const int fi = (int)plan.family;
@@ -538,28 +476,18 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
         }
         k.ray_counts = (unsigned long long *)ctx->counts.p;
     }
-    const bool same_epoch = f.epoch == ctx->epoch;
-    const bool settled = order_settled(ctx, f);
-    const bool measure = os.feedback && !settled && !f.building;  // one measurement in flight at a time (one cost buffer)
-    if (settled && !same_epoch) f.since++;
-    if (f.have) {
-        k.order = (const unsigned *)f.order[f.cur].p;
-        if (std::find(f.users.begin(), f.users.end(), stream) == f.users.end()) f.users.push_back(stream);
-    }
-    if (measure) {
+    const rt::FeedbackLaunch d = f ? rt::decide_launch(*f, stream, ctx->epoch, ctx->remeasure) : rt::FeedbackLaunch{};
+    if (d.read >= 0) k.order = (const unsigned *)f->order[d.read].p;
+    if (d.measure) {
         const size_t words = (size_t)os.items * sizeof(unsigned);
-        int rc = ensure(ctx, f.cost, words);
-        if (rc == RT_OK) rc = ensure(ctx, f.btmp, words);
-        if (rc == RT_OK) rc = ensure(ctx, f.order[0], 2 * words);     // longest-first order, then the tile-order one (order_kernel)
-        if (rc == RT_OK) rc = ensure(ctx, f.order[1], 2 * words);
-        if (rc == RT_OK) rc = ensure(ctx, f.gtmp, words + sizeof(unsigned));
+        int rc = ensure(ctx, f->cost, words);
+        if (rc == RT_OK) rc = ensure(ctx, f->btmp, words);
+        if (rc == RT_OK) rc = ensure(ctx, f->order[0], 2 * words);    // longest-first order, then the tile-order one (order_kernel)
+        if (rc == RT_OK) rc = ensure(ctx, f->order[1], 2 * words);
+        if (rc == RT_OK) rc = ensure(ctx, f->gtmp, words + sizeof(unsigned));
         if (rc != RT_OK) return rc;
-        for (auto &e : f.fence) {                              // (recorded at the last switch: complete long ago)
-            if (e.first != stream) RT_HIP(ctx, hipStreamWaitEvent(stream, e.second, 0));
-            f.spare.push_back(e.second);
-        }
-        f.fence.clear();
-        k.cost = (unsigned *)f.cost.p;
+        for (void *ev : d.wait) RT_HIP(ctx, hipStreamWaitEvent(stream, (hipEvent_t)ev, 0));
+        k.cost = (unsigned *)f->cost.p;
     }
     k.nframes = nframes; k.bpf = (int)grid; k.frame_stride = frame_stride; k.order_tiles = os.otiles ? 1 : 0;
     rt::div_magic((unsigned)k.bpf, k.bpf_magic, k.bpf_shift);
@@ -569,16 +497,14 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
     RT_HIP(ctx, hipLaunchKernel(fn, dim3(grid * (unsigned)nframes), dim3(64 * sh.wpw), args, plan.lds, stream));
     ctx->stats.launches++;
     ctx->stats.frames += (uint64_t)nframes;
-    if (settled) ctx->stats.launches_settled++;
-    if (measure) ctx->stats.launches_measuring++;
-    if (measure) {
-        hipLaunchKernelGGL(rt::order_kernel, dim3(1), dim3(rt::ORDER_THREADS), 0, stream, (const unsigned *)f.cost.p,
-                           (unsigned *)f.gtmp.p, (unsigned *)f.btmp.p, (unsigned *)f.order[f.cur ^ 1].p, (int)os.items, os.otiles ? os.gshift + os.wshift : os.gshift,
+    if (d.settled) ctx->stats.launches_settled++;
+    if (d.measure) ctx->stats.launches_measuring++;
+    if (d.measure) {
+        hipLaunchKernelGGL(rt::order_kernel, dim3(1), dim3(rt::ORDER_THREADS), 0, stream, (const unsigned *)f->cost.p,
+                           (unsigned *)f->gtmp.p, (unsigned *)f->btmp.p, (unsigned *)f->order[d.write].p, (int)os.items, os.otiles ? os.gshift + os.wshift : os.gshift,
                            os.otiles ? os.wshift : 0, os.otiles ? k.ntiles : (int)grid);
-        RT_HIP(ctx, hipEventRecord(f.done, stream));
-        f.building = true;
-        f.build_epoch = ctx->epoch;
-        f.since = 0;
+        RT_HIP(ctx, hipEventRecord((hipEvent_t)f->done, stream));
+        rt::order_queued(*f, ctx->epoch);
     }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
@@ -654,9 +580,7 @@ int rt_destroy(rt_ctx *ctx)
     for (auto &e : ctx->film) if (e.second.p) (void)hipFree(e.second.p);
     for (auto &f : ctx->fbs) {
         for (Buf *b : {&f.cost, &f.gtmp, &f.btmp, &f.order[0], &f.order[1]}) if (b->p) (void)hipFree(b->p);
-        for (auto &r : f.fence) (void)hipEventDestroy(r.second);
-        for (hipEvent_t e : f.spare) (void)hipEventDestroy(e);
-        if (f.done) (void)hipEventDestroy(f.done);
+        for (void *e : rt::release_events(f)) (void)hipEventDestroy((hipEvent_t)e);
     }
     for (auto &st : ctx->tables)
         for (auto &t : st.sets) if (t.buf.p) (void)hipFree(t.buf.p);
@@ -1349,13 +1273,7 @@ static int forget_stream(rt_ctx *ctx, hipStream_t stream)
         if (ctx->film[i].first == stream) { if (ctx->film[i].second.p) (void)hipFree(ctx->film[i].second.p); ctx->film.erase(ctx->film.begin() + (long)i); }
         else ++i;
     }
-    for (auto &f : ctx->fbs) {                                  // (its work is complete: nothing of it reads an order any more)
-        for (size_t i = 0; i < f.fence.size();) {
-            if (f.fence[i].first == stream) { f.spare.push_back(f.fence[i].second); f.fence.erase(f.fence.begin() + (long)i); }
-            else ++i;
-        }
-        f.users.erase(std::remove(f.users.begin(), f.users.end(), stream), f.users.end());
-    }
+    ctx->book.forget(stream);                                   // (its work is complete: nothing of it reads an order any more)
     for (auto &rd : ctx->scene_readers) rd.erase(std::remove(rd.begin(), rd.end(), stream), rd.end());
     for (size_t i = 0; i < ctx->tables.size();) {               // the stream's own cull-table sets go with it
         if (ctx->tables[i].stream == stream) {

@@ -314,3 +314,66 @@ def test_launch_plan_is_the_recorded_one(tmp_path):
     assert (ro["code"][(co["knobs"] == 11) & four] & 64 == 0).all() and (ro["code"][default & four] & 64 == 64).all()
     assert (ro["seq"][co["knobs"] == 12] == 0).all() and (ro["seq"][co["knobs"] == 13] == 1).all()
     assert np.array_equal(ro["seq"][default], (ro["wpw"][default] == 2).astype(np.int32))
+
+
+@pytest.fixture(scope="module")
+def feedback_check(tmp_path_factory):
+    """tests/algo/feedback_check.cpp: the dispatch-order feedback rules (python-ray-tracer_amd/csrc/rt_feedback.h) over a fake
+    runtime, a stand-alone program under AddressSanitizer (leak detection on) and UndefinedBehaviorSanitizer."""
+    exe = str(tmp_path_factory.mktemp("feedback") / "feedback_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "feedback_check.cpp")])
+    return exe
+
+
+def _run_feedback_check(args):
+    res = subprocess.run(args, capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stdout + res.stderr
+    return res.stdout
+
+
+def test_feedback_decisions_are_the_recorded_ones(feedback_check, tmp_path):
+    """Script A of tests/algo/feedback_trace_cases.py (three contexts, MI355RT_REMEASURE 24, 2 and 0: settling in three launches
+    on three streams, camera and scene changes, every AA variant and depth as a geometry of its own, launches without feedback,
+    rt_stream_forget, twelve geometries over the eight slots, a one-block frame) through rt_feedback.h as dispatch() and
+    launch_one() call it, the launching stream synchronised after every launch.  The keys come from rt_scene.h's layout of the
+    scene, plan_launch, rt_geo_plan_of, rt_geo_lattice and order_shape.  Whether each step measured and whether it was settled must
+    be, exactly, what tests/golden/feedback_trace.npz holds: the launches_measuring and launches_settled deltas of rt_get_stats,
+    recorded on the GPU from the library as it was before the rules became a header of their own."""
+    import numpy as np
+    sys.path.insert(0, ALGO)
+    try:
+        import feedback_trace_cases as ftc
+    finally:
+        sys.path.remove(ALGO)
+    script, got_path = str(tmp_path / "script.txt"), str(tmp_path / "got.txt")
+    ftc.write_script(script)
+    out = _run_feedback_check([feedback_check, "replay", script, got_path])
+    n = len(ftc.SCRIPT_A)
+    assert out.strip() == f"steps={3 * n} ok", out
+    got = np.loadtxt(got_path, dtype=np.int64).reshape(3, n, 2)
+    want = np.load(os.path.join(REPO, "tests", "golden", "feedback_trace.npz"))
+    assert tuple(want["fields"][2:4]) == ("launches_measuring", "launches_settled")
+    for i, rm in enumerate(ftc.REMEASURES):
+        rows = want[f"A/{rm}"]
+        assert rows.shape == (n, len(ftc.FIELDS))
+        bad = np.flatnonzero((got[i] != rows[:, 2:4]).any(axis=1))
+        assert bad.size == 0, [(rm, int(j), ftc.SCRIPT_A[j], got[i][j].tolist(), rows[j, 2:4].tolist()) for j in bad[:5]]
+        # the paths the script is there for: settled in three launches, a re-measure once the order is older than MI355RT_REMEASURE
+        # launches, and a camera change that keeps the order where it is not
+        assert got[i][3:7].tolist() == [[1, 0], [1, 0], [0, 1], [0, 1]]
+        moved = got[i][ftc.SCRIPT_A.index(("camera", 1)) + 1:][:6]
+        assert moved[:, 0].tolist() == {24: [0] * 6, 2: [0, 0, 1, 1, 0, 0], 0: [1, 1, 0, 0, 0, 0]}[rm]
+
+
+def test_feedback_orders_are_never_overwritten_under_a_reader(feedback_check):
+    """The random walk of tests/algo/feedback_check.cpp: 12 geometries over the 8 slots on 4 streams of a fake runtime whose
+    completions are decoupled from the launches, for MI355RT_REMEASURE 0, 2 and 24.  After every step: a measurement's order
+    kernel is ordered behind every launch that reads the buffer it writes, a launch reads only an order the host has seen
+    complete, one measurement per slot is in flight, a key is in one slot and a live slot is evicted only behind a device
+    synchronise; at the end every event was released exactly once.  Each transition (switch, measurement with a fence to wait
+    for, eviction of a live slot, forget with a pending fence) is taken for every MI355RT_REMEASURE."""
+    out = _run_feedback_check([feedback_check, "walk"])
+    last = out.strip().splitlines()[-1].split()
+    assert last[0] == "steps=300000" and last[-1] == "ok" and len(out.strip().splitlines()) == 4, out
+    assert all(int(f.split("=")[1]) > 100 for f in last[1:-1]), out
