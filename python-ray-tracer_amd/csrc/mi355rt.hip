@@ -312,6 +312,9 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     {   // every ray origin of the launch lies within |cam| (+ a with a lens) + 999 (depth + 1) of the world origin
         const double reach = std::sqrt(cam2) + 999.0 * (p->depth + 1) + std::sqrt(ctx->lay.extent2);
         k.floor_anch = (float)(0x1p-39 * reach * reach);
+        // the facing certificate's margin (rt_facing.h): the same reach bounds |light - Pt|; a family without a material table reads the
+        // wave-uniform p.lamb (MS::mat is has_mat(family) in the kernels), the others look at the lane's own coefficient
+        k.facing_tau = rt_facing_tau(reach, rt::has_mat(lfam) ? 0.0 : p->lamb);
     }
     {
         int rc = acquire_tables(ctx, k, stream, &k.ftab);

@@ -31,6 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rt_facing.h"   // the facing certificate of the point-light loop (trace_bounce) and its margin
 #include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets, the LDS image's arithmetic (lds_bytes, table_layout, ...), TILE, div_magic:
                          // shared with the host's scene packer (rt_scene.h) and launch plan (rt_plan.h)
 
@@ -49,6 +50,9 @@
 #endif
 #ifndef RT_FAST_NORMALIZE
 #define RT_FAST_NORMALIZE 1
+#endif
+#ifndef RT_FACING_SKIP
+#define RT_FACING_SKIP 1     // 0: the point-light loops without the facing certificate (A/B builds)
 #endif
 
 namespace rt {
@@ -97,6 +101,8 @@ struct KParams {
     double cam_o[3];
     double cam_R[9];
     double amb, lamb;
+    double facing_tau;         // margin of the facing certificate (rt_facing.h; host: rt_facing_tau of the floor_anch reach): a light whose
+                               // (light - Pt).N is below -facing_tau on every live lane of a wave is skipped before its direction is formed
     union {
         double refl_pow[16];   // kernels without a material table: refl ** (b+1) (the MAT kernels weigh bounces with the table)
         struct {               // LENS kernels (MAT kernels: refl_pow is unused there), rt_set_lens
@@ -308,7 +314,7 @@ template <bool PARK, int WGT, bool REMAT = false> struct Park3 {
 // SKY (sky kernels, rt_set_scene_sky; LIT too): no slot and no LDS: the lanes of a trace that missed read the scene's sky block
 // from global memory through wave-uniform addresses (sky_color, SKY_DOUBLES).
 template <Family F, int WSLOT, bool FRESH> struct MatState {
-    static constexpr bool mat = true, refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F), lit = has_lit(F), sky = has_sky(F);
+    static constexpr bool mat = has_mat(F), refr = has_refr(F), scat = has_scat(F), soft = has_soft(F), lens = has_lens(F), tex = has_tex(F), lit = has_lit(F), sky = has_sky(F);
     static constexpr int COLS = table_cols(F);   // doubles per table row
     unsigned tab;              // LDS: M x {amb, lamb, refl} (REFR: M x {amb, lamb, refl, trans, ior}; SCAT: ..., rough)
     unsigned ids;              // LDS: the material of every slot (S spheres in slot order, then P planes)
@@ -329,6 +335,7 @@ template <Family F, int WSLOT, bool FRESH> struct MatState {
     }
 };
 template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
+    static_assert(!has_mat(Family::PLAIN), "MS::mat is has_mat(family) on both sides: the host folds p.lamb into facing_tau by the same predicate");
     static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false, lit = false, sky = false;
 };
 
@@ -1462,6 +1469,10 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                                              V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
     constexpr bool NOREC = MODE >= 1;         // no float64 sphere records in LDS (sphere_hot)
+    // The wave-level skip of back-facing point lights (rt_facing.h) is compiled out of the lane-owned kernels (MODE 2) of every
+    // family: they run at 128 VGPRs with scratch already, and the skip adds 4 to 8 bytes of it per lane there (DESIGN.md §4,
+    // "Back-facing lights").  Their light loops are the former ones.
+    constexpr bool FACING_SKIP = RT_FACING_SKIP != 0 && MODE != 2;
     const int S = p.S, P = p.P, L = opaque(p.L);
     rgb = V3{0.0, 0.0, 0.0};
     double t = 999.0; int idx = -1, type = HIT_NONE;
@@ -1611,6 +1622,12 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                     }
                 }
             } else {
+                if constexpr (FACING_SKIP) {                                  // (rt_facing.h: neither k > 0 nor cN > 0 on any live lane)
+                    const double *g = lt + m * LT_STRIDE;
+                    const bool cert = rt_facing_certified_lamb(g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z, N.x, N.y, N.z, p.facing_tau,
+                                                               *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave));
+                    if (__builtin_amdgcn_ballot_w64(!cert) == 0ull) { RT_MARK(5); continue; }
+                }
                 const V3 Ld = point_Ld(m);
                 const double cN = dot3(Ld, N);
                 const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * cN;       // :99
@@ -1645,9 +1662,23 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         } else
         for (int m = 0; m < L; ++m) {                                         // :86-102
             const double *g = lt + m * LT_STRIDE;
-            const V3 Ld = normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});   // common.py:84-91
+            const V3 v{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z};
             double lamb;
             if constexpr (MS::mat) lamb = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave); else lamb = p.lamb;
+            if constexpr (FACING_SKIP) {
+                // The facing certificate (rt_facing.h): where every live lane of the wave has v.N < -facing_tau (and no negative lamb:
+                // per lane with a material table, folded into facing_tau by the host otherwise), no lane's k will be positive, so
+                // the wave goes to the next light without normalising v.  One lane without the certificate: today's code for all.
+                bool cert;
+                if constexpr (MS::mat) cert = rt_facing_certified_lamb(v.x, v.y, v.z, N.x, N.y, N.z, p.facing_tau, lamb);
+                else cert = rt_facing_certified(v.x, v.y, v.z, N.x, N.y, N.z, p.facing_tau);
+                if (__builtin_amdgcn_ballot_w64(!cert) == 0ull) {
+                    cnt.shadow(true, false);
+                    RT_MARK(5);
+                    continue;
+                }
+            }
+            const V3 Ld = normalize3(v);                                      // common.py:84-91
             const double k = lamb * dot3(Ld, N);                              // :99
             // :92-102 — the shadow query's answer is only used when k > 0; it has no other effect,
             // so lanes with k <= 0 (light behind the surface) do not ask.
