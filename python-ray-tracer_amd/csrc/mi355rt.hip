@@ -2,7 +2,8 @@
 // render kernel in rt_device.h.  HIP only (no torch, no CPU fallback): without a HIP device
 // rt_create fails and nothing renders.  What a call decides before it touches the device lives in
 // HIP-free headers: the packed scene (rt_scene.h), the launch arithmetic (rt_geometry.h), the
-// launch's kernel and order shape (rt_plan.h), the dispatch-order feedback (rt_feedback.h).
+// launch's kernel and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the dispatch-order
+// feedback (rt_feedback.h).
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_denoise.h"
@@ -10,6 +11,7 @@
 #include "rt_film.h"
 #include "rt_geometry.h"
 #include "rt_guides.h"
+#include "rt_launch.h"
 #include "rt_plan.h"
 #include "rt_scene.h"
 
@@ -73,11 +75,8 @@ struct rt_ctx {
     rt::SceneLayout lay;          // the current scene (rt_scene.h): counts, families' flags, block offsets, plane codes, extent
     Buf texels[RT_SCENE_RING];    // per scene buffer of the ring: {R,G,B, texture id} float32 of the S + P object slots, then {R,G,B,-} of the scene's texels;
                                   // allocated by the first textured (or lit) scene that lands in the slot, grown when one needs more
-    double lens_a = 0.0, lens_f = 1.0;   // rt_set_lens: aperture (0: the pinhole camera) and focus distance
-    bool have_scene = false, have_cam = false, have_grid = false, explicit_grid = false;
-    double cam_o[3] = {0, 0, 0}, cam_R[9] = {0};
-    int w = 0, h = 0;
-    double px = 0, y0 = 0, dy = 0, z0 = 0, dz = 0;
+    bool have_scene = false;
+    rt::View view;                // camera, ray grid and lens (rt_launch.h)
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
     size_t guides_lds_set = 0;                 // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
@@ -138,24 +137,27 @@ int ensure(rt_ctx *ctx, Buf &b, size_t bytes)
     return RT_OK;
 }
 
-int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1)
+int refuse(rt_ctx *ctx, const rt::Refusal &r) { return r.code == RT_OK ? RT_OK : fail(ctx, r.code, r.msg); }
+
+int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1) { return refuse(ctx, rt::check_params(ctx->have_scene, ctx->view, ctx->lay, p, x0, x1)); }
+
+hipStream_t stream_of(rt_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// The current scene buffer, with `stream` noted as one of its readers (set_scene drains them before the buffer is rewritten).
+const double *scene_for(rt_ctx *ctx, hipStream_t stream)
 {
-    if (!p) return fail(ctx, RT_ERR_BAD_ARG, "params is NULL");
-    if (!ctx->have_scene) return fail(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
-    if (!ctx->have_cam) return fail(ctx, RT_ERR_STATE, "rt_set_camera has not been called");
-    if (!ctx->have_grid) return fail(ctx, RT_ERR_STATE, "rt_set_raygen / rt_set_pixel_loc has not been called");
-    if (p->depth < 0 || p->depth > RT_MAX_DEPTH) return fail(ctx, RT_ERR_BAD_ARG, "depth outside 0..RT_MAX_DEPTH");
-    if (p->aa_mode != RT_AA_NONE && p->aa_mode != RT_AA_REFERENCE && p->aa_mode != RT_AA_STOCHASTIC)
-        return fail(ctx, RT_ERR_BAD_ARG, "unknown aa_mode");
-    if (p->aa_mode == RT_AA_STOCHASTIC) {
-        if (p->spp < 1 || p->spp > RT_MAX_SPP) return fail(ctx, RT_ERR_BAD_ARG, "spp outside 1..RT_MAX_SPP");
-        if (ctx->explicit_grid) return fail(ctx, RT_ERR_STATE, "RT_AA_STOCHASTIC needs the closed-form ray grid (rt_set_raygen)");
-    }
-    if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
-    if (ctx->lay.M > 0 && (p->flags & RT_FLAG_COUNT_RAYS))
-        return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_COUNT_RAYS is not available for a scene with materials");
-    if (ctx->lens_a > 0.0 && ctx->lay.M == 0)
-        return fail(ctx, RT_ERR_STATE, "a lens with aperture > 0 needs a scene with a material table (M >= 1)");
+    auto &rd = ctx->scene_readers[ctx->scene_cur];
+    if (std::find(rd.begin(), rd.end(), stream) == rd.end()) rd.push_back(stream);
+    return (const double *)ctx->scene[ctx->scene_cur].p;
+}
+
+// More than the default 48 KiB of dynamic LDS: raised on all of `fns` (nullptr: no such kernel) at once; `set` remembers the size.
+int raise_lds(rt_ctx *ctx, const void *const *fns, size_t n, size_t lds, size_t &set)
+{
+    if (lds <= 48 * 1024 || lds <= set) return RT_OK;
+    for (size_t i = 0; i < n; ++i)
+        if (fns[i]) RT_HIP(ctx, hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    set = lds;
     return RT_OK;
 }
 
@@ -261,61 +263,18 @@ int lattice_buffer(rt_ctx *ctx, hipStream_t stream, size_t bytes, double **out)
 int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_f32, int64_t plane_stride,
            hipStream_t stream, int nframes = 1, int64_t frame_stride = 0)
 {
-    rt::KParams k;
-    std::memset(&k, 0, sizeof k);
-    k.scene = (const double *)ctx->scene[ctx->scene_cur].p;
-    {
-        auto &rd = ctx->scene_readers[ctx->scene_cur];
-        if (std::find(rd.begin(), rd.end(), stream) == rd.end()) rd.push_back(stream);
-    }
-    k.nframes = 1;
-    k.pixel_loc = ctx->explicit_grid ? (const double *)ctx->pixel_loc.p : nullptr;
-    k.out_u8 = (uint8_t *)d_u8;
-    k.out_f32 = (float *)d_f32;
-    k.tile_cycles = ctx->tile_stats;
-    k.plane_stride = plane_stride;
-    k.w = ctx->w; k.h = ctx->h; k.x0 = x0; k.x1 = x1;
-    k.S = ctx->lay.S; k.P = ctx->lay.P; k.L = ctx->lay.L; k.depth = p->depth; k.NC = ctx->lay.NC; k.plane_codes = ctx->lay.plane_codes;
-    k.aa = p->aa_mode; k.u8_rgb = (p->flags & RT_FLAG_U8_RGB) ? 1 : 0; k.u8_hwc = (p->flags & RT_FLAG_U8_HWC) ? 1 : 0;
-    k.spp = p->spp; k.seed = p->seed;
-    k.lanes_primary = ctx->lanes_primary;
-    k.tiles_y = (int)rt_geo_tiles(ctx->h);
-    k.ntiles = (int)(rt_geo_tiles(x1 - x0) * k.tiles_y);      // (rt_geo_frame_ok: below 2^28)
-    k.px = ctx->px; k.y0 = ctx->y0; k.dy = ctx->dy; k.z0 = ctx->z0; k.dz = ctx->dz;
-    std::memcpy(k.cam_o, ctx->cam_o, sizeof k.cam_o);
-    std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
-    k.amb = p->amb; k.lamb = p->lamb;
-    std::memcpy(k.refl_pow, p->refl_pow, sizeof k.refl_pow);
+    const rt::View &v = ctx->view;
     // (RT_AA_REFERENCE on the closed-form grid renders the half-pixel lattice, below: lattice columns [li0, li1))
     long long li0 = 0, li1 = 0;
-    const bool lattice = k.aa == RT_AA_REFERENCE && !ctx->explicit_grid && rt_geo_lattice(ctx->w, ctx->h, x0, x1, &li0, &li1) &&
+    const bool lattice = p->aa_mode == RT_AA_REFERENCE && !v.explicit_grid && rt_geo_lattice(v.w, v.h, x0, x1, &li0, &li1) &&
                          !(p->flags & RT_FLAG_AA_PER_PIXEL);
     // the launch's family, kernel and LDS size (rt_plan.h), decided once: every slab and frame of the launch runs the same kernel
-    k.anchors = rt::anchors_of(ctx->lay);
-    const rt::LaunchPlan plan = rt::plan_launch(ctx->lay, ctx->knobs, ctx->lens_a, !lattice && k.aa != 0, p->flags, lattice, k.anchors);
+    const rt::LaunchPlan plan = rt::plan_launch(ctx->lay, ctx->knobs, v.lens_a, !lattice && p->aa_mode != 0, p->flags, lattice, rt::anchors_of(ctx->lay));
     if (plan.index < 0 || !KERNELS[(int)plan.family][plan.index])
         return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: rt_plan.h, missing_kernels_never_park)
-    // a lens (aperture > 0; check_params: the scene has a material table) runs the lens kernels, which read no refl_pow:
-    // the lens travels in its place, by value with this launch
-    const rt::Family lfam = plan.family;
-    const bool lens = rt::has_lens(lfam);
-    if (lens) { k.lens.aperture = ctx->lens_a; k.lens.focus = ctx->lens_f; k.lens.mat = ctx->lay.lens_mat; }
-    // the texture kernels read no refl_pow either: the 6-column material block, the texture block and the texel array of the
-    // scene buffer that is current now travel in its place
-    if (rt::has_tex(lfam)) { k.lens.mat = ctx->lay.lens_mat; k.lens.tex = ctx->lay.tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
-    if (rt::has_lit(lfam)) k.lens.lit = ctx->lay.lit_off;                // (the lighting kernels are texture kernels: the above too)
-    if (rt::has_sky(lfam)) k.lens.sky = ctx->lay.sky_off;                // (and the sky kernels lighting kernels)
-
-    double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
-    if (lens) { const double e = std::sqrt(cam2) + ctx->lens_a; cam2 = e * e; }   // (primary rays start on the lens, |L - cam| <= a)
-    k.extent2 = (float)(1.0001 * (cam2 > ctx->lay.extent2 ? cam2 : ctx->lay.extent2));
-    {   // every ray origin of the launch lies within |cam| (+ a with a lens) + 999 (depth + 1) of the world origin
-        const double reach = std::sqrt(cam2) + 999.0 * (p->depth + 1) + std::sqrt(ctx->lay.extent2);
-        k.floor_anch = (float)(0x1p-39 * reach * reach);
-        // the facing certificate's margin (rt_facing.h): the same reach bounds |light - Pt|; a family without a material table reads the
-        // wave-uniform p.lamb (MS::mat is has_mat(family) in the kernels), the others look at the lane's own coefficient
-        k.facing_tau = rt_facing_tau(reach, rt::has_mat(lfam) ? 0.0 : p->lamb);
-    }
+    rt::KParams k;
+    rt::render_part(k, v, ctx->lay, plan.family, p, scene_for(ctx, stream), (const double *)ctx->pixel_loc.p,
+                    (const float *)ctx->texels[ctx->scene_cur].p, ctx->lanes_primary, x0, x1, d_u8, d_f32, plane_stride, ctx->tile_stats);
     {
         int rc = acquire_tables(ctx, k, stream, &k.ftab);
         if (rc != RT_OK) return rc;
@@ -327,24 +286,17 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     // over the lattice "frame", stored as float64 (R,G,B), and a second small kernel sums each pixel's nine samples in
     // the reference's order (kernels.py:53-65, including its G/B swap).  Explicit pixel_loc grids are not separable
     // in general and keep the nine-taps-per-pixel kernel.
-    const long long LW = 2ll * ctx->w - 1, LH = 2ll * ctx->h - 1;
     if (lattice) {
         double *lat = nullptr;
-        int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0) * (size_t)LH * 3 * sizeof(double), &lat);
+        int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0) * (size_t)(2ll * v.h - 1) * 3 * sizeof(double), &lat);
         if (rc != RT_OK) return rc;
-        rt::KParams kl = k;
-        kl.aa = 0; kl.lattice = 1; kl.out_u8 = nullptr; kl.out_f32 = nullptr; kl.out_f64 = lat; kl.tile_cycles = nullptr;   // (rt_set_tile_stats: pixel launches only)
-        kl.w = (int)LW; kl.h = (int)LH; kl.x0 = (int)li0; kl.x1 = (int)li1; kl.plane_stride = 0;
-        kl.tiles_y = (int)rt_geo_tiles(LH);
-        kl.ntiles = (int)(rt_geo_tiles(li1 - li0) * kl.tiles_y);
-        k.out_f64 = lat; k.lat_x0 = (int)li0; k.lat_h = (int)LH;
-        const long long npx = (long long)(x1 - x0) * ctx->h;
+        rt::KParams kl;
+        rt::lattice_pair(k, kl, li0, li1, lat);
+        const long long npx = (long long)(x1 - x0) * v.h;
         for (int f = 0; f < nframes; ++f) {                    // the stream's one lattice buffer serves the frames in turn
             rc = dispatch(ctx, p, kl, plan, stream, 1, 0);
             if (rc != RT_OK) return rc;
-            rt::KParams kf = k;
-            if (kf.out_u8) kf.out_u8 += (size_t)f * frame_stride;
-            if (kf.out_f32) kf.out_f32 += (size_t)f * frame_stride;
+            const rt::KParams kf = rt::frame_params(k, f, frame_stride);
             hipLaunchKernelGGL(rt::aa_resolve_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, kf);
             RT_HIP(ctx, hipGetLastError());
         }
@@ -369,18 +321,11 @@ int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPl
     // At most RT_GEO_MAX_ITEMS work-items per dispatch (rt_geometry.h): a frame beyond that alone goes out as column slabs
     // (they assemble bit-identically), one dispatch each; a sequence as batches of frames.
     const rt_geo_plan g = rt_geo_plan_of(x0, x1, k.h, plan.shape.wpw, nframes);
-    auto frame_of = [&](int fr) { rt::KParams kf = k; if (kf.out_u8) kf.out_u8 += (size_t)fr * frame_stride; if (kf.out_f32) kf.out_f32 += (size_t)fr * frame_stride; return kf; };
+    auto frame_of = [&](int fr) { return rt::frame_params(k, fr, frame_stride); };
     if (g.nslabs > 1) {
         for (int fr = 0; fr < nframes; ++fr)
             for (long long s = 0; s < g.nslabs; ++s) {
-                const long long sx0 = x0 + s * g.slab_tiles * rt::TILE, sx1 = std::min<long long>(x1, sx0 + g.slab_tiles * rt::TILE);
-                const long long dx = sx0 - x0;
-                rt::KParams kf = frame_of(fr);
-                kf.x0 = (int)sx0; kf.x1 = (int)sx1; kf.ntiles = (int)(rt_geo_tiles(sx1 - sx0) * k.tiles_y);
-                if (kf.out_u8) kf.out_u8 += k.u8_hwc ? 3 * dx : dx * k.h;       // (element [c, x, y] of rt_render_device)
-                if (kf.out_f32) kf.out_f32 += dx * k.h;
-                if (kf.out_f64) kf.out_f64 += 3 * dx * k.h;                      // (lattice samples, [column - x0][row][3])
-                if (kf.tile_cycles) kf.tile_cycles += dx / rt::TILE * k.tiles_y;
+                rt::KParams kf = rt::slab_params(frame_of(fr), g, s);
                 int rc = dispatch(ctx, p, kf, plan, stream, 1, 0);
                 if (rc != RT_OK) return rc;
             }
@@ -465,16 +410,12 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
     if (ctx->log_kernels)
         std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
                      (int)sh.lat, sh.mode, fi);
-    // more than the default 48 KiB of dynamic LDS: raised on all of the family's kernels at once
-    if (plan.lds > 48 * 1024 && plan.lds > ctx->lds_limit_set[fi]) {
-        for (const void *kf : KERNELS[fi])
-            if (kf) RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-        ctx->lds_limit_set[fi] = plan.lds;
-    }
+    int rc = raise_lds(ctx, KERNELS[fi].data(), KERNELS[fi].size(), plan.lds, ctx->lds_limit_set[fi]);
+    if (rc != RT_OK) return rc;
     if (sh.count) {
         if (!ctx->counts.p) {
-            int rc0 = ensure(ctx, ctx->counts, RT_COUNT_WORDS * sizeof(unsigned long long));
-            if (rc0 != RT_OK) return rc0;
+            rc = ensure(ctx, ctx->counts, RT_COUNT_WORDS * sizeof(unsigned long long));
+            if (rc != RT_OK) return rc;
             RT_HIP(ctx, hipMemsetAsync(ctx->counts.p, 0, RT_COUNT_WORDS * sizeof(unsigned long long), stream));
         }
         k.ray_counts = (unsigned long long *)ctx->counts.p;
@@ -483,7 +424,7 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
     if (d.read >= 0) k.order = (const unsigned *)f->order[d.read].p;
     if (d.measure) {
         const size_t words = (size_t)os.items * sizeof(unsigned);
-        int rc = ensure(ctx, f->cost, words);
+        rc = ensure(ctx, f->cost, words);
         if (rc == RT_OK) rc = ensure(ctx, f->btmp, words);
         if (rc == RT_OK) rc = ensure(ctx, f->order[0], 2 * words);    // longest-first order, then the tile-order one (order_kernel)
         if (rc == RT_OK) rc = ensure(ctx, f->order[1], 2 * words);
@@ -492,10 +433,7 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
         for (void *ev : d.wait) RT_HIP(ctx, hipStreamWaitEvent(stream, (hipEvent_t)ev, 0));
         k.cost = (unsigned *)f->cost.p;
     }
-    k.nframes = nframes; k.bpf = (int)grid; k.frame_stride = frame_stride; k.order_tiles = os.otiles ? 1 : 0;
-    rt::div_magic((unsigned)k.bpf, k.bpf_magic, k.bpf_shift);
-    rt::div_magic((unsigned)k.tiles_y, k.tiles_y_magic, k.tiles_y_shift);
-    k.seq_offset = os.seq_offset;
+    rt::dispatch_part(k, nframes, grid, frame_stride, os);
     void *args[] = {(void *)&k};
     RT_HIP(ctx, hipLaunchKernel(fn, dim3(grid * (unsigned)nframes), dim3(64 * sh.wpw), args, plan.lds, stream));
     ctx->stats.launches++;
@@ -644,6 +582,14 @@ static rt::SceneDesc scene_desc(const float *spheres, int S, const float *lights
     return d;
 }
 
+// The entries from rt_set_scene_textures on.
+static void add_textures(rt::SceneDesc &d, const rt_texture *textures, int T, const int32_t *sphere_texture, const int32_t *plane_texture,
+                         const float *texels, int64_t n_texels)
+{
+    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
+    d.texels = texels; d.n_texels = n_texels;
+}
+
 // The entries from rt_set_scene_area_lights on: the radii may be NULL only where there is no light.
 static int set_scene_radii(rt_ctx *ctx, rt::SceneDesc &d, const float *light_radius, int shadow_samples)
 {
@@ -696,8 +642,7 @@ int rt_set_scene_textures(rt_ctx *ctx, const float *spheres, int S, const float 
                           const float *texels, int64_t n_texels)
 {
     rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
-    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
-    d.texels = texels; d.n_texels = n_texels;
+    add_textures(d, textures, T, sphere_texture, plane_texture, texels, n_texels);
     return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
 
@@ -708,8 +653,7 @@ int rt_set_scene_lighting(rt_ctx *ctx, const float *spheres, int S, const float 
                           const float *texels, int64_t n_texels, const float *light_rgb)
 {
     rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
-    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
-    d.texels = texels; d.n_texels = n_texels;
+    add_textures(d, textures, T, sphere_texture, plane_texture, texels, n_texels);
     d.light_rgb = light_rgb; d.lighting = true;
     return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
@@ -721,8 +665,7 @@ int rt_set_scene_sky(rt_ctx *ctx, const float *spheres, int S, const float *ligh
                      const float *texels, int64_t n_texels, const float *light_rgb, const double *sky)
 {
     rt::SceneDesc d = scene_desc(spheres, S, lights, L, planes, P, flags, materials, M, ncols, sphere_material, plane_material);
-    d.textures = textures; d.T = T; d.sphere_texture = sphere_texture; d.plane_texture = plane_texture;
-    d.texels = texels; d.n_texels = n_texels;
+    add_textures(d, textures, T, sphere_texture, plane_texture, texels, n_texels);
     d.light_rgb = light_rgb; d.lighting = true; d.sky = sky;
     return set_scene_radii(ctx, d, light_radius, shadow_samples);
 }
@@ -733,11 +676,12 @@ int rt_set_camera(rt_ctx *ctx, const double origin[3], const double rotation[9])
     if (!origin || !rotation) return fail(ctx, RT_ERR_BAD_ARG, "NULL camera array");
     // the same camera again (the reference's driver passes it with every launch, main.py:41-47) changes nothing a
     // tile's cost depends on: the measured dispatch order and the cull tables stay valid
-    if (ctx->have_cam && std::memcmp(ctx->cam_o, origin, sizeof ctx->cam_o) == 0 &&
-        std::memcmp(ctx->cam_R, rotation, sizeof ctx->cam_R) == 0) return RT_OK;
-    std::memcpy(ctx->cam_o, origin, sizeof ctx->cam_o);
-    std::memcpy(ctx->cam_R, rotation, sizeof ctx->cam_R);
-    ctx->have_cam = true;
+    rt::View &v = ctx->view;
+    if (v.have_cam && std::memcmp(v.cam_o, origin, sizeof v.cam_o) == 0 &&
+        std::memcmp(v.cam_R, rotation, sizeof v.cam_R) == 0) return RT_OK;
+    std::memcpy(v.cam_o, origin, sizeof v.cam_o);
+    std::memcpy(v.cam_R, rotation, sizeof v.cam_R);
+    v.have_cam = true;
     ctx->epoch++;
     return RT_OK;
 }
@@ -750,9 +694,10 @@ int rt_set_lens(rt_ctx *ctx, double aperture, double focus_distance)
         return fail(ctx, RT_ERR_BAD_ARG, "focus_distance must be finite and > 0");
     // the same lens again changes nothing (as rt_set_camera), nor does a new focus without an aperture (the pinhole camera
     // ignores it); a new lens starts dispatch-order measuring again
-    if (aperture == ctx->lens_a && (focus_distance == ctx->lens_f || aperture == 0.0)) { ctx->lens_f = focus_distance; return RT_OK; }
-    ctx->lens_a = aperture;
-    ctx->lens_f = focus_distance;
+    rt::View &v = ctx->view;
+    if (aperture == v.lens_a && (focus_distance == v.lens_f || aperture == 0.0)) { v.lens_f = focus_distance; return RT_OK; }
+    v.lens_a = aperture;
+    v.lens_f = focus_distance;
     ctx->epoch++;
     return RT_OK;
 }
@@ -761,14 +706,15 @@ int rt_set_raygen(rt_ctx *ctx, int w, int h, double px, double y0, double dy, do
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (!rt_geo_frame_ok(w, h)) return fail(ctx, RT_ERR_BAD_ARG, "frame size out of range (1 <= w <= 2^31 - 8, 1 <= h <= 2^29 - 32, w*h <= 2^31)");
+    rt::View &v = ctx->view;
     {
-        const double now[5] = {px, y0, dy, z0, dz}, was[5] = {ctx->px, ctx->y0, ctx->dy, ctx->z0, ctx->dz};
-        if (ctx->have_grid && !ctx->explicit_grid && ctx->w == w && ctx->h == h && std::memcmp(now, was, sizeof now) == 0)
+        const double now[5] = {px, y0, dy, z0, dz}, was[5] = {v.px, v.y0, v.dy, v.z0, v.dz};
+        if (v.have_grid && !v.explicit_grid && v.w == w && v.h == h && std::memcmp(now, was, sizeof now) == 0)
             return RT_OK;                                       // unchanged: keep the measured dispatch order
     }
-    ctx->w = w; ctx->h = h; ctx->px = px; ctx->y0 = y0; ctx->dy = dy; ctx->z0 = z0; ctx->dz = dz;
-    ctx->explicit_grid = false;
-    ctx->have_grid = true;
+    v.w = w; v.h = h; v.px = px; v.y0 = y0; v.dy = dy; v.z0 = z0; v.dz = dz;
+    v.explicit_grid = false;
+    v.have_grid = true;
     ctx->epoch++;
     return RT_OK;
 }
@@ -786,9 +732,9 @@ int rt_set_pixel_loc(rt_ctx *ctx, const double *pixel_loc, int w, int h)
     if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipMemcpyAsync(ctx->pixel_loc.p, pixel_loc, bytes, hipMemcpyHostToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->w = w; ctx->h = h;
-    ctx->explicit_grid = true;
-    ctx->have_grid = true;
+    ctx->view.w = w; ctx->view.h = h;
+    ctx->view.explicit_grid = true;
+    ctx->view.have_grid = true;
     ctx->epoch++;
     return RT_OK;
 }
@@ -797,14 +743,10 @@ int rt_render_device(rt_ctx *ctx, const rt_params *params, int x0, int x1, void 
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     int rc = check_params(ctx, params, x0, x1);
+    if (rc == RT_OK) rc = refuse(ctx, rt::check_device_outputs(ctx->view, params, x0, x1, 1, d_u8, d_f32, plane_stride, 0));
     if (rc != RT_OK) return rc;
-    if (!d_u8 && !d_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
-    if (params->flags & RT_FLAG_U8_HWC) {
-        if (d_f32) return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC re-uses plane_stride as the image row pitch: render the float32 buffer in a separate call");
-        if (plane_stride < (int64_t)(x1 - x0)) return fail(ctx, RT_ERR_BAD_ARG, "row pitch smaller than the slab width");
-    } else if (plane_stride < (int64_t)(x1 - x0) * ctx->h) return fail(ctx, RT_ERR_BAD_ARG, "plane_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    return launch(ctx, params, x0, x1, d_u8, d_f32, plane_stride, stream ? (hipStream_t)stream : ctx->stream);
+    return launch(ctx, params, x0, x1, d_u8, d_f32, plane_stride, stream_of(ctx, stream));
 }
 
 int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int n, void *d_u8, void *d_f32, int64_t plane_stride,
@@ -818,17 +760,8 @@ int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
         if (rc0 != RT_OK) return rc0;
     }
     int rc = check_params(ctx, params, x0, x1);
+    if (rc == RT_OK) rc = refuse(ctx, rt::check_device_outputs(ctx->view, params, x0, x1, n, d_u8, d_f32, plane_stride, frame_stride));
     if (rc != RT_OK) return rc;
-    if (!d_u8 && !d_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
-    const bool hwc = (params->flags & RT_FLAG_U8_HWC) != 0;
-    if (hwc) {
-        if (d_f32) return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC re-uses plane_stride as the image row pitch: render the float32 buffer in a separate call");
-        if (plane_stride < (int64_t)(x1 - x0)) return fail(ctx, RT_ERR_BAD_ARG, "row pitch smaller than the slab width");
-        if (n > 1 && frame_stride < 3 * plane_stride * ctx->h) return fail(ctx, RT_ERR_BAD_ARG, "frame_stride smaller than one image");
-    } else {
-        if (plane_stride < (int64_t)(x1 - x0) * ctx->h) return fail(ctx, RT_ERR_BAD_ARG, "plane_stride smaller than the slab");
-        if (n > 1 && frame_stride < 3 * plane_stride) return fail(ctx, RT_ERR_BAD_ARG, "frame_stride smaller than three planes");
-    }
     if (n_streams < 0 || (n_streams > 0 && !streams)) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_sequence: n_streams without a stream array");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     auto stream_of = [&](int i) { return (n_streams > 0 && streams[i % n_streams]) ? (hipStream_t)streams[i % n_streams] : ctx->stream; };
@@ -864,11 +797,11 @@ int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
     if (rc != RT_OK) return rc;
     if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: passes < 1");
     if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: d_sum is NULL");
-    const long long npx = (long long)(x1 - x0) * ctx->h;
+    const long long npx = (long long)(x1 - x0) * ctx->view.h;
     if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: (x1-x0)*h above RT_FILM_MAX_PIXELS");
     if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: sum_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, stream);
     rt_params p = *params;
     p.flags &= ~(RT_FLAG_U8_RGB | RT_FLAG_U8_HWC);
     // pass planes padded to a multiple of four floats: every plane of the scratch is 16-byte aligned whatever npx is
@@ -925,71 +858,41 @@ int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
     a.h = h; a.rgb = (tone->flags & RT_FLAG_U8_RGB) ? 1 : 0; a.hwc = hwc ? 1 : 0;
     a.tone = rt::film_tone_of(n, tone->exposure, tone->white, tone->gamma);
     hipLaunchKernelGGL(rt::film_resolve_kernel, dim3(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
-                       stream ? (hipStream_t)stream : ctx->stream, a);
+                       stream_of(ctx, stream), a);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 
 // The first-hit guides: one launch of the guides kernel (rt_guides.h) per dispatch the slab needs, in plain tile order.  Scene,
-// camera and grid travel by value as in launch(); the cull tables are the stream's own (acquire_tables), built for rays that start
-// at the camera and go no further than the first hit.
+// camera and grid travel by value as in a render launch (rt_launch.h: frame_part); the cull tables are the stream's own
+// (acquire_tables), built for rays that start at the camera and go no further than the first hit: no lens, depth 0.
 int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: d_guides is NULL");
-    if (!ctx->have_scene) return fail(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
-    if (!ctx->have_cam) return fail(ctx, RT_ERR_STATE, "rt_set_camera has not been called");
-    if (!ctx->have_grid) return fail(ctx, RT_ERR_STATE, "rt_set_raygen / rt_set_pixel_loc has not been called");
-    if (x0 < 0 || x1 > ctx->w || x0 >= x1) return fail(ctx, RT_ERR_BAD_ARG, "column range must satisfy 0 <= x0 < x1 <= w");
-    if (plane_stride < (int64_t)(x1 - x0) * ctx->h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
+    const rt::View &v = ctx->view;
+    int rc = refuse(ctx, rt::check_state(ctx->have_scene, v));
+    if (rc == RT_OK) rc = refuse(ctx, rt::check_columns(v, x0, x1));
+    if (rc != RT_OK) return rc;
+    if (plane_stride < (int64_t)(x1 - x0) * v.h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, stream);
     rt::KParams k;
-    std::memset(&k, 0, sizeof k);
-    k.scene = (const double *)ctx->scene[ctx->scene_cur].p;
-    {
-        auto &rd = ctx->scene_readers[ctx->scene_cur];
-        if (std::find(rd.begin(), rd.end(), st) == rd.end()) rd.push_back(st);
-    }
-    k.nframes = 1;
-    k.pixel_loc = ctx->explicit_grid ? (const double *)ctx->pixel_loc.p : nullptr;
-    k.out_f32 = (float *)d_guides;
-    k.plane_stride = plane_stride;
-    k.w = ctx->w; k.h = ctx->h; k.x0 = x0; k.x1 = x1;
-    k.S = ctx->lay.S; k.P = ctx->lay.P; k.L = ctx->lay.L; k.NC = ctx->lay.NC; k.plane_codes = ctx->lay.plane_codes;
-    k.lanes_primary = ctx->lanes_primary;
-    k.tiles_y = (int)rt_geo_tiles(ctx->h);
-    k.px = ctx->px; k.y0 = ctx->y0; k.dy = ctx->dy; k.z0 = ctx->z0; k.dz = ctx->dz;
-    std::memcpy(k.cam_o, ctx->cam_o, sizeof k.cam_o);
-    std::memcpy(k.cam_R, ctx->cam_R, sizeof k.cam_R);
-    const int textured = ctx->lay.T > 0 ? 1 : 0;
-    if (textured) { k.lens.tex = ctx->lay.tex_off; k.lens.texels = (const float *)ctx->texels[ctx->scene_cur].p; }
-    k.anchors = rt::anchors_of(ctx->lay);
+    rt::guides_part(k, v, ctx->lay, scene_for(ctx, st), (const double *)ctx->pixel_loc.p, (const float *)ctx->texels[ctx->scene_cur].p,
+                    ctx->lanes_primary, x0, x1, d_guides, plane_stride);
     const rt::GuidesPlan plan = rt::plan_guides(ctx->lay, ctx->knobs, k.anchors);
-    const double cam2 = ctx->cam_o[0] * ctx->cam_o[0] + ctx->cam_o[1] * ctx->cam_o[1] + ctx->cam_o[2] * ctx->cam_o[2];
-    k.extent2 = (float)(1.0001 * (cam2 > ctx->lay.extent2 ? cam2 : ctx->lay.extent2));
-    {   // (as launch() with depth 0: every ray starts at the camera)
-        const double reach = std::sqrt(cam2) + 999.0 + std::sqrt(ctx->lay.extent2);
-        k.floor_anch = (float)(0x1p-39 * reach * reach);
-    }
-    int rc = acquire_tables(ctx, k, st, &k.ftab);
+    rc = acquire_tables(ctx, k, st, &k.ftab);
     if (rc != RT_OK) return rc;
     const void *fn = plan.mode == 2 ? (const void *)rt::guides_kernel<2> : (plan.mode == 1 ? (const void *)rt::guides_kernel<1> : (const void *)rt::guides_kernel<0>);
-    if (plan.lds > 48 * 1024 && plan.lds > ctx->guides_lds_set) {
-        for (const void *kf : {(const void *)rt::guides_kernel<0>, (const void *)rt::guides_kernel<1>, (const void *)rt::guides_kernel<2>})
-            RT_HIP(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-        ctx->guides_lds_set = plan.lds;
-    }
+    const void *const all[] = {(const void *)rt::guides_kernel<0>, (const void *)rt::guides_kernel<1>, (const void *)rt::guides_kernel<2>};
+    rc = raise_lds(ctx, all, 3, plan.lds, ctx->guides_lds_set);
+    if (rc != RT_OK) return rc;
     rt::div_magic((unsigned)k.tiles_y, k.tiles_y_magic, k.tiles_y_shift);
-    // at most RT_GEO_MAX_ITEMS work-items per dispatch: a slab beyond that goes out as narrower column slabs, as dispatch() cuts a frame
-    const rt_geo_plan g = rt_geo_plan_of(x0, x1, ctx->h, rt::GUIDE_WPW, 1);
+    // at most RT_GEO_MAX_ITEMS work-items per dispatch: a slab beyond that goes out as narrower column slabs
+    const rt_geo_plan g = rt_geo_plan_of(x0, x1, v.h, rt::GUIDE_WPW, 1);
     for (long long s = 0; s < g.nslabs; ++s) {
-        const long long sx0 = x0 + s * g.slab_tiles * rt::TILE, sx1 = std::min<long long>(x1, sx0 + g.slab_tiles * rt::TILE);
-        rt::KParams ks = k;
-        ks.x0 = (int)sx0; ks.x1 = (int)sx1;
-        ks.ntiles = (int)(rt_geo_tiles(sx1 - sx0) * k.tiles_y);
-        ks.out_f32 += (sx0 - x0) * ctx->h;
-        int tex = textured;
+        rt::KParams ks = rt::slab_params(k, g, s);
+        int tex = ctx->lay.T > 0 ? 1 : 0;
         void *args[] = {(void *)&ks, (void *)&tex};
         const unsigned blocks = (unsigned)((ks.ntiles + rt::GUIDE_WPW - 1) / rt::GUIDE_WPW);
         RT_HIP(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64 * rt::GUIDE_WPW), args, plan.lds, st));
@@ -1026,7 +929,7 @@ int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
     if (d_out == d_sum || d_out == d_guides || (d_work && (d_work == d_sum || d_work == d_guides || d_work == d_out)))
         return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_out and d_work must be buffers of their own");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, stream);
     rt::DenoiseArgs a;
     std::memset(&a, 0, sizeof a);
     a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
@@ -1047,6 +950,23 @@ int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
     return RT_OK;
 }
 
+// The staging planes grown where the frame is larger than any before, one launch into them and one copy per output to host memory,
+// all queued on `stream`.
+static int render_staged(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out_u8, float *out_f32, Buf &u8, Buf &f32,
+                         hipStream_t stream)
+{
+    const size_t npx = (size_t)(x1 - x0) * ctx->view.h;
+    int rc = out_u8 ? ensure(ctx, u8, 3 * npx) : RT_OK;
+    if (rc == RT_OK && out_f32) rc = ensure(ctx, f32, 3 * npx * sizeof(float));
+    if (rc == RT_OK)
+        rc = launch(ctx, params, x0, x1, out_u8 ? u8.p : nullptr, out_f32 ? f32.p : nullptr,
+                    (params->flags & RT_FLAG_U8_HWC) ? (int64_t)(x1 - x0) : (int64_t)npx, stream);
+    if (rc != RT_OK) return rc;
+    if (out_u8) RT_HIP(ctx, hipMemcpyAsync(out_u8, u8.p, 3 * npx, hipMemcpyDeviceToHost, stream));
+    if (out_f32) RT_HIP(ctx, hipMemcpyAsync(out_f32, f32.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, stream));
+    return RT_OK;
+}
+
 int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out_u8, float *out_f32)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
@@ -1054,12 +974,11 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
     if (rc != RT_OK) return rc;
     if (!out_u8 && !out_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)(x1 - x0) * ctx->h;
-    if (out_u8 && (rc = ensure(ctx, ctx->u8, 3 * npx)) != RT_OK) return rc;
+    const size_t npx = (size_t)(x1 - x0) * ctx->view.h;
+    if (out_u8 && (rc = ensure(ctx, ctx->u8, 3 * npx)) != RT_OK) return rc;      // (the chunks below need the staging planes too)
     if (out_f32 && (rc = ensure(ctx, ctx->f32, 3 * npx * sizeof(float))) != RT_OK) return rc;
+    if ((rc = refuse(ctx, rt::check_host_hwc(params, out_f32))) != RT_OK) return rc;
     const bool hwc = (params->flags & RT_FLAG_U8_HWC) != 0;
-    if (hwc && out_f32)
-        return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC: request the uint8 image and the float32 buffer in separate calls");
     // Large planar frames are rendered in RT_RENDER_CHUNKS column chunks, alternately on two streams (consecutive
     // launches overlap), and every chunk's planes start their way to the host (third stream, behind an
     // event) while the following chunks still render: the copy of a 1080p frame costs about as much as rendering it,
@@ -1067,11 +986,8 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
     const long long tiles = rt_geo_tiles(x1 - x0);
     const int NCH = ctx->render_chunks;
     if (hwc || NCH < 2 || npx < (1u << 19) || tiles < 4 * NCH) {
-        rc = launch(ctx, params, x0, x1, out_u8 ? ctx->u8.p : nullptr, out_f32 ? ctx->f32.p : nullptr,
-                    hwc ? (int64_t)(x1 - x0) : (int64_t)npx, ctx->stream);
+        rc = render_staged(ctx, params, x0, x1, out_u8, out_f32, ctx->u8, ctx->f32, ctx->stream);
         if (rc != RT_OK) return rc;
-        if (out_u8) RT_HIP(ctx, hipMemcpyAsync(out_u8, ctx->u8.p, 3 * npx, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_f32) RT_HIP(ctx, hipMemcpyAsync(out_f32, ctx->f32.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return RT_OK;
     }
@@ -1123,10 +1039,10 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
         return RT_OK;
     };
     unsigned *const tile_stats = ctx->tile_stats;
-    const int tiles_y = (ctx->h + rt::TILE - 1) / rt::TILE;
+    const int tiles_y = (ctx->view.h + rt::TILE - 1) / rt::TILE;
     for (int c = 0; c < NCH; ++c) {
         hipStream_t s = instream ? ctx->chunk_stream[c] : ((c & 1) ? ctx->stream2 : ctx->stream);
-        const size_t off = (size_t)(cx[c] - x0) * ctx->h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->h;
+        const size_t off = (size_t)(cx[c] - x0) * ctx->view.h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->view.h;
         // rt_set_tile_stats: a chunk records from its own first tile column on (chunk edges are multiples of the tile size)
         if (tile_stats) ctx->tile_stats = tile_stats + (size_t)((cx[c] - x0) / rt::TILE) * tiles_y;
         rc = launch(ctx, params, cx[c], cx[c + 1], out_u8 ? (uint8_t *)ctx->u8.p + off : nullptr,
@@ -1142,7 +1058,7 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
         return RT_OK;
     }
     for (int c = 0; c < NCH; ++c) {
-        const size_t off = (size_t)(cx[c] - x0) * ctx->h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->h;
+        const size_t off = (size_t)(cx[c] - x0) * ctx->view.h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->view.h;
         RT_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->chunk_ev[c], 0));
         if ((rc = copy_chunk(off, n, ctx->copy_stream)) != RT_OK) return rc;
     }
@@ -1157,9 +1073,7 @@ int rt_render_begin(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_
     if (rc != RT_OK) return rc;
     if (slot < 0 || slot >= RT_RENDER_SLOTS) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_begin: slot outside 0..RT_RENDER_SLOTS-1");
     if (!out_u8 && !out_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
-    const bool hwc = (params->flags & RT_FLAG_U8_HWC) != 0;
-    if (hwc && out_f32)
-        return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC: request the uint8 image and the float32 buffer in separate calls");
+    if ((rc = refuse(ctx, rt::check_host_hwc(params, out_f32))) != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     rt_ctx::Slot &sl = ctx->slots[slot];
     if (!sl.stream) RT_HIP(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
@@ -1167,15 +1081,7 @@ int rt_render_begin(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_
     // ahead of it in that stream (its staging planes are free by the time this launch writes them), the frames of the
     // other slots render and travel beside it.  The staging planes grow on the first frame of a larger size only
     // (hipFree waits for the device).
-    const size_t npx = (size_t)(x1 - x0) * ctx->h;
-    if (out_u8 && (rc = ensure(ctx, sl.u8, 3 * npx)) != RT_OK) return rc;
-    if (out_f32 && (rc = ensure(ctx, sl.f32, 3 * npx * sizeof(float))) != RT_OK) return rc;
-    rc = launch(ctx, params, x0, x1, out_u8 ? sl.u8.p : nullptr, out_f32 ? sl.f32.p : nullptr,
-                hwc ? (int64_t)(x1 - x0) : (int64_t)npx, sl.stream);
-    if (rc != RT_OK) return rc;
-    if (out_u8) RT_HIP(ctx, hipMemcpyAsync(out_u8, sl.u8.p, 3 * npx, hipMemcpyDeviceToHost, sl.stream));
-    if (out_f32) RT_HIP(ctx, hipMemcpyAsync(out_f32, sl.f32.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, sl.stream));
-    return RT_OK;
+    return render_staged(ctx, params, x0, x1, out_u8, out_f32, sl.u8, sl.f32, sl.stream);
 }
 
 int rt_render_end(rt_ctx *ctx, int slot)
@@ -1311,7 +1217,7 @@ int rt_stream_sync(rt_ctx *ctx, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(stream_of(ctx, stream)));
     return RT_OK;
 }
 
@@ -1319,7 +1225,7 @@ int rt_timer_begin(rt_ctx *ctx, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipEventRecord(ctx->ev0, stream ? (hipStream_t)stream : ctx->stream));
+    RT_HIP(ctx, hipEventRecord(ctx->ev0, stream_of(ctx, stream)));
     return RT_OK;
 }
 
@@ -1328,7 +1234,7 @@ int rt_timer_end(rt_ctx *ctx, void *stream, float *ms)
     if (!ctx) return RT_ERR_BAD_ARG;
     if (!ms) return fail(ctx, RT_ERR_BAD_ARG, "ms is NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipEventRecord(ctx->ev1, stream ? (hipStream_t)stream : ctx->stream));
+    RT_HIP(ctx, hipEventRecord(ctx->ev1, stream_of(ctx, stream)));
     RT_HIP(ctx, hipEventSynchronize(ctx->ev1));
     RT_HIP(ctx, hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
     return RT_OK;

@@ -377,3 +377,87 @@ def test_feedback_orders_are_never_overwritten_under_a_reader(feedback_check):
     last = out.strip().splitlines()[-1].split()
     assert last[0] == "steps=300000" and last[-1] == "ok" and len(out.strip().splitlines()) == 4, out
     assert all(int(f.split("=")[1]) > 100 for f in last[1:-1]), out
+
+
+LAUNCH_PARAMS_FIELDS = (
+    "scene", "pixel_loc", "out_u8", "out_f32", "tile_cycles", "cost", "order", "order_tiles", "seq_offset", "nframes", "bpf", "frame_stride",
+    "ftab", "ray_counts", "out_f64", "lattice", "lat_x0", "lat_h", "plane_stride", "w", "h", "x0", "x1", "S", "P", "L", "depth", "NC",
+    "plane_codes", "aa", "u8_rgb", "tiles_y", "ntiles", "tiles_y_magic", "tiles_y_shift", "bpf_magic", "bpf_shift", "anchors", "spp", "seed",
+    "u8_hwc", "lanes_primary", "extent2", "floor_anch", "px", "y0", "dy", "z0", "dz") + tuple(f"cam_o{i}" for i in range(3)) + tuple(
+    f"cam_R{i}" for i in range(9)) + ("amb", "lamb", "facing_tau") + tuple(f"union{i}" for i in range(16)) + ("texels",)
+
+_STATE = [(-4, "rt_set_scene has not been called"), (-4, "rt_set_camera has not been called"),
+          (-4, "rt_set_raygen / rt_set_pixel_loc has not been called")]
+_COLUMNS = (-1, "column range must satisfy 0 <= x0 < x1 <= w")
+_HWC_F32 = (-1, "RT_FLAG_U8_HWC re-uses plane_stride as the image row pitch: render the float32 buffer in a separate call")
+_OK = (0, "")
+# (code, rt_last_error text) per case of tests/algo/launch_check.cpp's entry_checks(), in its order: the texts of mi355rt.hip as it
+# was before the checks became functions of rt_launch.h
+LAUNCH_CHECKS = [
+    ("params/ok", _OK), ("params/null", (-1, "params is NULL")),
+    ("params/no_scene", _STATE[0]), ("params/no_camera", _STATE[1]), ("params/no_grid", _STATE[2]),
+    ("params/depth_above", (-1, "depth outside 0..RT_MAX_DEPTH")), ("params/depth_below", (-1, "depth outside 0..RT_MAX_DEPTH")),
+    ("params/aa_mode", (-1, "unknown aa_mode")),
+    ("params/spp_zero", (-1, "spp outside 1..RT_MAX_SPP")), ("params/spp_above", (-1, "spp outside 1..RT_MAX_SPP")),
+    ("params/stochastic_explicit_grid", (-4, "RT_AA_STOCHASTIC needs the closed-form ray grid (rt_set_raygen)")),
+    ("params/stochastic_ok", _OK),
+    ("params/x0_negative", _COLUMNS), ("params/x1_above_w", _COLUMNS), ("params/empty_range", _COLUMNS),
+    ("params/count_rays_with_materials", (-1, "RT_FLAG_COUNT_RAYS is not available for a scene with materials")),
+    ("params/count_rays_plain_ok", _OK),
+    ("params/lens_without_materials", (-4, "a lens with aperture > 0 needs a scene with a material table (M >= 1)")),
+    ("params/lens_ok", _OK),
+    ("guides/no_scene", _STATE[0]), ("guides/no_camera", _STATE[1]), ("guides/no_grid", _STATE[2]), ("guides/state_ok", _OK),
+    ("guides/x1_above_w", _COLUMNS), ("guides/columns_ok", _OK),
+    ("device/ok", _OK), ("device/both_null", (-1, "both output pointers are NULL")), ("device/hwc_f32", _HWC_F32),
+    ("device/hwc_pitch", (-1, "row pitch smaller than the slab width")), ("device/hwc_frame_stride", _OK), ("device/hwc_ok", _OK),
+    ("device/plane_stride", (-1, "plane_stride smaller than the slab")), ("device/frame_stride", _OK),
+    ("sequence/ok", _OK), ("sequence/both_null", (-1, "both output pointers are NULL")), ("sequence/hwc_f32", _HWC_F32),
+    ("sequence/hwc_pitch", (-1, "row pitch smaller than the slab width")),
+    ("sequence/hwc_frame_stride", (-1, "frame_stride smaller than one image")), ("sequence/hwc_ok", _OK),
+    ("sequence/plane_stride", (-1, "plane_stride smaller than the slab")),
+    ("sequence/frame_stride", (-1, "frame_stride smaller than three planes")),
+    ("host/hwc_f32", (-1, "RT_FLAG_U8_HWC: request the uint8 image and the float32 buffer in separate calls")),
+    ("host/hwc_ok", _OK), ("host/planar_ok", _OK),
+]
+
+
+def test_launch_params_are_the_recorded_ones(tmp_path):
+    """python-ray-tracer_amd/csrc/rt_launch.h, the kernels' argument (rt::KParams) as the host fills it and the entry checks, under
+    AddressSanitizer and UndefinedBehaviorSanitizer over the table of tests/algo/launch_check.cpp: the closed-form and the explicit
+    grid x depth 0, 3, 16 x a camera at the origin, near it and far beyond the scene's extent x a lens off / on x a PLAIN, MAT, TEX,
+    LIT and SKY scene (with the lens: LENS, TEX_LENS, LIT_LENS_SOFT, SKY_LENS_SOFT), each as a render launch, as it leaves for the
+    device (one frame, or three in one dispatch) and as a guides launch; the lattice pair of RT_AA_REFERENCE for a slab at the left
+    edge, in the interior and at the right edge, with frames 0 and 3 of a sequence; and every slab of a frame beyond one dispatch
+    ((RT_GEO_MAX_W - 8) x 8, whole and from column 24 to 3 short of the end) with uint8 planar + tile cycles, uint8 HWC, float32,
+    float64 lattice samples, frame 3 of a float32 sequence, and as a guides launch.  648 KParams, every field of each (floats as raw
+    bits, pointers as offsets from made-up bases) exactly what tests/golden/launch_params.npz holds: what the library built before
+    this became a header, recorded by a program that included that commit's rt_device.h, held that commit's launch(), dispatch(),
+    launch_one() and rt_render_guides() expressions copied verbatim, was built with hipcc for gfx950 and ran on a CPU without a HIP
+    call.  The program itself checks that the guides' reach values (extent2, floor_anch) are those of a depth-0 render of the same
+    view without a lens, whatever the view's lens, and that the slabs tile their column range.  The entry checks' codes and texts
+    are compared with LAUNCH_CHECKS above."""
+    import numpy as np
+    exe, got_path, checks_path = str(tmp_path / "launch_check"), str(tmp_path / "got.bin"), str(tmp_path / "checks.txt")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "launch_check.cpp")])
+    res = subprocess.run([exe, got_path, checks_path], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == f"records=648 checks={len(LAUNCH_CHECKS)} ok", res.stdout
+    want = np.load(os.path.join(REPO, "tests", "golden", "launch_params.npz"))["rows"]
+    got = np.fromfile(got_path, np.int64).reshape(-1, 3 + len(LAUNCH_PARAMS_FIELDS))
+    assert got.shape == want.shape == (648, 84)
+    assert np.array_equal(got[:, :3], want[:, :3])
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, [(got[i, :3].tolist(), LAUNCH_PARAMS_FIELDS[j - 3], int(got[i, j]), int(want[i, j])) for i, j in bad[:8]]
+    # what the table is there for: every kind of record, every union shape, both sides of |cam|^2 against the extent, slabs
+    kind, fam = got[:, 1], got[got[:, 1] == 0][:, 2]
+    assert {k: int((kind == k).sum()) for k in range(7)} == {0: 180, 1: 180, 2: 180, 3: 12, 4: 12, 5: 24, 6: 60}
+    assert set(fam.tolist()) == {0, 1, 5, 7, 9, 12, 14, 16, 18}
+    col = {n: got[:, 3 + i] for i, n in enumerate(LAUNCH_PARAMS_FIELDS)}
+    assert len(set(col["extent2"][kind == 0].tolist())) >= 3 and len(set(col["floor_anch"][kind == 0].tolist())) >= 9
+    assert set(col["texels"][kind == 2].tolist()) == {-1, 0} and (col["out_f64"][kind == 4] >= 0).all()
+    slab = kind == 6
+    assert slab.sum() == 60 and col["x1"][slab].max() == 2**31 - 16 and col["ntiles"][slab].max() * 64 + 256 <= 2**32
+    with open(checks_path) as f:
+        lines = [ln.rstrip("\n").split("\t") for ln in f]
+    assert [(n, (int(c), m)) for n, c, m in lines] == LAUNCH_CHECKS
