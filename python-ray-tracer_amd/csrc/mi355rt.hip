@@ -3,7 +3,7 @@
 // rt_create fails and nothing renders.  What a call decides before it touches the device lives in
 // HIP-free headers: the packed scene (rt_scene.h), the launch arithmetic (rt_geometry.h), the
 // launch's kernel and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the dispatch-order
-// feedback (rt_feedback.h).
+// feedback (rt_feedback.h), the per-stream state: cull-table sets, scratch buffers, scene readers (rt_streams.h).
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_denoise.h"
@@ -14,6 +14,7 @@
 #include "rt_launch.h"
 #include "rt_plan.h"
 #include "rt_scene.h"
+#include "rt_streams.h"
 
 #include <cmath>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -33,23 +35,39 @@ namespace {
 
 std::string g_create_error;
 
-struct Buf {
+struct Buf {                          // device memory, owned: freed with the Buf
     void *p = nullptr;
     size_t cap = 0;
+    Buf() = default;
+    Buf(Buf &&o) noexcept { *this = std::move(o); }
+    Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~Buf() { if (p) (void)hipFree(p); }
 };
 
 }  // namespace
 
-#define RT_SCENE_RING 4
 #define RT_COUNT_WORDS (4 + 2 * (RT_MAX_DEPTH + 1))   /* ray counters + per bounce {waves, alive lanes} */
 #define RT_RENDER_CHUNKS 8   /* upper bound; the pipeline uses ctx->render_chunks of them */
 
 struct rt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr, copy_stream = nullptr;   // rt_render's chunk pipeline (created on first use)
-    hipEvent_t chunk_ev[RT_RENDER_CHUNKS] = {};
-    hipStream_t chunk_stream[RT_RENDER_CHUNKS] = {};
+    struct Pipeline {                 // rt_render's chunk pipeline (created on first use, completely or not at all)
+        hipStream_t stream2 = nullptr, copy_stream = nullptr;
+        hipEvent_t chunk_ev[RT_RENDER_CHUNKS] = {};
+        hipStream_t chunk_stream[RT_RENDER_CHUNKS] = {};
+        template <class F> void streams(F f)
+        {
+            for (hipStream_t s : {stream2, copy_stream}) if (s) f(s);
+            for (hipStream_t s : chunk_stream) if (s) f(s);
+        }
+        ~Pipeline()
+        {
+            streams([](hipStream_t s) { (void)hipStreamDestroy(s); });
+            for (hipEvent_t e : chunk_ev) if (e) (void)hipEventDestroy(e);
+        }
+    };
+    std::unique_ptr<Pipeline> pipe;
     int chunk_mode = -1;              // -1 = by destination memory type
     int cluster_min = rt::CLUSTER_MIN;            // scenes with more spheres are stored in clusters (MI355RT_CLUSTER_MINS overrides)
     int lanes_primary = 1;            // MI355RT_LANES_PRIMARY=0: the lane-owned traversal from bounce 1 on only (primary rays and their shadow
@@ -67,9 +85,8 @@ struct rt_ctx {
     // The packed scene records live in a ring of device buffers: rt_set_scene fills the NEXT one and launches carry the
     // pointer of the one that was current when they were queued, so frames in flight on any stream keep the scene they
     // were launched with (include/mi355rt.h: rt_render_begin).  A buffer comes up for reuse RT_SCENE_RING scene changes
-    // later; the streams that launched with it are synchronised then (by that time they have long finished with it).
+    // later; the streams that launched with it (rt_streams.h) are synchronised then (by that time they have long finished with it).
     Buf scene[RT_SCENE_RING];
-    std::vector<hipStream_t> scene_readers[RT_SCENE_RING];
     int scene_cur = 0;
     Buf pixel_loc, u8, f32;
     rt::SceneLayout lay;          // the current scene (rt_scene.h): counts, families' flags, block offsets, plane codes, extent
@@ -86,30 +103,30 @@ struct rt_ctx {
     } fbs[RT_FEEDBACK_SLOTS];
     rt::FeedbackBook book;
     rt_ctx() { for (int i = 0; i < RT_FEEDBACK_SLOTS; ++i) book.slot[i] = &fbs[i]; }
+    // Every stream the context created (a caller's streams are the caller's).
+    template <class F> void own_streams(F f)
+    {
+        if (stream) f(stream);
+        for (Slot &sl : slots) if (sl.stream) f(sl.stream);
+        if (pipe) pipe->streams(f);
+    }
+    // (the device is the current one, and the streams are drained: rt_destroy; the members free their buffers after this)
+    ~rt_ctx()
+    {
+        for (auto &f : fbs)
+            for (void *e : rt::release_events(f)) (void)hipEventDestroy((hipEvent_t)e);
+        pipe.reset();
+        own_streams([](hipStream_t s) { (void)hipStreamDestroy(s); });
+        for (hipEvent_t e : {ev0, ev1}) if (e) (void)hipEventDestroy(e);
+    }
     rt_stats stats = {};              // host-side launch counters (the ray counters live in `counts`)
     Buf counts;                       // 4 x uint64 on the device: ray counters of RT_FLAG_COUNT_RAYS launches
-    std::vector<std::pair<hipStream_t, Buf>> lattice;   // per launching stream: float64 lattice samples (RT_AA_REFERENCE)
-    std::vector<std::pair<hipStream_t, Buf>> film;      // per launching stream: float32 pass frames (rt_film_accumulate)
     int cu_count = 256;
     unsigned long long epoch = 1;     // bumped by every rt_set_*: scene, camera or ray grid changed
     unsigned long long scene_epoch = 1;   // bumped by rt_set_scene only
-    // The float32 cull tables (rt::tables_kernel) of the last (scene, camera position, floor) combinations, PER STREAM: a
-    // set is built on the stream of the launch that needs it and read only by launches of that stream, so rebuilding a
-    // stream's older set is ordered behind its readers by the stream itself — no events, no cross-stream waits.  (Round 2
-    // shared three sets among the streams behind events; with a camera that moves every frame the events made every
-    // stream wait for the others' newest launches: frames of different streams no longer overlapped, +45 %.)  Frames
-    // of a static camera on n streams build n identical sets once (a few microseconds each).
-    struct Tables {
-        Buf buf;
-        bool valid = false;
-        unsigned long long scene_epoch = 0, stamp = 0;
-        double cam[3] = {0, 0, 0};
-        float floor_anch = 0.0f;
-        int anchors = -1;
-    };
-    struct StreamTables { hipStream_t stream = nullptr; Tables sets[2]; };
-    std::vector<StreamTables> tables;
-    unsigned long long table_stamp = 0;
+    // Per launching stream (rt_streams.h): its two cull-table sets, its float64 lattice samples (RT_AA_REFERENCE), its float32 pass
+    // frames (rt_film_accumulate), and the scene buffers of the ring it reads.
+    rt::StreamBook<Buf> streams;
     std::string err;
 };
 
@@ -143,12 +160,16 @@ int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1) { return refus
 
 hipStream_t stream_of(rt_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
-// The current scene buffer, with `stream` noted as one of its readers (set_scene drains them before the buffer is rewritten).
-const double *scene_for(rt_ctx *ctx, hipStream_t stream)
+using StreamRecord = rt::StreamBook<Buf>::Record;
+
+// The record of a launching stream (rt_streams.h), with the current scene buffer noted as one it reads (set_scene drains the
+// readers before the buffer is rewritten).
+int stream_record(rt_ctx *ctx, hipStream_t stream, StreamRecord **out)
 {
-    auto &rd = ctx->scene_readers[ctx->scene_cur];
-    if (std::find(rd.begin(), rd.end(), stream) == rd.end()) rd.push_back(stream);
-    return (const double *)ctx->scene[ctx->scene_cur].p;
+    const int rc = ctx->streams.record(stream, out);
+    if (rc != RT_OK) return fail(ctx, rc, ctx->streams.NO_MEMORY);
+    ctx->streams.reads_scene(**out, ctx->scene_cur);
+    return RT_OK;
 }
 
 // More than the default 48 KiB of dynamic LDS: raised on all of `fns` (nullptr: no such kernel) at once; `set` remembers the size.
@@ -196,67 +217,34 @@ static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int
               (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
               "KERNELS lists the families in enum order");
 
-// The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
-int acquire_tables(rt_ctx *ctx, const rt::KParams &k, hipStream_t stream, const float **out)
+// One of the stream's own buffers, `bytes` large (rt_streams.h: growing frees the old buffer, behind a synchronise).
+int stream_buffer(rt_ctx *ctx, Buf &b, hipStream_t stream, size_t bytes, bool sync)
 {
-    rt_ctx::StreamTables *st = nullptr;
-    for (auto &c : ctx->tables) if (c.stream == stream) { st = &c; break; }
-    if (!st) {
-        try { ctx->tables.emplace_back(); } catch (const std::bad_alloc &) { return fail(ctx, RT_ERR_ALLOC, "out of host memory"); }
-        st = &ctx->tables.back();
-        st->stream = stream;
-    }
-    rt_ctx::Tables *victim = &st->sets[0];
-    for (auto &t : st->sets) {
-        if (t.valid && t.scene_epoch == ctx->scene_epoch && t.anchors == k.anchors && t.floor_anch == k.floor_anch &&
-            std::memcmp(t.cam, k.cam_o, sizeof t.cam) == 0) {
-            t.stamp = ++ctx->table_stamp;
-            *out = (const float *)t.buf.p;
-            return RT_OK;
-        }
-        if ((!t.valid && victim->valid) || (t.valid == victim->valid && t.stamp < victim->stamp)) victim = &t;
-    }
-    rt_ctx::Tables &t = *victim;
-    t.valid = false;
+    if (sync) RT_HIP(ctx, hipStreamSynchronize(stream));
+    return ensure(ctx, b, bytes);
+}
+
+// The cull tables for this launch's scene / camera position / floor: reuse one of the stream's sets or rebuild its older one.
+int acquire_tables(rt_ctx *ctx, StreamRecord &sr, const rt::KParams &k, const float **out)
+{
+    const hipStream_t stream = (hipStream_t)sr.stream;
+    const rt::TableKey key = rt::table_key(ctx->scene_epoch, k.anchors, k.floor_anch, k.cam_o);
     const size_t bytes = rt::table_floats(k.S, k.NC, k.anchors, false, true, k.P) * sizeof(float);   // (with the colours)
-    if (t.buf.cap < (bytes ? bytes : 16)) RT_HIP(ctx, hipStreamSynchronize(stream));       // (growing frees the old buffer)
-    int rc = ensure(ctx, t.buf, bytes ? bytes : 16);
-    if (rc != RT_OK) return rc;
-    hipLaunchKernelGGL(rt::tables_kernel, dim3(1), dim3(rt::TABLE_THREADS), 0, stream, k, (float *)t.buf.p);
-    ctx->stats.table_builds++;
-    RT_HIP(ctx, hipGetLastError());
-    t.scene_epoch = ctx->scene_epoch; t.anchors = k.anchors; t.floor_anch = k.floor_anch;
-    std::memcpy(t.cam, k.cam_o, sizeof t.cam);
-    t.valid = true;
-    t.stamp = ++ctx->table_stamp;
-    *out = (const float *)t.buf.p;
+    const rt::TableDecision d = ctx->streams.tables(sr, key, bytes);
+    Buf &b = sr.buf[rt::BUF_TABLES0 + d.set];
+    if (d.rebuild) {
+        int rc = stream_buffer(ctx, b, stream, d.bytes, d.sync);
+        if (rc != RT_OK) return rc;
+        hipLaunchKernelGGL(rt::tables_kernel, dim3(1), dim3(rt::TABLE_THREADS), 0, stream, k, (float *)b.p);
+        ctx->stats.table_builds++;
+        RT_HIP(ctx, hipGetLastError());
+        ctx->streams.tables_queued(sr, d.set, key);
+    }
+    *out = (const float *)b.p;
     return RT_OK;
 }
 
 int dispatch(rt_ctx *ctx, const rt_params *p, rt::KParams &k, const rt::LaunchPlan &plan, hipStream_t stream, int nframes, int64_t frame_stride);
-
-// The lattice buffer of a stream (RT_AA_REFERENCE with the closed-form grid renders the half-pixel lattice once into
-// float64 samples, then sums nine of them per pixel): one buffer per launching stream, so that frames in flight on
-// different streams keep their samples apart.
-int stream_buffer(rt_ctx *ctx, std::vector<std::pair<hipStream_t, Buf>> &bufs, hipStream_t stream, size_t bytes, void **out)
-{
-    for (auto &e : bufs)
-        if (e.first == stream) {
-            if (e.second.cap < bytes) RT_HIP(ctx, hipStreamSynchronize(stream));
-            int rc = ensure(ctx, e.second, bytes);
-            *out = e.second.p;
-            return rc;
-        }
-    bufs.emplace_back(stream, Buf{});
-    int rc = ensure(ctx, bufs.back().second, bytes);
-    *out = bufs.back().second.p;
-    return rc;
-}
-
-int lattice_buffer(rt_ctx *ctx, hipStream_t stream, size_t bytes, double **out)
-{
-    return stream_buffer(ctx, ctx->lattice, stream, bytes, (void **)out);
-}
 
 // nframes > 1 (rt_render_sequence): that many frames of the current scene and camera, frame f into the outputs +
 // f * frame_stride elements — one launch for all of them where the dispatch order is settled.
@@ -272,13 +260,14 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     const rt::LaunchPlan plan = rt::plan_launch(ctx->lay, ctx->knobs, v.lens_a, !lattice && p->aa_mode != 0, p->flags, lattice, rt::anchors_of(ctx->lay));
     if (plan.index < 0 || !KERNELS[(int)plan.family][plan.index])
         return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: rt_plan.h, missing_kernels_never_park)
+    StreamRecord *sr = nullptr;                                // the stream's record, looked up once: scene, tables, lattice
+    int rc = stream_record(ctx, stream, &sr);
+    if (rc != RT_OK) return rc;
     rt::KParams k;
-    rt::render_part(k, v, ctx->lay, plan.family, p, scene_for(ctx, stream), (const double *)ctx->pixel_loc.p,
+    rt::render_part(k, v, ctx->lay, plan.family, p, (const double *)ctx->scene[ctx->scene_cur].p, (const double *)ctx->pixel_loc.p,
                     (const float *)ctx->texels[ctx->scene_cur].p, ctx->lanes_primary, x0, x1, d_u8, d_f32, plane_stride, ctx->tile_stats);
-    {
-        int rc = acquire_tables(ctx, k, stream, &k.ftab);
-        if (rc != RT_OK) return rc;
-    }
+    rc = acquire_tables(ctx, *sr, k, &k.ftab);
+    if (rc != RT_OK) return rc;
     // RT_AA_REFERENCE on the closed-form grid: the reference's nine taps of a pixel are the 3x3 neighbourhood of the
     // pixel's centre on the (2w-1) x (2h-1) half-pixel lattice — the tap between two pixels is 0.5 Pa + 0.5 Pb, bit
     // for bit the same from either side (IEEE addition commutes), and with a separable grid both diagonals of a cell
@@ -287,9 +276,12 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
     // the reference's order (kernels.py:53-65, including its G/B swap).  Explicit pixel_loc grids are not separable
     // in general and keep the nine-taps-per-pixel kernel.
     if (lattice) {
-        double *lat = nullptr;
-        int rc = lattice_buffer(ctx, stream, (size_t)(li1 - li0) * (size_t)(2ll * v.h - 1) * 3 * sizeof(double), &lat);
+        // one lattice buffer per launching stream, so that frames in flight on different streams keep their samples apart
+        Buf &lb = sr->buf[rt::BUF_LATTICE];
+        const size_t bytes = (size_t)(li1 - li0) * (size_t)(2ll * v.h - 1) * 3 * sizeof(double);
+        rc = stream_buffer(ctx, lb, stream, bytes, rt::growth(lb.cap, bytes).sync);
         if (rc != RT_OK) return rc;
+        double *lat = (double *)lb.p;
         rt::KParams kl;
         rt::lattice_pair(k, kl, li0, li1, lat);
         const long long npx = (long long)(x1 - x0) * v.h;
@@ -512,29 +504,7 @@ int rt_destroy(rt_ctx *ctx)
 {
     if (!ctx) return RT_OK;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (Buf *b : {&ctx->pixel_loc, &ctx->u8, &ctx->f32, &ctx->counts})
-        if (b->p) (void)hipFree(b->p);
-    for (Buf &b : ctx->scene) if (b.p) (void)hipFree(b.p);
-    for (Buf &b : ctx->texels) if (b.p) (void)hipFree(b.p);
-    for (auto &e : ctx->lattice) if (e.second.p) (void)hipFree(e.second.p);
-    for (auto &e : ctx->film) if (e.second.p) (void)hipFree(e.second.p);
-    for (auto &f : ctx->fbs) {
-        for (Buf *b : {&f.cost, &f.gtmp, &f.btmp, &f.order[0], &f.order[1]}) if (b->p) (void)hipFree(b->p);
-        for (void *e : rt::release_events(f)) (void)hipEventDestroy((hipEvent_t)e);
-    }
-    for (auto &st : ctx->tables)
-        for (auto &t : st.sets) if (t.buf.p) (void)hipFree(t.buf.p);
-    for (hipStream_t st : {ctx->stream2, ctx->copy_stream}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (auto &sl : ctx->slots) {
-        if (sl.stream) { (void)hipStreamSynchronize(sl.stream); (void)hipStreamDestroy(sl.stream); }
-        for (Buf *b : {&sl.u8, &sl.f32}) if (b->p) (void)hipFree(b->p);
-    }
-    for (hipEvent_t e : ctx->chunk_ev) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : ctx->chunk_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    ctx->own_streams([](hipStream_t s) { (void)hipStreamSynchronize(s); });
     delete ctx;
     return RT_OK;
 }
@@ -553,9 +523,8 @@ static int set_scene(rt_ctx *ctx, const rt::SceneDesc &desc)
     // the next buffer of the ring: launches in flight keep reading the buffers they were queued with.  Whatever
     // launched with THIS buffer did so RT_SCENE_RING scene changes ago; its streams are drained before it is rewritten.
     const int next = (ctx->scene_cur + 1) % RT_SCENE_RING;
-    for (hipStream_t st : ctx->scene_readers[next]) RT_HIP(ctx, hipStreamSynchronize(st));
-    ctx->scene_readers[next].clear();
-    int rc = ensure(ctx, ctx->scene[next], bytes);
+    int rc = ctx->streams.drain_scene(next, [ctx](void *st) { RT_HIP(ctx, hipStreamSynchronize((hipStream_t)st)); return (int)RT_OK; });
+    if (rc == RT_OK) rc = ensure(ctx, ctx->scene[next], bytes);
     if (rc != RT_OK) return rc;
     if (ps.layout.T > 0 || ps.layout.lit) {                 // (the texture and lighting kernels' texel array)
         rc = ensure(ctx, ctx->texels[next], ps.texels.size() * sizeof(float));
@@ -809,9 +778,13 @@ int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
     const size_t pass_bytes = (size_t)fplane * 3 * sizeof(float);
     int batch = passes < rt::FILM_BATCH ? passes : rt::FILM_BATCH;
     if (batch * pass_bytes > rt::FILM_SCRATCH_MAX) batch = 1;
-    float *frames = nullptr;
-    rc = stream_buffer(ctx, ctx->film, st, batch * pass_bytes, (void **)&frames);
+    StreamRecord *sr = nullptr;
+    rc = stream_record(ctx, st, &sr);
     if (rc != RT_OK) return rc;
+    Buf &fb = sr->buf[rt::BUF_FILM];
+    rc = stream_buffer(ctx, fb, st, batch * pass_bytes, rt::growth(fb.cap, batch * pass_bytes).sync);
+    if (rc != RT_OK) return rc;
+    float *const frames = (float *)fb.p;
     rt::FilmAddArgs a;
     a.sum = (double *)d_sum; a.frames = frames; a.sum_stride = sum_stride; a.fplane = fplane; a.npx = npx;
     const dim3 grid(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 3), 3);
@@ -877,11 +850,14 @@ int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_
     if (plane_stride < (int64_t)(x1 - x0) * v.h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
+    StreamRecord *sr = nullptr;
+    rc = stream_record(ctx, st, &sr);
+    if (rc != RT_OK) return rc;
     rt::KParams k;
-    rt::guides_part(k, v, ctx->lay, scene_for(ctx, st), (const double *)ctx->pixel_loc.p, (const float *)ctx->texels[ctx->scene_cur].p,
-                    ctx->lanes_primary, x0, x1, d_guides, plane_stride);
+    rt::guides_part(k, v, ctx->lay, (const double *)ctx->scene[ctx->scene_cur].p, (const double *)ctx->pixel_loc.p,
+                    (const float *)ctx->texels[ctx->scene_cur].p, ctx->lanes_primary, x0, x1, d_guides, plane_stride);
     const rt::GuidesPlan plan = rt::plan_guides(ctx->lay, ctx->knobs, k.anchors);
-    rc = acquire_tables(ctx, k, st, &k.ftab);
+    rc = acquire_tables(ctx, *sr, k, &k.ftab);
     if (rc != RT_OK) return rc;
     const void *fn = plan.mode == 2 ? (const void *)rt::guides_kernel<2> : (plan.mode == 1 ? (const void *)rt::guides_kernel<1> : (const void *)rt::guides_kernel<0>);
     const void *const all[] = {(const void *)rt::guides_kernel<0>, (const void *)rt::guides_kernel<1>, (const void *)rt::guides_kernel<2>};
@@ -1004,15 +980,19 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
         else (void)hipGetLastError();                           // plain malloc memory: "invalid value", not an error here
         if (ctx->chunk_mode >= 0) instream = ctx->chunk_mode == 1;
     }
-    if (!ctx->copy_stream) {
-        RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-        RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        for (auto &e : ctx->chunk_ev) RT_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!ctx->pipe) {                                          // (a set-up that fails half-way is released here, and tried again by the next call)
+        std::unique_ptr<rt_ctx::Pipeline> pl(new (std::nothrow) rt_ctx::Pipeline);
+        if (!pl) return fail(ctx, RT_ERR_ALLOC, "out of host memory");
+        RT_HIP(ctx, hipStreamCreateWithFlags(&pl->stream2, hipStreamNonBlocking));
+        RT_HIP(ctx, hipStreamCreateWithFlags(&pl->copy_stream, hipStreamNonBlocking));
+        for (auto &e : pl->chunk_ev) RT_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         int lo = 0, hi = 0;
         RT_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));   // lo = least urgent (numerically largest)
         for (int c = 0; c < RT_RENDER_CHUNKS; ++c)
-            RT_HIP(ctx, hipStreamCreateWithPriority(&ctx->chunk_stream[c], hipStreamNonBlocking, std::min(lo, hi + c)));
+            RT_HIP(ctx, hipStreamCreateWithPriority(&pl->chunk_stream[c], hipStreamNonBlocking, std::min(lo, hi + c)));
+        ctx->pipe = std::move(pl);
     }
+    rt_ctx::Pipeline &pl = *ctx->pipe;
     int cx[RT_RENDER_CHUNKS + 1];
     // the first and the last chunk are half as wide as the others: the copies start sooner, and the one copy that
     // nothing overlaps (the last chunk's) is short
@@ -1041,7 +1021,7 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
     unsigned *const tile_stats = ctx->tile_stats;
     const int tiles_y = (ctx->view.h + rt::TILE - 1) / rt::TILE;
     for (int c = 0; c < NCH; ++c) {
-        hipStream_t s = instream ? ctx->chunk_stream[c] : ((c & 1) ? ctx->stream2 : ctx->stream);
+        hipStream_t s = instream ? pl.chunk_stream[c] : ((c & 1) ? pl.stream2 : ctx->stream);
         const size_t off = (size_t)(cx[c] - x0) * ctx->view.h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->view.h;
         // rt_set_tile_stats: a chunk records from its own first tile column on (chunk edges are multiples of the tile size)
         if (tile_stats) ctx->tile_stats = tile_stats + (size_t)((cx[c] - x0) / rt::TILE) * tiles_y;
@@ -1051,18 +1031,18 @@ int rt_render(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out
         if (rc != RT_OK) return rc;
         if (instream) {
             if ((rc = copy_chunk(off, n, s)) != RT_OK) return rc;
-        } else RT_HIP(ctx, hipEventRecord(ctx->chunk_ev[c], s));
+        } else RT_HIP(ctx, hipEventRecord(pl.chunk_ev[c], s));
     }
     if (instream) {
-        for (int c = 0; c < NCH; ++c) RT_HIP(ctx, hipStreamSynchronize(ctx->chunk_stream[c]));
+        for (int c = 0; c < NCH; ++c) RT_HIP(ctx, hipStreamSynchronize(pl.chunk_stream[c]));
         return RT_OK;
     }
     for (int c = 0; c < NCH; ++c) {
         const size_t off = (size_t)(cx[c] - x0) * ctx->view.h, n = (size_t)(cx[c + 1] - cx[c]) * ctx->view.h;
-        RT_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->chunk_ev[c], 0));
-        if ((rc = copy_chunk(off, n, ctx->copy_stream)) != RT_OK) return rc;
+        RT_HIP(ctx, hipStreamWaitEvent(pl.copy_stream, pl.chunk_ev[c], 0));
+        if ((rc = copy_chunk(off, n, pl.copy_stream)) != RT_OK) return rc;
     }
-    RT_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    RT_HIP(ctx, hipStreamSynchronize(pl.copy_stream));
     return RT_OK;
 }
 
@@ -1169,27 +1149,13 @@ int rt_stream_create(rt_ctx *ctx, void **stream)
     return RT_OK;
 }
 
-// The context remembers streams that launched on it (owner / readers of the dispatch order, readers of the cull
-// tables) so that it can fence them later: drop every reference to `stream` once its queued work is complete.
+// The context remembers streams that launched on it (owner / readers of the dispatch order, rt_feedback.h; the stream's record,
+// rt_streams.h) so that it can fence them later: drop every reference to `stream` once its queued work is complete.
 static int forget_stream(rt_ctx *ctx, hipStream_t stream)
 {
     RT_HIP(ctx, hipStreamSynchronize(stream));
-    for (size_t i = 0; i < ctx->lattice.size();) {
-        if (ctx->lattice[i].first == stream) { if (ctx->lattice[i].second.p) (void)hipFree(ctx->lattice[i].second.p); ctx->lattice.erase(ctx->lattice.begin() + (long)i); }
-        else ++i;
-    }
-    for (size_t i = 0; i < ctx->film.size();) {
-        if (ctx->film[i].first == stream) { if (ctx->film[i].second.p) (void)hipFree(ctx->film[i].second.p); ctx->film.erase(ctx->film.begin() + (long)i); }
-        else ++i;
-    }
     ctx->book.forget(stream);                                   // (its work is complete: nothing of it reads an order any more)
-    for (auto &rd : ctx->scene_readers) rd.erase(std::remove(rd.begin(), rd.end(), stream), rd.end());
-    for (size_t i = 0; i < ctx->tables.size();) {               // the stream's own cull-table sets go with it
-        if (ctx->tables[i].stream == stream) {
-            for (auto &t : ctx->tables[i].sets) if (t.buf.p) (void)hipFree(t.buf.p);
-            ctx->tables.erase(ctx->tables.begin() + (long)i);
-        } else ++i;
-    }
+    ctx->streams.forget(stream);                                // (its table sets and scratch buffers go with its record: ~Buf)
     return RT_OK;
 }
 

@@ -1,12 +1,13 @@
 /* The library's dispatch-order feedback rules (python-ray-tracer_amd/csrc/rt_feedback.h) without HIP, driven as mi355rt.hip's dispatch()
- * and launch_one() drive them, over a fake runtime.  Built with AddressSanitizer and UndefinedBehaviorSanitizer (leak detection on)
+ * and launch_one() drive them, over a fake runtime; in the replay also the cull-table cache of rt_streams.h, as acquire_tables() drives it.  Built with AddressSanitizer and UndefinedBehaviorSanitizer (leak detection on)
  * and run by tests/test_algorithms.py.
  *
- *   feedback_check replay SCRIPT OUT   runs the step script tests/algo/feedback_trace_cases.py writes (the scene, then per context
- *                                      its MI355RT_REMEASURE and its steps), synchronising the launching stream after every launch,
- *                                      and writes one line "measured settled" (0/1 each) per step to OUT.  The keys come from the
- *                                      scene's layout (rt_scene.h), plan_launch and order_shape (rt_plan.h), rt_geo_plan_of and
- *                                      rt_geo_lattice (rt_geometry.h), as launch() and dispatch() build them.
+ *   feedback_check replay SCRIPT OUT   runs the step script tests/algo/feedback_trace_cases.py writes (the scene and the cameras, then
+ *                                      per context its MI355RT_REMEASURE and its steps), synchronising the launching stream after every
+ *                                      launch, and writes one line "measured settled tables_built" (0/1 each) per step to OUT.  The
+ *                                      keys come from the scene's layout (rt_scene.h), plan_launch and order_shape (rt_plan.h),
+ *                                      rt_geo_plan_of and rt_geo_lattice (rt_geometry.h), as launch() and dispatch() build them; the
+ *                                      cull tables' key from the launch's KParams (rt_launch.h: render_part), as launch() fills it.
  *   feedback_check walk [SEED]         a random walk of WALK_STEPS = 100000 steps for each MI355RT_REMEASURE of 0, 2 and 24: 12
  *                                      geometries over the 8 slots, 4 streams; launches with and without feedback, epoch bumps,
  *                                      completion of a prefix of a stream's queue (so a switch comes late, early or never),
@@ -24,7 +25,9 @@
  * Happens-before is a vector clock per stream, advanced by same-stream order, by "stream waits event", by an event or a stream
  * the host has observed complete, and by a device synchronise. */
 #include "../../python-ray-tracer_amd/csrc/rt_feedback.h"
+#include "../../python-ray-tracer_amd/csrc/rt_launch.h"
 #include "../../python-ray-tracer_amd/csrc/rt_plan.h"
+#include "../../python-ray-tracer_amd/csrc/rt_streams.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -135,8 +138,10 @@ struct Context {
     Fake &fk;
     rt::FeedbackSlot slots[RT_FEEDBACK_SLOTS];
     rt::FeedbackBook book;
-    unsigned long long epoch = 1;
+    unsigned long long epoch = 1, scene_epoch = 1;
     int remeasure;
+    struct TableBuf { size_t cap = 0; };              /* (the replay keeps no device memory: streams_check.cpp does) */
+    rt::StreamBook<TableBuf> streams;
     std::vector<Op> readers[RT_FEEDBACK_SLOTS][2];    /* launches that read order[b] */
     Op writer[RT_FEEDBACK_SLOTS][2];                  /* the last order kernel that wrote order[b] (op 0: none) */
     Op last_order[RT_FEEDBACK_SLOTS];                 /* the slot's last order kernel: the reader of its cost buffer */
@@ -215,9 +220,25 @@ struct Context {
             for (int b = a + 1; b < RT_FEEDBACK_SLOTS; ++b) CHECK(!(slots[a].key == slots[b].key), "a key in two slots");
         return d;
     }
+    /* acquire_tables() for a launch with these kernel arguments: whether it builds a table set */
+    bool tables(void *stream, const rt::KParams &k)
+    {
+        rt::StreamBook<TableBuf>::Record *sr = nullptr;
+        CHECK(streams.record(stream, &sr) == RT_OK, "out of host memory");
+        const rt::TableKey key = rt::table_key(scene_epoch, k.anchors, k.floor_anch, k.cam_o);
+        const rt::TableDecision d = streams.tables(*sr, key, rt::table_floats(k.S, k.NC, k.anchors, false, true, k.P) * sizeof(float));
+        if (!d.rebuild) return false;
+        if (d.sync) fk.sync(fk.of(stream));
+        TableBuf &b = sr->buf[rt::BUF_TABLES0 + d.set];
+        if (b.cap < d.bytes) b.cap = d.bytes;
+        fk.queue(fk.of(stream));                                                    /* the tables kernel */
+        streams.tables_queued(*sr, d.set, key);
+        return true;
+    }
     void forget(void *stream)                         /* forget_stream() */
     {
         fk.sync(fk.of(stream));
+        streams.forget(stream);
         bool pending = false;
         for (const rt::FeedbackSlot &f : slots)
             for (const auto &e : f.fence) pending |= e.first == stream;
@@ -297,6 +318,10 @@ static int replay(const char *script, const char *out_path)
     const rt::PackedScene ps = rt::pack_scene(desc, rt::CLUSTER_MIN, knobs.lanes_min_spheres);
     if (ps.status != RT_OK) { std::fprintf(stderr, "pack_scene: %s\n", ps.error.c_str()); return 1; }
     const rt::SceneLayout &lay = ps.layout;
+    int ncam = 0;
+    if (std::fscanf(fi, " cameras %d", &ncam) != 1 || ncam < 1) return 2;
+    std::vector<double> cameras((size_t)(3 * ncam));                             /* rt_set_camera's origins, as float64 */
+    for (double &v : cameras) if (std::fscanf(fi, "%lf", &v) != 1) return 2;
 
     Fake *fk = nullptr;
     Context *ctx = nullptr;
@@ -312,7 +337,7 @@ static int replay(const char *script, const char *out_path)
     };
     for (g_step = 0; std::fscanf(fi, "%31s", word) == 1; ++g_step) {
         const std::string kind = word;
-        int measured = 0, settled = 0;
+        int measured = 0, settled = 0, built = 0;
         if (kind == "ctx") {                                                      /* rt_create under MI355RT_REMEASURE */
             int rm;
             if (std::fscanf(fi, "%d", &rm) != 1) return 2;
@@ -326,9 +351,10 @@ static int replay(const char *script, const char *out_path)
         if (!ctx) return 2;
         if (kind == "scene") {                                                    /* rt_set_scene: always a new epoch */
             ctx->epoch++;
+            ctx->scene_epoch++;
         } else if (kind == "camera") {                                            /* rt_set_camera: the same camera again changes nothing */
             int c;
-            if (std::fscanf(fi, "%d", &c) != 1) return 2;
+            if (std::fscanf(fi, "%d", &c) != 1 || c < 0 || c >= ncam) return 2;
             if (c != cam) ctx->epoch++;
             cam = c;
         } else if (kind == "grid") {                                              /* rt_set_raygen: nor does the same grid */
@@ -343,10 +369,19 @@ static int replay(const char *script, const char *out_path)
         } else if (kind == "launch") {
             int s, x0, x1, depth, aa, spp, flags;
             if (std::fscanf(fi, "%d %d %d %d %d %d %d", &s, &x0, &x1, &depth, &aa, &spp, &flags) != 7) return 2;
-            if (s < 0 || s > 2 || x0 < 0 || x1 > w || x0 >= x1) return 2;
+            if (s < 0 || s > 2 || x0 < 0 || x1 > w || x0 >= x1 || cam < 0) return 2;
             long long l0 = 0, l1 = 0;
             const bool lattice = aa == RT_AA_REFERENCE && rt_geo_lattice(w, h, x0, x1, &l0, &l1) && !(flags & RT_FLAG_AA_PER_PIXEL);
             const rt::LaunchPlan plan = rt::plan_launch(lay, knobs, 0.0, !lattice && aa != 0, flags, lattice, rt::anchors_of(lay));
+            rt::View v;                                                           /* (the tables' key takes the camera's position only) */
+            v.w = w; v.h = h; v.have_cam = v.have_grid = true;
+            std::memcpy(v.cam_o, &cameras[(size_t)(3 * cam)], sizeof v.cam_o);
+            rt_params p;
+            std::memset(&p, 0, sizeof p);
+            p.depth = depth; p.aa_mode = aa; p.spp = spp; p.flags = flags;
+            rt::KParams k;
+            rt::render_part(k, v, lay, plan.family, &p, nullptr, nullptr, nullptr, 1, x0, x1, nullptr, nullptr, 0, nullptr);
+            built = ctx->tables(fk->handle(s), k);
             const int kx0 = lattice ? (int)l0 : x0, kx1 = lattice ? (int)l1 : x1, kh = lattice ? 2 * h - 1 : h, kaa = lattice ? 0 : aa;
             const rt_geo_plan g = rt_geo_plan_of(kx0, kx1, kh, plan.shape.wpw, 1);
             if (g.nslabs != 1) return 2;
@@ -359,7 +394,7 @@ static int replay(const char *script, const char *out_path)
             std::fprintf(stderr, "unknown step %s\n", word);
             return 2;
         }
-        std::fprintf(fo, "%d %d\n", measured, settled);
+        std::fprintf(fo, "%d %d %d\n", measured, settled, built);
         ++steps;
     }
     close();

@@ -78,12 +78,16 @@ def _range(g):
 
 
 def write_script(path):
-    """SCRIPT_A, once per MI355RT_REMEASURE, in the text form feedback_check reads: the scene, then `ctx R` and the steps."""
+    """SCRIPT_A, once per MI355RT_REMEASURE, in the text form feedback_check reads: the scene, the cameras' origins, then `ctx R` and the
+    steps."""
     g = np.load(os.path.join(GOLDEN, f"frame_{FIXTURE}.npz"))
     with open(path, "w") as f:
         f.write(f"scene {g['spheres'].shape[1]} {g['lights'].shape[1]} {g['planes'].shape[1]}\n")
         for a in (g["spheres"], g["lights"], g["planes"]):
             f.write(" ".join(repr(float(v)) for v in np.ascontiguousarray(a, np.float32).ravel()) + "\n")
+        f.write(f"cameras {len(CAMERA_SHIFTS)}\n")              # rt_set_camera's origins, as replay() passes them
+        for shift in CAMERA_SHIFTS:
+            f.write(" ".join(repr(float(v)) for v in np.asarray(g["cam_origin"], np.float64) + np.asarray(shift)) + "\n")
         for rm in REMEASURES:
             f.write(f"ctx {rm}\n")
             for s in SCRIPT_A:

@@ -339,7 +339,12 @@ def test_feedback_decisions_are_the_recorded_ones(feedback_check, tmp_path):
     launch_one() call it, the launching stream synchronised after every launch.  The keys come from rt_scene.h's layout of the
     scene, plan_launch, rt_geo_plan_of, rt_geo_lattice and order_shape.  Whether each step measured and whether it was settled must
     be, exactly, what tests/golden/feedback_trace.npz holds: the launches_measuring and launches_settled deltas of rt_get_stats,
-    recorded on the GPU from the library as it was before the rules became a header of their own."""
+    recorded on the GPU from the library as it was before the rules became a header of their own.  Each launch's KParams are filled
+    by rt_launch.h's render_part and rt_streams.h is asked for the cull tables as acquire_tables() asks it: whether the step built a
+    table set must be the table_builds delta of the same recording (three streams, four cameras, depths 1 and 3, the lattice variant,
+    scene changes and rt_stream_forget).  Tried once: rebuilding the more recently used set instead of the older one fails this at
+    step 83 (the 8 x 8 frame's first launch builds a set that the recording found), and dropping floor_anch from the key at steps 9
+    and 81 (a depth-1 launch after depth-3 ones must build)."""
     import numpy as np
     sys.path.insert(0, ALGO)
     try:
@@ -351,17 +356,18 @@ def test_feedback_decisions_are_the_recorded_ones(feedback_check, tmp_path):
     out = _run_feedback_check([feedback_check, "replay", script, got_path])
     n = len(ftc.SCRIPT_A)
     assert out.strip() == f"steps={3 * n} ok", out
-    got = np.loadtxt(got_path, dtype=np.int64).reshape(3, n, 2)
+    got = np.loadtxt(got_path, dtype=np.int64).reshape(3, n, 3)
     want = np.load(os.path.join(REPO, "tests", "golden", "feedback_trace.npz"))
-    assert tuple(want["fields"][2:4]) == ("launches_measuring", "launches_settled")
+    assert tuple(want["fields"][2:5]) == ("launches_measuring", "launches_settled", "table_builds")
     for i, rm in enumerate(ftc.REMEASURES):
         rows = want[f"A/{rm}"]
         assert rows.shape == (n, len(ftc.FIELDS))
-        bad = np.flatnonzero((got[i] != rows[:, 2:4]).any(axis=1))
-        assert bad.size == 0, [(rm, int(j), ftc.SCRIPT_A[j], got[i][j].tolist(), rows[j, 2:4].tolist()) for j in bad[:5]]
+        bad = np.flatnonzero((got[i] != rows[:, 2:5]).any(axis=1))
+        assert bad.size == 0, [(rm, int(j), ftc.SCRIPT_A[j], got[i][j].tolist(), rows[j, 2:5].tolist()) for j in bad[:5]]
+        assert rows[:, 4].sum() > 20 and (rows[:, 4] == 0).sum() > 20               # (the recording holds builds and hits)
         # the paths the script is there for: settled in three launches, a re-measure once the order is older than MI355RT_REMEASURE
         # launches, and a camera change that keeps the order where it is not
-        assert got[i][3:7].tolist() == [[1, 0], [1, 0], [0, 1], [0, 1]]
+        assert got[i][3:7, :2].tolist() == [[1, 0], [1, 0], [0, 1], [0, 1]]
         moved = got[i][ftc.SCRIPT_A.index(("camera", 1)) + 1:][:6]
         assert moved[:, 0].tolist() == {24: [0] * 6, 2: [0, 0, 1, 1, 0, 0], 0: [1, 1, 0, 0, 0, 0]}[rm]
 
@@ -377,6 +383,25 @@ def test_feedback_orders_are_never_overwritten_under_a_reader(feedback_check):
     last = out.strip().splitlines()[-1].split()
     assert last[0] == "steps=300000" and last[-1] == "ok" and len(out.strip().splitlines()) == 4, out
     assert all(int(f.split("=")[1]) > 100 for f in last[1:-1]), out
+
+
+def test_stream_state_survives_a_random_walk(tmp_path):
+    """The random walk of tests/algo/streams_check.cpp over python-ray-tracer_amd/csrc/rt_streams.h, a stand-alone program under
+    AddressSanitizer (leak detection on) and UndefinedBehaviorSanitizer: launches on 4 streams of a fake runtime whose completions
+    are decoupled from the launches, lattice and film requests that grow and shrink, scene changes round the ring, rt_stream_forget,
+    teardown and a fresh context, for 1, 3 and 6 camera positions and as many steps each as the feedback walk.  After every step: a
+    hit names a set built for exactly that key on that stream and a rebuild takes the right victim; a buffer is freed or regrown
+    only when what its stream has queued is complete; a scene buffer is rewritten only when its readers are complete; a forgotten
+    stream leaves no record and no buffer; at teardown every buffer and stream was released exactly once.  Each transition (hit,
+    rebuild of an invalid set, rebuild of the older set, growth behind a synchronise, drain at a scene change, forget with buffers,
+    teardown) is taken for every setting."""
+    exe = str(tmp_path / "streams_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "streams_check.cpp")])
+    out = _run_feedback_check([exe])
+    last = out.strip().splitlines()[-1].split()
+    assert last[0] == "steps=300000" and last[-1] == "ok" and len(out.strip().splitlines()) == 4, out
+    assert len(last) == 9 and all(int(f.split("=")[1]) > 100 for f in last[1:-1]), out
 
 
 LAUNCH_PARAMS_FIELDS = (
