@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rt_kparams.h"  // rt::KParams, the kernels' argument (the host fills it: rt_launch.h)
+#include "rt_math.h"     // V3, the seeded bodies of normalize3 / div_inrange / sqrt_inrange / renormalize_unit, the counter hashes, clip_color
 #include "rt_facing.h"   // the facing certificate of the point-light loop (trace_bounce) and its margin
 #include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets, the LDS image's arithmetic (lds_bytes, table_layout, ...), TILE, div_magic:
                          // shared with the host's scene packer (rt_scene.h) and launch plan (rt_plan.h)
@@ -65,32 +66,8 @@ __device__ __forceinline__ int div_by(int n, int d, unsigned M, unsigned sh)
     return d == 1 ? n : (int)(__umulhi((unsigned)n, M) >> sh);
 }
 
-struct V3 { double x, y, z; };
-struct F3 { float x, y, z; };
-
-__device__ __forceinline__ double dot3(const V3 &a, const V3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }   // common.py:35-37
-
-// common.py:28-32 — sqrt and three true divisions, as the compiler lowers them (correctly rounded).
-__device__ __forceinline__ V3 normalize3_generic(const V3 &v)
-{
-    double n = __builtin_sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-    return V3{v.x / n, v.y / n, v.z / n};
-}
-
-// The same normalize with the work the three divisions have in common done once.  The AMDGPU backend lowers
-//   sqrt(x):  y = rsq(x); g = x*y; h = y/2; r = fma(-h,g,1/2); g = fma(g,r,g); h = fma(h,r,h);
-//             twice { d = fma(-g,g,x); g = fma(d,h,g); }                      (+ range scaling of x)
-//   a / b:    r = rcp(b); twice { e = fma(-b,r,1); r = fma(r,e,r); }  q = a*r; res = fma(fma(-b,q,a), r, q)
-//                                                                             (+ div_scale / div_fixup)
-// both correctly rounded.  For operands well inside the exponent range the scaling steps are identities, so
-// the sequences below return bit-identical results while the reciprocal (5 of a division's 11 instructions) is
-// shared by x/n, y/n, z/n and the sqrt skips its range handling.  The reciprocal itself needs no v_rcp_f64
-// (a quarter-rate instruction): the sqrt iteration's h already approximates 1/(2g) to ~2^-50, so one Newton
-// step from 2h lands where the backend's two steps from the rcp seed land — within half an ulp (+2^-47) of
-// 1/g, which is what the final fma correction of each quotient requires.  26 instructions instead of 55.  Guard (wave-uniform): every component's magnitude >= 2^-200 (hence nonzero, and |v|² >= 2^-400) and
-// |v|² <= 2^400, so no intermediate leaves the normal range and no signed-zero case arises; otherwise the
-// generic path.  tests/test_algorithms.py replays this on the CPU against sqrt()/division on 10^8 vectors
-// with seeds 16x less accurate than v_rsq_f64 / v_rcp_f64.
+// The four exact-arithmetic shortcuts: rt_math.h has their derivations and their bodies (which the CPU checks of tests/algo run);
+// here are the build switches, the wave-uniform guards and the hardware's seeds.
 __device__ __forceinline__ V3 normalize3(const V3 &v)
 {
 #if RT_FAST_NORMALIZE == 0
@@ -98,42 +75,17 @@ __device__ __forceinline__ V3 normalize3(const V3 &v)
 #else
     const double nn = v.x * v.x + v.y * v.y + v.z * v.z;
     const double cmin = __builtin_fmin(__builtin_fmin(__builtin_fabs(v.x), __builtin_fabs(v.y)), __builtin_fabs(v.z));
-    const bool ok = (cmin >= 0x1p-200) && (nn <= 0x1p400);                  // NaNs fail both
+    const bool ok = (cmin >= NORMALIZE_MIN_COMPONENT) && (nn <= NORMALIZE_MAX_NN);   // NaNs fail both
     if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) return normalize3_generic(v);
-    const double y = __builtin_amdgcn_rsq(nn);
-    double g = nn * y, h = 0.5 * y;
-    const double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, nn); g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, nn); g = __builtin_fma(d, h, g);               // g = RN(sqrt(nn))
-    double rc = 2.0 * h;                                                    // h ~ 1/(2g), relative error ~2^-50
-    const double e = __builtin_fma(-g, rc, 1.0); rc = __builtin_fma(rc, e, rc);   // within 1/2 ulp(1 + 2^-47) of 1/g
-    const double qx = v.x * rc, qy = v.y * rc, qz = v.z * rc;
-    return V3{__builtin_fma(__builtin_fma(-g, qx, v.x), rc, qx),
-              __builtin_fma(__builtin_fma(-g, qy, v.y), rc, qy),
-              __builtin_fma(__builtin_fma(-g, qz, v.z), rc, qz)};
+    return normalize3_seeded(v, nn, __builtin_amdgcn_rsq(nn));
 #endif
 }
-
-// The scene queries' own division and square root (t = num/den of a plane, t = n/a of the closest sphere, sqrt of a sphere's
-// discriminant), as the backend lowers them minus the range handling (see normalize3 above): v_div_scale x2 / v_div_fixup
-// and the sqrt's ldexp scaling are identities for operands well inside the exponent range, and there they are: scene values
-// are float32 (magnitudes 2^-149 .. 2^128 or zero), a plane's denominator is at least 0.001 in magnitude where the quotient is
-// formed (intersections.py:55), a is within rounding of 1, numerators and discriminants are sums of a few products of such
-// values (zero, or above 2^-600), while the backend scales below 2^-767 (sqrt) / numerators below 2^-969, denominators of
-// extreme exponent, exponent differences beyond 2^768 (division).  Outside that range (a camera at 1e300, infinities) both
-// forms end in an infinity, a NaN or a value whose comparison with (0, 999) has the same outcome: no hit.  3 of 11
-// instructions per division, 7 of 21 per square root.  tests/algo/divsqrt_check.c replays both on the CPU.
 __device__ __forceinline__ double div_inrange(double a, double b)
 {
 #if RT_FAST_DIVSQRT == 0
     return a / b;
 #else
-    double r = __builtin_amdgcn_rcp(b);
-    double e = __builtin_fma(-b, r, 1.0); r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-b, r, 1.0); r = __builtin_fma(r, e, r);
-    const double q = a * r;
-    return __builtin_fma(__builtin_fma(-b, q, a), r, q);
+    return div_seeded(a, b, __builtin_amdgcn_rcp(b));
 #endif
 }
 __device__ __forceinline__ double sqrt_inrange(double x)      // x >= 0 (or NaN)
@@ -141,51 +93,15 @@ __device__ __forceinline__ double sqrt_inrange(double x)      // x >= 0 (or NaN)
 #if RT_FAST_DIVSQRT == 0
     return __builtin_sqrt(x);
 #else
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    const double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x); g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x); g = __builtin_fma(d, h, g);
-    return x > 0.0 ? g : x;                                   // sqrt(+0) = +0 (the iteration yields NaN there: 0 * inf)
+    return sqrt_seeded(x, __builtin_amdgcn_rsq(x));
 #endif
 }
-
-// ---------------------------------------------------------------------------------------------
-// normalize() of a vector that is ALREADY unit length (every direction a scene query receives is
-// the output of a normalize) — bit-identical to normalize3(), without the generic sqrt and divides.
-//
-//   nn = fl(x²+y²+z²) lies within a few ulp of 1; e = nn - 1 is exact.  With eps = 2^-52:
-//     e = k·eps    (k >= 0):  sqrt = 1 + e/2 - e²/8 ..  ->  RN = 1 + floor(k/2)·eps
-//     e = -j·eps/2 (j >= 1):  sqrt = 1 + e/2 - e²/8 ..  ->  RN = 1 - ceil(j/2)·eps/2
-//   i.e. RN(sqrt(nn)) is 1 + e/2 rounded to nearest with every tie (odd k, odd j) resolved downward, because
-//   the second-order term is negative.  One fma rounds exactly once, so nudging e toward -inf by a relative
-//   2^-30 first (e2 = e - |e|·2^-30, far below half a grid step, far above e²/8) makes
-//   nrm = fma(e2, 1/2, 1) that value: the nudge decides the ties and moves nothing else.
-//   y = RN(1/nrm) likewise: with dl = nrm - 1 (exact), 1/nrm = 1 - dl + dl² .., ties (dl = -i·eps/2, i odd)
-//   resolved upward: y = fma(-dl, 1 + 2^-30, 1).
-//   Each quotient x/nrm is then  q1 = fma(-x, dl, x)  (faithful: off by |x|·dl² at most),
-//   r = fma(-q1, nrm, x) (the exact remainder),  q = fma(r, y, q1)  — Markstein's final correction,
-//   which returns the correctly rounded quotient RN(x/nrm) given y = RN(1/nrm) and a faithful q1.
-// Falls back to the generic path (wave-uniformly) if any live lane's nn is not within 2^-33 of 1.
-// tests/test_algorithms.py replays this routine on the CPU: nrm and y against sqrt and division for EVERY double
-// within 2^-33 of 1 (1.57 million), the whole routine against sqrt-and-divide on 10^7 vectors.
-// (The same values used to be derived from the IEEE bit pattern with 64-bit integer arithmetic: ~25 more
-// instructions per call, 13 calls per tile — one in seven of all the kernel's VALU instructions.)
-// ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ V3 renormalize_unit(const V3 &d)
 {
     const double nn = d.x * d.x + d.y * d.y + d.z * d.z;
     const double e = nn - 1.0;                                     // exact
-    if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(e) < 0x1p-33)) != 0ull) return normalize3_generic(d);
-    const double e2 = __builtin_fma(-__builtin_fabs(e), 0x1p-30, e);
-    const double nrm = __builtin_fma(e2, 0.5, 1.0);                // RN(sqrt(nn))
-    const double dl = nrm - 1.0;                                   // exact
-    const double y = __builtin_fma(-dl, 1.0 + 0x1p-30, 1.0);       // RN(1/nrm)
-    V3 q{__builtin_fma(-d.x, dl, d.x), __builtin_fma(-d.y, dl, d.y), __builtin_fma(-d.z, dl, d.z)};
-    const V3 r{__builtin_fma(-q.x, nrm, d.x), __builtin_fma(-q.y, nrm, d.y), __builtin_fma(-q.z, nrm, d.z)};
-    q = V3{__builtin_fma(r.x, y, q.x), __builtin_fma(r.y, y, q.y), __builtin_fma(r.z, y, q.z)};
-    return q;
+    if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(e) < UNIT_WINDOW)) != 0ull) return normalize3_generic(d);
+    return renormalize_unit_fast(d, e);
 }
 
 enum { HIT_NONE = 0, HIT_SPHERE = 1, HIT_PLANE = 2 };
@@ -675,7 +591,7 @@ __device__ __forceinline__ int plane_code(const KParams &p, int k)
 // (-den, -num) as for (den, num) — |den| < 0.001, |num| against |den|, whether the signs agree, and the quotient bit for bit
 // (IEEE division, and div_inrange: rcp is odd and each of its steps negates exactly; only a ZERO quotient may change sign, and
 // t > 0 fails for both).  Leaving the negation out saves two v_xor and two v_cndmask per test, for either sign of the code.
-// tests/algo/plane_sign_check.c replays it.
+// tests/algo/plane_sign_check.cpp restates it (with div_inrange as rt_math.h has it).
 __device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int code, const V3 &o, const V3 &d, double &den, double &num,
                                               bool no_negate = false)
 {
@@ -1195,36 +1111,6 @@ template <> struct RayCount<true> {
     __device__ __forceinline__ void shadow(bool alive, bool traced) { n_issued += (alive && traced) ? 1u : 0u; n_skipped += (alive && !traced) ? 1u : 0u; }
 };
 
-// The scatter hash (rt_set_scene_materials_scatter, mi355rt.h): jitter_hash(X, Y, ((s*16 + b)*8 + j)*4 + c, seed ^ 0x5CA77E12)
-// in two parts.  scatter_key is its first two rounds, on (X, Y), with s folded in: for b <= 15 the third argument is the bit
-// pattern s << 9 | b << 5 | j << 2 | c, so XOR-ing s << 9 into the state before the third round is the same as XOR-ing it in
-// there.  scatter_hash finishes it for the low nine bits t = b << 5 | j << 2 | c.
-__device__ __forceinline__ unsigned scatter_key(unsigned x, unsigned y, unsigned s, unsigned seed)
-{
-    unsigned h = (seed ^ 0x5CA77E12u) ^ 0x9E3779B9u;
-    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
-    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
-    return h ^ (s << 9);
-}
-__device__ __forceinline__ unsigned scatter_hash(unsigned key, unsigned t)
-{
-    unsigned h = (key ^ t) * 0x27D4EB2Fu; h ^= h >> 15;
-    h *= 0x165667B1u; h ^= h >> 13;
-    return h;
-}
-
-// The area-light hash (rt_set_scene_area_lights, mi355rt.h): jitter_hash(X, Y, t, seed ^ 0x50F7117E) with
-// t = ((((s*32 + b)*64 + m)*16 + i)*8 + j)*4 + c, the bit pattern s << 20 | b << 15 | m << 9 | i << 5 | j << 2 | c (s < 64,
-// b <= 16, m < 64, i < 16).  soft_key is its first two rounds on (X, Y) with s folded in (as scatter_key); scatter_hash
-// finishes it for t without s.
-__device__ __forceinline__ unsigned soft_key(unsigned x, unsigned y, unsigned s, unsigned seed)
-{
-    unsigned h = (seed ^ 0x50F7117Eu) ^ 0x9E3779B9u;
-    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
-    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
-    return h ^ (s << 20);
-}
-
 // Shadow sample point Q of a light record g = {cx, cy, cz, rho} for the hash key `key` (soft_key with t = b << 15 | m << 9 |
 // i << 5 folded in): the first of eight hashed candidates q in the unit ball (as scatter_continue's), Q = c + rho*q (float64,
 // no fused multiply-add: -ffp-contract=off), or c itself if none of the eight is inside.
@@ -1233,9 +1119,7 @@ __device__ __forceinline__ V3 soft_light_point(unsigned key, const double *g)
 #pragma unroll 1
     for (int j = 0; j < 8; ++j) {
         const unsigned t = (unsigned)j << 2;
-        const V3 c{(double)(scatter_hash(key, t) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
-                   (double)(scatter_hash(key, t | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
-                   (double)(scatter_hash(key, t | 2u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0)};
+        const V3 c{hash_unit(key, t), hash_unit(key, t | 1u), hash_unit(key, t | 2u)};
         if (dot3(c, c) < 1.0) { const double rho = g[3]; return V3{g[0] + rho * c.x, g[1] + rho * c.y, g[2] + rho * c.z}; }
     }
     return V3{g[0], g[1], g[2]};
@@ -1255,9 +1139,7 @@ __device__ __forceinline__ bool scatter_continue(const Lds &lds, const MS &ms, c
 #pragma unroll 1
     for (int j = 0; j < 8 && !found; ++j) {
         const unsigned t = ((unsigned)b << 5) | ((unsigned)j << 2);
-        const V3 c{(double)(scatter_hash(key, t) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
-                   (double)(scatter_hash(key, t | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0),
-                   (double)(scatter_hash(key, t | 2u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0)};
+        const V3 c{hash_unit(key, t), hash_unit(key, t | 1u), hash_unit(key, t | 2u)};
         if (dot3(c, c) < 1.0) { q = c; found = true; }
     }
     if (found) nd = normalize3(V3{R.x + rough * q.x, R.y + rough * q.y, R.z + rough * q.z});   // linear_comb(R, q, 1.0, rough)
@@ -1722,28 +1604,6 @@ __device__ __forceinline__ V3 primary_dir(const KParams &p, const V3 &P)
     return normalize3(v);                                                     // kernels.py:23
 }
 
-// Sub-pixel jitter of sample s of pixel (x,y) for the stochastic mode: a counter hash (no state, any launch
-// tiling gives the same frame).  u = ((h & 0xFFFF) + 1/2)/65536 - 1/2, v likewise from the high half: exact.
-__device__ __forceinline__ unsigned jitter_hash(unsigned x, unsigned y, unsigned s, unsigned seed)
-{
-    unsigned h = seed ^ 0x9E3779B9u;
-    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
-    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
-    h = (h ^ s) * 0x27D4EB2Fu; h ^= h >> 15;
-    h *= 0x165667B1u; h ^= h >> 13;
-    return h;
-}
-
-// The lens hash (rt_set_lens, mi355rt.h): jitter_hash(X, Y, (s*8 + j)*2 + c, seed ^ 0x1E45D0F5), the bit pattern s << 4 | j << 1 | c.
-// lens_key is its first two rounds on (X, Y) with s folded in (as scatter_key); scatter_hash finishes it for t = j << 1 | c.
-__device__ __forceinline__ unsigned lens_key(unsigned x, unsigned y, unsigned s, unsigned seed)
-{
-    unsigned h = (seed ^ 0x1E45D0F5u) ^ 0x9E3779B9u;
-    h = (h ^ x) * 0x85EBCA6Bu; h ^= h >> 13;
-    h = (h ^ y) * 0xC2B2AE35u; h ^= h >> 16;
-    return h ^ (s << 4);
-}
-
 // The thin-lens primary ray (o, d) of sample (X, Y, s) through the pixel point P (rt_set_lens, mi355rt.h), float64 without
 // fused multiply-add: v = R P as primary_dir forms it, the focal point F = O + (f / P.x) v (linear_comb(O, v, 1.0, f / P.x);
 // 1.0*O is exact), u the first of eight hashed candidates in the unit disk (u_c and u.u exact) or (0, 0),
@@ -1760,24 +1620,14 @@ __device__ __forceinline__ void lens_ray(const KParams &p, unsigned x, unsigned 
 #pragma unroll 1
     for (int j = 0; j < 8; ++j) {
         const unsigned tj = (unsigned)j << 1;
-        const double c0 = (double)(scatter_hash(key, tj) >> 8) * 0x1p-23 + (0x1p-24 - 1.0);
-        const double c1 = (double)(scatter_hash(key, tj | 1u) >> 8) * 0x1p-23 + (0x1p-24 - 1.0);
+        const double c0 = hash_unit(key, tj);
+        const double c1 = hash_unit(key, tj | 1u);
         if (c0 * c0 + c1 * c1 < 1.0) { u0 = c0; u1 = c1; break; }
     }
     const double a0 = p.lens.aperture * u0, a1 = p.lens.aperture * u1;
     o = V3{(p.cam_o[0] + a0 * p.cam_R[1]) + a1 * p.cam_R[2], (p.cam_o[1] + a0 * p.cam_R[4]) + a1 * p.cam_R[5],
            (p.cam_o[2] + a0 * p.cam_R[7]) + a1 * p.cam_R[8]};
     d = normalize3(V3{F.x - o.x, F.y - o.y, F.z - o.z});                     // common.py:28-32 of vector_difference(o, F)
-}
-
-// common.py:52-57: min(max(0, int(round(c))), 255), round half to even (v_rndne_f64).
-__device__ __forceinline__ uint8_t clip_color(double c)
-{
-    if (!(c == c)) return 0;
-    if (c <= -0.5) return 0;
-    if (c >= 255.5) return 255;
-    const int i = (int)__builtin_rint(c);
-    return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
 }
 
 // kernels.py:69-73: clip and store one pixel; off = (x - x0) h + y.

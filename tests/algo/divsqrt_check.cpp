@@ -1,49 +1,36 @@
-/* CPU replay of rt_device.h's div_inrange() and sqrt_inrange(): the AMDGPU backend's f64 division and square root
- * without their range handling (v_div_scale / v_div_fixup, ldexp scaling), which are identities inside the exponent
- * range the scene queries work in.
- *   a / b:    r = rcp(b); twice { e = fma(-b,r,1); r = fma(r,e,r); }  q = a*r; res = fma(fma(-b,q,a), r, q)
- *   sqrt(x):  y = rsq(x); g = x*y; h = y/2; r = fma(-h,g,1/2); g = fma(g,r,g); h = fma(h,r,h);
- *             twice { d = fma(-g,g,x); g = fma(d,h,g); }; x == 0 -> x
+/* rt_math.h's div_seeded() and sqrt_seeded() (rt_device.h: div_inrange, sqrt_inrange), the text the kernel compiles, against the
+ * correctly rounded / and sqrt(): the AMDGPU backend's f64 division and square root without their range handling (v_div_scale /
+ * v_div_fixup, ldexp scaling), which are identities inside the exponent range the scene queries work in.  The sequences are
+ * written out above rt_math.h's normalize3_seeded; only the seeds are this program's.
  * Seeds carry a relative error of up to 2^-24 here, i.e. WORSE than v_rcp_f64 / v_rsq_f64, so agreement with the
  * correctly rounded / and sqrt() on every sample is a conservative check.  Operand ranges: denominators 1e-3 .. 1e40 and
  * within an ulp of 1 (t = n/a), numerators 0 and 1e-130 .. 1e80, radicands 0 and 1e-130 .. 1e80 — wider than what
- * float32 scenes produce (see rt_device.h).  Built and run by tests/test_algorithms.py. */
+ * float32 scenes produce (see rt_device.h).
+ * A second pass on a quarter as many operands (the stream goes on) has seeds 2^-16 off.  At 2^-24 a Newton step too few leaves the
+ * reciprocal 2^-48 off and the corrected quotient 2^-96: no sample count sees that.  From 2^-16 the sequence as written still ends
+ * at rounding level (2^-64 after two steps), while one step fewer leaves 2^-32 and a quotient 2^-64 off, wrong once in about 2^11
+ * operands.  Built and run by tests/test_algorithms.py. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include "../../python-ray-tracer_amd/csrc/rt_math.h"
 
 static uint64_t s[2] = {0x9E3779B97F4A7C15ull, 0xD1B54A32D192ED03ull};
 static inline uint64_t rnd(void) { uint64_t a = s[0], b = s[1]; s[0] = b; a ^= a << 23; s[1] = a ^ b ^ (a >> 17) ^ (b >> 26); return s[1] + b; }
 static inline double urand(void) { return (double)(rnd() >> 11) * (1.0 / 9007199254740992.0); }
-static inline double noise(void) { return 1.0 + (urand() * 2 - 1) * 0x1p-24; }
+static double seed_err = 0x1p-24;
+static inline double noise(void) { return 1.0 + (urand() * 2 - 1) * seed_err; }
 
-static double div_inrange(double a, double b)
-{
-    double r = (1.0 / b) * noise();                        /* stand-in for v_rcp_f64 */
-    double e = fma(-b, r, 1.0); r = fma(r, e, r);
-    e = fma(-b, r, 1.0); r = fma(r, e, r);
-    const double q = a * r;
-    return fma(fma(-b, q, a), r, q);
-}
-
-static double sqrt_inrange(double x)
-{
-    const double y = (x > 0.0 ? 1.0 / sqrt(x) : INFINITY) * noise();   /* stand-in for v_rsq_f64 */
-    double g = x * y, h = 0.5 * y;
-    const double r = fma(-h, g, 0.5);
-    g = fma(g, r, g); h = fma(h, r, h);
-    double d = fma(-g, g, x); g = fma(d, h, g);
-    d = fma(-g, g, x); g = fma(d, h, g);
-    return x > 0.0 ? g : x;
-}
+static double div_inrange(double a, double b) { return rt::div_seeded(a, b, (1.0 / b) * noise()); }   /* stand-in for v_rcp_f64 */
+static double sqrt_inrange(double x) { return rt::sqrt_seeded(x, (x > 0.0 ? 1.0 / sqrt(x) : INFINITY) * noise()); }   /* for v_rsq_f64 */
 
 static double magnitude(int wide) { return exp((urand() - 0.5) * (wide ? 480.0 : 40.0)); }   /* 1e-104..1e104 / 2e-9..5e8 */
 
-int main(int argc, char **argv)
+/* n operand pairs and radicands with seeds up to seed_err off */
+static void pass(long n, long *baddiv_out, long *badsqrt_out)
 {
-    long n = argc > 1 ? atol(argv[1]) : 10000000, baddiv = 0, badsqrt = 0;
-    if (argc > 2) { s[0] ^= (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ull; s[1] += (uint64_t)atoll(argv[2]); }
+    long baddiv = 0, badsqrt = 0;
     for (long it = 0; it < n; ++it) {
         const int mode = it & 7;
         double a = (urand() * 2 - 1) * magnitude(mode & 1), b;
@@ -63,6 +50,17 @@ int main(int argc, char **argv)
         const double ws = sqrt(x), gs = sqrt_inrange(x);
         if (ws != gs) { if (badsqrt++ < 5) fprintf(stderr, "SQRT x=%a want=%a got=%a\n", x, ws, gs); }
     }
+    *baddiv_out = baddiv; *badsqrt_out = badsqrt;
+}
+
+int main(int argc, char **argv)
+{
+    long n = argc > 1 ? atol(argv[1]) : 10000000, baddiv, badsqrt, cdiv, csqrt;
+    if (argc > 2) { s[0] ^= (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ull; s[1] += (uint64_t)atoll(argv[2]); }
+    pass(n, &baddiv, &badsqrt);
     printf("checked=%ld div_mismatches=%ld sqrt_mismatches=%ld\n", n, baddiv, badsqrt);
-    return (baddiv || badsqrt) ? 1 : 0;
+    seed_err = 0x1p-16;
+    pass(n / 4, &cdiv, &csqrt);
+    printf("coarse_seeds=%ld div_wrong=%ld sqrt_wrong=%ld\n", n / 4, cdiv, csqrt);
+    return (baddiv || badsqrt || cdiv || csqrt) ? 1 : 0;
 }

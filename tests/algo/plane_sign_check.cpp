@@ -1,11 +1,11 @@
-/* CPU replay of two restatements in rt_device.h's plane tests (Lds::trim kernels).
+/* Two restatements in rt_device.h's plane tests (Lds::trim kernels), restated here; the division is rt_math.h's own.
  *
  * 1. plane_den_num(no_negate): for a plane whose stored normal is -e_i the straightforward form negates both den and num.
  *    Everything a query does with the pair must be the same for (den, num) and (-den, -num):
  *      closest_hit:  !(|den| < 0.001), t = div_inrange(num, den), best > t && t > 0
  *      any_hit:      !(|den| < 0.001), the signs agree, |num| < 998 |den|, |num| > 1000 |den|, t = num / den, 999 > t && t > 0
  *    t is compared bit for bit (NaNs: both NaN; zeros: both zero — div_inrange's last fma gives a zero quotient the sign of
- *    r, not of num/den, and a zero t of either sign is no hit: t > 0 fails).  div_inrange is replayed with a reciprocal
+ *    r, not of num/den, and a zero t of either sign is no hit: t > 0 fails).  div_inrange is rt_math.h's div_seeded with a reciprocal
  *    seed that is odd in its operand, as v_rcp_f64 is, and up to 2^-24 off.
  * 2. any_hit_masks: "num > 0 && den > 0 || num < 0 && den < 0" restated as "the sign bits agree, |num| > 0" under
  *    !(|den| < 0.001); the whole occlusion decision of the straightforward form (any_hit) against the restated one.
@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "../../python-ray-tracer_amd/csrc/rt_math.h"
 
 static uint64_t s[2] = {0x9E3779B97F4A7C15ull, 0xD1B54A32D192ED03ull};
 static inline uint64_t rnd(void) { uint64_t a = s[0], b = s[1]; s[0] = b; a ^= a << 23; s[1] = a ^ b ^ (a >> 17) ^ (b >> 26); return s[1] + b; }
@@ -30,14 +31,7 @@ static double rcp_seed(double b)                          /* odd in b; relative 
     const double e = ((double)((bits(m) * 0x9E3779B97F4A7C15ull) >> 40) * 0x1p-24 * 2 - 1) * 0x1p-24;
     return copysign((1.0 / m) * (1.0 + e), b);
 }
-static double div_inrange(double a, double b)
-{
-    double r = rcp_seed(b);
-    double e = fma(-b, r, 1.0); r = fma(r, e, r);
-    e = fma(-b, r, 1.0); r = fma(r, e, r);
-    const double q = a * r;
-    return fma(fma(-b, q, a), r, q);
-}
+static double div_inrange(double a, double b) { return rt::div_seeded(a, b, rcp_seed(b)); }
 
 /* closest_hit's use of one plane: returns 1 and *t if the plane is a candidate (before the comparison with `best`) */
 static int closest_use(double den, double num, double *t)

@@ -1,10 +1,12 @@
-/* CPU replay of rt_device.h's renormalize_unit(): the two-fma sqrt/reciprocal + Markstein-quotient shortcut must equal
- * sqrt-and-divide normalisation bit for bit on unit-length inputs.  Built and run by tests/test_algorithms.py. */
+/* rt_math.h's unit_norm() and renormalize_unit_fast() (rt_device.h: renormalize_unit's fast path), the text the kernel compiles:
+ * the two-fma sqrt/reciprocal + Markstein-quotient shortcut must equal sqrt-and-divide normalisation bit for bit on unit-length
+ * inputs.  Built and run by tests/test_algorithms.py. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "../../python-ray-tracer_amd/csrc/rt_math.h"
 
 static inline int64_t bits(double x) { int64_t u; memcpy(&u, &x, 8); return u; }
 static inline double from_bits(int64_t u) { double x; memcpy(&x, &u, 8); return x; }
@@ -15,17 +17,14 @@ static void normalize_ref(const double v[3], double out[3])
     out[0] = v[0] / n; out[1] = v[1] / n; out[2] = v[2] / n;
 }
 
-/* sqrt and reciprocal of a value within 2^-33 of 1, as rt_device.h evaluates them: no integer work, no select.
- * Returns 0 if nn is outside the accepted range. */
+/* sqrt and reciprocal of a value within 2^-33 of 1, as the kernel evaluates them.  Returns 0 if nn is outside the accepted range
+ * (the guard of rt_device.h: renormalize_unit). */
 static int unit_sqrt_rcp(double nn, double *nrm_out, double *y_out)
 {
     const double e = nn - 1.0;                               /* exact */
-    if (!(fabs(e) < 0x1p-33)) return 0;
-    const double e2 = fma(-fabs(e), 0x1p-30, e);             /* nudged toward -inf: decides the ties of 1 + e/2 */
-    const double nrm = fma(e2, 0.5, 1.0);
-    const double dl = nrm - 1.0;                             /* exact */
-    const double y = fma(-dl, 1.0 + 0x1p-30, 1.0);
-    *nrm_out = nrm; *y_out = y;
+    if (!(fabs(e) < rt::UNIT_WINDOW)) return 0;
+    const rt::UnitNorm u = rt::unit_norm(e);
+    *nrm_out = u.nrm; *y_out = u.y;
     return 1;
 }
 
@@ -35,12 +34,8 @@ static int renormalize_unit(const double d[3], double out[3])
     const double nn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
     double nrm, y;
     if (!unit_sqrt_rcp(nn, &nrm, &y)) return 0;
-    const double dl = nrm - 1.0;
-    for (int c = 0; c < 3; ++c) {
-        double q = fma(-d[c], dl, d[c]);
-        double r = fma(-q, nrm, d[c]);
-        out[c] = fma(r, y, q);
-    }
+    const rt::V3 q = rt::renormalize_unit_fast(rt::V3{d[0], d[1], d[2]}, nn - 1.0);
+    out[0] = q.x; out[1] = q.y; out[2] = q.z;
     if (nrm != sqrt(nn) || y != 1.0 / nrm) return -1;
     return 1;
 }

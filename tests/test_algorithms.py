@@ -1,5 +1,5 @@
-"""CPU replays of the exact-arithmetic shortcuts the HIP kernel uses (rt_device.h), checked against the
-straightforward evaluation on tens of millions of inputs.  The shortcuts are algorithms, not hardware
+"""The exact-arithmetic shortcuts the HIP kernel uses (python-ray-tracer_amd/csrc/rt_math.h, the text rt_device.h compiles), run
+on the CPU and checked against the straightforward evaluation on tens of millions of inputs.  The shortcuts are algorithms, not hardware
 features, so they can be validated here without a GPU; the GPU parity tests then confirm the device code."""
 import os
 import subprocess
@@ -12,9 +12,10 @@ from conftest import REPO
 ALGO = os.path.join(REPO, "tests", "algo")
 
 
-def _build(name, tmp_path):
+def _build(name, tmp_path, extra=()):
     exe = str(tmp_path / name)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", exe, os.path.join(ALGO, name + ".c"), "-lm"])
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-o", exe,
+                           os.path.join(ALGO, name + ".cpp")])
     return exe
 
 
@@ -33,6 +34,34 @@ def test_in_range_division_and_sqrt_are_bit_identical(tmp_path):
     without their range handling, over operand ranges wider than float32 scenes produce."""
     out = subprocess.check_output([_build("divsqrt_check", tmp_path), "20000000"], text=True)
     assert "div_mismatches=0" in out and "sqrt_mismatches=0" in out, out
+
+
+def test_two_part_hashes_are_the_documented_jitter_hash(tmp_path):
+    """rt_math.h's scatter_key / soft_key / lens_key + scatter_hash against jitter_hash on the counters include/mi355rt.h documents
+    (arithmetic form and bit pattern), over seeds, lattice points and every field's boundary values; jitter_hash itself against
+    oracle.jitter's integer arithmetic on 4000 inputs."""
+    from oracle.oracle import jitter
+    exe = _build("hash_check", tmp_path)
+    out = subprocess.check_output([exe, "identities"], text=True)
+    assert "mismatches=0" in out and int(out.split("checked=")[1].split()[0]) > 1000000, out
+    rows = [tuple(int(t) for t in line.split()) for line in subprocess.check_output([exe, "jitter", "4000"], text=True).splitlines()]
+    assert len(rows) == 4000 and len({r[:4] for r in rows}) > 3900
+    for x, y, s, seed, h in rows:
+        assert jitter(x, y, s, seed) == ((h & 0xFFFF) * 2.0 ** -16 + (2.0 ** -17 - 0.5), (h >> 16) * 2.0 ** -16 + (2.0 ** -17 - 0.5)), (x, y, s, seed, h)
+
+
+def test_arithmetic_checks_under_ubsan(tmp_path):
+    """The four checks of rt_math.h's routines (and the hash identities: shifts that fill the word) as stand-alone programs under
+    UndefinedBehaviorSanitizer, 10^5 samples each, and clip_color on NaN, infinities, huge values and every half around [0, 255]
+    (its int conversion) against clamp-then-round."""
+    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
+    for name, args, want in [("renorm_check", ["100000"], "fast_path=100000"), ("normalize_check", ["100000"], "sqrt_mismatches=0"),
+                             ("divsqrt_check", ["100000"], "div_mismatches=0"), ("plane_sign_check", ["100000"], "checked="),
+                             ("hash_check", ["identities"], "checked="), ("hash_check", ["clip"], "checked=")]:
+        exe = _build(name, tmp_path, ["-g", "-fsanitize=undefined", "-fno-sanitize-recover=all"])
+        res = subprocess.run([exe] + args, env=env, capture_output=True, text=True)
+        assert res.returncode == 0 and "runtime error" not in res.stderr, res.stdout + res.stderr
+        assert "mismatches=0" in res.stdout and want in res.stdout, res.stdout
 
 
 def test_oracle_under_asan_ubsan(tmp_path):

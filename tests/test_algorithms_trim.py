@@ -10,7 +10,8 @@ ALGO = os.path.join(REPO, "tests", "algo")
 
 def _build(name, tmp_path):
     exe = str(tmp_path / name)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", exe, os.path.join(ALGO, name + ".c"), "-lm"])
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-o", exe,
+                           os.path.join(ALGO, name + ".cpp")])
     return exe
 
 

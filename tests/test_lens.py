@@ -55,7 +55,7 @@ def test_header_ctypes_and_library_declare_the_entry_point():
     assert "rt_set_lens" in L.PROTOTYPES and L.RT_ABI_VERSION == 7
     src = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "mi355rt.hip")).read()
     assert re.search(r"^int rt_set_lens\(", src, re.M)
-    dev = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "rt_device.h")).read()
+    dev = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "rt_math.h")).read()
     assert "0x1E45D0F5u" in dev
     assert SALT not in (0x5CA77E12, 0x50F7117E, 0x9E3779B9)
 

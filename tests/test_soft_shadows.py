@@ -49,7 +49,7 @@ def test_header_ctypes_and_library_declare_the_entry_point():
     assert "rt_set_scene_area_lights" in L.PROTOTYPES and L.RT_MAX_SHADOW_SAMPLES == 16
     src = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "mi355rt.hip")).read()
     assert re.search(r"^int rt_set_scene_area_lights\(", src, re.M)
-    dev = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "rt_device.h")).read()
+    dev = open(os.path.join(REPO, "python-ray-tracer_amd", "csrc", "rt_math.h")).read()
     assert "0x50F7117Eu" in dev
 
 
