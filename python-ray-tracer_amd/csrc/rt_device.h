@@ -190,6 +190,9 @@ template <Family F, int WSLOT, bool FRESH> struct MatState {
         return (volatile const lds_f64 *)(size_t)t + COLS * m;
     }
 };
+// SLOT(X): this lane's slot X, for a function that has the MatState as `ms`, the Lds view as `lds` and the workgroup's size as WGT.
+// The address is formed at every use (at): the slots are volatile and FRESH re-derives the lane, so no pointer is kept between uses.
+#define SLOT(X) (*ms.template at<WGT, MS::X>(lds.acc, lds.wave))
 template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
     static_assert(!has_mat(Family::PLAIN), "MS::mat is has_mat(family) on both sides: the host folds p.lamb into facing_tau by the same predicate");
     static constexpr bool mat = false, refr = false, scat = false, soft = false, lens = false, tex = false, lit = false, sky = false;
@@ -823,8 +826,10 @@ __device__ __forceinline__ unsigned lane_sphere_bits(const Lds &lds, int S, int 
     return nv >= CLUSTER ? sm : (sm & ((1u << nv) - 1u));
 }
 
+// A per-lane count of the lane-owned traversal (clusters or spheres a lane opened) for the measurement build
+// (hipcc -DRT_LANE_STATS, tools/lane_stats.py); empty, and every use a no-op, in the product build, as RT_MARK is.
 #ifdef RT_LANE_STATS
-// measurement build only: counters behind the per-tile cycles (p.tile_cycles[ntiles + base ..]): calls, sum of the
+// counters behind the per-tile cycles (p.tile_cycles[ntiles + base ..]): calls, sum of the
 // per-wave maximum, sum of ceil(total / 64), sum of the totals
 __device__ __forceinline__ void lane_stats(const KParams &p, int base, unsigned v)
 {
@@ -836,6 +841,18 @@ __device__ __forceinline__ void lane_stats(const KParams &p, int base, unsigned 
         atomicAdd(c + 0, 1u); atomicAdd(c + 1, mx); atomicAdd(c + 2, (sum + 63u) >> 6); atomicAdd(c + 3, sum);
     }
 }
+struct LaneCount {
+    unsigned n;
+    __device__ __forceinline__ LaneCount(unsigned v = 0u) : n(v) {}
+    __device__ __forceinline__ void set(unsigned v) { n = v; }
+    __device__ __forceinline__ void report(const KParams &p, int base) const { lane_stats(p, base, n); }
+};
+#else
+struct LaneCount {
+    __device__ __forceinline__ LaneCount(unsigned = 0u) {}
+    __device__ __forceinline__ void set(unsigned) {}
+    __device__ __forceinline__ void report(const KParams &, int) const {}
+};
 #endif
 template <bool ANCH>
 __device__ __forceinline__ void lanes_closest(const Lds &lds, const KParams &p, int anchor, const V3 &o, const V3 &R, double a,
@@ -847,20 +864,14 @@ __device__ __forceinline__ void lanes_closest(const Lds &lds, const KParams &p, 
         const int nc = lds.NC - cb < 32 ? lds.NC - cb : 32;
         unsigned cm = lane_cluster_bits<ANCH>(lds, anchor, cb, nc, q, p.extent2);
         RT_MARK(1);
-#ifdef RT_LANE_STATS
-        lane_stats(p, 0, __builtin_popcount(cm));
-#endif
+        LaneCount(__builtin_popcount(cm)).report(p, 0);
         while (__builtin_amdgcn_ballot_w64(cm != 0u) != 0ull) {
-#ifdef RT_LANE_STATS
-            unsigned smc = 0;
-#endif
+            LaneCount smc;
             if (cm != 0u) {
                 const int kb = (cb + __builtin_ctz(cm)) * CLUSTER;
                 cm &= cm - 1u;
                 unsigned sm = lane_sphere_bits<ANCH>(lds, p.S, anchor, kb, q);
-#ifdef RT_LANE_STATS
-                smc = __builtin_popcount(sm);
-#endif
+                smc.set(__builtin_popcount(sm));
                 while (__builtin_amdgcn_ballot_w64(sm != 0u) != 0ull) {
                     if (sm != 0u) {
                         const int k = kb + __builtin_ctz(sm);
@@ -869,9 +880,7 @@ __device__ __forceinline__ void lanes_closest(const Lds &lds, const KParams &p, 
                     }
                 }
             }
-#ifdef RT_LANE_STATS
-            lane_stats(p, 4, smc);
-#endif
+            smc.report(p, 4);
         }
         RT_MARK(2);
     }
@@ -898,21 +907,15 @@ __device__ __forceinline__ bool lanes_any(const Lds &lds, const KParams &p, int 
         unsigned cm = lane_cluster_bits<ANCH>(lds, anchor, cb, nc, q, p.extent2);
         RT_MARK(7);
         if (occ) cm = 0u;
-#ifdef RT_LANE_STATS
-        lane_stats(p, 8, __builtin_popcount(cm));
-#endif
+        LaneCount(__builtin_popcount(cm)).report(p, 8);
         while (__builtin_amdgcn_ballot_w64(cm != 0u) != 0ull) {
-#ifdef RT_LANE_STATS
-            unsigned smc = 0;
-#endif
+            LaneCount smc;
             if (cm != 0u) {
                 const int kb = (cb + __builtin_ctz(cm)) * CLUSTER;
                 cm &= cm - 1u;
                 unsigned sm = lane_sphere_bits<ANCH>(lds, p.S, anchor, kb, q);
                 if (self_culled && self >= kb && self < kb + CLUSTER) sm &= ~(1u << (self - kb));
-#ifdef RT_LANE_STATS
-                smc = __builtin_popcount(sm);
-#endif
+                smc.set(__builtin_popcount(sm));
                 while (__builtin_amdgcn_ballot_w64(sm != 0u) != 0ull) {
                     if (sm != 0u) {
                         const int k = kb + __builtin_ctz(sm);
@@ -921,9 +924,7 @@ __device__ __forceinline__ bool lanes_any(const Lds &lds, const KParams &p, int 
                     }
                 }
             }
-#ifdef RT_LANE_STATS
-            lane_stats(p, 12, smc);
-#endif
+            smc.report(p, 12);
         }
         RT_MARK(8);
     }
@@ -1111,35 +1112,61 @@ template <> struct RayCount<true> {
     __device__ __forceinline__ void shadow(bool alive, bool traced) { n_issued += (alive && traced) ? 1u : 0u; n_skipped += (alive && !traced) ? 1u : 0u; }
 };
 
+// Candidate t of the hashed points in the cube [-1, 1)^3 for the hash key `key`: its components are the counters t | {0, 1, 2}
+// (q_c = (h >> 8) 2^-23 + 2^-24 - 1, and q.q, are exact).  soft_light_point and scatter_continue take the first of eight that is
+// inside the unit ball; their counter layouts and what they do with it differ.
+__device__ __forceinline__ V3 hash_unit3(unsigned key, unsigned t)
+{
+    return V3{hash_unit(key, t), hash_unit(key, t | 1u), hash_unit(key, t | 2u)};
+}
+
 // Shadow sample point Q of a light record g = {cx, cy, cz, rho} for the hash key `key` (soft_key with t = b << 15 | m << 9 |
-// i << 5 folded in): the first of eight hashed candidates q in the unit ball (as scatter_continue's), Q = c + rho*q (float64,
+// i << 5 folded in): the first of eight hashed candidates q in the unit ball (hash_unit3, as scatter_continue's), Q = c + rho*q (float64,
 // no fused multiply-add: -ffp-contract=off), or c itself if none of the eight is inside.
 __device__ __forceinline__ V3 soft_light_point(unsigned key, const double *g)
 {
 #pragma unroll 1
     for (int j = 0; j < 8; ++j) {
         const unsigned t = (unsigned)j << 2;
-        const V3 c{hash_unit(key, t), hash_unit(key, t | 1u), hash_unit(key, t | 2u)};
+        const V3 c = hash_unit3(key, t);
         if (dot3(c, c) < 1.0) { const double rho = g[3]; return V3{g[0] + rho * c.x, g[1] + rho * c.y, g[2] + rho * c.z}; }
     }
     return V3{g[0], g[1], g[2]};
 }
 
+// The mirror direction d - 2(d.N)N of common.py:113-120.  |d - 2(d.N)N| = 1 up to rounding for unit d, N: the exact unit-vector
+// path applies (renormalize_unit falls back to sqrt-and-divide by itself otherwise).
+__device__ __forceinline__ V3 mirror_dir(const V3 &d, const V3 &N)
+{
+    const double c2 = -2.0 * dot3(d, N);
+    return renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
+}
+
+// The direction of shadow sample i of light m (record g) in trace b, from the biased hit point Pt: the sample's key is the light
+// key of the lane's sample (lkey: its LKEY slot, read by the caller at every sample: no VGPR holds it across the light loop) with
+// b, m and i folded in, its point on the light soft_light_point's.  common.py:84-91.
+__device__ __forceinline__ V3 soft_light_dir(unsigned lkey, int b, int m, int i, const double *g, const V3 &Pt)
+{
+    const unsigned key = lkey ^ (((unsigned)b << 15) | ((unsigned)m << 9) | ((unsigned)i << 5));
+    const V3 Q = soft_light_point(key, g);
+    return normalize3(V3{Q.x - Pt.x, Q.y - Pt.y, Q.z - Pt.z});
+}
+
 // The scatter of a SCAT kernel's hit on a rough surface (rough > 0, trace b < depth), in place of the mirror direction R:
-// the first of eight hashed candidates q in the unit ball (q_c = (h >> 8) 2^-23 + 2^-24 - 1, and q.q, are exact), then
+// the first of eight hashed candidates q in the unit ball (hash_unit3, counters b << 5 | j << 2 | c), then
 // D = normalize(R + rough*q) (R itself if none of the eight is inside).  Returns false if D leaves on the other side of the
 // surface from R (or either is on it, or NaN): the path ends after this trace (absorption).
 template <int WGT, class MS>
 __device__ __forceinline__ bool scatter_continue(const Lds &lds, const MS &ms, const V3 &N, int b, double rough, V3 &nd)
 {
-    const unsigned key = (unsigned)*ms.template at<WGT, MS::KEY>(lds.acc, lds.wave);
+    const unsigned key = (unsigned)SLOT(KEY);
     const V3 R = nd;
     bool found = false;
     V3 q{0.0, 0.0, 0.0};
 #pragma unroll 1
     for (int j = 0; j < 8 && !found; ++j) {
         const unsigned t = ((unsigned)b << 5) | ((unsigned)j << 2);
-        const V3 c{hash_unit(key, t), hash_unit(key, t | 1u), hash_unit(key, t | 2u)};
+        const V3 c = hash_unit3(key, t);
         if (dot3(c, c) < 1.0) { q = c; found = true; }
     }
     if (found) nd = normalize3(V3{R.x + rough * q.x, R.y + rough * q.y, R.z + rough * q.z});   // linear_comb(R, q, 1.0, rough)
@@ -1160,7 +1187,7 @@ __device__ __forceinline__ bool scatter_continue(const Lds &lds, const MS &ms, c
 template <int WGT, class MS>
 __device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, const V3 &N, const V3 &Pt, V3 &o, V3 &d, int sb = -1)
 {
-    const double eta_slot = *ms.template at<WGT, MS::ETA>(lds.acc, lds.wave);
+    const double eta_slot = SLOT(ETA);
     V3 nd;
     bool from_q = false, reflect = true;
     if (eta_slot != 0.0) {
@@ -1182,17 +1209,15 @@ __device__ __forceinline__ bool refract_continue(const Lds &lds, const MS &ms, c
         }
     }
     bool keep = true;
-    if (reflect) {                                                            // common.py:113-120
-        const double c2 = -2.0 * dot3(d, N);
-        nd = renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
+    if (reflect) {
+        nd = mirror_dir(d, N);
         if constexpr (MS::scat) {                                             // (a transparent row is never rough)
-            const double rough = *ms.template at<WGT, MS::ROUGH>(lds.acc, lds.wave);
+            const double rough = SLOT(ROUGH);
             if (rough > 0.0 && sb >= 0) keep = scatter_continue<WGT>(lds, ms, N, sb, rough, nd);
         }
     }
     V3 b = Pt;
-    if (from_q) b = V3{*ms.template at<WGT, MS::QX>(lds.acc, lds.wave), *ms.template at<WGT, MS::QY>(lds.acc, lds.wave),
-                       *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave)};
+    if (from_q) b = V3{SLOT(QX), SLOT(QY), SLOT(QZ)};
     o = V3{b.x + 0.0002 * nd.x, b.y + 0.0002 * nd.y, b.z + 0.0002 * nd.z};
     d = nd;
     return keep;
@@ -1281,6 +1306,28 @@ __device__ __forceinline__ V3 sky_color(const double *block, const V3 &d)
     return g;
 }
 
+// The set-up of a hit (type, idx).  trace_bounce and guides_kernel (rt_guides.h) share the first two.
+// hit_slot: the object's slot in the tables that list spheres in slot order, then planes (material ids, texels, lighting rows).
+// plane_base: where the planes' records start in the LDS records.  MODE 1 / 2 kernels (NOREC) keep no float64 sphere records in
+// LDS (sphere_hot): the planes' and lights' records start at 0.
+// hit_normal: the outward normal N at the unbiased hit point Pt and BIAS*N, trace.py:63-71.  (guides_kernel forms N in the branch
+// that also picks its colour and id: with the normal in a call of its own its instruction stream changes.)
+__device__ __forceinline__ int hit_slot(int type, int idx, int S) { return (type == HIT_SPHERE) ? idx : S + idx; }
+template <bool NOREC> __device__ __forceinline__ int plane_base(int S) { return NOREC ? 0 : S * SPH_STRIDE; }
+template <bool NOREC>
+__device__ __forceinline__ void hit_normal(const Lds &lds, int type, int idx, int plb, const V3 &Pt, V3 &N, V3 &bN)
+{
+    if (type == HIT_SPHERE) {                                                 // :63-66
+        const SphHot g = sphere_hot<NOREC>(lds, idx);
+        N = normalize3(V3{Pt.x - g.x, Pt.y - g.y, Pt.z - g.z});               // common.py:94-101
+        bN = V3{0.0002 * N.x, 0.0002 * N.y, 0.0002 * N.z};
+    } else {                                                                  // :68-71
+        const double *g = lds.recs() + plb + idx * PL_STRIDE;
+        N = V3{g[6], g[7], g[8]};                                             // float32-renormalised, host-side
+        bN = V3{g[9], g[10], g[11]};                                          // BIAS*N as the reference rounds it
+    }
+}
+
 // trace.py:44-112.  On entry `alive` lanes carry a ray (o,d); on exit `alive` is false for lanes
 // that missed (the reference's 404 sentinels), rgb is this bounce's colour, (o,d) the next ray.
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
@@ -1315,9 +1362,9 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         V3 Pt{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};                   // :60 (1.0*o is exact)
         // PARK: the object's colour is re-read from its LDS record where it is used (volatile: at the point of
         // use) instead of being held in 6 VGPRs across the shadow queries
-        // MODE 1 / 2 kernels keep no float64 sphere records in LDS (sphere_hot): the planes' and lights' records start at 0, and a
+        // MODE 1 / 2 kernels keep no float64 sphere records in LDS (plane_base), and a
         // hit sphere's colour comes from the packed scene in global memory — through one flat pointer that serves both cases
-        const int plb = NOREC ? 0 : opaque(S) * SPH_STRIDE;
+        const int plb = plane_base<NOREC>(NOREC ? 0 : opaque(S));            // (opaque only where S is used)
         const int coff = (type == HIT_SPHERE) ? idx * SPH_STRIDE + 4 : plb + idx * PL_STRIDE + 12;
         volatile const lds_f64 *colp = (volatile const lds_f64 *)lds.recs() + coff;
         volatile const double *colf = (NOREC && type == HIT_SPHERE) ? p.scene + coff : lds.recs() + coff;
@@ -1329,7 +1376,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         // unbiased Pt.  What stays live across the shadow queries is its 32-bit index; parked kernels read the texel again at
         // each point of use (an L2 hit), as they re-read a record's colour
         unsigned texi = 0u;
-        if constexpr (MS::tex) texi = texel_of(p, (type == HIT_SPHERE) ? idx : S + idx, Pt);
+        if constexpr (MS::tex) texi = texel_of(p, hit_slot(type, idx, S), Pt);
         auto texel = [&](int c) -> double { return (double)((volatile const float *)p.lens.texels)[4 * (size_t)texi + c]; };
         V3 colr{0.0, 0.0, 0.0};
         if constexpr (!PARK && MS::tex) {                                      // register variants: the 16-byte entry, one aligned load
@@ -1344,37 +1391,32 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             else if constexpr (PARK) return colp[c];
             else return c == 0 ? colr.x : (c == 1 ? colr.y : colr.z);
         };
+        auto lambert_add = [&](double k, const V3 &e) {                     // :101, rgb += (k * e) * col, e the light's colour
+            rgb = V3{rgb.x + (k * e.x) * col(0), rgb.y + (k * e.y) * col(1), rgb.z + (k * e.z) * col(2)};
+        };
         volatile const lds_f64 *mp = nullptr;
         V3 N, bN;
-        if (type == HIT_SPHERE) {                                             // :63-66
-            const SphHot g = sphere_hot<NOREC>(lds, idx);
-            N = normalize3(V3{Pt.x - g.x, Pt.y - g.y, Pt.z - g.z});           // common.py:94-101
-            bN = V3{0.0002 * N.x, 0.0002 * N.y, 0.0002 * N.z};
-        } else {                                                              // :68-71
-            const double *g = lds.recs() + plb + idx * PL_STRIDE;
-            N = V3{g[6], g[7], g[8]};                                         // float32-renormalised, host-side
-            bN = V3{g[9], g[10], g[11]};                                      // BIAS*N as the reference rounds it
-        }
+        hit_normal<NOREC>(lds, type, idx, plb, Pt, N, bN);
         if constexpr (MS::mat) {
             // the object's entry of the LDS material table (looked up after the normal: its address is live only here);
             // Lambert coefficient and reflectivity go to the lane's slots
-            mp = ms.entry((type == HIT_SPHERE) ? idx : S + idx);
-            *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) = mp[1];
+            mp = ms.entry((type == HIT_SPHERE) ? idx : S + idx);              // (hit_slot, spelled out: through the call the two terms of the entry's address swap in the add)
+            SLOT(LAMB) = mp[1];
             if constexpr (MS::refr) {
                 // a transparent hit: its weight is trans, and Q = P - BIAS*N (the unbiased P is gone after :82-83) is kept for
                 // the continuation; a plane's BIAS*N is its stored bN, rounded as the reference rounds it
                 const double tr = mp[3];
                 const bool glass = tr > 0.0;
-                *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = glass ? tr : mp[2];
-                *ms.template at<WGT, MS::ETA>(lds.acc, lds.wave) = glass ? ((type == HIT_SPHERE) ? mp[4] : -1.0) : 0.0;
+                SLOT(REFL) = glass ? tr : mp[2];
+                SLOT(ETA) = glass ? ((type == HIT_SPHERE) ? mp[4] : -1.0) : 0.0;
                 if (glass) {
-                    *ms.template at<WGT, MS::QX>(lds.acc, lds.wave) = Pt.x - bN.x;
-                    *ms.template at<WGT, MS::QY>(lds.acc, lds.wave) = Pt.y - bN.y;
-                    *ms.template at<WGT, MS::QZ>(lds.acc, lds.wave) = Pt.z - bN.z;
+                    SLOT(QX) = Pt.x - bN.x;
+                    SLOT(QY) = Pt.y - bN.y;
+                    SLOT(QZ) = Pt.z - bN.z;
                 }
-                if constexpr (MS::scat) *ms.template at<WGT, MS::ROUGH>(lds.acc, lds.wave) = mp[5];
+                if constexpr (MS::scat) SLOT(ROUGH) = mp[5];
             } else
-            *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave) = mp[2];
+            SLOT(REFL) = mp[2];
             const double amb = mp[0];
             rgb = V3{0.0 + amb * col(0), 0.0 + amb * col(1), 0.0 + amb * col(2)};   // :77 as the reference rounds it (+0 for a negative amb)
         } else
@@ -1394,23 +1436,18 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         // read off the stored spec / n, which gives the same bytes where the quotient underflows to 0 (mi355rt.h).  Ld is not
         // held across the query either: a lane that is lit and whose hit has spec > 0 forms it again, the same way from the same operands (the soft key
         // comes from its slot again, the light's record through an opaque index: again()), and reads -d for the half vector back from dpark.
-        const unsigned lslot = (unsigned)((type == HIT_SPHERE) ? idx : S + idx);
+        const unsigned lslot = (unsigned)(hit_slot(type, idx, S));
         auto lit_row = [&]() { return (volatile const double *)(p.scene + (size_t)p.lens.lit + (size_t)LT_STRIDE * L) + 2 * (size_t)lslot; };
         auto again = [](int m) { asm volatile("" : "+v"(m)); return m; };   // the light's index, opaque: what is read through it is read again
         auto point_Ld = [&](int m) {
             const double *g = lt + m * LT_STRIDE;
             return normalize3(V3{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z});     // common.py:84-91
         };
-        auto soft_Ld = [&](int m, int i) {
-            const double *g = lt + m * LT_STRIDE;
-            const unsigned key = (unsigned)*ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) ^ (((unsigned)b << 15) | ((unsigned)m << 9) | ((unsigned)i << 5));
-            const V3 Q = soft_light_point(key, g);
-            return normalize3(V3{Q.x - Pt.x, Q.y - Pt.y, Q.z - Pt.z});
-        };
+        auto soft_Ld = [&](int m, int i) { return soft_light_dir((unsigned)SLOT(LKEY), b, m, i, lt + m * LT_STRIDE, Pt); };
         auto lit_add = [&](int m, double k, auto &&form_Ld) {                 // light m, not occluded
             const double *e = p.scene + (size_t)p.lens.lit + LT_STRIDE * m;
             const double er = e[0], eg = e[1], eb = e[2];
-            if (k > 0.0) rgb = V3{rgb.x + (k * er) * col(0), rgb.y + (k * eg) * col(1), rgb.z + (k * eb) * col(2)};
+            if (k > 0.0) lambert_add(k, V3{er, eg, eb});
             volatile const double *lr = lit_row();
             const double spec = lr[0];
             if (spec > 0.0) {                                                 // (Ld again only for a hit that can have a highlight)
@@ -1436,7 +1473,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 for (int i = 0; i < ms.nsh; ++i) {
                     const V3 Ld = soft_Ld(m, i);
                     const double cN = dot3(Ld, N);
-                    const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * cN;   // :99
+                    const double k = SLOT(LAMB) * cN;   // :99
                     RT_MARK(5);
                     if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
                         const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
@@ -1447,12 +1484,12 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 if constexpr (FACING_SKIP) {                                  // (rt_facing.h: neither k > 0 nor cN > 0 on any live lane)
                     const double *g = lt + m * LT_STRIDE;
                     const bool cert = rt_facing_certified_lamb(g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z, N.x, N.y, N.z, p.facing_tau,
-                                                               *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave));
+                                                               SLOT(LAMB));
                     if (__builtin_amdgcn_ballot_w64(!cert) == 0ull) { RT_MARK(5); continue; }
                 }
                 const V3 Ld = point_Ld(m);
                 const double cN = dot3(Ld, N);
-                const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * cN;       // :99
+                const double k = SLOT(LAMB) * cN;       // :99
                 RT_MARK(5);
                 if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
                     const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
@@ -1470,14 +1507,12 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 #pragma unroll 1
             for (int i = 0; i < ms.nsh; ++i) {
                 // (the key is re-read from its slot per sample: no VGPR holds it across the light loop)
-                const unsigned key = (unsigned)*ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) ^ (((unsigned)b << 15) | ((unsigned)m << 9) | ((unsigned)i << 5));
-                const V3 Q = soft_light_point(key, g);
-                const V3 Ld = normalize3(V3{Q.x - Pt.x, Q.y - Pt.y, Q.z - Pt.z});   // common.py:84-91
-                const double k = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave) * dot3(Ld, N);   // :99
+                const V3 Ld = soft_light_dir((unsigned)SLOT(LKEY), b, m, i, g, Pt);
+                const double k = SLOT(LAMB) * dot3(Ld, N);   // :99
                 RT_MARK(5);
                 if (k > 0.0) {
                     const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
-                    if (!occluded) rgb = V3{rgb.x + k * col(0), rgb.y + k * col(1), rgb.z + k * col(2)};
+                    if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
                 }
             }
         }
@@ -1486,7 +1521,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             const double *g = lt + m * LT_STRIDE;
             const V3 v{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z};
             double lamb;
-            if constexpr (MS::mat) lamb = *ms.template at<WGT, MS::LAMB>(lds.acc, lds.wave); else lamb = p.lamb;
+            if constexpr (MS::mat) lamb = SLOT(LAMB); else lamb = p.lamb;
             if constexpr (FACING_SKIP) {
                 // The facing certificate (rt_facing.h): where every live lane of the wave has v.N < -facing_tau (and no negative lamb:
                 // per lane with a material table, folded into facing_tau by the host otherwise), no lane's k will be positive, so
@@ -1509,7 +1544,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             if (k > 0.0) {
                 // (the shadow rays of the primary hits still travel together: wave-uniform cull unless p.lanes_primary)
                 const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
-                if (!occluded) rgb = V3{rgb.x + k * col(0), rgb.y + k * col(1), rgb.z + k * col(2)};
+                if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
             }
         }
         d = dpark.get();
@@ -1518,10 +1553,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         } else if constexpr (MS::refr) {
             refract_continue<WGT>(lds, ms, N, Pt, o, d);
         } else {
-        const double c2 = -2.0 * dot3(d, N);                                  // common.py:113-120
-        // |d - 2(d.N)N| = 1 up to rounding for unit d, N: the exact unit-vector path applies (it falls
-        // back to sqrt-and-divide by itself otherwise)
-        const V3 Rd = renormalize_unit(V3{d.x + c2 * N.x, d.y + c2 * N.y, d.z + c2 * N.z});
+        const V3 Rd = mirror_dir(d, N);
         o = V3{Pt.x + 0.0002 * Rd.x, Pt.y + 0.0002 * Rd.y, Pt.z + 0.0002 * Rd.z};   // :110
         d = Rd;
         }
@@ -1542,9 +1574,9 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 {
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
-    if constexpr (MS::mat) *ms.template at<WGT, MS::W>(lds.acc, lds.wave) = 1.0;
-    if constexpr (MS::scat) *ms.template at<WGT, MS::KEY>(lds.acc, lds.wave) = (double)key;
-    if constexpr (MS::soft) *ms.template at<WGT, MS::LKEY>(lds.acc, lds.wave) = (double)lkey;
+    if constexpr (MS::mat) SLOT(W) = 1.0;
+    if constexpr (MS::scat) SLOT(KEY) = (double)key;
+    if constexpr (MS::soft) SLOT(LKEY) = (double)lkey;
     for (int b = 0; b <= p.depth; ++b) {
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;                                   // wave-uniform exit
         if constexpr (COUNT) {                                                // lane utilisation per bounce: waves entering, lanes alive
@@ -1562,14 +1594,14 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0; SKY: W * sky(d))
             double wgt;
-            if constexpr (MS::mat) wgt = *ms.template at<WGT, MS::W>(lds.acc, lds.wave); else wgt = p.refl_pow[b - 1];
+            if constexpr (MS::mat) wgt = SLOT(W); else wgt = p.refl_pow[b - 1];
             const V3 a = acc.get();
             acc.set(V3{a.x + wgt * rgb.x, a.y + wgt * rgb.y, a.z + wgt * rgb.z});
         }
         if constexpr (MS::mat) {                                              // W_{b+1} = W_b * refl_b (W_1 = 1 * refl_0 = refl_0)
             if (alive) {
-                volatile lds_f64 *w = ms.template at<WGT, MS::W>(lds.acc, lds.wave);
-                *w = *w * *ms.template at<WGT, MS::REFL>(lds.acc, lds.wave);
+                volatile lds_f64 *w = &SLOT(W);                              // (one read-modify-write of one slot)
+                *w = *w * SLOT(REFL);
             }
         }
     }
@@ -1778,6 +1810,13 @@ __device__ __forceinline__ MatState<F, WSLOT, FRESH> mat_state(double *matl, int
     else return {};
 }
 
+// One wave per 8x8 tile, tiles consecutive in y: tile -> (tx, ty).  render_kernel and guides_kernel (rt_guides.h).
+__device__ __forceinline__ void tile_xy(const KParams &p, int tile, int &tx, int &ty)
+{
+    tx = div_by(tile, p.tiles_y, p.tiles_y_magic, p.tiles_y_shift);
+    ty = tile - tx * p.tiles_y;
+}
+
 // AA = false: aliasing off — instantiated separately so that the common case does not carry the tap loop's
 // live state (registers decide occupancy here).
 // F: the kernel's feature family (Family; PLAIN has none of these features).
@@ -1873,7 +1912,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     const int tile = WPW >= TILE_ORDER_MIN_WPW ? __builtin_amdgcn_readfirstlane(tile_v) : tile_v;
     if (tile >= p.ntiles) return;                                             // whole wave, after the barriers
     const unsigned long long t_begin = (p.tile_cycles || p.cost) ? __builtin_amdgcn_s_memtime() : 0ull;
-    const int tx = div_by(tile, p.tiles_y, p.tiles_y_magic, p.tiles_y_shift), ty = tile - tx * p.tiles_y;
+    int tx, ty;
+    tile_xy(p, tile, tx, ty);
     const int x = p.x0 + tx * TILE + (lane >> 3);
     const int y = ty * TILE + (lane & 7);
     bool inb = (x < p.x1) && (y < p.h);

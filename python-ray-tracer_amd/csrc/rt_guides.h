@@ -1,10 +1,13 @@
 // rt_guides.h — the first-hit guides (include/mi355rt.h: rt_render_guides): what the pinhole camera's RT_AA_NONE primary ray of a
 // pixel hits first, as eight float32 planes — normal, distance, albedo, object id.  One kernel beside the render kernels, which it
-// does not touch: it stages the packed scene and the float32 cull tables into LDS as render_kernel does (the same two straight
-// copies, restated here so that render_kernel's text stays as it is), forms the ray with pixel_P and primary_dir, and asks
-// closest_hit, the render kernels' own query with their culls, for the exact closest hit.  Normal, hit point and texel index are
-// formed as trace_bounce forms them for the first trace.  One wave per 8x8 tile laid out as in render_kernel, four waves per
-// workgroup, tiles in plain order: no dispatch-order feedback, no parked state, no per-thread LDS slots.
+// does not touch: it stages the packed scene and the float32 cull tables into LDS as render_kernel does, forms the ray with pixel_P
+// and primary_dir, and asks closest_hit, the render kernels' own query with their culls, for the exact closest hit.  Normal, hit
+// point and texel index are formed as trace_bounce forms them for the first trace.  Shared with the render kernels through
+// rt_device.h: tile_xy, hit_slot, plane_base (and pixel_P, primary_dir, closest_hit, sphere_hot, sphere_orig, texel_of).  Still
+// written out here as render_kernel and trace_bounce have them, because moving them into a shared function changed instruction
+// streams of the render kernels or of this one (Denoiser: Guides): the two staging copies, the Lds view, the lane's
+// pixel, the normal.  One wave per 8x8 tile laid out as in render_kernel, four waves per workgroup, tiles in plain order: no
+// dispatch-order feedback, no parked state, no per-thread LDS slots.
 // MODE is closest_hit's (rt_plan.h: plan_guides picks it as plan_launch would for the scene): 0 float64 sphere records in LDS,
 // 1 none (sphere_hot widens the float32 table), 2 the lane-owned traversal of a clustered scene.
 #pragma once
@@ -43,7 +46,8 @@ __global__ __launch_bounds__(64 * GUIDE_WPW) void guides_kernel(const KParams p,
                   sph32 + tl.gtab, nullptr, p.NC, __builtin_amdgcn_readfirstlane(wave), MODE < 2, MODE >= 2, false, nullptr};
     const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x * GUIDE_WPW + wave);
     if (tile >= p.ntiles) return;                                             // whole wave, after the barrier
-    const int tx = div_by(tile, p.tiles_y, p.tiles_y_magic, p.tiles_y_shift), ty = tile - tx * p.tiles_y;
+    int tx, ty;
+    tile_xy(p, tile, tx, ty);
     const int x = p.x0 + tx * TILE + (lane >> 3);
     const int y = ty * TILE + (lane & 7);
     const bool inb = (x < p.x1) && (y < p.h);
@@ -59,7 +63,7 @@ __global__ __launch_bounds__(64 * GUIDE_WPW) void guides_kernel(const KParams p,
     float g[GUIDE_PLANES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1.0f};
     if (type != HIT_NONE) {
         const V3 Pt{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};             // trace.py:60
-        const int plb = NOREC ? 0 : p.S * SPH_STRIDE;
+        const int plb = plane_base<NOREC>(p.S);
         V3 N;
         const double *col;                                                    // the object's own colour (float32 widened)
         double id;
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(64 * GUIDE_WPW) void guides_kernel(const KParams p,
         g[0] = (float)N.x; g[1] = (float)N.y; g[2] = (float)N.z;
         g[3] = (float)t;
         if (textured) {                                                       // the first trace's texel (an untextured object's is its colour)
-            const unsigned ti = texel_of(p, (type == HIT_SPHERE) ? idx : p.S + idx, Pt);
+            const unsigned ti = texel_of(p, hit_slot(type, idx, p.S), Pt);
             const f4 tc = reinterpret_cast<const f4 *>(p.lens.texels)[ti];
             g[4] = tc[0]; g[5] = tc[1]; g[6] = tc[2];
         } else { g[4] = (float)col[0]; g[5] = (float)col[1]; g[6] = (float)col[2]; }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 ISA and resource usage of the kernels of two source trees (CPU only, no GPU).
 
-    python tools/isa_compare.py [--base REV] [--twins]
+    python tools/isa_compare.py [--base REV] [--base-asm FILE] [--twins]
 
 Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and once for REV (default HEAD, extracted with
 `git archive` into a temporary directory), then, for every kernel of REV:
@@ -18,6 +18,8 @@ REFR twin, each SOFT kernel next to its SCAT twin, each LENS and LENS_SOFT kerne
 texture kernel (TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT) next to its SCAT, SOFT, LENS and LENS_SOFT twin, and each lighting
 kernel (LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT) next to its texture twin, and each sky kernel (SKY_SCAT, SKY_SOFT, SKY_LENS,
 SKY_LENS_SOFT) next to its lighting twin.  Exit status 1 if any kernel differs.
+--base-asm FILE takes REV's build from an earlier run instead of building it again (a build is minutes of one core): FILE is REV's
+rt_kernel.gfx950.s and FILE.log what its `make asm` wrote to stderr (the resource-usage remarks).  What is compared is the same.
 """
 import argparse
 import os
@@ -103,12 +105,16 @@ def resources(log):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", default="HEAD")
+    ap.add_argument("--base-asm", help="REV's rt_kernel.gfx950.s from an earlier build; its stderr in FILE.log")
     ap.add_argument("--twins", action="store_true")
     a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        arch = subprocess.run(["git", "-C", REPO, "archive", a.base, CSRC, "include"], capture_output=True, check=True).stdout
-        subprocess.run(["tar", "-x", "-C", tmp], input=arch, check=True)
-        base_asm, base_log = build(tmp)
+    if a.base_asm:
+        base_asm, base_log = open(a.base_asm).read(), open(a.base_asm + ".log").read()
+    else:
+        with tempfile.TemporaryDirectory() as tmp:
+            arch = subprocess.run(["git", "-C", REPO, "archive", a.base, CSRC, "include"], capture_output=True, check=True).stdout
+            subprocess.run(["tar", "-x", "-C", tmp], input=arch, check=True)
+            base_asm, base_log = build(tmp)
     new_asm, new_log = build(REPO)
     bf, nf = functions(base_asm), functions(new_asm)
     br, nr = resources(base_log), resources(new_log)
