@@ -74,7 +74,7 @@ struct rt_ctx {
                                       // rays wave-uniform: +2..3 % since the group level exists)
     rt::PlanKnobs knobs;              // what steers the choice of a launch's kernel and order shape (rt_plan.h)
     int render_chunks = 4;            // MI355RT_CHUNKS overrides (1 = one launch, one copy)
-    int log_kernels = 0;              // MI355RT_LOG_KERNELS=1: every render launch names its kernel on stderr (its shape and family number)
+    int log_kernels = 0;              // MI355RT_LOG_KERNELS=1: every render launch names its kernel on stderr (its shape and family number), every rt_render_guides call its table mode
     int remeasure = 24;               // MI355RT_REMEASURE: launches a dispatch order measured under an older camera is kept for before
                                       // the tile costs are measured again (a moving camera; any order renders the same frame)
     struct Slot {                     // rt_render_begin / rt_render_end: a frame in flight to host memory
@@ -857,6 +857,7 @@ int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_
     rt::guides_part(k, v, ctx->lay, (const double *)ctx->scene[ctx->scene_cur].p, (const double *)ctx->pixel_loc.p,
                     (const float *)ctx->texels[ctx->scene_cur].p, ctx->lanes_primary, x0, x1, d_guides, plane_stride);
     const rt::GuidesPlan plan = rt::plan_guides(ctx->lay, ctx->knobs, k.anchors);
+    if (ctx->log_kernels) std::fprintf(stderr, "mi355rt: guides_kernel<%d>\n", plan.mode);
     rc = acquire_tables(ctx, *sr, k, &k.ftab);
     if (rc != RT_OK) return rc;
     const void *fn = plan.mode == 2 ? (const void *)rt::guides_kernel<2> : (plan.mode == 1 ? (const void *)rt::guides_kernel<1> : (const void *)rt::guides_kernel<0>);

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, load_frame, raygen_closed_form
+from closest_hit_scenes import size_limit_arrays
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402
@@ -196,29 +197,7 @@ def test_scene_size_limits_sampled(renderer, oracle):
     """M = 256 rows with ids over every row, S = 1024, P = 64, L = 64 with radii, a lens: sampled pixels (render_pixels)."""
     rng = np.random.default_rng(1024)
     S, P, NL, M = 1024, 64, 64, 256
-    sp = np.zeros((7, S), np.float32)
-    sp[0] = rng.uniform(2, 14, S)
-    sp[1:3] = rng.uniform(-6, 6, (2, S))
-    sp[3] = rng.uniform(0.05, 0.35, S)
-    sp[4:7] = rng.integers(0, 256, (3, S))
-    pl = np.zeros((9, P), np.float32)
-    pl[0] = rng.uniform(0, 40, P)
-    pl[2] = -3.0 - rng.uniform(0, 5, P)
-    nrm = rng.normal(size=(3, P)) * 0.2
-    nrm[2] += 1.0
-    pl[3:6] = nrm / np.linalg.norm(nrm, axis=0)
-    pl[6:9] = rng.integers(0, 256, (3, P))
-    li = rng.uniform(-4, 10, (3, NL)).astype(np.float32)
-    li[2] = np.abs(li[2]) + 3
-    table = np.zeros((M, 6))
-    table[:, 0] = rng.uniform(-0.05, 0.1, M)
-    table[:, 1] = rng.uniform(0.1, 0.9, M)
-    table[:, 2] = rng.uniform(0, 0.8, M)
-    table[:, 4] = 1.0
-    table[3::5, 2], table[3::5, 3], table[3::5, 4] = 0.0, 0.9, 1.5
-    table[4::5, 5] = rng.uniform(0.05, 1.0, len(table[4::5]))
-    sid = (np.arange(S) * 7 % M).astype(np.int32)
-    pid = (np.arange(P) * 5 % M).astype(np.int32)
+    sp, pl, li, table, sid, pid = size_limit_arrays(rng, S, P, NL, M)      # (the generator limit_scene shares: closest_hit_scenes.py)
     assert set(sid.tolist()) == set(range(M))
     w, h = 256, 160
     sc = dict(kind="limits", w=w, h=h, spheres=sp, lights=li, planes=pl, table=table, sid=sid, pid=pid,

@@ -1,11 +1,12 @@
 """The film on the GPU (rt_film_accumulate, rt_film_resolve; the two kernels of rt_film.h).  Truth for a pass is the unchanged
 render path, render_device with a float32 output and seed s + i, fed to the numpy restatements of python-ray-tracer_amd/film.py;
 every comparison is bit for bit.  Accumulate on three scenes and five pass counts over a NaN-filled sum, in two steps, in column
-slabs in place; one case against the CPU oracle's frames; tiny frames and a 1080p frame; resolve on synthetic sums of every awkward
+slabs in place; one case against the CPU oracle's frames; tiny frames, a 1080p frame and one whose passes go one by one; resolve on synthetic sums of every awkward
 size, stride, layout, output and tone; the identity at n = 1; two streams; the error paths; the example."""
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -243,6 +244,47 @@ def test_large_frame_loops_past_the_grid_cap(rend):
         rend.free(d8)
     for k in [k for k in _TRUTH if k[0] == "headline"]:
         del _TRUTH[k]                                             # (75 MB of frames nobody else needs)
+
+
+def test_passes_one_by_one_above_the_scratch_cap(rend):
+    """Four float32 pass frames above FILM_SCRATCH_MAX = 256 MiB: rt_film_accumulate then renders and adds its passes one by one
+    (batch = 1 with passes > 1), which is what a 4K or 8K film runs.  The headline scene at depth 1, RT_AA_STOCHASTIC spp 1, on
+    2368 x 2362 = 5 593 216 pixels (from 5 592 406 on), 5 passes into a NaN-filled sum; then 2 + 3 passes, the same bits."""
+    from python_ray_tracer_amd import workloads
+    from python_ray_tracer_amd.scene import Camera
+    w, h, passes = 2368, 2362, 5
+    film_batch, scratch_max = 4, 256 << 20                        # rt_film.h: FILM_BATCH, FILM_SCRATCH_MAX
+    fplane = (w * h + 3) & ~3                                     # mi355rt.hip: pass planes padded to four floats
+    assert film_batch * fplane * 3 * 4 > scratch_max and passes > 1 and w * h == 5593216
+    assert film_batch * 5592405 * 3 * 4 <= scratch_max < film_batch * 5592406 * 3 * 4    # (four unpadded frames of 12 B per pixel)
+    t0 = time.perf_counter()
+    wl = workloads.build(workloads.HEADLINE)
+    cam = Camera(resolution=(w, h), **workloads.CAMERA)
+    rend.set_scene(wl["spheres"], wl["lights"], wl["planes"])
+    rend.set_camera(cam.position, cam.rotation)
+    rend.set_raygen(w, h, *cam.raygen())
+    params_of = lambda seed: rend.params(wl["amb"], wl["lamb"], wl["refl"], 1, 2, spp=1, seed=seed)
+    try:
+        want = F.accumulate_reference(None, _pass_frames(rend, "onebyone", params_of, 31, passes, w, h))
+        assert not np.array_equal(_TRUTH[("onebyone", 31, 0, w)], _TRUTH[("onebyone", 35, 0, w)])
+    finally:
+        for k in [k for k in _TRUTH if k[0] == "onebyone"]:
+            del _TRUTH[k]                                         # (335 MB of frames nobody else needs)
+    t1 = time.perf_counter()
+    d = _nan_sum(rend, 3 * w * h)
+    try:
+        rend.film_accumulate(params_of(31), 0, w, passes, True, d)
+        rend.sync()
+        assert same_bits(_read(rend, d, (3, w, h)), want), "5 passes one by one"
+        rend.h2d(d, np.full(3 * w * h, np.nan))
+        rend.film_accumulate(params_of(31), 0, w, 2, True, d)
+        rend.film_accumulate(params_of(33), 0, w, 3, False, d)
+        rend.sync()
+        assert same_bits(_read(rend, d, (3, w, h)), want), "2 + 3 passes"
+    finally:
+        rend.free(d)
+    assert want.any() and np.isfinite(want).all()
+    print(f"one-by-one passes: truth {t1 - t0:.2f} s, two accumulates and read-backs {time.perf_counter() - t1:.2f} s")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
