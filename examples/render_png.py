@@ -6,6 +6,7 @@
                                   [--checker [--texture IMAGE]] [--lights] [--sky] [--out output/render.png]
                                   [--passes N [--exposure E] [--white W] [--gamma2]]
                                   [--denoise [--denoise-levels N]] [--guides PREFIX]
+                                  [--orbit K --temporal [--orbit-step DEG]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -31,6 +32,11 @@ root for display).  For example --sky --dof 0.1 --passes 64 --white 400: 64 lens
 what the pinhole camera hits first), with --denoise-levels N iterations (default 4); without --passes it takes four passes.  For
 example --sky --soft --shadow-samples 1 --passes 4 --denoise --white 400.  --guides PREFIX writes the guides as PREFIX_normal.png,
 PREFIX_depth.png, PREFIX_albedo.png and PREFIX_id.png.
+
+--orbit K --passes N --temporal renders K camera steps of an orbit about the point the camera looks at (--orbit-step degrees each,
+default 2), N passes per step, and carries the film through every move (rt_film_temporal: the previous mean reprojected through
+the first-hit guides and blended with the new passes); the last frame is written, filtered when --denoise is given.  For example
+--sky --soft --shadow-samples 1 --orbit 8 --passes 4 --temporal --denoise --white 400.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -76,11 +82,20 @@ def main():
     ap.add_argument("--denoise", action="store_true", help="filter the film's mean with the edge-stopping denoiser (four passes unless --passes)")
     ap.add_argument("--denoise-levels", type=int, default=4, metavar="N", help="--denoise: filter iterations, 0..6")
     ap.add_argument("--guides", default=None, metavar="PREFIX", help="write the first-hit guides as PREFIX_normal/_depth/_albedo/_id.png")
+    ap.add_argument("--orbit", type=int, default=0, metavar="K", help="--temporal: render K camera steps of an orbit and write the last frame")
+    ap.add_argument("--orbit-step", type=float, default=2.0, metavar="DEG", help="--orbit: degrees per camera step")
+    ap.add_argument("--temporal", action="store_true", help="carry the film through the camera moves of --orbit (temporal accumulation)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    if a.denoise and a.passes <= 0:
+    if (a.denoise or a.temporal) and a.passes <= 0:
         a.passes = 4
+    if a.temporal and a.orbit < 1:
+        a.orbit = 8
+    if a.orbit > 0 and not a.temporal:
+        ap.error("--orbit renders through --temporal")
+    if a.temporal and a.dof > 0:
+        ap.error("--temporal reprojects the pinhole camera's guides: not with --dof")
     euler = [0, -12, 0] if a.sky else [0, -30, 0]                   # --sky: the horizon a third of the way down the picture
     cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=euler)
     with pkg.Renderer(0) as r:
@@ -150,7 +165,24 @@ def main():
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
         aa = 2 if a.spp > 0 else a.aa
         p = r.params(0.0, 0.6, 0.3, a.depth, aa, flags=flags, spp=a.spp)
-        if a.passes > 0:                                        # a film: the passes summed and resolved on the device
+        if a.temporal:                                          # a film carried through the camera moves of an orbit
+            from python_ray_tracer_amd.temporal import orbit
+            start = (np.asarray(cam.position, np.float64), np.asarray(cam.rotation, np.float64))
+            pivot = start[0] + 4.0 * start[1][:, 0]             # a point the camera looks at
+            tone = dict(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags)
+            with pkg.Film(r) as film:
+                r.timer_begin()
+                for k in range(a.orbit):
+                    r.set_camera(*orbit(start, pivot, a.orbit_step * k))
+                    film.next_frame()
+                    p.seed = 1 + k * a.passes
+                    film.accumulate(p, a.passes)
+                    film.temporal()
+                    if a.denoise:
+                        film.denoise(levels=a.denoise_levels, temporal=True)
+                ms = r.timer_end() / (a.orbit * a.passes)
+                image = film.resolve(denoised=a.denoise, temporal=True, **tone)[0]
+        elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
             with pkg.Film(r) as film:
                 film.accumulate(p, a.passes)
                 if a.denoise:
@@ -184,7 +216,7 @@ def main():
                 Image.fromarray(np.clip(np.rint(pic), 0, 255).astype(np.uint8).transpose(2, 1, 0)).save(f"{a.guides}_{kind}.png")
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise} temporal={a.temporal} orbit={a.orbit}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -632,6 +632,65 @@ int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
                     const void *d_guides, int64_t guide_stride, const rt_denoise *dn,
                     void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
 
+/* Temporal accumulation: the film through a camera move.  rt_film_temporal carries the previous frame's mean to where its surfaces
+ * are under the current camera, rejects what has become visible, and blends in the new passes.  RT_ABI_VERSION is unchanged:
+ * callers detect this entry point by its symbol.
+ * The call works on the full w x h frame of the context's current camera (rt_set_camera) and closed-form grid (rt_set_raygen); both
+ * travel by value, as in every launch.  d_sum is a film sum of n passes of this frame (float64, 3 planes); d_guides this frame's
+ * guides (float32, 8 planes, rt_render_guides); d_hist the previous frame's mean (float64, 3 planes laid out like a sum);
+ * d_hist_len one float32 plane of w*h: how many passes each history pixel stands for; d_hist_guides the previous frame's guides;
+ * tp->prev_origin and tp->prev_rotation the camera the history was rendered with.  d_out (float64, 3 planes) receives the new mean
+ * and d_out_len (float32, w*h) the new length plane: the next call's history, and what rt_film_denoise / rt_film_resolve take with
+ * n = 1.  The history frame is assumed to have the same grid and the same, static scene: moving objects are out of scope (a moved
+ * object's pixels pass the tests against its old position or fail them by accident).  Mirrors and glass carry their own guides, not
+ * those of what is seen in them, and highlights depend on the view: such shading lags behind the camera.
+ * Per pixel p = (x, y), e = x*h + y, in float64 without fused multiply-add, in this order; o, R are the current camera, o', R' the
+ * previous one, px, y0, dy, z0, dz the grid:
+ *   fresh:   out[k][e] = s[k][e] / (double)n   (k = 0..2);   out_len[e] = (float)n
+ *   idp = guides[7][e];     idp < 0 (a miss) or max_history == 0:  fresh
+ *   P = (px, (double)x*dy + y0, (double)y*dz + z0);  d = normalize(R P) exactly as rt_render_guides forms it;  t = (double)guides[3][e]
+ *   Pt_k = o_k + t*d_k;     u_k = Pt_k - o'_k
+ *   q_j = (R'[j]*u_0 + R'[3+j]*u_1) + R'[6+j]*u_2      (j = 0..2: R' transposed times u)
+ *   !(q_0 > 0):  fresh
+ *   r2 = (u_0*u_0 + u_1*u_1) + u_2*u_2;   sc = px / q_0;   fx = (q_1*sc - y0) / dy;   fy = (q_2*sc - z0) / dz
+ *   snap:  rx = floor(fx + 0.5);  |fx - rx| <= 2^-20:  fx = rx        (the same for fy)
+ *   !(fx > -1 && fx < w && fy > -1 && fy < h):  fresh                 (NaN lands here)
+ *   ix = floor(fx); ax = fx - ix;   iy = floor(fy); ay = fy - iy;    W = H_k = Lh = +0.0
+ *   for a = 0, 1 (outer), b = 0, 1 (inner):   q = (ix + a, iy + b);   bw = (a ? ax : 1.0 - ax) * (b ? ay : 1.0 - ay)
+ *       bw == 0, or q outside [0,w) x [0,h):  skip
+ *       hist_guides[7][q] != idp:  skip
+ *       tq = (double)hist_guides[3][q];   !(fabs(tq*tq - r2) <= depth_tol * r2):  skip
+ *       cn = ((nx_p*nx_q) + (ny_p*ny_q)) + (nz_p*nz_q)   (float32 normals widened; p from guides, q from hist_guides);  !(cn >= normal_cos): skip
+ *       lq = (double)hist_len[q];   !(lq > 0):  skip
+ *       W = W + bw;   H_k = H_k + bw * hist[k][q];   Lh = Lh + bw * lq
+ *   !(W > 0):  fresh
+ *   hm_k = H_k / W;   L = Lh / W;   L > max_history:  L = max_history
+ *   out[k][e] = (L * hm_k + s[k][e]) / (L + (double)n);      out_len[e] = (float)(L + (double)n)
+ * The snap makes a still camera read exactly one history pixel: a still camera gives the running mean and nothing is blurred.  With
+ * a large max_history the result is the cumulative mean, with a small one an exponential average.  No sqrt or pow() beyond the
+ * normalize the guides already use: the bytes do not depend on a math library.  A non-finite sum, history or guide gives
+ * unspecified values but does not fault: every tap index is range-checked before it is read.
+ * Taps cross column slabs, so a multi-rank caller reprojects the assembled frame.
+ * RT_ERR_BAD_ARG for a NULL buffer or tp; n < 1 or n > 2^24; a stride < w*h; w*h > RT_FILM_MAX_PIXELS; non-finite camera entries
+ * (either camera); depth_tol or max_history not finite or < 0; normal_cos outside [-1, 1]; reserved != 0; d_out or d_out_len equal to
+ * any input (or to each other).  RT_ERR_STATE without a camera or a grid, with an explicit rt_set_pixel_loc grid, or with a grid
+ * whose dy or dz is 0.  The outputs are then untouched.  Asynchronous on `stream`; it needs no scene. */
+typedef struct rt_temporal {
+    double  prev_origin[3];    /* the camera the history was rendered with */
+    double  prev_rotation[9];
+    double  depth_tol;         /* finite, >= 0: relative tolerance on the SQUARED distance */
+    double  normal_cos;        /* in [-1, 1] */
+    double  max_history;       /* finite, >= 0: cap on a pixel's history length, in passes; 0: no history is used */
+    int32_t reserved[2];       /* must be 0 */
+} rt_temporal;                 /* 128 bytes */
+
+int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t n,
+                     const void *d_guides, int64_t guide_stride,
+                     const void *d_hist, int64_t hist_stride, const void *d_hist_len,
+                     const void *d_hist_guides, int64_t hist_guide_stride,
+                     const rt_temporal *tp,
+                     void *d_out, int64_t out_stride, void *d_out_len, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

@@ -15,6 +15,7 @@ from . import cuda            # noqa: F401
 from .renderer import Renderer, RenderError   # noqa: F401
 from . import film            # noqa: F401
 from . import denoise         # noqa: F401
+from . import temporal        # noqa: F401
 from .film import Film        # noqa: F401
 
-__all__ = ["cuda", "denoise", "film", "Film", "Renderer", "RenderError"]
+__all__ = ["cuda", "denoise", "film", "temporal", "Film", "Renderer", "RenderError"]

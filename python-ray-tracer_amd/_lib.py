@@ -18,6 +18,7 @@ RT_MAX_TEXTURES, RT_MAX_TEXTURE_DIM, RT_MAX_TEXELS = 64, 4096, 1 << 22
 RT_SKY_DOUBLES = 24
 RT_FILM_MAX_PIXELS = 1 << 27
 RT_GUIDE_PLANES = 8
+RT_TEMPORAL_MAX_N = 1 << 24          # rt_film_temporal: the most passes one call blends in
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -55,6 +56,14 @@ class rt_denoise(C.Structure):
     1, 2, 4, ..., 1024; sigma 0 (no colour weight) or finite and > 0; demodulate 0 or 1; reserved 0."""
     _fields_ = [("levels", C.c_int32), ("normal_shin", C.c_int32), ("sigma", C.c_double), ("demodulate", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class rt_temporal(C.Structure):
+    """rt_film_temporal's settings (include/mi355rt.h; the arithmetic in numpy: temporal.temporal_reference): the camera the history
+    was rendered with; depth_tol finite and >= 0, relative, on the squared distance; normal_cos in [-1, 1]; max_history finite and
+    >= 0, in passes (0: no history is used); reserved 0.  128 bytes."""
+    _fields_ = [("prev_origin", C.c_double * 3), ("prev_rotation", C.c_double * 9), ("depth_tol", C.c_double), ("normal_cos", C.c_double),
+                ("max_history", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
@@ -100,6 +109,8 @@ PROTOTYPES = {
     "rt_render_guides": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
     "rt_film_denoise": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, C.POINTER(rt_denoise), _vp, C.c_int64,
                                   _vp, C.c_int64, _vp]),
+    "rt_film_temporal": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(rt_temporal),
+                                   _vp, C.c_int64, _vp, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -121,7 +132,7 @@ PROTOTYPES = {
 
 # Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
 # times such a build beside this one), and Renderer raises where one is called.
-LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise")
+LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal")
 
 _lib = None
 

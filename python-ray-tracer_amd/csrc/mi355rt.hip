@@ -15,6 +15,7 @@
 #include "rt_plan.h"
 #include "rt_scene.h"
 #include "rt_streams.h"
+#include "rt_temporal.h"
 
 #include <cmath>
 #include <cstdio>
@@ -924,6 +925,56 @@ int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
         RT_HIP(ctx, hipGetLastError());
         src = a.dst; src_stride = a.dst_stride;
     }
+    return RT_OK;
+}
+
+// The film through a camera move: one launch of the temporal kernel (rt_temporal.h) over the full frame of the current camera and
+// closed-form grid, which travel by value with the previous camera.
+int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t n, const void *d_guides, int64_t guide_stride,
+                     const void *d_hist, int64_t hist_stride, const void *d_hist_len, const void *d_hist_guides, int64_t hist_guide_stride,
+                     const rt_temporal *tp, void *d_out, int64_t out_stride, void *d_out_len, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_sum || !d_guides || !d_hist || !d_hist_len || !d_hist_guides || !d_out || !d_out_len)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a buffer is NULL");
+    if (!tp) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: tp is NULL");
+    if (n < 1 || n > (1 << 24)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: n outside 1..2^24");
+    if (!(std::isfinite(tp->depth_tol) && tp->depth_tol >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: depth_tol must be finite and >= 0");
+    if (!(tp->normal_cos >= -1.0 && tp->normal_cos <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: normal_cos outside [-1, 1]");
+    if (!(std::isfinite(tp->max_history) && tp->max_history >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: max_history must be finite and >= 0");
+    if (tp->reserved[0] != 0 || tp->reserved[1] != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: reserved must be 0");
+    const rt::View &v = ctx->view;
+    if (!v.have_cam) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: rt_set_camera has not been called");
+    if (!v.have_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: rt_set_raygen has not been called");
+    if (v.explicit_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: an explicit rt_set_pixel_loc grid cannot be reprojected");
+    if (v.dy == 0.0 || v.dz == 0.0) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: the grid's dy or dz is 0");
+    bool finite = true;
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(v.cam_o[i]) && std::isfinite(tp->prev_origin[i]);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v.cam_R[i]) && std::isfinite(tp->prev_rotation[i]);
+    if (!finite) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a camera entry is not finite");
+    const long long npx = (long long)v.w * v.h;
+    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: w*h above RT_FILM_MAX_PIXELS");
+    if (sum_stride < npx || guide_stride < npx || hist_stride < npx || hist_guide_stride < npx || out_stride < npx)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a plane stride is smaller than the frame");
+    const void *const ins[] = {d_sum, d_guides, d_hist, d_hist_len, d_hist_guides};
+    for (const void *in : ins)
+        if (d_out == in || d_out_len == in) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: d_out and d_out_len must be buffers of their own");
+    if (d_out == d_out_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: d_out and d_out_len must be buffers of their own");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rt::TemporalArgs a;
+    a.sum = (const double *)d_sum; a.guides = (const float *)d_guides; a.hist = (const double *)d_hist;
+    a.hist_len = (const float *)d_hist_len; a.hist_guides = (const float *)d_hist_guides;
+    a.out = (double *)d_out; a.out_len = (float *)d_out_len;
+    a.sum_stride = sum_stride; a.guide_stride = guide_stride; a.hist_stride = hist_stride; a.hist_guide_stride = hist_guide_stride;
+    a.out_stride = out_stride;
+    a.w = v.w; a.h = v.h; a.n = (double)n;
+    a.px = v.px; a.y0 = v.y0; a.dy = v.dy; a.z0 = v.z0; a.dz = v.dz;
+    std::memcpy(a.o, v.cam_o, sizeof a.o); std::memcpy(a.R, v.cam_R, sizeof a.R);
+    std::memcpy(a.po, tp->prev_origin, sizeof a.po); std::memcpy(a.pR, tp->prev_rotation, sizeof a.pR);
+    a.depth_tol = tp->depth_tol; a.normal_cos = tp->normal_cos; a.max_history = tp->max_history;
+    hipLaunchKernelGGL(rt::temporal_kernel, dim3(rt::temporal_grid(npx, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
+                       stream_of(ctx, stream), a);
+    RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 

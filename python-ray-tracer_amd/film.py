@@ -12,11 +12,23 @@ their arithmetic in numpy is in denoise.py):
         film.accumulate(params, passes=4)
         film.denoise()                                # first-hit guides, then the edge-stopping filter on the mean
         image, _ = film.resolve(white=400.0, denoised=True)
+
+Film.next_frame and Film.temporal carry the film through a camera move (rt_film_temporal; its arithmetic in numpy is in
+temporal.py):
+
+        for camera in orbit:
+            renderer.set_camera(*camera)
+            film.next_frame()                         # the latest mean becomes the history; the passes start again
+            film.accumulate(params, passes=4)
+            film.temporal()                           # history reprojected through the move, blended with the new passes
+            film.denoise(temporal=True)
+            image, _ = film.resolve(white=400.0, denoised=True, temporal=True)   # (temporal=True alone: without the filter)
 """
 import numpy as np
 
 from . import _lib as L
 from .denoise import check_denoise
+from .temporal import DEPTH_TOL, MAX_HISTORY, NORMAL_COS, check_temporal
 
 # Film.denoise's default sigma, in the units the filter sees: colour / albedo with demodulation, so about 0..1 and not 0..255.  The
 # best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 at levels 4, normal_shininess 32 with demodulation on four passes of the
@@ -113,12 +125,22 @@ class Film:
         self.d_sum = renderer.malloc(24 * self.ws * self.h)
         self.d_guides = self.d_denoised = self.d_work = None      # allocated by guides() and denoise()
         self.denoised_passes = 0                                  # the pass count the filtered mean in d_denoised belongs to (0: none)
+        # temporal accumulation: allocated by next_frame() and temporal()
+        self.d_temporal = self.d_temporal_len = None              # the temporal mean of the current passes and its length plane
+        self.d_hist = self.d_hist_len = self.d_hist_guides = None  # the previous frame's mean, lengths and guides
+        self.temporal_passes = 0                                  # the pass count the mean in d_temporal belongs to (0: none)
+        self.history_camera = None                                # (origin, rotation) the history was rendered with (None: no history)
+        self.guides_camera = None                                 # the camera d_guides was last rendered with by this film
+        self.guides_stale = False                                 # next_frame() took the guides: d_guides holds an older frame's
+        self.denoised_temporal = False                            # d_denoised is the filtered temporal mean
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
-        extra = [getattr(self, n, None) for n in ("d_guides", "d_denoised", "d_work")]
-        self.d_guides = self.d_denoised = self.d_work = None
+        names = ("d_temporal", "d_temporal_len", "d_hist", "d_hist_len", "d_hist_guides", "d_guides", "d_denoised", "d_work")
+        extra = [getattr(self, n, None) for n in names]
+        for n in names:
+            setattr(self, n, None)
         for e in extra + [d]:
             if e and not self.renderer.closed:
                 self.renderer.free(e)
@@ -157,6 +179,7 @@ class Film:
         """Forget every pass: the next accumulate starts from zero.  The guides stay (they do not depend on the passes)."""
         self.passes = 0
         self.denoised_passes = 0
+        self.temporal_passes = 0
 
     # -- the denoiser -----------------------------------------------------------------------
     def guides(self, stream=None):
@@ -168,50 +191,128 @@ class Film:
             raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
                              f"[{self.x0}, {self.x1}) of height {self.h}")
         r, n = self.renderer, self.ws * self.h
-        if not self.d_guides:
-            self.d_guides = r.malloc(4 * L.RT_GUIDE_PLANES * n)
-        r.render_guides(self.x0, self.x1, self.d_guides, n, stream)
+        self._render_guides(stream)
         r.sync(stream)
         out = np.empty((L.RT_GUIDE_PLANES, self.ws, self.h), np.float32)
         r.d2h(out, self.d_guides)
         return out
 
-    def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None):
+    def _render_guides(self, stream=None):
+        """The guides of the current scene, camera and grid into d_guides.  Asynchronous."""
+        r, n = self.renderer, self.ws * self.h
+        if not self.d_guides:
+            self.d_guides = r.malloc(4 * L.RT_GUIDE_PLANES * n)
+        r.render_guides(self.x0, self.x1, self.d_guides, n, stream)
+        self.guides_camera = getattr(r, "camera", None)
+        self.guides_stale = False
+
+    def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None, temporal=False):
         """Filter the mean of the passes so far (Renderer.film_denoise: an edge-stopping a-trous filter guided by guides(), which is
         called first if it has not been) into the film's own buffers; resolve(denoised=True) shows the result.  levels 0..6,
         normal_shininess 1, 2, 4, ..., 1024, sigma 0 (no colour weight) or > 0 in colour units, demodulate: filter colour / albedo.
         sigma is measured in what the filter sees: colour units (0..255) without demodulation, colour / albedo (about 0..1) with it.
         The default, DENOISE_SIGMA = 1/8, is the best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 recorded in DESIGN.md (Denoiser): four
         passes of the soft_default_64_d4 scene with one shadow sample against its 1024-pass mean, RMSE x0.85; the values 4 to 64
-        switch the colour weight off under demodulation and make that frame worse (x2.7 to x2.9).  Asynchronous."""
+        switch the colour weight off under demodulation and make that frame worse (x2.7 to x2.9).  temporal: filter the mean that
+        temporal() wrote (with n = 1) instead of the mean of the passes.  Asynchronous."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         levels, shin, sigma, demodulate = check_denoise(levels, normal_shininess, sigma, demodulate)
         r, n = self.renderer, self.ws * self.h
-        if not self.d_guides:
+        if not self.d_guides or self.guides_stale:
             self.guides(stream)
         if not self.d_denoised:
             self.d_denoised = r.malloc(24 * n)
         if levels >= 2 and not self.d_work:
             self.d_work = r.malloc(24 * n)
-        r.film_denoise(self.d_sum, self.ws, self.h, self.passes, self.d_guides, self.d_denoised, self.d_work, levels=levels,
+        src, n_src = self._source(False, temporal)
+        r.film_denoise(src, self.ws, self.h, n_src, self.d_guides, self.d_denoised, self.d_work, levels=levels,
                        normal_shin=shin, sigma=sigma, demodulate=demodulate, stream=stream)
         self.denoised_passes = self.passes
+        self.denoised_temporal = bool(temporal)
 
-    def _source(self, denoised):
-        """(sum or filtered mean, its n) of a resolve."""
+    def _source(self, denoised, temporal=False):
+        """(sum or mean, its n) of a resolve or a filter: the sum of the passes, the temporal mean, or the filtered mean of either."""
+        if temporal and (not self.temporal_passes or self.temporal_passes != self.passes):
+            raise ValueError("the film has no temporal mean of its current passes: call temporal() first")
         if not denoised:
-            return self.d_sum, self.passes
+            return (self.d_temporal, 1) if temporal else (self.d_sum, self.passes)
         if not self.denoised_passes or self.denoised_passes != self.passes:
             raise ValueError("the film has no filtered mean of its current passes: call denoise() first")
+        if temporal and not self.denoised_temporal:
+            raise ValueError("the filtered mean is that of the plain passes: call denoise(temporal=True) first")
         return self.d_denoised, 1
+
+    # -- temporal accumulation ---------------------------------------------------------------
+    def _full_frame(self):
+        if self.x0 != 0 or self.x1 != self.renderer.w or self.renderer.h != self.h:
+            raise ValueError(f"temporal accumulation works on the full frame: the film holds columns [{self.x0}, {self.x1}) of height "
+                             f"{self.h}, the renderer's frame is {self.renderer.w} x {self.renderer.h}")
+
+    def next_frame(self, stream=None):
+        """The camera has moved (call this after Renderer.set_camera): the film's latest mean becomes the history, with its length
+        plane and its guides, and the passes start again (clear()).  The latest mean is what temporal() wrote for the current
+        passes, or sum / passes with length passes if it has not run; the history's camera is the one its guides were rendered
+        with.  A film without a pass keeps the history it has.  Asynchronous."""
+        self._live()
+        self._full_frame()
+        r, n = self.renderer, self.ws * self.h
+        if self.passes < 1:
+            return
+        if self.temporal_passes == self.passes:                   # the temporal buffers become the history: a swap
+            self.d_hist, self.d_temporal = self.d_temporal, self.d_hist
+            self.d_hist_len, self.d_temporal_len = self.d_temporal_len, self.d_hist_len
+        else:                                                     # the plain mean: a fresh temporal call writes sum / passes and (float)passes
+            if self.guides_camera is None:
+                raise ValueError("the film has no guides of the frame that ends: call guides() or temporal() before the camera moves")
+            if not self.d_hist:
+                self.d_hist, self.d_hist_len = r.malloc(24 * n), r.malloc(4 * n)
+            o, R = self.guides_camera
+            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_hist,
+                            self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
+        self.d_hist_guides, self.d_guides = self.d_guides, self.d_hist_guides
+        self.history_camera, self.guides_camera = self.guides_camera, None
+        self.guides_stale = True
+        self.clear()
+
+    def temporal(self, max_history=MAX_HISTORY, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS, stream=None):
+        """Blend the passes so far with the history that next_frame() kept (Renderer.film_temporal), into the film's own buffers:
+        the guides of the current camera are rendered first, the history is reprojected through them and every pixel whose history
+        survives becomes (L * history + sum) / (L + passes) with L its history length, capped at max_history; every other pixel,
+        and every pixel of a film without a history, the fresh mean sum / passes.  depth_tol: relative tolerance on the squared
+        distance; normal_cos: the least cosine between the pixel's normal and a history tap's.  The defaults are the best of the
+        sweep recorded in DESIGN.md (Temporal accumulation).  resolve(temporal=True) and denoise(temporal=True) take the result.
+        Asynchronous."""
+        self._live()
+        if self.passes < 1:
+            raise ValueError("the film holds no pass yet")
+        depth_tol, normal_cos, max_history, _ = check_temporal(depth_tol, normal_cos, max_history, self.passes)
+        self._full_frame()
+        r, n = self.renderer, self.ws * self.h
+        if getattr(r, "camera", None) is None:
+            raise ValueError("the renderer has no camera yet: call set_camera first")
+        if self.guides_camera is None or any(not np.array_equal(a, b) for a, b in zip(self.guides_camera, r.camera)):
+            self._render_guides(stream)
+        if not self.d_temporal:
+            self.d_temporal, self.d_temporal_len = r.malloc(24 * n), r.malloc(4 * n)
+        if self.history_camera is None:                           # no history: every pixel fresh (the inputs are placeholders)
+            o, R = r.camera
+            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_temporal,
+                            self.d_temporal_len, depth_tol=depth_tol, normal_cos=normal_cos, max_history=0.0, stream=stream)
+        else:
+            o, R = self.history_camera
+            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_hist, self.d_hist_len, self.d_hist_guides, o, R,
+                            self.d_temporal, self.d_temporal_len, depth_tol=depth_tol, normal_cos=normal_cos,
+                            max_history=max_history, stream=stream)
+        self.temporal_passes = self.passes
 
     # -- frames -----------------------------------------------------------------------------
     def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None,
-                       denoised=False):
+                       denoised=False, temporal=False):
         """The mean of the passes so far, tone-mapped, into caller-owned device memory (raw addresses), laid out as
-        Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead.  Asynchronous."""
+        Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead; temporal: the mean that temporal()
+        wrote (with denoised: its filtered version, denoise(temporal=True)).  Asynchronous."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
@@ -220,20 +321,21 @@ class Film:
             raise ValueError("both outputs are None")
         if int(flags) & L.RT_FLAG_U8_HWC and d_f32:
             raise ValueError("RT_FLAG_U8_HWC is a uint8 layout: resolve the float32 frame in a separate call")
-        src, n = self._source(denoised)
+        src, n = self._source(denoised, temporal)
         self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
                                    flags=flags, out_stride=out_stride, stream=stream)
 
-    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False):
+    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False):
         """(uint8 or None, float32 or None) host arrays shaped like Renderer.render's: (3, ws, h), or (h, ws, 3) for the uint8
-        frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered.  Waits for the context's stream."""
+        frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered; temporal: of the mean that temporal() wrote.  Waits
+        for the context's stream."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         check_tone(self.passes, exposure, white, gamma, flags)
         if not u8 and not f32:
             raise ValueError("neither u8 nor f32 is asked for")
-        self._source(denoised)
+        self._source(denoised, temporal)
         r, n = self.renderer, self.ws * self.h
         hwc = bool(int(flags) & L.RT_FLAG_U8_HWC)
         out8 = np.empty((self.h, self.ws, 3) if hwc else (3, self.ws, self.h), np.uint8) if u8 else None
@@ -241,7 +343,7 @@ class Film:
         d8 = r.malloc(3 * n) if u8 else None
         d32 = r.malloc(12 * n) if f32 else None
         try:
-            kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised)
+            kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised, temporal=temporal)
             if hwc:                                             # (the image layout is uint8 only: two calls)
                 self.resolve_device(d8, None, flags=flags, **kw)
                 if f32:

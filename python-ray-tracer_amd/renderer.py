@@ -97,6 +97,7 @@ class Renderer:
             raise RenderError(st, self._lib.rt_last_error(None).decode())
         self.device = int(device)
         self.w = self.h = None
+        self.camera = self.raygen = None                          # (origin, rotation) and (px, y0, dy, z0, dz) as last set
         self._pinned = weakref.WeakValueDictionary()     # host_array(): data address -> _PinnedBlock (owned by the arrays)
         self.closed = False
         self.generation = {"scene": 0, "camera": 0, "grid": 0}   # bumped by every set_*: caches above this class key on it
@@ -242,6 +243,7 @@ class Renderer:
         r = np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
         dp = C.POINTER(C.c_double)
         self._check(self._lib.rt_set_camera(self._ctx, o.ctypes.data_as(dp), r.ctypes.data_as(dp)))
+        self.camera = (o.copy(), r.copy())                         # what Film.next_frame remembers as the history's camera
         self.generation["camera"] += 1
 
     def set_lens(self, aperture, focus_distance):
@@ -256,6 +258,7 @@ class Renderer:
         w, h = check_frame(w, h)
         self._check(self._lib.rt_set_raygen(self._ctx, w, h, float(px), float(y0), float(dy), float(z0), float(dz)))
         self.w, self.h = w, h
+        self.raygen = (float(px), float(y0), float(dy), float(z0), float(dz))
         self.generation["grid"] += 1
 
     def set_pixel_loc(self, pixel_loc):
@@ -265,6 +268,7 @@ class Renderer:
         check_frame(a.shape[1], a.shape[2])
         self._check(self._lib.rt_set_pixel_loc(self._ctx, a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[1], a.shape[2]))
         self.w, self.h = a.shape[1], a.shape[2]
+        self.raygen = None
         self.generation["grid"] += 1
 
     def set_grid(self, pixel_loc):
@@ -440,6 +444,26 @@ class Renderer:
         vp = lambda d: C.c_void_p(d) if d else None
         self._check(self._later_entry("rt_film_denoise")(self._ctx, vp(d_sum), sum_stride, int(ws), int(h), int(n), vp(d_guides), guide_stride,
                                                          C.byref(dn), vp(d_out), out_stride, vp(d_work), work_stride, vp(stream)))
+
+    def film_temporal(self, d_sum, n, d_guides, d_hist, d_hist_len, d_hist_guides, prev_origin, prev_rotation, d_out, d_out_len, *,
+                      depth_tol, normal_cos, max_history, sum_stride=None, guide_stride=None, hist_stride=None, hist_guide_stride=None,
+                      out_stride=None, stream=None, reserved=(0, 0)):
+        """Temporal accumulation over the full frame of the current camera and closed-form grid (rt_film_temporal): the history
+        (mean d_hist, length plane d_hist_len, guides d_hist_guides, rendered with the camera prev_origin / prev_rotation) is
+        reprojected through this frame's guides d_guides and blended with the sum of n passes at d_sum into the float64
+        (3, w, h) mean d_out and the float32 (w, h) length plane d_out_len.  The result is a mean: resolve or denoise it with
+        n = 1.  Asynchronous.  In numpy: temporal.temporal_reference."""
+        npx = int(self.w or 0) * int(self.h or 0)
+        strides = [npx if v is None else int(v) for v in (sum_stride, guide_stride, hist_stride, hist_guide_stride, out_stride)]
+        tp = L.rt_temporal()
+        tp.prev_origin[:] = [float(v) for v in np.asarray(prev_origin, dtype=np.float64).reshape(3)]
+        tp.prev_rotation[:] = [float(v) for v in np.asarray(prev_rotation, dtype=np.float64).reshape(9)]
+        tp.depth_tol, tp.normal_cos, tp.max_history = float(depth_tol), float(normal_cos), float(max_history)
+        tp.reserved[:] = [int(v) for v in reserved]
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_temporal")(self._ctx, vp(d_sum), strides[0], int(n), vp(d_guides), strides[1], vp(d_hist),
+                                                          strides[2], vp(d_hist_len), vp(d_hist_guides), strides[3], C.byref(tp),
+                                                          vp(d_out), strides[4], vp(d_out_len), vp(stream)))
 
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""

@@ -1,0 +1,386 @@
+"""Temporal accumulation on the CPU (rt_film_temporal): the header, the binding and the exported symbol; properties of the numpy
+restatement temporal_reference: a still camera is the running mean from one tap, max_history clamps, the reprojection lands where
+the geometry says, what a move uncovers starts fresh; the arithmetic of python-ray-tracer_amd/csrc/rt_temporal.h, the text the
+temporal kernel compiles, run by tests/algo/temporal_check.cpp under AddressSanitizer and UBSan and compared bit for bit with
+temporal_reference; the wrappers' ValueErrors."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+from test_denoise import _NoDevice
+from test_film import same_bits
+import temporal_cases as tc
+
+from python_ray_tracer_amd import Film, denoise as D, temporal as T
+from python_ray_tracer_amd import _lib as L
+
+ALGO = os.path.join(REPO, "tests", "algo")
+
+CONTRACT = """fresh:   out[k][e] = s[k][e] / (double)n   (k = 0..2);   out_len[e] = (float)n
+idp = guides[7][e];     idp < 0 (a miss) or max_history == 0:  fresh
+P = (px, (double)x*dy + y0, (double)y*dz + z0);  d = normalize(R P) exactly as rt_render_guides forms it;  t = (double)guides[3][e]
+Pt_k = o_k + t*d_k;     u_k = Pt_k - o'_k
+q_j = (R'[j]*u_0 + R'[3+j]*u_1) + R'[6+j]*u_2      (j = 0..2: R' transposed times u)
+!(q_0 > 0):  fresh
+r2 = (u_0*u_0 + u_1*u_1) + u_2*u_2;   sc = px / q_0;   fx = (q_1*sc - y0) / dy;   fy = (q_2*sc - z0) / dz
+snap:  rx = floor(fx + 0.5);  |fx - rx| <= 2^-20:  fx = rx        (the same for fy)
+!(fx > -1 && fx < w && fy > -1 && fy < h):  fresh                 (NaN lands here)
+ix = floor(fx); ax = fx - ix;   iy = floor(fy); ay = fy - iy;    W = H_k = Lh = +0.0
+for a = 0, 1 (outer), b = 0, 1 (inner):   q = (ix + a, iy + b);   bw = (a ? ax : 1.0 - ax) * (b ? ay : 1.0 - ay)
+bw == 0, or q outside [0,w) x [0,h):  skip
+hist_guides[7][q] != idp:  skip
+tq = (double)hist_guides[3][q];   !(fabs(tq*tq - r2) <= depth_tol * r2):  skip
+cn = ((nx_p*nx_q) + (ny_p*ny_q)) + (nz_p*nz_q)   (float32 normals widened; p from guides, q from hist_guides);  !(cn >= normal_cos): skip
+lq = (double)hist_len[q];   !(lq > 0):  skip
+W = W + bw;   H_k = H_k + bw * hist[k][q];   Lh = Lh + bw * lq
+!(W > 0):  fresh
+hm_k = H_k / W;   L = Lh / W;   L > max_history:  L = max_history
+out[k][e] = (L * hm_k + s[k][e]) / (L + (double)n);      out_len[e] = (float)(L + (double)n)""".split("\n")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Header, binding, exported symbol
+
+def test_header_binding_and_exported_symbol(tmp_path):
+    hdr = open(os.path.join(REPO, "include", "mi355rt.h")).read()
+    assert "int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t n," in hdr
+    assert "} rt_temporal;" in hdr and "#define RT_ABI_VERSION 7" in hdr and L.RT_ABI_VERSION == 7
+    assert "oving objects are out of scope" in hdr
+    tm = L.PROTOTYPES["rt_film_temporal"]
+    assert tm[0] is C.c_int and len(tm[1]) == 16 and all(tm[1][i] is C.c_int64 for i in (2, 3, 5, 7, 10, 13))
+    assert "rt_film_temporal" in L.LATER_ENTRIES
+    assert C.sizeof(L.rt_temporal) == 128
+    offsets = {"prev_origin": 0, "prev_rotation": 24, "depth_tol": 96, "normal_cos": 104, "max_history": 112, "reserved": 120}
+    assert {n: getattr(L.rt_temporal, n).offset for n in offsets} == offsets
+    src = tmp_path / "size.c"
+    src.write_text('#include "mi355rt.h"\n#include <stddef.h>\n_Static_assert(sizeof(rt_temporal) == 128, "rt_temporal is 128 bytes");\n' +
+                   "".join(f'_Static_assert(offsetof(rt_temporal, {n}) == {o}, "{n}");\n' for n, o in offsets.items()) +
+                   'int main(void) { return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)])
+    lib = L.load()                                               # the cross-compiled library
+    assert lib.rt_abi_version() == 7 and hasattr(lib, "rt_film_temporal")
+    # header and numpy restatement state the same arithmetic, line for line
+    doc = T.temporal_reference.__doc__
+    for line in CONTRACT:
+        assert line in hdr, line
+        assert line in doc, line
+    for name in ("README.md", "DESIGN.md", "INTEGRATION.md"):
+        assert "rt_film_temporal" in open(os.path.join(REPO, name)).read(), name
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# temporal_reference: a still camera, the cap
+
+STILL = (1e-9, 0.999, 1000.0)         # (depth_tol, normal_cos, max_history): a still camera passes the tightest tests
+
+
+@pytest.mark.parametrize("name", ["odd_37x29", "planes_only_32", "spheres_only_32", "inside_sphere_32"])
+def test_still_camera_is_the_running_mean_from_one_tap(name):
+    f = tc.frame(name, "still")
+    w, h, n = f["w"], f["h"], 4
+    s, hist, hl = tc.random_inputs(w, h, n, 11)
+    hl = np.maximum(hl, 1.0).astype(np.float32)
+    out, out_len = tc.reference(f, s, n, hist, hl, STILL)
+    hm, Lr, valid, info = tc.taps(f, hist, hl, STILL)
+    surface = f["guides"][7] >= 0
+    assert np.array_equal(valid, surface) and surface.any()
+    assert (info["used"].sum(axis=0)[surface] == 1).all() and (info["used"][0] == surface).all()      # tap (0, 0), weight 1
+    Ld = hl.astype(np.float64)
+    want = np.where(surface, (Ld * hist + s) / (Ld + np.float64(n)), s / np.float64(n))
+    assert same_bits(out, want)
+    assert same_bits(out_len, np.where(surface, Ld + n, n).astype(np.float32))
+    assert (name == "spheres_only_32") == (not surface.all())
+
+
+def test_max_history_clamps_and_zero_is_fresh():
+    f = tc.frame("odd_37x29", "still")
+    w, h, n = f["w"], f["h"], 3
+    s, hist, hl = tc.random_inputs(w, h, n, 12)
+    hl = (hl + 1.0).astype(np.float32)                            # 1..41
+    out, out_len = tc.reference(f, s, n, hist, hl, (1e-9, 0.999, 8.0))
+    Lc = np.minimum(hl.astype(np.float64), 8.0)
+    assert same_bits(out, (Lc * hist + s) / (Lc + 3.0)) and same_bits(out_len, (Lc + 3.0).astype(np.float32))
+    assert (hl > 8).any() and (hl < 8).any() and out_len.max() == 11.0
+    out0, len0 = tc.reference(f, s, n, hist, hl, (1e-9, 0.999, 0.0))
+    assert same_bits(out0, s / np.float64(3)) and (len0 == 3.0).all()
+    f = tc.frame("odd_37x29", "moved")
+    out0, len0 = tc.reference(f, s, n, hist, hl, (0.25, 0.5, 0.0))
+    assert same_bits(out0, s / np.float64(3)) and (len0 == 3.0).all()
+    hm, Lr, valid = T.temporal_taps_reference(f["guides"], hist, hl, f["hist_guides"], f["cam"], f["prev_cam"], f["raygen"], w, h, 0.25, 0.5, 0.0)
+    assert not valid.any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Geometry: the history's channels are the previous frame's world hit points
+
+def _world_points(cam, guides, w, h, rg):
+    o, d = D.primary_rays(cam[0], cam[1], w, h, rg)
+    return o[:, None, None] + guides[3].astype(np.float64) * d.T.reshape(3, w, h)
+
+
+@pytest.mark.parametrize("name", ["odd_37x29", "planes_only_32", "inside_sphere_32"])
+def test_reprojection_lands_on_the_same_world_point(name):
+    """The history holds the world points the previous camera saw, so hm is a convex combination of the contributing taps' world
+    points.  Where all four taps of the cell contribute, the current hit point lies between them (on a plane exactly, on a sphere
+    to the second order of a pixel), and hm is no further from it than the largest distance between two of those points.  Where
+    fewer contribute (an edge of an object or of the frame took the others) the current point lies outside their hull (with one tap
+    the largest distance is 0), and what convexity still gives is that hm is no further from it than the furthest contributing
+    tap is; that tap in turn shows the same object within one pixel of the projection.  No tuned tolerance in either."""
+    f = tc.frame(name, "moved")
+    w, h, rg = f["w"], f["h"], f["raygen"]
+    hist = _world_points(f["prev_cam"], f["hist_guides"], w, h, rg)
+    hl = np.ones((w, h), np.float32)
+    hm, Lr, valid, info = tc.taps(f, hist, hl)
+    Pt = _world_points(f["cam"], f["guides"], w, h, rg)
+    assert np.allclose(Pt, info["Pt"], rtol=0, atol=1e-12)
+    used = info["used"]
+    tapP = np.stack([hist[:, info["qx"][i], info["qy"][i]] for i in range(4)])          # (4, 3, w, h)
+    dist = np.sqrt(((hm - Pt) ** 2).sum(axis=0))
+    span = np.zeros((w, h))
+    for i in range(4):
+        for j in range(i + 1, 4):
+            dij = np.sqrt(((tapP[i] - tapP[j]) ** 2).sum(axis=0))
+            span = np.maximum(span, np.where(used[i] & used[j], dij, 0.0))
+    reach = np.zeros((w, h))
+    for i in range(4):
+        reach = np.maximum(reach, np.where(used[i], np.sqrt(((tapP[i] - Pt) ** 2).sum(axis=0)), 0.0))
+    full = valid & used.all(axis=0)
+    part = valid & ~used.all(axis=0)
+    print(f"{name}: {int(valid.sum())} of {w * h} pixels valid, {int(full.sum())} with four taps, {int(part.sum())} with fewer; "
+          f"largest distance / span over four-tap pixels {float((dist[full] / span[full]).max()):.3f}")
+    assert full.sum() > w * h // 2 and part.any()
+    assert (dist[full] <= span[full]).all()
+    assert (dist[part] <= reach[part] * (1 + 1e-12)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Disocclusion
+
+def test_what_a_sideways_move_uncovers_is_fresh():
+    """A sphere in front of a wall, the previous camera a step to the side: wall pixels whose projection lands on the sphere (another
+    id at every tap) or off the frame have no history."""
+    w, h = 48, 32
+    spheres = np.array([[4.0], [0.0], [0.0], [1.0], [200.0], [50.0], [50.0]], np.float32)
+    planes = np.array([[8.0], [0.0], [0.0], [-1.0], [0.0], [0.0], [90.0], [90.0], [90.0]], np.float32)
+    rg = (1.0, -0.75, 1.5 / (w - 1), 0.5, -1.0 / (h - 1))
+    cam, prev_cam = (np.zeros(3), np.eye(3)), (np.array([0.0, -0.9, 0.0]), np.eye(3))
+    gd = D.guides_reference(spheres, planes, cam[0], cam[1], w, h, raygen=rg)
+    hg = D.guides_reference(spheres, planes, prev_cam[0], prev_cam[1], w, h, raygen=rg)
+    s, hist, hl = tc.random_inputs(w, h, 2, 13)
+    hl = np.maximum(hl, 1.0).astype(np.float32)
+    out, out_len = T.temporal_reference(s, 2, gd, hist, hl, hg, cam, prev_cam, rg, w, h, 0.25, 0.5, 16.0)
+    # the projection, by the plain formula (the move is a translation: q = Pt - o')
+    Pt = _world_points(cam, gd, w, h, rg)
+    q = Pt - prev_cam[0][:, None, None]
+    fx, fy = (q[1] / q[0] * rg[0] - rg[1]) / rg[2], (q[2] / q[0] * rg[0] - rg[3]) / rg[4]
+    off = (fx < -1.001) | (fx > w + 0.001) | (fy < -1.001) | (fy > h + 0.001)
+    ix, iy = np.floor(fx).astype(int), np.floor(fy).astype(int)
+    inside = (ix >= 0) & (ix + 1 < w) & (iy >= 0) & (iy + 1 < h)
+    cx, cy = np.clip(ix, 0, w - 2), np.clip(iy, 0, h - 2)
+    other = inside & np.all([hg[7][cx + a, cy + b] != gd[7] for a in (0, 1) for b in (0, 1)], axis=0)
+    wall = gd[7] == 1.0
+    fresh = out_len == 2.0
+    print(f"disocclusion: {int((wall & other).sum())} wall pixels project onto the sphere, {int((wall & off).sum())} off the frame, "
+          f"{int(fresh.sum())} of {w * h} fresh")
+    assert (wall & other).sum() >= 1 and (wall & off).sum() >= 1
+    assert fresh[other].all() and fresh[off].all()
+    assert same_bits(out[:, other | off], (s / np.float64(2))[:, other | off])
+    assert (~fresh).sum() > w * h // 2                              # (and most of the frame keeps its history)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# rt_temporal.h's arithmetic under the sanitizers against temporal_reference
+
+def temporal_cases():
+    """[(frame, sum, n, hist, hist_len, settings, pad, sprinkle)]: 37 x 29 and 40 x 24 frames under a moved, a still and a
+    backward-facing previous camera; then the same with NaN and Inf sprinkled into sums, history, lengths and both guides."""
+    cases = []
+    for k, (name, prev, settings, n, pad) in enumerate((("odd_37x29", "moved", tc.SETTINGS, 4, 3), ("odd_37x29", "still", STILL, 1, 0),
+                                                        ("odd_37x29", "backward", tc.SETTINGS, 4, 1), ("nonsquare_40x24", "moved", (0.05, 0.9, 4.0), 7, 5),
+                                                        ("nonsquare_40x24", "still", (0.0, 1.0, 1e6), 2, 0), ("nonsquare_40x24", "backward", tc.SETTINGS, 1, 2),
+                                                        ("odd_37x29", "moved", (0.25, -1.0, 0.0), 3, 0), ("nonsquare_40x24", "moved", (1e3, -1.0, 2.5), 1 << 24, 1))):
+        f = tc.frame(name, prev)
+        s, hist, hl = tc.random_inputs(f["w"], f["h"], min(n, 100), 100 + k)
+        cases.append((f, s, n, hist, hl, settings, pad, False))
+    rng = np.random.default_rng(77)
+    for k, (name, prev) in enumerate((("odd_37x29", "moved"), ("nonsquare_40x24", "moved"), ("odd_37x29", "still"))):
+        f = dict(tc.frame(name, prev))
+        s, hist, hl = tc.random_inputs(f["w"], f["h"], 4, 200 + k)
+        gd, hg = np.array(f["guides"]), np.array(f["hist_guides"])
+        for a in (s, hist, hl, gd, hg):
+            flat = a.reshape(-1)
+            at = rng.choice(flat.size, flat.size // 12, replace=False)
+            flat[at] = rng.choice([np.nan, np.inf, -np.inf, 1e300 if a.dtype == np.float64 else 3e38, -1.0], at.size)
+        f["guides"], f["hist_guides"] = gd, hg
+        cases.append((f, s, 4, hist, hl, tc.SETTINGS, 2, True))
+    return cases
+
+
+def test_temporal_arithmetic_under_sanitizers_matches_numpy(tmp_path):
+    exe, table, got = str(tmp_path / "temporal_check"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "temporal_check.cpp")])
+    cases = temporal_cases()
+
+    def padded(a, planes, pad, dtype, fill):
+        p = np.full((planes, a.size // planes + pad), fill, dtype)
+        p[:, :a.size // planes] = a.reshape(planes, -1)
+        return p.astype("<f8" if dtype == np.float64 else "<f4").tobytes()
+
+    with open(table, "wb") as fh:
+        fh.write(np.array([len(cases)], "<i8").tobytes())
+        for f, s, n, hist, hl, (dtol, ncos, mh), pad, _ in cases:
+            fh.write(np.array([f["w"], f["h"], n, pad], "<i8").tobytes())
+            fh.write(np.concatenate([[dtol, ncos, mh], f["raygen"], f["cam"][0].reshape(3), f["cam"][1].reshape(9),
+                                     f["prev_cam"][0].reshape(3), f["prev_cam"][1].reshape(9)]).astype("<f8").tobytes())
+            fh.write(padded(s, 3, pad, np.float64, 1e300) + padded(f["guides"], 8, pad, np.float32, np.nan) + padded(hist, 3, pad, np.float64, 1e300) +
+                     padded(hl, 1, pad, np.float32, np.nan) + padded(f["hist_guides"], 8, pad, np.float32, np.nan))
+    res = subprocess.run([exe, table, got], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == f"cases={len(cases)} ok", res.stdout
+    raw = open(got, "rb").read()
+    at = 0
+    for i, (f, s, n, hist, hl, settings, pad, sprinkled) in enumerate(cases):
+        want, want_len = tc.reference(f, s, n, hist, hl, settings)
+        npx = f["w"] * f["h"]
+        out = np.frombuffer(raw, "<f8", 3 * npx, at).reshape(want.shape)
+        out_len = np.frombuffer(raw, "<f4", npx, at + 24 * npx).reshape(want_len.shape)
+        at += 28 * npx
+        fresh = int((want_len == np.float32(n)).sum())
+        if sprinkled:                                             # no fault; every finite pixel still equal, and most are finite
+            fin = np.isfinite(want).all(axis=0)
+            assert fin.sum() > npx // 2, (i, int(fin.sum()))
+            assert same_bits(out[:, fin], want[:, fin]) and same_bits(out_len[fin], want_len[fin]), i
+            continue
+        bad = np.argwhere(out.view(np.uint64) != want.view(np.uint64))
+        assert bad.size == 0, (i, settings, len(bad), bad[:4], out[tuple(bad[0])], want[tuple(bad[0])])
+        assert same_bits(out_len, want_len), i
+        assert np.isfinite(want).all()
+        prev_is = ("moved", "still", "backward")[i % 3] if i < 6 else "moved"
+        if prev_is == "backward" or settings[2] == 0.0:
+            assert fresh == npx and same_bits(want, s / np.float64(n)), i
+        elif settings[0] > 0.0:                                   # (depth_tol 0 with normal_cos 1 asks for equal bits: few pixels pass)
+            assert npx // 4 < npx - fresh, (i, fresh)                 # the history reaches a good part of the frame
+            if prev_is == "moved":
+                assert fresh > 0, i
+    assert at == len(raw) and len(cases) >= 11
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The wrappers' argument checks, before the library sees anything
+
+def test_check_temporal_and_reference_value_errors():
+    assert T.check_temporal(0.1, 0.9, 32, 4) == (0.1, 0.9, 32.0, 4) and T.check_temporal(0, -1, 0) == (0.0, -1.0, 0.0, 1)
+    nan, inf = float("nan"), float("inf")
+    for bad, match in (((-0.1, 0.9, 8), "depth_tol"), ((nan, 0.9, 8), "depth_tol"), ((inf, 0.9, 8), "depth_tol"), ((0.1, 1.5, 8), "normal_cos"),
+                       ((0.1, -1.5, 8), "normal_cos"), ((0.1, nan, 8), "normal_cos"), ((0.1, 0.9, -1), "max_history"), ((0.1, 0.9, inf), "max_history"),
+                       ((0.1, 0.9, nan), "max_history"), ((0.1, 0.9, 8, 0), "n must"), ((0.1, 0.9, 8, (1 << 24) + 1), "n must"), ((0.1, 0.9, 8, 1.5), "n must")):
+        with pytest.raises(ValueError, match=match):
+            T.check_temporal(*bad)
+    w, h = 4, 3
+    s, g, hl = np.zeros((3, w, h)), np.zeros((8, w, h), np.float32), np.ones((w, h), np.float32)
+    cam, rg = (np.zeros(3), np.eye(3)), (1.0, -0.5, 0.3, 0.5, -0.4)
+    ok = dict(total=s, n=1, guides=g, hist=s, hist_len=hl, hist_guides=g, cam=cam, prev_cam=cam, raygen=rg, w=w, h=h, depth_tol=0.1,
+              normal_cos=0.9, max_history=8.0)
+    out, out_len = T.temporal_reference(**ok)
+    assert out.shape == (3, w, h) and out_len.dtype == np.float32 and out_len.shape == (w, h)
+    for change in (dict(total=s[:2]), dict(n=0), dict(guides=g.astype(np.float64)), dict(guides=g[:, :3]), dict(hist=s[:, :3]),
+                   dict(hist_len=hl.astype(np.float64)), dict(hist_len=hl[:3]), dict(hist_guides=g[:7]), dict(cam=(np.zeros(2), np.eye(3))),
+                   dict(prev_cam=(np.array([0.0, nan, 0.0]), np.eye(3))), dict(cam=(np.zeros(3), np.full((3, 3), inf))),
+                   dict(raygen=(1.0, -0.5, 0.0, 0.5, -0.4)), dict(raygen=(1.0, -0.5, 0.3, 0.5, 0.0)), dict(depth_tol=-1.0), dict(max_history=nan)):
+        with pytest.raises(ValueError):
+            T.temporal_reference(**{**ok, **change})
+
+
+class _NoDeviceTemporal(_NoDevice):
+    """_NoDevice with a camera and the temporal call."""
+
+    def __init__(self, w=8, h=4):
+        super().__init__(w, h)
+        self.camera = (np.zeros(3), np.eye(3).reshape(9))
+
+    def film_temporal(self, *a, **kw):
+        self.calls.append(("temporal",) + a + (kw,))
+
+
+def test_film_temporal_value_errors_and_buffers():
+    r = _NoDeviceTemporal()
+    with Film(r, 2, 6) as slab:                                   # a column slab cannot be reprojected
+        slab.accumulate(L.rt_params(), 1)
+        with pytest.raises(ValueError, match="full frame"):
+            slab.temporal()
+        with pytest.raises(ValueError, match="full frame"):
+            slab.next_frame()
+    r = _NoDeviceTemporal()
+    with Film(r) as film:
+        with pytest.raises(ValueError, match="no pass"):
+            film.temporal()
+        film.next_frame()                                         # no pass: nothing to keep, nothing called
+        assert [c[0] for c in r.calls] == ["malloc"] and film.history_camera is None
+        film.accumulate(L.rt_params(), 4)
+        with pytest.raises(ValueError, match="temporal\\(\\) first"):
+            film.resolve(temporal=True)
+        n = len(r.calls)
+        for kw, match in ((dict(depth_tol=-1.0), "depth_tol"), (dict(normal_cos=2.0), "normal_cos"), (dict(max_history=float("inf")), "max_history")):
+            with pytest.raises(ValueError, match=match):
+                film.temporal(**kw)
+        assert len(r.calls) == n                                  # nothing reached the library
+        film.temporal()                                           # no history: guides, then a call whose max_history is 0
+        assert [c[0] for c in r.calls[n:]] == ["malloc", "guides", "malloc", "malloc", "temporal"]
+        call = r.calls[-1]
+        assert call[1:4] == (film.d_sum, 4, film.d_guides) and call[9:11] == (film.d_temporal, film.d_temporal_len)
+        assert call[-1]["max_history"] == 0.0
+        film.resolve(temporal=True)
+        assert [c for c in r.calls if c[0] == "resolve"][-1][1:5] == (film.d_temporal, 8, 4, 1)       # the mean resolves with n = 1
+        with pytest.raises(ValueError, match="denoise"):
+            film.resolve(temporal=True, denoised=True)
+        film.denoise(temporal=True, levels=1)
+        den = [c for c in r.calls if c[0] == "denoise"][-1]
+        assert den[1:6] == (film.d_temporal, 8, 4, 1, film.d_guides)
+        film.resolve(temporal=True, denoised=True)
+        assert [c for c in r.calls if c[0] == "resolve"][-1][1:5] == (film.d_denoised, 8, 4, 1)
+        film.denoise(levels=1)                                    # the plain filter again: the temporal one is gone
+        with pytest.raises(ValueError, match="temporal=True"):
+            film.resolve(temporal=True, denoised=True)
+        # the camera moves
+        first_mean, first_len, first_guides = film.d_temporal, film.d_temporal_len, film.d_guides
+        cam0 = r.camera
+        r.camera = (np.array([0.1, 0.0, 0.0]), np.eye(3).reshape(9))
+        n = len(r.calls)
+        film.next_frame()
+        assert len(r.calls) == n                                  # a swap: the temporal mean is the history, no call
+        assert (film.d_hist, film.d_hist_len, film.d_hist_guides) == (first_mean, first_len, first_guides)
+        assert film.passes == 0 and film.temporal_passes == 0 and film.history_camera is cam0
+        film.accumulate(L.rt_params(), 2)
+        film.temporal(max_history=8, depth_tol=0.5, normal_cos=0.25)
+        call = r.calls[-1]
+        assert [c[0] for c in r.calls[n + 1:]] == ["malloc", "guides", "malloc", "malloc", "temporal"]
+        assert call[1:7] == (film.d_sum, 2, film.d_guides, first_mean, first_len, first_guides) and call[7] is cam0[0] and call[8] is cam0[1]
+        assert call[9:11] == (film.d_temporal, film.d_temporal_len) and film.d_temporal != first_mean and film.d_guides != first_guides
+        assert call[-1] == dict(depth_tol=0.5, normal_cos=0.25, max_history=8.0, stream=None)
+        film.accumulate(L.rt_params(), 2)                         # more passes of the same camera: the guides stay
+        with pytest.raises(ValueError, match="temporal\\(\\) first"):
+            film.resolve_device(d_u8=1, temporal=True)
+        film.temporal()
+        assert [c[0] for c in r.calls[-2:]] == ["accumulate", "temporal"] and r.calls[-1][2] == 4
+        # a frame that ends without temporal(): its plain mean becomes the history through a call that uses no history
+        r.camera = (np.array([0.2, 0.0, 0.0]), np.eye(3).reshape(9))
+        film.next_frame()
+        film.accumulate(L.rt_params(), 3)
+        film.guides()
+        r.camera = (np.array([0.3, 0.0, 0.0]), np.eye(3).reshape(9))
+        n = len(r.calls)
+        film.next_frame()
+        assert [c[0] for c in r.calls[n:]] == ["temporal"] and r.calls[-1][-1]["max_history"] == 0.0
+        assert r.calls[-1][1:3] == (film.d_sum, 3) and r.calls[-1][9:11] == (film.d_hist, film.d_hist_len)
+        film.accumulate(L.rt_params(), 1)
+        r.camera = (np.array([0.4, 0.0, 0.0]), np.eye(3).reshape(9))
+        with pytest.raises(ValueError, match="no guides"):
+            film.next_frame()
+        held = {film.d_temporal, film.d_temporal_len, film.d_hist, film.d_hist_len, film.d_hist_guides, film.d_guides, film.d_denoised, film.d_sum}
+        assert None not in held and len(held) == 8
+    assert held <= {c[1] for c in r.calls if c[0] == "free"}      # (resolve() frees its own staging buffers too)
