@@ -6,6 +6,7 @@
                                   [--checker [--texture IMAGE]] [--lights] [--sky] [--out output/render.png]
                                   [--passes N [--exposure E] [--white W] [--gamma2]]
                                   [--denoise [--denoise-levels N]] [--guides PREFIX]
+                                  [--denoise-variance [--kappa K]]
                                   [--orbit K --temporal [--orbit-step DEG]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
@@ -32,6 +33,11 @@ root for display).  For example --sky --dof 0.1 --passes 64 --white 400: 64 lens
 what the pinhole camera hits first), with --denoise-levels N iterations (default 4); without --passes it takes four passes.  For
 example --sky --soft --shadow-samples 1 --passes 4 --denoise --white 400.  --guides PREFIX writes the guides as PREFIX_normal.png,
 PREFIX_depth.png, PREFIX_albedo.png and PREFIX_id.png.
+
+--denoise-variance filters with the variance-guided denoiser instead (rt_film_accumulate_moments, rt_film_denoise_variance: the film
+keeps a sum of squares and every pixel's colour tolerance is --kappa standard deviations of its mean, default the library's), with
+--denoise-levels N iterations; without --passes it takes four passes.  For example --sky --soft --shadow-samples 1 --passes 8
+--denoise-variance --white 400.
 
 --orbit K --passes N --temporal renders K camera steps of an orbit about the point the camera looks at (--orbit-step degrees each,
 default 2), N passes per step, and carries the film through every move (rt_film_temporal: the previous mean reprojected through
@@ -81,6 +87,8 @@ def main():
     ap.add_argument("--gamma2", action="store_true", help="--passes: square-root display gamma")
     ap.add_argument("--denoise", action="store_true", help="filter the film's mean with the edge-stopping denoiser (four passes unless --passes)")
     ap.add_argument("--denoise-levels", type=int, default=4, metavar="N", help="--denoise: filter iterations, 0..6")
+    ap.add_argument("--denoise-variance", action="store_true", help="filter the film's mean with the variance-guided denoiser (four passes unless --passes)")
+    ap.add_argument("--kappa", type=float, default=None, metavar="K", help="--denoise-variance: colour tolerance in standard deviations of the mean")
     ap.add_argument("--guides", default=None, metavar="PREFIX", help="write the first-hit guides as PREFIX_normal/_depth/_albedo/_id.png")
     ap.add_argument("--orbit", type=int, default=0, metavar="K", help="--temporal: render K camera steps of an orbit and write the last frame")
     ap.add_argument("--orbit-step", type=float, default=2.0, metavar="DEG", help="--orbit: degrees per camera step")
@@ -88,8 +96,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    if (a.denoise or a.temporal) and a.passes <= 0:
+    if (a.denoise or a.temporal or a.denoise_variance) and a.passes <= 0:
         a.passes = 4
+    if a.denoise_variance and (a.denoise or a.temporal):
+        ap.error("--denoise-variance stands in place of --denoise and does not take a temporal mean")
+    if a.denoise_variance and a.passes < 2:
+        ap.error("--denoise-variance needs at least two passes")
     if a.temporal and a.orbit < 1:
         a.orbit = 8
     if a.orbit > 0 and not a.temporal:
@@ -183,11 +195,14 @@ def main():
                 ms = r.timer_end() / (a.orbit * a.passes)
                 image = film.resolve(denoised=a.denoise, temporal=True, **tone)[0]
         elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
-            with pkg.Film(r) as film:
+            with pkg.Film(r, moments=a.denoise_variance) as film:
                 film.accumulate(p, a.passes)
                 if a.denoise:
                     film.denoise(levels=a.denoise_levels)
-                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags, denoised=a.denoise)[0]
+                if a.denoise_variance:
+                    film.denoise(variance=True, levels=a.denoise_levels, **({} if a.kappa is None else dict(kappa=a.kappa)))
+                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags,
+                                     denoised=a.denoise or a.denoise_variance)[0]
                 r.timer_begin()
                 for _ in range(a.frames):                       # (timed: one more pass into the sum, per pass)
                     film.accumulate(p, 1)
@@ -216,7 +231,7 @@ def main():
                 Image.fromarray(np.clip(np.rint(pic), 0, 255).astype(np.uint8).transpose(2, 1, 0)).save(f"{a.guides}_{kind}.png")
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
-        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise} temporal={a.temporal} orbit={a.orbit}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
+        print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise} denoise_variance={a.denoise_variance} temporal={a.temporal} orbit={a.orbit}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
 
 
 if __name__ == "__main__":

@@ -691,6 +691,77 @@ int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t
                      const rt_temporal *tp,
                      void *d_out, int64_t out_stride, void *d_out_len, void *stream);
 
+/* The variance-guided denoiser: the film keeps a sum of squares beside its sum, and the filter takes every pixel's colour tolerance
+ * from the estimated variance of its mean instead of one global sigma, so it fades out by itself as the film converges.
+ * RT_ABI_VERSION is unchanged: callers detect these two entry points by their symbols.
+ *
+ * rt_film_accumulate_moments: rt_film_accumulate with a second buffer.  Everything rt_film_accumulate does stays: the pass seeds,
+ * the scratch, the batches of up to four passes, the slab addressing, the status codes; d_sum receives the same bits.  d_sq is a
+ * second float64 buffer of three planes with the same addressing (element [c, x, y] at d_sq[c * sq_stride + (x - x0) * h + y]).
+ * Per element e, float64, in pass order:
+ *   q = reset ? +0.0 : sq[e];  for i: g = (double)f_i[e]; q = q + g*g;  sq[e] = q
+ * (the product of two widened float32 values is exact in float64).  RT_ERR_BAD_ARG as rt_film_accumulate, and for d_sq NULL,
+ * sq_stride < (x1-x0)*h and d_sq == d_sum; both buffers are then untouched.
+ *
+ * rt_film_denoise_variance: rt_film_denoise's a-trous filter with a per-pixel colour tolerance.  d_sum and d_sq are a film's sum
+ * and sum of squares of n >= 2 passes of a ws x h frame, d_guides that frame's guides.  d_out and d_work are float64 buffers of
+ * FOUR planes (RT_DENOISE_VAR_PLANES) laid out like a sum: planes 0..2 receive the filtered MEAN, which rt_film_resolve takes with
+ * n = 1 (it reads three planes), plane 3 the propagated variance of that mean.  d_work may be NULL only for levels == 0.  Which of
+ * the two holds which level is the library's business; the result always ends in d_out.  The library allocates nothing.  d_out and
+ * d_work must not overlap an input or each other: equal pointers are refused, partial overlap is the caller's error.
+ * Per pixel p in float64, no fused multiply-add, in this order (k[] is the B3 spline of rt_film_denoise, which is why the tolerance
+ * is called kappa):
+ *   m_0[c][p] = s[c][p] / (double)n;    r = sq[c][p] / (double)n - m_0[c][p]*m_0[c][p];    r > 0 ? r : 0   (NaN: 0)
+ *   var_c = r / (double)(n - 1)                                   (the variance of the MEAN, per channel)
+ *   demodulate:  a[c][p] = max((double)albedo_c[p], 1.0);   m_0[c][p] = m_0[c][p] / a[c][p];   var_c = var_c / (a[c][p]*a[c][p])
+ *   v_0[p] = (var_0 + var_1) + var_2
+ *   levels == 0:  out[c][p] = s[c][p] / (double)n;  out[3][p] = v_0[p] computed WITHOUT demodulation;  nothing else is evaluated
+ *   for i = 0 .. levels-1:    step = 1 << i
+ *       prefilter:  gw = gv = +0.0;  for dx = -1..1 (outer), dy = -1..1 (inner):  q = (p.x+dx, p.y+dy)   (step 1 at every level)
+ *                       q outside the frame, or id[q] != id[p]:  skip
+ *                       t = g[dx]*g[dy]   g = (1/4, 1/2, 1/4);    gw = gw + t;   gv = gv + t * v_i[q]
+ *                   vp = gv / gw                                   (the centre contributes 1/4, so gw > 0)
+ *       else:       vp = v_i[p]
+ *       den = (kappa*kappa) * vp + var_floor
+ *       W = +0.0; A_c = +0.0; V = +0.0
+ *       for dx = -2..2 (outer), dy = -2..2 (inner):   q = (p.x + step*dx, p.y + step*dy)
+ *           outside, id, normal test and cn:  exactly the lines of rt_film_denoise
+ *           e_c = m_i[c][q] - m_i[c][p];   d2 = (e_0*e_0 + e_1*e_1) + e_2*e_2
+ *           den > 0:  wc = 1.0 / (1.0 + d2 / den)        else:  wc = d2 > 0 ? 0.0 : 1.0
+ *           w = ((k[dx] * k[dy]) * cn) * wc
+ *           W = W + w;   A_c = A_c + w * m_i[c][q];   V = V + (w*w) * v_i[q]
+ *       m_{i+1}[c][p] = A_c / W;     v_{i+1}[p] = V / (W*W)
+ *   out[c][p] = demodulate ? m_levels[c][p] * a[c][p] : m_levels[c][p];     out[3][p] = v_levels[p]   (filter units)
+ * kappa is the colour tolerance in standard deviations of the mean; var_floor is added to the scaled variance, in squared filter
+ * units (colour / albedo with demodulate, colour without).  With kappa = 0 and var_floor = 0, or where a pixel's variance is 0 (n
+ * identical passes), only taps of exactly the centre's colour are mixed in.  No exp(), no pow(), no sqrt: the bytes do not depend on
+ * a math library.  A non-finite sum, sum of squares or guide gives unspecified values but does not fault: every tap index is
+ * range-checked before it is read.  Taps do not cross the edge of the buffer, so a multi-rank caller denoises the assembled frame.
+ * A temporal mean (rt_film_temporal) has no second moment: carrying one through the history is out of scope, and this filter takes a
+ * film's own sum and sum of squares only.
+ * RT_ERR_BAD_ARG as rt_film_denoise (NULL d_sum, d_guides, dv or d_out; levels; normal_shin; demodulate; ws, h), and for d_sq NULL;
+ * n < 2; a kappa or var_floor that is not finite or is negative; a prefilter that is not 0 or 1; any of the five strides < ws*h
+ * (work_stride counts when d_work is given); d_work == NULL with levels >= 1; equal buffers among d_out, d_work and any input.  The
+ * outputs are then untouched.  Asynchronous on `stream`; it needs no scene. */
+#define RT_DENOISE_VAR_PLANES 4
+
+int rt_film_accumulate_moments(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset,
+                               void *d_sum, int64_t sum_stride, void *d_sq, int64_t sq_stride, void *stream);
+
+typedef struct rt_denoise_variance {
+    int32_t levels;       /* 0..6 */
+    int32_t normal_shin;  /* 1, 2, 4, ..., 1024 */
+    double  kappa;        /* finite, >= 0: colour tolerance in standard deviations of the mean */
+    double  var_floor;    /* finite, >= 0: added to the scaled variance, in squared filter units */
+    int32_t demodulate;   /* 0 or 1 */
+    int32_t prefilter;    /* 0 or 1: 3x3 smoothing of the variance before it is used */
+} rt_denoise_variance;    /* 32 bytes */
+
+int rt_film_denoise_variance(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride,
+                             int ws, int h, int64_t n, const void *d_guides, int64_t guide_stride,
+                             const rt_denoise_variance *dv, void *d_out, int64_t out_stride,
+                             void *d_work, int64_t work_stride, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

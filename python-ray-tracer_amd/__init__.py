@@ -16,6 +16,7 @@ from .renderer import Renderer, RenderError   # noqa: F401
 from . import film            # noqa: F401
 from . import denoise         # noqa: F401
 from . import temporal        # noqa: F401
+from . import variance        # noqa: F401
 from .film import Film        # noqa: F401
 
-__all__ = ["cuda", "denoise", "film", "temporal", "Film", "Renderer", "RenderError"]
+__all__ = ["cuda", "denoise", "film", "temporal", "variance", "Film", "Renderer", "RenderError"]

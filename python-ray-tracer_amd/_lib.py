@@ -58,6 +58,13 @@ class rt_denoise(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class rt_denoise_variance(C.Structure):
+    """rt_film_denoise_variance's settings (include/mi355rt.h; the arithmetic in numpy: variance.denoise_variance_reference): levels
+    0..6; normal_shin 1, 2, 4, ..., 1024; kappa and var_floor finite and >= 0; demodulate and prefilter 0 or 1.  32 bytes."""
+    _fields_ = [("levels", C.c_int32), ("normal_shin", C.c_int32), ("kappa", C.c_double), ("var_floor", C.c_double),
+                ("demodulate", C.c_int32), ("prefilter", C.c_int32)]
+
+
 class rt_temporal(C.Structure):
     """rt_film_temporal's settings (include/mi355rt.h; the arithmetic in numpy: temporal.temporal_reference): the camera the history
     was rendered with; depth_tol finite and >= 0, relative, on the squared distance; normal_cos in [-1, 1]; max_history finite and
@@ -111,6 +118,9 @@ PROTOTYPES = {
                                   _vp, C.c_int64, _vp]),
     "rt_film_temporal": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(rt_temporal),
                                    _vp, C.c_int64, _vp, _vp]),
+    "rt_film_accumulate_moments": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "rt_film_denoise_variance": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64,
+                                           C.POINTER(rt_denoise_variance), _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -132,7 +142,7 @@ PROTOTYPES = {
 
 # Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
 # times such a build beside this one), and Renderer raises where one is called.
-LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal")
+LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance")
 
 _lib = None
 

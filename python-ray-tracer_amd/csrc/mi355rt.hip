@@ -7,6 +7,7 @@
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_denoise.h"
+#include "rt_denoise_var.h"
 #include "rt_feedback.h"
 #include "rt_film.h"
 #include "rt_geometry.h"
@@ -757,19 +758,14 @@ int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
 }
 
 // The film: `passes` frames of the unchanged render path (launch(), float32 output, seed + i) into the stream's scratch, up to
-// rt::FILM_BATCH of them folded into the float64 sum by one add kernel.  Everything is queued on `stream`: a batch's renders write
-// the scratch only after the add kernel before them has read it.
-int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
-                       void *stream)
+// rt::FILM_BATCH of them folded into the float64 sum by one add kernel (with d_sq: into the sum and the sum of squares by one add2
+// kernel).  Everything is queued on `stream`: a batch's renders write the scratch only after the add kernel before them has read it.
+// The arguments have been checked by the entry point.
+static int film_queue_passes(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
+                             void *d_sq, int64_t sq_stride, void *stream)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    int rc = check_params(ctx, params, x0, x1);
-    if (rc != RT_OK) return rc;
-    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: passes < 1");
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: d_sum is NULL");
+    int rc = RT_OK;
     const long long npx = (long long)(x1 - x0) * ctx->view.h;
-    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: (x1-x0)*h above RT_FILM_MAX_PIXELS");
-    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: sum_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
     rt_params p = *params;
@@ -788,6 +784,9 @@ int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
     float *const frames = (float *)fb.p;
     rt::FilmAddArgs a;
     a.sum = (double *)d_sum; a.frames = frames; a.sum_stride = sum_stride; a.fplane = fplane; a.npx = npx;
+    rt::FilmAdd2Args a2;
+    a2.sum = (double *)d_sum; a2.sq = (double *)d_sq; a2.frames = frames; a2.sum_stride = sum_stride; a2.sq_stride = sq_stride;
+    a2.fplane = fplane; a2.npx = npx;
     const dim3 grid(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 3), 3);
     for (int i = 0; i < passes; i += batch) {
         const int nb = std::min(batch, passes - i);
@@ -796,11 +795,44 @@ int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
             rc = launch(ctx, &p, x0, x1, nullptr, frames + (size_t)b * 3 * fplane, fplane, st);
             if (rc != RT_OK) return rc;
         }
-        a.nb = nb; a.reset = (reset && i == 0) ? 1 : 0;
-        hipLaunchKernelGGL(rt::film_add_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a);
+        a.nb = a2.nb = nb; a.reset = a2.reset = (reset && i == 0) ? 1 : 0;
+        if (d_sq) hipLaunchKernelGGL(rt::film_add2_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a2);
+        else hipLaunchKernelGGL(rt::film_add_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a);
         RT_HIP(ctx, hipGetLastError());
     }
     return RT_OK;
+}
+
+int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
+                       void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = check_params(ctx, params, x0, x1);
+    if (rc != RT_OK) return rc;
+    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: passes < 1");
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: d_sum is NULL");
+    const long long npx = (long long)(x1 - x0) * ctx->view.h;
+    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: (x1-x0)*h above RT_FILM_MAX_PIXELS");
+    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: sum_stride smaller than the slab");
+    return film_queue_passes(ctx, params, x0, x1, passes, reset, d_sum, sum_stride, nullptr, 0, stream);
+}
+
+// rt_film_accumulate with the sum of squares beside the sum (rt_film.h: film_add2_kernel): the same passes, seeds, scratch and batches.
+int rt_film_accumulate_moments(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
+                               void *d_sq, int64_t sq_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = check_params(ctx, params, x0, x1);
+    if (rc != RT_OK) return rc;
+    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: passes < 1");
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sum is NULL");
+    if (!d_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sq is NULL");
+    if (d_sq == d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sq and d_sum must be buffers of their own");
+    const long long npx = (long long)(x1 - x0) * ctx->view.h;
+    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: (x1-x0)*h above RT_FILM_MAX_PIXELS");
+    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: sum_stride smaller than the slab");
+    if (sq_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: sq_stride smaller than the slab");
+    return film_queue_passes(ctx, params, x0, x1, passes, reset, d_sum, sum_stride, d_sq, sq_stride, stream);
 }
 
 int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone,
@@ -924,6 +956,63 @@ int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
         hipLaunchKernelGGL(rt::denoise_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
         RT_HIP(ctx, hipGetLastError());
         src = a.dst; src_stride = a.dst_stride;
+    }
+    return RT_OK;
+}
+
+// The variance-guided filter: a prepare launch (rt_denoise_var.h: the mean and the variance of the mean from sum and sum of squares)
+// and one launch per level, ping-pong between d_out and d_work so that the last write ends in d_out; levels == 0 is the prepare
+// launch alone, without demodulation.
+int rt_film_denoise_variance(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int ws, int h, int64_t n,
+                             const void *d_guides, int64_t guide_stride, const rt_denoise_variance *dv, void *d_out, int64_t out_stride,
+                             void *d_work, int64_t work_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_sum is NULL");
+    if (!d_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_sq is NULL");
+    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_guides is NULL");
+    if (!dv) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: dv is NULL");
+    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out is NULL");
+    if (n < 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: n < 2");
+    if (dv->levels < 0 || dv->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: levels outside 0..6");
+    int nsq = -1;
+    for (int i = 0; i <= 10; ++i) if (dv->normal_shin == (1 << i)) nsq = i;
+    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: normal_shin must be 1, 2, 4, ..., 1024");
+    if (!(std::isfinite(dv->kappa) && dv->kappa >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: kappa must be finite and >= 0");
+    if (!(std::isfinite(dv->var_floor) && dv->var_floor >= 0.0))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: var_floor must be finite and >= 0");
+    if (dv->demodulate != 0 && dv->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: demodulate must be 0 or 1");
+    if (dv->prefilter != 0 && dv->prefilter != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: prefilter must be 0 or 1");
+    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: ws*h outside 1..RT_FILM_MAX_PIXELS");
+    const long long npx = (long long)ws * h;
+    if (sum_stride < npx || sq_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: a plane stride is smaller than the frame");
+    if (!d_work && dv->levels >= 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_work is NULL with levels >= 1");
+    for (const void *in : {d_sum, d_sq, d_guides})
+        if (d_out == in || (d_work && d_work == in))
+            return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out and d_work must be buffers of their own");
+    if (d_work && d_work == d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out and d_work must be buffers of their own");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_of(ctx, stream);
+    const int levels = dv->levels;
+    rt::DenoiseVarArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.sum = (const double *)d_sum; a.sum_stride = sum_stride; a.sq = (const double *)d_sq; a.sq_stride = sq_stride;
+    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
+    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dv->demodulate; a.prefilter = dv->prefilter; a.copy = levels == 0;
+    a.n = (double)n; a.n1 = (double)(n - 1); a.k2 = dv->kappa * dv->kappa; a.var_floor = dv->var_floor;
+    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
+    for (int k = 0; k <= levels; ++k) {
+        const bool to_out = rt::denoise_var_to_out(levels, k);
+        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
+        if (k == 0) hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
+        else {
+            rt::denoise_var_level(a, levels, k - 1);
+            hipLaunchKernelGGL(rt::denoise_var_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
+        }
+        RT_HIP(ctx, hipGetLastError());
+        a.src = a.dst; a.src_stride = a.dst_stride;
     }
     return RT_OK;
 }

@@ -1,8 +1,9 @@
-// rt_film.h — the film (include/mi355rt.h: rt_film_accumulate, rt_film_resolve): a float64 sum of float32 pass frames in device
-// memory, and its resolve to a frame (mean, exposure, highlight compression, display gamma, bytes).
-// The arithmetic of one element (film_add, film_tone, film_clip) is HIP-free, like rt_plan.h and rt_scene.h and for the same
-// reason: the two kernels below and tests/algo/film_check.cpp, a CPU program built under AddressSanitizer and UBSan, compile the
-// same text.  Everything here is evaluated without fused multiply-add (the Makefile's -ffp-contract=off; the CPU program's too).
+// rt_film.h — the film (include/mi355rt.h: rt_film_accumulate, rt_film_accumulate_moments, rt_film_resolve): a float64 sum of float32
+// pass frames in device memory (with the moments entry a float64 sum of their squares beside it), and its resolve to a frame (mean,
+// exposure, highlight compression, display gamma, bytes).
+// The arithmetic of one element (film_add, film_add_sq, film_tone, film_clip) is HIP-free, like rt_plan.h and rt_scene.h and for the same
+// reason: the kernels below and tests/algo/film_check.cpp and variance_check.cpp, CPU programs built under AddressSanitizer and UBSan,
+// compile the same text.  Everything here is evaluated without fused multiply-add (the Makefile's -ffp-contract=off; the CPU program's too).
 // The kernels (hipcc only) are memory-bound streams: 16-byte accesses per lane on planes whose base is 16-byte aligned, 8-, 4-
 // or 1-byte accesses on planes whose base is not (a caller's plane stride may be odd), a scalar tail for the last npx mod 4
 // elements, a grid capped near 8 blocks per CU with a grid-stride loop, no LDS, no scratch, 64-bit plane offsets.
@@ -19,6 +20,14 @@ namespace rt {
 
 // One pass's float32 colour onto the float64 sum.
 RT_FILM_HD inline double film_add(double s, float f) { return s + (double)f; }
+
+// One pass's float32 colour, squared, onto the float64 sum of squares (rt_film_accumulate_moments).  The product of two widened
+// float32 values is exact in float64: fusing it into the addition could not change the result.
+RT_FILM_HD inline double film_add_sq(double q, float f)
+{
+    const double g = (double)f;
+    return q + g * g;
+}
 
 // What a resolve evaluates once: n as a double, and the square of white / 255.
 struct FilmTone {
@@ -76,6 +85,14 @@ struct FilmAddArgs {
     double *sum;
     const float *frames;
     long long sum_stride, fplane, npx;
+    int nb, reset;
+};
+
+// film_add2_kernel: FilmAddArgs with the sum of squares beside the sum; sum and sq are planes of their own stride and alignment
+struct FilmAdd2Args {
+    double *sum, *sq;
+    const float *frames;
+    long long sum_stride, sq_stride, fplane, npx;
     int nb, reset;
 };
 
@@ -146,6 +163,52 @@ __global__ __launch_bounds__(FILM_THREADS) void film_add_kernel(const FilmAddArg
         double acc = a.reset ? 0.0 : s[e];
         for (int b = 0; b < a.nb; ++b) acc = film_add(acc, f[b * pass + e]);
         s[e] = acc;
+    }
+}
+
+// film_add_kernel with a second buffer: sq[c][e] = (reset ? +0.0 : sq[c][e]) + f_0[c][e]^2 + ... + f_{nb-1}[c][e]^2 beside the sum, each
+// pass element read once for both.  The sum's bits are film_add_kernel's.  A sum plane and a sq plane may differ in alignment.
+__global__ __launch_bounds__(FILM_THREADS) void film_add2_kernel(const FilmAdd2Args a)
+{
+    const long long c = blockIdx.y;
+    double *const s = a.sum + c * a.sum_stride;
+    double *const q = a.sq + c * a.sq_stride;
+    const float *const f = a.frames + c * a.fplane;
+    const long long pass = 3 * a.fplane;
+    const bool vec_s = film_aligned(s, 16), vec_q = film_aligned(q, 16);
+    const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
+    for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
+        const long long e = g << 2;
+        film_f4 v[FILM_BATCH];
+#pragma unroll
+        for (int b = 0; b < FILM_BATCH; ++b)
+            if (b < a.nb) v[b] = *reinterpret_cast<const film_f4 *>(f + b * pass + e);
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
+        if (!a.reset) {
+            film_load4(s + e, vec_s, acc);
+            film_load4(q + e, vec_q, sq);
+        }
+#pragma unroll
+        for (int b = 0; b < FILM_BATCH; ++b)
+            if (b < a.nb) {
+                acc[0] = film_add(acc[0], v[b].x); acc[1] = film_add(acc[1], v[b].y);
+                acc[2] = film_add(acc[2], v[b].z); acc[3] = film_add(acc[3], v[b].w);
+                sq[0] = film_add_sq(sq[0], v[b].x); sq[1] = film_add_sq(sq[1], v[b].y);
+                sq[2] = film_add_sq(sq[2], v[b].z); sq[3] = film_add_sq(sq[3], v[b].w);
+            }
+        film_store4(s + e, vec_s, acc);
+        film_store4(q + e, vec_q, sq);
+    }
+    if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
+        const long long e = (ngroups << 2) + threadIdx.x;
+        double acc = a.reset ? 0.0 : s[e], sq = a.reset ? 0.0 : q[e];
+        for (int b = 0; b < a.nb; ++b) {
+            const float x = f[b * pass + e];
+            acc = film_add(acc, x);
+            sq = film_add_sq(sq, x);
+        }
+        s[e] = acc;
+        q[e] = sq;
     }
 }
 

@@ -23,12 +23,22 @@ temporal.py):
             film.temporal()                           # history reprojected through the move, blended with the new passes
             film.denoise(temporal=True)
             image, _ = film.resolve(white=400.0, denoised=True, temporal=True)   # (temporal=True alone: without the filter)
+
+Film(renderer, moments=True) keeps a sum of squares beside the sum (rt_film_accumulate_moments), and denoise(variance=True) takes
+every pixel's colour tolerance from the variance of its mean (rt_film_denoise_variance; their arithmetic in numpy is in variance.py):
+
+    with Film(renderer, moments=True) as film:
+        film.accumulate(params, passes=8)
+        film.denoise(variance=True)                   # no sigma to tune: the filter fades out as the film converges
+        image, _ = film.resolve(white=400.0, denoised=True)
+        noise = film.variance()                       # float64 (ws, h): the estimated variance of the mean, to stop refining on
 """
 import numpy as np
 
 from . import _lib as L
 from .denoise import check_denoise
 from .temporal import DEPTH_TOL, MAX_HISTORY, NORMAL_COS, check_temporal
+from .variance import KAPPA, VAR_PLANES, check_denoise_variance
 
 # Film.denoise's default sigma, in the units the filter sees: colour / albedo with demodulation, so about 0..1 and not 0..255.  The
 # best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 at levels 4, normal_shininess 32 with demodulation on four passes of the
@@ -107,9 +117,10 @@ def check_tone(n, exposure, white, gamma, flags=0):
 
 class Film:
     """A float64 (3, x1-x0, h) sum of pass frames in the renderer's device memory, and how many passes it holds.  The frame size is
-    the renderer's at construction (set_raygen / set_pixel_loc first)."""
+    the renderer's at construction (set_raygen / set_pixel_loc first).  moments: the film also owns a float64 sum of the passes'
+    squares, which denoise(variance=True) and variance() need."""
 
-    def __init__(self, renderer, x0=0, x1=None):
+    def __init__(self, renderer, x0=0, x1=None, moments=False):
         w, h = getattr(renderer, "w", None), getattr(renderer, "h", None)
         if not w or not h:
             raise ValueError("the renderer has no ray grid yet: call set_raygen or set_pixel_loc before making a Film")
@@ -123,6 +134,10 @@ class Film:
         self.ws = x1 - x0
         self.passes = 0
         self.d_sum = renderer.malloc(24 * self.ws * self.h)
+        self.moments = bool(moments)
+        self.d_sq = renderer.malloc(24 * self.ws * self.h) if self.moments else None
+        self.d_denoised_var = self.d_work_var = None              # four planes each: allocated by denoise(variance=True) and variance()
+        self.denoised_variance = False                            # the filtered mean of the current passes is in d_denoised_var
         self.d_guides = self.d_denoised = self.d_work = None      # allocated by guides() and denoise()
         self.denoised_passes = 0                                  # the pass count the filtered mean in d_denoised belongs to (0: none)
         # temporal accumulation: allocated by next_frame() and temporal()
@@ -137,7 +152,8 @@ class Film:
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
-        names = ("d_temporal", "d_temporal_len", "d_hist", "d_hist_len", "d_hist_guides", "d_guides", "d_denoised", "d_work")
+        names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_hist", "d_hist_len", "d_hist_guides", "d_guides",
+                 "d_denoised", "d_work")
         extra = [getattr(self, n, None) for n in names]
         for n in names:
             setattr(self, n, None)
@@ -172,13 +188,18 @@ class Film:
         if self.renderer.h != self.h or self.x1 > (self.renderer.w or 0):
             raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
                              f"[{self.x0}, {self.x1}) of height {self.h}")
-        self.renderer.film_accumulate(params, self.x0, self.x1, passes, self.passes == 0, self.d_sum, self.ws * self.h, stream)
+        if self.moments:
+            self.renderer.film_accumulate_moments(params, self.x0, self.x1, passes, self.passes == 0, self.d_sum, self.d_sq,
+                                                  self.ws * self.h, self.ws * self.h, stream)
+        else:
+            self.renderer.film_accumulate(params, self.x0, self.x1, passes, self.passes == 0, self.d_sum, self.ws * self.h, stream)
         self.passes += passes
 
     def clear(self):
         """Forget every pass: the next accumulate starts from zero.  The guides stay (they do not depend on the passes)."""
         self.passes = 0
         self.denoised_passes = 0
+        self.denoised_variance = False
         self.temporal_passes = 0
 
     # -- the denoiser -----------------------------------------------------------------------
@@ -206,7 +227,8 @@ class Film:
         self.guides_camera = getattr(r, "camera", None)
         self.guides_stale = False
 
-    def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None, temporal=False):
+    def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None, temporal=False, variance=False,
+                kappa=KAPPA, var_floor=0.0, prefilter=True):
         """Filter the mean of the passes so far (Renderer.film_denoise: an edge-stopping a-trous filter guided by guides(), which is
         called first if it has not been) into the film's own buffers; resolve(denoised=True) shows the result.  levels 0..6,
         normal_shininess 1, 2, 4, ..., 1024, sigma 0 (no colour weight) or > 0 in colour units, demodulate: filter colour / albedo.
@@ -214,8 +236,15 @@ class Film:
         The default, DENOISE_SIGMA = 1/8, is the best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 recorded in DESIGN.md (Denoiser): four
         passes of the soft_default_64_d4 scene with one shadow sample against its 1024-pass mean, RMSE x0.85; the values 4 to 64
         switch the colour weight off under demodulation and make that frame worse (x2.7 to x2.9).  temporal: filter the mean that
-        temporal() wrote (with n = 1) instead of the mean of the passes.  Asynchronous."""
+        temporal() wrote (with n = 1) instead of the mean of the passes.
+        variance: the variance-guided filter instead (Renderer.film_denoise_variance), on a film made with moments=True that holds
+        at least two passes: sigma is not used; a tap's colour tolerance is kappa standard deviations of the pixel's mean (KAPPA:
+        the choice of the sweep in DESIGN.md, Variance-guided denoiser) plus var_floor, with the variance smoothed over 3 x 3 pixels
+        of the same object when prefilter is set.  It filters into four-plane buffers of the film's own, and cannot take the
+        temporal mean: a temporal mean has no second moment.  Asynchronous."""
         self._live()
+        if variance:
+            return self._denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, stream)
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         levels, shin, sigma, demodulate = check_denoise(levels, normal_shininess, sigma, demodulate)
@@ -231,6 +260,44 @@ class Film:
                        normal_shin=shin, sigma=sigma, demodulate=demodulate, stream=stream)
         self.denoised_passes = self.passes
         self.denoised_temporal = bool(temporal)
+        self.denoised_variance = False
+
+    def _variance_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, stream):
+        """rt_film_denoise_variance on the film's sums into d_out (four planes), after what it needs is there."""
+        if not self.moments:
+            raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
+        if self.passes < 2:
+            raise ValueError(f"a variance needs at least 2 passes, the film holds {self.passes}")
+        if not self.d_guides or self.guides_stale:
+            self.guides(stream)
+        n = self.ws * self.h
+        for name in (d_out, d_work):
+            if name and not getattr(self, name):
+                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * n))
+        self.renderer.film_denoise_variance(self.d_sum, self.d_sq, self.ws, self.h, self.passes, self.d_guides, getattr(self, d_out),
+                                            getattr(self, d_work) if d_work else None, levels=levels, normal_shin=shin, kappa=kappa,
+                                            var_floor=var_floor, demodulate=demodulate, prefilter=prefilter, stream=stream)
+
+    def _denoise_variance(self, levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, stream):
+        levels, shin, kappa, var_floor, demodulate, prefilter = check_denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter)
+        if temporal:
+            raise ValueError("the variance-guided filter cannot take the temporal mean: a temporal mean has no second moment")
+        self._variance_call("d_denoised_var", "d_work_var" if levels >= 1 else None, levels, shin, kappa, var_floor, demodulate, prefilter, stream)
+        self.denoised_passes = self.passes
+        self.denoised_temporal = False
+        self.denoised_variance = True
+
+    def variance(self, stream=None):
+        """The estimated variance of the mean of the passes so far, per pixel, summed over the channels: float64 (ws, h), plane 3 of
+        the levels = 0 call of Renderer.film_denoise_variance (into the film's work buffer: a filtered mean stays).  A caller stops
+        refining on it.  It needs a film made with moments=True and two passes.  Waits for the stream."""
+        self._live()
+        self._variance_call("d_work_var", None, 0, 1, 0.0, 0.0, 0, 0, stream)
+        r = self.renderer
+        r.sync(stream)
+        out = np.empty((self.ws, self.h), np.float64)
+        r.d2h(out, self.d_work_var + 8 * 3 * self.ws * self.h)
+        return out
 
     def _source(self, denoised, temporal=False):
         """(sum or mean, its n) of a resolve or a filter: the sum of the passes, the temporal mean, or the filtered mean of either."""
@@ -242,7 +309,7 @@ class Film:
             raise ValueError("the film has no filtered mean of its current passes: call denoise() first")
         if temporal and not self.denoised_temporal:
             raise ValueError("the filtered mean is that of the plain passes: call denoise(temporal=True) first")
-        return self.d_denoised, 1
+        return (self.d_denoised_var if self.denoised_variance else self.d_denoised), 1
 
     # -- temporal accumulation ---------------------------------------------------------------
     def _full_frame(self):

@@ -465,6 +465,31 @@ class Renderer:
                                                           strides[2], vp(d_hist_len), vp(d_hist_guides), strides[3], C.byref(tp),
                                                           vp(d_out), strides[4], vp(d_out_len), vp(stream)))
 
+    def film_accumulate_moments(self, params, x0, x1, passes, reset, d_sum, d_sq, sum_stride=None, sq_stride=None, stream=None):
+        """film_accumulate with the sum of the frames' squares added to a second float64 (3, x1-x0, h) buffer at d_sq
+        (rt_film_accumulate_moments); d_sum receives the bits film_accumulate would give.  Asynchronous.  In numpy:
+        variance.accumulate_moments_reference."""
+        npx = (int(x1) - int(x0)) * (self.h or 0)
+        sum_stride, sq_stride = (npx if v is None else int(v) for v in (sum_stride, sq_stride))
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_accumulate_moments")(self._ctx, C.byref(params), int(x0), int(x1), int(passes), int(bool(reset)),
+                                                                    vp(d_sum), sum_stride, vp(d_sq), sq_stride, vp(stream)))
+
+    def film_denoise_variance(self, d_sum, d_sq, ws, h, n, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, kappa=1.0, var_floor=0.0,
+                              demodulate=1, prefilter=1, sum_stride=None, sq_stride=None, guide_stride=None, out_stride=None, work_stride=None,
+                              stream=None):
+        """The variance-guided a-trous filter on the mean of n >= 2 passes (sum at d_sum, sum of squares at d_sq), guided by d_guides,
+        into the float64 (4, ws, h) buffer d_out: the filtered mean and, in plane 3, its propagated variance
+        (rt_film_denoise_variance); d_work is a second such buffer (None allowed for levels == 0).  The result is a mean: resolve
+        it with film_resolve(..., n=1).  Asynchronous.  In numpy: variance.denoise_variance_reference."""
+        npx = int(ws) * int(h)
+        strides = [npx if v is None else int(v) for v in (sum_stride, sq_stride, guide_stride, out_stride, work_stride)]
+        dv = L.rt_denoise_variance(int(levels), int(normal_shin), float(kappa), float(var_floor), int(demodulate), int(prefilter))
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_denoise_variance")(self._ctx, vp(d_sum), strides[0], vp(d_sq), strides[1], int(ws), int(h), int(n),
+                                                                  vp(d_guides), strides[2], C.byref(dv), vp(d_out), strides[3], vp(d_work),
+                                                                  strides[4], vp(stream)))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
         if stream:
