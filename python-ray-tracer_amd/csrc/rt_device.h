@@ -13,7 +13,8 @@
 //     with wave-uniform (broadcast) ds_reads;
 //   * every scene query normalises its direction ONCE (the reference re-normalises per sphere,
 //     intersections.py:13 — same value every time), with an exact two-fma shortcut for
-//     already-unit vectors, and works on the quadratic scaled by 1/4 (exact in binary FP);
+//     already-unit vectors, and works on the quadratic scaled by 1/4 (exact in binary FP); the wave-uniform
+//     queries do so only once their cull has left a sphere to test (rt_cull.h: the cull reads the incoming direction);
 //   * closest-hit keeps the smallest positive numerator and divides once per query;
 //   * shadow queries are any-hit: no sqrt/divide unless a decision is within rounding reach,
 //     the sphere loop exits as soon as a wave ballot says every live lane is occluded, and
@@ -33,6 +34,7 @@
 #include <stdint.h>
 #include "rt_kparams.h"  // rt::KParams, the kernels' argument (the host fills it: rt_launch.h)
 #include "rt_math.h"     // V3, the seeded bodies of normalize3 / div_inrange / sqrt_inrange / renormalize_unit, the counter hashes, clip_color
+#include "rt_cull.h"     // the float32 cull's certificates (RayF, cull_anchored, cull_origin, anchored_tau, CULL_K_*) and the guard for culling on the incoming direction
 #include "rt_facing.h"   // the facing certificate of the point-light loop (trace_bounce) and its margin
 #include "rt_layout.h"   // record strides, rt::Family, block sizes and offsets, the LDS image's arithmetic (lds_bytes, table_layout, ...), TILE, div_magic:
                          // shared with the host's scene packer (rt_scene.h) and launch plan (rt_plan.h)
@@ -55,6 +57,12 @@
 #endif
 #ifndef RT_FACING_SKIP
 #define RT_FACING_SKIP 1     // 0: the point-light loops without the facing certificate (A/B builds)
+#endif
+#ifndef RT_DEFER_DIRECTION
+#define RT_DEFER_DIRECTION 1 // 0: every scene query forms its float64 direction R before its cull (A/B builds); 1: the wave-uniform queries
+#endif                       //    form R only when the cull leaves a sphere (closest_spheres, any_spheres_masks; rt_cull.h)
+#ifndef RT_DEFER_SHADOW
+#define RT_DEFER_SHADOW 1    // 0: only closest_hit defers, any_hit_masks keeps the former order (A/B builds)
 #endif
 
 namespace rt {
@@ -225,10 +233,8 @@ template <int WSLOT, bool FRESH> struct MatState<Family::PLAIN, WSLOT, FRESH> {
 // bounds it for every query of the launch.
 // A sphere is skipped only if EVERY live lane holds a certificate; NaNs certify nothing.
 // ---------------------------------------------------------------------------------------------
-constexpr float CULL_K_ANCHOR = 0x1p-19f * 1.0001f;
-constexpr float CULL_K_ORIGIN = 0x1p-18f;
-constexpr float CULL_K_S = 0x1p-21f;
-constexpr float CULL_K_FLOOR = 0x1p-40f;
+// (the CULL_K_* constants and the certificates' arithmetic — make_rayf_dir, add_origin, anchored_tau, cull_anchored, cull_origin —
+// are in rt_cull.h, HIP-free, with the bound for culling on the incoming direction)
 
 // The workgroup's dynamic LDS.  Its base is a link-time constant: reading the float64 records through this symbol (and
 // not through a pointer carried in a struct) lets every record access be a ds_read at an immediate offset of the slot
@@ -253,6 +259,10 @@ struct Lds {
     bool trim;             // a compile-time constant per kernel: the instruction trims measured on the two-wave kernels without a material
                            // table — shadow queries keep their occlusion flag as one scalar lane mask (any_hit_masks), and a plane with
                            // normal -e_i is tested without negating den and num (plane_den_num)
+    bool defer;            // a compile-time constant per kernel: the wave-uniform queries form their float64 direction behind their cull
+                           // (closest_spheres, any_spheres_masks).  Not in the lane-owned kernels, whose queries need R before the traversal,
+                           // and not in the parked 9-tap kernels (AA && PARK), which run at 72 VGPRs with 68 to 92 B/lane of scratch already:
+                           // the PLAIN ones gain 4 to 8 B/lane with it
 #ifdef RT_REGION_STATS
     unsigned *reg;         // measurement build: 32 words per wave — cycles per code region [0, 24), bounce class [30], last stamp [31]
 #endif
@@ -281,42 +291,10 @@ __device__ __forceinline__ void region_mark(unsigned *reg, int id)
 #define RT_MARK(id)
 #endif
 
-struct RayF {              // float32 shadow of a query, for the cull only
-    F3 o, R;
-    float mgq, esq;        // per-ray parts of the origin form's margins: K_O |o|² + floor,  K_S (1 + |o|²)
-};
-
-// The anchored form needs the direction only; the origin terms are added where the origin form is used.
-__device__ __forceinline__ RayF make_rayf_dir(const V3 &R)
-{
-    RayF q;
-    q.o = F3{0.0f, 0.0f, 0.0f};
-    q.R = F3{(float)R.x, (float)R.y, (float)R.z};
-    q.mgq = 0.0f; q.esq = 0.0f;
-    return q;
-}
-__device__ __forceinline__ void add_origin(RayF &q, const V3 &o, float extent2)
-{
-    q.o = F3{(float)o.x, (float)o.y, (float)o.z};
-    const float oo = __builtin_fmaf(q.o.z, q.o.z, __builtin_fmaf(q.o.y, q.o.y, q.o.x * q.o.x));
-    q.mgq = __builtin_fmaf(CULL_K_ORIGIN, oo, CULL_K_FLOOR * (oo + extent2));
-    q.esq = __builtin_fmaf(CULL_K_S, oo, CULL_K_S);
-}
-
-// tau of one (anchor, sphere) pair: the line through the anchor with unit direction R misses the sphere by more
-// than every error the budget above allows when |(A-c).R32| < tau.  ll = |A-c|² (float64).
-__device__ __forceinline__ float anchored_tau(double ll, double r2, float floor_anch)
-{
-    const double W = ((ll - r2) - (ll + r2) * (double)CULL_K_ANCHOR) - (double)floor_anch;
-    if (!(W > 0.0)) return 0.0f;                              // anchor inside or too close (or NaN): never certified
-    return (float)(__builtin_sqrt(W) * (1.0 - 0x1p-20));      // rounded down: the float32 rounding is within 2^-24
-}
-
 // Table entries are read through a 32-bit LDS address that is pinned in a VGPR (the empty asm): the index is
 // wave-uniform, and left to itself the compiler forms every entry's address on the scalar unit and moves it
 // into a VGPR for its ds_read — one extra VALU instruction per sphere.  With the base in a VGPR the entries of
 // a group are immediate offsets of one 16-byte ds_read_b128 each.
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const f4 lds_cf4;
 __device__ __forceinline__ lds_cf4 *pin_lds(const float *generic)
 {
@@ -325,32 +303,10 @@ __device__ __forceinline__ lds_cf4 *pin_lds(const float *generic)
     return (lds_cf4 *)(size_t)a;
 }
 
-// true = this lane holds a certificate that sphere k reports a miss for this ray (anchored form)
-__device__ __forceinline__ bool cull_anchored(const f4 e, const RayF &q)
-{
-    const float s = __builtin_fmaf(e[2], q.R.z, __builtin_fmaf(e[1], q.R.y, e[0] * q.R.x));
-    return __builtin_fabsf(s) < e[3];                         // e[3] = tau (0: never, +inf: padding, always)
-}
-
 // Phase 1 of a scene query: one bit per sphere of the chunk [k0, k0+n), set when SOME live lane holds
 // no certificate.  Straight-line float32 work with no dependence between spheres; the mask is
 // wave-uniform (it is built from ballots), so phase 2 — the float64 test — runs only for set bits.
 // self: the sphere a shadow ray starts on (-1: none), certified by the origin form's "behind" test.
-// origin form: line-miss or behind certificate
-__device__ __forceinline__ bool cull_origin(const f4 c, const RayF &q)
-{
-    const float lx = q.o.x - c[0], ly = q.o.y - c[1], lz = q.o.z - c[2];
-    const float s = __builtin_fmaf(lz, q.R.z, __builtin_fmaf(ly, q.R.y, lx * q.R.x));
-    const float ll = __builtin_fmaf(lz, lz, __builtin_fmaf(ly, ly, lx * lx));
-    const float cc = ll - c[3];
-    const float D = __builtin_fmaf(s, s, -cc);
-    const float mg = __builtin_fmaf(CULL_K_ORIGIN, ll + c[3], q.mgq);
-    const float es = __builtin_fmaf(CULL_K_S, ll, q.esq);
-    // no short-circuit: a divergent branch here costs an exec-mask region plus a select and a compare to get the
-    // result back into a lane mask
-    return (bool)((int)(D < -mg) | ((int)(s > es) & (int)(cc > mg)));
-}
-
 // Lane masks of the cull are produced by the compares themselves (inline asm, one VALU instruction each, result in
 // an SGPR pair, zero for inactive lanes), combined on the scalar unit and pushed into the accumulator with
 // s_cmp + s_addc:  acc = 2 acc + (some live lane holds no certificate).  Going through bool and a ballot instead
@@ -536,10 +492,11 @@ __device__ __forceinline__ unsigned long long cull_mask_t(const Lds &lds, int S,
     return mask;
 }
 
+// dir: the float32 direction the certificates read — float32(R), or float32(d) of a wave inside the unit window (rt_cull.h)
 __device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, int anchor, int k0, int n,
-                                                        const V3 &o, const V3 &R, float extent2, int self)
+                                                        const V3 &o, const F3 &dir, float extent2, int self)
 {
-    RayF q = make_rayf_dir(R);
+    RayF q = make_rayf_dir(dir);
     if (anchor >= 0) {
         const bool cand = self >= k0 && self < k0 + n;                        // per lane
         if (__builtin_amdgcn_ballot_w64(cand) != 0ull) {                                         // only shadow rays leaving a sphere
@@ -553,6 +510,12 @@ __device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, i
     }
     add_origin(q, o, extent2);
     return cull_mask_t<false, false>(lds, S, anchor, k0, n, q, -1);
+}
+
+__device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, int anchor, int k0, int n,
+                                                        const V3 &o, const V3 &R, float extent2, int self)
+{
+    return cull_mask(lds, S, anchor, k0, n, o, cull_dir32(R), extent2, self);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -931,6 +894,81 @@ __device__ __forceinline__ bool lanes_any(const Lds &lds, const KParams &p, int 
     return occ;
 }
 
+// The sphere part of a wave-uniform scene query whose float64 direction is DEFERRED (rt_cull.h has the guard and the bound): the
+// caller has formed e = |d|² - 1 and the wave's window ballot, and calls one of two instantiations under that wave-uniform branch.
+//   IN_WINDOW: every live lane has |e| < UNIT_WINDOW.  The cull reads float32(d); R = renormalize_unit_fast(d, e) — the very call
+//              renormalize_unit would have made — a = R.R (and the shadow query's a_sane) are formed under the wave-uniform `if (mask)`
+//              of a chunk, in front of its first float64 test, and live in that block only (carried round the chunk loop they cost
+//              the headline kernel scratch; a scene above 64 spheres forms them once per chunk with an open sphere: the same values).
+//              A query whose cull leaves no sphere never forms them.
+//   otherwise: the former order, R = normalize3_generic(d) first and the cull on float32(R).
+// Two bodies and not one with selects: `in_window ? renormalize_unit_fast(d, e) : normalize3_generic(d)` compiles to six to twelve
+// v_cndmask per query in the path every query takes, more than the deferral saves.
+// closest_spheres returns R.R for the query's one division (read only with bidx >= 0, which implies an open chunk).
+// A value made opaque where it stands: what is computed from the result stays behind this point.  R is the same in every chunk,
+// so the compiler otherwise moves it (and a, and a_sane) out of the chunk loop as loop-invariant — to in front of the cull.
+__device__ __forceinline__ double pinned_here(double x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+template <bool F32, bool IN_WINDOW>
+__device__ __forceinline__ double closest_spheres(const Lds &lds, const KParams &p, int S, int canchor, const V3 &o, const V3 &d, double e,
+                                                  double &bestn, int &bidx)
+{
+    double a = 1.0;
+    V3 Rg{0.0, 0.0, 0.0};
+    if constexpr (!IN_WINDOW) { Rg = normalize3_generic(d); a = dot3(Rg, Rg); }
+    for (int k0 = 0; k0 < S; k0 += 64) {
+      const int n = (S - k0 < 64) ? S - k0 : 64;
+      // the float32 ray is rebuilt per chunk so that it is not live during the float64 phase
+      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, -1);
+      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);       // padding slots certify themselves, except to a NaN ray
+      RT_MARK(1);
+      if (mask) {
+        V3 R = Rg;
+        if constexpr (IN_WINDOW) { R = renormalize_unit_fast(d, pinned_here(e)); a = dot3(R, R); }
+        do {                                                  // spheres some live lane might hit, ascending
+          const int k = k0 + __builtin_ctzll(mask);
+          mask &= mask - 1ull;
+          sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
+        } while (mask);
+      }
+      RT_MARK(2);
+    }
+    return a;
+}
+// any_hit_masks' sphere loop the same way: the lanes some sphere occludes.
+template <bool IN_WINDOW>
+__device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KParams &p, int S, int canchor, const V3 &o, const V3 &d, double e,
+                                                      int self, lanemask live)
+{
+    lanemask occ = 0ull;
+    V3 Rg{0.0, 0.0, 0.0};
+    if constexpr (!IN_WINDOW) Rg = normalize3_generic(d);
+    for (int k0 = 0; k0 < S; k0 += 64) {
+      if (k0 > 0 && (live & ~occ) == 0ull) break;
+      const int n = (S - k0 < 64) ? S - k0 : 64;
+      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, self);
+      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);
+      RT_MARK(7);
+      if (mask) {
+        V3 R = Rg;
+        if constexpr (IN_WINDOW) R = renormalize_unit_fast(d, pinned_here(e));
+        const double a = dot3(R, R);
+        const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
+        do {
+          const int k = k0 + __builtin_ctzll(mask);
+          mask &= mask - 1ull;
+          occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
+          if (mask && (live & ~occ) == 0ull) break;
+        } while (mask);
+      }
+      RT_MARK(8);
+    }
+    return occ;
+}
+
 // trace.py:7-41, closest hit.  R = normalize(d) and a = R.R are computed once per query.
 // anchor: index into the cull table of a point every live lane's ray passes through (0 = camera),
 // or -1 for rays with no common anchor (reflections).
@@ -940,13 +978,23 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
 {
     const int P = opaque(p.P);
     const int S = p.S;
+    // Lds::defer: R and a are formed in front of the first float64 sphere test, not in front of the cull (closest_spheres).
+    constexpr bool F32 = MODE >= 1;                           // sphere records: the float32 LDS table (see sphere_hot)
+    double bestn = __builtin_inf();
+    int bidx = -1;
+    double aq;                                                // R.R, for the one division below
+    if (MODE < 2 && lds.defer) {
+        const double e = unit_excess(d);
+        const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
+        RT_MARK(0);
+        const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
+        if (in_window) aq = closest_spheres<F32, true>(lds, p, S, canchor, o, d, e, bestn, bidx);
+        else aq = closest_spheres<F32, false>(lds, p, S, canchor, o, d, e, bestn, bidx);
+    } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(0);
     const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-    double bestn = __builtin_inf();
-    int bidx = -1;
-    constexpr bool F32 = MODE >= 1;                           // sphere records: the float32 LDS table (see sphere_hot)
     // lane-owned traversal for the rays without a common anchor (bounce 1 on), where the wave's rays have parted;
     // the primary rays of a tile travel together: the wave-uniform cull below is cheaper for them
     if (MODE >= 2 && lds.NC > 0 && (canchor < 0 || p.lanes_primary)) {
@@ -966,10 +1014,12 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
       }
       RT_MARK(2);
     }
+    aq = a;
+    }
     double best = 999.0;                                      // trace.py:17
     int idx = -1, type = HIT_NONE;
     if (bidx >= 0) {
-        const double t = div_inrange(bestn, a);               // :31 / :36, once per query
+        const double t = div_inrange(bestn, aq);              // :31 / :36, once per query
         if (best > t && t > 0.0) { best = t; idx = bidx; type = HIT_SPHERE; }
     }
     const double *pl = lds.recs() + (F32 ? 0 : opaque(p.S) * SPH_STRIDE);
@@ -994,13 +1044,22 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
 {
     const int P = opaque(p.P);
     const int S = p.S;
+    const lanemask live = lanes_where(true);
+    lanemask occ;
+    if (RT_DEFER_SHADOW != 0 && lds.defer) {   // R, a and a_sane in front of the first float64 test, not in front of the cull (any_spheres_masks)
+        const double e = unit_excess(d);
+        const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
+        RT_MARK(6);
+        const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
+        if (in_window) occ = any_spheres_masks<true>(lds, p, S, canchor, o, d, e, self, live);
+        else occ = any_spheres_masks<false>(lds, p, S, canchor, o, d, e, self, live);
+    } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(6);
     const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-    const lanemask live = lanes_where(true);
     const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
-    lanemask occ = 0ull;
+    occ = 0ull;
     for (int k0 = 0; k0 < S; k0 += 64) {
       if (k0 > 0 && (live & ~occ) == 0ull) break;
       const int n = (S - k0 < 64) ? S - k0 : 64;
@@ -1014,6 +1073,7 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
         if (mask && (live & ~occ) == 0ull) break;
       }
       RT_MARK(8);
+    }
     }
     const double *pl = lds.recs() + opaque(p.S) * SPH_STRIDE;
     for (int k = 0; k < P; ++k) {
@@ -1876,11 +1936,11 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     // NC a constant 0 there, none of the cluster code is compiled into those kernels (the headline kernel sits in a narrow
     // register optimum)
 #ifdef RT_REGION_STATS
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, wgstat + 4, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, RT_DEFER_DIRECTION != 0 && MODE < 2 && !(AA && PARK), wgstat + 4, accum};
     for (int i = threadIdx.x & 63; i < 32; i += 64) lds.reg[(threadIdx.x >> 6) * 32 + i] = 0u;
     if ((threadIdx.x & 63) == 0) lds.reg[(threadIdx.x >> 6) * 32 + 31] = (unsigned)__builtin_amdgcn_s_memtime();
 #else
-    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, accum};
+    const Lds lds{sph32, tab, csph32, ctab, cbox, sph32 + tl.gbox, sph32 + tl.gtab, MODE == 1 ? sph32 + tl.col32 : nullptr, WPW == 2 ? 0 : p.NC, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), MODE < 2, MODE >= 2, WPW == 2 && !MAT, RT_DEFER_DIRECTION != 0 && MODE < 2 && !(AA && PARK), accum};
 #endif
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

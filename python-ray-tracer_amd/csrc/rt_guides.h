@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64 * GUIDE_WPW) void guides_kernel(const KParams p,
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const Lds lds{sph32, sph32 + tl.tab, LANES ? nullptr : sph32 + tl.csph32, sph32 + tl.ctab, sph32 + tl.cbox, sph32 + tl.gbox,
-                  sph32 + tl.gtab, nullptr, p.NC, __builtin_amdgcn_readfirstlane(wave), MODE < 2, MODE >= 2, false, nullptr};
+                  sph32 + tl.gtab, nullptr, p.NC, __builtin_amdgcn_readfirstlane(wave), MODE < 2, MODE >= 2, false, RT_DEFER_DIRECTION != 0 && MODE < 2, nullptr};
     const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x * GUIDE_WPW + wave);
     if (tile >= p.ntiles) return;                                             // whole wave, after the barrier
     int tx, ty;
