@@ -7,7 +7,7 @@
                                   [--passes N [--exposure E] [--white W] [--gamma2]]
                                   [--denoise [--denoise-levels N]] [--guides PREFIX]
                                   [--denoise-variance [--kappa K]]
-                                  [--orbit K --temporal [--orbit-step DEG]]
+                                  [--orbit K --temporal [--orbit-step DEG] [--denoise-variance [--spatial-below L]]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -42,7 +42,11 @@ keeps a sum of squares and every pixel's colour tolerance is --kappa standard de
 --orbit K --passes N --temporal renders K camera steps of an orbit about the point the camera looks at (--orbit-step degrees each,
 default 2), N passes per step, and carries the film through every move (rt_film_temporal: the previous mean reprojected through
 the first-hit guides and blended with the new passes); the last frame is written, filtered when --denoise is given.  For example
---sky --soft --shadow-samples 1 --orbit 8 --passes 4 --temporal --denoise --white 400.
+--sky --soft --shadow-samples 1 --orbit 8 --passes 4 --temporal --denoise --white 400.  With --denoise-variance in place of --denoise the
+film carries its second moment through the moves as well (rt_film_temporal_moments) and the temporal mean is filtered with a colour
+tolerance per pixel (rt_film_denoise_variance_temporal): tight where the history survived, wide where the move uncovered something;
+pixels whose history is shorter than --spatial-below passes (default the library's) take their variance from their neighbours, so
+--passes 1 is enough.  For example --sky --soft --shadow-samples 1 --orbit 8 --passes 1 --temporal --denoise-variance --white 400.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -89,6 +93,8 @@ def main():
     ap.add_argument("--denoise-levels", type=int, default=4, metavar="N", help="--denoise: filter iterations, 0..6")
     ap.add_argument("--denoise-variance", action="store_true", help="filter the film's mean with the variance-guided denoiser (four passes unless --passes)")
     ap.add_argument("--kappa", type=float, default=None, metavar="K", help="--denoise-variance: colour tolerance in standard deviations of the mean")
+    ap.add_argument("--spatial-below", type=float, default=None, metavar="L",
+                    help="--temporal --denoise-variance: pixels with a history shorter than L passes take their variance from their neighbours")
     ap.add_argument("--guides", default=None, metavar="PREFIX", help="write the first-hit guides as PREFIX_normal/_depth/_albedo/_id.png")
     ap.add_argument("--orbit", type=int, default=0, metavar="K", help="--temporal: render K camera steps of an orbit and write the last frame")
     ap.add_argument("--orbit-step", type=float, default=2.0, metavar="DEG", help="--orbit: degrees per camera step")
@@ -98,10 +104,12 @@ def main():
     w, h = (int(v) for v in a.size.lower().split("x"))
     if (a.denoise or a.temporal or a.denoise_variance) and a.passes <= 0:
         a.passes = 4
-    if a.denoise_variance and (a.denoise or a.temporal):
-        ap.error("--denoise-variance stands in place of --denoise and does not take a temporal mean")
-    if a.denoise_variance and a.passes < 2:
-        ap.error("--denoise-variance needs at least two passes")
+    if a.denoise_variance and a.denoise:
+        ap.error("--denoise-variance stands in place of --denoise")
+    if a.denoise_variance and a.passes < 2 and not a.temporal:
+        ap.error("--denoise-variance needs at least two passes, or --temporal")
+    if a.spatial_below is not None and not (a.temporal and a.denoise_variance):
+        ap.error("--spatial-below goes with --temporal --denoise-variance")
     if a.temporal and a.orbit < 1:
         a.orbit = 8
     if a.orbit > 0 and not a.temporal:
@@ -182,7 +190,8 @@ def main():
             start = (np.asarray(cam.position, np.float64), np.asarray(cam.rotation, np.float64))
             pivot = start[0] + 4.0 * start[1][:, 0]             # a point the camera looks at
             tone = dict(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags)
-            with pkg.Film(r) as film:
+            var_kw = {**({} if a.kappa is None else dict(kappa=a.kappa)), **({} if a.spatial_below is None else dict(spatial_below=a.spatial_below))}
+            with pkg.Film(r, moments=a.denoise_variance) as film:
                 r.timer_begin()
                 for k in range(a.orbit):
                     r.set_camera(*orbit(start, pivot, a.orbit_step * k))
@@ -192,8 +201,10 @@ def main():
                     film.temporal()
                     if a.denoise:
                         film.denoise(levels=a.denoise_levels, temporal=True)
+                    if a.denoise_variance:
+                        film.denoise(variance=True, temporal=True, levels=a.denoise_levels, **var_kw)
                 ms = r.timer_end() / (a.orbit * a.passes)
-                image = film.resolve(denoised=a.denoise, temporal=True, **tone)[0]
+                image = film.resolve(denoised=a.denoise or a.denoise_variance, temporal=True, **tone)[0]
         elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
             with pkg.Film(r, moments=a.denoise_variance) as film:
                 film.accumulate(p, a.passes)

@@ -737,8 +737,9 @@ int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t
  * identical passes), only taps of exactly the centre's colour are mixed in.  No exp(), no pow(), no sqrt: the bytes do not depend on
  * a math library.  A non-finite sum, sum of squares or guide gives unspecified values but does not fault: every tap index is
  * range-checked before it is read.  Taps do not cross the edge of the buffer, so a multi-rank caller denoises the assembled frame.
- * A temporal mean (rt_film_temporal) has no second moment: carrying one through the history is out of scope, and this filter takes a
- * film's own sum and sum of squares only.
+ * A temporal mean (rt_film_temporal) has no second moment of its own, and this filter takes a film's own sum and sum of squares only:
+ * rt_film_temporal_moments carries a second moment through the history beside the mean, and rt_film_denoise_variance_temporal
+ * filters what it wrote (below).
  * RT_ERR_BAD_ARG as rt_film_denoise (NULL d_sum, d_guides, dv or d_out; levels; normal_shin; demodulate; ws, h), and for d_sq NULL;
  * n < 2; a kappa or var_floor that is not finite or is negative; a prefilter that is not 0 or 1; any of the five strides < ws*h
  * (work_stride counts when d_work is given); d_work == NULL with levels >= 1; equal buffers among d_out, d_work and any input.  The
@@ -761,6 +762,57 @@ int rt_film_denoise_variance(rt_ctx *ctx, const void *d_sum, int64_t sum_stride,
                              int ws, int h, int64_t n, const void *d_guides, int64_t guide_stride,
                              const rt_denoise_variance *dv, void *d_out, int64_t out_stride,
                              void *d_work, int64_t work_stride, void *stream);
+
+/* The two together: a second moment carried through the history, and the variance-guided filter on the temporal mean, so that a moving
+ * camera's frame of 1 to 4 passes gets a colour tolerance per pixel (tight where the history survived, wide at a disocclusion) instead
+ * of one global sigma.  RT_ABI_VERSION is unchanged: callers detect these two entry points by their symbols.
+ *
+ * rt_film_temporal_moments: rt_film_temporal with three more buffers.  Every line of rt_film_temporal holds, in the same order; d_out
+ * and d_out_len receive the same bits as rt_film_temporal on the same inputs.  d_sq is the frame's sum of squares
+ * (rt_film_accumulate_moments); d_hist_sq the history's MEAN of squares (float64, 3 planes); d_out_sq receives the new mean of squares:
+ * the next call's d_hist_sq.  Per pixel, float64, no fused multiply-add:
+ *   fresh:                         out_sq[k][e] = sq[k][e] / (double)n
+ *   in the tap loop, after H_k:    Q_k = Q_k + bw * hist_sq[k][q]
+ *   after hm_k:                    hq_k = Q_k / W
+ *                                  out_sq[k][e] = (L * hq_k + sq[k][e]) / (L + (double)n)
+ * With max_history == 0 it writes sum / n, sq / n and the length n.  Every error rt_film_temporal raises, with the same statuses;
+ * RT_ERR_BAD_ARG for a NULL d_sq, d_hist_sq or d_out_sq, for sq_stride, hist_sq_stride or out_sq_stride < w*h, and for d_out_sq equal
+ * to any other buffer (d_out or d_out_len equal to d_sq or d_hist_sq is refused as well).  The outputs are then untouched. */
+int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int64_t n,
+                             const void *d_guides, int64_t guide_stride,
+                             const void *d_hist, int64_t hist_stride, const void *d_hist_sq, int64_t hist_sq_stride, const void *d_hist_len,
+                             const void *d_hist_guides, int64_t hist_guide_stride, const rt_temporal *tp,
+                             void *d_out, int64_t out_stride, void *d_out_sq, int64_t out_sq_stride, void *d_out_len, void *stream);
+
+/* rt_film_denoise_variance_temporal: rt_film_denoise_variance on what rt_film_temporal_moments wrote.  d_mean is the mean (float64, 3
+ * planes), d_msq the mean of squares (3 planes), d_len the per-pixel length (float32, one plane of ws*h).  Only the prepare pass
+ * differs: the levels, the plan of which buffer gets which write, d_out and d_work (four planes each) are rt_film_denoise_variance's.
+ * Per pixel p, float64, no fused multiply-add, in this order:
+ *   Lp = (double)len[p];   m_c = mean[c][p]
+ *   Lp >= spatial_below  (own):
+ *       r_c = msq[c][p] - m_c*m_c;  r_c > 0 ? r_c : 0 (NaN: 0)
+ *       Lp > 1:  var_c = r_c / (Lp - 1.0)        else:  var_c = 0
+ *   else  (pooled; a NaN length lands here):
+ *       SL = M_c = Q_c = +0.0
+ *       for dx = -2..2 (outer), dy = -2..2 (inner), step 1:   q = (p.x+dx, p.y+dy)
+ *           q outside the frame, or id[q] != id[p]:  skip
+ *           lq = (double)len[q];   !(lq > 0):  skip
+ *           SL = SL + lq;   M_c = M_c + lq * mean[c][q];   Q_c = Q_c + lq * msq[c][q]
+ *       !(SL > 1) or !(Lp > 0):  var_c = 0
+ *       else:  pm = M_c / SL;   r_c = Q_c / SL - pm*pm  (clamped as above);   var_c = (r_c / (SL - 1.0)) * (SL / Lp)
+ *   demodulate, v_0, levels == 0 (out = mean, out[3] = v_0 without demodulation), the levels and the output:
+ *       exactly rt_film_denoise_variance's lines
+ * The pooled path is for a disocclusion: a pixel with 1 to 3 passes has no usable variance of its own, so it takes the spread of its
+ * object's neighbours, weighted by how many passes each stands for, scaled from "one sample" to "a mean of Lp samples".  The own path
+ * makes a frame of fresh pixels (len == (float)n, mean == s/n, msq == sq/n) rt_film_denoise_variance's filter bit for bit: then
+ * Lp - 1.0 == (double)(n - 1).  spatial_below = 0 pools nowhere.
+ * RT_ERR_BAD_ARG as rt_film_denoise_variance (no n exists), and for a NULL d_msq or d_len; a spatial_below that is not finite or is
+ * negative; a stride < ws*h; equal buffers among d_out, d_work and any input.  The outputs are then untouched.  Every index is
+ * range-checked before it is read: non-finite inputs give unspecified values and do not fault.  Asynchronous on `stream`. */
+int rt_film_denoise_variance_temporal(rt_ctx *ctx, const void *d_mean, int64_t mean_stride, const void *d_msq, int64_t msq_stride,
+                                      const void *d_len, int ws, int h, const void *d_guides, int64_t guide_stride,
+                                      const rt_denoise_variance *dv, double spatial_below,
+                                      void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
 
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the

@@ -121,6 +121,10 @@ PROTOTYPES = {
     "rt_film_accumulate_moments": (C.c_int, [_vp, C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "rt_film_denoise_variance": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64,
                                            C.POINTER(rt_denoise_variance), _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "rt_film_temporal_moments": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp,
+                                           C.c_int64, C.POINTER(rt_temporal), _vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "rt_film_denoise_variance_temporal": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, C.c_int64,
+                                                    C.POINTER(rt_denoise_variance), C.c_double, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -142,7 +146,8 @@ PROTOTYPES = {
 
 # Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
 # times such a build beside this one), and Renderer raises where one is called.
-LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance")
+LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance",
+                 "rt_film_temporal_moments", "rt_film_denoise_variance_temporal")
 
 _lib = None
 

@@ -1067,6 +1067,135 @@ int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t
     return RT_OK;
 }
 
+// rt_film_temporal with the second moment beside the mean: the same checks in the same order, then what the three new buffers add;
+// one launch of temporal_moments_kernel (rt_temporal.h), a kernel of its own so that temporal_kernel stays what it was.
+int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int64_t n,
+                             const void *d_guides, int64_t guide_stride, const void *d_hist, int64_t hist_stride, const void *d_hist_sq,
+                             int64_t hist_sq_stride, const void *d_hist_len, const void *d_hist_guides, int64_t hist_guide_stride,
+                             const rt_temporal *tp, void *d_out, int64_t out_stride, void *d_out_sq, int64_t out_sq_stride, void *d_out_len,
+                             void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_sum || !d_guides || !d_hist || !d_hist_len || !d_hist_guides || !d_out || !d_out_len)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a buffer is NULL");
+    if (!tp) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: tp is NULL");
+    if (n < 1 || n > (1 << 24)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: n outside 1..2^24");
+    if (!(std::isfinite(tp->depth_tol) && tp->depth_tol >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: depth_tol must be finite and >= 0");
+    if (!(tp->normal_cos >= -1.0 && tp->normal_cos <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: normal_cos outside [-1, 1]");
+    if (!(std::isfinite(tp->max_history) && tp->max_history >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: max_history must be finite and >= 0");
+    if (tp->reserved[0] != 0 || tp->reserved[1] != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: reserved must be 0");
+    const rt::View &v = ctx->view;
+    if (!v.have_cam) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: rt_set_camera has not been called");
+    if (!v.have_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: rt_set_raygen has not been called");
+    if (v.explicit_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: an explicit rt_set_pixel_loc grid cannot be reprojected");
+    if (v.dy == 0.0 || v.dz == 0.0) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: the grid's dy or dz is 0");
+    bool finite = true;
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(v.cam_o[i]) && std::isfinite(tp->prev_origin[i]);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v.cam_R[i]) && std::isfinite(tp->prev_rotation[i]);
+    if (!finite) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a camera entry is not finite");
+    const long long npx = (long long)v.w * v.h;
+    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: w*h above RT_FILM_MAX_PIXELS");
+    if (sum_stride < npx || guide_stride < npx || hist_stride < npx || hist_guide_stride < npx || out_stride < npx)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a plane stride is smaller than the frame");
+    const void *const ins[] = {d_sum, d_guides, d_hist, d_hist_len, d_hist_guides};
+    for (const void *in : ins)
+        if (d_out == in || d_out_len == in) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
+    if (d_out == d_out_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
+    if (!d_sq || !d_hist_sq || !d_out_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_sq, d_hist_sq or d_out_sq is NULL");
+    if (sq_stride < npx || hist_sq_stride < npx || out_sq_stride < npx)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a plane stride of the second moment is smaller than the frame");
+    const void *const others[] = {d_sum, d_sq, d_guides, d_hist, d_hist_sq, d_hist_len, d_hist_guides, d_out, d_out_len};
+    for (const void *o : others)
+        if (d_out_sq == o) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out_sq must be a buffer of its own");
+    if (d_out == d_sq || d_out == d_hist_sq || d_out_len == d_sq || d_out_len == d_hist_sq)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rt::TemporalMomentsArgs m;
+    rt::TemporalArgs &a = m.t;
+    a.sum = (const double *)d_sum; a.guides = (const float *)d_guides; a.hist = (const double *)d_hist;
+    a.hist_len = (const float *)d_hist_len; a.hist_guides = (const float *)d_hist_guides;
+    a.out = (double *)d_out; a.out_len = (float *)d_out_len;
+    a.sum_stride = sum_stride; a.guide_stride = guide_stride; a.hist_stride = hist_stride; a.hist_guide_stride = hist_guide_stride;
+    a.out_stride = out_stride;
+    a.w = v.w; a.h = v.h; a.n = (double)n;
+    a.px = v.px; a.y0 = v.y0; a.dy = v.dy; a.z0 = v.z0; a.dz = v.dz;
+    std::memcpy(a.o, v.cam_o, sizeof a.o); std::memcpy(a.R, v.cam_R, sizeof a.R);
+    std::memcpy(a.po, tp->prev_origin, sizeof a.po); std::memcpy(a.pR, tp->prev_rotation, sizeof a.pR);
+    a.depth_tol = tp->depth_tol; a.normal_cos = tp->normal_cos; a.max_history = tp->max_history;
+    m.sq = (const double *)d_sq; m.hist_sq = (const double *)d_hist_sq; m.out_sq = (double *)d_out_sq;
+    m.sq_stride = sq_stride; m.hist_sq_stride = hist_sq_stride; m.out_sq_stride = out_sq_stride;
+    hipLaunchKernelGGL(rt::temporal_moments_kernel, dim3(rt::temporal_grid(npx, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
+                       stream_of(ctx, stream), m);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// The variance-guided filter on a temporal mean: the prepare launch takes each pixel's variance from its own moments or, where its
+// history is shorter than spatial_below, from its object's neighbours (rt_denoise_var.h: denoise_var_prepare_len_kernel); the levels
+// are rt_film_denoise_variance's launches, with its plan of which buffer gets which write.
+int rt_film_denoise_variance_temporal(rt_ctx *ctx, const void *d_mean, int64_t mean_stride, const void *d_msq, int64_t msq_stride,
+                                      const void *d_len, int ws, int h, const void *d_guides, int64_t guide_stride,
+                                      const rt_denoise_variance *dv, double spatial_below, void *d_out, int64_t out_stride, void *d_work,
+                                      int64_t work_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_mean) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_mean is NULL");
+    if (!d_msq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_msq is NULL");
+    if (!d_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_len is NULL");
+    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_guides is NULL");
+    if (!dv) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: dv is NULL");
+    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out is NULL");
+    if (dv->levels < 0 || dv->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: levels outside 0..6");
+    int nsq = -1;
+    for (int i = 0; i <= 10; ++i) if (dv->normal_shin == (1 << i)) nsq = i;
+    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: normal_shin must be 1, 2, 4, ..., 1024");
+    if (!(std::isfinite(dv->kappa) && dv->kappa >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: kappa must be finite and >= 0");
+    if (!(std::isfinite(dv->var_floor) && dv->var_floor >= 0.0))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: var_floor must be finite and >= 0");
+    if (dv->demodulate != 0 && dv->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: demodulate must be 0 or 1");
+    if (dv->prefilter != 0 && dv->prefilter != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: prefilter must be 0 or 1");
+    if (!(std::isfinite(spatial_below) && spatial_below >= 0.0))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: spatial_below must be finite and >= 0");
+    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: ws*h outside 1..RT_FILM_MAX_PIXELS");
+    const long long npx = (long long)ws * h;
+    if (mean_stride < npx || msq_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
+        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: a plane stride is smaller than the frame");
+    if (!d_work && dv->levels >= 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_work is NULL with levels >= 1");
+    for (const void *in : {d_mean, d_msq, d_len, d_guides})
+        if (d_out == in || (d_work && d_work == in))
+            return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out and d_work must be buffers of their own");
+    if (d_work && d_work == d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out and d_work must be buffers of their own");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_of(ctx, stream);
+    const int levels = dv->levels;
+    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
+    const bool first_to_out = rt::denoise_var_to_out(levels, 0);
+    rt::DenoiseVarLenArgs p;
+    std::memset(&p, 0, sizeof p);
+    p.mean = (const double *)d_mean; p.mean_stride = mean_stride; p.msq = (const double *)d_msq; p.msq_stride = msq_stride;
+    p.len = (const float *)d_len; p.guides = (const float *)d_guides; p.guide_stride = guide_stride;
+    p.dst = (double *)(first_to_out ? d_out : d_work); p.dst_stride = first_to_out ? out_stride : work_stride;
+    p.ws = ws; p.h = h; p.demod = dv->demodulate; p.copy = levels == 0; p.spatial_below = spatial_below;
+    hipLaunchKernelGGL(rt::denoise_var_prepare_len_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, p);
+    RT_HIP(ctx, hipGetLastError());
+    rt::DenoiseVarArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
+    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dv->demodulate; a.prefilter = dv->prefilter;
+    a.k2 = dv->kappa * dv->kappa; a.var_floor = dv->var_floor;
+    a.src = p.dst; a.src_stride = p.dst_stride;
+    for (int k = 1; k <= levels; ++k) {
+        const bool to_out = rt::denoise_var_to_out(levels, k);
+        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
+        rt::denoise_var_level(a, levels, k - 1);
+        hipLaunchKernelGGL(rt::denoise_var_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
+        RT_HIP(ctx, hipGetLastError());
+        a.src = a.dst; a.src_stride = a.dst_stride;
+    }
+    return RT_OK;
+}
+
 // The staging planes grown where the frame is larger than any before, one launch into them and one copy per output to host memory,
 // all queued on `stream`.
 static int render_staged(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out_u8, float *out_f32, Buf &u8, Buf &f32,

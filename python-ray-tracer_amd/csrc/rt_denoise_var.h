@@ -9,6 +9,12 @@
 // exp(), pow() or sqrt.  The kernels (hipcc only) are shaped like denoise_kernel: one thread per pixel, consecutive threads consecutive
 // y, a grid capped near 8 blocks per CU with a grid-stride loop, one launch per level, taps gathered through the caches; 8- and 4-byte
 // accesses, so any plane stride will do; no LDS, no scratch, 64-bit plane offsets.
+// rt_film_denoise_variance_temporal filters what rt_film_temporal_moments wrote (a mean, a mean of squares and a length per pixel) and
+// only its prepare pass is new (denoise_var_prepare_len_pixel, denoise_var_prepare_len_kernel, with the argument struct DenoiseVarLenArgs
+// of their own): a pixel whose length reaches spatial_below takes the variance of its own moments, a shorter one pools the moments of
+// the 5x5 pixels of its object around it.  Only lanes whose length is short walk the 25 taps; a wave with one such lane pays the whole
+// loop once (25 iterations of an id load, a length load and, where both pass, six 8-byte loads, executed for the short lanes with the
+// others masked off), a wave without one pays the compare and a branch.  The levels are denoise_var_kernel's, unchanged.
 #pragma once
 #include <cstdint>
 
@@ -78,6 +84,75 @@ RT_DN_HD inline void denoise_var_prepare_pixel(const DenoiseVarArgs &a, long lon
         v[c] = var;
     }
     a.dst[3 * a.dst_stride + e] = (v[0] + v[1]) + v[2];
+}
+
+// The prepare pass of rt_film_denoise_variance_temporal over a ws x h frame: (mean, msq, len) -> dst, four planes.
+struct DenoiseVarLenArgs {
+    const double *mean, *msq;    // the temporal mean and mean of squares, three planes each
+    const float *len;            // the length plane
+    const float *guides;
+    double *dst;
+    long long mean_stride, msq_stride, guide_stride, dst_stride;
+    int ws, h;
+    int demod;
+    int copy;                    // levels == 0: dst = (mean, v_0 without demodulation)
+    double spatial_below;
+};
+
+// Pixel (x, y) of that prepare pass: (m_0, v_0) from the pixel's own moments where its length reaches spatial_below, else from the
+// moments of its object's pixels in the 5x5 window, weighted by their lengths.
+RT_DN_HD inline void denoise_var_prepare_len_pixel(const DenoiseVarLenArgs &a, int x, int y)
+{
+    const long long e = (long long)x * a.h + y;
+    const bool demod = a.demod && !a.copy;
+    const double Lp = (double)a.len[e];
+    double m[3] = {a.mean[e], a.mean[a.mean_stride + e], a.mean[2 * a.mean_stride + e]};
+    double var[3] = {0.0, 0.0, 0.0};
+    if (Lp >= a.spatial_below) {                                                      // own
+        for (int c = 0; c < 3; ++c) {
+            const double r = denoise_var_pos(a.msq[c * a.msq_stride + e] - m[c] * m[c]);
+            var[c] = Lp > 1.0 ? r / (Lp - 1.0) : 0.0;
+        }
+    } else {                                                                          // pooled (a NaN length lands here)
+        const float *const ids = a.guides + 7 * a.guide_stride;
+        const float idp = ids[e];
+        double SL = 0.0, M[3] = {0.0, 0.0, 0.0}, Q[3] = {0.0, 0.0, 0.0};
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= a.ws) continue;
+            for (int dy = -2; dy <= 2; ++dy) {
+                const int qy = y + dy;
+                if (qy < 0 || qy >= a.h) continue;
+                const long long eq = (long long)qx * a.h + qy;
+                if (ids[eq] != idp) continue;
+                const double lq = (double)a.len[eq];
+                if (!(lq > 0.0)) continue;
+                SL = SL + lq;
+                for (int c = 0; c < 3; ++c) {
+                    M[c] = M[c] + lq * a.mean[c * a.mean_stride + eq];
+                    Q[c] = Q[c] + lq * a.msq[c * a.msq_stride + eq];
+                }
+            }
+        }
+        if (SL > 1.0 && Lp > 0.0)
+            for (int c = 0; c < 3; ++c) {
+                const double pm = M[c] / SL;
+                const double r = denoise_var_pos(Q[c] / SL - pm * pm);
+                var[c] = (r / (SL - 1.0)) * (SL / Lp);
+            }
+    }
+    for (int c = 0; c < 3; ++c) {
+        if (demod) {
+            const double al = denoise_albedo(a.guides[(4 + c) * a.guide_stride + e]);
+            m[c] = m[c] / al;
+            var[c] = var[c] / (al * al);
+        }
+        a.dst[c * a.dst_stride + e] = m[c];
+    }
+    a.dst[3 * a.dst_stride + e] = (var[0] + var[1]) + var[2];
 }
 
 // Pixel (x, y) of one level, written to dst.
@@ -153,6 +228,15 @@ __global__ __launch_bounds__(DENOISE_THREADS) void denoise_var_prepare_kernel(co
 {
     const unsigned npx = (unsigned)a.ws * (unsigned)a.h, step = gridDim.x * DENOISE_THREADS;
     for (unsigned e = blockIdx.x * DENOISE_THREADS + threadIdx.x; e < npx; e += step) denoise_var_prepare_pixel(a, (long long)e);
+}
+
+__global__ __launch_bounds__(DENOISE_THREADS) void denoise_var_prepare_len_kernel(const DenoiseVarLenArgs a)
+{
+    const unsigned npx = (unsigned)a.ws * (unsigned)a.h, step = gridDim.x * DENOISE_THREADS;
+    for (unsigned e = blockIdx.x * DENOISE_THREADS + threadIdx.x; e < npx; e += step) {
+        const unsigned x = e / (unsigned)a.h;
+        denoise_var_prepare_len_pixel(a, (int)x, (int)(e - x * (unsigned)a.h));
+    }
 }
 
 __global__ __launch_bounds__(DENOISE_THREADS) void denoise_var_kernel(const DenoiseVarArgs a)

@@ -32,13 +32,26 @@ every pixel's colour tolerance from the variance of its mean (rt_film_denoise_va
         film.denoise(variance=True)                   # no sigma to tune: the filter fades out as the film converges
         image, _ = film.resolve(white=400.0, denoised=True)
         noise = film.variance()                       # float64 (ws, h): the estimated variance of the mean, to stop refining on
+
+On a film with moments, next_frame and temporal carry the second moment through the history beside the mean
+(rt_film_temporal_moments), and denoise(variance=True, temporal=True) filters the temporal mean with a tolerance per pixel: tight
+where the history survived, wide at a disocclusion (rt_film_denoise_variance_temporal).  One pass per frame is enough:
+
+    with Film(renderer, moments=True) as film:
+        for camera in orbit:
+            renderer.set_camera(*camera)
+            film.next_frame()
+            film.accumulate(params, passes=1)
+            film.temporal()
+            film.denoise(variance=True, temporal=True)
+            image, _ = film.resolve(white=400.0, denoised=True, temporal=True)
 """
 import numpy as np
 
 from . import _lib as L
 from .denoise import check_denoise
 from .temporal import DEPTH_TOL, MAX_HISTORY, NORMAL_COS, check_temporal
-from .variance import KAPPA, VAR_PLANES, check_denoise_variance
+from .variance import KAPPA, SPATIAL_BELOW, VAR_PLANES, check_denoise_variance, check_spatial_below
 
 # Film.denoise's default sigma, in the units the filter sees: colour / albedo with demodulation, so about 0..1 and not 0..255.  The
 # best of the sweep 1/32, 1/16, 1/8, 1/4, 1/2 at levels 4, normal_shininess 32 with demodulation on four passes of the
@@ -143,6 +156,7 @@ class Film:
         # temporal accumulation: allocated by next_frame() and temporal()
         self.d_temporal = self.d_temporal_len = None              # the temporal mean of the current passes and its length plane
         self.d_hist = self.d_hist_len = self.d_hist_guides = None  # the previous frame's mean, lengths and guides
+        self.d_temporal_sq = self.d_hist_sq = None                # with moments: the mean of squares beside d_temporal and d_hist
         self.temporal_passes = 0                                  # the pass count the mean in d_temporal belongs to (0: none)
         self.history_camera = None                                # (origin, rotation) the history was rendered with (None: no history)
         self.guides_camera = None                                 # the camera d_guides was last rendered with by this film
@@ -152,7 +166,7 @@ class Film:
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
-        names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_hist", "d_hist_len", "d_hist_guides", "d_guides",
+        names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_temporal_sq", "d_hist", "d_hist_len", "d_hist_sq", "d_hist_guides", "d_guides",
                  "d_denoised", "d_work")
         extra = [getattr(self, n, None) for n in names]
         for n in names:
@@ -228,7 +242,7 @@ class Film:
         self.guides_stale = False
 
     def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None, temporal=False, variance=False,
-                kappa=KAPPA, var_floor=0.0, prefilter=True):
+                kappa=KAPPA, var_floor=0.0, prefilter=True, spatial_below=SPATIAL_BELOW):
         """Filter the mean of the passes so far (Renderer.film_denoise: an edge-stopping a-trous filter guided by guides(), which is
         called first if it has not been) into the film's own buffers; resolve(denoised=True) shows the result.  levels 0..6,
         normal_shininess 1, 2, 4, ..., 1024, sigma 0 (no colour weight) or > 0 in colour units, demodulate: filter colour / albedo.
@@ -240,11 +254,14 @@ class Film:
         variance: the variance-guided filter instead (Renderer.film_denoise_variance), on a film made with moments=True that holds
         at least two passes: sigma is not used; a tap's colour tolerance is kappa standard deviations of the pixel's mean (KAPPA:
         the choice of the sweep in DESIGN.md, Variance-guided denoiser) plus var_floor, with the variance smoothed over 3 x 3 pixels
-        of the same object when prefilter is set.  It filters into four-plane buffers of the film's own, and cannot take the
-        temporal mean: a temporal mean has no second moment.  Asynchronous."""
+        of the same object when prefilter is set.  It filters into four-plane buffers of the film's own.  With temporal=True it
+        filters the temporal mean with the second moment that temporal() carried through the history
+        (Renderer.film_denoise_variance_temporal): it needs temporal() of the current passes, one pass is enough, and a pixel whose
+        history is shorter than spatial_below passes takes its variance from its object's neighbours in a 5 x 5 window (SPATIAL_BELOW:
+        the choice of the sweep in DESIGN.md, Variance under a history).  Asynchronous."""
         self._live()
         if variance:
-            return self._denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, stream)
+            return self._denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, spatial_below, stream)
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         levels, shin, sigma, demodulate = check_denoise(levels, normal_shininess, sigma, demodulate)
@@ -278,21 +295,46 @@ class Film:
                                             getattr(self, d_work) if d_work else None, levels=levels, normal_shin=shin, kappa=kappa,
                                             var_floor=var_floor, demodulate=demodulate, prefilter=prefilter, stream=stream)
 
-    def _denoise_variance(self, levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, stream):
+    def _variance_temporal_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, spatial_below, stream):
+        """rt_film_denoise_variance_temporal on the temporal mean, its mean of squares and its lengths into d_out (four planes)."""
+        if not self.moments:
+            raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
+        if not self.temporal_passes or self.temporal_passes != self.passes or not self.d_temporal_sq:
+            raise ValueError("the film has no temporal mean of its current passes, and so no second moment of one: call temporal() first")
+        if not self.d_guides or self.guides_stale:
+            self.guides(stream)
+        n = self.ws * self.h
+        for name in (d_out, d_work):
+            if name and not getattr(self, name):
+                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * n))
+        self.renderer.film_denoise_variance_temporal(self.d_temporal, self.d_temporal_sq, self.d_temporal_len, self.ws, self.h, self.d_guides,
+                                                     getattr(self, d_out), getattr(self, d_work) if d_work else None, levels=levels,
+                                                     normal_shin=shin, kappa=kappa, var_floor=var_floor, demodulate=demodulate,
+                                                     prefilter=prefilter, spatial_below=spatial_below, stream=stream)
+
+    def _denoise_variance(self, levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, spatial_below, stream):
         levels, shin, kappa, var_floor, demodulate, prefilter = check_denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter)
+        work = "d_work_var" if levels >= 1 else None
         if temporal:
-            raise ValueError("the variance-guided filter cannot take the temporal mean: a temporal mean has no second moment")
-        self._variance_call("d_denoised_var", "d_work_var" if levels >= 1 else None, levels, shin, kappa, var_floor, demodulate, prefilter, stream)
+            self._variance_temporal_call("d_denoised_var", work, levels, shin, kappa, var_floor, demodulate, prefilter,
+                                         check_spatial_below(spatial_below), stream)
+        else:
+            self._variance_call("d_denoised_var", work, levels, shin, kappa, var_floor, demodulate, prefilter, stream)
         self.denoised_passes = self.passes
-        self.denoised_temporal = False
+        self.denoised_temporal = bool(temporal)
         self.denoised_variance = True
 
-    def variance(self, stream=None):
+    def variance(self, stream=None, temporal=False, spatial_below=SPATIAL_BELOW):
         """The estimated variance of the mean of the passes so far, per pixel, summed over the channels: float64 (ws, h), plane 3 of
         the levels = 0 call of Renderer.film_denoise_variance (into the film's work buffer: a filtered mean stays).  A caller stops
-        refining on it.  It needs a film made with moments=True and two passes.  Waits for the stream."""
+        refining on it.  It needs a film made with moments=True and two passes.  temporal: the variance of the temporal mean instead
+        (the levels = 0 call of Renderer.film_denoise_variance_temporal), after temporal() of the current passes; one pass is enough.
+        Waits for the stream."""
         self._live()
-        self._variance_call("d_work_var", None, 0, 1, 0.0, 0.0, 0, 0, stream)
+        if temporal:
+            self._variance_temporal_call("d_work_var", None, 0, 1, 0.0, 0.0, 0, 0, check_spatial_below(spatial_below), stream)
+        else:
+            self._variance_call("d_work_var", None, 0, 1, 0.0, 0.0, 0, 0, stream)
         r = self.renderer
         r.sync(stream)
         out = np.empty((self.ws, self.h), np.float64)
@@ -321,7 +363,9 @@ class Film:
         """The camera has moved (call this after Renderer.set_camera): the film's latest mean becomes the history, with its length
         plane and its guides, and the passes start again (clear()).  The latest mean is what temporal() wrote for the current
         passes, or sum / passes with length passes if it has not run; the history's camera is the one its guides were rendered
-        with.  A film without a pass keeps the history it has.  Asynchronous."""
+        with.  A film without a pass keeps the history it has.  A film with moments keeps the second moment of the frame that ends
+        as well (the mean of squares, in d_hist_sq): what temporal() wrote, or sq / passes through Renderer.film_temporal_moments.
+        Asynchronous."""
         self._live()
         self._full_frame()
         r, n = self.renderer, self.ws * self.h
@@ -330,14 +374,23 @@ class Film:
         if self.temporal_passes == self.passes:                   # the temporal buffers become the history: a swap
             self.d_hist, self.d_temporal = self.d_temporal, self.d_hist
             self.d_hist_len, self.d_temporal_len = self.d_temporal_len, self.d_hist_len
+            if self.moments:
+                self.d_hist_sq, self.d_temporal_sq = self.d_temporal_sq, self.d_hist_sq
         else:                                                     # the plain mean: a fresh temporal call writes sum / passes and (float)passes
             if self.guides_camera is None:
                 raise ValueError("the film has no guides of the frame that ends: call guides() or temporal() before the camera moves")
             if not self.d_hist:
                 self.d_hist, self.d_hist_len = r.malloc(24 * n), r.malloc(4 * n)
             o, R = self.guides_camera
-            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_hist,
-                            self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
+            if self.moments:                                      # sum / passes, sq / passes and the length passes
+                if not self.d_hist_sq:
+                    self.d_hist_sq = r.malloc(24 * n)
+                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_sum, self.d_sq, self.d_guides, self.d_guides,
+                                        o, R, self.d_hist, self.d_hist_sq, self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0,
+                                        stream=stream)
+            else:
+                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_hist,
+                                self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
         self.d_hist_guides, self.d_guides = self.d_guides, self.d_hist_guides
         self.history_camera, self.guides_camera = self.guides_camera, None
         self.guides_stale = True
@@ -350,7 +403,8 @@ class Film:
         and every pixel of a film without a history, the fresh mean sum / passes.  depth_tol: relative tolerance on the squared
         distance; normal_cos: the least cosine between the pixel's normal and a history tap's.  The defaults are the best of the
         sweep recorded in DESIGN.md (Temporal accumulation).  resolve(temporal=True) and denoise(temporal=True) take the result.
-        Asynchronous."""
+        A film with moments blends the second moment by the same lengths (Renderer.film_temporal_moments) into d_temporal_sq, which
+        denoise(variance=True, temporal=True) takes.  Asynchronous."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
@@ -363,15 +417,26 @@ class Film:
             self._render_guides(stream)
         if not self.d_temporal:
             self.d_temporal, self.d_temporal_len = r.malloc(24 * n), r.malloc(4 * n)
+        if self.moments and not self.d_temporal_sq:
+            self.d_temporal_sq = r.malloc(24 * n)
+        kw = dict(depth_tol=depth_tol, normal_cos=normal_cos, stream=stream)
         if self.history_camera is None:                           # no history: every pixel fresh (the inputs are placeholders)
             o, R = r.camera
-            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_temporal,
-                            self.d_temporal_len, depth_tol=depth_tol, normal_cos=normal_cos, max_history=0.0, stream=stream)
+            if self.moments:
+                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_sum, self.d_sq, self.d_guides, self.d_guides,
+                                        o, R, self.d_temporal, self.d_temporal_sq, self.d_temporal_len, max_history=0.0, **kw)
+            else:
+                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_temporal,
+                                self.d_temporal_len, max_history=0.0, **kw)
         else:
             o, R = self.history_camera
-            r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_hist, self.d_hist_len, self.d_hist_guides, o, R,
-                            self.d_temporal, self.d_temporal_len, depth_tol=depth_tol, normal_cos=normal_cos,
-                            max_history=max_history, stream=stream)
+            if self.moments:
+                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_hist, self.d_hist_sq, self.d_hist_len,
+                                        self.d_hist_guides, o, R, self.d_temporal, self.d_temporal_sq, self.d_temporal_len,
+                                        max_history=max_history, **kw)
+            else:
+                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_hist, self.d_hist_len, self.d_hist_guides, o, R,
+                                self.d_temporal, self.d_temporal_len, max_history=max_history, **kw)
         self.temporal_passes = self.passes
 
     # -- frames -----------------------------------------------------------------------------

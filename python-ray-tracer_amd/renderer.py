@@ -490,6 +490,42 @@ class Renderer:
                                                                   vp(d_guides), strides[2], C.byref(dv), vp(d_out), strides[3], vp(d_work),
                                                                   strides[4], vp(stream)))
 
+    def film_temporal_moments(self, d_sum, d_sq, n, d_guides, d_hist, d_hist_sq, d_hist_len, d_hist_guides, prev_origin, prev_rotation, d_out,
+                              d_out_sq, d_out_len, *, depth_tol, normal_cos, max_history, sum_stride=None, sq_stride=None, guide_stride=None,
+                              hist_stride=None, hist_sq_stride=None, hist_guide_stride=None, out_stride=None, out_sq_stride=None, stream=None,
+                              reserved=(0, 0)):
+        """film_temporal with the second moment carried beside the mean (rt_film_temporal_moments): d_sq is this frame's sum of squares,
+        d_hist_sq the history's mean of squares, d_out_sq receives the new mean of squares, float64 (3, w, h) each; d_out and d_out_len
+        receive the bits film_temporal would give.  Asynchronous.  In numpy: temporal.temporal_moments_reference."""
+        npx = int(self.w or 0) * int(self.h or 0)
+        strides = [npx if v is None else int(v) for v in (sum_stride, sq_stride, guide_stride, hist_stride, hist_sq_stride, hist_guide_stride,
+                                                          out_stride, out_sq_stride)]
+        tp = L.rt_temporal()
+        tp.prev_origin[:] = [float(v) for v in np.asarray(prev_origin, dtype=np.float64).reshape(3)]
+        tp.prev_rotation[:] = [float(v) for v in np.asarray(prev_rotation, dtype=np.float64).reshape(9)]
+        tp.depth_tol, tp.normal_cos, tp.max_history = float(depth_tol), float(normal_cos), float(max_history)
+        tp.reserved[:] = [int(v) for v in reserved]
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_temporal_moments")(
+            self._ctx, vp(d_sum), strides[0], vp(d_sq), strides[1], int(n), vp(d_guides), strides[2], vp(d_hist), strides[3], vp(d_hist_sq),
+            strides[4], vp(d_hist_len), vp(d_hist_guides), strides[5], C.byref(tp), vp(d_out), strides[6], vp(d_out_sq), strides[7],
+            vp(d_out_len), vp(stream)))
+
+    def film_denoise_variance_temporal(self, d_mean, d_msq, d_len, ws, h, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, kappa=1.0,
+                                       var_floor=0.0, demodulate=1, prefilter=1, spatial_below=0.0, mean_stride=None, msq_stride=None,
+                                       guide_stride=None, out_stride=None, work_stride=None, stream=None):
+        """The variance-guided filter on a temporal mean (rt_film_denoise_variance_temporal): d_mean, d_msq and d_len are what
+        film_temporal_moments wrote (mean, mean of squares, length plane); a pixel shorter than spatial_below passes takes its variance
+        from its object's neighbours.  d_out and d_work as film_denoise_variance's.  Asynchronous.  In numpy:
+        variance.denoise_variance_temporal_reference."""
+        npx = int(ws) * int(h)
+        strides = [npx if v is None else int(v) for v in (mean_stride, msq_stride, guide_stride, out_stride, work_stride)]
+        dv = L.rt_denoise_variance(int(levels), int(normal_shin), float(kappa), float(var_floor), int(demodulate), int(prefilter))
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_denoise_variance_temporal")(
+            self._ctx, vp(d_mean), strides[0], vp(d_msq), strides[1], vp(d_len), int(ws), int(h), vp(d_guides), strides[2], C.byref(dv),
+            float(spatial_below), vp(d_out), strides[3], vp(d_work), strides[4], vp(stream)))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
         if stream:

@@ -1,5 +1,6 @@
 """Temporal accumulation — the film through a camera move (rt_film_temporal of include/mi355rt.h) in numpy: temporal_reference is
-the contract's second statement, as film.tone_reference is the resolve's and denoise.denoise_reference the filter's.  It is the
+the contract's second statement, as film.tone_reference is the resolve's and denoise.denoise_reference the filter's;
+temporal_moments_reference is rt_film_temporal_moments', the same call with a second moment carried beside the mean.  It is the
 header's loop, vectorised over the frame with the four taps in the header's order; the primary ray is denoise.primary_rays, the one
 guides_reference forms.  Nothing here touches the device: Film.next_frame and Film.temporal do.
 """
@@ -63,6 +64,15 @@ def temporal_taps_reference(guides, hist, hist_len, hist_guides, cam, prev_cam, 
     fresh).  taps=True adds a dict: "Pt" (3, w, h) the world point of each pixel's first hit, "qx", "qy" (4, w, h) the taps'
     pixel indices clipped into the frame, "used" bool (4, w, h) which taps contributed, "bw" (4, w, h) their bilinear weights, in
     the order (a, b) = (0, 0), (0, 1), (1, 0), (1, 1)."""
+    return _taps(guides, hist, hist_len, hist_guides, cam, prev_cam, raygen, w, h, depth_tol, normal_cos, max_history, taps, None)[0]
+
+
+def _taps(guides, hist, hist_len, hist_guides, cam, prev_cam, raygen, w, h, depth_tol, normal_cos, max_history, taps, hist_sq):
+    """(what temporal_taps_reference returns, hq): hq float64 (3, w, h) is the surviving taps' weighted mean of hist_sq (None
+    without one), summed in the taps' order beside hm."""
+    hsq = None if hist_sq is None else np.asarray(hist_sq, dtype=np.float64)
+    if hsq is not None and hsq.shape != (3, int(w), int(h)):
+        raise ValueError(f"hist_sq must have shape {(3, int(w), int(h))}, got {hsq.shape}")
     depth_tol, normal_cos, max_history, _ = check_temporal(depth_tol, normal_cos, max_history)
     w, h = int(w), int(h)
     g, hg = np.asarray(guides), np.asarray(hist_guides)
@@ -108,6 +118,7 @@ def temporal_taps_reference(guides, hist, hist_len, hist_guides, cam, prev_cam, 
         HT = hg[3].astype(np.float64)
         HL = hl.astype(np.float64)
         W, Lh, H = np.zeros((w, h)), np.zeros((w, h)), np.zeros((3, w, h))
+        Q = np.zeros((3, w, h))
         info = dict(Pt=Pt, qx=[], qy=[], used=[], bw=[])
         for a in (0, 1):
             for b in (0, 1):
@@ -124,6 +135,8 @@ def temporal_taps_reference(guides, hist, hist_len, hist_guides, cam, prev_cam, 
                 ok &= lq > 0.0
                 W = np.where(ok, W + bw, W)
                 H = np.where(ok, H + bw * hs[:, cx, cy], H)
+                if hsq is not None:
+                    Q = np.where(ok, Q + bw * hsq[:, cx, cy], Q)
                 Lh = np.where(ok, Lh + bw * lq, Lh)
                 info["qx"].append(cx); info["qy"].append(cy); info["used"].append(ok); info["bw"].append(bw)
         valid = W > 0.0
@@ -131,9 +144,10 @@ def temporal_taps_reference(guides, hist, hist_len, hist_guides, cam, prev_cam, 
         hm = np.where(valid, H / Ws, 0.0)
         L = np.where(valid, Lh / Ws, 0.0)
         L = np.where(L > max_history, max_history, L)
+        hq = None if hsq is None else np.where(valid, Q / Ws, 0.0)
     if taps:
-        return hm, L, valid, {k: (v if k == "Pt" else np.stack(v)) for k, v in info.items()}
-    return hm, L, valid
+        return (hm, L, valid, {k: (v if k == "Pt" else np.stack(v)) for k, v in info.items()}), hq
+    return (hm, L, valid), hq
 
 
 def temporal_reference(total, n, guides, hist, hist_len, hist_guides, cam, prev_cam, raygen, w, h, depth_tol, normal_cos, max_history):
@@ -173,3 +187,30 @@ def temporal_reference(total, n, guides, hist, hist_len, hist_guides, cam, prev_
         out = np.where(valid, (L * hm + s) / (L + nn), s / nn)
         out_len = np.where(valid, L + nn, nn).astype(np.float32)
     return out, out_len
+
+
+def temporal_moments_reference(total, total_sq, n, guides, hist, hist_sq, hist_len, hist_guides, cam, prev_cam, raygen, w, h, depth_tol,
+                               normal_cos, max_history):
+    """rt_film_temporal_moments in numpy: temporal_reference with the second moment beside the mean.  total_sq: float64 (3, w, h), the
+    sum of squares of the n passes of this frame; hist_sq: float64 (3, w, h), the history's MEAN of squares; everything else as
+    temporal_reference.  Returns (out, out_sq, out_len): out and out_len are temporal_reference's bits, out_sq float64 (3, w, h) the
+    new mean of squares.  Every line of temporal_reference holds, in the same order, and per pixel, float64, no fused multiply-add:
+        fresh:                         out_sq[k][e] = sq[k][e] / (double)n
+        in the tap loop, after H_k:    Q_k = Q_k + bw * hist_sq[k][q]
+        after hm_k:                    hq_k = Q_k / W
+                                       out_sq[k][e] = (L * hq_k + sq[k][e]) / (L + (double)n)"""
+    depth_tol, normal_cos, max_history, n = check_temporal(depth_tol, normal_cos, max_history, n)
+    s, sq = np.asarray(total, dtype=np.float64), np.asarray(total_sq, dtype=np.float64)
+    for name, a in (("total", s), ("total_sq", sq)):
+        if a.shape != (3, int(w), int(h)):
+            raise ValueError(f"{name} must have shape {(3, int(w), int(h))}, got {a.shape}")
+    if hist_sq is None:
+        raise ValueError("hist_sq is None: the history of a moments call has a mean of squares")
+    (hm, L, valid), hq = _taps(guides, hist, hist_len, hist_guides, cam, prev_cam, raygen, w, h, depth_tol, normal_cos, max_history, False,
+                               hist_sq)
+    nn = np.float64(n)
+    with np.errstate(all="ignore"):
+        out = np.where(valid, (L * hm + s) / (L + nn), s / nn)
+        out_sq = np.where(valid, (L * hq + sq) / (L + nn), sq / nn)
+        out_len = np.where(valid, L + nn, nn).astype(np.float32)
+    return out, out_sq, out_len
