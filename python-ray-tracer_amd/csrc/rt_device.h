@@ -359,7 +359,7 @@ constexpr int ORDER_THREADS = 1024, ORDER_BUCKETS = 1024, ORDER_XCDS = 8;
 //   that matters is below |o| + extent;
 //   both are covered by growing the box by m = 2^-18 (extent + |o|_1) on every side — done on the ray instead: the lower
 //   faces are tested from o + m, the upper ones from o - m;
-//   float32 arithmetic: a face's parameter is t = fma(face, inv, c), inv = rcp(R_i) (1 ulp), c = -(o_i +- m) inv rounded:
+//   float32 arithmetic: a face's parameter is t = fma(face, inv, c), inv = rcp(R_i) (1 ulp; measured 0.88), c = -(o_i +- m) inv rounded:
 //   t carries a relative error below 2^-21 and an absolute one below 2^-23 |c|; c is moved by 2^-21 |c| in the direction
 //   that lowers the near parameter and raises the far one, and the final comparison allows 2^-18 relative.
 //   R_i = 0 is replaced by +-2^-40 (a change of direction far below the float32 rounding already covered).
@@ -555,8 +555,8 @@ __device__ __forceinline__ int plane_code(const KParams &p, int k)
 
 // no_negate (Lds::trim): for a normal -e_i both den and num are negated, and everything a query does with the pair is the same for
 // (-den, -num) as for (den, num) — |den| < 0.001, |num| against |den|, whether the signs agree, and the quotient bit for bit
-// (IEEE division, and div_inrange: rcp is odd and each of its steps negates exactly; only a ZERO quotient may change sign, and
-// t > 0 fails for both).  Leaving the negation out saves two v_xor and two v_cndmask per test, for either sign of the code.
+// (IEEE division, and div_inrange: rcp is odd and each of its steps negates exactly, and a zero quotient has IEEE's sign in both).
+// Leaving the negation out saves two v_xor and two v_cndmask per test, for either sign of the code.
 // tests/algo/plane_sign_check.cpp restates it (with div_inrange as rt_math.h has it).
 __device__ __forceinline__ void plane_den_num(const double *__restrict__ g, int code, const V3 &o, const V3 &d, double &den, double &num,
                                               bool no_negate = false)

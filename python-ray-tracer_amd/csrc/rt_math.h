@@ -3,7 +3,10 @@
 // reaches the frames, and each shortcut is justified by a CPU check over 10^7 to 10^8 operands, so the kernel and the checks
 // (tests/algo/normalize_check.cpp, renorm_check.cpp, divsqrt_check.cpp, plane_sign_check.cpp, hash_check.cpp) compile this same
 // text.  HIP-free C++17: no HIP type or builtin.  What the hardware supplies — the v_rsq_f64 / v_rcp_f64 seed of an iteration —
-// is an argument: rt_device.h's wrappers pass the instruction's result, the checks a stand-in that is 2^-24 off.  The
+// is an argument: rt_device.h's wrappers pass the instruction's result, the checks a stand-in that is 2^-24 off, which bounds the
+// instructions' own error with little to spare (measured on an MI355X over the operands of tests/device_math_cases.py: v_rcp_f64 at
+// most 2^-24.39 off, v_rsq_f64 2^-24.18; profiles/device_math_seeds.json;
+// tests/test_gpu_device_math.py asserts the bound and runs the wrappers on the device against IEEE).  The
 // wave-uniform guards (a ballot) stay with the wrappers; their constants are named here.
 // No multiply-add may be fused and none split: clang is told below, other compilers need -ffp-contract=off.
 #pragma once
@@ -46,8 +49,8 @@ RT_MATH_FN V3 normalize3_generic(const V3 &v)
 // 1/g, which is what the final fma correction of each quotient requires.  26 instructions instead of 55.  Guard (wave-uniform): every component's magnitude >= 2^-200 (hence nonzero, and |v|² >= 2^-400) and
 // |v|² <= 2^400, so no intermediate leaves the normal range and no signed-zero case arises; otherwise the
 // generic path.  tests/test_algorithms.py runs this on the CPU against sqrt()/division on 10^8 vectors
-// with seeds 16x less accurate than v_rsq_f64 / v_rcp_f64, and once more with seeds 2^-16 off: only from there does a sample show
-// whether the reciprocal's Newton step is present (tests/algo/normalize_check.cpp has the arithmetic).
+// with seeds 2^-24 off (the bound of v_rsq_f64 / v_rcp_f64 measured above), and once more with seeds 2^-16 off: only from there does a
+// sample show whether the reciprocal's Newton step is present (tests/algo/normalize_check.cpp has the arithmetic).
 constexpr double NORMALIZE_MIN_COMPONENT = 0x1p-200, NORMALIZE_MAX_NN = 0x1p400;   // the guard (rt_device.h: normalize3)
 // The square root's iteration on its own: g = RN(sqrt(x)) and h ~ 1/(2g) (relative error ~2^-50), from y = rsq(x).
 struct SqrtIter { double g, h; };
@@ -88,7 +91,10 @@ RT_MATH_FN double div_seeded(double a, double b, double r)     // r = rcp(b)
     double e = __builtin_fma(-b, r, 1.0); r = __builtin_fma(r, e, r);
     e = __builtin_fma(-b, r, 1.0); r = __builtin_fma(r, e, r);
     const double q = a * r;
-    return __builtin_fma(__builtin_fma(-b, q, a), r, q);
+    // q has the quotient's sign (r has b's), a zero q included; the correction's sum of zeros has not: fma(-b, q, a) is +0 for either
+    // zero numerator, and -0 / b with b > 0 came out +0.  One v_bfi_b32 puts q's sign on the result (it has it already wherever the
+    // result is not zero), so a zero quotient is IEEE's as well (tests/test_gpu_device_math.py compares signed zeros on the device).
+    return __builtin_copysign(__builtin_fma(__builtin_fma(-b, q, a), r, q), q);
 }
 RT_MATH_FN double sqrt_seeded(double x, double y)              // x >= 0 (or NaN), y = rsq(x)
 {

@@ -3,8 +3,9 @@
  * the norm taken from that iteration's own 1/(2g) estimate plus one Newton step and shared by the three quotients, one fma
  * correction per quotient (the backend's f64 division without div_scale/div_fixup).  The routine is the header's, the text the
  * kernel compiles; only the seed is this program's.
- * Seeds carry a relative error of up to 2^-24 here, i.e. WORSE than v_rsq_f64 / v_rcp_f64, so agreement with
- * sqrt()/division on every sample is a conservative check.  One sample in four sits at the edges of the guard
+ * Seeds carry a relative error of up to 2^-24 here: no better than v_rsq_f64 / v_rcp_f64, whose measured maxima on an MI355X are
+ * 2^-24.18 (rsq) and 2^-24.39 (rcp) (profiles/device_math_seeds.json; tests/test_gpu_device_math.py asserts <= 2^-24), so agreement
+ * with the correctly rounded / and sqrt() on every sample covers the hardware's seeds; the pass at 2^-16 below shows the margin.  One sample in four sits at the edges of the guard
  * (components down to 2^-200, |v|^2 up to 2^400).
  * A second pass on a quarter as many vectors (the stream goes on) has seeds 2^-16 off.  At 2^-24 the iteration's 2h is already
  * within 2^-47 of 1/g and a quotient formed without the Newton step is 2^-94 off: no sample count sees that.  From 2^-16, h is

@@ -4,9 +4,9 @@
  *    Everything a query does with the pair must be the same for (den, num) and (-den, -num):
  *      closest_hit:  !(|den| < 0.001), t = div_inrange(num, den), best > t && t > 0
  *      any_hit:      !(|den| < 0.001), the signs agree, |num| < 998 |den|, |num| > 1000 |den|, t = num / den, 999 > t && t > 0
- *    t is compared bit for bit (NaNs: both NaN; zeros: both zero — div_inrange's last fma gives a zero quotient the sign of
- *    r, not of num/den, and a zero t of either sign is no hit: t > 0 fails).  div_inrange is rt_math.h's div_seeded with a reciprocal
- *    seed that is odd in its operand, as v_rcp_f64 is, and up to 2^-24 off.
+ *    t is compared bit for bit, signed zeros included (NaNs: both NaN): div_seeded gives its result the sign of q = num * r, which
+ *    is the quotient's for a zero too.  div_inrange is rt_math.h's div_seeded with a reciprocal seed that is odd in its operand, as
+ *    v_rcp_f64 is, and up to 2^-24 off.
  * 2. any_hit_masks: "num > 0 && den > 0 || num < 0 && den < 0" restated as "the sign bits agree, |num| > 0" under
  *    !(|den| < 0.001); the whole occlusion decision of the straightforward form (any_hit) against the restated one.
  *
@@ -23,7 +23,7 @@ static uint64_t s[2] = {0x9E3779B97F4A7C15ull, 0xD1B54A32D192ED03ull};
 static inline uint64_t rnd(void) { uint64_t a = s[0], b = s[1]; s[0] = b; a ^= a << 23; s[1] = a ^ b ^ (a >> 17) ^ (b >> 26); return s[1] + b; }
 static inline double urand(void) { return (double)(rnd() >> 11) * (1.0 / 9007199254740992.0); }
 static inline uint64_t bits(double x) { uint64_t u; memcpy(&u, &x, 8); return u; }
-static inline int same_bits(double a, double b) { return bits(a) == bits(b) || (a != a && b != b) || (a == 0.0 && b == 0.0); }
+static inline int same_bits(double a, double b) { return bits(a) == bits(b) || (a != a && b != b); }
 
 static double rcp_seed(double b)                          /* odd in b; relative error up to 2^-24, a function of |b| */
 {

@@ -1,6 +1,7 @@
 """The exact-arithmetic shortcuts the HIP kernel uses (python-ray-tracer_amd/csrc/rt_math.h, the text rt_device.h compiles), run
 on the CPU and checked against the straightforward evaluation on tens of millions of inputs.  The shortcuts are algorithms, not hardware
-features, so they can be validated here without a GPU; the GPU parity tests then confirm the device code."""
+features, so they can be validated here without a GPU; what the hardware adds (the seed instructions' accuracy, the backend's lowering of
+division and square root, the wrappers' ballots) is run on the device, primitive by primitive, by tests/test_gpu_device_math.py."""
 import os
 import subprocess
 import sys
