@@ -2,14 +2,16 @@
 // render kernel in rt_device.h.  HIP only (no torch, no CPU fallback): without a HIP device
 // rt_create fails and nothing renders.  What a call decides before it touches the device lives in
 // HIP-free headers: the packed scene (rt_scene.h), the launch arithmetic (rt_geometry.h), the
-// launch's kernel and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the dispatch-order
-// feedback (rt_feedback.h), the per-stream state: cull-table sets, scratch buffers, scene readers (rt_streams.h).
+// launch's kernel and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the film entries' checks,
+// kernel arguments and ping-pong plans (rt_film_launch.h), the dispatch-order feedback (rt_feedback.h), the per-stream state: cull-table
+// sets, scratch buffers, scene readers (rt_streams.h).
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_denoise.h"
 #include "rt_denoise_var.h"
 #include "rt_feedback.h"
 #include "rt_film.h"
+#include "rt_film_launch.h"
 #include "rt_geometry.h"
 #include "rt_guides.h"
 #include "rt_launch.h"
@@ -156,7 +158,11 @@ int ensure(rt_ctx *ctx, Buf &b, size_t bytes)
     return RT_OK;
 }
 
-int refuse(rt_ctx *ctx, const rt::Refusal &r) { return r.code == RT_OK ? RT_OK : fail(ctx, r.code, r.msg); }
+int refuse(rt_ctx *ctx, const rt::Refusal &r)
+{
+    if (r.code == RT_OK) return RT_OK;
+    return fail(ctx, r.code, r.entry ? std::string(r.entry) + ": " + r.msg : std::string(r.msg));
+}
 
 int check_params(rt_ctx *ctx, const rt_params *p, int x0, int x1) { return refuse(ctx, rt::check_params(ctx->have_scene, ctx->view, ctx->lay, p, x0, x1)); }
 
@@ -442,6 +448,21 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
         rt::order_queued(*f, ctx->epoch);
     }
     RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// The writes of a variance filter: `prepare` launches write 0 (it is handed the write and the grid), then one launch of
+// denoise_var_kernel per level, ping-pong between d_out and d_work so that the last write ends in d_out.
+template <class Prepare>
+int variance_filter(rt_ctx *ctx, const rt::DenoiseVarArgs &common, int levels, const rt::FilmPingPong &pp, hipStream_t st, Prepare prepare)
+{
+    const dim3 grid(rt::denoise_grid((long long)common.ws * common.h, ctx->cu_count));
+    for (int k = 0; k <= levels; ++k) {
+        const rt::FilmWrite w = rt::film_write(true, levels, k, nullptr, 0, pp);
+        if (k == 0) prepare(w, grid);
+        else hipLaunchKernelGGL(rt::denoise_var_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, rt::denoise_var_write(common, w, levels, k));
+        RT_HIP(ctx, hipGetLastError());
+    }
     return RT_OK;
 }
 
@@ -757,10 +778,10 @@ int rt_render_sequence(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
     return RT_OK;
 }
 
-// The film: `passes` frames of the unchanged render path (launch(), float32 output, seed + i) into the stream's scratch, up to
-// rt::FILM_BATCH of them folded into the float64 sum by one add kernel (with d_sq: into the sum and the sum of squares by one add2
-// kernel).  Everything is queued on `stream`: a batch's renders write the scratch only after the add kernel before them has read it.
-// The arguments have been checked by the entry point.
+// The film: `passes` frames of the unchanged render path (launch(), float32 output, seed + i) into the stream's scratch, a batch of
+// them (rt_film_launch.h: film_batch) folded into the float64 sum by one add kernel (with d_sq: into the sum and the sum of squares by
+// one add2 kernel).  Everything is queued on `stream`: a batch's renders write the scratch only after the add kernel before them has
+// read it.  The arguments have been checked by the entry point.
 static int film_queue_passes(rt_ctx *ctx, const rt_params *params, int x0, int x1, int passes, int reset, void *d_sum, int64_t sum_stride,
                              void *d_sq, int64_t sq_stride, void *stream)
 {
@@ -770,34 +791,25 @@ static int film_queue_passes(rt_ctx *ctx, const rt_params *params, int x0, int x
     hipStream_t st = stream_of(ctx, stream);
     rt_params p = *params;
     p.flags &= ~(RT_FLAG_U8_RGB | RT_FLAG_U8_HWC);
-    // pass planes padded to a multiple of four floats: every plane of the scratch is 16-byte aligned whatever npx is
-    const long long fplane = (npx + 3) & ~3ll;
-    const size_t pass_bytes = (size_t)fplane * 3 * sizeof(float);
-    int batch = passes < rt::FILM_BATCH ? passes : rt::FILM_BATCH;
-    if (batch * pass_bytes > rt::FILM_SCRATCH_MAX) batch = 1;
+    const rt::FilmBatch fb = rt::film_batch(npx, passes);
     StreamRecord *sr = nullptr;
     rc = stream_record(ctx, st, &sr);
     if (rc != RT_OK) return rc;
-    Buf &fb = sr->buf[rt::BUF_FILM];
-    rc = stream_buffer(ctx, fb, st, batch * pass_bytes, rt::growth(fb.cap, batch * pass_bytes).sync);
+    Buf &scratch = sr->buf[rt::BUF_FILM];
+    rc = stream_buffer(ctx, scratch, st, fb.batch * fb.pass_bytes, rt::growth(scratch.cap, fb.batch * fb.pass_bytes).sync);
     if (rc != RT_OK) return rc;
-    float *const frames = (float *)fb.p;
-    rt::FilmAddArgs a;
-    a.sum = (double *)d_sum; a.frames = frames; a.sum_stride = sum_stride; a.fplane = fplane; a.npx = npx;
-    rt::FilmAdd2Args a2;
-    a2.sum = (double *)d_sum; a2.sq = (double *)d_sq; a2.frames = frames; a2.sum_stride = sum_stride; a2.sq_stride = sq_stride;
-    a2.fplane = fplane; a2.npx = npx;
+    float *const frames = (float *)scratch.p;
     const dim3 grid(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 3), 3);
-    for (int i = 0; i < passes; i += batch) {
-        const int nb = std::min(batch, passes - i);
+    for (int i = 0; i < passes; i += fb.batch) {
+        const int nb = std::min(fb.batch, passes - i), first = (reset && i == 0) ? 1 : 0;
         for (int b = 0; b < nb; ++b) {
             p.seed = params->seed + (uint32_t)(i + b);
-            rc = launch(ctx, &p, x0, x1, nullptr, frames + (size_t)b * 3 * fplane, fplane, st);
+            rc = launch(ctx, &p, x0, x1, nullptr, frames + (size_t)b * 3 * fb.fplane, fb.fplane, st);
             if (rc != RT_OK) return rc;
         }
-        a.nb = a2.nb = nb; a.reset = a2.reset = (reset && i == 0) ? 1 : 0;
-        if (d_sq) hipLaunchKernelGGL(rt::film_add2_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a2);
-        else hipLaunchKernelGGL(rt::film_add_kernel, grid, dim3(rt::FILM_THREADS), 0, st, a);
+        if (d_sq) hipLaunchKernelGGL(rt::film_add2_kernel, grid, dim3(rt::FILM_THREADS), 0, st,
+                                     rt::film_add2_args(d_sum, sum_stride, d_sq, sq_stride, frames, fb.fplane, npx, nb, first));
+        else hipLaunchKernelGGL(rt::film_add_kernel, grid, dim3(rt::FILM_THREADS), 0, st, rt::film_add_args(d_sum, sum_stride, frames, fb.fplane, npx, nb, first));
         RT_HIP(ctx, hipGetLastError());
     }
     return RT_OK;
@@ -807,13 +819,9 @@ int rt_film_accumulate(rt_ctx *ctx, const rt_params *params, int x0, int x1, int
                        void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    int rc = check_params(ctx, params, x0, x1);
+    int rc = refuse(ctx, rt::check_film_accumulate("rt_film_accumulate", ctx->have_scene, ctx->view, ctx->lay, params, x0, x1, passes, d_sum, sum_stride,
+                                                   false, nullptr, 0));
     if (rc != RT_OK) return rc;
-    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: passes < 1");
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: d_sum is NULL");
-    const long long npx = (long long)(x1 - x0) * ctx->view.h;
-    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: (x1-x0)*h above RT_FILM_MAX_PIXELS");
-    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate: sum_stride smaller than the slab");
     return film_queue_passes(ctx, params, x0, x1, passes, reset, d_sum, sum_stride, nullptr, 0, stream);
 }
 
@@ -822,16 +830,9 @@ int rt_film_accumulate_moments(rt_ctx *ctx, const rt_params *params, int x0, int
                                void *d_sq, int64_t sq_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    int rc = check_params(ctx, params, x0, x1);
+    int rc = refuse(ctx, rt::check_film_accumulate("rt_film_accumulate_moments", ctx->have_scene, ctx->view, ctx->lay, params, x0, x1, passes, d_sum,
+                                                   sum_stride, true, d_sq, sq_stride));
     if (rc != RT_OK) return rc;
-    if (passes < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: passes < 1");
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sum is NULL");
-    if (!d_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sq is NULL");
-    if (d_sq == d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: d_sq and d_sum must be buffers of their own");
-    const long long npx = (long long)(x1 - x0) * ctx->view.h;
-    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: (x1-x0)*h above RT_FILM_MAX_PIXELS");
-    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: sum_stride smaller than the slab");
-    if (sq_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_accumulate_moments: sq_stride smaller than the slab");
     return film_queue_passes(ctx, params, x0, x1, passes, reset, d_sum, sum_stride, d_sq, sq_stride, stream);
 }
 
@@ -839,31 +840,11 @@ int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
                     void *d_u8, void *d_f32, int64_t out_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: d_sum is NULL");
-    if (!tone) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: tone is NULL");
-    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: ws*h outside 1..RT_FILM_MAX_PIXELS");
-    if (n < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: n < 1");
-    if (!(std::isfinite(tone->exposure) && tone->exposure > 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: exposure must be finite and > 0");
-    if (!(tone->white == 0.0 || (std::isfinite(tone->white) && tone->white > 0.0)))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: white must be 0, or finite and > 0");
-    if (tone->gamma != 1 && tone->gamma != 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: gamma must be 1 or 2");
-    if (tone->flags & ~(RT_FLAG_U8_RGB | RT_FLAG_U8_HWC)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: unknown flag bit");
-    if (!d_u8 && !d_f32) return fail(ctx, RT_ERR_BAD_ARG, "both output pointers are NULL");
-    const long long npx = (long long)ws * h;
-    if (sum_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_resolve: sum_stride smaller than the frame");
-    const bool hwc = (tone->flags & RT_FLAG_U8_HWC) != 0;
-    if (hwc) {
-        if (d_f32) return fail(ctx, RT_ERR_BAD_ARG, "RT_FLAG_U8_HWC re-uses out_stride as the image row pitch: resolve the float32 buffer in a separate call");
-        if (out_stride < (int64_t)ws) return fail(ctx, RT_ERR_BAD_ARG, "row pitch smaller than the frame width");
-    } else if (out_stride < npx) return fail(ctx, RT_ERR_BAD_ARG, "out_stride smaller than the frame");
+    int rc = refuse(ctx, rt::check_film_resolve(d_sum, sum_stride, ws, h, n, tone, d_u8, d_f32, out_stride));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    rt::FilmResolveArgs a;
-    a.sum = (const double *)d_sum; a.u8 = (uint8_t *)d_u8; a.f32 = (float *)d_f32;
-    a.sum_stride = sum_stride; a.out_stride = out_stride; a.npx = npx;
-    a.h = h; a.rgb = (tone->flags & RT_FLAG_U8_RGB) ? 1 : 0; a.hwc = hwc ? 1 : 0;
-    a.tone = rt::film_tone_of(n, tone->exposure, tone->white, tone->gamma);
-    hipLaunchKernelGGL(rt::film_resolve_kernel, dim3(rt::film_grid((npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
+    const rt::FilmResolveArgs a = rt::film_resolve_args(d_sum, sum_stride, ws, h, n, tone, d_u8, d_f32, out_stride);
+    hipLaunchKernelGGL(rt::film_resolve_kernel, dim3(rt::film_grid((a.npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
                        stream_of(ctx, stream), a);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
@@ -912,109 +893,44 @@ int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_
 }
 
 // The film's filter: one launch of the denoise kernel (rt_denoise.h) per level, ping-pong between d_out and d_work so that the last
-// level writes d_out; levels == 0 is one launch that writes the mean.
+// level writes d_out (rt_film_launch.h: film_write); levels == 0 is one launch that writes the mean.
 int rt_film_denoise(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const void *d_guides, int64_t guide_stride,
                     const rt_denoise *dn, void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_sum is NULL");
-    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_guides is NULL");
-    if (!dn) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: dn is NULL");
-    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_out is NULL");
-    if (n < 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: n < 1");
-    if (dn->levels < 0 || dn->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: levels outside 0..6");
     int nsq = -1;
-    for (int i = 0; i <= 10; ++i) if (dn->normal_shin == (1 << i)) nsq = i;
-    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: normal_shin must be 1, 2, 4, ..., 1024");
-    if (!(dn->sigma == 0.0 || (std::isfinite(dn->sigma) && dn->sigma > 0.0)))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: sigma must be 0, or finite and > 0");
-    if (dn->demodulate != 0 && dn->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: demodulate must be 0 or 1");
-    if (dn->reserved != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: reserved must be 0");
-    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: ws*h outside 1..RT_FILM_MAX_PIXELS");
-    const long long npx = (long long)ws * h;
-    if (sum_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: a plane stride is smaller than the frame");
-    if (!d_work && dn->levels >= 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_work is NULL with levels >= 2");
-    if (d_out == d_sum || d_out == d_guides || (d_work && (d_work == d_sum || d_work == d_guides || d_work == d_out)))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise: d_out and d_work must be buffers of their own");
+    int rc = refuse(ctx, rt::check_film_denoise(d_sum, sum_stride, ws, h, n, d_guides, guide_stride, dn, d_out, out_stride, d_work, work_stride, nsq));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
-    rt::DenoiseArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
-    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dn->demodulate; a.n = (double)n;
-    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
-    const int levels = dn->levels;
-    const double *src = (const double *)d_sum;
-    long long src_stride = sum_stride;
-    for (int i = 0; i < (levels ? levels : 1); ++i) {
-        const bool to_out = rt::denoise_to_out(levels, i);
-        a.src = src; a.src_stride = src_stride;
-        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
-        rt::denoise_level(a, levels, i, dn->sigma);
-        hipLaunchKernelGGL(rt::denoise_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
+    const rt::FilmPingPong pp = {d_out, out_stride, d_work, work_stride};
+    const dim3 grid(rt::denoise_grid((long long)ws * h, ctx->cu_count));
+    for (int i = 0; i < (dn->levels ? dn->levels : 1); ++i) {
+        const rt::FilmWrite w = rt::film_write(false, dn->levels, i, d_sum, sum_stride, pp);
+        hipLaunchKernelGGL(rt::denoise_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, rt::denoise_args(w, d_guides, guide_stride, ws, h, n, dn, nsq, i));
         RT_HIP(ctx, hipGetLastError());
-        src = a.dst; src_stride = a.dst_stride;
     }
     return RT_OK;
 }
 
 // The variance-guided filter: a prepare launch (rt_denoise_var.h: the mean and the variance of the mean from sum and sum of squares)
-// and one launch per level, ping-pong between d_out and d_work so that the last write ends in d_out; levels == 0 is the prepare
-// launch alone, without demodulation.
+// and one launch per level; levels == 0 is the prepare launch alone, without demodulation.
 int rt_film_denoise_variance(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int ws, int h, int64_t n,
                              const void *d_guides, int64_t guide_stride, const rt_denoise_variance *dv, void *d_out, int64_t out_stride,
                              void *d_work, int64_t work_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_sum) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_sum is NULL");
-    if (!d_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_sq is NULL");
-    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_guides is NULL");
-    if (!dv) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: dv is NULL");
-    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out is NULL");
-    if (n < 2) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: n < 2");
-    if (dv->levels < 0 || dv->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: levels outside 0..6");
     int nsq = -1;
-    for (int i = 0; i <= 10; ++i) if (dv->normal_shin == (1 << i)) nsq = i;
-    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: normal_shin must be 1, 2, 4, ..., 1024");
-    if (!(std::isfinite(dv->kappa) && dv->kappa >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: kappa must be finite and >= 0");
-    if (!(std::isfinite(dv->var_floor) && dv->var_floor >= 0.0))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: var_floor must be finite and >= 0");
-    if (dv->demodulate != 0 && dv->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: demodulate must be 0 or 1");
-    if (dv->prefilter != 0 && dv->prefilter != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: prefilter must be 0 or 1");
-    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: ws*h outside 1..RT_FILM_MAX_PIXELS");
-    const long long npx = (long long)ws * h;
-    if (sum_stride < npx || sq_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: a plane stride is smaller than the frame");
-    if (!d_work && dv->levels >= 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_work is NULL with levels >= 1");
-    for (const void *in : {d_sum, d_sq, d_guides})
-        if (d_out == in || (d_work && d_work == in))
-            return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out and d_work must be buffers of their own");
-    if (d_work && d_work == d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance: d_out and d_work must be buffers of their own");
+    int rc = refuse(ctx, rt::check_film_denoise_variance(d_sum, sum_stride, d_sq, sq_stride, ws, h, n, d_guides, guide_stride, dv, d_out, out_stride,
+                                                         d_work, work_stride, nsq));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
-    const int levels = dv->levels;
-    rt::DenoiseVarArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.sum = (const double *)d_sum; a.sum_stride = sum_stride; a.sq = (const double *)d_sq; a.sq_stride = sq_stride;
-    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
-    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dv->demodulate; a.prefilter = dv->prefilter; a.copy = levels == 0;
-    a.n = (double)n; a.n1 = (double)(n - 1); a.k2 = dv->kappa * dv->kappa; a.var_floor = dv->var_floor;
-    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
-    for (int k = 0; k <= levels; ++k) {
-        const bool to_out = rt::denoise_var_to_out(levels, k);
-        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
-        if (k == 0) hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
-        else {
-            rt::denoise_var_level(a, levels, k - 1);
-            hipLaunchKernelGGL(rt::denoise_var_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
-        }
-        RT_HIP(ctx, hipGetLastError());
-        a.src = a.dst; a.src_stride = a.dst_stride;
-    }
-    return RT_OK;
+    rt::DenoiseVarArgs a = rt::denoise_var_common(d_guides, guide_stride, ws, h, dv, nsq);
+    rt::denoise_var_inputs(a, d_sum, sum_stride, d_sq, sq_stride, n, dv->levels);
+    return variance_filter(ctx, a, dv->levels, {d_out, out_stride, d_work, work_stride}, st, [&](const rt::FilmWrite &w, dim3 grid) {
+        hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, rt::denoise_var_write(a, w, dv->levels, 0));
+    });
 }
 
 // The film through a camera move: one launch of the temporal kernel (rt_temporal.h) over the full frame of the current camera and
@@ -1024,51 +940,22 @@ int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t
                      const rt_temporal *tp, void *d_out, int64_t out_stride, void *d_out_len, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_sum || !d_guides || !d_hist || !d_hist_len || !d_hist_guides || !d_out || !d_out_len)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a buffer is NULL");
-    if (!tp) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: tp is NULL");
-    if (n < 1 || n > (1 << 24)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: n outside 1..2^24");
-    if (!(std::isfinite(tp->depth_tol) && tp->depth_tol >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: depth_tol must be finite and >= 0");
-    if (!(tp->normal_cos >= -1.0 && tp->normal_cos <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: normal_cos outside [-1, 1]");
-    if (!(std::isfinite(tp->max_history) && tp->max_history >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: max_history must be finite and >= 0");
-    if (tp->reserved[0] != 0 || tp->reserved[1] != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: reserved must be 0");
     const rt::View &v = ctx->view;
-    if (!v.have_cam) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: rt_set_camera has not been called");
-    if (!v.have_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: rt_set_raygen has not been called");
-    if (v.explicit_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: an explicit rt_set_pixel_loc grid cannot be reprojected");
-    if (v.dy == 0.0 || v.dz == 0.0) return fail(ctx, RT_ERR_STATE, "rt_film_temporal: the grid's dy or dz is 0");
-    bool finite = true;
-    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(v.cam_o[i]) && std::isfinite(tp->prev_origin[i]);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v.cam_R[i]) && std::isfinite(tp->prev_rotation[i]);
-    if (!finite) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a camera entry is not finite");
-    const long long npx = (long long)v.w * v.h;
-    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: w*h above RT_FILM_MAX_PIXELS");
-    if (sum_stride < npx || guide_stride < npx || hist_stride < npx || hist_guide_stride < npx || out_stride < npx)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: a plane stride is smaller than the frame");
-    const void *const ins[] = {d_sum, d_guides, d_hist, d_hist_len, d_hist_guides};
-    for (const void *in : ins)
-        if (d_out == in || d_out_len == in) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: d_out and d_out_len must be buffers of their own");
-    if (d_out == d_out_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal: d_out and d_out_len must be buffers of their own");
+    int rc = refuse(ctx, rt::check_film_temporal("rt_film_temporal", v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len,
+                                                 d_hist_guides, hist_guide_stride, tp, d_out, out_stride, d_out_len));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     rt::TemporalArgs a;
-    a.sum = (const double *)d_sum; a.guides = (const float *)d_guides; a.hist = (const double *)d_hist;
-    a.hist_len = (const float *)d_hist_len; a.hist_guides = (const float *)d_hist_guides;
-    a.out = (double *)d_out; a.out_len = (float *)d_out_len;
-    a.sum_stride = sum_stride; a.guide_stride = guide_stride; a.hist_stride = hist_stride; a.hist_guide_stride = hist_guide_stride;
-    a.out_stride = out_stride;
-    a.w = v.w; a.h = v.h; a.n = (double)n;
-    a.px = v.px; a.y0 = v.y0; a.dy = v.dy; a.z0 = v.z0; a.dz = v.dz;
-    std::memcpy(a.o, v.cam_o, sizeof a.o); std::memcpy(a.R, v.cam_R, sizeof a.R);
-    std::memcpy(a.po, tp->prev_origin, sizeof a.po); std::memcpy(a.pR, tp->prev_rotation, sizeof a.pR);
-    a.depth_tol = tp->depth_tol; a.normal_cos = tp->normal_cos; a.max_history = tp->max_history;
-    hipLaunchKernelGGL(rt::temporal_kernel, dim3(rt::temporal_grid(npx, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
+    rt::temporal_args(a, v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out,
+                      out_stride, d_out_len);
+    hipLaunchKernelGGL(rt::temporal_kernel, dim3(rt::temporal_grid((long long)v.w * v.h, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
                        stream_of(ctx, stream), a);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 
-// rt_film_temporal with the second moment beside the mean: the same checks in the same order, then what the three new buffers add;
-// one launch of temporal_moments_kernel (rt_temporal.h), a kernel of its own so that temporal_kernel stays what it was.
+// rt_film_temporal with the second moment beside the mean: one launch of temporal_moments_kernel (rt_temporal.h), a kernel of its own
+// so that temporal_kernel stays what it was.
 int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int64_t n,
                              const void *d_guides, int64_t guide_stride, const void *d_hist, int64_t hist_stride, const void *d_hist_sq,
                              int64_t hist_sq_stride, const void *d_hist_len, const void *d_hist_guides, int64_t hist_guide_stride,
@@ -1076,55 +963,17 @@ int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride,
                              void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_sum || !d_guides || !d_hist || !d_hist_len || !d_hist_guides || !d_out || !d_out_len)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a buffer is NULL");
-    if (!tp) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: tp is NULL");
-    if (n < 1 || n > (1 << 24)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: n outside 1..2^24");
-    if (!(std::isfinite(tp->depth_tol) && tp->depth_tol >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: depth_tol must be finite and >= 0");
-    if (!(tp->normal_cos >= -1.0 && tp->normal_cos <= 1.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: normal_cos outside [-1, 1]");
-    if (!(std::isfinite(tp->max_history) && tp->max_history >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: max_history must be finite and >= 0");
-    if (tp->reserved[0] != 0 || tp->reserved[1] != 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: reserved must be 0");
     const rt::View &v = ctx->view;
-    if (!v.have_cam) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: rt_set_camera has not been called");
-    if (!v.have_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: rt_set_raygen has not been called");
-    if (v.explicit_grid) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: an explicit rt_set_pixel_loc grid cannot be reprojected");
-    if (v.dy == 0.0 || v.dz == 0.0) return fail(ctx, RT_ERR_STATE, "rt_film_temporal_moments: the grid's dy or dz is 0");
-    bool finite = true;
-    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(v.cam_o[i]) && std::isfinite(tp->prev_origin[i]);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v.cam_R[i]) && std::isfinite(tp->prev_rotation[i]);
-    if (!finite) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a camera entry is not finite");
-    const long long npx = (long long)v.w * v.h;
-    if (npx > RT_FILM_MAX_PIXELS) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: w*h above RT_FILM_MAX_PIXELS");
-    if (sum_stride < npx || guide_stride < npx || hist_stride < npx || hist_guide_stride < npx || out_stride < npx)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a plane stride is smaller than the frame");
-    const void *const ins[] = {d_sum, d_guides, d_hist, d_hist_len, d_hist_guides};
-    for (const void *in : ins)
-        if (d_out == in || d_out_len == in) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
-    if (d_out == d_out_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
-    if (!d_sq || !d_hist_sq || !d_out_sq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_sq, d_hist_sq or d_out_sq is NULL");
-    if (sq_stride < npx || hist_sq_stride < npx || out_sq_stride < npx)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: a plane stride of the second moment is smaller than the frame");
-    const void *const others[] = {d_sum, d_sq, d_guides, d_hist, d_hist_sq, d_hist_len, d_hist_guides, d_out, d_out_len};
-    for (const void *o : others)
-        if (d_out_sq == o) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out_sq must be a buffer of its own");
-    if (d_out == d_sq || d_out == d_hist_sq || d_out_len == d_sq || d_out_len == d_hist_sq)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_temporal_moments: d_out and d_out_len must be buffers of their own");
+    int rc = refuse(ctx, rt::check_film_temporal_moments(v, d_sum, sum_stride, d_sq, sq_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_sq,
+                                                         hist_sq_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out, out_stride, d_out_sq,
+                                                         out_sq_stride, d_out_len));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     rt::TemporalMomentsArgs m;
-    rt::TemporalArgs &a = m.t;
-    a.sum = (const double *)d_sum; a.guides = (const float *)d_guides; a.hist = (const double *)d_hist;
-    a.hist_len = (const float *)d_hist_len; a.hist_guides = (const float *)d_hist_guides;
-    a.out = (double *)d_out; a.out_len = (float *)d_out_len;
-    a.sum_stride = sum_stride; a.guide_stride = guide_stride; a.hist_stride = hist_stride; a.hist_guide_stride = hist_guide_stride;
-    a.out_stride = out_stride;
-    a.w = v.w; a.h = v.h; a.n = (double)n;
-    a.px = v.px; a.y0 = v.y0; a.dy = v.dy; a.z0 = v.z0; a.dz = v.dz;
-    std::memcpy(a.o, v.cam_o, sizeof a.o); std::memcpy(a.R, v.cam_R, sizeof a.R);
-    std::memcpy(a.po, tp->prev_origin, sizeof a.po); std::memcpy(a.pR, tp->prev_rotation, sizeof a.pR);
-    a.depth_tol = tp->depth_tol; a.normal_cos = tp->normal_cos; a.max_history = tp->max_history;
-    m.sq = (const double *)d_sq; m.hist_sq = (const double *)d_hist_sq; m.out_sq = (double *)d_out_sq;
-    m.sq_stride = sq_stride; m.hist_sq_stride = hist_sq_stride; m.out_sq_stride = out_sq_stride;
-    hipLaunchKernelGGL(rt::temporal_moments_kernel, dim3(rt::temporal_grid(npx, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
+    rt::temporal_args(m.t, v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out,
+                      out_stride, d_out_len);
+    rt::temporal_moments_args(m, d_sq, sq_stride, d_hist_sq, hist_sq_stride, d_out_sq, out_sq_stride);
+    hipLaunchKernelGGL(rt::temporal_moments_kernel, dim3(rt::temporal_grid((long long)v.w * v.h, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
                        stream_of(ctx, stream), m);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
@@ -1132,68 +981,24 @@ int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride,
 
 // The variance-guided filter on a temporal mean: the prepare launch takes each pixel's variance from its own moments or, where its
 // history is shorter than spatial_below, from its object's neighbours (rt_denoise_var.h: denoise_var_prepare_len_kernel); the levels
-// are rt_film_denoise_variance's launches, with its plan of which buffer gets which write.
+// are rt_film_denoise_variance's.
 int rt_film_denoise_variance_temporal(rt_ctx *ctx, const void *d_mean, int64_t mean_stride, const void *d_msq, int64_t msq_stride,
                                       const void *d_len, int ws, int h, const void *d_guides, int64_t guide_stride,
                                       const rt_denoise_variance *dv, double spatial_below, void *d_out, int64_t out_stride, void *d_work,
                                       int64_t work_stride, void *stream)
 {
     if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_mean) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_mean is NULL");
-    if (!d_msq) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_msq is NULL");
-    if (!d_len) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_len is NULL");
-    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_guides is NULL");
-    if (!dv) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: dv is NULL");
-    if (!d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out is NULL");
-    if (dv->levels < 0 || dv->levels > 6) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: levels outside 0..6");
     int nsq = -1;
-    for (int i = 0; i <= 10; ++i) if (dv->normal_shin == (1 << i)) nsq = i;
-    if (nsq < 0) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: normal_shin must be 1, 2, 4, ..., 1024");
-    if (!(std::isfinite(dv->kappa) && dv->kappa >= 0.0)) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: kappa must be finite and >= 0");
-    if (!(std::isfinite(dv->var_floor) && dv->var_floor >= 0.0))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: var_floor must be finite and >= 0");
-    if (dv->demodulate != 0 && dv->demodulate != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: demodulate must be 0 or 1");
-    if (dv->prefilter != 0 && dv->prefilter != 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: prefilter must be 0 or 1");
-    if (!(std::isfinite(spatial_below) && spatial_below >= 0.0))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: spatial_below must be finite and >= 0");
-    if (ws < 1 || h < 1 || (long long)ws * h > RT_FILM_MAX_PIXELS)
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: ws*h outside 1..RT_FILM_MAX_PIXELS");
-    const long long npx = (long long)ws * h;
-    if (mean_stride < npx || msq_stride < npx || guide_stride < npx || out_stride < npx || (d_work && work_stride < npx))
-        return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: a plane stride is smaller than the frame");
-    if (!d_work && dv->levels >= 1) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_work is NULL with levels >= 1");
-    for (const void *in : {d_mean, d_msq, d_len, d_guides})
-        if (d_out == in || (d_work && d_work == in))
-            return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out and d_work must be buffers of their own");
-    if (d_work && d_work == d_out) return fail(ctx, RT_ERR_BAD_ARG, "rt_film_denoise_variance_temporal: d_out and d_work must be buffers of their own");
+    int rc = refuse(ctx, rt::check_film_denoise_variance_temporal(d_mean, mean_stride, d_msq, msq_stride, d_len, ws, h, d_guides, guide_stride, dv,
+                                                                  spatial_below, d_out, out_stride, d_work, work_stride, nsq));
+    if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
-    const int levels = dv->levels;
-    const dim3 grid(rt::denoise_grid(npx, ctx->cu_count));
-    const bool first_to_out = rt::denoise_var_to_out(levels, 0);
-    rt::DenoiseVarLenArgs p;
-    std::memset(&p, 0, sizeof p);
-    p.mean = (const double *)d_mean; p.mean_stride = mean_stride; p.msq = (const double *)d_msq; p.msq_stride = msq_stride;
-    p.len = (const float *)d_len; p.guides = (const float *)d_guides; p.guide_stride = guide_stride;
-    p.dst = (double *)(first_to_out ? d_out : d_work); p.dst_stride = first_to_out ? out_stride : work_stride;
-    p.ws = ws; p.h = h; p.demod = dv->demodulate; p.copy = levels == 0; p.spatial_below = spatial_below;
-    hipLaunchKernelGGL(rt::denoise_var_prepare_len_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, p);
-    RT_HIP(ctx, hipGetLastError());
-    rt::DenoiseVarArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.guides = (const float *)d_guides; a.guide_stride = guide_stride;
-    a.ws = ws; a.h = h; a.nsq = nsq; a.demod = dv->demodulate; a.prefilter = dv->prefilter;
-    a.k2 = dv->kappa * dv->kappa; a.var_floor = dv->var_floor;
-    a.src = p.dst; a.src_stride = p.dst_stride;
-    for (int k = 1; k <= levels; ++k) {
-        const bool to_out = rt::denoise_var_to_out(levels, k);
-        a.dst = (double *)(to_out ? d_out : d_work); a.dst_stride = to_out ? out_stride : work_stride;
-        rt::denoise_var_level(a, levels, k - 1);
-        hipLaunchKernelGGL(rt::denoise_var_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st, a);
-        RT_HIP(ctx, hipGetLastError());
-        a.src = a.dst; a.src_stride = a.dst_stride;
-    }
-    return RT_OK;
+    return variance_filter(ctx, rt::denoise_var_common(d_guides, guide_stride, ws, h, dv, nsq), dv->levels, {d_out, out_stride, d_work, work_stride}, st,
+                           [&](const rt::FilmWrite &w, dim3 grid) {
+        hipLaunchKernelGGL(rt::denoise_var_prepare_len_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st,
+                           rt::denoise_var_len_args(w, d_mean, mean_stride, d_msq, msq_stride, d_len, ws, h, d_guides, guide_stride, dv, spatial_below));
+    });
 }
 
 // The staging planes grown where the frame is larger than any before, one launch into them and one copy per output to host memory,

@@ -8,6 +8,7 @@
 // or 1-byte accesses on planes whose base is not (a caller's plane stride may be odd), a scalar tail for the last npx mod 4
 // elements, a grid capped near 8 blocks per CU with a grid-stride loop, no LDS, no scratch, 64-bit plane offsets.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -73,9 +74,6 @@ RT_FILM_HD inline uint8_t film_clip(double c)
     return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
 }
 
-#if defined(__HIPCC__)
-
-constexpr int FILM_THREADS = 256;
 constexpr int FILM_BATCH = 4;                       // passes one add kernel folds
 constexpr size_t FILM_SCRATCH_MAX = 256u << 20;      // bytes of pass frames beyond which passes go one by one
 
@@ -104,6 +102,10 @@ struct FilmResolveArgs {
     int h, rgb, hwc;
     FilmTone tone;
 };
+
+#if defined(__HIPCC__)
+
+constexpr int FILM_THREADS = 256;
 
 // 16 bytes per lane as the compiler's own vector types: one global_load / global_store _dwordx4 each
 typedef double film_d2 __attribute__((ext_vector_type(2)));

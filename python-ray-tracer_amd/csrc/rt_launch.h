@@ -153,10 +153,12 @@ inline void dispatch_part(KParams &k, int nframes, unsigned grid, long long fram
     k.seq_offset = os.seq_offset;
 }
 
-// An entry check's answer: RT_OK, or the code and the rt_last_error text.
+// An entry check's answer: RT_OK, or the code and the rt_last_error text ("entry: msg" where the refusal names its entry:
+// rt_film_launch.h).
 struct Refusal {
     int code = RT_OK;
     const char *msg = nullptr;
+    const char *entry = nullptr;
 };
 
 // What every launch needs before anything else: a scene, a camera, a ray grid.

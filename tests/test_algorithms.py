@@ -516,3 +516,157 @@ def test_launch_params_are_the_recorded_ones(tmp_path):
     with open(checks_path) as f:
         lines = [ln.rstrip("\n").split("\t") for ln in f]
     assert [(n, (int(c), m)) for n, c, m in lines] == LAUNCH_CHECKS
+
+
+def _film_checks(group, entry, cases):
+    """(name, (code, text)) per case of one entry: text None is an accepted call, a text that starts with "=" goes out as it is (the
+    rest carry the entry's name), a case given as (name, text, code) has a code of its own."""
+    out = []
+    for c in cases:
+        name, text, code = c if len(c) == 3 else (c[0], c[1], -1)
+        out.append((f"{group}/{name}", _OK if text is None else (code, text[1:] if text.startswith("=") else f"{entry}: {text}")))
+    return out
+
+
+def _accumulate_checks(group, entry, moments):
+    own, sq_stride = ("d_sq and d_sum must be buffers of their own", "sq_stride smaller than the slab") if moments else (None, None)
+    return _film_checks(group, entry, [
+        ("ok", None), ("params_null", "=params is NULL"), ("no_scene", "=rt_set_scene has not been called", -4),
+        ("columns", "=column range must satisfy 0 <= x0 < x1 <= w"), ("passes", "passes < 1"), ("passes_and_sum_null", "passes < 1"),
+        ("sum_null", "d_sum is NULL"), ("sq_null", "d_sq is NULL" if moments else None), ("sq_is_sum", own),
+        ("sq_is_sum_and_sum_stride", own or "sum_stride smaller than the slab"), ("above_max", "(x1-x0)*h above RT_FILM_MAX_PIXELS"),
+        ("sum_stride", "sum_stride smaller than the slab"), ("sum_stride_of_a_slab", "sum_stride smaller than the slab"),
+        ("sq_stride", sq_stride), ("slab_ok", None)])
+
+
+def _filter_checks(group, entry, which):
+    """rt_film_denoise (which 0), rt_film_denoise_variance (1), rt_film_denoise_variance_temporal (2)."""
+    area, stride, shin = "ws*h outside 1..RT_FILM_MAX_PIXELS", "a plane stride is smaller than the frame", "normal_shin must be 1, 2, 4, ..., 1024"
+    own = "d_out and d_work must be buffers of their own"
+    names = [("sum", "sq", "len"), ("d_sum", None, None), ("d_sum", "d_sq", None), ("d_mean", "d_msq", "d_len")][which + 1]
+    c = [("ok", None), ("sum_null", f"{names[0]} is NULL")]
+    c += [("sq_null", f"{names[1]} is NULL")] if which else []
+    c += [("len_null", "d_len is NULL")] if which == 2 else []
+    c += [("guides_null", "d_guides is NULL"), ("settings_null", "dv is NULL" if which else "dn is NULL"), ("out_null", "d_out is NULL")]
+    c += [("n", "n < 1")] if which == 0 else [("n", "n < 2")] if which == 1 else []
+    c += [("levels_below", "levels outside 0..6"), ("levels_above", "levels outside 0..6"), ("levels_six_ok", None),
+          ("normal_shin_three", shin), ("normal_shin_above", shin), ("normal_shin_zero", shin)]
+    if which == 0:
+        sigma = "sigma must be 0, or finite and > 0"
+        c += [("sigma_negative", sigma), ("sigma_nan", sigma), ("sigma_inf", sigma), ("sigma_ok", None),
+              ("demodulate", "demodulate must be 0 or 1"), ("reserved", "reserved must be 0")]
+    else:
+        c += [("kappa_negative", "kappa must be finite and >= 0"), ("kappa_nan", "kappa must be finite and >= 0"),
+              ("var_floor_negative", "var_floor must be finite and >= 0"), ("var_floor_inf", "var_floor must be finite and >= 0"),
+              ("demodulate", "demodulate must be 0 or 1"), ("prefilter", "prefilter must be 0 or 1")]
+    if which == 2:
+        c += [(f"spatial_below_{x}", "spatial_below must be finite and >= 0") for x in ("negative", "nan", "inf")]
+    c += [("ws", area), ("h", area), ("above_max", area), ("sum_stride", stride)]
+    c += [("sq_stride", stride)] if which else []
+    c += [("guide_stride", stride), ("out_stride", stride), ("work_stride", stride),
+          ("no_work", "d_work is NULL with levels >= 1" if which else "d_work is NULL with levels >= 2"), ("no_work_ok", None), ("out_is_sum", own)]
+    c += [("out_is_sq", own)] if which else []
+    c += [("out_is_len", own)] if which == 2 else []
+    c += [("out_is_guides", own), ("work_is_sum", own)]
+    c += [("work_is_sq", own)] if which else []
+    c += [("work_is_len", own)] if which == 2 else []
+    c += [("work_is_guides", own), ("work_is_out", own)]
+    c += [("len_is_no_input_ok", None)] if which < 2 else []
+    return _film_checks(group, entry, c)
+
+
+def _temporal_checks(group, entry, moments):
+    null, stride, own = "a buffer is NULL", "a plane stride is smaller than the frame", "d_out and d_out_len must be buffers of their own"
+    finite = "a camera entry is not finite"
+    c = [("ok", None)] + [(f"{b}_null", null) for b in ("sum", "guides", "hist", "hist_len", "hist_guides", "out", "out_len")]
+    c += [("tp_null", "tp is NULL"), ("n_zero", "n outside 1..2^24"), ("n_above", "n outside 1..2^24"), ("n_at_max_ok", None),
+          ("depth_tol_negative", "depth_tol must be finite and >= 0"), ("depth_tol_nan", "depth_tol must be finite and >= 0"),
+          ("normal_cos_above", "normal_cos outside [-1, 1]"), ("normal_cos_nan", "normal_cos outside [-1, 1]"),
+          ("max_history_negative", "max_history must be finite and >= 0"), ("max_history_inf", "max_history must be finite and >= 0"),
+          ("reserved0", "reserved must be 0"), ("reserved1", "reserved must be 0"),
+          ("no_camera", "rt_set_camera has not been called", -4), ("no_grid", "rt_set_raygen has not been called", -4),
+          ("explicit_grid", "an explicit rt_set_pixel_loc grid cannot be reprojected", -4),
+          ("dy_zero", "the grid's dy or dz is 0", -4), ("dz_zero", "the grid's dy or dz is 0", -4),
+          ("camera_nan", finite), ("rotation_inf", finite), ("prev_origin_nan", finite), ("prev_rotation_inf", finite),
+          ("above_max", "w*h above RT_FILM_MAX_PIXELS")]
+    c += [(f"{s}_stride", stride) for s in ("sum", "guide", "hist", "hist_guide", "out")]
+    ins = ("sum", "guides", "hist", "hist_len", "hist_guides")
+    c += [(f"out_is_{b}", own) for b in ins] + [(f"out_len_is_{b}", own) for b in ins] + [("out_len_is_out", own)]
+    if moments:
+        sq_null, sq_stride = "d_sq, d_hist_sq or d_out_sq is NULL", "a plane stride of the second moment is smaller than the frame"
+        c += [("sq_null", sq_null), ("hist_sq_null", sq_null), ("out_sq_null", sq_null)]
+        c += [("sq_stride", sq_stride), ("hist_sq_stride", sq_stride), ("out_sq_stride", sq_stride)]
+        c += [(f"out_sq_is_{b}", "d_out_sq must be a buffer of its own")
+              for b in ("sum", "sq", "guides", "hist", "hist_sq", "hist_len", "hist_guides", "out", "out_len")]
+        c += [("out_is_sq", own), ("out_is_hist_sq", own), ("out_len_is_sq", own), ("out_len_is_hist_sq", own)]
+    return _film_checks(group, entry, c)
+
+
+_AREA = "ws*h outside 1..RT_FILM_MAX_PIXELS"
+# (code, rt_last_error text) per case of tests/algo/film_launch_check.cpp's entry_checks(), in its order: the texts of mi355rt.hip as it
+# was before the film entries' checks became functions of rt_film_launch.h.  Where a case has two bad arguments (the program says
+# which), the text is that of the rule the entry looked at first.
+FILM_LAUNCH_CHECKS = (
+    _accumulate_checks("accumulate", "rt_film_accumulate", False) + _accumulate_checks("moments", "rt_film_accumulate_moments", True) +
+    _film_checks("resolve", "rt_film_resolve", [
+        ("ok", None), ("sum_null", "d_sum is NULL"), ("tone_null", "tone is NULL"), ("ws", _AREA), ("h", _AREA), ("above_max", _AREA),
+        ("at_max_ok", None), ("ws_and_n", _AREA), ("n", "n < 1"),
+        ("exposure_zero", "exposure must be finite and > 0"), ("exposure_inf", "exposure must be finite and > 0"),
+        ("exposure_nan", "exposure must be finite and > 0"), ("white_negative", "white must be 0, or finite and > 0"),
+        ("white_nan", "white must be 0, or finite and > 0"), ("white_ok", None), ("gamma", "gamma must be 1 or 2"),
+        ("flags", "unknown flag bit"), ("both_null", "=both output pointers are NULL"), ("sum_stride", "sum_stride smaller than the frame"),
+        ("hwc_f32", "=RT_FLAG_U8_HWC re-uses out_stride as the image row pitch: resolve the float32 buffer in a separate call"),
+        ("hwc_pitch", "=row pitch smaller than the frame width"), ("hwc_ok", None), ("out_stride", "=out_stride smaller than the frame")]) +
+    _filter_checks("denoise", "rt_film_denoise", 0) + _filter_checks("variance", "rt_film_denoise_variance", 1) +
+    _filter_checks("variance_temporal", "rt_film_denoise_variance_temporal", 2) +
+    _temporal_checks("temporal", "rt_film_temporal", False) + _temporal_checks("temporal_moments", "rt_film_temporal_moments", True))
+
+# fields per kind of row of tests/algo/film_launch_check.cpp
+FILM_LAUNCH_KINDS = {0: ("TemporalArgs", 47), 1: ("TemporalMomentsArgs", 53), 2: ("FilmResolveArgs", 14), 3: ("FilmBatch", 3), 4: ("FilmAddArgs", 7),
+                     5: ("FilmAdd2Args", 9), 6: ("DenoiseArgs", 16), 7: ("DenoiseVarArgs", 22), 8: ("DenoiseVarLenArgs", 14),
+                     9: ("DenoiseVarArgs of the temporal filter's levels", 22)}
+
+
+def test_film_launch_arguments_and_checks_are_the_recorded_ones(tmp_path):
+    """python-ray-tracer_amd/csrc/rt_film_launch.h, what the nine film entries decide before they touch the device, under
+    AddressSanitizer and UndefinedBehaviorSanitizer over the table of tests/algo/film_launch_check.cpp.  The entry checks: every
+    refusal of every entry, its accepted call, and two bad arguments at once wherever the order of the rules shows; codes and texts
+    are compared with FILM_LAUNCH_CHECKS above.  The arguments: TemporalArgs and TemporalMomentsArgs for two views x two previous
+    cameras; FilmResolveArgs for planar RGB, planar BGR and HWC; the film's batch plan with the add and add2 arguments of every add
+    launch for 1, 5 and 128 pixels x 1, 4 and 9 passes and for a frame large enough that its passes go one by one; DenoiseArgs,
+    DenoiseVarArgs and DenoiseVarLenArgs of every write of levels 0..6 with and without demodulation.  217 rows, every field of each
+    (floats as raw bits, pointers as made-up addresses) exactly what tests/golden/film_launch_args.npz holds: what the library built
+    before this became a header, recorded by a program with this one's table and row writer that included that commit's rt_film.h,
+    rt_denoise.h, rt_denoise_var.h and rt_temporal.h, held that commit's film_queue_passes(), rt_film_resolve(), rt_film_denoise(),
+    rt_film_denoise_variance(), rt_film_temporal(), rt_film_temporal_moments() and rt_film_denoise_variance_temporal() fill
+    expressions and loops copied verbatim, was built with hipcc for gfx950 and ran on a CPU without a HIP call.  The program itself
+    checks every filter's plan: each write reads what the write before it wrote and never the buffer it writes, and the last lands
+    in d_out."""
+    import numpy as np
+    exe, got_path, checks_path = str(tmp_path / "film_launch_check"), str(tmp_path / "got.bin"), str(tmp_path / "checks.txt")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "film_launch_check.cpp")])
+    res = subprocess.run([exe, got_path, checks_path], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == f"records=217 checks={len(FILM_LAUNCH_CHECKS)} ok", res.stdout
+    with open(checks_path) as f:
+        lines = [ln.rstrip("\n").split("\t") for ln in f]
+    got_checks = [(n, (int(c), m)) for n, c, m in lines]
+    assert got_checks == FILM_LAUNCH_CHECKS, [(g, w) for g, w in zip(got_checks, FILM_LAUNCH_CHECKS) if g != w][:6]
+    want = np.load(os.path.join(REPO, "tests", "golden", "film_launch_args.npz"))["rows"]
+    got = np.fromfile(got_path, np.int64).reshape(-1, 4 + 53)
+    assert got.shape == want.shape == (217, 57)
+    assert np.array_equal(got[:, :4], want[:, :4])
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, [(FILM_LAUNCH_KINDS[int(got[i, 0])][0], got[i, 1:3].tolist(), int(j) - 4, int(got[i, j]), int(want[i, j])) for i, j in bad[:8]]
+    # what the table is there for: every kind of row with its number of fields, both layouts of the resolve, batches and single
+    # passes, every write of every number of levels with both buffers written
+    kind = got[:, 0]
+    assert {k: int((kind == k).sum()) for k in range(10)} == {0: 4, 1: 4, 2: 3, 3: 10, 4: 20, 5: 20, 6: 44, 7: 56, 8: 14, 9: 42}
+    assert all((got[kind == k, 3] == n).all() for k, (_, n) in FILM_LAUNCH_KINDS.items())
+    assert got[kind == 2][:, 4 + 8].tolist() == [0, 0, 1] and got[kind == 2][:, 4 + 7].tolist() == [1, 0, 0]
+    plan = got[kind == 3]
+    assert plan[:, 4 + 2].tolist() == [1, 4, 4, 1, 4, 4, 1, 4, 4, 1] and plan[-1, 4 + 1] * 4 > 256 << 20 >= plan[-1, 4 + 1] * 3
+    assert set(got[kind == 4][:, 4 + 5].tolist()) == {1, 4} and set(got[kind == 4][:, 4 + 6].tolist()) == {0, 1}
+    for k, dst in ((6, 2), (7, 4), (9, 4)):
+        assert len(set(got[kind == k][:, 4 + dst].tolist())) == 2
