@@ -7,6 +7,7 @@
                                   [--passes N [--exposure E] [--white W] [--gamma2]]
                                   [--denoise [--denoise-levels N]] [--guides PREFIX]
                                   [--denoise-variance [--kappa K]]
+                                  [--bloom [STRENGTH] [--bloom-threshold T] [--bloom-levels N]]
                                   [--orbit K --temporal [--orbit-step DEG] [--denoise-variance [--spatial-below L]]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
@@ -38,6 +39,10 @@ PREFIX_depth.png, PREFIX_albedo.png and PREFIX_id.png.
 keeps a sum of squares and every pixel's colour tolerance is --kappa standard deviations of its mean, default the library's), with
 --denoise-levels N iterations; without --passes it takes four passes.  For example --sky --soft --shadow-samples 1 --passes 8
 --denoise-variance --white 400.
+
+--bloom [STRENGTH] adds glare before the tone curve (rt_film_bloom): the light above --bloom-threshold T (default 255) is blurred at
+--bloom-levels N scales (default 6) and STRENGTH of it (default 0.25) is added to the mean, filtered or not; without --passes it takes
+four passes.  For example --sky --dof 0.1 --passes 64 --white 400 --bloom: the sun glows instead of ending in a hard-edged white disc.
 
 --orbit K --passes N --temporal renders K camera steps of an orbit about the point the camera looks at (--orbit-step degrees each,
 default 2), N passes per step, and carries the film through every move (rt_film_temporal: the previous mean reprojected through
@@ -95,6 +100,10 @@ def main():
     ap.add_argument("--kappa", type=float, default=None, metavar="K", help="--denoise-variance: colour tolerance in standard deviations of the mean")
     ap.add_argument("--spatial-below", type=float, default=None, metavar="L",
                     help="--temporal --denoise-variance: pixels with a history shorter than L passes take their variance from their neighbours")
+    ap.add_argument("--bloom", type=float, nargs="?", const=0.25, default=None, metavar="STRENGTH",
+                    help="glare around what is brighter than --bloom-threshold: this share of its light is spread (four passes unless --passes)")
+    ap.add_argument("--bloom-threshold", type=float, default=255.0, metavar="T", help="--bloom: what is brighter than this glows")
+    ap.add_argument("--bloom-levels", type=int, default=6, metavar="N", help="--bloom: scales of the blur, 0..8")
     ap.add_argument("--guides", default=None, metavar="PREFIX", help="write the first-hit guides as PREFIX_normal/_depth/_albedo/_id.png")
     ap.add_argument("--orbit", type=int, default=0, metavar="K", help="--temporal: render K camera steps of an orbit and write the last frame")
     ap.add_argument("--orbit-step", type=float, default=2.0, metavar="DEG", help="--orbit: degrees per camera step")
@@ -102,7 +111,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    if (a.denoise or a.temporal or a.denoise_variance) and a.passes <= 0:
+    if (a.denoise or a.temporal or a.denoise_variance or a.bloom is not None) and a.passes <= 0:
         a.passes = 4
     if a.denoise_variance and a.denoise:
         ap.error("--denoise-variance stands in place of --denoise")
@@ -204,7 +213,9 @@ def main():
                     if a.denoise_variance:
                         film.denoise(variance=True, temporal=True, levels=a.denoise_levels, **var_kw)
                 ms = r.timer_end() / (a.orbit * a.passes)
-                image = film.resolve(denoised=a.denoise or a.denoise_variance, temporal=True, **tone)[0]
+                if a.bloom is not None:
+                    film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, denoised=a.denoise or a.denoise_variance, temporal=True)
+                image = film.resolve(denoised=a.denoise or a.denoise_variance, temporal=True, bloom=a.bloom is not None, **tone)[0]
         elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
             with pkg.Film(r, moments=a.denoise_variance) as film:
                 film.accumulate(p, a.passes)
@@ -212,8 +223,10 @@ def main():
                     film.denoise(levels=a.denoise_levels)
                 if a.denoise_variance:
                     film.denoise(variance=True, levels=a.denoise_levels, **({} if a.kappa is None else dict(kappa=a.kappa)))
+                if a.bloom is not None:                         # the glow of the source that the resolve shows, before the tone curve
+                    film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, denoised=a.denoise or a.denoise_variance)
                 image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags,
-                                     denoised=a.denoise or a.denoise_variance)[0]
+                                     denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None)[0]
                 r.timer_begin()
                 for _ in range(a.frames):                       # (timed: one more pass into the sum, per pass)
                     film.accumulate(p, 1)

@@ -814,6 +814,53 @@ int rt_film_denoise_variance_temporal(rt_ctx *ctx, const void *d_mean, int64_t m
                                       const rt_denoise_variance *dv, double spatial_below,
                                       void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
 
+/* Bloom: glare around what is brighter than white.  After rt_film_resolve's tone curve a sun of 5000 colour units and a wall of
+ * 400 are the same white; rt_film_bloom spreads a share of the light above a threshold into its neighbourhood, in linear colour,
+ * before the curve.  RT_ABI_VERSION is unchanged: callers detect this entry point by its symbol.
+ *
+ * rt_film_bloom: d_sum is a film sum of n passes of a ws x h frame or slab: three float64 planes, element [c, x, y] at
+ * c*sum_stride + x*h + y, like every film buffer; with n = 1 it is a mean, what rt_film_denoise* or rt_film_temporal* wrote (a
+ * four-plane buffer is fine: only planes 0..2 are read).  d_out, three float64 planes, receives the mean plus the glow: the caller
+ * tone-maps it with rt_film_resolve and n = 1.  d_work is the caller's and holds RT_BLOOM_WORK_PLANES float64 planes of work_stride
+ * (the library allocates nothing); it may be NULL when levels == 0.  Which work planes hold what at which level is the library's
+ * business.  d_out and d_work must not overlap d_sum or each other: equal pointers are refused, partial overlap is the caller's
+ * error.
+ * Per pixel p = (x, y) and channel c in float64, no fused multiply-add, in this order:
+ *   m_c = s[c][p] / (double)n;      out[c][p] = m_c
+ *   levels == 0:  nothing else is evaluated
+ *   mx = m_0 > m_1 ? m_0 : m_1;   mx = mx > m_2 ? mx : m_2
+ *   mx > threshold:  g = (mx - threshold) / mx;   b_0[c][p] = m_c > 0 ? m_c * g : +0.0        else:  b_0[c][p] = +0.0
+ *   wl = strength / (double)levels   (once)
+ *   for i = 0 .. levels-1:    step = 1 << i;     k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *       t[c][x,y]       = T after:  T = +0.0;  for d = -2..2:  qx = x + step*d;  0 <= qx < ws:  T = T + k[d] * b_i[c][qx, y]
+ *       b_{i+1}[c][x,y] = B after:  B = +0.0;  for d = -2..2:  qy = y + step*d;  0 <= qy < h:   B = B + k[d] * t[c][x, qy]
+ *       out[c][p] = out[c][p] + wl * b_{i+1}[c][p]
+ * The bright pass scales the pixel by its brightest channel, so the glow keeps the pixel's hue.  A tap outside the frame is skipped
+ * and not renormalised: light that leaves the frame is lost.  Each level is the separable B3 a-trous blur the denoisers use, without
+ * any edge-stopping.  The glow is the mean of the `levels` scales times strength: a tight core and a wide tail, which away from
+ * the borders carries exactly strength times the bright light.  There is no exp(), pow() or sqrt(): the bytes do not depend on a
+ * math library.  Sums are assumed finite: a non-finite sum gives unspecified values but does not fault.
+ * The call sees only the buffer it is given: taps do not cross its edge, so a multi-rank caller blooms the assembled frame.
+ * RT_BLOOM_NO_TILES makes every level run as two gather kernels; without it the levels with small steps run as one kernel that
+ * stages a tile in LDS.  The bytes are the same either way: the flag is for A/B measurements and tests.
+ * RT_ERR_BAD_ARG, in this order, for: a NULL d_sum, bl or d_out; ws*h outside 1..RT_FILM_MAX_PIXELS; n < 1; levels outside
+ * 0..RT_BLOOM_MAX_LEVELS; a threshold that is not (finite and >= 0); a strength that is not (finite and >= 0); an unknown flag
+ * bit; d_work == NULL with levels >= 1; sum_stride, out_stride or (when d_work is given) work_stride < ws*h; d_out or d_work equal
+ * to d_sum or to each other.  The outputs are then untouched.  Asynchronous on `stream`; it needs no scene. */
+#define RT_BLOOM_MAX_LEVELS  8
+#define RT_BLOOM_WORK_PLANES 6
+#define RT_BLOOM_NO_TILES    1      /* rt_bloom.flags: gather at every level (A/B and tests) */
+
+typedef struct rt_bloom {
+    double  threshold;   /* colour units, finite, >= 0: what is brighter than this glows */
+    double  strength;    /* finite, >= 0: the share of the bright light that is spread */
+    int32_t levels;      /* 0..RT_BLOOM_MAX_LEVELS */
+    int32_t flags;       /* RT_BLOOM_NO_TILES; every other bit 0 */
+} rt_bloom;              /* 24 bytes */
+
+int rt_film_bloom(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl,
+                  void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

@@ -17,6 +17,7 @@ from . import film            # noqa: F401
 from . import denoise         # noqa: F401
 from . import temporal        # noqa: F401
 from . import variance        # noqa: F401
+from . import bloom           # noqa: F401
 from .film import Film        # noqa: F401
 
-__all__ = ["cuda", "denoise", "film", "temporal", "variance", "Film", "Renderer", "RenderError"]
+__all__ = ["bloom", "cuda", "denoise", "film", "temporal", "variance", "Film", "Renderer", "RenderError"]

@@ -19,6 +19,7 @@ RT_SKY_DOUBLES = 24
 RT_FILM_MAX_PIXELS = 1 << 27
 RT_GUIDE_PLANES = 8
 RT_TEMPORAL_MAX_N = 1 << 24          # rt_film_temporal: the most passes one call blends in
+RT_BLOOM_MAX_LEVELS, RT_BLOOM_WORK_PLANES, RT_BLOOM_NO_TILES = 8, 6, 1
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -73,6 +74,12 @@ class rt_temporal(C.Structure):
                 ("max_history", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+class rt_bloom(C.Structure):
+    """rt_film_bloom's settings (include/mi355rt.h; the arithmetic in numpy: bloom.bloom_reference): threshold and strength finite and
+    >= 0; levels 0..RT_BLOOM_MAX_LEVELS; flags RT_BLOOM_NO_TILES only.  24 bytes."""
+    _fields_ = [("threshold", C.c_double), ("strength", C.c_double), ("levels", C.c_int32), ("flags", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
 _dp, _fp, _vp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p
 PROTOTYPES = {
@@ -125,6 +132,7 @@ PROTOTYPES = {
                                            C.c_int64, C.POINTER(rt_temporal), _vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "rt_film_denoise_variance_temporal": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, C.c_int64,
                                                     C.POINTER(rt_denoise_variance), C.c_double, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "rt_film_bloom": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_bloom), _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -147,7 +155,7 @@ PROTOTYPES = {
 # Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
 # times such a build beside this one), and Renderer raises where one is called.
 LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance",
-                 "rt_film_temporal_moments", "rt_film_denoise_variance_temporal")
+                 "rt_film_temporal_moments", "rt_film_denoise_variance_temporal", "rt_film_bloom")
 
 _lib = None
 

@@ -7,6 +7,7 @@
 // sets, scratch buffers, scene readers (rt_streams.h).
 #include "../../include/mi355rt.h"
 #include "rt_device.h"
+#include "rt_bloom.h"
 #include "rt_denoise.h"
 #include "rt_denoise_var.h"
 #include "rt_feedback.h"
@@ -999,6 +1000,32 @@ int rt_film_denoise_variance_temporal(rt_ctx *ctx, const void *d_mean, int64_t m
         hipLaunchKernelGGL(rt::denoise_var_prepare_len_kernel, grid, dim3(rt::DENOISE_THREADS), 0, st,
                            rt::denoise_var_len_args(w, d_mean, mean_stride, d_msq, msq_stride, d_len, ws, h, d_guides, guide_stride, dv, spatial_below));
     });
+}
+
+// Bloom: the launches of rt_bloom.h's plan, one after the other on the stream: the bright pass, then per level two gather kernels or
+// one tile kernel (bloom_plan says which, and which work planes each reads and writes).
+int rt_film_bloom(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl, void *d_out,
+                  int64_t out_stride, void *d_work, int64_t work_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_film_bloom(d_sum, sum_stride, ws, h, n, bl, d_out, out_stride, d_work, work_stride));
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_of(ctx, stream);
+    const rt::BloomPlan plan = rt::bloom_plan(bl->levels, bl->flags);
+    const dim3 grid(rt::bloom_grid((long long)ws * h, ctx->cu_count)), tiles(rt::bloom_tile_blocks(ws, h), 3), threads(rt::BLOOM_THREADS);
+    for (int k = 0; k < plan.count; ++k) {
+        const rt::BloomLaunch &l = plan.l[k];
+        const rt::BloomArgs a = rt::bloom_args(l, d_sum, sum_stride, ws, h, n, bl, d_out, out_stride, d_work, work_stride);
+        if (l.kind == rt::BLOOM_BRIGHT) hipLaunchKernelGGL(rt::bloom_bright_kernel, grid, threads, 0, st, a);
+        else if (l.kind == rt::BLOOM_X) hipLaunchKernelGGL(rt::bloom_x_kernel, grid, threads, 0, st, a);
+        else if (l.kind == rt::BLOOM_Y) hipLaunchKernelGGL(rt::bloom_y_kernel, grid, threads, 0, st, a);
+        else if (l.step == 1) hipLaunchKernelGGL(rt::bloom_tile_kernel<1>, tiles, threads, 0, st, a);
+        else if (l.step == 2) hipLaunchKernelGGL(rt::bloom_tile_kernel<2>, tiles, threads, 0, st, a);
+        else hipLaunchKernelGGL(rt::bloom_tile_kernel<4>, tiles, threads, 0, st, a);
+        RT_HIP(ctx, hipGetLastError());
+    }
+    return RT_OK;
 }
 
 // The staging planes grown where the frame is larger than any before, one launch into them and one copy per output to host memory,

@@ -14,6 +14,7 @@
 #include "rt_denoise.h"
 #include "rt_denoise_var.h"
 #include "rt_temporal.h"
+#include "rt_bloom.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -376,5 +377,52 @@ inline DenoiseVarLenArgs denoise_var_len_args(const FilmWrite &w, const void *d_
     p.ws = ws; p.h = h; p.demod = dv->demodulate; p.copy = dv->levels == 0; p.spatial_below = spatial_below;
     return p;
 }
+
+// rt_film_bloom: its rules in the header's order (the rule macros again: this entry was added behind the filters' arguments).
+#define RT_FILM_RULE(ok, ...) do { if (!(ok)) return film_refusal(e, __VA_ARGS__); } while (0)
+#define RT_FILM_RULES(call) do { const Refusal r_ = (call); if (r_.code != RT_OK) return r_; } while (0)
+
+inline Refusal check_film_bloom(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl, const void *d_out,
+                                int64_t out_stride, const void *d_work, int64_t work_stride)
+{
+    const char *const e = "rt_film_bloom";
+    RT_FILM_RULE(d_sum, "d_sum is NULL");
+    RT_FILM_RULE(bl, "bl is NULL");
+    RT_FILM_RULE(d_out, "d_out is NULL");
+    RT_FILM_RULES(film_area(e, ws, h));
+    RT_FILM_RULE(n >= 1, "n < 1");
+    RT_FILM_RULE(bl->levels >= 0 && bl->levels <= RT_BLOOM_MAX_LEVELS, "levels outside 0..8");
+    RT_FILM_RULE(std::isfinite(bl->threshold) && bl->threshold >= 0.0, "threshold must be finite and >= 0");
+    RT_FILM_RULE(std::isfinite(bl->strength) && bl->strength >= 0.0, "strength must be finite and >= 0");
+    RT_FILM_RULE(!(bl->flags & ~RT_BLOOM_NO_TILES), "unknown flag bit");
+    RT_FILM_RULE(d_work || bl->levels < 1, "d_work is NULL with levels >= 1");
+    const long long npx = (long long)ws * h;
+    RT_FILM_RULES(film_strides(e, npx, {sum_stride, out_stride}));
+    if (d_work) RT_FILM_RULES(film_strides(e, npx, {work_stride}));
+    return film_own(e, {d_out, d_work}, {d_sum}, "d_out and d_work must be buffers of their own");
+}
+
+#undef RT_FILM_RULE
+#undef RT_FILM_RULES
+
+// One launch of rt_film_bloom's plan (rt_bloom.h: bloom_plan): set s of the work planes is planes 3s .. 3s+2 of d_work.
+inline BloomArgs bloom_args(const BloomLaunch &l, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl, void *d_out,
+                            int64_t out_stride, void *d_work, int64_t work_stride)
+{
+    const auto set = [&](int s) { return s < 0 ? (double *)nullptr : (double *)d_work + (long long)3 * s * work_stride; };
+    BloomArgs a;
+    std::memset(&a, 0, sizeof a);
+    if (l.kind == BLOOM_BRIGHT) { a.src = (const double *)d_sum; a.src_stride = sum_stride; }
+    else { a.src = set(l.src); a.src_stride = work_stride; }
+    a.dst = set(l.dst); a.dst_stride = work_stride;
+    a.out = (double *)d_out; a.out_stride = out_stride;
+    a.ws = ws; a.h = h; a.step = l.step;
+    a.n = (double)n; a.threshold = bl->threshold;
+    a.wl = bl->levels > 0 ? bl->strength / (double)bl->levels : 0.0;
+    return a;
+}
+
+static_assert(BLOOM_MAX_LEVELS == RT_BLOOM_MAX_LEVELS && BLOOM_NO_TILES == RT_BLOOM_NO_TILES, "rt_bloom.h restates the header's constants");
+static_assert(2 * 3 == RT_BLOOM_WORK_PLANES, "the plan uses two sets of three work planes");
 
 }  // namespace rt

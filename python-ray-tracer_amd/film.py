@@ -45,10 +45,18 @@ where the history survived, wide at a disocclusion (rt_film_denoise_variance_tem
             film.temporal()
             film.denoise(variance=True, temporal=True)
             image, _ = film.resolve(white=400.0, denoised=True, temporal=True)
+
+Film.bloom and resolve(bloom=True) add the glare of what is brighter than white before the tone curve (rt_film_bloom; its arithmetic
+in numpy is in bloom.py); bloom(denoised=..., temporal=...) takes the source that resolve would show:
+
+        film.accumulate(params, passes=64)
+        film.bloom()                                  # threshold 255, strength 1/4, six scales
+        image, _ = film.resolve(white=400.0, gamma=2, bloom=True)
 """
 import numpy as np
 
 from . import _lib as L
+from .bloom import LEVELS as BLOOM_LEVELS, STRENGTH as BLOOM_STRENGTH, THRESHOLD as BLOOM_THRESHOLD, check_bloom
 from .denoise import check_denoise
 from .temporal import DEPTH_TOL, MAX_HISTORY, NORMAL_COS, check_temporal
 from .variance import KAPPA, SPATIAL_BELOW, VAR_PLANES, check_denoise_variance, check_spatial_below
@@ -162,12 +170,15 @@ class Film:
         self.guides_camera = None                                 # the camera d_guides was last rendered with by this film
         self.guides_stale = False                                 # next_frame() took the guides: d_guides holds an older frame's
         self.denoised_temporal = False                            # d_denoised is the filtered temporal mean
+        self.d_bloom = self.d_bloom_work = None                   # three and six planes: allocated by bloom()
+        self.bloom_passes = 0                                     # the pass count the mean plus glow in d_bloom belongs to (0: none)
+        self.bloom_source = None                                  # (denoised, temporal) of the source bloom() took
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
         names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_temporal_sq", "d_hist", "d_hist_len", "d_hist_sq", "d_hist_guides", "d_guides",
-                 "d_denoised", "d_work")
+                 "d_denoised", "d_work", "d_bloom", "d_bloom_work")
         extra = [getattr(self, n, None) for n in names]
         for n in names:
             setattr(self, n, None)
@@ -215,6 +226,7 @@ class Film:
         self.denoised_passes = 0
         self.denoised_variance = False
         self.temporal_passes = 0
+        self.bloom_passes = 0
 
     # -- the denoiser -----------------------------------------------------------------------
     def guides(self, stream=None):
@@ -353,6 +365,34 @@ class Film:
             raise ValueError("the filtered mean is that of the plain passes: call denoise(temporal=True) first")
         return (self.d_denoised_var if self.denoised_variance else self.d_denoised), 1
 
+    # -- bloom ------------------------------------------------------------------------------
+    def bloom(self, threshold=BLOOM_THRESHOLD, strength=BLOOM_STRENGTH, levels=BLOOM_LEVELS, stream=None, denoised=False, temporal=False):
+        """The mean plus the glow of what is brighter than `threshold` (Renderer.film_bloom) into the film's own buffer, which
+        resolve(bloom=True) shows: the bright part of every pixel, blurred at `levels` scales (0..8) of the B3 spline, their mean
+        times `strength` added in linear colour.  denoised, temporal: the source, exactly what resolve(denoised=..., temporal=...)
+        would show.  The result belongs to the current passes and that source.  Asynchronous."""
+        self._live()
+        if self.passes < 1:
+            raise ValueError("the film holds no pass yet")
+        threshold, strength, levels, _ = check_bloom(threshold, strength, levels)
+        src, n_src = self._source(denoised, temporal)
+        r, n = self.renderer, self.ws * self.h
+        if not self.d_bloom:
+            self.d_bloom = r.malloc(24 * n)
+        if not self.d_bloom_work:
+            self.d_bloom_work = r.malloc(8 * L.RT_BLOOM_WORK_PLANES * n)
+        r.film_bloom(src, self.ws, self.h, n_src, self.d_bloom, self.d_bloom_work, threshold=threshold, strength=strength, levels=levels,
+                     stream=stream)
+        self.bloom_passes = self.passes
+        self.bloom_source = (bool(denoised), bool(temporal))
+
+    def _bloomed(self, denoised, temporal):
+        """(d_bloom, 1) for a resolve with bloom=True, or ValueError where bloom() has not run for the current passes and source."""
+        self._source(denoised, temporal)
+        if not self.bloom_passes or self.bloom_passes != self.passes or self.bloom_source != (bool(denoised), bool(temporal)):
+            raise ValueError("the film has no bloom of its current passes and this source: call bloom() with the same denoised and temporal first")
+        return self.d_bloom, 1
+
     # -- temporal accumulation ---------------------------------------------------------------
     def _full_frame(self):
         if self.x0 != 0 or self.x1 != self.renderer.w or self.renderer.h != self.h:
@@ -441,10 +481,11 @@ class Film:
 
     # -- frames -----------------------------------------------------------------------------
     def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None,
-                       denoised=False, temporal=False):
+                       denoised=False, temporal=False, bloom=False):
         """The mean of the passes so far, tone-mapped, into caller-owned device memory (raw addresses), laid out as
         Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead; temporal: the mean that temporal()
-        wrote (with denoised: its filtered version, denoise(temporal=True)).  Asynchronous."""
+        wrote (with denoised: its filtered version, denoise(temporal=True)); bloom: that source with the glow that bloom() added.
+        Asynchronous."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
@@ -453,21 +494,24 @@ class Film:
             raise ValueError("both outputs are None")
         if int(flags) & L.RT_FLAG_U8_HWC and d_f32:
             raise ValueError("RT_FLAG_U8_HWC is a uint8 layout: resolve the float32 frame in a separate call")
-        src, n = self._source(denoised, temporal)
+        src, n = self._bloomed(denoised, temporal) if bloom else self._source(denoised, temporal)
         self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
                                    flags=flags, out_stride=out_stride, stream=stream)
 
-    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False):
+    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False, bloom=False):
         """(uint8 or None, float32 or None) host arrays shaped like Renderer.render's: (3, ws, h), or (h, ws, 3) for the uint8
-        frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered; temporal: of the mean that temporal() wrote.  Waits
-        for the context's stream."""
+        frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered; temporal: of the mean that temporal() wrote; bloom: with
+        the glow that bloom() added to that source.  Waits for the context's stream."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
         check_tone(self.passes, exposure, white, gamma, flags)
         if not u8 and not f32:
             raise ValueError("neither u8 nor f32 is asked for")
-        self._source(denoised, temporal)
+        if bloom:
+            self._bloomed(denoised, temporal)
+        else:
+            self._source(denoised, temporal)
         r, n = self.renderer, self.ws * self.h
         hwc = bool(int(flags) & L.RT_FLAG_U8_HWC)
         out8 = np.empty((self.h, self.ws, 3) if hwc else (3, self.ws, self.h), np.uint8) if u8 else None
@@ -476,6 +520,8 @@ class Film:
         d32 = r.malloc(12 * n) if f32 else None
         try:
             kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised, temporal=temporal)
+            if bloom:
+                kw["bloom"] = True
             if hwc:                                             # (the image layout is uint8 only: two calls)
                 self.resolve_device(d8, None, flags=flags, **kw)
                 if f32:

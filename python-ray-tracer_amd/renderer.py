@@ -526,6 +526,19 @@ class Renderer:
             self._ctx, vp(d_mean), strides[0], vp(d_msq), strides[1], vp(d_len), int(ws), int(h), vp(d_guides), strides[2], C.byref(dv),
             float(spatial_below), vp(d_out), strides[3], vp(d_work), strides[4], vp(stream)))
 
+    def film_bloom(self, d_sum, ws, h, n, d_out, d_work=None, *, threshold=255.0, strength=0.25, levels=6, flags=0, sum_stride=None,
+                   out_stride=None, work_stride=None, stream=None):
+        """Bloom on the mean of the sum of n passes at d_sum (rt_film_bloom): what is brighter than threshold, blurred at `levels`
+        scales and times strength, added to the mean in the float64 (3, ws, h) buffer d_out; d_work holds RT_BLOOM_WORK_PLANES
+        float64 planes (None allowed for levels == 0).  The result is a mean: resolve it with film_resolve(..., n=1).  Asynchronous.
+        In numpy: bloom.bloom_reference."""
+        npx = int(ws) * int(h)
+        sum_stride, out_stride, work_stride = (npx if v is None else int(v) for v in (sum_stride, out_stride, work_stride))
+        bl = L.rt_bloom(float(threshold), float(strength), int(levels), int(flags))
+        vp = lambda d: C.c_void_p(d) if d else None
+        self._check(self._later_entry("rt_film_bloom")(self._ctx, vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(bl), vp(d_out),
+                                                       out_stride, vp(d_work), work_stride, vp(stream)))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
         if stream:

@@ -1,0 +1,292 @@
+"""Bloom on the device (rt_film_bloom; python-ray-tracer_amd/csrc/rt_bloom.h): the kernels against bloom.bloom_reference bit for bit on
+tests/bloom_cases.py's sums, every setting with tiles and again with RT_BLOOM_NO_TILES and the two outputs equal; odd strides with
+sentinels, a NaN-poisoned work buffer, levels 0 without one; the grid-stride loop; every refusal with its text and an untouched
+output; through Film on a rendered scene with a sun."""
+import itertools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, raygen_closed_form
+import closest_hit_scenes as chs
+import bloom_cases as bc
+from test_film import same_bits
+
+from python_ray_tracer_amd import Film, bloom as B, film as F
+from python_ray_tracer_amd import _lib as L
+
+pytestmark = pytest.mark.gpu
+
+FRAMES = ((1, 1), (33, 1), (5, 300), (37, 29), (64, 64), (97, 71))    # at steps up to 128 all but the centre tap fall outside these
+LEVELS = (0, 1, 2, 3, 6, 8)
+THRESHOLDS = (0.0, 255.0, 1e9)
+STRENGTHS = (0.0, 0.5, 4.0)
+PASSES = (1, 7)
+OUT_FILL, WORK_FILL = -777.0, -888.0
+
+_WANT = {}
+
+
+def want_of(ws, h, n, threshold, strength, levels):
+    key = (ws, h, n, threshold, strength, levels)
+    if key not in _WANT:
+        _WANT[key] = B.bloom_reference(bc.bloom_sums(ws, h, n), n, threshold, strength, levels)
+    return _WANT[key]
+
+
+def _read(r, d, shape, dtype=np.float64):
+    a = np.empty(shape, dtype)
+    r.d2h(a, d)
+    return a
+
+
+def _padded(planes, stride, fill):
+    """(len(planes), stride) float64: the planes' elements, then `fill`."""
+    p = np.full((len(planes), stride), fill)
+    p[:, :planes[0].size] = np.asarray(planes).reshape(len(planes), -1)
+    return p
+
+
+def _same(what, got, want):
+    bad = np.argwhere(got.view(np.uint64) != want.view(np.uint64))
+    assert bad.size == 0, (what, len(bad), bad[:4].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+class _Buffers:
+    """A sum with stride npx + pads[0], two outputs with npx + pads[1] and a work buffer with npx + pads[2], sentinels in the pads."""
+
+    def __init__(self, r, ws, h, pads=(1, 3, 5)):
+        self.r, self.ws, self.h, self.npx = r, ws, h, ws * h
+        self.ss, self.os, self.wk = (self.npx + p for p in pads)
+        self.d_sum, self.d_out, self.d_out2 = r.malloc(24 * self.ss), r.malloc(24 * self.os), r.malloc(24 * self.os)
+        self.d_work = r.malloc(8 * L.RT_BLOOM_WORK_PLANES * self.wk)
+
+    def close(self):
+        for d in (self.d_sum, self.d_out, self.d_out2, self.d_work):
+            self.r.free(d)
+
+    def put_sum(self, s):
+        self.r.h2d(self.d_sum, _padded(s, self.ss, 1e300))
+
+    def run(self, n, threshold, strength, levels, work_fill=WORK_FILL, work=True):
+        """Both forms from sentinel-filled outputs: (with tiles, with RT_BLOOM_NO_TILES), each (3, ws, h), after the pads of every
+        buffer have been found intact."""
+        r, npx = self.r, self.npx
+        outs = []
+        for d_out, flags in ((self.d_out, 0), (self.d_out2, L.RT_BLOOM_NO_TILES)):
+            r.h2d(d_out, np.full(3 * self.os, OUT_FILL))
+            r.h2d(self.d_work, _padded(np.full((L.RT_BLOOM_WORK_PLANES, npx), work_fill), self.wk, WORK_FILL))
+            r.film_bloom(self.d_sum, self.ws, self.h, n, d_out, self.d_work if work else None, threshold=threshold, strength=strength,
+                         levels=levels, flags=flags, sum_stride=self.ss, out_stride=self.os, work_stride=self.wk)
+            r.sync()
+            got = _read(r, d_out, (3, self.os))
+            assert (got[:, npx:] == OUT_FILL).all(), "the pad of out was written"
+            wk = _read(r, self.d_work, (L.RT_BLOOM_WORK_PLANES, self.wk))
+            assert (wk[:, npx:] == WORK_FILL).all(), "the pad of work was written"
+            outs.append(np.ascontiguousarray(got[:, :npx]).reshape(3, self.ws, self.h))
+        return outs
+
+
+@pytest.fixture
+def rend(renderer):
+    yield renderer
+    renderer.set_lens(0.0, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The kernels against the restatement
+
+@pytest.mark.parametrize("ws,h", FRAMES)
+def test_bloom_matches_the_reference_with_and_without_tiles(rend, ws, h):
+    b = _Buffers(rend, ws, h)
+    try:
+        ran = 0
+        for n in PASSES:
+            b.put_sum(bc.bloom_sums(ws, h, n))
+            for levels, threshold, strength in itertools.product(LEVELS, THRESHOLDS, STRENGTHS):
+                tiles, gather = b.run(n, threshold, strength, levels)
+                want = want_of(ws, h, n, threshold, strength, levels)
+                what = (ws, h, n, levels, threshold, strength)
+                _same(("gather",) + what, gather, want)
+                _same(("tiles",) + what, tiles, want)
+                assert same_bits(tiles, gather), what
+                ran += 1
+        assert ran == 108
+    finally:
+        b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Buffer bounds
+
+@pytest.mark.parametrize("pads", [(1, 3, 5), (5, 1, 3), (3, 5, 1)])
+def test_odd_strides_a_poisoned_work_buffer_and_no_work_buffer(rend, pads):
+    ws, h = 37, 29
+    b = _Buffers(rend, ws, h, pads)
+    try:
+        b.put_sum(bc.bloom_sums(ws, h, 7))
+        for levels in (1, 3, 8):
+            tiles, gather = b.run(7, 255.0, 0.5, levels, work_fill=np.nan)      # (run checks the pads of out and work)
+            want = want_of(ws, h, 7, 255.0, 0.5, levels)
+            assert np.isfinite(want).all()
+            _same(("gather", levels), gather, want)
+            _same(("tiles", levels), tiles, want)
+        tiles, gather = b.run(7, 255.0, 0.5, 0, work=False)                    # levels 0 needs no work buffer
+        want = want_of(ws, h, 7, 255.0, 0.5, 0)
+        _same("levels 0, gather", gather, want)
+        _same("levels 0, tiles", tiles, want)
+        wk = _read(rend, b.d_work, (L.RT_BLOOM_WORK_PLANES, b.wk))
+        assert (wk[:, :ws * h] == WORK_FILL).all()                              # and touches none it is not given
+    finally:
+        b.close()
+
+
+def test_bloom_loops_past_the_grid_cap(rend):
+    """A frame with more pixels than a gather launch has threads (8 blocks of 256 per CU): the grid-stride loop takes a second turn."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert cus == rend.kernel_info()["cu_count"]
+    ws, h = chs.grid_cap_frame(cus)
+    assert ws * h > 8 * 256 * cus
+    b = _Buffers(rend, ws, h)
+    try:
+        b.put_sum(bc.bloom_sums(ws, h, 1))
+        tiles, gather = b.run(1, 255.0, 0.5, 2)
+        want = want_of(ws, h, 1, 255.0, 0.5, 2)
+        _same("gather", gather, want)
+        _same("tiles", tiles, want)
+    finally:
+        b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Refusals
+
+def test_refusals_carry_their_text_and_leave_the_output_untouched(rend):
+    import python_ray_tracer_amd as pkg
+    ws, h = 37, 29
+    npx = ws * h
+    d_sum, d_out, d_work = rend.malloc(24 * npx), rend.malloc(24 * npx), rend.malloc(48 * npx)
+    nan, inf = float("nan"), float("inf")
+    try:
+        rend.h2d(d_sum, np.ascontiguousarray(bc.bloom_sums(ws, h, 1)))
+        rend.h2d(d_out, np.full(3 * npx, OUT_FILL))
+        rend.h2d(d_work, np.full(6 * npx, WORK_FILL))
+        ok = dict(threshold=255.0, strength=0.25, levels=3)
+        call = lambda *a, **kw: rend.film_bloom(*a, **{**ok, **kw})
+        area, stride, own = "ws*h outside 1..RT_FILM_MAX_PIXELS", "a plane stride is smaller than the frame", "d_out and d_work must be buffers of their own"
+        bad = [("d_sum is NULL", lambda: call(None, ws, h, 1, d_out, d_work)),
+               ("d_out is NULL", lambda: call(d_sum, ws, h, 1, None, d_work)),
+               (area, lambda: call(d_sum, 0, h, 1, d_out, d_work)),
+               (area, lambda: call(d_sum, ws, -1, 1, d_out, d_work)),
+               (area, lambda: call(d_sum, 1 << 14, (1 << 13) + 1, 1, d_out, d_work)),
+               ("n < 1", lambda: call(d_sum, ws, h, 0, d_out, d_work)),
+               ("levels outside 0..8", lambda: call(d_sum, ws, h, 1, d_out, d_work, levels=9)),
+               ("levels outside 0..8", lambda: call(d_sum, ws, h, 1, d_out, d_work, levels=-1)),
+               ("threshold must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, threshold=nan)),
+               ("threshold must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, threshold=-1.0)),
+               ("threshold must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, threshold=inf)),
+               ("strength must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, strength=inf)),
+               ("strength must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, strength=-0.5)),
+               ("strength must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, strength=nan)),
+               ("unknown flag bit", lambda: call(d_sum, ws, h, 1, d_out, d_work, flags=2)),
+               ("unknown flag bit", lambda: call(d_sum, ws, h, 1, d_out, d_work, flags=-2)),
+               ("d_work is NULL with levels >= 1", lambda: call(d_sum, ws, h, 1, d_out, None)),
+               (stride, lambda: call(d_sum, ws, h, 1, d_out, d_work, sum_stride=npx - 1)),
+               (stride, lambda: call(d_sum, ws, h, 1, d_out, d_work, out_stride=npx - 1)),
+               (stride, lambda: call(d_sum, ws, h, 1, d_out, d_work, work_stride=npx - 1)),
+               (own, lambda: call(d_sum, ws, h, 1, d_sum, d_work)),
+               (own, lambda: call(d_sum, ws, h, 1, d_out, d_sum)),
+               (own, lambda: call(d_sum, ws, h, 1, d_out, d_out)),
+               # the order: the first broken rule speaks
+               ("d_sum is NULL", lambda: call(None, 0, h, 0, None, None, levels=9)),
+               (area, lambda: call(d_sum, 0, h, 0, d_out, d_work, levels=9)),
+               ("n < 1", lambda: call(d_sum, ws, h, 0, d_out, d_work, levels=9, threshold=nan)),
+               ("levels outside 0..8", lambda: call(d_sum, ws, h, 1, d_out, d_work, levels=9, threshold=nan)),
+               ("threshold must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, threshold=nan, strength=nan)),
+               ("strength must be finite and >= 0", lambda: call(d_sum, ws, h, 1, d_out, d_work, strength=nan, flags=4)),
+               ("unknown flag bit", lambda: call(d_sum, ws, h, 1, d_out, None, flags=4)),
+               ("d_work is NULL with levels >= 1", lambda: call(d_sum, ws, h, 1, d_out, None, out_stride=1)),
+               (stride, lambda: call(d_sum, ws, h, 1, d_sum, d_work, out_stride=1))]
+        for text, fn in bad:
+            with pytest.raises(pkg.RenderError) as e:
+                fn()
+            assert e.value.status == L.RT_ERR_BAD_ARG and str(e.value).endswith("rt_film_bloom: " + text), (text, str(e.value))
+        lib = L.load()                                            # bl == NULL: below the wrapper, which always passes one
+        rc = lib.rt_film_bloom(rend._ctx, d_sum, npx, ws, h, 1, None, d_out, npx, d_work, npx, None)
+        assert rc == L.RT_ERR_BAD_ARG and lib.rt_last_error(rend._ctx).decode() == "rt_film_bloom: bl is NULL"
+        rend.sync()
+        assert (_read(rend, d_out, (3 * npx,)) == OUT_FILL).all(), "a refused call touched d_out"
+        assert (_read(rend, d_work, (6 * npx,)) == WORK_FILL).all(), "a refused call touched d_work"
+        call(d_sum, ws, h, 1, d_out, d_work, levels=8, threshold=0.0, strength=0.0, flags=L.RT_BLOOM_NO_TILES)     # the edges are accepted
+        call(d_sum, ws, h, 1, d_out, None, levels=0, work_stride=0)
+        rend.sync()
+    finally:
+        for d in (d_sum, d_out, d_work):
+            rend.free(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Through Film on a rendered scene with a sun
+
+class _Counting:
+    """The renderer with its bloom calls and allocations counted."""
+
+    def __init__(self, r):
+        self._r, self.blooms, self.mallocs = r, 0, 0
+
+    def __getattr__(self, name):
+        return getattr(self._r, name)
+
+    def malloc(self, n):
+        self.mallocs += 1
+        return self._r.malloc(n)
+
+    def film_bloom(self, *a, **kw):
+        self.blooms += 1
+        return self._r.film_bloom(*a, **kw)
+
+
+def test_film_bloom_on_a_scene_with_a_sun(rend):
+    g = np.load(os.path.join(GOLDEN, "sky_default_64_d4.npz"))
+    w, h = int(g["w"]), int(g["h"])
+    rend.set_scene(g["spheres"], g["lights"], g["planes"], materials=(g["materials"], g["sphere_material"], g["plane_material"]),
+                   light_radius=g["light_radius"], shadow_samples=int(g["shadow_samples"]), light_rgb=g["light_rgb"], sky=g["sky"])
+    rend.set_camera(g["cam_origin"], g["cam_rot"])
+    rend.set_lens(0.0, 1.0)
+    rend.set_raygen(w, h, *raygen_closed_form(w, h, float(g["fov"])))
+    params = rend.params(7.0, -3.0, 2.0, depth=int(g["depth"]), aa=2, spp=1, seed=int(g["seed"]))
+    tone = dict(white=400.0, gamma=2)
+    r = _Counting(rend)
+    with Film(r) as film:
+        film.accumulate(params, 2)
+        base = r.mallocs
+        plain = film.resolve(u8=False, f32=True, **tone)[1]
+        film.denoise()
+        assert r.blooms == 0 and film.d_bloom is None and film.d_bloom_work is None    # a film that never calls bloom()
+        with pytest.raises(ValueError, match="bloom\\(\\)"):
+            film.resolve(bloom=True, **tone)
+        rend.sync()
+        s = _read(rend, film.d_sum, (3, w, h))
+        mean_max = (s / 2.0).max(axis=0)
+        threshold = 255.0
+        print(f"sky_default_64_d4, 2 passes: brightest mean {mean_max.max():.1f}, {int((mean_max > threshold).sum())} of {w * h} pixels above {threshold}")
+        assert 0 < (mean_max > threshold).sum() < w * h
+        for kw in (dict(threshold=threshold, strength=0.5, levels=6), dict(threshold=threshold, strength=0.25, levels=3)):
+            film.bloom(**kw)
+            got = film.resolve(u8=False, f32=True, bloom=True, **tone)[1]
+            want = F.tone_reference(B.bloom_reference(s, 2, kw["threshold"], kw["strength"], kw["levels"]), 1, **tone).astype(np.float32)
+            assert same_bits(got, want), kw
+            assert not same_bits(got, plain) and (got >= plain).all()
+        assert r.blooms == 2 and film.d_bloom and film.d_bloom_work
+        with pytest.raises(ValueError, match="bloom\\(\\)"):        # the glow of the plain mean is not that of the filtered one
+            film.resolve(bloom=True, denoised=True, **tone)
+        rend.sync()
+        den = _read(rend, film.d_denoised, (3, w, h))
+        film.bloom(threshold=threshold, strength=0.5, levels=6, denoised=True)
+        got = film.resolve(u8=False, f32=True, bloom=True, denoised=True, **tone)[1]
+        assert same_bits(got, F.tone_reference(B.bloom_reference(den, 1, threshold, 0.5, 6), 1, **tone).astype(np.float32))
+        with pytest.raises(ValueError, match="bloom\\(\\)"):
+            film.resolve(bloom=True, **tone)
+        assert base >= 1
