@@ -100,7 +100,8 @@ struct rt_ctx {
     bool have_scene = false;
     rt::View view;                // camera, ray grid and lens (rt_launch.h)
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
-    size_t guides_lds_set = 0;                 // ... of the three guides kernels (rt_render_guides)
+    size_t ground_lds_set = 0;                 // ... of PLAIN's ground-plane twins (GROUND_KERNELS)
+    size_t guides_lds_set = 0;                // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback (rt_feedback.h has the rules and the slots' host state; the device buffers stay here)
     struct Feedback : rt::FeedbackSlot {
@@ -191,14 +192,14 @@ int raise_lds(rt_ctx *ctx, const void *const *fns, size_t n, size_t lds, size_t 
     return RT_OK;
 }
 
-using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel;
+using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel; using rt::has_ground_kernel;
 
-template <rt::Family F, int I>
+template <rt::Family F, int I, bool GROUND = false>
 const void *kernel_at()
 {
     constexpr Shape s = SHAPES[I];
-    if constexpr (has_kernel(F, s))
-        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F>;
+    if constexpr (GROUND ? has_ground_kernel(F, s) : has_kernel(F, s))
+        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F, GROUND>;
     else
         return nullptr;
 }
@@ -206,6 +207,11 @@ template <rt::Family F, int... I>
 std::array<const void *, NSHAPES> family_kernels(std::integer_sequence<int, I...>)
 {
     return {kernel_at<F, I>()...};
+}
+template <int... I>
+std::array<const void *, NSHAPES> ground_kernels(std::integer_sequence<int, I...>)
+{
+    return {kernel_at<rt::Family::PLAIN, I, true>()...};
 }
 
 // KERNELS[f][i]: family f's render kernel of shape SHAPES[i] (nullptr: it has none)
@@ -222,6 +228,11 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
     family_kernels<rt::Family::SKY_SCAT>(ALL_SHAPES), family_kernels<rt::Family::SKY_SOFT>(ALL_SHAPES),
     family_kernels<rt::Family::SKY_LENS>(ALL_SHAPES), family_kernels<rt::Family::SKY_LENS_SOFT>(ALL_SHAPES),
 };
+// GROUND_KERNELS[i]: the ground-plane twin of PLAIN's kernel of shape SHAPES[i] (rt_plan.h: ground_plane; nullptr: the shape has
+// none: has_ground_kernel)
+const std::array<const void *, NSHAPES> GROUND_KERNELS = ground_kernels(ALL_SHAPES);
+// The kernels a launch of family fi picks from: its family's, or the twins.
+const std::array<const void *, NSHAPES> &kernels_of(int fi, bool ground) { return ground ? GROUND_KERNELS : KERNELS[fi]; }
 static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14 &&
               (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
               "KERNELS lists the families in enum order");
@@ -406,12 +417,17 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
 {
     const Shape &sh = plan.shape;
     const int fi = (int)plan.family;
-    const void *fn = KERNELS[fi][plan.index];
+    // the twin of the planned shape, where the scene has the ground plane and the shape a twin (the shape counts rays exactly when
+    // the launch's flags ask for it: plan_launch)
+    const bool ground = rt::ground_plane(ctx->lay, ctx->knobs, plan.family, sh.count ? RT_FLAG_COUNT_RAYS : 0) && has_ground_kernel(plan.family, sh);
+    const std::array<const void *, NSHAPES> &kernels = kernels_of(fi, ground);
+    const void *fn = kernels[plan.index];
+    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: launch() checked KERNELS, has_ground_kernel GROUND_KERNELS)
     const unsigned grid = (unsigned)g.blocks;
     if (ctx->log_kernels)
-        std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
-                     (int)sh.lat, sh.mode, fi);
-    int rc = raise_lds(ctx, KERNELS[fi].data(), KERNELS[fi].size(), plan.lds, ctx->lds_limit_set[fi]);
+        std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>%s\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
+                     (int)sh.lat, sh.mode, fi, ground ? " ground" : "");
+    int rc = raise_lds(ctx, kernels.data(), kernels.size(), plan.lds, ground ? ctx->ground_lds_set : ctx->lds_limit_set[fi]);
     if (rc != RT_OK) return rc;
     if (sh.count) {
         if (!ctx->counts.p) {
@@ -505,6 +521,7 @@ int rt_create(rt_ctx **out, int device)
     if (const char *e = std::getenv("MI355RT_WPW2_MAX_IMAGE")) ctx->knobs.wpw2_max_image = (size_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("MI355RT_ORDER_TILES")) ctx->knobs.order_tiles = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LANES_PARK")) ctx->knobs.lanes_park = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_GROUND_PLANE")) ctx->knobs.ground_plane = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LOG_KERNELS")) ctx->log_kernels = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_SEQ_ORDER")) ctx->knobs.seq_order = std::atoi(e) != 0 ? 1 : 0;
     if (const char *e = std::getenv("MI355RT_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= RT_RENDER_CHUNKS) ctx->render_chunks = v; }
@@ -1349,7 +1366,11 @@ int rt_get_kernel_info(rt_ctx *ctx, rt_kernel_info *info)
     if (!info) return fail(ctx, RT_ERR_BAD_ARG, "info is NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipFuncAttributes a;
-    RT_HIP(ctx, hipFuncGetAttributes(&a, (const void *)rt::render_kernel<false, true, 2>));
+    // the headline kernel, or its twin where the current scene's plain launches run that (rt_plan.h: ground_plane)
+    const bool ground = ctx->have_scene && rt::ground_plane(ctx->lay, ctx->knobs, rt::Family::PLAIN, 0);
+    const void *fn = ground ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, rt::Family::PLAIN, true>
+                            : (const void *)rt::render_kernel<false, true, 2>;
+    RT_HIP(ctx, hipFuncGetAttributes(&a, fn));
     hipDeviceProp_t prop;
     RT_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
     std::memset(info, 0, sizeof *info);

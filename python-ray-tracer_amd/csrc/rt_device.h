@@ -543,14 +543,28 @@ __device__ __forceinline__ int opaque(int x)
     return x;
 }
 
-__device__ __forceinline__ int plane_code(const KParams &p, int k)
+// GROUND (the ground-plane kernels: render_kernel's last template argument; rt_plan.h: ground_plane picks them): the scene has
+// exactly one plane and its stored normal is (0,0,1), the reference's ground.  The queries then take P as 1 (plane_count) and the axis
+// code as +3: no loop over the planes, no decode of the packed codes, no chain of wave-uniform branches on the code, and the one
+// record at a fixed address.  The arithmetic is plane_den_num's z-branch, unchanged.  A template argument, not a flag in Lds like
+// trim and defer: the feature kernels call the queries from lambdas, which are simplified before they are inlined, and a flag read
+// through `lds` there is folded too late to leave their instruction streams as they were.
+template <bool GROUND = false> __device__ __forceinline__ int plane_code(const KParams &p, int k)
 {
+    if constexpr (GROUND) return 3;
     // the decoded code and the booleans derived from it are loop-invariant, and the compiler hoists them out of the bounce
     // loop — into scalar registers it does not have: they come back as v_readlane (a VALU slot each) at every use.
     // Re-deriving them from the one kernel-argument word costs scalar instructions only.
     unsigned c = p.plane_codes;
     asm volatile("" : "+s"(c));
     return k < 4 ? (int)(signed char)(c >> (8 * k)) : 0;
+}
+
+// The number of planes a query tests: the kernel argument, opaque (above), or the constant 1 of the ground-plane kernels.
+template <bool GROUND = false> __device__ __forceinline__ int plane_count(const KParams &p)
+{
+    if constexpr (GROUND) return 1;
+    else return opaque(p.P);
 }
 
 // no_negate (Lds::trim): for a normal -e_i both den and num are negated, and everything a query does with the pair is the same for
@@ -972,11 +986,11 @@ __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KPar
 // trace.py:7-41, closest hit.  R = normalize(d) and a = R.R are computed once per query.
 // anchor: index into the cull table of a point every live lane's ray passes through (0 = camera),
 // or -1 for rays with no common anchor (reflections).
-template <int MODE>      // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
+template <int MODE, bool GROUND = false>      // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
 __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor,
                                             double &t_out, int &idx_out, int &type_out)
 {
-    const int P = opaque(p.P);
+    const int P = plane_count<GROUND>(p);
     const int S = p.S;
     // Lds::defer: R and a are formed in front of the first float64 sphere test, not in front of the cull (closest_spheres).
     constexpr bool F32 = MODE >= 1;                           // sphere records: the float32 LDS table (see sphere_hot)
@@ -1026,7 +1040,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     for (int k = 0; k < P; ++k) {                             // intersections.py:41-68
         const double *g = pl + k * PL_STRIDE;
         double den, num;
-        plane_den_num(g, plane_code(p, k), o, d, den, num, lds.trim);   // :52, :59-61
+        plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num, lds.trim);   // :52, :59-61
         if (!(__builtin_fabs(den) < 0.001)) {                 // :55
             const double t = div_inrange(num, den);           // :63
             if (best > t && t > 0.0) { best = t; idx = k; type = HIT_PLANE; }
@@ -1040,9 +1054,10 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
 // two-wave kernels without a material table): "is any live lane still unoccluded" is then two scalar instructions wherever
 // it is asked, no test runs under a per-lane condition, and the flag becomes a per-lane bool once, at the end.  Same compares
 // on the same values as any_hit's loops below; a lane that is already occluded is tested again (its answer can only stay).
+template <bool GROUND = false>
 __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self)
 {
-    const int P = opaque(p.P);
+    const int P = plane_count<GROUND>(p);
     const int S = p.S;
     const lanemask live = lanes_where(true);
     lanemask occ;
@@ -1080,7 +1095,7 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
         if ((live & ~occ) == 0ull) break;
         const double *g = pl + k * PL_STRIDE;
         double den, num;
-        plane_den_num(g, plane_code(p, k), o, d, den, num, true);
+        plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num, true);
         const double an = __builtin_fabs(num), ad = __builtin_fabs(den);
         // the signs agree (any_hit: num > 0 && den > 0 || num < 0 && den < 0) where the sign bits do and neither is zero; den is
         // not zero under !(|den| < 0.001); a NaN num fails |num| > 0, a NaN den every test of the quotient below
@@ -1104,11 +1119,11 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
 // Called with the lanes that need the answer active; returns true if occluded.
 // anchor = cull-table index of the light the ray points at; self = index of the sphere the ray
 // starts on (-1: a plane), whose miss is certified by the origin-form "behind" test.
-template <int MODE>
+template <int MODE, bool GROUND = false>
 __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self, bool lanes = true)
 {
-    if (MODE == 0 && lds.trim) return any_hit_masks(lds, p, o, d, anchor, self);
-    const int P = opaque(p.P);
+    if (MODE == 0 && lds.trim) return any_hit_masks<GROUND>(lds, p, o, d, anchor, self);
+    const int P = plane_count<GROUND>(p);
     const int S = p.S;
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
@@ -1141,7 +1156,7 @@ __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const 
         if (!occ) {
             const double *g = pl + k * PL_STRIDE;
             double den, num;
-            plane_den_num(g, plane_code(p, k), o, d, den, num);
+            plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num);
             if (!(__builtin_fabs(den) < 0.001)) {
                 const double an = __builtin_fabs(num), ad = __builtin_fabs(den);
                 const bool same_sign = (num > 0.0 && den > 0.0) || (num < 0.0 && den < 0.0);
@@ -1393,7 +1408,7 @@ __device__ __forceinline__ void hit_normal(const Lds &lds, int type, int idx, in
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
 // b: the trace index (0: the primary ray); SCAT kernels scatter off rough surfaces with it, and clear `alive` where a scattered
 // path ends (absorption) after this trace's colour.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS>
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
                                              V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
@@ -1409,7 +1424,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
     RT_MARK(11);
     // (LENS: a primary ray starts on the lens, not at the camera: no anchor for its closest hit.  `anchor` itself still says
     // which trace this is for the shadow rays below.)
-    if (alive) closest_hit<MODE>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
+    if (alive) closest_hit<MODE, GROUND>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
     // SKY: the lanes that entered alive and missed return the sky's colour for their direction instead of (0, 0, 0); they end
     // as before.  d is still in registers here, parked kernels included (the hit lanes park it below), so it is neither held
     // longer nor read back; the branch is skipped when no lane of the wave missed (s_cbranch_execz).
@@ -1536,7 +1551,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                     const double k = SLOT(LAMB) * cN;   // :99
                     RT_MARK(5);
                     if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                        const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
+                        const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, -1, self, true);
                         if (!occluded) lit_add(m, k, [&]() { return soft_Ld(again(m), i); });
                     }
                 }
@@ -1552,7 +1567,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * cN;       // :99
                 RT_MARK(5);
                 if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                    const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                    const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                     if (!occluded) lit_add(m, k, [&]() { return point_Ld(again(m)); });
                 }
             }
@@ -1571,7 +1586,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * dot3(Ld, N);   // :99
                 RT_MARK(5);
                 if (k > 0.0) {
-                    const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, -1, self, true);
+                    const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, -1, self, true);
                     if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
                 }
             }
@@ -1603,7 +1618,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             RT_MARK(5);
             if (k > 0.0) {
                 // (the shadow rays of the primary hits still travel together: wave-uniform cull unless p.lanes_primary)
-                const bool occluded = any_hit<MODE>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                 if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
             }
         }
@@ -1628,7 +1643,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
 // SCAT: key is the sample's scatter_key, kept in its slot for the scatter.  SOFT: lkey is its soft_key, kept in its slot for
 // the light loop.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
 __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
                                      unsigned key = 0u, unsigned lkey = 0u)
 {
@@ -1650,7 +1665,7 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
+        trace_bounce<PARK, WGT, COUNT, MODE, MS, GROUND>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0; SKY: W * sky(d))
             double wgt;
@@ -1885,7 +1900,8 @@ __device__ __forceinline__ void tile_xy(const KParams &p, int tile, int &tx, int
 // SCAT (with REFR): the table has rough rows (rt_set_scene_materials_scatter): scattered reflections (scatter_continue).
 // SOFT (with SCAT): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
 // LENS (with SCAT, and LENS_SOFT with SOFT): the camera has an aperture (rt_set_lens): thin-lens primary rays (lens_ray).
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, Family F = Family::PLAIN>
+// GROUND: the ground-plane twin (plane_code) of a PLAIN kernel that does not count rays; false: the generic kernel.
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, Family F = Family::PLAIN, bool GROUND = false>
 __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT_W_AAPARK : 4) : (PARK ? RT_W_PARK : 5))) void render_kernel(const KParams p)
 {
     constexpr int WG_THREADS = 64 * WPW, WAVES_PER_WG = WPW;
@@ -2006,7 +2022,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         V3 ro = o, rd;
         if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
         else rd = primary_dir(p, P0);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms)>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -2044,7 +2060,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             V3 ro = o, rd;
             if constexpr (LENS) lens_ray(p, lx, ly, stoch ? (unsigned)tap : 0u, Pt, ro, rd);
             else rd = primary_dir(p, Pt);
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

@@ -29,6 +29,8 @@ struct PlanKnobs {
                                       // frame longest-first; default -1 = tile order for the two-wave kernels (small flat scenes: headline
                                       // 0.1050 ms either way, writes 31.8 instead of 38.7 MB per frame), longest-first for the four-wave ones
                                       // (config 4: 0.734 against 0.785 ms — runs of cheap sky tiles starve the dispatcher in tile order)
+    int ground_plane = 1;             // MI355RT_GROUND_PLANE=0: scenes with the reference's single z-up ground plane run the generic kernels
+                                      // too (A/B, and the tests that compare the twins with them)
 };
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
@@ -87,6 +89,35 @@ constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
 constexpr bool has_kernel(Family f, const Shape &s)
 {
     return (!s.count || f == Family::PLAIN) && !(has_refr(f) && s.park && s.mode < 2);
+}
+
+// The ground-plane twins (rt_device.h: GROUND): kernels of the PLAIN family that do not count rays have a second
+// instantiation, compiled for a scene whose only plane has the stored normal (0,0,1): the reference's ground, which every
+// BASELINE workload has.  ground_plane says whether a launch is of such a scene, has_ground_kernel whether its shape has a twin;
+// a launch for which both hold runs the twin.  The choice is a dimension of its own: the plan's family, shape, index and LDS size
+// do not depend on it (a twin stages the same LDS image as its generic kernel).
+// `code0`: plane 0's axis code, the low byte of SceneLayout::plane_codes (+3: exactly +e_z).
+// Six of PLAIN's 22 shapes that do not count rays have no twin: measured against the parent's kernel of the same shape
+// (profiles/ground_plane_shapes.txt), theirs gained 0.3 to 1.1 %, which is within what register allocation alone moves these
+// kernels by; the other 16 gained 2.4 to 5.8 %.  All six are register variants (park = false).  A launch of one of them runs the
+// generic kernel whatever ground_plane says.
+constexpr Shape NO_GROUND_TWIN[] = {
+    {false, false, 2, false, false, 0}, {true, false, 2, false, false, 0},      // two-wave register variants, without AA and with
+    {false, false, 4, false, false, 1}, {false, false, 4, false, true, 1},      // MODE 1 register variants
+    {false, false, 4, false, false, 2}, {false, false, 4, false, true, 2},      // lane-owned register variants without an AA mode of their own
+};
+constexpr bool has_ground_kernel(Family f, const Shape &s)
+{
+    if (f != Family::PLAIN || s.count) return false;
+    for (const Shape &n : NO_GROUND_TWIN)
+        if (n == s) return false;
+    return true;
+}
+
+inline bool ground_plane(const SceneLayout &lay, const PlanKnobs &kn, Family fam, int flags)
+{
+    const int code0 = (int)(signed char)(lay.plane_codes & 0xffu);
+    return kn.ground_plane != 0 && fam == Family::PLAIN && !(flags & RT_FLAG_COUNT_RAYS) && lay.P == 1 && code0 == 3;
 }
 
 // The parking rule of the wave-uniform kernels (plan_launch): their state parks in LDS while PARK_WAVES wavefronts per CU still
