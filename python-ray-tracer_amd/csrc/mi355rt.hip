@@ -483,6 +483,17 @@ int variance_filter(rt_ctx *ctx, const rt::DenoiseVarArgs &common, int levels, c
     return RT_OK;
 }
 
+// One launch of a temporal kernel (rt_temporal.h) over the context's full frame; the arguments have been checked and built.
+template <class Args>
+int temporal_launch(rt_ctx *ctx, void (*kernel)(Args), const Args &a, void *stream)
+{
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(kernel, dim3(rt::temporal_grid((long long)ctx->view.w * ctx->view.h, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
+                       stream_of(ctx, stream), a);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -962,18 +973,13 @@ int rt_film_temporal(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int64_t
     int rc = refuse(ctx, rt::check_film_temporal("rt_film_temporal", v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len,
                                                  d_hist_guides, hist_guide_stride, tp, d_out, out_stride, d_out_len));
     if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
     rt::TemporalArgs a;
     rt::temporal_args(a, v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out,
                       out_stride, d_out_len);
-    hipLaunchKernelGGL(rt::temporal_kernel, dim3(rt::temporal_grid((long long)v.w * v.h, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
-                       stream_of(ctx, stream), a);
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
+    return temporal_launch(ctx, rt::temporal_kernel, a, stream);
 }
 
-// rt_film_temporal with the second moment beside the mean: one launch of temporal_moments_kernel (rt_temporal.h), a kernel of its own
-// so that temporal_kernel stays what it was.
+// rt_film_temporal with the second moment beside the mean: one launch of temporal_moments_kernel (rt_temporal.h).
 int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, const void *d_sq, int64_t sq_stride, int64_t n,
                              const void *d_guides, int64_t guide_stride, const void *d_hist, int64_t hist_stride, const void *d_hist_sq,
                              int64_t hist_sq_stride, const void *d_hist_len, const void *d_hist_guides, int64_t hist_guide_stride,
@@ -986,15 +992,11 @@ int rt_film_temporal_moments(rt_ctx *ctx, const void *d_sum, int64_t sum_stride,
                                                          hist_sq_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out, out_stride, d_out_sq,
                                                          out_sq_stride, d_out_len));
     if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
     rt::TemporalMomentsArgs m;
     rt::temporal_args(m.t, v, d_sum, sum_stride, n, d_guides, guide_stride, d_hist, hist_stride, d_hist_len, d_hist_guides, hist_guide_stride, tp, d_out,
                       out_stride, d_out_len);
     rt::temporal_moments_args(m, d_sq, sq_stride, d_hist_sq, hist_sq_stride, d_out_sq, out_sq_stride);
-    hipLaunchKernelGGL(rt::temporal_moments_kernel, dim3(rt::temporal_grid((long long)v.w * v.h, ctx->cu_count)), dim3(rt::TEMPORAL_THREADS), 0,
-                       stream_of(ctx, stream), m);
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
+    return temporal_launch(ctx, rt::temporal_moments_kernel, m, stream);
 }
 
 // The variance-guided filter on a temporal mean: the prepare launch takes each pixel's variance from its own moments or, where its

@@ -66,22 +66,30 @@ RT_DN_HD inline double denoise_var_wc(double d2, double den)
     return d2 > 0.0 ? 0.0 : 1.0;
 }
 
+// The end of both prepare passes for channel c of element e: the mean m over the albedo and the variance over its square with demod,
+// the mean stored; returns the variance, of which the caller stores v_0 = (var_0 + var_1) + var_2.  Per channel, as both passes
+// interleave it with their loads: one call for the three channels made denoise_var_prepare_kernel hold every load at once.
+RT_DN_HD inline double denoise_var_prepare_store(const float *guides, long long guide_stride, double *dst, long long dst_stride,
+                                                 int c, long long e, bool demod, double m, double var)
+{
+    if (demod) {
+        const double al = denoise_albedo(guides[(4 + c) * guide_stride + e]);
+        m = m / al;
+        var = var / (al * al);
+    }
+    dst[c * dst_stride + e] = m;
+    return var;
+}
+
 // Element e of the prepare pass: (m_0, v_0) from the sum and the sum of squares, over the albedo with demod.
 RT_DN_HD inline void denoise_var_prepare_pixel(const DenoiseVarArgs &a, long long e)
 {
     const bool demod = a.demod && !a.copy;
     double v[3];
     for (int c = 0; c < 3; ++c) {
-        double m = a.sum[c * a.sum_stride + e] / a.n;
+        const double m = a.sum[c * a.sum_stride + e] / a.n;
         const double r = denoise_var_pos(a.sq[c * a.sq_stride + e] / a.n - m * m);
-        double var = r / a.n1;
-        if (demod) {
-            const double al = denoise_albedo(a.guides[(4 + c) * a.guide_stride + e]);
-            m = m / al;
-            var = var / (al * al);
-        }
-        a.dst[c * a.dst_stride + e] = m;
-        v[c] = var;
+        v[c] = denoise_var_prepare_store(a.guides, a.guide_stride, a.dst, a.dst_stride, c, e, demod, m, r / a.n1);
     }
     a.dst[3 * a.dst_stride + e] = (v[0] + v[1]) + v[2];
 }
@@ -106,7 +114,7 @@ RT_DN_HD inline void denoise_var_prepare_len_pixel(const DenoiseVarLenArgs &a, i
     const long long e = (long long)x * a.h + y;
     const bool demod = a.demod && !a.copy;
     const double Lp = (double)a.len[e];
-    double m[3] = {a.mean[e], a.mean[a.mean_stride + e], a.mean[2 * a.mean_stride + e]};
+    const double m[3] = {a.mean[e], a.mean[a.mean_stride + e], a.mean[2 * a.mean_stride + e]};
     double var[3] = {0.0, 0.0, 0.0};
     if (Lp >= a.spatial_below) {                                                      // own
         for (int c = 0; c < 3; ++c) {
@@ -144,14 +152,7 @@ RT_DN_HD inline void denoise_var_prepare_len_pixel(const DenoiseVarLenArgs &a, i
                 var[c] = (r / (SL - 1.0)) * (SL / Lp);
             }
     }
-    for (int c = 0; c < 3; ++c) {
-        if (demod) {
-            const double al = denoise_albedo(a.guides[(4 + c) * a.guide_stride + e]);
-            m[c] = m[c] / al;
-            var[c] = var[c] / (al * al);
-        }
-        a.dst[c * a.dst_stride + e] = m[c];
-    }
+    for (int c = 0; c < 3; ++c) var[c] = denoise_var_prepare_store(a.guides, a.guide_stride, a.dst, a.dst_stride, c, e, demod, m[c], var[c]);
     a.dst[3 * a.dst_stride + e] = (var[0] + var[1]) + var[2];
 }
 

@@ -134,50 +134,20 @@ __device__ __forceinline__ void film_store4(double *p, bool vec, const double (&
     }
 }
 
-// sum[c][e] = (reset ? +0.0 : sum[c][e]) + f_0[c][e] + ... + f_{nb-1}[c][e], left to right.  blockIdx.y is the plane; a thread
-// takes groups of four elements in a grid-stride loop, and the first npx mod 4 threads of block 0 the elements behind the last group.
-__global__ __launch_bounds__(FILM_THREADS) void film_add_kernel(const FilmAddArgs a)
+// sum[c][e] = (reset ? +0.0 : sum[c][e]) + f_0[c][e] + ... + f_{nb-1}[c][e], left to right, and with SQ (Args = FilmAdd2Args) the
+// same of the squares into sq[c][e] beside it, each pass element read once for both; the sum's bits do not depend on SQ.
+// blockIdx.y is the plane; a thread takes groups of four elements in a grid-stride loop, and the first npx mod 4 threads of block 0
+// the elements behind the last group.  A sum plane and a sq plane may differ in alignment.
+template <bool SQ, class Args>
+__device__ __forceinline__ void film_add_body(const Args &a)
 {
     const long long c = blockIdx.y;
     double *const s = a.sum + c * a.sum_stride;
+    double *q = nullptr;
+    if constexpr (SQ) q = a.sq + c * a.sq_stride;
     const float *const f = a.frames + c * a.fplane;
     const long long pass = 3 * a.fplane;
-    const bool vec = film_aligned(s, 16);
-    const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
-    for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
-        const long long e = g << 2;
-        film_f4 v[FILM_BATCH];
-#pragma unroll
-        for (int b = 0; b < FILM_BATCH; ++b)
-            if (b < a.nb) v[b] = *reinterpret_cast<const film_f4 *>(f + b * pass + e);
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        if (!a.reset) film_load4(s + e, vec, acc);
-#pragma unroll
-        for (int b = 0; b < FILM_BATCH; ++b)
-            if (b < a.nb) {
-                acc[0] = film_add(acc[0], v[b].x); acc[1] = film_add(acc[1], v[b].y);
-                acc[2] = film_add(acc[2], v[b].z); acc[3] = film_add(acc[3], v[b].w);
-            }
-        film_store4(s + e, vec, acc);
-    }
-    if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
-        const long long e = (ngroups << 2) + threadIdx.x;
-        double acc = a.reset ? 0.0 : s[e];
-        for (int b = 0; b < a.nb; ++b) acc = film_add(acc, f[b * pass + e]);
-        s[e] = acc;
-    }
-}
-
-// film_add_kernel with a second buffer: sq[c][e] = (reset ? +0.0 : sq[c][e]) + f_0[c][e]^2 + ... + f_{nb-1}[c][e]^2 beside the sum, each
-// pass element read once for both.  The sum's bits are film_add_kernel's.  A sum plane and a sq plane may differ in alignment.
-__global__ __launch_bounds__(FILM_THREADS) void film_add2_kernel(const FilmAdd2Args a)
-{
-    const long long c = blockIdx.y;
-    double *const s = a.sum + c * a.sum_stride;
-    double *const q = a.sq + c * a.sq_stride;
-    const float *const f = a.frames + c * a.fplane;
-    const long long pass = 3 * a.fplane;
-    const bool vec_s = film_aligned(s, 16), vec_q = film_aligned(q, 16);
+    const bool vec_s = film_aligned(s, 16), vec_q = SQ && film_aligned(q, 16);
     const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
     for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
         const long long e = g << 2;
@@ -188,31 +158,37 @@ __global__ __launch_bounds__(FILM_THREADS) void film_add2_kernel(const FilmAdd2A
         double acc[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
         if (!a.reset) {
             film_load4(s + e, vec_s, acc);
-            film_load4(q + e, vec_q, sq);
+            if constexpr (SQ) film_load4(q + e, vec_q, sq);
         }
 #pragma unroll
         for (int b = 0; b < FILM_BATCH; ++b)
             if (b < a.nb) {
                 acc[0] = film_add(acc[0], v[b].x); acc[1] = film_add(acc[1], v[b].y);
                 acc[2] = film_add(acc[2], v[b].z); acc[3] = film_add(acc[3], v[b].w);
-                sq[0] = film_add_sq(sq[0], v[b].x); sq[1] = film_add_sq(sq[1], v[b].y);
-                sq[2] = film_add_sq(sq[2], v[b].z); sq[3] = film_add_sq(sq[3], v[b].w);
+                if constexpr (SQ) {
+                    sq[0] = film_add_sq(sq[0], v[b].x); sq[1] = film_add_sq(sq[1], v[b].y);
+                    sq[2] = film_add_sq(sq[2], v[b].z); sq[3] = film_add_sq(sq[3], v[b].w);
+                }
             }
         film_store4(s + e, vec_s, acc);
-        film_store4(q + e, vec_q, sq);
+        if constexpr (SQ) film_store4(q + e, vec_q, sq);
     }
     if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
         const long long e = (ngroups << 2) + threadIdx.x;
-        double acc = a.reset ? 0.0 : s[e], sq = a.reset ? 0.0 : q[e];
+        double acc = a.reset ? 0.0 : s[e], sq = 0.0;
+        if constexpr (SQ) sq = a.reset ? 0.0 : q[e];
         for (int b = 0; b < a.nb; ++b) {
             const float x = f[b * pass + e];
             acc = film_add(acc, x);
-            sq = film_add_sq(sq, x);
+            if constexpr (SQ) sq = film_add_sq(sq, x);
         }
         s[e] = acc;
-        q[e] = sq;
+        if constexpr (SQ) q[e] = sq;
     }
 }
+
+__global__ __launch_bounds__(FILM_THREADS) void film_add_kernel(const FilmAddArgs a) { film_add_body<false>(a); }
+__global__ __launch_bounds__(FILM_THREADS) void film_add2_kernel(const FilmAdd2Args a) { film_add_body<true>(a); }
 
 // One pixel's three bytes (the tail, and the image layout): e = (x - x0) h + y.
 __device__ __forceinline__ void film_store_u8_pixel(const FilmResolveArgs &a, long long e, double R, double G, double B)

@@ -13,8 +13,9 @@
 // The kernel (hipcc only): one thread per pixel, consecutive threads consecutive y (the fast axis of the layout), a grid capped
 // near 8 blocks per CU with a grid-stride loop; under a small camera move neighbouring pixels read neighbouring taps, so the four
 // gathers mostly coalesce; 8- and 4-byte accesses, so any plane stride will do; no LDS, no scratch, 64-bit plane offsets.
-// rt_film_temporal_moments carries the history's mean of squares through the same taps (temporal_moments_pixel, temporal_moments_kernel):
-// a kernel, an argument struct and a tap loop of their own, so that temporal_kernel is instruction for instruction what it was.
+// rt_film_temporal_moments carries the history's mean of squares through the same taps: the tap loop and the blend are written once,
+// as templates over MOMENTS (temporal_taps_of, temporal_pixel_of), and the plain instantiation, which compiles none of the moment
+// lines, is handed a null TemporalMomentsArgs that it never reads.
 #pragma once
 #include <cstdint>
 
@@ -53,86 +54,8 @@ struct TemporalTaps {
     double hm[3], L;
 };
 
-RT_TP_HD inline double temporal_snap(double f)
-{
-    const double r = __builtin_floor(f + 0.5);
-    return __builtin_fabs(f - r) <= 0x1p-20 ? r : f;
-}
-
-RT_TP_HD inline TemporalTaps temporal_taps(const TemporalArgs &a, int x, int y)
-{
-    TemporalTaps r{false, {0.0, 0.0, 0.0}, 0.0};
-    const long long e = (long long)x * a.h + y;
-    const float idp = a.guides[7 * a.guide_stride + e];
-    if (idp < 0.0f || a.max_history == 0.0) return r;
-    const V3 P{a.px, (double)x * a.dy + a.y0, (double)y * a.dz + a.z0};
-    const V3 d = normalize3_generic(V3{a.R[0] * P.x + a.R[1] * P.y + a.R[2] * P.z,
-                                       a.R[3] * P.x + a.R[4] * P.y + a.R[5] * P.z,
-                                       a.R[6] * P.x + a.R[7] * P.y + a.R[8] * P.z});
-    const double t = (double)a.guides[3 * a.guide_stride + e];
-    const double u0 = (a.o[0] + t * d.x) - a.po[0], u1 = (a.o[1] + t * d.y) - a.po[1], u2 = (a.o[2] + t * d.z) - a.po[2];
-    const double q0 = (a.pR[0] * u0 + a.pR[3] * u1) + a.pR[6] * u2;
-    const double q1 = (a.pR[1] * u0 + a.pR[4] * u1) + a.pR[7] * u2;
-    const double q2 = (a.pR[2] * u0 + a.pR[5] * u1) + a.pR[8] * u2;
-    if (!(q0 > 0.0)) return r;
-    const double r2 = (u0 * u0 + u1 * u1) + u2 * u2;
-    const double sc = a.px / q0;
-    const double fx = temporal_snap((q1 * sc - a.y0) / a.dy), fy = temporal_snap((q2 * sc - a.z0) / a.dz);
-    if (!(fx > -1.0 && fx < (double)a.w && fy > -1.0 && fy < (double)a.h)) return r;   // (NaN lands here)
-    const double flx = __builtin_floor(fx), fly = __builtin_floor(fy);
-    const double ax = fx - flx, ay = fy - fly;
-    const int ix = (int)flx, iy = (int)fly;                                           // -1 .. w-1, -1 .. h-1
-    const double nx = (double)a.guides[e], ny = (double)a.guides[a.guide_stride + e], nz = (double)a.guides[2 * a.guide_stride + e];
-    double W = 0.0, H0 = 0.0, H1 = 0.0, H2 = 0.0, Lh = 0.0;
-    for (int ta = 0; ta < 2; ++ta) {
-        const int qx = ix + ta;
-        for (int tb = 0; tb < 2; ++tb) {
-            const int qy = iy + tb;
-            const double bw = (ta ? ax : 1.0 - ax) * (tb ? ay : 1.0 - ay);
-            if (bw == 0.0 || qx < 0 || qx >= a.w || qy < 0 || qy >= a.h) continue;
-            const long long eq = (long long)qx * a.h + qy;
-            if (a.hist_guides[7 * a.hist_guide_stride + eq] != idp) continue;
-            const double tq = (double)a.hist_guides[3 * a.hist_guide_stride + eq];
-            if (!(__builtin_fabs(tq * tq - r2) <= a.depth_tol * r2)) continue;
-            const double cn = ((nx * (double)a.hist_guides[eq]) + (ny * (double)a.hist_guides[a.hist_guide_stride + eq])) +
-                              (nz * (double)a.hist_guides[2 * a.hist_guide_stride + eq]);
-            if (!(cn >= a.normal_cos)) continue;
-            const double lq = (double)a.hist_len[eq];
-            if (!(lq > 0.0)) continue;
-            W = W + bw;
-            H0 = H0 + bw * a.hist[eq]; H1 = H1 + bw * a.hist[a.hist_stride + eq]; H2 = H2 + bw * a.hist[2 * a.hist_stride + eq];
-            Lh = Lh + bw * lq;
-        }
-    }
-    if (!(W > 0.0)) return r;
-    r.valid = true;
-    r.hm[0] = H0 / W; r.hm[1] = H1 / W; r.hm[2] = H2 / W;
-    const double L = Lh / W;
-    r.L = L > a.max_history ? a.max_history : L;
-    return r;
-}
-
-// Pixel (x, y), written to out and out_len.
-RT_TP_HD inline void temporal_pixel(const TemporalArgs &a, int x, int y)
-{
-    const long long e = (long long)x * a.h + y;
-    const TemporalTaps tp = temporal_taps(a, x, y);
-    const double s0 = a.sum[e], s1 = a.sum[a.sum_stride + e], s2 = a.sum[2 * a.sum_stride + e];
-    if (!tp.valid) {                                                                  // fresh
-        a.out[e] = s0 / a.n; a.out[a.out_stride + e] = s1 / a.n; a.out[2 * a.out_stride + e] = s2 / a.n;
-        a.out_len[e] = (float)a.n;
-        return;
-    }
-    const double den = tp.L + a.n;
-    a.out[e] = (tp.L * tp.hm[0] + s0) / den;
-    a.out[a.out_stride + e] = (tp.L * tp.hm[1] + s1) / den;
-    a.out[2 * a.out_stride + e] = (tp.L * tp.hm[2] + s2) / den;
-    a.out_len[e] = (float)den;
-}
-
 // rt_film_temporal_moments: the call above and, beside it, the second moment.  sq is this frame's sum of squares, hist_sq the
-// history's MEAN of squares, out_sq the new mean of squares, three planes each.  A kernel argument of its own: TemporalArgs is
-// temporal_kernel's and stays as it is.
+// history's MEAN of squares, out_sq the new mean of squares, three planes each.
 struct TemporalMomentsArgs {
     TemporalArgs t;
     const double *sq, *hist_sq;
@@ -140,13 +63,17 @@ struct TemporalMomentsArgs {
     long long sq_stride, hist_sq_stride, out_sq_stride;
 };
 
-// temporal_taps with the history's mean of squares (three planes at m.hist_sq) weighed through the same taps into hq: the same lines
-// in the same order, and after H_k the line Q_k = Q_k + bw * hist_sq[k][q].  A loop of its own rather than a template over
-// temporal_taps: a shared template changed temporal_kernel's instruction stream, and that kernel stays what it was;
-// tests/algo/temporal_moments_check.cpp holds the two loops to the same bits in the mean and the lengths.
-RT_TP_HD inline TemporalTaps temporal_moments_taps(const TemporalMomentsArgs &m, int x, int y, double *hq)
+RT_TP_HD inline double temporal_snap(double f)
 {
-    const TemporalArgs &a = m.t;
+    const double r = __builtin_floor(f + 0.5);
+    return __builtin_fabs(f - r) <= 0x1p-20 ? r : f;
+}
+
+// The history's taps around where pixel (x, y) was.  With MOMENTS the history's mean of squares (three planes at m->hist_sq) is
+// weighed through the same taps into hq: after H_k the line Q_k = Q_k + bw * hist_sq[k][q].
+template <bool MOMENTS>
+RT_TP_HD inline TemporalTaps temporal_taps_of(const TemporalArgs &a, const TemporalMomentsArgs *m, int x, int y, double *hq)
+{
     TemporalTaps r{false, {0.0, 0.0, 0.0}, 0.0};
     const long long e = (long long)x * a.h + y;
     const float idp = a.guides[7 * a.guide_stride + e];
@@ -187,32 +114,36 @@ RT_TP_HD inline TemporalTaps temporal_moments_taps(const TemporalMomentsArgs &m,
             if (!(lq > 0.0)) continue;
             W = W + bw;
             H0 = H0 + bw * a.hist[eq]; H1 = H1 + bw * a.hist[a.hist_stride + eq]; H2 = H2 + bw * a.hist[2 * a.hist_stride + eq];
-            Q0 = Q0 + bw * m.hist_sq[eq]; Q1 = Q1 + bw * m.hist_sq[m.hist_sq_stride + eq]; Q2 = Q2 + bw * m.hist_sq[2 * m.hist_sq_stride + eq];
+            if constexpr (MOMENTS) {
+                Q0 = Q0 + bw * m->hist_sq[eq]; Q1 = Q1 + bw * m->hist_sq[m->hist_sq_stride + eq]; Q2 = Q2 + bw * m->hist_sq[2 * m->hist_sq_stride + eq];
+            }
             Lh = Lh + bw * lq;
         }
     }
     if (!(W > 0.0)) return r;
     r.valid = true;
     r.hm[0] = H0 / W; r.hm[1] = H1 / W; r.hm[2] = H2 / W;
-    hq[0] = Q0 / W; hq[1] = Q1 / W; hq[2] = Q2 / W;
+    if constexpr (MOMENTS) { hq[0] = Q0 / W; hq[1] = Q1 / W; hq[2] = Q2 / W; }
     const double L = Lh / W;
     r.L = L > a.max_history ? a.max_history : L;
     return r;
 }
 
-// Pixel (x, y) with moments: out and out_len receive temporal_pixel's bits (the same operations in the same order), out_sq the
-// second moment blended by the same lengths.
-RT_TP_HD inline void temporal_moments_pixel(const TemporalMomentsArgs &m, int x, int y)
+// Pixel (x, y), written to out and out_len; with MOMENTS out_sq receives the second moment blended by the same lengths.
+template <bool MOMENTS>
+RT_TP_HD inline void temporal_pixel_of(const TemporalArgs &a, const TemporalMomentsArgs *m, int x, int y)
 {
-    const TemporalArgs &a = m.t;
     const long long e = (long long)x * a.h + y;
     double hq[3] = {0.0, 0.0, 0.0};
-    const TemporalTaps tp = temporal_moments_taps(m, x, y, hq);
+    const TemporalTaps tp = temporal_taps_of<MOMENTS>(a, m, x, y, hq);
     const double s0 = a.sum[e], s1 = a.sum[a.sum_stride + e], s2 = a.sum[2 * a.sum_stride + e];
-    const double q0 = m.sq[e], q1 = m.sq[m.sq_stride + e], q2 = m.sq[2 * m.sq_stride + e];
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    if constexpr (MOMENTS) { q0 = m->sq[e]; q1 = m->sq[m->sq_stride + e]; q2 = m->sq[2 * m->sq_stride + e]; }
     if (!tp.valid) {                                                                  // fresh
         a.out[e] = s0 / a.n; a.out[a.out_stride + e] = s1 / a.n; a.out[2 * a.out_stride + e] = s2 / a.n;
-        m.out_sq[e] = q0 / a.n; m.out_sq[m.out_sq_stride + e] = q1 / a.n; m.out_sq[2 * m.out_sq_stride + e] = q2 / a.n;
+        if constexpr (MOMENTS) {
+            m->out_sq[e] = q0 / a.n; m->out_sq[m->out_sq_stride + e] = q1 / a.n; m->out_sq[2 * m->out_sq_stride + e] = q2 / a.n;
+        }
         a.out_len[e] = (float)a.n;
         return;
     }
@@ -220,11 +151,20 @@ RT_TP_HD inline void temporal_moments_pixel(const TemporalMomentsArgs &m, int x,
     a.out[e] = (tp.L * tp.hm[0] + s0) / den;
     a.out[a.out_stride + e] = (tp.L * tp.hm[1] + s1) / den;
     a.out[2 * a.out_stride + e] = (tp.L * tp.hm[2] + s2) / den;
-    m.out_sq[e] = (tp.L * hq[0] + q0) / den;
-    m.out_sq[m.out_sq_stride + e] = (tp.L * hq[1] + q1) / den;
-    m.out_sq[2 * m.out_sq_stride + e] = (tp.L * hq[2] + q2) / den;
+    if constexpr (MOMENTS) {
+        m->out_sq[e] = (tp.L * hq[0] + q0) / den;
+        m->out_sq[m->out_sq_stride + e] = (tp.L * hq[1] + q1) / den;
+        m->out_sq[2 * m->out_sq_stride + e] = (tp.L * hq[2] + q2) / den;
+    }
     a.out_len[e] = (float)den;
 }
+
+RT_TP_HD inline TemporalTaps temporal_taps(const TemporalArgs &a, int x, int y) { return temporal_taps_of<false>(a, nullptr, x, y, nullptr); }
+RT_TP_HD inline void temporal_pixel(const TemporalArgs &a, int x, int y) { temporal_pixel_of<false>(a, nullptr, x, y); }
+
+// out and out_len receive temporal_pixel's bits: the same lines.
+RT_TP_HD inline TemporalTaps temporal_moments_taps(const TemporalMomentsArgs &m, int x, int y, double *hq) { return temporal_taps_of<true>(m.t, &m, x, y, hq); }
+RT_TP_HD inline void temporal_moments_pixel(const TemporalMomentsArgs &m, int x, int y) { temporal_pixel_of<true>(m.t, &m, x, y); }
 
 #if defined(__HIPCC__)
 

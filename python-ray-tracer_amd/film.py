@@ -291,21 +291,26 @@ class Film:
         self.denoised_temporal = bool(temporal)
         self.denoised_variance = False
 
+    def _variance_buffers(self, d_out, d_work, stream):
+        """What both variance calls need once their own conditions hold: current guides, and the four-plane buffers named d_out and
+        d_work (None: no work buffer), allocated on first use.  Returns their addresses."""
+        if not self.d_guides or self.guides_stale:
+            self.guides(stream)
+        for name in (d_out, d_work):
+            if name and not getattr(self, name):
+                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * self.ws * self.h))
+        return getattr(self, d_out), getattr(self, d_work) if d_work else None
+
     def _variance_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, stream):
         """rt_film_denoise_variance on the film's sums into d_out (four planes), after what it needs is there."""
         if not self.moments:
             raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
         if self.passes < 2:
             raise ValueError(f"a variance needs at least 2 passes, the film holds {self.passes}")
-        if not self.d_guides or self.guides_stale:
-            self.guides(stream)
-        n = self.ws * self.h
-        for name in (d_out, d_work):
-            if name and not getattr(self, name):
-                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * n))
-        self.renderer.film_denoise_variance(self.d_sum, self.d_sq, self.ws, self.h, self.passes, self.d_guides, getattr(self, d_out),
-                                            getattr(self, d_work) if d_work else None, levels=levels, normal_shin=shin, kappa=kappa,
-                                            var_floor=var_floor, demodulate=demodulate, prefilter=prefilter, stream=stream)
+        out, work = self._variance_buffers(d_out, d_work, stream)
+        self.renderer.film_denoise_variance(self.d_sum, self.d_sq, self.ws, self.h, self.passes, self.d_guides, out, work, levels=levels,
+                                            normal_shin=shin, kappa=kappa, var_floor=var_floor, demodulate=demodulate, prefilter=prefilter,
+                                            stream=stream)
 
     def _variance_temporal_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, spatial_below, stream):
         """rt_film_denoise_variance_temporal on the temporal mean, its mean of squares and its lengths into d_out (four planes)."""
@@ -313,16 +318,10 @@ class Film:
             raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
         if not self.temporal_passes or self.temporal_passes != self.passes or not self.d_temporal_sq:
             raise ValueError("the film has no temporal mean of its current passes, and so no second moment of one: call temporal() first")
-        if not self.d_guides or self.guides_stale:
-            self.guides(stream)
-        n = self.ws * self.h
-        for name in (d_out, d_work):
-            if name and not getattr(self, name):
-                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * n))
+        out, work = self._variance_buffers(d_out, d_work, stream)
         self.renderer.film_denoise_variance_temporal(self.d_temporal, self.d_temporal_sq, self.d_temporal_len, self.ws, self.h, self.d_guides,
-                                                     getattr(self, d_out), getattr(self, d_work) if d_work else None, levels=levels,
-                                                     normal_shin=shin, kappa=kappa, var_floor=var_floor, demodulate=demodulate,
-                                                     prefilter=prefilter, spatial_below=spatial_below, stream=stream)
+                                                     out, work, levels=levels, normal_shin=shin, kappa=kappa, var_floor=var_floor,
+                                                     demodulate=demodulate, prefilter=prefilter, spatial_below=spatial_below, stream=stream)
 
     def _denoise_variance(self, levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, spatial_below, stream):
         levels, shin, kappa, var_floor, demodulate, prefilter = check_denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter)
@@ -399,6 +398,17 @@ class Film:
             raise ValueError(f"temporal accumulation works on the full frame: the film holds columns [{self.x0}, {self.x1}) of height "
                              f"{self.h}, the renderer's frame is {self.renderer.w} x {self.renderer.h}")
 
+    def _temporal_call(self, hist, hist_sq, hist_len, hist_guides, camera, out, out_sq, out_len, **settings):
+        """The film's sums and guides blended with a history (mean, mean of squares, lengths, guides, the camera they were rendered
+        with) into out, out_sq and out_len: Renderer.film_temporal_moments on a film with moments, else Renderer.film_temporal,
+        which takes neither hist_sq nor out_sq.  settings: depth_tol, normal_cos, max_history, stream."""
+        r, (o, R) = self.renderer, camera
+        if self.moments:
+            r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, hist, hist_sq, hist_len, hist_guides, o, R,
+                                    out, out_sq, out_len, **settings)
+        else:
+            r.film_temporal(self.d_sum, self.passes, self.d_guides, hist, hist_len, hist_guides, o, R, out, out_len, **settings)
+
     def next_frame(self, stream=None):
         """The camera has moved (call this after Renderer.set_camera): the film's latest mean becomes the history, with its length
         plane and its guides, and the passes start again (clear()).  The latest mean is what temporal() wrote for the current
@@ -421,15 +431,10 @@ class Film:
                 raise ValueError("the film has no guides of the frame that ends: call guides() or temporal() before the camera moves")
             if not self.d_hist:
                 self.d_hist, self.d_hist_len = r.malloc(24 * n), r.malloc(4 * n)
-            o, R = self.guides_camera
-            if self.moments:                                      # sum / passes, sq / passes and the length passes
-                if not self.d_hist_sq:
-                    self.d_hist_sq = r.malloc(24 * n)
-                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_sum, self.d_sq, self.d_guides, self.d_guides,
-                                        o, R, self.d_hist, self.d_hist_sq, self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0,
-                                        stream=stream)
-            else:
-                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_hist,
+            if self.moments and not self.d_hist_sq:
+                self.d_hist_sq = r.malloc(24 * n)
+            # sum / passes, the length passes and with moments sq / passes: max_history 0 makes every pixel fresh, the history a placeholder
+            self._temporal_call(self.d_sum, self.d_sq, self.d_guides, self.d_guides, self.guides_camera, self.d_hist, self.d_hist_sq,
                                 self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
         self.d_hist_guides, self.d_guides = self.d_guides, self.d_hist_guides
         self.history_camera, self.guides_camera = self.guides_camera, None
@@ -459,24 +464,13 @@ class Film:
             self.d_temporal, self.d_temporal_len = r.malloc(24 * n), r.malloc(4 * n)
         if self.moments and not self.d_temporal_sq:
             self.d_temporal_sq = r.malloc(24 * n)
+        out = (self.d_temporal, self.d_temporal_sq, self.d_temporal_len)
         kw = dict(depth_tol=depth_tol, normal_cos=normal_cos, stream=stream)
         if self.history_camera is None:                           # no history: every pixel fresh (the inputs are placeholders)
-            o, R = r.camera
-            if self.moments:
-                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_sum, self.d_sq, self.d_guides, self.d_guides,
-                                        o, R, self.d_temporal, self.d_temporal_sq, self.d_temporal_len, max_history=0.0, **kw)
-            else:
-                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_sum, self.d_guides, self.d_guides, o, R, self.d_temporal,
-                                self.d_temporal_len, max_history=0.0, **kw)
+            self._temporal_call(self.d_sum, self.d_sq, self.d_guides, self.d_guides, r.camera, *out, max_history=0.0, **kw)
         else:
-            o, R = self.history_camera
-            if self.moments:
-                r.film_temporal_moments(self.d_sum, self.d_sq, self.passes, self.d_guides, self.d_hist, self.d_hist_sq, self.d_hist_len,
-                                        self.d_hist_guides, o, R, self.d_temporal, self.d_temporal_sq, self.d_temporal_len,
-                                        max_history=max_history, **kw)
-            else:
-                r.film_temporal(self.d_sum, self.passes, self.d_guides, self.d_hist, self.d_hist_len, self.d_hist_guides, o, R,
-                                self.d_temporal, self.d_temporal_len, max_history=max_history, **kw)
+            self._temporal_call(self.d_hist, self.d_hist_sq, self.d_hist_len, self.d_hist_guides, self.history_camera, *out,
+                                max_history=max_history, **kw)
         self.temporal_passes = self.passes
 
     # -- frames -----------------------------------------------------------------------------

@@ -33,6 +33,26 @@ def _f32(a, rows, name):
     return a
 
 
+def _vp(d):
+    """A device address or stream handle as a C argument: 0 and None are NULL."""
+    return C.c_void_p(d) if d else None
+
+
+def _strides(npx, *strides):
+    """Plane strides as ints, a missing one the frame's pixel count."""
+    return [npx if v is None else int(v) for v in strides]
+
+
+def _temporal(prev_origin, prev_rotation, depth_tol, normal_cos, max_history, reserved):
+    """An rt_temporal: the camera the history was rendered with and the tap tests' settings."""
+    tp = L.rt_temporal()
+    tp.prev_origin[:] = [float(v) for v in np.asarray(prev_origin, dtype=np.float64).reshape(3)]
+    tp.prev_rotation[:] = [float(v) for v in np.asarray(prev_rotation, dtype=np.float64).reshape(9)]
+    tp.depth_tol, tp.normal_cos, tp.max_history = float(depth_tol), float(normal_cos), float(max_history)
+    tp.reserved[:] = [int(v) for v in reserved]
+    return tp
+
+
 _serials = itertools.count(1)
 
 
@@ -438,12 +458,10 @@ class Renderer:
         """The edge-stopping a-trous filter on the mean of the sum of n passes at d_sum, guided by d_guides, into the float64
         (3, ws, h) buffer d_out (rt_film_denoise); d_work is a second such buffer (None allowed for levels <= 1).  The result is a
         mean: resolve it with film_resolve(..., n=1).  Asynchronous.  In numpy: denoise.denoise_reference."""
-        npx = int(ws) * int(h)
-        sum_stride, guide_stride, out_stride, work_stride = (npx if v is None else int(v) for v in (sum_stride, guide_stride, out_stride, work_stride))
+        sum_stride, guide_stride, out_stride, work_stride = _strides(int(ws) * int(h), sum_stride, guide_stride, out_stride, work_stride)
         dn = L.rt_denoise(int(levels), int(normal_shin), float(sigma), int(demodulate), int(reserved))
-        vp = lambda d: C.c_void_p(d) if d else None
-        self._check(self._later_entry("rt_film_denoise")(self._ctx, vp(d_sum), sum_stride, int(ws), int(h), int(n), vp(d_guides), guide_stride,
-                                                         C.byref(dn), vp(d_out), out_stride, vp(d_work), work_stride, vp(stream)))
+        self._check(self._later_entry("rt_film_denoise")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), _vp(d_guides), guide_stride,
+                                                         C.byref(dn), _vp(d_out), out_stride, _vp(d_work), work_stride, _vp(stream)))
 
     def film_temporal(self, d_sum, n, d_guides, d_hist, d_hist_len, d_hist_guides, prev_origin, prev_rotation, d_out, d_out_len, *,
                       depth_tol, normal_cos, max_history, sum_stride=None, guide_stride=None, hist_stride=None, hist_guide_stride=None,
@@ -453,27 +471,19 @@ class Renderer:
         reprojected through this frame's guides d_guides and blended with the sum of n passes at d_sum into the float64
         (3, w, h) mean d_out and the float32 (w, h) length plane d_out_len.  The result is a mean: resolve or denoise it with
         n = 1.  Asynchronous.  In numpy: temporal.temporal_reference."""
-        npx = int(self.w or 0) * int(self.h or 0)
-        strides = [npx if v is None else int(v) for v in (sum_stride, guide_stride, hist_stride, hist_guide_stride, out_stride)]
-        tp = L.rt_temporal()
-        tp.prev_origin[:] = [float(v) for v in np.asarray(prev_origin, dtype=np.float64).reshape(3)]
-        tp.prev_rotation[:] = [float(v) for v in np.asarray(prev_rotation, dtype=np.float64).reshape(9)]
-        tp.depth_tol, tp.normal_cos, tp.max_history = float(depth_tol), float(normal_cos), float(max_history)
-        tp.reserved[:] = [int(v) for v in reserved]
-        vp = lambda d: C.c_void_p(d) if d else None
-        self._check(self._later_entry("rt_film_temporal")(self._ctx, vp(d_sum), strides[0], int(n), vp(d_guides), strides[1], vp(d_hist),
-                                                          strides[2], vp(d_hist_len), vp(d_hist_guides), strides[3], C.byref(tp),
-                                                          vp(d_out), strides[4], vp(d_out_len), vp(stream)))
+        strides = _strides(int(self.w or 0) * int(self.h or 0), sum_stride, guide_stride, hist_stride, hist_guide_stride, out_stride)
+        tp = _temporal(prev_origin, prev_rotation, depth_tol, normal_cos, max_history, reserved)
+        self._check(self._later_entry("rt_film_temporal")(self._ctx, _vp(d_sum), strides[0], int(n), _vp(d_guides), strides[1], _vp(d_hist),
+                                                          strides[2], _vp(d_hist_len), _vp(d_hist_guides), strides[3], C.byref(tp),
+                                                          _vp(d_out), strides[4], _vp(d_out_len), _vp(stream)))
 
     def film_accumulate_moments(self, params, x0, x1, passes, reset, d_sum, d_sq, sum_stride=None, sq_stride=None, stream=None):
         """film_accumulate with the sum of the frames' squares added to a second float64 (3, x1-x0, h) buffer at d_sq
         (rt_film_accumulate_moments); d_sum receives the bits film_accumulate would give.  Asynchronous.  In numpy:
         variance.accumulate_moments_reference."""
-        npx = (int(x1) - int(x0)) * (self.h or 0)
-        sum_stride, sq_stride = (npx if v is None else int(v) for v in (sum_stride, sq_stride))
-        vp = lambda d: C.c_void_p(d) if d else None
+        sum_stride, sq_stride = _strides((int(x1) - int(x0)) * (self.h or 0), sum_stride, sq_stride)
         self._check(self._later_entry("rt_film_accumulate_moments")(self._ctx, C.byref(params), int(x0), int(x1), int(passes), int(bool(reset)),
-                                                                    vp(d_sum), sum_stride, vp(d_sq), sq_stride, vp(stream)))
+                                                                    _vp(d_sum), sum_stride, _vp(d_sq), sq_stride, _vp(stream)))
 
     def film_denoise_variance(self, d_sum, d_sq, ws, h, n, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, kappa=1.0, var_floor=0.0,
                               demodulate=1, prefilter=1, sum_stride=None, sq_stride=None, guide_stride=None, out_stride=None, work_stride=None,
@@ -482,13 +492,11 @@ class Renderer:
         into the float64 (4, ws, h) buffer d_out: the filtered mean and, in plane 3, its propagated variance
         (rt_film_denoise_variance); d_work is a second such buffer (None allowed for levels == 0).  The result is a mean: resolve
         it with film_resolve(..., n=1).  Asynchronous.  In numpy: variance.denoise_variance_reference."""
-        npx = int(ws) * int(h)
-        strides = [npx if v is None else int(v) for v in (sum_stride, sq_stride, guide_stride, out_stride, work_stride)]
+        strides = _strides(int(ws) * int(h), sum_stride, sq_stride, guide_stride, out_stride, work_stride)
         dv = L.rt_denoise_variance(int(levels), int(normal_shin), float(kappa), float(var_floor), int(demodulate), int(prefilter))
-        vp = lambda d: C.c_void_p(d) if d else None
-        self._check(self._later_entry("rt_film_denoise_variance")(self._ctx, vp(d_sum), strides[0], vp(d_sq), strides[1], int(ws), int(h), int(n),
-                                                                  vp(d_guides), strides[2], C.byref(dv), vp(d_out), strides[3], vp(d_work),
-                                                                  strides[4], vp(stream)))
+        self._check(self._later_entry("rt_film_denoise_variance")(self._ctx, _vp(d_sum), strides[0], _vp(d_sq), strides[1], int(ws), int(h), int(n),
+                                                                  _vp(d_guides), strides[2], C.byref(dv), _vp(d_out), strides[3], _vp(d_work),
+                                                                  strides[4], _vp(stream)))
 
     def film_temporal_moments(self, d_sum, d_sq, n, d_guides, d_hist, d_hist_sq, d_hist_len, d_hist_guides, prev_origin, prev_rotation, d_out,
                               d_out_sq, d_out_len, *, depth_tol, normal_cos, max_history, sum_stride=None, sq_stride=None, guide_stride=None,
@@ -497,19 +505,13 @@ class Renderer:
         """film_temporal with the second moment carried beside the mean (rt_film_temporal_moments): d_sq is this frame's sum of squares,
         d_hist_sq the history's mean of squares, d_out_sq receives the new mean of squares, float64 (3, w, h) each; d_out and d_out_len
         receive the bits film_temporal would give.  Asynchronous.  In numpy: temporal.temporal_moments_reference."""
-        npx = int(self.w or 0) * int(self.h or 0)
-        strides = [npx if v is None else int(v) for v in (sum_stride, sq_stride, guide_stride, hist_stride, hist_sq_stride, hist_guide_stride,
-                                                          out_stride, out_sq_stride)]
-        tp = L.rt_temporal()
-        tp.prev_origin[:] = [float(v) for v in np.asarray(prev_origin, dtype=np.float64).reshape(3)]
-        tp.prev_rotation[:] = [float(v) for v in np.asarray(prev_rotation, dtype=np.float64).reshape(9)]
-        tp.depth_tol, tp.normal_cos, tp.max_history = float(depth_tol), float(normal_cos), float(max_history)
-        tp.reserved[:] = [int(v) for v in reserved]
-        vp = lambda d: C.c_void_p(d) if d else None
+        strides = _strides(int(self.w or 0) * int(self.h or 0), sum_stride, sq_stride, guide_stride, hist_stride, hist_sq_stride,
+                           hist_guide_stride, out_stride, out_sq_stride)
+        tp = _temporal(prev_origin, prev_rotation, depth_tol, normal_cos, max_history, reserved)
         self._check(self._later_entry("rt_film_temporal_moments")(
-            self._ctx, vp(d_sum), strides[0], vp(d_sq), strides[1], int(n), vp(d_guides), strides[2], vp(d_hist), strides[3], vp(d_hist_sq),
-            strides[4], vp(d_hist_len), vp(d_hist_guides), strides[5], C.byref(tp), vp(d_out), strides[6], vp(d_out_sq), strides[7],
-            vp(d_out_len), vp(stream)))
+            self._ctx, _vp(d_sum), strides[0], _vp(d_sq), strides[1], int(n), _vp(d_guides), strides[2], _vp(d_hist), strides[3], _vp(d_hist_sq),
+            strides[4], _vp(d_hist_len), _vp(d_hist_guides), strides[5], C.byref(tp), _vp(d_out), strides[6], _vp(d_out_sq), strides[7],
+            _vp(d_out_len), _vp(stream)))
 
     def film_denoise_variance_temporal(self, d_mean, d_msq, d_len, ws, h, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, kappa=1.0,
                                        var_floor=0.0, demodulate=1, prefilter=1, spatial_below=0.0, mean_stride=None, msq_stride=None,
@@ -518,13 +520,11 @@ class Renderer:
         film_temporal_moments wrote (mean, mean of squares, length plane); a pixel shorter than spatial_below passes takes its variance
         from its object's neighbours.  d_out and d_work as film_denoise_variance's.  Asynchronous.  In numpy:
         variance.denoise_variance_temporal_reference."""
-        npx = int(ws) * int(h)
-        strides = [npx if v is None else int(v) for v in (mean_stride, msq_stride, guide_stride, out_stride, work_stride)]
+        strides = _strides(int(ws) * int(h), mean_stride, msq_stride, guide_stride, out_stride, work_stride)
         dv = L.rt_denoise_variance(int(levels), int(normal_shin), float(kappa), float(var_floor), int(demodulate), int(prefilter))
-        vp = lambda d: C.c_void_p(d) if d else None
         self._check(self._later_entry("rt_film_denoise_variance_temporal")(
-            self._ctx, vp(d_mean), strides[0], vp(d_msq), strides[1], vp(d_len), int(ws), int(h), vp(d_guides), strides[2], C.byref(dv),
-            float(spatial_below), vp(d_out), strides[3], vp(d_work), strides[4], vp(stream)))
+            self._ctx, _vp(d_mean), strides[0], _vp(d_msq), strides[1], _vp(d_len), int(ws), int(h), _vp(d_guides), strides[2], C.byref(dv),
+            float(spatial_below), _vp(d_out), strides[3], _vp(d_work), strides[4], _vp(stream)))
 
     def film_bloom(self, d_sum, ws, h, n, d_out, d_work=None, *, threshold=255.0, strength=0.25, levels=6, flags=0, sum_stride=None,
                    out_stride=None, work_stride=None, stream=None):
@@ -532,12 +532,10 @@ class Renderer:
         scales and times strength, added to the mean in the float64 (3, ws, h) buffer d_out; d_work holds RT_BLOOM_WORK_PLANES
         float64 planes (None allowed for levels == 0).  The result is a mean: resolve it with film_resolve(..., n=1).  Asynchronous.
         In numpy: bloom.bloom_reference."""
-        npx = int(ws) * int(h)
-        sum_stride, out_stride, work_stride = (npx if v is None else int(v) for v in (sum_stride, out_stride, work_stride))
+        sum_stride, out_stride, work_stride = _strides(int(ws) * int(h), sum_stride, out_stride, work_stride)
         bl = L.rt_bloom(float(threshold), float(strength), int(levels), int(flags))
-        vp = lambda d: C.c_void_p(d) if d else None
-        self._check(self._later_entry("rt_film_bloom")(self._ctx, vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(bl), vp(d_out),
-                                                       out_stride, vp(d_work), work_stride, vp(stream)))
+        self._check(self._later_entry("rt_film_bloom")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(bl), _vp(d_out),
+                                                       out_stride, _vp(d_work), work_stride, _vp(stream)))
 
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""

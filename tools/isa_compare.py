@@ -6,7 +6,8 @@
 Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and once for REV (default HEAD, extracted with
 `git archive` into a temporary directory), then, for every kernel of REV:
   * the instruction stream, with comments and assembler directives dropped and `.LBB` / `.Lfunc_end` labels and the
-    kernel's own symbol renumbered, must be identical in the working tree;
+    kernel's own symbol renumbered, must be identical in the working tree (where it is not, the line also says whether the two
+    streams at least hold every mnemonic equally often: the same instructions in another order or in other registers);
   * so must its -Rpass-analysis=kernel-resource-usage lines (VGPRs, SGPRs, scratch, LDS, occupancy, spills).
 A render_kernel instantiation is matched by its first six template arguments (AA, PARK, WPW, COUNT, LAT, MODE) and its feature
 family (rt::Family, rt_device.h), whichever way the tree spells the family: as the seventh argument `Family F` (mangled
@@ -23,6 +24,7 @@ SKY_LENS_SOFT) next to its lighting twin.  Exit status 1 if any kernel differs.
 rt_kernel.gfx950.s and FILE.log what its `make asm` wrote to stderr (the resource-usage remarks).  What is compared is the same.
 """
 import argparse
+import collections
 import os
 import re
 import subprocess
@@ -92,6 +94,11 @@ def functions(asm):
     return out
 
 
+def mnemonics(text):
+    """A normalized stream -> {mnemonic: count} (labels dropped)."""
+    return collections.Counter(ln.split()[0] for ln in text.splitlines() if ln.strip() and not ln.rstrip().endswith(":"))
+
+
 def resources(log):
     out, cur = {}, None
     for ln in log.split("\n"):
@@ -131,8 +138,9 @@ def main():
             print(f"MISSING  {b}"); bad += 1; continue
         same_isa = bf[b] == nf[n]
         same_res = br.get(b) == nr.get(n)
+        counts = "" if same_isa else f"  (mnemonic counts {'equal' if mnemonics(bf[b]) == mnemonics(nf[n]) else 'DIFFER'})"
         print(f"{'same' if same_isa and same_res else 'DIFF'}  isa={'=' if same_isa else '!'} res={'=' if same_res else '!'} "
-              f"{len(bf[b].splitlines()):6d} lines  {key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}")
+              f"{len(bf[b].splitlines()):6d} lines  {key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}{counts}")
         bad += not (same_isa and same_res)
     base_keys = {key(b) for b in bf}
     new = sorted(n for n in nf if key(n) not in base_keys)
