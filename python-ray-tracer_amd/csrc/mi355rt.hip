@@ -101,6 +101,7 @@ struct rt_ctx {
     rt::View view;                // camera, ray grid and lens (rt_launch.h)
     size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
     size_t ground_lds_set = 0;                 // ... of PLAIN's ground-plane twins (GROUND_KERNELS)
+    size_t small_lds_set[rt::SMALL_MAX_GROUPS] = {};   // ... of their small-scene twins (SMALL_KERNELS), per number of cull groups
     size_t guides_lds_set = 0;                // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback (rt_feedback.h has the rules and the slots' host state; the device buffers stay here)
@@ -192,14 +193,14 @@ int raise_lds(rt_ctx *ctx, const void *const *fns, size_t n, size_t lds, size_t 
     return RT_OK;
 }
 
-using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel; using rt::has_ground_kernel;
+using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel; using rt::has_ground_kernel; using rt::has_small_kernel;
 
-template <rt::Family F, int I, bool GROUND = false>
+template <rt::Family F, int I, bool GROUND = false, int NG = 0>
 const void *kernel_at()
 {
     constexpr Shape s = SHAPES[I];
-    if constexpr (GROUND ? has_ground_kernel(F, s) : has_kernel(F, s))
-        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F, GROUND>;
+    if constexpr (NG > 0 ? has_small_kernel(F, s) : (GROUND ? has_ground_kernel(F, s) : has_kernel(F, s)))
+        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F, GROUND, NG>;
     else
         return nullptr;
 }
@@ -212,6 +213,11 @@ template <int... I>
 std::array<const void *, NSHAPES> ground_kernels(std::integer_sequence<int, I...>)
 {
     return {kernel_at<rt::Family::PLAIN, I, true>()...};
+}
+template <int NG, int... I>
+std::array<const void *, NSHAPES> small_kernels(std::integer_sequence<int, I...>)
+{
+    return {kernel_at<rt::Family::PLAIN, I, true, NG>()...};
 }
 
 // KERNELS[f][i]: family f's render kernel of shape SHAPES[i] (nullptr: it has none)
@@ -231,8 +237,21 @@ const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
 // GROUND_KERNELS[i]: the ground-plane twin of PLAIN's kernel of shape SHAPES[i] (rt_plan.h: ground_plane; nullptr: the shape has
 // none: has_ground_kernel)
 const std::array<const void *, NSHAPES> GROUND_KERNELS = ground_kernels(ALL_SHAPES);
-// The kernels a launch of family fi picks from: its family's, or the twins.
-const std::array<const void *, NSHAPES> &kernels_of(int fi, bool ground) { return ground ? GROUND_KERNELS : KERNELS[fi]; }
+// SMALL_KERNELS[ng - 1][i]: the small-scene twin for ng cull groups of GROUND_KERNELS[i] (rt_plan.h: cull_groups; nullptr: the shape
+// has none: has_small_kernel)
+const std::array<const void *, NSHAPES> SMALL_KERNELS[rt::SMALL_MAX_GROUPS] = {small_kernels<1>(ALL_SHAPES), small_kernels<2>(ALL_SHAPES)};
+static_assert(rt::SMALL_MAX_GROUPS == 2, "SMALL_KERNELS lists the twins of every number of cull groups");
+// The kernels a launch of family fi picks from: its family's, the ground-plane twins, or their small-scene twins for ng cull groups.
+const std::array<const void *, NSHAPES> &kernels_of(int fi, bool ground, int ng = 0)
+{
+    return ng > 0 ? SMALL_KERNELS[ng - 1] : (ground ? GROUND_KERNELS : KERNELS[fi]);
+}
+const void *kernel_of_shape(const std::array<const void *, NSHAPES> &kernels, const Shape &s)
+{
+    for (int i = 0; i < NSHAPES; ++i)
+        if (SHAPES[i] == s) return kernels[i];
+    return nullptr;
+}
 static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14 &&
               (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
               "KERNELS lists the families in enum order");
@@ -420,14 +439,18 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
     // the twin of the planned shape, where the scene has the ground plane and the shape a twin (the shape counts rays exactly when
     // the launch's flags ask for it: plan_launch)
     const bool ground = rt::ground_plane(ctx->lay, ctx->knobs, plan.family, sh.count ? RT_FLAG_COUNT_RAYS : 0) && has_ground_kernel(plan.family, sh);
-    const std::array<const void *, NSHAPES> &kernels = kernels_of(fi, ground);
+    // and of that twin the one compiled for the scene's cull groups, where the scene is small and the shape has such twins
+    const int ng = has_small_kernel(plan.family, sh) ? rt::cull_groups(ctx->lay, ctx->knobs, plan.family, sh.count ? RT_FLAG_COUNT_RAYS : 0, k.anchors) : 0;
+    const std::array<const void *, NSHAPES> &kernels = kernels_of(fi, ground, ng);
     const void *fn = kernels[plan.index];
-    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: launch() checked KERNELS, has_ground_kernel GROUND_KERNELS)
+    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: launch() checked KERNELS, has_ground_kernel GROUND_KERNELS, has_small_kernel SMALL_KERNELS)
     const unsigned grid = (unsigned)g.blocks;
     if (ctx->log_kernels)
         std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>%s\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
                      (int)sh.lat, sh.mode, fi, ground ? " ground" : "");
-    int rc = raise_lds(ctx, kernels.data(), kernels.size(), plan.lds, ground ? ctx->ground_lds_set : ctx->lds_limit_set[fi]);
+    if (ctx->log_kernels && ng > 0) std::fprintf(stderr, "mi355rt: cull groups %d\n", ng);
+    int rc = raise_lds(ctx, kernels.data(), kernels.size(), plan.lds,
+                       ng > 0 ? ctx->small_lds_set[ng - 1] : (ground ? ctx->ground_lds_set : ctx->lds_limit_set[fi]));
     if (rc != RT_OK) return rc;
     if (sh.count) {
         if (!ctx->counts.p) {
@@ -533,6 +556,7 @@ int rt_create(rt_ctx **out, int device)
     if (const char *e = std::getenv("MI355RT_ORDER_TILES")) ctx->knobs.order_tiles = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LANES_PARK")) ctx->knobs.lanes_park = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_GROUND_PLANE")) ctx->knobs.ground_plane = std::atoi(e) != 0;
+    if (const char *e = std::getenv("MI355RT_SMALL_SCENE")) ctx->knobs.small_scene = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_LOG_KERNELS")) ctx->log_kernels = std::atoi(e) != 0;
     if (const char *e = std::getenv("MI355RT_SEQ_ORDER")) ctx->knobs.seq_order = std::atoi(e) != 0 ? 1 : 0;
     if (const char *e = std::getenv("MI355RT_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= RT_RENDER_CHUNKS) ctx->render_chunks = v; }
@@ -1370,7 +1394,12 @@ int rt_get_kernel_info(rt_ctx *ctx, rt_kernel_info *info)
     hipFuncAttributes a;
     // the headline kernel, or its twin where the current scene's plain launches run that (rt_plan.h: ground_plane)
     const bool ground = ctx->have_scene && rt::ground_plane(ctx->lay, ctx->knobs, rt::Family::PLAIN, 0);
-    const void *fn = ground ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, rt::Family::PLAIN, true>
+    constexpr Shape headline{false, true, 2, false, false, 0};
+    // ... and of the twin the one for the scene's cull groups (rt_plan.h: cull_groups), as launch_one picks it
+    const int ng = ground && has_small_kernel(rt::Family::PLAIN, headline)
+                       ? rt::cull_groups(ctx->lay, ctx->knobs, rt::Family::PLAIN, 0, rt::anchors_of(ctx->lay)) : 0;
+    const void *fn = ng > 0 ? kernel_of_shape(SMALL_KERNELS[ng - 1], headline)
+                   : ground ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, rt::Family::PLAIN, true>
                             : (const void *)rt::render_kernel<false, true, 2>;
     RT_HIP(ctx, hipFuncGetAttributes(&a, fn));
     hipDeviceProp_t prop;

@@ -455,10 +455,22 @@ __device__ __forceinline__ unsigned cull4(lds_cf4 *base, const RayF &q, int jsel
 // when SOME live lane holds no certificate.  Clustered scenes first test the (up to 8) bounding spheres of the
 // chunk's clusters and only open the clusters some lane might hit.  Everything here is wave-uniform control
 // flow on scalar masks.
-template <bool ANCH, bool SELF>
+// NG > 0 (the small-scene kernels: render_kernel's last template argument; rt_plan.h: cull_groups picks them): the scene is flat and
+// has at most 4 NG spheres, so its table rows are exactly NG groups of four (padS(S, 0) = pad4(S) = 4 NG), k0 is 0 and n is S.  The
+// cull is then NG chained cull4 calls, highest group first, as the clustered branch chains `hi` into `lohi`: no loop, no shift by a
+// register, no pointer advance, immediate LDS offsets.  The same compares on the same entries in the same order.
+template <bool ANCH, bool SELF, int NG = 0>
 __device__ __forceinline__ unsigned long long cull_mask_t(const Lds &lds, int S, int anchor, int k0, int n,
                                                           const RayF &q, int selfj)
 {
+    if constexpr (NG > 0) {
+        lds_cf4 *sbase = pin_lds(ANCH ? lds.tab + (size_t)anchor * (4 * NG) * CULL_STRIDE : lds.sph32);
+        unsigned m = 0u;
+#pragma unroll
+        for (int g = NG - 1; g >= 0; --g)
+            m = lds.pairs ? cull4<ANCH, SELF, true>(sbase + 4 * g, q, selfj - 4 * g, m) : cull4<ANCH, SELF, false>(sbase + 4 * g, q, selfj - 4 * g, m);
+        return m;
+    }
     unsigned long long mask = 0ull;
     const int Sp = padS(S, lds.NC);
     lds_cf4 *sbase = pin_lds(ANCH ? lds.tab + ((size_t)anchor * Sp + k0) * CULL_STRIDE : lds.sph32 + 4 * k0);
@@ -493,29 +505,32 @@ __device__ __forceinline__ unsigned long long cull_mask_t(const Lds &lds, int S,
 }
 
 // dir: the float32 direction the certificates read — float32(R), or float32(d) of a wave inside the unit window (rt_cull.h)
+// NG > 0 (cull_mask_t): one chunk, k0 = 0 and n = S, so a sphere index is in the chunk's window exactly when it is one (self >= 0).
+template <int NG = 0>
 __device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, int anchor, int k0, int n,
                                                         const V3 &o, const F3 &dir, float extent2, int self)
 {
     RayF q = make_rayf_dir(dir);
     if (anchor >= 0) {
-        const bool cand = self >= k0 && self < k0 + n;                        // per lane
+        const bool cand = NG > 0 ? self >= 0 : (self >= k0 && self < k0 + n);  // per lane
         if (__builtin_amdgcn_ballot_w64(cand) != 0ull) {                                         // only shadow rays leaving a sphere
             add_origin(q, o, extent2);
             const float *cs = lds.sph32 + 4 * self;
             const bool self_culled = cand ? cull_origin(f4{cs[0], cs[1], cs[2], cs[3]}, q) : false;
             if (__builtin_amdgcn_ballot_w64(self_culled) != 0ull)
-                return cull_mask_t<true, true>(lds, S, anchor, k0, n, q, self_culled ? self - k0 : -1);
+                return cull_mask_t<true, true, NG>(lds, S, anchor, k0, n, q, self_culled ? self - k0 : -1);
         }
-        return cull_mask_t<true, false>(lds, S, anchor, k0, n, q, -1);
+        return cull_mask_t<true, false, NG>(lds, S, anchor, k0, n, q, -1);
     }
     add_origin(q, o, extent2);
-    return cull_mask_t<false, false>(lds, S, anchor, k0, n, q, -1);
+    return cull_mask_t<false, false, NG>(lds, S, anchor, k0, n, q, -1);
 }
 
+template <int NG = 0>
 __device__ __forceinline__ unsigned long long cull_mask(const Lds &lds, int S, int anchor, int k0, int n,
                                                         const V3 &o, const V3 &R, float extent2, int self)
 {
-    return cull_mask(lds, S, anchor, k0, n, o, cull_dir32(R), extent2, self);
+    return cull_mask<NG>(lds, S, anchor, k0, n, o, cull_dir32(R), extent2, self);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -926,13 +941,32 @@ __device__ __forceinline__ double pinned_here(double x)
     asm volatile("" : "+v"(x));
     return x;
 }
-template <bool F32, bool IN_WINDOW>
+// The trim of a small-scene kernel's 32-bit mask (NG > 0: 1 <= S <= 4 NG <= 8): the padding slots certify themselves, except to a
+// NaN ray, which must not send one to the float64 test (it would read a plane record as a sphere).
+__device__ __forceinline__ unsigned small_mask(unsigned long long m, int S) { return (unsigned)m & ((1u << S) - 1u); }
+
+template <bool F32, bool IN_WINDOW, int NG = 0>
 __device__ __forceinline__ double closest_spheres(const Lds &lds, const KParams &p, int S, int canchor, const V3 &o, const V3 &d, double e,
                                                   double &bestn, int &bidx)
 {
     double a = 1.0;
     V3 Rg{0.0, 0.0, 0.0};
     if constexpr (!IN_WINDOW) { Rg = normalize3_generic(d); a = dot3(Rg, Rg); }
+    if constexpr (NG > 0) {                                   // one chunk, all of it: no loop, a 32-bit mask
+      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, -1), S);
+      RT_MARK(1);
+      if (mask) {
+        V3 R = Rg;
+        if constexpr (IN_WINDOW) { R = renormalize_unit_fast(d, pinned_here(e)); a = dot3(R, R); }
+        do {                                                  // spheres some live lane might hit, ascending
+          const int k = __builtin_ctz(mask);
+          mask &= mask - 1u;
+          sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
+        } while (mask);
+      }
+      RT_MARK(2);
+      return a;
+    }
     for (int k0 = 0; k0 < S; k0 += 64) {
       const int n = (S - k0 < 64) ? S - k0 : 64;
       // the float32 ray is rebuilt per chunk so that it is not live during the float64 phase
@@ -953,13 +987,31 @@ __device__ __forceinline__ double closest_spheres(const Lds &lds, const KParams 
     return a;
 }
 // any_hit_masks' sphere loop the same way: the lanes some sphere occludes.
-template <bool IN_WINDOW>
+template <bool IN_WINDOW, int NG = 0>
 __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KParams &p, int S, int canchor, const V3 &o, const V3 &d, double e,
                                                       int self, lanemask live)
 {
     lanemask occ = 0ull;
     V3 Rg{0.0, 0.0, 0.0};
     if constexpr (!IN_WINDOW) Rg = normalize3_generic(d);
+    if constexpr (NG > 0) {                                   // one chunk, all of it (closest_spheres)
+      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, self), S);
+      RT_MARK(7);
+      if (mask) {
+        V3 R = Rg;
+        if constexpr (IN_WINDOW) R = renormalize_unit_fast(d, pinned_here(e));
+        const double a = dot3(R, R);
+        const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
+        do {
+          const int k = __builtin_ctz(mask);
+          mask &= mask - 1u;
+          occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
+          if (mask && (live & ~occ) == 0ull) break;
+        } while (mask);
+      }
+      RT_MARK(8);
+      return occ;
+    }
     for (int k0 = 0; k0 < S; k0 += 64) {
       if (k0 > 0 && (live & ~occ) == 0ull) break;
       const int n = (S - k0 < 64) ? S - k0 : 64;
@@ -986,7 +1038,7 @@ __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KPar
 // trace.py:7-41, closest hit.  R = normalize(d) and a = R.R are computed once per query.
 // anchor: index into the cull table of a point every live lane's ray passes through (0 = camera),
 // or -1 for rays with no common anchor (reflections).
-template <int MODE, bool GROUND = false>      // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
+template <int MODE, bool GROUND = false, int NG = 0>      // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
 __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor,
                                             double &t_out, int &idx_out, int &type_out)
 {
@@ -1001,19 +1053,28 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
         const double e = unit_excess(d);
         const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
         RT_MARK(0);
-        const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-        if (in_window) aq = closest_spheres<F32, true>(lds, p, S, canchor, o, d, e, bestn, bidx);
-        else aq = closest_spheres<F32, false>(lds, p, S, canchor, o, d, e, bestn, bidx);
+        const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+        if (in_window) aq = closest_spheres<F32, true, NG>(lds, p, S, canchor, o, d, e, bestn, bidx);
+        else aq = closest_spheres<F32, false, NG>(lds, p, S, canchor, o, d, e, bestn, bidx);
     } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(0);
-    const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
+    const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
     // lane-owned traversal for the rays without a common anchor (bounce 1 on), where the wave's rays have parted;
     // the primary rays of a tile travel together: the wave-uniform cull below is cheaper for them
     if (MODE >= 2 && lds.NC > 0 && (canchor < 0 || p.lanes_primary)) {
         if (canchor >= 0) lanes_closest<true>(lds, p, canchor, o, R, a, bestn, bidx);
         else lanes_closest<false>(lds, p, -1, o, R, a, bestn, bidx);
+    } else if constexpr (NG > 0) {                            // one chunk, all of it (closest_spheres)
+      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, R, p.extent2, -1), S);
+      RT_MARK(1);
+      while (mask) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
+      }
+      RT_MARK(2);
     } else
     for (int k0 = 0; k0 < S; k0 += 64) {
       const int n = (S - k0 < 64) ? S - k0 : 64;
@@ -1054,7 +1115,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
 // two-wave kernels without a material table): "is any live lane still unoccluded" is then two scalar instructions wherever
 // it is asked, no test runs under a per-lane condition, and the flag becomes a per-lane bool once, at the end.  Same compares
 // on the same values as any_hit's loops below; a lane that is already occluded is tested again (its answer can only stay).
-template <bool GROUND = false>
+template <bool GROUND = false, int NG = 0>
 __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self)
 {
     const int P = plane_count<GROUND>(p);
@@ -1065,16 +1126,27 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
         const double e = unit_excess(d);
         const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
         RT_MARK(6);
-        const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
-        if (in_window) occ = any_spheres_masks<true>(lds, p, S, canchor, o, d, e, self, live);
-        else occ = any_spheres_masks<false>(lds, p, S, canchor, o, d, e, self, live);
+        const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+        if (in_window) occ = any_spheres_masks<true, NG>(lds, p, S, canchor, o, d, e, self, live);
+        else occ = any_spheres_masks<false, NG>(lds, p, S, canchor, o, d, e, self, live);
     } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(6);
-    const int canchor = (opaque(p.anchors) > 0) ? anchor : -1;
+    const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
     const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
     occ = 0ull;
+    if constexpr (NG > 0) {                                   // one chunk, all of it (closest_spheres)
+      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, R, p.extent2, self), S);
+      RT_MARK(7);
+      while (mask) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
+        if (mask && (live & ~occ) == 0ull) break;
+      }
+      RT_MARK(8);
+    } else
     for (int k0 = 0; k0 < S; k0 += 64) {
       if (k0 > 0 && (live & ~occ) == 0ull) break;
       const int n = (S - k0 < 64) ? S - k0 : 64;
@@ -1119,10 +1191,12 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
 // Called with the lanes that need the answer active; returns true if occluded.
 // anchor = cull-table index of the light the ray points at; self = index of the sphere the ray
 // starts on (-1: a plane), whose miss is certified by the origin-form "behind" test.
-template <int MODE, bool GROUND = false>
+// NG > 0: only the two-wave kernels without a material table (Lds::trim) have small-scene twins, so any_hit_masks answers for them.
+template <int MODE, bool GROUND = false, int NG = 0>
 __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self, bool lanes = true)
 {
-    if (MODE == 0 && lds.trim) return any_hit_masks<GROUND>(lds, p, o, d, anchor, self);
+    static_assert(NG == 0 || MODE == 0, "small-scene kernels are wave-uniform (MODE 0)");
+    if (MODE == 0 && lds.trim) return any_hit_masks<GROUND, NG>(lds, p, o, d, anchor, self);
     const int P = plane_count<GROUND>(p);
     const int S = p.S;
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
@@ -1408,7 +1482,7 @@ __device__ __forceinline__ void hit_normal(const Lds &lds, int type, int idx, in
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
 // b: the trace index (0: the primary ray); SCAT kernels scatter off rough surfaces with it, and clear `alive` where a scattered
 // path ends (absorption) after this trace's colour.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false>
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false, int NG = 0>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
                                              V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
@@ -1424,7 +1498,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
     RT_MARK(11);
     // (LENS: a primary ray starts on the lens, not at the camera: no anchor for its closest hit.  `anchor` itself still says
     // which trace this is for the shadow rays below.)
-    if (alive) closest_hit<MODE, GROUND>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
+    if (alive) closest_hit<MODE, GROUND, NG>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
     // SKY: the lanes that entered alive and missed return the sky's colour for their direction instead of (0, 0, 0); they end
     // as before.  d is still in registers here, parked kernels included (the hit lanes park it below), so it is neither held
     // longer nor read back; the branch is skipped when no lane of the wave missed (s_cbranch_execz).
@@ -1551,7 +1625,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                     const double k = SLOT(LAMB) * cN;   // :99
                     RT_MARK(5);
                     if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                        const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, -1, self, true);
+                        const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, -1, self, true);
                         if (!occluded) lit_add(m, k, [&]() { return soft_Ld(again(m), i); });
                     }
                 }
@@ -1567,7 +1641,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * cN;       // :99
                 RT_MARK(5);
                 if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                    const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                    const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                     if (!occluded) lit_add(m, k, [&]() { return point_Ld(again(m)); });
                 }
             }
@@ -1586,7 +1660,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * dot3(Ld, N);   // :99
                 RT_MARK(5);
                 if (k > 0.0) {
-                    const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, -1, self, true);
+                    const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, -1, self, true);
                     if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
                 }
             }
@@ -1618,7 +1692,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             RT_MARK(5);
             if (k > 0.0) {
                 // (the shadow rays of the primary hits still travel together: wave-uniform cull unless p.lanes_primary)
-                const bool occluded = any_hit<MODE, GROUND>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                 if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
             }
         }
@@ -1643,7 +1717,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
 // SCAT: key is the sample's scatter_key, kept in its slot for the scatter.  SOFT: lkey is its soft_key, kept in its slot for
 // the light loop.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
+template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false, int NG = 0>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
 __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
                                      unsigned key = 0u, unsigned lkey = 0u)
 {
@@ -1665,7 +1739,7 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE, MS, GROUND>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
+        trace_bounce<PARK, WGT, COUNT, MODE, MS, GROUND, NG>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0; SKY: W * sky(d))
             double wgt;
@@ -1901,12 +1975,15 @@ __device__ __forceinline__ void tile_xy(const KParams &p, int tile, int &tx, int
 // SOFT (with SCAT): a light has a radius (rt_set_scene_area_lights): n shadow samples per light (soft_light_point).
 // LENS (with SCAT, and LENS_SOFT with SOFT): the camera has an aperture (rt_set_lens): thin-lens primary rays (lens_ray).
 // GROUND: the ground-plane twin (plane_code) of a PLAIN kernel that does not count rays; false: the generic kernel.
-template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, Family F = Family::PLAIN, bool GROUND = false>
+// NG: the cull groups of a small-scene twin (cull_mask_t) of a two-wave ground-plane twin: the scene is flat, has 4 NG - 3 to 4 NG spheres
+// and anchored tables; 0: the kernel for any scene.
+template <bool AA, bool PARK, int WPW, bool COUNT = false, bool LAT = false, int MODE = 0, Family F = Family::PLAIN, bool GROUND = false, int NG = 0>
 __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT_W_AAPARK : 4) : (PARK ? RT_W_PARK : 5))) void render_kernel(const KParams p)
 {
     constexpr int WG_THREADS = 64 * WPW, WAVES_PER_WG = WPW;
     constexpr bool M2 = MODE >= 2;
     constexpr bool NOREC = MODE >= 1;
+    static_assert(NG == 0 || (NG <= 2 && GROUND && WPW == 2 && MODE == 0 && !COUNT && F == Family::PLAIN), "small-scene twins: two-wave ground-plane kernels");
     constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F), TEX = has_tex(F);
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
@@ -2022,7 +2099,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         V3 ro = o, rd;
         if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
         else rd = primary_dir(p, P0);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
+        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND, NG>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -2060,7 +2137,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             V3 ro = o, rd;
             if constexpr (LENS) lens_ray(p, lx, ly, stoch ? (unsigned)tap : 0u, Pt, ro, rd);
             else rd = primary_dir(p, Pt);
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND, NG>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

@@ -31,6 +31,8 @@ struct PlanKnobs {
                                       // (config 4: 0.734 against 0.785 ms — runs of cheap sky tiles starve the dispatcher in tile order)
     int ground_plane = 1;             // MI355RT_GROUND_PLANE=0: scenes with the reference's single z-up ground plane run the generic kernels
                                       // too (A/B, and the tests that compare the twins with them)
+    int small_scene = 1;              // MI355RT_SMALL_SCENE=0: scenes of at most eight spheres run the ground-plane twins compiled for any sphere
+                                      // count (A/B, and the tests that compare the small-scene twins with them)
 };
 
 // The feature family of a launch: which render kernels it runs, and how many per-thread slots and material columns those
@@ -118,6 +120,37 @@ inline bool ground_plane(const SceneLayout &lay, const PlanKnobs &kn, Family fam
 {
     const int code0 = (int)(signed char)(lay.plane_codes & 0xffu);
     return kn.ground_plane != 0 && fam == Family::PLAIN && !(flags & RT_FLAG_COUNT_RAYS) && lay.P == 1 && code0 == 3;
+}
+
+// The small-scene twins (rt_device.h: NG, render_kernel's last template argument): two-wave ground-plane twins have further
+// instantiations compiled for a flat scene of at most eight spheres, whose cull-table rows are one or two groups of four: the
+// queries run no chunk loop and no loop over the groups.  A dimension of its own beside ground_plane, like it: the plan's family,
+// shape, index and LDS size do not depend on it (the twins stage the same LDS image).
+// cull_groups: the groups (1: 1 to 4 spheres, 2: 5 to 8) a launch's kernel may be compiled for, or 0: the launch is of a scene
+// with the ground plane (ground_plane), flat, with 1 to 8 spheres and the anchored tables of all its lights (`anchors`: the launch's,
+// anchors_of(lay) or 0).  has_small_kernel: the shape has such twins; a launch for which both hold runs one.
+// Three shapes were candidates, the two-wave parked ground twins (every two-wave register variant runs the generic kernel or is
+// LDS-bound); SMALL_TWIN names the ones whose twins gained more than register allocation alone moves these kernels by
+// (profiles/small_scene_shapes.txt).
+constexpr int SMALL_MAX_GROUPS = 2;
+constexpr Shape SMALL_TWIN[] = {
+    {false, true, 2, false, false, 0},      // the headline kernel
+    {true, true, 2, false, false, 0},       // with AA
+    {false, true, 2, false, true, 0},       // over the half-pixel lattice
+};
+constexpr bool has_small_kernel(Family f, const Shape &s)
+{
+    if (!has_ground_kernel(f, s)) return false;
+    for (const Shape &k : SMALL_TWIN)
+        if (k == s) return true;
+    return false;
+}
+
+inline int cull_groups(const SceneLayout &lay, const PlanKnobs &kn, Family fam, int flags, int anchors)
+{
+    if (!ground_plane(lay, kn, fam, flags) || kn.small_scene == 0) return 0;
+    if (lay.NC != 0 || lay.S < 1 || lay.S > 4 * SMALL_MAX_GROUPS || anchors != lay.L + 1) return 0;
+    return (lay.S + 3) / 4;
 }
 
 // The parking rule of the wave-uniform kernels (plan_launch): their state parks in LDS while PARK_WAVES wavefronts per CU still

@@ -2,11 +2,12 @@
 """Static audit of one render kernel's gfx950 ISA: which source construct produced every select, compare, move, lane
 read/write and exec-mask instruction, per region of the bounce (CPU only, no GPU).
 
-    python tools/isa_audit.py [--tree DIR] [--kernel "false, true, 2, false, false, 0, rt::Family::PLAIN"] [--ground] [--top 40]
+    python tools/isa_audit.py [--tree DIR] [--kernel "false, true, 2, false, false, 0, rt::Family::PLAIN"] [--ground] [--groups N] [--top 40]
 
 Compiles a translation unit that instantiates just that kernel from DIR's rt_device.h (default: this tree; the headline
 kernel) with the Makefile's flags plus -gline-tables-only, checks with tools/isa_compare.py's parser that the line info
-(--ground: its ground-plane twin, the eighth template argument GROUND = true; --kernel may also spell all eight)
+(--ground: its ground-plane twin, the eighth template argument GROUND = true; --groups N with it: that twin's small-scene twin for N
+cull groups, the ninth argument NG; --kernel may also spell all of them)
 changes no instruction, disassembles the code object and asks llvm-symbolizer for every instruction's inline stack.
 The stack (render_kernel > sample > trace_bounce > closest_hit > sphere_closest ...) and a few source markers place an
 instruction in a region; its mnemonic places it in a class.  Prints
@@ -186,11 +187,14 @@ def main():
     ap.add_argument("--planes", type=int, default=1)
     ap.add_argument("--top", type=int, default=40, help="source lines listed (0: all)")
     ap.add_argument("--ground", action="store_true", help="the kernel's ground-plane twin (GROUND = true)")
+    ap.add_argument("--groups", type=int, default=0, help="with --ground: the small-scene twin for that many cull groups (NG = 1 or 2)")
     a = ap.parse_args()
+    if a.groups and not a.ground:
+        sys.exit("isa_audit: --groups wants --ground (the small-scene kernels are twins of the ground-plane kernels)")
     if a.ground:
         if len(a.kernel.split(",")) != 7:
             sys.exit("isa_audit: --ground wants --kernel with its seven arguments up to the family")
-        a.kernel += ", true"
+        a.kernel += ", true" + (f", {a.groups}" if a.groups else "")
     tree = os.path.abspath(a.tree)
     hdr = os.path.join(tree, CSRC, "rt_device.h")
     src = Source(hdr)

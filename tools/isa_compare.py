@@ -12,10 +12,11 @@ Builds `make -C python-ray-tracer_amd/csrc asm` once for the working tree and on
 A render_kernel instantiation is matched by its first six template arguments (AA, PARK, WPW, COUNT, LAT, MODE) and its feature
 family (rt::Family, rt_device.h), whichever way the tree spells the family: as the seventh argument `Family F` (mangled
 `LNS_6FamilyE<n>E`; an eighth argument GROUND = true behind it makes the kernel the "ground" twin of its family, a kernel of its
-own that a tree without the argument does not have, and GROUND = false or absent is the family's generic kernel), or, in trees from before that parameter, as up to five trailing bool arguments MAT, REFR, SCAT, SOFT and
+own that a tree without the argument does not have, and GROUND = false or absent is the family's generic kernel; a ninth argument
+NG = 1 or 2 behind that makes it the "ground_small1" or "ground_small2" twin of the ground twin, the small-scene kernel for that many cull groups), or, in trees from before that parameter, as up to five trailing bool arguments MAT, REFR, SCAT, SOFT and
 LENS, of which a missing one counts as false.  So a tree of either form compares with one of the other, and a tree with more
 families with one with fewer.  Kernels of the working tree that the base does not have are listed as NEW.
---twins also prints each ground-plane kernel next to its generic PLAIN twin, each MAT kernel next to its PLAIN twin, each REFR kernel next to its MAT twin, each SCAT kernel next to its
+--twins also prints each ground-plane kernel next to its generic PLAIN twin, each small-scene kernel next to its ground-plane twin, each MAT kernel next to its PLAIN twin, each REFR kernel next to its MAT twin, each SCAT kernel next to its
 REFR twin, each SOFT kernel next to its SCAT twin, each LENS and LENS_SOFT kernel next to its SCAT and SOFT twin, and each
 texture kernel (TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT) next to its SCAT, SOFT, LENS and LENS_SOFT twin, and each lighting
 kernel (LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT) next to its texture twin, and each sky kernel (SKY_SCAT, SKY_SOFT, SKY_LENS,
@@ -46,7 +47,8 @@ FAMILIES = ("", "mat", "refr", "scat", "soft", "lens", "lens_soft",    # rt::Fam
             "tex_scat", "tex_soft", "tex_lens", "tex_lens_soft", "lit_scat", "lit_soft", "lit_lens", "lit_lens_soft",
             "sky_scat", "sky_soft", "sky_lens", "sky_lens_soft")
 # --twins: (family, its twin, the family's title), and how a twin is called in the heading ("" is PLAIN: "default")
-TWINS = (("ground", "", "ground-plane kernel"), ("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"), ("scat", "refr", "scatter kernel"),
+TWINS = (("ground", "", "ground-plane kernel"), ("ground_small1", "ground", "small-scene kernel, 1 cull group"),
+         ("ground_small2", "ground", "small-scene kernel, 2 cull groups"), ("mat", "", "material kernel"), ("refr", "mat", "refraction kernel"), ("scat", "refr", "scatter kernel"),
          ("soft", "scat", "area-light kernel"), ("lens", "scat", "lens kernel"), ("lens_soft", "soft", "lens area-light kernel"),
          ("tex_scat", "scat", "texture kernel"), ("tex_soft", "soft", "texture area-light kernel"),
          ("tex_lens", "lens", "texture lens kernel"), ("tex_lens_soft", "lens_soft", "texture lens area-light kernel"),
@@ -54,7 +56,7 @@ TWINS = (("ground", "", "ground-plane kernel"), ("mat", "", "material kernel"), 
          ("lit_lens", "tex_lens", "lighting lens kernel"), ("lit_lens_soft", "tex_lens_soft", "lighting lens area-light kernel"),
          ("sky_scat", "lit_scat", "sky kernel"), ("sky_soft", "lit_soft", "sky area-light kernel"),
          ("sky_lens", "lit_lens", "sky lens kernel"), ("sky_lens_soft", "lit_lens_soft", "sky lens area-light kernel"))
-TWIN_NAMES = {"": "default", "mat": "material", "refr": "refraction", "scat": "scatter", "soft": "area-light", "lens": "lens",
+TWIN_NAMES = {"": "default", "ground": "ground-plane", "mat": "material", "refr": "refraction", "scat": "scatter", "soft": "area-light", "lens": "lens",
               "lens_soft": "lens area-light", "tex_scat": "texture", "tex_soft": "texture area-light", "tex_lens": "texture lens",
               "tex_lens_soft": "texture lens area-light", "lit_scat": "lighting", "lit_soft": "lighting area-light",
               "lit_lens": "lighting lens", "lit_lens_soft": "lighting lens area-light"}
@@ -62,7 +64,7 @@ TWIN_NAMES = {"": "default", "mat": "material", "refr": "refraction", "scat": "s
 
 def key(name):
     """Kernel symbol -> ((kernel, its first six template arguments), its family: one of FAMILIES)."""
-    m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)(?:LNS_6FamilyE(\d+)E)?(?:Lb([01])E)?EEvNS_7KParamsE$", name)
+    m = re.match(r"_ZN2rt\d+(\w+?)I((?:L[bi]\d+E)+)(?:LNS_6FamilyE(\d+)E)?(?:Lb([01])E)?(?:Li(\d+)E)?EEvNS_7KParamsE$", name)
     if not m:
         return name, ""
     args = re.findall(r"L[bi](\d+)E", m.group(2))
@@ -70,6 +72,8 @@ def key(name):
         fam = FAMILIES[int(m.group(3))]
         if m.group(4) == "1":                                  # GROUND, behind the family: PLAIN's ground-plane twin
             fam = (fam + "_ground").lstrip("_")
+        if m.group(5) not in (None, "0"):                      # NG, behind GROUND: the ground twin's small-scene twin
+            fam += "_small" + m.group(5)
     else:
         mat, refr, scat, soft, lens = ((args[6:] + ["0"] * 5)[i] == "1" for i in range(5))
         fam = (("lens_soft" if soft else "lens") if lens else "soft" if soft else "scat" if scat else "refr" if refr else
