@@ -2,7 +2,7 @@
 // render kernel in rt_device.h.  HIP only (no torch, no CPU fallback): without a HIP device
 // rt_create fails and nothing renders.  What a call decides before it touches the device lives in
 // HIP-free headers: the packed scene (rt_scene.h), the launch arithmetic (rt_geometry.h), the
-// launch's kernel and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the film entries' checks,
+// launch's kernel (family, shape and twin: its entry in the one table KERNELS below) and order shape (rt_plan.h), the kernels' argument and the entry checks (rt_launch.h), the film entries' checks,
 // kernel arguments and ping-pong plans (rt_film_launch.h), the dispatch-order feedback (rt_feedback.h), the per-stream state: cull-table
 // sets, scratch buffers, scene readers (rt_streams.h).
 #include "../../include/mi355rt.h"
@@ -99,9 +99,7 @@ struct rt_ctx {
                                   // allocated by the first textured (or lit) scene that lands in the slot, grown when one needs more
     bool have_scene = false;
     rt::View view;                // camera, ray grid and lens (rt_launch.h)
-    size_t lds_limit_set[rt::FAMILIES] = {};   // per feature family: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
-    size_t ground_lds_set = 0;                 // ... of PLAIN's ground-plane twins (GROUND_KERNELS)
-    size_t small_lds_set[rt::SMALL_MAX_GROUPS] = {};   // ... of their small-scene twins (SMALL_KERNELS), per number of cull groups
+    size_t lds_set[rt::ROWS] = {};            // per row of KERNELS: hipFuncAttributeMaxDynamicSharedMemorySize of its kernels
     size_t guides_lds_set = 0;                // ... of the three guides kernels (rt_render_guides)
     unsigned *tile_stats = nullptr;   // caller-owned device buffer or NULL
     // Scheduler feedback (rt_feedback.h has the rules and the slots' host state; the device buffers stay here)
@@ -193,68 +191,33 @@ int raise_lds(rt_ctx *ctx, const void *const *fns, size_t n, size_t lds, size_t 
     return RT_OK;
 }
 
-using rt::Shape; using rt::SHAPES; using rt::NSHAPES; using rt::has_kernel; using rt::has_ground_kernel; using rt::has_small_kernel;
+using rt::Shape; using rt::SHAPES; using rt::NSHAPES;
 
-template <rt::Family F, int I, bool GROUND = false, int NG = 0>
+// KERNELS[row][i]: the render kernel of shape SHAPES[i] in that row of rt_plan.h's table (row_kernels: a family's kernels, the
+// ground-plane twins, their small-scene twins per number of cull groups), or nullptr: the row has none (row_has_kernel).  A plan
+// names its entry: KERNELS[plan.row()][plan.index].
+template <int ROW, int I>
 const void *kernel_at()
 {
     constexpr Shape s = SHAPES[I];
-    if constexpr (NG > 0 ? has_small_kernel(F, s) : (GROUND ? has_ground_kernel(F, s) : has_kernel(F, s)))
-        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, F, GROUND, NG>;
+    constexpr rt::Row r = rt::row_kernels(ROW);
+    if constexpr (rt::row_has_kernel(ROW, s))
+        return (const void *)rt::render_kernel<s.aa, s.park, s.wpw, s.count, s.lat, s.mode, r.family, r.ground, r.groups>;
     else
         return nullptr;
 }
-template <rt::Family F, int... I>
-std::array<const void *, NSHAPES> family_kernels(std::integer_sequence<int, I...>)
+using KernelRow = std::array<const void *, NSHAPES>;
+template <int ROW, int... I>
+KernelRow kernel_row(std::integer_sequence<int, I...>)
 {
-    return {kernel_at<F, I>()...};
+    return {kernel_at<ROW, I>()...};
 }
-template <int... I>
-std::array<const void *, NSHAPES> ground_kernels(std::integer_sequence<int, I...>)
+template <int... ROW>
+std::array<KernelRow, rt::ROWS> all_kernels(std::integer_sequence<int, ROW...>)
 {
-    return {kernel_at<rt::Family::PLAIN, I, true>()...};
+    return {{kernel_row<ROW>(std::make_integer_sequence<int, NSHAPES>{})...}};
 }
-template <int NG, int... I>
-std::array<const void *, NSHAPES> small_kernels(std::integer_sequence<int, I...>)
-{
-    return {kernel_at<rt::Family::PLAIN, I, true, NG>()...};
-}
-
-// KERNELS[f][i]: family f's render kernel of shape SHAPES[i] (nullptr: it has none)
-constexpr std::make_integer_sequence<int, NSHAPES> ALL_SHAPES{};
-const std::array<const void *, NSHAPES> KERNELS[rt::FAMILIES] = {
-    family_kernels<rt::Family::PLAIN>(ALL_SHAPES), family_kernels<rt::Family::MAT>(ALL_SHAPES),
-    family_kernels<rt::Family::REFR>(ALL_SHAPES),  family_kernels<rt::Family::SCAT>(ALL_SHAPES),
-    family_kernels<rt::Family::SOFT>(ALL_SHAPES),  family_kernels<rt::Family::LENS>(ALL_SHAPES),
-    family_kernels<rt::Family::LENS_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::TEX_SCAT>(ALL_SHAPES), family_kernels<rt::Family::TEX_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::TEX_LENS>(ALL_SHAPES), family_kernels<rt::Family::TEX_LENS_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::LIT_SCAT>(ALL_SHAPES), family_kernels<rt::Family::LIT_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::LIT_LENS>(ALL_SHAPES), family_kernels<rt::Family::LIT_LENS_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::SKY_SCAT>(ALL_SHAPES), family_kernels<rt::Family::SKY_SOFT>(ALL_SHAPES),
-    family_kernels<rt::Family::SKY_LENS>(ALL_SHAPES), family_kernels<rt::Family::SKY_LENS_SOFT>(ALL_SHAPES),
-};
-// GROUND_KERNELS[i]: the ground-plane twin of PLAIN's kernel of shape SHAPES[i] (rt_plan.h: ground_plane; nullptr: the shape has
-// none: has_ground_kernel)
-const std::array<const void *, NSHAPES> GROUND_KERNELS = ground_kernels(ALL_SHAPES);
-// SMALL_KERNELS[ng - 1][i]: the small-scene twin for ng cull groups of GROUND_KERNELS[i] (rt_plan.h: cull_groups; nullptr: the shape
-// has none: has_small_kernel)
-const std::array<const void *, NSHAPES> SMALL_KERNELS[rt::SMALL_MAX_GROUPS] = {small_kernels<1>(ALL_SHAPES), small_kernels<2>(ALL_SHAPES)};
-static_assert(rt::SMALL_MAX_GROUPS == 2, "SMALL_KERNELS lists the twins of every number of cull groups");
-// The kernels a launch of family fi picks from: its family's, the ground-plane twins, or their small-scene twins for ng cull groups.
-const std::array<const void *, NSHAPES> &kernels_of(int fi, bool ground, int ng = 0)
-{
-    return ng > 0 ? SMALL_KERNELS[ng - 1] : (ground ? GROUND_KERNELS : KERNELS[fi]);
-}
-const void *kernel_of_shape(const std::array<const void *, NSHAPES> &kernels, const Shape &s)
-{
-    for (int i = 0; i < NSHAPES; ++i)
-        if (SHAPES[i] == s) return kernels[i];
-    return nullptr;
-}
-static_assert(rt::FAMILIES == 19 && (int)rt::Family::TEX_LENS_SOFT == 10 && (int)rt::Family::LIT_LENS_SOFT == 14 &&
-              (int)rt::Family::SKY_SCAT == 15 && (int)rt::Family::SKY_LENS_SOFT == 18,
-              "KERNELS lists the families in enum order");
+const std::array<KernelRow, rt::ROWS> KERNELS = all_kernels(std::make_integer_sequence<int, rt::ROWS>{});
 
 // One of the stream's own buffers, `bytes` large (rt_streams.h: growing frees the old buffer, behind a synchronise).
 int stream_buffer(rt_ctx *ctx, Buf &b, hipStream_t stream, size_t bytes, bool sync)
@@ -297,8 +260,8 @@ int launch(rt_ctx *ctx, const rt_params *p, int x0, int x1, void *d_u8, void *d_
                          !(p->flags & RT_FLAG_AA_PER_PIXEL);
     // the launch's family, kernel and LDS size (rt_plan.h), decided once: every slab and frame of the launch runs the same kernel
     const rt::LaunchPlan plan = rt::plan_launch(ctx->lay, ctx->knobs, v.lens_a, !lattice && p->aa_mode != 0, p->flags, lattice, rt::anchors_of(ctx->lay));
-    if (plan.index < 0 || !KERNELS[(int)plan.family][plan.index])
-        return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: rt_plan.h, missing_kernels_never_park)
+    if (plan.index < 0 || !KERNELS[plan.row()][plan.index])
+        return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: rt_plan.h, missing_kernels_never_park; a twin is named only where the shape has one)
     StreamRecord *sr = nullptr;                                // the stream's record, looked up once: scene, tables, lattice
     int rc = stream_record(ctx, stream, &sr);
     if (rc != RT_OK) return rc;
@@ -435,22 +398,14 @@ int launch_one(rt_ctx *ctx, rt::KParams &k, const rt::LaunchPlan &plan, const rt
                Feedback *f, hipStream_t stream, int nframes, int64_t frame_stride)
 {
     const Shape &sh = plan.shape;
-    const int fi = (int)plan.family;
-    // the twin of the planned shape, where the scene has the ground plane and the shape a twin (the shape counts rays exactly when
-    // the launch's flags ask for it: plan_launch)
-    const bool ground = rt::ground_plane(ctx->lay, ctx->knobs, plan.family, sh.count ? RT_FLAG_COUNT_RAYS : 0) && has_ground_kernel(plan.family, sh);
-    // and of that twin the one compiled for the scene's cull groups, where the scene is small and the shape has such twins
-    const int ng = has_small_kernel(plan.family, sh) ? rt::cull_groups(ctx->lay, ctx->knobs, plan.family, sh.count ? RT_FLAG_COUNT_RAYS : 0, k.anchors) : 0;
-    const std::array<const void *, NSHAPES> &kernels = kernels_of(fi, ground, ng);
-    const void *fn = kernels[plan.index];
-    if (!fn) return fail(ctx, RT_ERR_STATE, "no render kernel for this launch");   // (unreachable: launch() checked KERNELS, has_ground_kernel GROUND_KERNELS, has_small_kernel SMALL_KERNELS)
+    const KernelRow &kernels = KERNELS[plan.row()];
+    const void *fn = kernels[plan.index];                      // (launch() checked it)
     const unsigned grid = (unsigned)g.blocks;
     if (ctx->log_kernels)
         std::fprintf(stderr, "mi355rt: render_kernel<%d, %d, %d, %d, %d, %d, (rt::Family)%d>%s\n", (int)sh.aa, (int)sh.park, sh.wpw, (int)sh.count,
-                     (int)sh.lat, sh.mode, fi, ground ? " ground" : "");
-    if (ctx->log_kernels && ng > 0) std::fprintf(stderr, "mi355rt: cull groups %d\n", ng);
-    int rc = raise_lds(ctx, kernels.data(), kernels.size(), plan.lds,
-                       ng > 0 ? ctx->small_lds_set[ng - 1] : (ground ? ctx->ground_lds_set : ctx->lds_limit_set[fi]));
+                     (int)sh.lat, sh.mode, (int)plan.family, plan.twin.ground ? " ground" : "");
+    if (ctx->log_kernels && plan.twin.groups > 0) std::fprintf(stderr, "mi355rt: cull groups %d\n", plan.twin.groups);
+    int rc = raise_lds(ctx, kernels.data(), kernels.size(), plan.lds, ctx->lds_set[plan.row()]);
     if (rc != RT_OK) return rc;
     if (sh.count) {
         if (!ctx->counts.p) {
@@ -1392,15 +1347,12 @@ int rt_get_kernel_info(rt_ctx *ctx, rt_kernel_info *info)
     if (!info) return fail(ctx, RT_ERR_BAD_ARG, "info is NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipFuncAttributes a;
-    // the headline kernel, or its twin where the current scene's plain launches run that (rt_plan.h: ground_plane)
-    const bool ground = ctx->have_scene && rt::ground_plane(ctx->lay, ctx->knobs, rt::Family::PLAIN, 0);
+    // the headline kernel, in the twin that the current scene's plain launches run (rt_plan.h: twin_of); without a scene the generic one
     constexpr Shape headline{false, true, 2, false, false, 0};
-    // ... and of the twin the one for the scene's cull groups (rt_plan.h: cull_groups), as launch_one picks it
-    const int ng = ground && has_small_kernel(rt::Family::PLAIN, headline)
-                       ? rt::cull_groups(ctx->lay, ctx->knobs, rt::Family::PLAIN, 0, rt::anchors_of(ctx->lay)) : 0;
-    const void *fn = ng > 0 ? kernel_of_shape(SMALL_KERNELS[ng - 1], headline)
-                   : ground ? (const void *)rt::render_kernel<false, true, 2, false, false, 0, rt::Family::PLAIN, true>
-                            : (const void *)rt::render_kernel<false, true, 2>;
+    constexpr rt::Family plain = rt::Family::PLAIN;
+    const rt::Twin twin = ctx->have_scene ? rt::twin_of(ctx->lay, ctx->knobs, plain, headline, 0, rt::anchors_of(ctx->lay)) : rt::Twin{false, 0};
+    static_assert(rt::has_small_kernel(plain, headline), "the headline shape has a kernel in every row it can be asked for in");
+    const void *fn = KERNELS[rt::row_of(plain, twin)][rt::shape_index(headline)];
     RT_HIP(ctx, hipFuncGetAttributes(&a, fn));
     hipDeviceProp_t prop;
     RT_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));

@@ -32,6 +32,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rt_kparams.h"  // rt::KParams, the kernels' argument (the host fills it: rt_launch.h)
 #include "rt_math.h"     // V3, the seeded bodies of normalize3 / div_inrange / sqrt_inrange / renormalize_unit, the counter hashes, clip_color
 #include "rt_cull.h"     // the float32 cull's certificates (RayF, cull_anchored, cull_origin, anchored_tau, CULL_K_*) and the guard for culling on the incoming direction
@@ -558,15 +559,26 @@ __device__ __forceinline__ int opaque(int x)
     return x;
 }
 
+// What a kernel's scene queries are compiled for, as one type handed down from the kernel (render_kernel's MODE, GROUND and NG;
+// guides_kernel's MODE) through sample and trace_bounce to closest_hit, any_hit, any_hit_masks, plane_code and plane_count: a
+// further axis of specialisation is a member here, not a parameter of each of them.
+template <int MODE_, bool GROUND_ = false, int NG_ = 0>
+struct Query {
+    static constexpr int MODE = MODE_;          // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
+    static constexpr bool GROUND = GROUND_;     // the one plane is the z-up ground (below)
+    static constexpr int NG = NG_;              // > 0: the scene's spheres are that many cull groups of four (cull_mask_t)
+    static_assert(NG == 0 || (NG <= 2 && GROUND && MODE == 0), "small-scene kernels are wave-uniform (MODE 0) ground-plane kernels of one or two cull groups");
+};
+
 // GROUND (the ground-plane kernels: render_kernel's last template argument; rt_plan.h: ground_plane picks them): the scene has
 // exactly one plane and its stored normal is (0,0,1), the reference's ground.  The queries then take P as 1 (plane_count) and the axis
 // code as +3: no loop over the planes, no decode of the packed codes, no chain of wave-uniform branches on the code, and the one
 // record at a fixed address.  The arithmetic is plane_den_num's z-branch, unchanged.  A template argument, not a flag in Lds like
 // trim and defer: the feature kernels call the queries from lambdas, which are simplified before they are inlined, and a flag read
 // through `lds` there is folded too late to leave their instruction streams as they were.
-template <bool GROUND = false> __device__ __forceinline__ int plane_code(const KParams &p, int k)
+template <class Q> __device__ __forceinline__ int plane_code(const KParams &p, int k)
 {
-    if constexpr (GROUND) return 3;
+    if constexpr (Q::GROUND) return 3;
     // the decoded code and the booleans derived from it are loop-invariant, and the compiler hoists them out of the bounce
     // loop — into scalar registers it does not have: they come back as v_readlane (a VALU slot each) at every use.
     // Re-deriving them from the one kernel-argument word costs scalar instructions only.
@@ -576,10 +588,17 @@ template <bool GROUND = false> __device__ __forceinline__ int plane_code(const K
 }
 
 // The number of planes a query tests: the kernel argument, opaque (above), or the constant 1 of the ground-plane kernels.
-template <bool GROUND = false> __device__ __forceinline__ int plane_count(const KParams &p)
+template <class Q> __device__ __forceinline__ int plane_count(const KParams &p)
 {
-    if constexpr (GROUND) return 1;
+    if constexpr (Q::GROUND) return 1;
     else return opaque(p.P);
+}
+
+// The cull anchor of a query: the caller's where the launch has anchored tables, else none.
+// (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+template <class Q> __device__ __forceinline__ int cull_anchor(const KParams &p, int anchor)
+{
+    return (Q::NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;
 }
 
 // no_negate (Lds::trim): for a normal -e_i both den and num are negated, and everything a query does with the pair is the same for
@@ -945,6 +964,30 @@ __device__ __forceinline__ double pinned_here(double x)
 // NaN ray, which must not send one to the float64 test (it would read a plane record as a sphere).
 __device__ __forceinline__ unsigned small_mask(unsigned long long m, int S) { return (unsigned)m & ((1u << S) - 1u); }
 
+// The chunk of spheres that one cull_mask call of a wave-uniform query answers for, and so the shape of the query's sphere walk
+// `for (int k0 = 0; k0 < C::end(S); k0 += 64)`: 64 spheres and a 64-bit mask, or (NG > 0, the small-scene kernels) all of the
+// scene's at most eight in one chunk and a 32-bit mask: one trip with k0 = 0.  A walk says so with `if constexpr (NG > 0) break;`
+// at the end of its body: the increment is then unreachable and no loop is formed at all.  Left to the bound alone the one-trip
+// loop is deleted only after its invariants (the trim's `~(-1 << S)`) have been hoisted in front of the cull, and the small-scene
+// kernels come out with other instruction counts and, one of them, other resource lines.
+template <int NG> struct Chunk {
+    using mask_t = typename std::conditional<(NG > 0), unsigned, unsigned long long>::type;
+    static __device__ __forceinline__ int end(int S) { return NG > 0 ? 1 : S; }
+    // the chunk's spheres, of the `left` = S - k0 from its first one on
+    static __device__ __forceinline__ int count(int left) { return (NG > 0 || left < 64) ? left : 64; }
+    // padding slots certify themselves, except to a NaN ray
+    static __device__ __forceinline__ mask_t trim(unsigned long long m, int n)
+    {
+        if constexpr (NG > 0) return small_mask(m, n);
+        else return m & ((n == 64) ? ~0ull : ((1ull << n) - 1ull));
+    }
+    static __device__ __forceinline__ int first(mask_t m)
+    {
+        if constexpr (NG > 0) return __builtin_ctz(m);
+        else return __builtin_ctzll(m);
+    }
+};
+
 template <bool F32, bool IN_WINDOW, int NG = 0>
 __device__ __forceinline__ double closest_spheres(const Lds &lds, const KParams &p, int S, int canchor, const V3 &o, const V3 &d, double e,
                                                   double &bestn, int &bidx)
@@ -952,37 +995,23 @@ __device__ __forceinline__ double closest_spheres(const Lds &lds, const KParams 
     double a = 1.0;
     V3 Rg{0.0, 0.0, 0.0};
     if constexpr (!IN_WINDOW) { Rg = normalize3_generic(d); a = dot3(Rg, Rg); }
-    if constexpr (NG > 0) {                                   // one chunk, all of it: no loop, a 32-bit mask
-      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, -1), S);
-      RT_MARK(1);
-      if (mask) {
-        V3 R = Rg;
-        if constexpr (IN_WINDOW) { R = renormalize_unit_fast(d, pinned_here(e)); a = dot3(R, R); }
-        do {                                                  // spheres some live lane might hit, ascending
-          const int k = __builtin_ctz(mask);
-          mask &= mask - 1u;
-          sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
-        } while (mask);
-      }
-      RT_MARK(2);
-      return a;
-    }
-    for (int k0 = 0; k0 < S; k0 += 64) {
-      const int n = (S - k0 < 64) ? S - k0 : 64;
+    using C = Chunk<NG>;
+    for (int k0 = 0; k0 < C::end(S); k0 += 64) {
+      const int n = C::count(S - k0);
       // the float32 ray is rebuilt per chunk so that it is not live during the float64 phase
-      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, -1);
-      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);       // padding slots certify themselves, except to a NaN ray
+      typename C::mask_t mask = C::trim(cull_mask<NG>(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, -1), n);
       RT_MARK(1);
       if (mask) {
         V3 R = Rg;
         if constexpr (IN_WINDOW) { R = renormalize_unit_fast(d, pinned_here(e)); a = dot3(R, R); }
         do {                                                  // spheres some live lane might hit, ascending
-          const int k = k0 + __builtin_ctzll(mask);
-          mask &= mask - 1ull;
+          const int k = k0 + C::first(mask);
+          mask &= mask - 1;
           sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
         } while (mask);
       }
       RT_MARK(2);
+      if constexpr (NG > 0) break;                             // (Chunk: one trip)
     }
     return a;
 }
@@ -994,29 +1023,11 @@ __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KPar
     lanemask occ = 0ull;
     V3 Rg{0.0, 0.0, 0.0};
     if constexpr (!IN_WINDOW) Rg = normalize3_generic(d);
-    if constexpr (NG > 0) {                                   // one chunk, all of it (closest_spheres)
-      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, self), S);
-      RT_MARK(7);
-      if (mask) {
-        V3 R = Rg;
-        if constexpr (IN_WINDOW) R = renormalize_unit_fast(d, pinned_here(e));
-        const double a = dot3(R, R);
-        const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
-        do {
-          const int k = __builtin_ctz(mask);
-          mask &= mask - 1u;
-          occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
-          if (mask && (live & ~occ) == 0ull) break;
-        } while (mask);
-      }
-      RT_MARK(8);
-      return occ;
-    }
-    for (int k0 = 0; k0 < S; k0 += 64) {
+    using C = Chunk<NG>;
+    for (int k0 = 0; k0 < C::end(S); k0 += 64) {
       if (k0 > 0 && (live & ~occ) == 0ull) break;
-      const int n = (S - k0 < 64) ? S - k0 : 64;
-      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, self);
-      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);
+      const int n = C::count(S - k0);
+      typename C::mask_t mask = C::trim(cull_mask<NG>(lds, S, canchor, k0, n, o, cull_dir32(IN_WINDOW ? d : Rg), p.extent2, self), n);
       RT_MARK(7);
       if (mask) {
         V3 R = Rg;
@@ -1024,13 +1035,14 @@ __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KPar
         const double a = dot3(R, R);
         const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
         do {
-          const int k = k0 + __builtin_ctzll(mask);
-          mask &= mask - 1ull;
+          const int k = k0 + C::first(mask);
+          mask &= mask - 1;
           occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
           if (mask && (live & ~occ) == 0ull) break;
         } while (mask);
       }
       RT_MARK(8);
+      if constexpr (NG > 0) break;                             // (Chunk: one trip)
     }
     return occ;
 }
@@ -1038,11 +1050,13 @@ __device__ __forceinline__ lanemask any_spheres_masks(const Lds &lds, const KPar
 // trace.py:7-41, closest hit.  R = normalize(d) and a = R.R are computed once per query.
 // anchor: index into the cull table of a point every live lane's ray passes through (0 = camera),
 // or -1 for rays with no common anchor (reflections).
-template <int MODE, bool GROUND = false, int NG = 0>      // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
+template <class Q>
 __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor,
                                             double &t_out, int &idx_out, int &type_out)
 {
-    const int P = plane_count<GROUND>(p);
+    constexpr int MODE = Q::MODE, NG = Q::NG;
+    using C = Chunk<NG>;
+    const int P = plane_count<Q>(p);
     const int S = p.S;
     // Lds::defer: R and a are formed in front of the first float64 sphere test, not in front of the cull (closest_spheres).
     constexpr bool F32 = MODE >= 1;                           // sphere records: the float32 LDS table (see sphere_hot)
@@ -1053,38 +1067,42 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
         const double e = unit_excess(d);
         const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
         RT_MARK(0);
-        const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+        const int canchor = cull_anchor<Q>(p, anchor);
         if (in_window) aq = closest_spheres<F32, true, NG>(lds, p, S, canchor, o, d, e, bestn, bidx);
         else aq = closest_spheres<F32, false, NG>(lds, p, S, canchor, o, d, e, bestn, bidx);
     } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(0);
-    const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+    const int canchor = cull_anchor<Q>(p, anchor);
     // lane-owned traversal for the rays without a common anchor (bounce 1 on), where the wave's rays have parted;
     // the primary rays of a tile travel together: the wave-uniform cull below is cheaper for them
     if (MODE >= 2 && lds.NC > 0 && (canchor < 0 || p.lanes_primary)) {
         if (canchor >= 0) lanes_closest<true>(lds, p, canchor, o, R, a, bestn, bidx);
         else lanes_closest<false>(lds, p, -1, o, R, a, bestn, bidx);
-    } else if constexpr (NG > 0) {                            // one chunk, all of it (closest_spheres)
-      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, R, p.extent2, -1), S);
+    } else if constexpr (NG > 0) {                            // one chunk, all of it (Chunk)
+      // This walk alone keeps a copy for the one chunk: written as the loop below with a break at its end, like the other three
+      // walks, the loop's variables stand in front of `idx` and `type` in this function, the compiler promotes those two to
+      // registers in the other order, and all six small-scene kernels come out with two v_cndmask swapped and other register
+      // names.  Two of the six then measured 0.2 and 0.3 % over what two builds of the parent differ by
+      // (profiles/kernel_twin_bench.json); with the copy every kernel is its parent's, instruction for instruction.
+      typename C::mask_t mask = C::trim(cull_mask<NG>(lds, S, canchor, 0, S, o, R, p.extent2, -1), S);
       RT_MARK(1);
       while (mask) {
-        const int k = __builtin_ctz(mask);
-        mask &= mask - 1u;
+        const int k = C::first(mask);
+        mask &= mask - 1;
         sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
       }
       RT_MARK(2);
     } else
-    for (int k0 = 0; k0 < S; k0 += 64) {
-      const int n = (S - k0 < 64) ? S - k0 : 64;
+    for (int k0 = 0; k0 < C::end(S); k0 += 64) {
+      const int n = C::count(S - k0);
       // the float32 ray is rebuilt per chunk so that it is not live during the float64 phase
-      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, -1);
-      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);       // padding slots certify themselves, except to a NaN ray
+      typename C::mask_t mask = C::trim(cull_mask<NG>(lds, S, canchor, k0, n, o, R, p.extent2, -1), n);
       RT_MARK(1);
       while (mask) {                                          // spheres some live lane might hit, ascending
-        const int k = k0 + __builtin_ctzll(mask);
-        mask &= mask - 1ull;
+        const int k = k0 + C::first(mask);
+        mask &= mask - 1;
         sphere_closest<F32>(lds, p, k, o, R, a, bestn, bidx);
       }
       RT_MARK(2);
@@ -1101,7 +1119,7 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
     for (int k = 0; k < P; ++k) {                             // intersections.py:41-68
         const double *g = pl + k * PL_STRIDE;
         double den, num;
-        plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num, lds.trim);   // :52, :59-61
+        plane_den_num(g, plane_code<Q>(p, k), o, d, den, num, lds.trim);   // :52, :59-61
         if (!(__builtin_fabs(den) < 0.001)) {                 // :55
             const double t = div_inrange(num, den);           // :63
             if (best > t && t > 0.0) { best = t; idx = k; type = HIT_PLANE; }
@@ -1115,10 +1133,12 @@ __device__ __forceinline__ void closest_hit(const Lds &lds, const KParams &p, co
 // two-wave kernels without a material table): "is any live lane still unoccluded" is then two scalar instructions wherever
 // it is asked, no test runs under a per-lane condition, and the flag becomes a per-lane bool once, at the end.  Same compares
 // on the same values as any_hit's loops below; a lane that is already occluded is tested again (its answer can only stay).
-template <bool GROUND = false, int NG = 0>
+template <class Q>
 __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self)
 {
-    const int P = plane_count<GROUND>(p);
+    constexpr int NG = Q::NG;
+    using C = Chunk<NG>;
+    const int P = plane_count<Q>(p);
     const int S = p.S;
     const lanemask live = lanes_where(true);
     lanemask occ;
@@ -1126,40 +1146,29 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
         const double e = unit_excess(d);
         const bool in_window = cull_reads_d(__builtin_amdgcn_ballot_w64(outside_unit_window(e)));   // wave-uniform
         RT_MARK(6);
-        const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+        const int canchor = cull_anchor<Q>(p, anchor);
         if (in_window) occ = any_spheres_masks<true, NG>(lds, p, S, canchor, o, d, e, self, live);
         else occ = any_spheres_masks<false, NG>(lds, p, S, canchor, o, d, e, self, live);
     } else {
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
     RT_MARK(6);
-    const int canchor = (NG > 0 || opaque(p.anchors) > 0) ? anchor : -1;   // (NG > 0: anchored tables are part of the predicate, rt_plan.h: cull_groups)
+    const int canchor = cull_anchor<Q>(p, anchor);
     const lanemask a_sane = lanes_where(a > 0.999999) & lanes_where(a < 1.000001);
     occ = 0ull;
-    if constexpr (NG > 0) {                                   // one chunk, all of it (closest_spheres)
-      unsigned mask = small_mask(cull_mask<NG>(lds, S, canchor, 0, S, o, R, p.extent2, self), S);
-      RT_MARK(7);
-      while (mask) {
-        const int k = __builtin_ctz(mask);
-        mask &= mask - 1u;
-        occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
-        if (mask && (live & ~occ) == 0ull) break;
-      }
-      RT_MARK(8);
-    } else
-    for (int k0 = 0; k0 < S; k0 += 64) {
+    for (int k0 = 0; k0 < C::end(S); k0 += 64) {
       if (k0 > 0 && (live & ~occ) == 0ull) break;
-      const int n = (S - k0 < 64) ? S - k0 : 64;
-      unsigned long long mask = cull_mask(lds, S, canchor, k0, n, o, R, p.extent2, self);
-      mask &= (n == 64) ? ~0ull : ((1ull << n) - 1ull);
+      const int n = C::count(S - k0);
+      typename C::mask_t mask = C::trim(cull_mask<NG>(lds, S, canchor, k0, n, o, R, p.extent2, self), n);
       RT_MARK(7);
       while (mask) {
-        const int k = k0 + __builtin_ctzll(mask);
-        mask &= mask - 1ull;
+        const int k = k0 + C::first(mask);
+        mask &= mask - 1;
         occ |= sphere_any_mask<false>(lds, k, o, R, a, a_sane);
         if (mask && (live & ~occ) == 0ull) break;
       }
       RT_MARK(8);
+      if constexpr (NG > 0) break;                             // (Chunk: one trip)
     }
     }
     const double *pl = lds.recs() + opaque(p.S) * SPH_STRIDE;
@@ -1167,7 +1176,7 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
         if ((live & ~occ) == 0ull) break;
         const double *g = pl + k * PL_STRIDE;
         double den, num;
-        plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num, true);
+        plane_den_num(g, plane_code<Q>(p, k), o, d, den, num, true);
         const double an = __builtin_fabs(num), ad = __builtin_fabs(den);
         // the signs agree (any_hit: num > 0 && den > 0 || num < 0 && den < 0) where the sign bits do and neither is zero; den is
         // not zero under !(|den| < 0.001); a NaN num fails |num| > 0, a NaN den every test of the quotient below
@@ -1192,12 +1201,12 @@ __device__ __forceinline__ bool any_hit_masks(const Lds &lds, const KParams &p, 
 // anchor = cull-table index of the light the ray points at; self = index of the sphere the ray
 // starts on (-1: a plane), whose miss is certified by the origin-form "behind" test.
 // NG > 0: only the two-wave kernels without a material table (Lds::trim) have small-scene twins, so any_hit_masks answers for them.
-template <int MODE, bool GROUND = false, int NG = 0>
+template <class Q>
 __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const V3 &o, const V3 &d, int anchor, int self, bool lanes = true)
 {
-    static_assert(NG == 0 || MODE == 0, "small-scene kernels are wave-uniform (MODE 0)");
-    if (MODE == 0 && lds.trim) return any_hit_masks<GROUND, NG>(lds, p, o, d, anchor, self);
-    const int P = plane_count<GROUND>(p);
+    constexpr int MODE = Q::MODE;
+    if (MODE == 0 && lds.trim) return any_hit_masks<Q>(lds, p, o, d, anchor, self);
+    const int P = plane_count<Q>(p);
     const int S = p.S;
     const V3 R = renormalize_unit(d);                         // R == normalize(d), intersections.py:13
     const double a = dot3(R, R);
@@ -1230,7 +1239,7 @@ __device__ __forceinline__ bool any_hit(const Lds &lds, const KParams &p, const 
         if (!occ) {
             const double *g = pl + k * PL_STRIDE;
             double den, num;
-            plane_den_num(g, plane_code<GROUND>(p, k), o, d, den, num);
+            plane_den_num(g, plane_code<Q>(p, k), o, d, den, num);
             if (!(__builtin_fabs(den) < 0.001)) {
                 const double an = __builtin_fabs(num), ad = __builtin_fabs(den);
                 const bool same_sign = (num > 0.0 && den > 0.0) || (num < 0.0 && den < 0.0);
@@ -1482,10 +1491,11 @@ __device__ __forceinline__ void hit_normal(const Lds &lds, int type, int idx, in
 // MS::mat: ambient_int and lambert_int are the hit object's material coefficients; its reflectivity is left in the REFL slot (alive lanes).
 // b: the trace index (0: the primary ray); SCAT kernels scatter off rough surfaces with it, and clear `alive` where a scattered
 // path ends (absorption) after this trace's colour.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false, int NG = 0>
+template <bool PARK, int WGT, bool COUNT, class Q, class MS>
 __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, bool &alive, int anchor,
                                              V3 &o, V3 &d, V3 &rgb, RayCount<COUNT> &cnt, MS &ms, int b = 0)
 {
+    constexpr int MODE = Q::MODE;
     constexpr bool NOREC = MODE >= 1;         // no float64 sphere records in LDS (sphere_hot)
     // The wave-level skip of back-facing point lights (rt_facing.h) is compiled out of the lane-owned kernels (MODE 2) of every
     // family: they run at 128 VGPRs with scratch already, and the skip adds 4 to 8 bytes of it per lane there (DESIGN.md §4,
@@ -1498,7 +1508,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
     RT_MARK(11);
     // (LENS: a primary ray starts on the lens, not at the camera: no anchor for its closest hit.  `anchor` itself still says
     // which trace this is for the shadow rays below.)
-    if (alive) closest_hit<MODE, GROUND, NG>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
+    if (alive) closest_hit<Q>(lds, p, o, d, MS::lens ? -1 : anchor, t, idx, type);   // :53 (idle lanes masked off)
     // SKY: the lanes that entered alive and missed return the sky's colour for their direction instead of (0, 0, 0); they end
     // as before.  d is still in registers here, parked kernels included (the hit lanes park it below), so it is neither held
     // longer nor read back; the branch is skipped when no lane of the wave missed (s_cbranch_execz).
@@ -1625,7 +1635,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                     const double k = SLOT(LAMB) * cN;   // :99
                     RT_MARK(5);
                     if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                        const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, -1, self, true);
+                        const bool occluded = any_hit<Q>(lds, p, Pt, Ld, -1, self, true);
                         if (!occluded) lit_add(m, k, [&]() { return soft_Ld(again(m), i); });
                     }
                 }
@@ -1641,7 +1651,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * cN;       // :99
                 RT_MARK(5);
                 if (k > 0.0 || (lit_row()[0] > 0.0 && cN > 0.0)) {
-                    const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                    const bool occluded = any_hit<Q>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                     if (!occluded) lit_add(m, k, [&]() { return point_Ld(again(m)); });
                 }
             }
@@ -1660,7 +1670,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const double k = SLOT(LAMB) * dot3(Ld, N);   // :99
                 RT_MARK(5);
                 if (k > 0.0) {
-                    const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, -1, self, true);
+                    const bool occluded = any_hit<Q>(lds, p, Pt, Ld, -1, self, true);
                     if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
                 }
             }
@@ -1692,7 +1702,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
             RT_MARK(5);
             if (k > 0.0) {
                 // (the shadow rays of the primary hits still travel together: wave-uniform cull unless p.lanes_primary)
-                const bool occluded = any_hit<MODE, GROUND, NG>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
+                const bool occluded = any_hit<Q>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                 if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
             }
         }
@@ -1717,10 +1727,11 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
 // bounce adds W*0, as the reference's does, and the ones after it add the same again (no change).
 // SCAT: key is the sample's scatter_key, kept in its slot for the scatter.  SOFT: lkey is its soft_key, kept in its slot for
 // the light loop.
-template <bool PARK, int WGT, bool COUNT, int MODE, class MS, bool GROUND = false, int NG = 0>       // MODE: 0 plain, 1 plain without float64 sphere records, 2 lane-owned traversal
+template <bool PARK, int WGT, bool COUNT, class Q, class MS>
 __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool alive, V3 o, V3 d, RayCount<COUNT> &cnt, MS &ms,
                                      unsigned key = 0u, unsigned lkey = 0u)
 {
+    constexpr int MODE = Q::MODE;
     Park3<PARK, WGT, MODE == 3> acc(lds.acc, 0, lds.wave);           // the running colour
     acc.set(V3{0.0, 0.0, 0.0});
     if constexpr (MS::mat) SLOT(W) = 1.0;
@@ -1739,7 +1750,7 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
 #ifdef RT_REGION_STATS
         ((volatile unsigned *)lds.reg)[(threadIdx.x >> 6) * 32 + 30] = b >= 2 ? 12u : 0u;
 #endif
-        trace_bounce<PARK, WGT, COUNT, MODE, MS, GROUND, NG>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
+        trace_bounce<PARK, WGT, COUNT, Q, MS>(lds, p, alive, b == 0 ? 0 : -1, o, d, rgb, cnt, ms, b);
         if (b == 0) acc.set(rgb);                                             // :120
         else {                                                                // :131 (a missed bounce adds pow*0; SKY: W * sky(d))
             double wgt;
@@ -1983,7 +1994,8 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     constexpr int WG_THREADS = 64 * WPW, WAVES_PER_WG = WPW;
     constexpr bool M2 = MODE >= 2;
     constexpr bool NOREC = MODE >= 1;
-    static_assert(NG == 0 || (NG <= 2 && GROUND && WPW == 2 && MODE == 0 && !COUNT && F == Family::PLAIN), "small-scene twins: two-wave ground-plane kernels");
+    using Q = Query<MODE, GROUND, NG>;        // what the scene queries below are compiled for
+    static_assert(NG == 0 || (WPW == 2 && !COUNT && F == Family::PLAIN), "small-scene twins: of PLAIN's two-wave kernels");
     constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F), TEX = has_tex(F);
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
     const double *rec_src = p.scene + (NOREC ? (size_t)p.S * SPH_STRIDE : 0);
@@ -2099,7 +2111,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         V3 ro = o, rd;
         if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
         else rd = primary_dir(p, P0);
-        const V3 c = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND, NG>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
+        const V3 c = sample<PARK, WG_THREADS, COUNT, Q, decltype(ms)>(lds, p, inb, ro, rd, cnt, ms, key, lkey);   // kernels.py:19-26
         R = c.x; G = c.y; B = c.z;
     } else {
         // kernels.py:26-65 as ONE loop: tap 0 is the centre sample, taps 1-8 the half-pixel neighbours (only
@@ -2137,7 +2149,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             V3 ro = o, rd;
             if constexpr (LENS) lens_ray(p, lx, ly, stoch ? (unsigned)tap : 0u, Pt, ro, rd);
             else rd = primary_dir(p, Pt);
-            const V3 s = sample<PARK, WG_THREADS, COUNT, MODE, decltype(ms), GROUND, NG>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
+            const V3 s = sample<PARK, WG_THREADS, COUNT, Q, decltype(ms)>(lds, p, (tap && !stoch) ? interior : inb, ro, rd, cnt, ms, key, lkey);   // :26 / :56
             if (tap == 0) taps.set(s);
             else if (stoch) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.y, a.z + s.z}); }
             else if (interior) { const V3 a = taps.get(); taps.set(V3{a.x + s.x, a.y + s.z, a.z + s.y}); }   // :58-60 (G += B_s; B += G_s)

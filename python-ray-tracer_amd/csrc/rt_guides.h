@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64 * GUIDE_WPW) void guides_kernel(const KParams p,
     const V3 d = primary_dir(p, pixel_P(p, xc, yc));
     double t = 999.0;
     int idx = -1, type = HIT_NONE;
-    if (inb) closest_hit<MODE>(lds, p, o, d, 0, t, idx, type);               // (anchor 0: the camera, as the first trace)
+    if (inb) closest_hit<Query<MODE>>(lds, p, o, d, 0, t, idx, type);               // (anchor 0: the camera, as the first trace)
     if (!inb) return;
 
     float g[GUIDE_PLANES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1.0f};

@@ -2,9 +2,11 @@
 // family's kernels runs (its shape: workgroup size, lane-owned or wave-uniform, MODE 1 or not, parked or not), with how much
 // dynamic LDS, and the shape of the dispatch order (group shift, tile or block items, seq_offset).
 // HIP-free, like rt_geometry.h and rt_scene.h and for the same reason: a pure choice on the scene's layout, the MI355RT_* knobs,
-// the AA mode and the flags, testable where there is no GPU.  mi355rt.hip keeps the kernels' addresses (KERNELS, built from SHAPES)
-// and launches what the plan says; tests/algo/launch_plan_check.cpp walks the plan over a table of scenes and knobs under
-// AddressSanitizer and UBSan and compares it with the recorded choice.
+// the AA mode and the flags, testable where there is no GPU.  The plan names the kernel completely: family, shape and twin (the
+// ground-plane or small-scene instantiation of that shape), so the row and column of the one table of kernels' addresses that
+// mi355rt.hip keeps (KERNELS, built from row_kernels and SHAPES).  mi355rt.hip launches what the plan says;
+// tests/algo/launch_plan_check.cpp walks the plan over a table of scenes and knobs under AddressSanitizer and UBSan and compares
+// it with the recorded choice.
 #pragma once
 #include "rt_layout.h"
 #include "rt_scene.h"
@@ -82,6 +84,12 @@ constexpr Shape SHAPES[] = {
     {false, false, 4, true, false, 0}, {true, false, 4, true, false, 0}, {false, false, 4, true, true, 0},
 };
 constexpr int NSHAPES = sizeof SHAPES / sizeof SHAPES[0];
+constexpr int shape_index(const Shape &s)    // in SHAPES, or -1
+{
+    for (int i = 0; i < NSHAPES; ++i)
+        if (SHAPES[i] == s) return i;
+    return -1;
+}
 
 // A family has one render kernel per shape, except
 //  * the counting shapes, which PLAIN alone has (check_params refuses RT_FLAG_COUNT_RAYS for a scene with materials), and
@@ -153,6 +161,38 @@ inline int cull_groups(const SceneLayout &lay, const PlanKnobs &kn, Family fam, 
     return (lay.S + 3) / 4;
 }
 
+// The twin of family fam's kernel of shape s that a launch runs (LaunchPlan names it): both predicates above with the shape's say.
+// `flags` and `anchors` are the launch's, as plan_launch has them.
+struct Twin {
+    bool ground;    // the ground-plane twin
+    int groups;     // > 0: of that twin, the small-scene twin for so many cull groups
+};
+inline Twin twin_of(const SceneLayout &lay, const PlanKnobs &kn, Family fam, const Shape &s, int flags, int anchors)
+{
+    return Twin{ground_plane(lay, kn, fam, flags) && has_ground_kernel(fam, s),
+                has_small_kernel(fam, s) ? cull_groups(lay, kn, fam, flags, anchors) : 0};
+}
+
+// The render kernels stand in one table (mi355rt.hip: KERNELS) of ROWS rows of NSHAPES: a row per family, then the ground-plane
+// twins' row, then a row of small-scene twins per number of cull groups.
+constexpr int GROUND_ROW = FAMILIES, ROWS = FAMILIES + 1 + SMALL_MAX_GROUPS;
+struct Row {
+    Family family;
+    bool ground;
+    int groups;
+};
+constexpr Row row_kernels(int row)
+{
+    return row < FAMILIES ? Row{(Family)row, false, 0} : Row{Family::PLAIN, true, row - GROUND_ROW};
+}
+constexpr int row_of(Family fam, const Twin &t) { return t.groups > 0 ? GROUND_ROW + t.groups : (t.ground ? GROUND_ROW : (int)fam); }
+// Whether the table has a kernel of shape s in that row: has_kernel, has_ground_kernel and has_small_kernel are its cases.
+constexpr bool row_has_kernel(int row, const Shape &s)
+{
+    const Row r = row_kernels(row);
+    return r.groups > 0 ? has_small_kernel(r.family, s) : (r.ground ? has_ground_kernel(r.family, s) : has_kernel(r.family, s));
+}
+
 // The parking rule of the wave-uniform kernels (plan_launch): their state parks in LDS while PARK_WAVES wavefronts per CU still
 // fit their workgroups' LDS images.
 constexpr int PARK_WAVES = 24;
@@ -196,6 +236,8 @@ struct LaunchPlan {
     Shape shape;
     int index;      // of shape in SHAPES
     size_t lds;     // dynamic LDS bytes of the launch
+    Twin twin;      // which twin of that kernel runs (twin_of): a dimension of its own, nothing above depends on it
+    int row() const { return row_of(family, twin); }   // the kernel is KERNELS[row()][index]
 };
 
 // Chooses the kernel instantiation for a launch: `aa`: the launch has an AA mode of its own (a lattice launch has none), `flags`:
@@ -204,7 +246,7 @@ struct LaunchPlan {
 // (every workgroup stages its own copy; rt_layout.h has the measurements).
 // Kernel variant: state parked in LDS (7 waves/SIMD, no scratch) while at least PARK_WAVES wavefronts per CU still
 // fit their workgroups' LDS images; otherwise the register variant (its occupancy is then LDS-bound anyway).
-// The kernel is the family's of the launch's shape (mi355rt.hip: KERNELS).
+// The kernel is the family's of the launch's shape, or the twin of it that twin_of names (mi355rt.hip: KERNELS).
 inline LaunchPlan plan_launch(const SceneLayout &lay, const PlanKnobs &kn, double lens_a, bool aa, int flags, bool lattice, int anchors)
 {
     const Family fam = family_of(lay, lens_a);
@@ -242,9 +284,8 @@ inline LaunchPlan plan_launch(const SceneLayout &lay, const PlanKnobs &kn, doubl
     pl.family = fam;
     pl.shape = Shape{aa, park, wpw, count, lattice, lanes && aa && park ? 3 : mode};
     pl.lds = park ? lds_park : bytes(false, mode);
-    pl.index = -1;
-    for (int i = 0; i < NSHAPES; ++i)
-        if (SHAPES[i] == pl.shape) pl.index = i;
+    pl.index = shape_index(pl.shape);
+    pl.twin = twin_of(lay, kn, fam, pl.shape, flags, anchors);
     return pl;
 }
 

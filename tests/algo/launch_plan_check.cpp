@@ -6,9 +6,10 @@
  *                              {knob row, S, P, L, family, AA (0 off, 1 on, 2 the lattice), RT_FLAG_COUNT_RAYS, RT_FLAG_NO_BUNDLES}
  *                              and its 13 results {family, the shape's aa, park, wpw, count, lat, mode, its index in SHAPES, LDS
  *                              bytes, anchors, gshift, the order's code, seq_offset != 0}
- * and prints "cases=N kernels=K ok": K the (family, shape) pairs has_kernel admits.  The order's shape is that of a 32 x 24 frame
- * (12 tiles: 3 or 6 workgroups, so feedback and tile-order items are live).  It fails if a case picks a shape its family has no
- * kernel for, or an LDS size that is not lds_bytes of the picked shape. */
+ * and prints "cases=N kernels=K table=T ok": K the (family, shape) pairs has_kernel admits, T the (row, shape) pairs of the whole
+ * table of render kernels (row_has_kernel: the families' rows, the ground-plane twins' and the small-scene twins').  The order's
+ * shape is that of a 32 x 24 frame (12 tiles: 3 or 6 workgroups, so feedback and tile-order items are live).  It fails if a case
+ * plans a row and shape the table has no kernel for, or an LDS size that is not lds_bytes of the picked shape. */
 #include "../../python-ray-tracer_amd/csrc/rt_plan.h"
 
 #include <cstdint>
@@ -76,7 +77,7 @@ int main(int argc, char **argv)
             for (int am = 0; am < 3; ++am) for (int cnt = 0; cnt < (f == rt::Family::PLAIN ? 2 : 1); ++cnt) for (int nb = 0; nb < 2; ++nb) {
                 const int flags = (cnt ? RT_FLAG_COUNT_RAYS : 0) | (nb ? RT_FLAG_NO_BUNDLES : 0);
                 const rt::LaunchPlan pl = rt::plan_launch(lay, kn, lens_a, am == 1, flags, am == 2, anchors);
-                if (pl.family != f || pl.index < 0 || !(rt::SHAPES[pl.index] == pl.shape) || !rt::has_kernel(f, pl.shape)) {
+                if (pl.family != f || pl.index < 0 || !(rt::SHAPES[pl.index] == pl.shape) || !rt::row_has_kernel(pl.row(), pl.shape)) {
                     std::fprintf(stderr, "knobs %d S=%d P=%d L=%d family %d aa %d flags %d: no kernel of the picked shape\n", kr, S, P, L, fi, am, flags);
                     return 1;
                 }
@@ -96,8 +97,11 @@ int main(int argc, char **argv)
     int kernels = 0;
     for (int fi = 0; fi < rt::FAMILIES; ++fi)
         for (const rt::Shape &s : rt::SHAPES) kernels += rt::has_kernel((rt::Family)fi, s);
+    int table = 0;                          /* ... and of every row: the families', the ground-plane twins', the small-scene twins' */
+    for (int row = 0; row < rt::ROWS; ++row)
+        for (const rt::Shape &s : rt::SHAPES) table += rt::row_has_kernel(row, s);
     FILE *fo = std::fopen(argv[1], "wb");
     if (!fo || std::fwrite(out.data(), sizeof(int32_t), out.size(), fo) != out.size() || std::fclose(fo) != 0) return 1;
-    std::printf("cases=%ld kernels=%d ok\n", cases, kernels);
+    std::printf("cases=%ld kernels=%d table=%d ok\n", cases, kernels, table);
     return 0;
 }

@@ -1,8 +1,10 @@
 /* small_scene_check.cpp — rt::cull_groups (rt_plan.h), the choice between a two-wave ground-plane kernel and its small-scene twin
  * compiled for one or two cull groups (rt_device.h: NG), on scenes packed by the library's own packer (rt_scene.h), with the anchors
  * rt::anchors_of gives them, as a launch has them.
- * Prints one line per case, "<name> <groups>", and checks beside it that the choice changes nothing else of the plan: plan_launch
- * does not read the knob.  Then the shapes that have such twins (has_small_kernel), one line each.
+ * Prints one line per case, "<name> <groups>", and checks beside it that the choice changes nothing else of the plan: plan_launch's
+ * family, shape, index and LDS bytes do not read the knob, and the twin the plan names (LaunchPlan::twin) has cull_groups where
+ * has_small_kernel(shape), else 0, and ground_plane && has_ground_kernel(shape), for each of the three AA modes.  Then the shapes
+ * that have such twins (has_small_kernel), one line each.
  *   small_scene_check          the table of tests/test_small_scene.py
  *   small_scene_check lights   one case, for a build with -DRT_MAX_CULL_TABLE_BYTES=2048: 8 spheres and 16 lights, whose anchored
  *                              table (17 rows of 128 bytes) is over that budget, so that anchors_of returns 0.  With the product's
@@ -60,6 +62,13 @@ static void report(const char *name, const rt::PackedScene &ps, int flags = 0, i
         const rt::LaunchPlan b = rt::plan_launch(lay, off, 0.0, am == 1, flags, am == 2, anchors);
         if (a.family != b.family || !(a.shape == b.shape) || a.index != b.index || a.lds != b.lds) {
             std::fprintf(stderr, "%s: the plan depends on the knob\n", name); ++failures;
+        }
+        /* the twin the plan names is the predicate's answer where the shape has small-scene twins, else none */
+        if (a.twin.groups != (rt::has_small_kernel(a.family, a.shape) ? g : 0) || b.twin.groups != 0) {
+            std::fprintf(stderr, "%s: aa mode %d: the plan's cull groups are not cull_groups where has_small_kernel\n", name, am); ++failures;
+        }
+        if (a.twin.ground != (rt::ground_plane(lay, on, fam, flags) && rt::has_ground_kernel(a.family, a.shape)) || a.twin.ground != b.twin.ground) {
+            std::fprintf(stderr, "%s: aa mode %d: the plan's twin is not ground_plane && has_ground_kernel\n", name, am); ++failures;
         }
         /* the table rows of a scene with groups are exactly those groups of four, and it plans a wave-uniform shape (whether a
          * two-wave one, which alone has the twins, is the LDS image's business: 64 lights make it a four-wave one) */

@@ -304,15 +304,17 @@ def test_launch_plan_is_the_recorded_one(tmp_path):
     100 800 cases.  Every row must be, exactly, what tests/golden/launch_plan.npz holds: the choice of the library's dispatch() as it
     was before the plan became a header of its own, recorded by a program that included that commit's rt_device.h, held that
     commit's launch() and dispatch() expressions copied verbatim, was built with hipcc for gfx950 and ran its host arithmetic on a
-    CPU.  No case may pick a shape its family has no kernel for, the picked (family, shape) pairs are exactly the 285 has_kernel
-    admits, the LDS size is lds_bytes of the picked shape (the program checks both), and both sides of each threshold occur."""
+    CPU.  No case may plan a row and shape of the kernel table that has no kernel (row_has_kernel), the picked (family, shape) pairs
+    are exactly the 285 has_kernel admits, the LDS size is lds_bytes of the picked shape (the program checks both), and both sides
+    of each threshold occur.  The whole table has 307 render kernels: those 285, the 16 ground-plane twins and the 2 x 3 small-scene
+    twins (with the library's 21 other kernels, the 328 that tools/isa_compare.py counts)."""
     import numpy as np
     exe, got_path = str(tmp_path / "launch_plan_check"), str(tmp_path / "got.bin")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "launch_plan_check.cpp")])
     res = subprocess.run([exe, got_path], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
     assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
-    assert res.stdout.strip() == "cases=100800 kernels=285 ok", res.stdout
+    assert res.stdout.strip() == "cases=100800 kernels=285 table=307 ok", res.stdout
     want = np.load(os.path.join(REPO, "tests", "golden", "launch_plan.npz"))
     got = np.fromfile(got_path, np.int32)
     nk = want["knobs"].size

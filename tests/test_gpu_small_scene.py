@@ -182,6 +182,39 @@ def test_scenes_that_take_no_small_scene_twin(monkeypatch, capfd, name, scene, t
     _compare(monkeypatch, capfd, name, scene(), 32, 24, 2, 0, tail=tail)
 
 
+@pytest.mark.parametrize("name,scene,tail,groups", [("default_scene", lambda: gps.fixture_scene("default_128_d3"), "ground", 2),
+                                                    ("nine_spheres", _nine, "ground", 0), ("tilted_plane", _tilted, "", 0)])
+def test_kernel_info_reads_the_twin_the_scene_runs(monkeypatch, capfd, name, scene, tail, groups):
+    """rt_get_kernel_info reports the headline shape's kernel in the twin that the current scene's plain launches run: the
+    small-scene twin for the default scene's eight spheres, the ground-plane twin with a ninth sphere, the generic kernel over a
+    tilted plane.  One 32 x 24 frame each, default parameters; the launch must log that twin, and the call must succeed behind it.
+    The three instantiations have the same register count (71 VGPRs, 94 SGPRs in the compiler's resource remarks for
+    render_kernel<0, 1, 2, 0, 0, 0, PLAIN>, <..., true> and <..., true, 2>), so `vgprs` cannot tell them apart and is not compared:
+    that the call reads the entry of the launch's own table is what rt_plan.h's twin_of and the checks under tests/algo pin."""
+    import python_ray_tracer_amd as pkg
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("MI355RT_LOG_KERNELS", "1")
+    sc, w, h = scene(), 32, 24
+    amb, lamb, refl = sc["shade"]
+    capfd.readouterr()
+    with pkg.Renderer(0) as r:
+        before = r.kernel_info()                                  # no scene yet: the generic kernel
+        r.set_scene(sc["spheres"], sc["lights"], sc["planes"])
+        r.set_camera(sc["cam_origin"], sc["cam_rot"])
+        r.set_raygen(w, h, *raygen_closed_form(w, h, sc["fov"]))
+        u8, _ = r.render(amb, lamb, refl, 3, 0, u8=True)
+        info = r.kernel_info()
+    got = LOG_LINE.findall(capfd.readouterr().err)
+    kernels = [m for m in got if not m[8]]
+    print(f"{name}: {got}, kernel_info {info}")
+    assert kernels and all(tuple(int(v) for v in m[:7]) == (0, 1, 2, 0, 0, 0, 0) and m[7].strip() == tail for m in kernels), (name, got)
+    assert [int(m[8]) for m in got if m[8]] == ([groups] * len(kernels) if groups else []), (name, got)
+    assert np.asarray(u8).any(), name
+    for i in (before, info):
+        assert i["vgprs"] > 0 and i["wave_size"] == 64 and i["cu_count"] > 0, (name, i)
+
+
 def test_against_the_oracle(monkeypatch, capfd, oracle):
     sc, w, h = small_scene(6), 48, 48
     u8, f32 = _compare(monkeypatch, capfd, "S=6 48x48 d3", sc, w, h, 3, 2)
