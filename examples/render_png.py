@@ -9,6 +9,7 @@
                                   [--denoise-variance [--kappa K]]
                                   [--bloom [STRENGTH] [--bloom-threshold T] [--bloom-levels N]]
                                   [--orbit K --temporal [--orbit-step DEG] [--denoise-variance [--spatial-below L]]]
+                                  [--auto-exposure [KEY] [--adapt RATE]]
 
 --materials renders the scene with per-object materials (rt_set_scene_materials): a mirror floor under matte spheres.
 --scatter renders rough materials (rt_set_scene_materials_scatter): brushed-metal spheres and a satin floor; with --spp N
@@ -52,6 +53,13 @@ film carries its second moment through the moves as well (rt_film_temporal_momen
 tolerance per pixel (rt_film_denoise_variance_temporal): tight where the history survived, wide where the move uncovered something;
 pixels whose history is shorter than --spatial-below passes (default the library's) take their variance from their neighbours, so
 --passes 1 is enough.  For example --sky --soft --shadow-samples 1 --orbit 8 --passes 1 --temporal --denoise-variance --white 400.
+
+--auto-exposure [KEY] meters the picture on the device (rt_film_meter, rt_film_meter_solve, rt_film_resolve_metered): the median
+luminance of what the resolve shows (filtered, bloomed or plain) is mapped to KEY colour units (default 46, 18 % of 255) and
+--exposure becomes a compensation on top; without --passes it takes four passes.  With --orbit K the exposure moves --adapt RATE of
+the way to each step's own (default 1: it jumps), as an eye adapts; --orbit then also works without --temporal (every step a
+fresh film, so with --dof).  For example --sky --dof 0.1 --passes 16 --white 400 --bloom --auto-exposure, and the same with
+--orbit 8 --adapt 0.25.
 
 The device writes the interleaved (h, w, 3) image directly (RT_FLAG_U8_HWC | RT_FLAG_U8_RGB) into page-locked host
 memory; the frame time is measured with HIP events over `--frames` launches.  For the numba-shaped call the
@@ -108,10 +116,13 @@ def main():
     ap.add_argument("--orbit", type=int, default=0, metavar="K", help="--temporal: render K camera steps of an orbit and write the last frame")
     ap.add_argument("--orbit-step", type=float, default=2.0, metavar="DEG", help="--orbit: degrees per camera step")
     ap.add_argument("--temporal", action="store_true", help="carry the film through the camera moves of --orbit (temporal accumulation)")
+    ap.add_argument("--auto-exposure", type=float, nargs="?", const=46.0, default=None, metavar="KEY",
+                    help="meter the picture on the device: its median luminance maps to KEY (four passes unless --passes)")
+    ap.add_argument("--adapt", type=float, default=1.0, metavar="RATE", help="--auto-exposure --orbit: the share of the way the exposure moves per step, (0, 1]")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    if (a.denoise or a.temporal or a.denoise_variance or a.bloom is not None) and a.passes <= 0:
+    if (a.denoise or a.temporal or a.denoise_variance or a.bloom is not None or a.auto_exposure is not None) and a.passes <= 0:
         a.passes = 4
     if a.denoise_variance and a.denoise:
         ap.error("--denoise-variance stands in place of --denoise")
@@ -121,8 +132,10 @@ def main():
         ap.error("--spatial-below goes with --temporal --denoise-variance")
     if a.temporal and a.orbit < 1:
         a.orbit = 8
-    if a.orbit > 0 and not a.temporal:
-        ap.error("--orbit renders through --temporal")
+    if a.orbit > 0 and not a.temporal and a.auto_exposure is None:
+        ap.error("--orbit renders through --temporal, or with --auto-exposure")
+    if a.adapt != 1.0 and a.auto_exposure is None:
+        ap.error("--adapt goes with --auto-exposure")
     if a.temporal and a.dof > 0:
         ap.error("--temporal reprojects the pinhole camera's guides: not with --dof")
     euler = [0, -12, 0] if a.sky else [0, -30, 0]                   # --sky: the horizon a third of the way down the picture
@@ -194,7 +207,9 @@ def main():
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
         aa = 2 if a.spp > 0 else a.aa
         p = r.params(0.0, 0.6, 0.3, a.depth, aa, flags=flags, spp=a.spp)
-        if a.temporal:                                          # a film carried through the camera moves of an orbit
+        auto = a.auto_exposure is not None
+        meter_kw = dict(key=a.auto_exposure, rate=a.adapt) if auto else {}
+        if a.temporal or a.orbit > 0:                           # a film carried through the camera moves of an orbit
             from python_ray_tracer_amd.temporal import orbit
             start = (np.asarray(cam.position, np.float64), np.asarray(cam.rotation, np.float64))
             pivot = start[0] + 4.0 * start[1][:, 0]             # a point the camera looks at
@@ -204,18 +219,29 @@ def main():
                 r.timer_begin()
                 for k in range(a.orbit):
                     r.set_camera(*orbit(start, pivot, a.orbit_step * k))
-                    film.next_frame()
+                    if a.temporal:
+                        film.next_frame()
+                    else:                                       # (--auto-exposure alone: every step a fresh film; the exposure stays)
+                        film.clear()
                     p.seed = 1 + k * a.passes
                     film.accumulate(p, a.passes)
-                    film.temporal()
+                    src = dict(denoised=a.denoise or a.denoise_variance, temporal=a.temporal)
+                    if a.temporal:
+                        film.temporal()
                     if a.denoise:
-                        film.denoise(levels=a.denoise_levels, temporal=True)
+                        film.denoise(levels=a.denoise_levels, temporal=a.temporal)
                     if a.denoise_variance:
-                        film.denoise(variance=True, temporal=True, levels=a.denoise_levels, **var_kw)
+                        film.denoise(variance=True, temporal=a.temporal, levels=a.denoise_levels, **var_kw)
+                    if auto:                                    # every step is metered: the exposure adapts along the orbit
+                        if a.bloom is not None:
+                            film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, **src)
+                        film.meter(bloom=a.bloom is not None, **src, **meter_kw)
                 ms = r.timer_end() / (a.orbit * a.passes)
-                if a.bloom is not None:
-                    film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, denoised=a.denoise or a.denoise_variance, temporal=True)
-                image = film.resolve(denoised=a.denoise or a.denoise_variance, temporal=True, bloom=a.bloom is not None, **tone)[0]
+                if a.bloom is not None and not auto:
+                    film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, **src)
+                image = film.resolve(bloom=a.bloom is not None, auto_exposure=auto, **src, **tone)[0]
+                if auto:
+                    print("auto-exposure: exposure {:.6g}, metered luminance {:.6g}, {:.0f} pixels, bin {:.0f}".format(*film.exposure()))
         elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
             with pkg.Film(r, moments=a.denoise_variance) as film:
                 film.accumulate(p, a.passes)
@@ -225,8 +251,12 @@ def main():
                     film.denoise(variance=True, levels=a.denoise_levels, **({} if a.kappa is None else dict(kappa=a.kappa)))
                 if a.bloom is not None:                         # the glow of the source that the resolve shows, before the tone curve
                     film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, denoised=a.denoise or a.denoise_variance)
+                if auto:                                        # the exposure of the source that the resolve shows, solved on the device
+                    film.meter(denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None, **meter_kw)
                 image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags,
-                                     denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None)[0]
+                                     denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None, auto_exposure=auto)[0]
+                if auto:
+                    print("auto-exposure: exposure {:.6g}, metered luminance {:.6g}, {:.0f} pixels, bin {:.0f}".format(*film.exposure()))
                 r.timer_begin()
                 for _ in range(a.frames):                       # (timed: one more pass into the sum, per pass)
                     film.accumulate(p, 1)

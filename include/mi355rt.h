@@ -861,6 +861,74 @@ typedef struct rt_bloom {
 int rt_film_bloom(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl,
                   void *d_out, int64_t out_stride, void *d_work, int64_t work_stride, void *stream);
 
+/* Metering: a luminance histogram of the film and an exposure solved from it, on the device.  rt_film_resolve takes its exposure
+ * by value from the host; a caller who wanted one that suits the picture had to copy the float64 mean back.  The three entries
+ * below are queued on one stream (meter, solve, resolve) and never synchronise with the host.  RT_ABI_VERSION is unchanged: callers
+ * detect these entry points by their symbols.
+ *
+ * rt_film_meter: d_sum is three float64 planes like every film buffer, element [c, x, y] at c*sum_stride + x*h + y: a sum of n
+ * passes, or a mean with n = 1 (a four-plane buffer is fine: only planes 0..2 are read).  d_hist is RT_METER_BINS uint64 counts,
+ * 8-byte aligned.  reset != 0 zeroes the counts first; reset == 0 adds to what is there, so slabs, ranks and frames add up exactly
+ * (integers).  Per pixel p, in float64 without fused multiply-add:
+ *   m_c = s[c][p] / (double)n
+ *   Y = (0.2126 * m_0 + 0.7152 * m_1) + 0.0722 * m_2
+ *   !(Y > 0)  (zero, negative, NaN):  bin 0
+ *   else  u = the 64 bits of Y;   k = (int64)(u >> 49) - 8056        (8056 = (1023 + RT_METER_LO) * 8)
+ *         k < 0: bin 1        k >= 320: bin 322  (+Inf included)        else: bin 2 + k
+ *   hist[bin] = hist[bin] + 1
+ * So bins 2..321 cover [2^-16, 2^24) colour units, eight per octave: bin b is [edge(b), edge(b+1)) with edge(b) the float64 whose
+ * bits are (uint64)(b - 2 + 8056) << 49, which is (1 + j/8) * 2^E, exact.  Bin 0 holds what has no luminance, bin 1 what is below
+ * 2^-16, bin 322 what is at or above 2^24.  There is no log(): the bins come from the bits of a float64 and the counts are
+ * integers, so the bytes depend neither on a math library nor on the order in which lanes arrive.
+ * RT_ERR_BAD_ARG, in this order, for: a NULL d_sum or d_hist; ws*h outside 1..RT_FILM_MAX_PIXELS; n < 1; sum_stride < ws*h; a
+ * d_hist that is not 8-byte aligned or equals d_sum.  The counts are then untouched.  Asynchronous on `stream`; it needs no scene.
+ *
+ * rt_film_meter_solve: a histogram to an exposure.  mt holds the settings; d_state is RT_METER_STATE_DOUBLES float64 that the call
+ * reads and writes (8-byte aligned); a state of zeros means "no history".
+ *   N = hist[1] + ... + hist[322]                    (bin 0 is not metered)
+ *   prev = state[0];   usable = prev is finite and > 0
+ *   N == 0:  e = usable ? prev : clamp(1.0);   state = (e, +0.0, 0.0, 0.0);   done
+ *   r = (uint64)(percentile * (double)N);   r > N-1: r = N-1
+ *   b = the smallest bin in 1..322 with C_b > r,  C_b = hist[1] + ... + hist[b];   below = C_{b-1}
+ *   b == 1: Ym = 2^-16     b == 322: Ym = 2^24
+ *   else  lo = edge(b); hi = edge(b+1);  Ym = lo + (hi - lo) * ((double)(r - below) / (double)hist[b])
+ *   t = clamp(key / Ym)                      clamp(v): v < min_exposure ? min_exposure : (v > max_exposure ? max_exposure : v)
+ *   e = (usable and rate < 1) ? clamp(prev + (t - prev) * rate) : t
+ *   state = (e, Ym, (double)N, (double)b)
+ * key is the luminance the metered value is mapped to; the interpolation inside the bin keeps the exposure from moving in steps
+ * of an eighth of an octave; rate is the eye's adaptation from frame to frame (1 jumps).  Float64 without fused multiply-add; the
+ * counts are assumed to add up below 2^63.
+ * RT_ERR_BAD_ARG, in this order, for: a NULL d_hist, mt or d_state; a key that is not (finite and > 0); a percentile outside 0..1;
+ * a min_exposure that is not (finite and > 0); a max_exposure that is not (finite and > 0); min_exposure > max_exposure; a rate
+ * outside (0, 1]; flags != 0; reserved != 0; d_state equal to d_hist.  The state is then untouched.  Asynchronous on `stream`.
+ *
+ * rt_film_resolve_metered: rt_film_resolve with one line changed.  The exposure used is E = tone->exposure * x, one float64
+ * product, formed once; x = state[0] when that is finite and > 0, otherwise x = 1.0; tone->exposure becomes the user's
+ * compensation.  With state[0] == 1.0 the outputs are rt_film_resolve's bit for bit.  The refusals are rt_film_resolve's, in its
+ * order, and a NULL d_state (behind a NULL tone). */
+#define RT_METER_LO            (-16)   /* log2 of the lower edge of bin 2 */
+#define RT_METER_OCTAVES       40
+#define RT_METER_SUB           8       /* bins per octave */
+#define RT_METER_BINS          323     /* 40 * 8 + 3 */
+#define RT_METER_STATE_DOUBLES 4       /* exposure, metered luminance, pixels metered, the bin it fell in */
+
+typedef struct rt_meter {
+    double  key;            /* finite, > 0, colour units: the luminance the metered value is mapped to */
+    double  percentile;     /* 0..1 */
+    double  min_exposure;   /* finite, > 0, min_exposure <= max_exposure */
+    double  max_exposure;   /* finite, > 0 */
+    double  rate;           /* in (0, 1]; 1 jumps */
+    int32_t flags;          /* must be 0 */
+    int32_t reserved;       /* must be 0 */
+} rt_meter;                 /* 48 bytes */
+
+int rt_film_meter(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, int reset, void *d_hist,
+                  void *stream);
+int rt_film_meter_solve(rt_ctx *ctx, const void *d_hist, const rt_meter *mt, void *d_state, void *stream);
+int rt_film_resolve_metered(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n,
+                            const rt_film_tone *tone, const void *d_state, void *d_u8, void *d_f32, int64_t out_stride,
+                            void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

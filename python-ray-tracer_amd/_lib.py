@@ -20,6 +20,7 @@ RT_FILM_MAX_PIXELS = 1 << 27
 RT_GUIDE_PLANES = 8
 RT_TEMPORAL_MAX_N = 1 << 24          # rt_film_temporal: the most passes one call blends in
 RT_BLOOM_MAX_LEVELS, RT_BLOOM_WORK_PLANES, RT_BLOOM_NO_TILES = 8, 6, 1
+RT_METER_LO, RT_METER_OCTAVES, RT_METER_SUB, RT_METER_BINS, RT_METER_STATE_DOUBLES = -16, 40, 8, 323, 4
 RT_FLAG_TYPED_BIAS, RT_FLAG_U8_RGB, RT_FLAG_NO_FEEDBACK, RT_FLAG_U8_HWC, RT_FLAG_COUNT_RAYS, RT_FLAG_AA_PER_PIXEL, RT_FLAG_NO_BUNDLES = 1, 2, 4, 8, 16, 32, 64
 
 STATUS_NAMES = {0: "RT_OK", -1: "RT_ERR_BAD_ARG", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEVICE", -4: "RT_ERR_STATE", -5: "RT_ERR_ALLOC"}
@@ -80,6 +81,14 @@ class rt_bloom(C.Structure):
     _fields_ = [("threshold", C.c_double), ("strength", C.c_double), ("levels", C.c_int32), ("flags", C.c_int32)]
 
 
+class rt_meter(C.Structure):
+    """rt_film_meter_solve's settings (include/mi355rt.h; the arithmetic in numpy: meter.solve_reference): key finite and > 0;
+    percentile 0..1; min_exposure and max_exposure finite and > 0, min_exposure <= max_exposure; rate in (0, 1]; flags and reserved
+    0.  48 bytes."""
+    _fields_ = [("key", C.c_double), ("percentile", C.c_double), ("min_exposure", C.c_double), ("max_exposure", C.c_double),
+                ("rate", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
 _dp, _fp, _vp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p
 PROTOTYPES = {
@@ -133,6 +142,9 @@ PROTOTYPES = {
     "rt_film_denoise_variance_temporal": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, C.c_int64,
                                                     C.POINTER(rt_denoise_variance), C.c_double, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "rt_film_bloom": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_bloom), _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "rt_film_meter": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _vp, _vp]),
+    "rt_film_meter_solve": (C.c_int, [_vp, _vp, C.POINTER(rt_meter), _vp, _vp]),
+    "rt_film_resolve_metered": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_film_tone), _vp, _vp, _vp, C.c_int64, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -155,7 +167,8 @@ PROTOTYPES = {
 # Entry points added without a new ABI version: a build of the same version from before them binds without them (tools/ab_bench.py
 # times such a build beside this one), and Renderer raises where one is called.
 LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance",
-                 "rt_film_temporal_moments", "rt_film_denoise_variance_temporal", "rt_film_bloom")
+                 "rt_film_temporal_moments", "rt_film_denoise_variance_temporal", "rt_film_bloom", "rt_film_meter", "rt_film_meter_solve",
+                 "rt_film_resolve_metered")
 
 _lib = None
 

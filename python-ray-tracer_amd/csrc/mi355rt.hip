@@ -1026,6 +1026,48 @@ int rt_film_bloom(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, in
     return RT_OK;
 }
 
+// Metering (rt_meter.h): the histogram of the film's luminance, the exposure solved from it, and the resolve that multiplies it in.
+// Three launches on the caller's stream; nothing is allocated and nothing waits for the device.
+int rt_film_meter(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, int reset, void *d_hist, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_film_meter(d_sum, sum_stride, ws, h, n, d_hist));
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_of(ctx, stream);
+    const rt::MeterHistArgs a = rt::meter_hist_args(d_sum, sum_stride, ws, h, n, d_hist);
+    if (reset) hipLaunchKernelGGL(rt::meter_clear_kernel, dim3(1), dim3(rt::METER_THREADS), 0, st, a.hist);
+    hipLaunchKernelGGL(rt::meter_hist_kernel, dim3(rt::meter_grid((a.npx + 3) >> 2, ctx->cu_count)), dim3(rt::METER_THREADS), 0, st, a);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+int rt_film_meter_solve(rt_ctx *ctx, const void *d_hist, const rt_meter *mt, void *d_state, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_film_meter_solve(d_hist, mt, d_state));
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(rt::meter_solve_kernel, dim3(1), dim3(rt::METER_SOLVE_THREADS), 0, stream_of(ctx, stream),
+                       (const unsigned long long *)d_hist, *mt, (double *)d_state);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+int rt_film_resolve_metered(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone,
+                            const void *d_state, void *d_u8, void *d_f32, int64_t out_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_film_resolve_metered(d_sum, sum_stride, ws, h, n, tone, d_state, d_u8, d_f32, out_stride));
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const rt::FilmResolveArgs a = rt::film_resolve_args(d_sum, sum_stride, ws, h, n, tone, d_u8, d_f32, out_stride);
+    hipLaunchKernelGGL(rt::film_resolve_metered_kernel, dim3(rt::film_grid((a.npx + 3) >> 2, ctx->cu_count, 1)), dim3(rt::FILM_THREADS), 0,
+                       stream_of(ctx, stream), a, (const double *)d_state);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 // The staging planes grown where the frame is larger than any before, one launch into them and one copy per output to host memory,
 // all queued on `stream`.
 static int render_staged(rt_ctx *ctx, const rt_params *params, int x0, int x1, uint8_t *out_u8, float *out_f32, Buf &u8, Buf &f32,

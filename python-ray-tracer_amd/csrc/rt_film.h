@@ -1,6 +1,7 @@
-// rt_film.h — the film (include/mi355rt.h: rt_film_accumulate, rt_film_accumulate_moments, rt_film_resolve): a float64 sum of float32
-// pass frames in device memory (with the moments entry a float64 sum of their squares beside it), and its resolve to a frame (mean,
-// exposure, highlight compression, display gamma, bytes).
+// rt_film.h — the film (include/mi355rt.h: rt_film_accumulate, rt_film_accumulate_moments, rt_film_resolve, rt_film_resolve_metered): a
+// float64 sum of float32 pass frames in device memory (with the moments entry a float64 sum of their squares beside it), and its
+// resolve to a frame (mean, exposure, with the metered entry times the exposure a meter solved on the device, highlight compression,
+// display gamma, bytes).
 // The arithmetic of one element (film_add, film_add_sq, film_tone, film_clip) is HIP-free, like rt_plan.h and rt_scene.h and for the same
 // reason: the kernels below and tests/algo/film_check.cpp and variance_check.cpp, CPU programs built under AddressSanitizer and UBSan,
 // compile the same text.  Everything here is evaluated without fused multiply-add (the Makefile's -ffp-contract=off; the CPU program's too).
@@ -73,6 +74,11 @@ RT_FILM_HD inline uint8_t film_clip(double c)
     const int i = (int)__builtin_rint(c);
     return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
 }
+
+// rt_film_resolve_metered's exposure: the tone's own (the user's compensation) times the metered one x = state[0], or times 1.0
+// where x is not (finite and > 0): a state that no solve has written yet.
+RT_FILM_HD inline bool film_exposure_usable(double x) { return x > 0.0 && x <= 1.7976931348623157e308; }
+RT_FILM_HD inline double film_metered_exposure(double exposure, double x) { return exposure * (film_exposure_usable(x) ? x : 1.0); }
 
 constexpr int FILM_BATCH = 4;                       // passes one add kernel folds
 constexpr size_t FILM_SCRATCH_MAX = 256u << 20;      // bytes of pass frames beyond which passes go one by one
@@ -219,48 +225,21 @@ __device__ __forceinline__ void film_store_u8x4(uint8_t *p, bool vec, const doub
     else { p[0] = b0; p[1] = b1; p[2] = b2; p[3] = b3; }
 }
 
-// A thread resolves groups of four consecutive elements of a column run (all three channels: the image layout interleaves them)
-// in a grid-stride loop; the first npx mod 4 threads of block 0 the pixels behind the last group.
+// The resolve (rt_film_resolve.inc: the body of both kernels, as text).  film_resolve_metered_kernel (rt_film_resolve_metered) forms
+// its exposure first: the tone's times state[0] (film_metered_exposure), one product formed once.  The state is read through a
+// pointer to the constant address space, as the sky block is (rt_device.h: sky_color): the kernel never writes it and the address is
+// a kernel argument, so the read is one scalar load and the product is formed on the scalar unit.
+typedef __attribute__((address_space(4))) const double film_state_f64;
+
 __global__ __launch_bounds__(FILM_THREADS) void film_resolve_kernel(const FilmResolveArgs a)
 {
-    const double *const s0 = a.sum, *const s1 = a.sum + a.sum_stride, *const s2 = a.sum + 2 * a.sum_stride;
-    const bool v0 = film_aligned(s0, 16), v1 = film_aligned(s1, 16), v2 = film_aligned(s2, 16);
-    // the uint8 planes in stored order: (R,B,G) unless RT_FLAG_U8_RGB
-    float *const f0 = a.f32, *const f1 = a.f32 + a.out_stride, *const f2 = a.f32 + 2 * a.out_stride;
-    const bool w0 = film_aligned(f0, 16), w1 = film_aligned(f1, 16), w2 = film_aligned(f2, 16);
-    uint8_t *const u0 = a.u8, *const u1 = a.u8 + a.out_stride, *const u2 = a.u8 + 2 * a.out_stride;
-    const bool b0 = film_aligned(u0, 4), b1 = film_aligned(u1, 4), b2 = film_aligned(u2, 4);
-    const long long ngroups = a.npx >> 2, step = (long long)gridDim.x * FILM_THREADS;
-    for (long long g = (long long)blockIdx.x * FILM_THREADS + threadIdx.x; g < ngroups; g += step) {
-        const long long e = g << 2;
-        double R[4], G[4], B[4];
-        film_load4(s0 + e, v0, R);
-        film_load4(s1 + e, v1, G);
-        film_load4(s2 + e, v2, B);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { R[i] = film_tone(R[i], a.tone); G[i] = film_tone(G[i], a.tone); B[i] = film_tone(B[i], a.tone); }
-        if (a.f32) {
-            film_store_f32x4(f0 + e, w0, R);
-            film_store_f32x4(f1 + e, w1, G);
-            film_store_f32x4(f2 + e, w2, B);
-        }
-        if (a.u8) {
-            if (a.hwc) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) film_store_u8_pixel(a, e + i, R[i], G[i], B[i]);
-            } else {
-                film_store_u8x4(u0 + e, b0, R);
-                film_store_u8x4(u1 + e, b1, a.rgb ? G : B);
-                film_store_u8x4(u2 + e, b2, a.rgb ? B : G);
-            }
-        }
-    }
-    if (blockIdx.x == 0 && (long long)threadIdx.x < (a.npx & 3)) {
-        const long long e = (ngroups << 2) + threadIdx.x;
-        const double R = film_tone(s0[e], a.tone), G = film_tone(s1[e], a.tone), B = film_tone(s2[e], a.tone);
-        if (a.f32) { f0[e] = (float)R; f1[e] = (float)G; f2[e] = (float)B; }
-        if (a.u8) film_store_u8_pixel(a, e, R, G, B);
-    }
+#include "rt_film_resolve.inc"
+}
+
+__global__ __launch_bounds__(FILM_THREADS) void film_resolve_metered_kernel(FilmResolveArgs a, const double *state)
+{
+    a.tone.exposure = film_metered_exposure(a.tone.exposure, *(film_state_f64 *)(size_t)state);
+#include "rt_film_resolve.inc"
 }
 
 // blocks along x of a film kernel over `groups` groups of four elements: at most 8 per CU in all (`planes` rows of them)

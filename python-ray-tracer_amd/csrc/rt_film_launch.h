@@ -1,4 +1,4 @@
-// rt_film_launch.h — what the film entries (rt_film_accumulate to rt_film_denoise_variance_temporal) decide before they touch the device:
+// rt_film_launch.h — what the film entries (rt_film_accumulate to rt_film_resolve_metered) decide before they touch the device:
 //   * the entry checks (check_film_*): each entry's rules in its own order, each shared rule written once (film_*); a film refusal
 //     carries its entry's name, which rt_last_error puts before the text;
 //   * the kernels' arguments: the film's batch plan, the add, resolve and temporal kernels', the filters' (film_batch, *_args);
@@ -15,6 +15,7 @@
 #include "rt_denoise_var.h"
 #include "rt_temporal.h"
 #include "rt_bloom.h"
+#include "rt_meter.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -85,13 +86,14 @@ inline Refusal check_film_accumulate(const char *e, bool have_scene, const View 
     return {};
 }
 
+// rt_film_resolve's rules under entry `e`; metered: rt_film_resolve_metered's, which asks for a state behind the tone.
 // (the texts about the outputs name no entry, as rt_render_device's do not)
-inline Refusal check_film_resolve(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone, const void *d_u8,
-                                  const void *d_f32, int64_t out_stride)
+inline Refusal film_resolve_rules(const char *e, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone,
+                                  bool metered, const void *d_state, const void *d_u8, const void *d_f32, int64_t out_stride)
 {
-    const char *const e = "rt_film_resolve";
     RT_FILM_RULE(d_sum, "d_sum is NULL");
     RT_FILM_RULE(tone, "tone is NULL");
+    RT_FILM_RULE(!metered || d_state, "d_state is NULL");
     RT_FILM_RULES(film_area(e, ws, h));
     RT_FILM_RULE(n >= 1, "n < 1");
     RT_FILM_RULE(std::isfinite(tone->exposure) && tone->exposure > 0.0, "exposure must be finite and > 0");
@@ -106,6 +108,18 @@ inline Refusal check_film_resolve(const void *d_sum, int64_t sum_stride, int ws,
         if (out_stride < (int64_t)ws) return {RT_ERR_BAD_ARG, "row pitch smaller than the frame width"};
     } else if (out_stride < npx) return {RT_ERR_BAD_ARG, "out_stride smaller than the frame"};
     return {};
+}
+
+inline Refusal check_film_resolve(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone, const void *d_u8,
+                                  const void *d_f32, int64_t out_stride)
+{
+    return film_resolve_rules("rt_film_resolve", d_sum, sum_stride, ws, h, n, tone, false, nullptr, d_u8, d_f32, out_stride);
+}
+
+inline Refusal check_film_resolve_metered(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_film_tone *tone,
+                                          const void *d_state, const void *d_u8, const void *d_f32, int64_t out_stride)
+{
+    return film_resolve_rules("rt_film_resolve_metered", d_sum, sum_stride, ws, h, n, tone, true, d_state, d_u8, d_f32, out_stride);
 }
 
 // What the three filters ask of their frame and buffers, behind their settings: `strides` are the inputs' and d_out's, `ins` the
@@ -402,8 +416,45 @@ inline Refusal check_film_bloom(const void *d_sum, int64_t sum_stride, int ws, i
     return film_own(e, {d_out, d_work}, {d_sum}, "d_out and d_work must be buffers of their own");
 }
 
+// rt_film_meter and rt_film_meter_solve: their rules in the header's order.
+inline Refusal check_film_meter(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const void *d_hist)
+{
+    const char *const e = "rt_film_meter";
+    RT_FILM_RULE(d_sum, "d_sum is NULL");
+    RT_FILM_RULE(d_hist, "d_hist is NULL");
+    RT_FILM_RULES(film_area(e, ws, h));
+    RT_FILM_RULE(n >= 1, "n < 1");
+    RT_FILM_RULE(sum_stride >= (long long)ws * h, "sum_stride smaller than the frame");
+    RT_FILM_RULE(((unsigned long long)(uintptr_t)d_hist & 7) == 0, "d_hist is not 8-byte aligned");
+    return film_own(e, {d_hist}, {d_sum}, "d_hist and d_sum must be buffers of their own");
+}
+
+inline Refusal check_film_meter_solve(const void *d_hist, const rt_meter *mt, const void *d_state)
+{
+    const char *const e = "rt_film_meter_solve";
+    RT_FILM_RULE(d_hist, "d_hist is NULL");
+    RT_FILM_RULE(mt, "mt is NULL");
+    RT_FILM_RULE(d_state, "d_state is NULL");
+    RT_FILM_RULE(std::isfinite(mt->key) && mt->key > 0.0, "key must be finite and > 0");
+    RT_FILM_RULE(mt->percentile >= 0.0 && mt->percentile <= 1.0, "percentile outside 0..1");
+    RT_FILM_RULE(std::isfinite(mt->min_exposure) && mt->min_exposure > 0.0, "min_exposure must be finite and > 0");
+    RT_FILM_RULE(std::isfinite(mt->max_exposure) && mt->max_exposure > 0.0, "max_exposure must be finite and > 0");
+    RT_FILM_RULE(mt->min_exposure <= mt->max_exposure, "min_exposure above max_exposure");
+    RT_FILM_RULE(mt->rate > 0.0 && mt->rate <= 1.0, "rate outside (0, 1]");
+    RT_FILM_RULE(mt->flags == 0, "flags must be 0");
+    RT_FILM_RULE(mt->reserved == 0, "reserved must be 0");
+    return film_own(e, {d_state}, {d_hist}, "d_state and d_hist must be buffers of their own");
+}
+
 #undef RT_FILM_RULE
 #undef RT_FILM_RULES
+
+inline MeterHistArgs meter_hist_args(const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, void *d_hist)
+{
+    return {(const double *)d_sum, (unsigned long long *)d_hist, sum_stride, (long long)ws * h, (double)n};
+}
+
+static_assert(sizeof(rt_meter) == 48, "rt_meter is 48 bytes");
 
 // One launch of rt_film_bloom's plan (rt_bloom.h: bloom_plan): set s of the work planes is planes 3s .. 3s+2 of d_work.
 inline BloomArgs bloom_args(const BloomLaunch &l, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, const rt_bloom *bl, void *d_out,

@@ -52,12 +52,22 @@ in numpy is in bloom.py); bloom(denoised=..., temporal=...) takes the source tha
         film.accumulate(params, passes=64)
         film.bloom()                                  # threshold 255, strength 1/4, six scales
         image, _ = film.resolve(white=400.0, gamma=2, bloom=True)
+
+Film.meter and resolve(auto_exposure=True) let the film look at its own picture (rt_film_meter, rt_film_meter_solve,
+rt_film_resolve_metered; their arithmetic in numpy is in meter.py): a luminance histogram of the source that resolve would show, an
+exposure solved from it on the device, and a resolve that multiplies it in, all on one stream without a copy to the host.  The
+exposure survives next_frame() and clear(), so rate < 1 adapts along an orbit:
+
+        film.accumulate(params, passes=16)
+        film.meter(key=46.0, rate=0.25)               # the median luminance towards 18 % of 255, a quarter of the way per frame
+        image, _ = film.resolve(white=400.0, gamma=2, auto_exposure=True)
 """
 import numpy as np
 
 from . import _lib as L
 from .bloom import LEVELS as BLOOM_LEVELS, STRENGTH as BLOOM_STRENGTH, THRESHOLD as BLOOM_THRESHOLD, check_bloom
 from .denoise import check_denoise
+from .meter import KEY as METER_KEY, MAX_EXPOSURE, MIN_EXPOSURE, PERCENTILE as METER_PERCENTILE, RATE as METER_RATE, check_meter
 from .temporal import DEPTH_TOL, MAX_HISTORY, NORMAL_COS, check_temporal
 from .variance import KAPPA, SPATIAL_BELOW, VAR_PLANES, check_denoise_variance, check_spatial_below
 
@@ -173,12 +183,15 @@ class Film:
         self.d_bloom = self.d_bloom_work = None                   # three and six planes: allocated by bloom()
         self.bloom_passes = 0                                     # the pass count the mean plus glow in d_bloom belongs to (0: none)
         self.bloom_source = None                                  # (denoised, temporal) of the source bloom() took
+        self.d_meter_hist = self.d_meter_state = None             # RT_METER_BINS counts and the exposure state: allocated by meter()
+        self.meter_passes = 0                                     # the pass count the histogram in d_meter_hist belongs to (0: none)
+        self.meter_source = None                                  # (denoised, temporal, bloom) of the source meter() took
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         d, self.d_sum = getattr(self, "d_sum", None), None
         names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_temporal_sq", "d_hist", "d_hist_len", "d_hist_sq", "d_hist_guides", "d_guides",
-                 "d_denoised", "d_work", "d_bloom", "d_bloom_work")
+                 "d_denoised", "d_work", "d_bloom", "d_bloom_work", "d_meter_hist", "d_meter_state")
         extra = [getattr(self, n, None) for n in names]
         for n in names:
             setattr(self, n, None)
@@ -227,6 +240,7 @@ class Film:
         self.denoised_variance = False
         self.temporal_passes = 0
         self.bloom_passes = 0
+        self.meter_passes = 0                                     # (the exposure state stays: reset_meter() zeroes it)
 
     # -- the denoiser -----------------------------------------------------------------------
     def guides(self, stream=None):
@@ -392,6 +406,71 @@ class Film:
             raise ValueError("the film has no bloom of its current passes and this source: call bloom() with the same denoised and temporal first")
         return self.d_bloom, 1
 
+    # -- metering ---------------------------------------------------------------------------
+    def _meter_buffers(self):
+        """The counts and the state, allocated on first use; the state starts as zeros: no history."""
+        r = self.renderer
+        if not self.d_meter_hist:
+            self.d_meter_hist = r.malloc(8 * L.RT_METER_BINS)
+        if not self.d_meter_state:
+            self.d_meter_state = r.malloc(8 * L.RT_METER_STATE_DOUBLES)
+            r.h2d(self.d_meter_state, np.zeros(L.RT_METER_STATE_DOUBLES, np.float64))
+
+    def meter(self, key=METER_KEY, percentile=METER_PERCENTILE, min_exposure=MIN_EXPOSURE, max_exposure=MAX_EXPOSURE, rate=METER_RATE,
+              stream=None, denoised=False, temporal=False, bloom=False):
+        """Meter the source that resolve(denoised=..., temporal=..., bloom=...) would show (Renderer.film_meter: a histogram of its
+        luminance, eight bins per octave over 2^-16 .. 2^24) and solve the exposure that maps the `percentile` of it to `key` colour
+        units (Renderer.film_meter_solve), clamped to min_exposure .. max_exposure and moved from the exposure before by `rate`
+        (1: jump; a film that has not metered yet jumps as well).  Counts and exposure stay in the film's own device buffers;
+        resolve(auto_exposure=True) uses them, exposure() and histogram() read them.  The exposure survives next_frame() and clear().
+        The defaults are starting points, not measurements: 46 is 18 % of 255.  Asynchronous."""
+        self._live()
+        if self.passes < 1:
+            raise ValueError("the film holds no pass yet")
+        key, percentile, min_exposure, max_exposure, rate = check_meter(key, percentile, min_exposure, max_exposure, rate)
+        src, n_src = self._bloomed(denoised, temporal) if bloom else self._source(denoised, temporal)
+        self._meter_buffers()
+        r = self.renderer
+        r.film_meter(src, self.ws, self.h, n_src, self.d_meter_hist, reset=True, stream=stream)
+        r.film_meter_solve(self.d_meter_hist, self.d_meter_state, key=key, percentile=percentile, min_exposure=min_exposure,
+                           max_exposure=max_exposure, rate=rate, stream=stream)
+        self.meter_passes = self.passes
+        self.meter_source = (bool(denoised), bool(temporal), bool(bloom))
+
+    def _metered(self, denoised, temporal, bloom):
+        """d_meter_state for a resolve with auto_exposure=True, or ValueError where meter() has not run for the current passes and source."""
+        if not self.meter_passes or self.meter_passes != self.passes or self.meter_source != (bool(denoised), bool(temporal), bool(bloom)):
+            raise ValueError("the film has no metering of its current passes and this source: call meter() with the same denoised, temporal "
+                             "and bloom first")
+        return self.d_meter_state
+
+    def exposure(self, stream=None):
+        """The meter's state, float64 (4,): the exposure resolve(auto_exposure=True) multiplies in, the metered luminance, the
+        number of pixels metered and the bin the percentile fell in; zeros before the first meter().  Waits for the stream."""
+        self._live()
+        out = np.zeros(L.RT_METER_STATE_DOUBLES, np.float64)
+        if self.d_meter_state:
+            self.renderer.sync(stream)
+            self.renderer.d2h(out, self.d_meter_state)
+        return out
+
+    def histogram(self, stream=None):
+        """The counts of the last meter(): uint64 (RT_METER_BINS,); meter.bin_edges() has the bins' edges.  Waits for the stream."""
+        self._live()
+        if not self.d_meter_hist or not self.meter_source:
+            raise ValueError("the film has not metered yet: call meter() first")
+        out = np.zeros(L.RT_METER_BINS, np.uint64)
+        self.renderer.sync(stream)
+        self.renderer.d2h(out, self.d_meter_hist)
+        return out
+
+    def reset_meter(self):
+        """Forget the exposure: the next meter() jumps whatever its rate."""
+        self._live()
+        self.meter_passes = 0
+        if self.d_meter_state:
+            self.renderer.h2d(self.d_meter_state, np.zeros(L.RT_METER_STATE_DOUBLES, np.float64))
+
     # -- temporal accumulation ---------------------------------------------------------------
     def _full_frame(self):
         if self.x0 != 0 or self.x1 != self.renderer.w or self.renderer.h != self.h:
@@ -475,10 +554,11 @@ class Film:
 
     # -- frames -----------------------------------------------------------------------------
     def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None,
-                       denoised=False, temporal=False, bloom=False):
+                       denoised=False, temporal=False, bloom=False, auto_exposure=False):
         """The mean of the passes so far, tone-mapped, into caller-owned device memory (raw addresses), laid out as
         Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead; temporal: the mean that temporal()
-        wrote (with denoised: its filtered version, denoise(temporal=True)); bloom: that source with the glow that bloom() added.
+        wrote (with denoised: its filtered version, denoise(temporal=True)); bloom: that source with the glow that bloom() added;
+        auto_exposure: `exposure` times the exposure that meter() solved for that source (Renderer.film_resolve_metered).
         Asynchronous."""
         self._live()
         if self.passes < 1:
@@ -489,13 +569,20 @@ class Film:
         if int(flags) & L.RT_FLAG_U8_HWC and d_f32:
             raise ValueError("RT_FLAG_U8_HWC is a uint8 layout: resolve the float32 frame in a separate call")
         src, n = self._bloomed(denoised, temporal) if bloom else self._source(denoised, temporal)
+        if auto_exposure:
+            self.renderer.film_resolve_metered(src, self.ws, self.h, n, self._metered(denoised, temporal, bloom), d_u8, d_f32, exposure=exposure,
+                                               white=white, gamma=gamma, flags=flags, out_stride=out_stride, stream=stream)
+            return
         self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
                                    flags=flags, out_stride=out_stride, stream=stream)
 
-    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False, bloom=False):
+    def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False, bloom=False,
+                auto_exposure=False):
         """(uint8 or None, float32 or None) host arrays shaped like Renderer.render's: (3, ws, h), or (h, ws, 3) for the uint8
         frame with RT_FLAG_U8_HWC; denoised: of the mean that denoise() filtered; temporal: of the mean that temporal() wrote; bloom: with
-        the glow that bloom() added to that source.  Waits for the context's stream."""
+        the glow that bloom() added to that source; auto_exposure: with `exposure` times the exposure that meter() solved for that source
+        (ValueError unless meter() ran for the current passes and the same denoised, temporal and bloom).  Waits for the context's
+        stream."""
         self._live()
         if self.passes < 1:
             raise ValueError("the film holds no pass yet")
@@ -506,6 +593,8 @@ class Film:
             self._bloomed(denoised, temporal)
         else:
             self._source(denoised, temporal)
+        if auto_exposure:
+            self._metered(denoised, temporal, bloom)
         r, n = self.renderer, self.ws * self.h
         hwc = bool(int(flags) & L.RT_FLAG_U8_HWC)
         out8 = np.empty((self.h, self.ws, 3) if hwc else (3, self.ws, self.h), np.uint8) if u8 else None
@@ -516,6 +605,8 @@ class Film:
             kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised, temporal=temporal)
             if bloom:
                 kw["bloom"] = True
+            if auto_exposure:
+                kw["auto_exposure"] = True
             if hwc:                                             # (the image layout is uint8 only: two calls)
                 self.resolve_device(d8, None, flags=flags, **kw)
                 if f32:

@@ -537,8 +537,34 @@ class Renderer:
         self._check(self._later_entry("rt_film_bloom")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(bl), _vp(d_out),
                                                        out_stride, _vp(d_work), work_stride, _vp(stream)))
 
+    def film_meter(self, d_sum, ws, h, n, d_hist, *, reset=True, sum_stride=None, stream=None):
+        """The luminance histogram of the mean of the sum of n passes at d_sum into the RT_METER_BINS uint64 counts at d_hist
+        (rt_film_meter); reset=False adds to the counts that are there.  Asynchronous.  In numpy: meter.histogram_reference."""
+        sum_stride, = _strides(int(ws) * int(h), sum_stride)
+        self._check(self._later_entry("rt_film_meter")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), 1 if reset else 0, _vp(d_hist),
+                                                       _vp(stream)))
+
+    def film_meter_solve(self, d_hist, d_state, *, key=46.0, percentile=0.5, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, rate=1.0,
+                         flags=0, reserved=0, stream=None):
+        """The counts at d_hist to an exposure in the RT_METER_STATE_DOUBLES float64 at d_state, which holds the exposure before
+        (rt_film_meter_solve): state = (exposure, metered luminance, pixels metered, bin).  Asynchronous.  In numpy:
+        meter.solve_reference."""
+        mt = L.rt_meter(float(key), float(percentile), float(min_exposure), float(max_exposure), float(rate), int(flags), int(reserved))
+        self._check(self._later_entry("rt_film_meter_solve")(self._ctx, _vp(d_hist), C.byref(mt), _vp(d_state), _vp(stream)))
+
+    def film_resolve_metered(self, d_sum, ws, h, n, d_state, d_u8=None, d_f32=None, *, exposure=1.0, white=0.0, gamma=1, flags=0,
+                             sum_stride=None, out_stride=None, stream=None):
+        """film_resolve with the exposure times the metered one at d_state[0] (rt_film_resolve_metered): `exposure` is the caller's
+        compensation.  Asynchronous."""
+        sum_stride, = _strides(int(ws) * int(h), sum_stride)
+        if out_stride is None:
+            out_stride = int(ws) if int(flags) & L.RT_FLAG_U8_HWC else int(ws) * int(h)
+        tone = L.rt_film_tone(float(exposure), float(white), int(gamma), int(flags))
+        self._check(self._later_entry("rt_film_resolve_metered")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(tone),
+                                                                 _vp(d_state), _vp(d_u8), _vp(d_f32), int(out_stride), _vp(stream)))
+
     def sync(self, stream=None):
-        """Wait for the context's stream, or for `stream` (a handle from stream_create / a hipStream_t address)."""
+        """Wait for the context's stream, or for `stream`(a handle from stream_create / a hipStream_t address)."""
         if stream:
             self._check(self._lib.rt_stream_sync(self._ctx, C.c_void_p(stream)))
         else:

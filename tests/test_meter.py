@@ -1,0 +1,348 @@
+"""Metering on the CPU (rt_film_meter, rt_film_meter_solve, rt_film_resolve_metered): the header, the binding and the exported symbols;
+properties of the numpy restatements in meter.py on constructed inputs; the text the kernels compile
+(python-ray-tracer_amd/csrc/rt_meter.h: the per-pixel functions, the histogram kernel's phases, the solve; rt_film_launch.h: the three
+checks) run by tests/algo/meter_check.cpp under AddressSanitizer and UBSan and compared bit for bit with the restatements; Film's call
+sequences and ValueErrors."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+from test_film import same_bits
+from test_bloom import _NoDeviceBloom
+import meter_cases as mc
+
+from python_ray_tracer_amd import Film, meter as M
+from python_ray_tracer_amd import _lib as L
+
+ALGO = os.path.join(REPO, "tests", "algo")
+
+HIST_CONTRACT = ("m_c = s[c][p] / (double)n",
+                 "Y = (0.2126 * m_0 + 0.7152 * m_1) + 0.0722 * m_2",
+                 "!(Y > 0)  (zero, negative, NaN):  bin 0",
+                 "else  u = the 64 bits of Y;   k = (int64)(u >> 49) - 8056        (8056 = (1023 + RT_METER_LO) * 8)",
+                 "k < 0: bin 1        k >= 320: bin 322  (+Inf included)        else: bin 2 + k",
+                 "hist[bin] = hist[bin] + 1")
+SOLVE_CONTRACT = ("N = hist[1] + ... + hist[322]                    (bin 0 is not metered)",
+                  "prev = state[0];   usable = prev is finite and > 0",
+                  "N == 0:  e = usable ? prev : clamp(1.0);   state = (e, +0.0, 0.0, 0.0);   done",
+                  "r = (uint64)(percentile * (double)N);   r > N-1: r = N-1",
+                  "b = the smallest bin in 1..322 with C_b > r,  C_b = hist[1] + ... + hist[b];   below = C_{b-1}",
+                  "b == 1: Ym = 2^-16     b == 322: Ym = 2^24",
+                  "else  lo = edge(b); hi = edge(b+1);  Ym = lo + (hi - lo) * ((double)(r - below) / (double)hist[b])",
+                  "t = clamp(key / Ym)                      clamp(v): v < min_exposure ? min_exposure : (v > max_exposure ? max_exposure : v)",
+                  "e = (usable and rate < 1) ? clamp(prev + (t - prev) * rate) : t",
+                  "state = (e, Ym, (double)N, (double)b)")
+ZERO = np.zeros(4)
+
+
+def test_header_binding_exported_symbols_and_contract(tmp_path):
+    hdr = open(os.path.join(REPO, "include", "mi355rt.h")).read()
+    assert "int rt_film_meter(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n, int reset, void *d_hist," in hdr
+    assert "int rt_film_meter_solve(rt_ctx *ctx, const void *d_hist, const rt_meter *mt, void *d_state, void *stream);" in hdr
+    assert "int rt_film_resolve_metered(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, int h, int64_t n," in hdr
+    assert "#define RT_ABI_VERSION 7" in hdr and L.RT_ABI_VERSION == 7
+    assert (L.RT_METER_LO, L.RT_METER_OCTAVES, L.RT_METER_SUB, L.RT_METER_BINS, L.RT_METER_STATE_DOUBLES) == (-16, 40, 8, 323, 4)
+    mp, sp, rp = (L.PROTOTYPES[n] for n in ("rt_film_meter", "rt_film_meter_solve", "rt_film_resolve_metered"))
+    assert mp[0] is C.c_int and len(mp[1]) == 9 and mp[1][2] is C.c_int64 and mp[1][5] is C.c_int64 and all(mp[1][i] is C.c_int for i in (3, 4, 6))
+    assert sp[0] is C.c_int and len(sp[1]) == 5 and sp[1][2] == C.POINTER(L.rt_meter)
+    assert rp[0] is C.c_int and len(rp[1]) == 12 and rp[1][6] == C.POINTER(L.rt_film_tone) and all(rp[1][i] is C.c_int64 for i in (2, 5, 10))
+    assert {"rt_film_meter", "rt_film_meter_solve", "rt_film_resolve_metered"} <= set(L.LATER_ENTRIES)
+    assert C.sizeof(L.rt_meter) == 48
+    assert [f[0] for f in L.rt_meter._fields_] == ["key", "percentile", "min_exposure", "max_exposure", "rate", "flags", "reserved"]
+    src = tmp_path / "size.c"
+    src.write_text('#include <stddef.h>\n#include "mi355rt.h"\n_Static_assert(sizeof(rt_meter) == 48, "rt_meter is 48 bytes");\n'
+                   '_Static_assert(offsetof(rt_meter, rate) == 32 && offsetof(rt_meter, flags) == 40 && offsetof(rt_meter, reserved) == 44, "layout");\n'
+                   '_Static_assert(RT_METER_LO == -16 && RT_METER_OCTAVES == 40 && RT_METER_SUB == 8 && RT_METER_BINS == 323, "constants");\n'
+                   '_Static_assert(RT_METER_BINS == RT_METER_OCTAVES * RT_METER_SUB + 3 && RT_METER_STATE_DOUBLES == 4, "constants");\n'
+                   'int main(void) { return 0; }\n')
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)])
+    lib = L.load()                                               # the cross-compiled library
+    assert lib.rt_abi_version() == 7
+    for name in ("rt_film_meter", "rt_film_meter_solve", "rt_film_resolve_metered"):
+        assert hasattr(lib, name), name
+    at = hdr.index("rt_film_meter: d_sum is three float64 planes")
+    for line in HIST_CONTRACT:                                    # header and numpy restatement state the same arithmetic, line for line
+        assert line in hdr[at:], line
+        assert line in M.histogram_reference.__doc__, line
+    for line in HIST_CONTRACT[2:5]:
+        assert line in M.bin_reference.__doc__, line
+    at = hdr.index("rt_film_meter_solve: a histogram to an exposure")
+    for line in SOLVE_CONTRACT:
+        assert line in hdr[at:], line
+        assert line in M.solve_reference.__doc__, line
+    assert "(uint64)(b - 2 + 8056) << 49" in hdr and "(uint64)(b - 2 + 8056) << 49" in M.bin_edges.__doc__
+    for name in ("README.md", "DESIGN.md"):
+        text = open(os.path.join(REPO, name)).read()
+        assert "rt_film_meter" in text and "rt_film_resolve_metered" in text, name
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Properties of the restatement
+
+def test_the_contracts_examples_and_every_edge():
+    lo, hi = 2.0 ** -16, 2.0 ** 24
+    ys = [lo, np.nextafter(lo, 0.0), 1.0, 1.125, 255.0, hi, np.inf, np.nextafter(hi, 0.0), 5e-324, 0.0, -0.0, -3.0, -np.inf, np.nan]
+    assert M.bin_reference(np.array(ys)).tolist() == [2, 1, 130, 131, 193, 322, 322, 321, 1, 0, 0, 0, 0, 0]
+    e = M.bin_edges()
+    assert e.shape == (321,) and e[0] == lo and e[-1] == hi and e[128] == 1.0 and e[129] == 1.125 and (np.diff(e) > 0).all()
+    assert M.bin_reference(e).tolist() == list(range(2, 323))
+    assert M.bin_reference(np.nextafter(e, 0.0)).tolist() == list(range(1, 322))
+    mant, _ = np.frexp(e)
+    assert ((mant * 16) % 1 == 0).all()                          # (1 + j/8) * 2^E, exact
+    rng = np.random.default_rng(5)
+    Y = np.exp2(rng.uniform(-16.0, 24.0, 100000))
+    Y = Y[(Y >= lo) & (Y < hi)]
+    b = M.bin_reference(Y)
+    assert b.min() >= 2 and b.max() <= 321 and len(np.unique(b)) == 320
+    assert (e[b - 2] <= Y).all() and (Y < e[b - 1]).all()        # every in-range Y lies in [edge(b), edge(b+1))
+
+
+def test_the_generator_fills_every_kind_of_bin():
+    for ws, h in ((5, 300), (37, 29), (64, 64), (97, 71)):
+        for n in mc.PASSES:
+            s = mc.meter_sums(ws, h, n)
+            hist = M.histogram_reference(s, n)
+            nothing, below, inside, above = mc.kinds(hist)
+            npx = ws * h
+            assert hist.dtype == np.uint64 and hist.shape == (323,) and int(hist.sum()) == npx          # sum(hist) == ws*h
+            assert nothing > 0.04 * npx and below > 0.03 * npx and above > 0.03 * npx and inside > 0.5 * npx, (ws, h, n, mc.kinds(hist))
+            assert np.isnan(s).any() and np.isposinf(s).any() and (s < 0).any() and (s == 0).any()
+            assert (hist[2:322] > 0).sum() > 250
+            assert not s.flags.writeable and mc.meter_sums(ws, h, n) is s
+    assert int(M.histogram_reference(mc.meter_sums(1, 1, 1), 1).sum()) == 1
+
+
+@pytest.mark.parametrize("n", mc.PASSES)
+def test_slabs_add_up_and_a_fourth_plane_is_not_read(n):
+    ws, h = 97, 71
+    s = mc.meter_sums(ws, h, n)
+    whole = M.histogram_reference(s, n)
+    for cut in (1, 48, 96):
+        assert np.array_equal(M.histogram_reference(s[:, :cut], n) + M.histogram_reference(s[:, cut:], n), whole)
+    four = np.concatenate([s, np.full((1,) + s.shape[1:], 1e300)])
+    assert np.array_equal(M.histogram_reference(four, n), whole)
+    const = M.histogram_reference(mc.constant_sums(ws, h, n), n)
+    assert const[M.bin_reference(np.array([(0.2126 * 100.0 + 0.7152 * 100.0) + 0.0722 * 100.0]))[0]] == 6887 and (const > 0).sum() == 1
+
+
+def test_a_frame_twice_as_bright_gets_exactly_half_the_exposure():
+    s = np.array(mc.meter_sums(64, 64, 1))
+    s[~np.isfinite(s)] = 0.0
+    h1, h2 = M.histogram_reference(s, 1), M.histogram_reference(2.0 * s, 1)
+    assert np.array_equal(h2[10:322], h1[2:314])                 # a power of two moves every bin by 8
+    inner = np.zeros(323, np.uint64)
+    inner[40:300] = h1[40:300]                                   # (what stays in range when it is doubled)
+    moved = np.zeros(323, np.uint64)
+    moved[48:308] = inner[40:300]
+    for pct in (0.0, 0.1, 0.5, 0.9, 1.0):
+        a = M.solve_reference(inner, ZERO, 46.0, pct, 2.0 ** -40, 2.0 ** 40, 1.0)
+        b = M.solve_reference(moved, ZERO, 46.0, pct, 2.0 ** -40, 2.0 ** 40, 1.0)
+        assert b[0] == a[0] / 2 and b[1] == a[1] * 2 and b[2] == a[2] and b[3] == a[3] + 8
+
+
+def test_the_solve_is_monotone_in_the_percentile_and_interpolates_inside_a_bin():
+    hist = M.histogram_reference(mc.meter_sums(97, 71, 1), 1)
+    pcts = np.linspace(0.0, 1.0, 201)
+    out = np.array([M.solve_reference(hist, ZERO, 46.0, p, 2.0 ** -30, 2.0 ** 30, 1.0) for p in pcts])
+    assert (np.diff(out[:, 1]) >= 0).all() and (np.diff(out[:, 0]) <= 0).all() and (np.diff(out[:, 3]) >= 0).all()
+    assert out[0, 3] == 1 and out[0, 1] == 2.0 ** -16 and out[-1, 3] == 322 and out[-1, 1] == 2.0 ** 24
+    assert (out[:, 2] == float(hist[1:].sum())).all()
+    one = np.zeros(323, np.uint64)
+    one[130] = 8                                                 # eight pixels in [1, 1.125): rank r sits r/8 of the way through the bin
+    for r in range(8):
+        st = M.solve_reference(one, ZERO, 46.0, r / 8.0, 2.0 ** -10, 2.0 ** 10, 1.0)
+        assert st[1] == 1.0 + 0.125 * (r / 8.0) and st[0] == 46.0 / st[1] and st[3] == 130 and st[2] == 8
+    assert M.solve_reference(one, ZERO, 46.0, 1.0, 2.0 ** -10, 2.0 ** 10, 1.0)[1] == 1.0 + 0.125 * (7 / 8.0)       # r > N-1: r = N-1
+
+
+def test_rate_history_an_empty_histogram_and_the_clamps():
+    hist = np.zeros(323, np.uint64)
+    hist[130] = 10
+    hist[0] = 99                                                 # bin 0 is not metered
+    t = 46.0 / 1.0625
+    jump = M.solve_reference(hist, ZERO, 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 1.0)
+    assert jump.tolist() == [t, 1.0625, 10.0, 130.0]
+    for prev in (0.001, 3.0, 1e6):                               # rate 1 ignores the state
+        assert same_bits(M.solve_reference(hist, [prev, 9, 9, 9], 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 1.0), jump)
+    for prev in (0.0, -1.0, np.nan, np.inf, -np.inf):            # a state without a usable exposure jumps whatever the rate
+        assert same_bits(M.solve_reference(hist, [prev, 0, 0, 0], 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 0.25), jump)
+    st = M.solve_reference(hist, [3.0, 0, 0, 0], 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 0.25)
+    assert st[0] == 3.0 + (t - 3.0) * 0.25 and st[1:].tolist() == [1.0625, 10.0, 130.0]
+    e = 3.0
+    for _ in range(200):                                         # adaptation converges on the target
+        e = M.solve_reference(hist, [e, 0, 0, 0], 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 0.25)[0]
+    assert abs(e - t) < 1e-12 * t
+    empty = np.zeros(323, np.uint64)
+    empty[0] = 5
+    assert M.solve_reference(empty, [3.0, 7, 7, 7], 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 0.25).tolist() == [3.0, 0.0, 0.0, 0.0]   # N == 0 holds
+    assert M.solve_reference(empty, ZERO, 46.0, 0.5, 2.0 ** -10, 2.0 ** 10, 1.0).tolist() == [1.0, 0.0, 0.0, 0.0]
+    assert M.solve_reference(empty, ZERO, 46.0, 0.5, 2.0, 4.0, 1.0)[0] == 2.0 and M.solve_reference(empty, ZERO, 46.0, 0.5, 0.25, 0.5, 1.0)[0] == 0.5
+    assert M.solve_reference(empty, [100.0, 0, 0, 0], 46.0, 0.5, 2.0, 4.0, 1.0)[0] == 100.0          # (held as it is)
+    assert M.solve_reference(hist, ZERO, 46.0, 0.5, 2.0 ** -10, 8.0, 1.0)[0] == 8.0                   # the clamps
+    assert M.solve_reference(hist, ZERO, 46.0, 0.5, 64.0, 128.0, 1.0)[0] == 64.0
+    assert M.solve_reference(hist, [1000.0, 0, 0, 0], 46.0, 0.5, 2.0 ** -10, 8.0, 0.001)[0] == 8.0    # the adapted value is clamped too
+    assert M.solve_reference(hist, [1e-9, 0, 0, 0], 46.0, 0.5, 64.0, 128.0, 0.001)[0] == 64.0
+
+
+def test_reference_value_errors():
+    hist = np.zeros(323, np.uint64)
+    ok = dict(key=46.0, percentile=0.5, min_exposure=0.5, max_exposure=2.0, rate=1.0)
+    for bad in (dict(key=0.0), dict(key=np.nan), dict(key=np.inf), dict(percentile=-0.1), dict(percentile=1.1), dict(percentile=np.nan),
+                dict(min_exposure=0.0), dict(min_exposure=np.inf), dict(max_exposure=np.nan), dict(max_exposure=-1.0),
+                dict(min_exposure=3.0), dict(rate=0.0), dict(rate=1.5), dict(rate=np.nan)):
+        with pytest.raises(ValueError):
+            M.solve_reference(hist, ZERO, **{**ok, **bad})
+    with pytest.raises(ValueError):
+        M.solve_reference(hist[:-1], ZERO, **ok)
+    with pytest.raises(ValueError):
+        M.solve_reference(hist, np.zeros(3), **ok)
+    s = np.zeros((3, 4, 4))
+    for bad in ((s, 0), (s[:2], 1), (s.astype(np.float32), 1), (s[:, :0], 1)):
+        with pytest.raises(ValueError):
+            M.histogram_reference(*bad)
+    assert M.check_meter(46, 0, 1, 1, 1) == (46.0, 0.0, 1.0, 1.0, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The kernels' text under the sanitizers against the restatement
+
+def solve_cases():
+    """[(hist, state, settings)]: the histogram of a generated frame, a constant one, an empty one and one with everything out of
+    range, each with a zero state and a carried one over the settings grid."""
+    hists = [M.histogram_reference(mc.meter_sums(97, 71, 1), 1), M.histogram_reference(mc.constant_sums(97, 71, 7), 7)]
+    empty = np.zeros(323, np.uint64)
+    empty[0] = 11
+    ends = np.zeros(323, np.uint64)
+    ends[1], ends[322] = 5, 5
+    hists += [empty, ends]
+    return [(h, st, cfg) for h in hists for st in (ZERO, np.array(mc.CARRIED)) for cfg in mc.SETTINGS]
+
+
+def test_kernel_text_under_sanitizers_matches_numpy(tmp_path):
+    exe, table, got = str(tmp_path / "meter_check"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, os.path.join(ALGO, "meter_check.cpp")])
+    cases = []
+    for k, ((ws, h), n) in enumerate((f, n) for f in mc.FRAMES for n in mc.PASSES):
+        cases.append(dict(s=mc.meter_sums(ws, h, n), n=n, pad=(1, 3, 0, 2)[k % 4], nblocks=(1, 2, 5)[k % 3]))
+    cases.append(dict(s=mc.constant_sums(97, 71, 7), n=7, pad=1, nblocks=4))
+    solves = solve_cases()
+    with open(table, "wb") as fh:
+        fh.write(np.array([len(cases)], "<i8").tobytes())
+        for c in cases:
+            _, ws, h = c["s"].shape
+            fh.write(np.array([ws, h, c["n"], c["pad"], c["nblocks"]], "<i8").tobytes())
+            padded = np.full((3, ws * h + c["pad"]), 1e300)
+            padded[:, :ws * h] = c["s"].reshape(3, -1)
+            fh.write(padded.astype("<f8").tobytes())
+        fh.write(np.array([len(solves)], "<i8").tobytes())
+        for hist, state, cfg in solves:
+            fh.write(hist.astype("<u8").tobytes() + np.asarray(state, "<f8").tobytes() + np.array(cfg, "<f8").tobytes())
+    res = subprocess.run([exe, table, got], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert res.returncode == 0 and "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stdout + res.stderr
+    assert res.stdout.strip() == f"cases={len(cases)} solves={len(solves)} ok", res.stdout
+    raw = open(got, "rb").read()
+    at = 0
+    for i, c in enumerate(cases):
+        out = np.frombuffer(raw, "<u8", 323, at)
+        at += 8 * 323
+        want = M.histogram_reference(c["s"], c["n"])
+        assert np.array_equal(out, want), (i, c["s"].shape, np.flatnonzero(out != want)[:6])
+    interpolated = 0
+    for i, (hist, state, cfg) in enumerate(solves):
+        out = np.frombuffer(raw, "<f8", 4, at)
+        at += 32
+        want = M.solve_reference(hist, state, *cfg)
+        assert same_bits(out, want), (i, cfg, out.tolist(), want.tolist())
+        interpolated += int(2 <= want[3] <= 321)
+    assert at == len(raw) and len(cases) == 13 and len(solves) == 4 * 2 * 32 and interpolated >= 32
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Film's call sequences, before the library sees anything
+
+class _NoDeviceMeter(_NoDeviceBloom):
+    def h2d(self, d, host):
+        self.calls.append(("h2d", d, host.tobytes()))
+
+    def film_meter(self, *a, **kw):
+        self.calls.append(("meter",) + a + (kw,))
+
+    def film_meter_solve(self, *a, **kw):
+        self.calls.append(("solve",) + a + (kw,))
+
+    def film_resolve_metered(self, *a, **kw):
+        self.calls.append(("resolve_metered",) + a)
+
+
+def test_film_meter_call_sequences_and_value_errors():
+    r = _NoDeviceMeter()
+    p = L.rt_params()
+    defaults = dict(key=46.0, percentile=0.5, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, rate=1.0, stream=None)
+    with Film(r) as film:
+        with pytest.raises(ValueError, match="no pass"):
+            film.meter()
+        assert film.exposure().tolist() == [0.0] * 4
+        film.accumulate(p, 2)
+        n = len(r.calls)
+        film.resolve()                                            # auto_exposure=False: exactly the calls made before
+        assert [c[0] for c in r.calls[n:]] == ["malloc", "resolve", "free"] and film.d_meter_hist is None and film.d_meter_state is None
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.resolve(auto_exposure=True)
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.histogram()
+        for bad in (dict(key=0.0), dict(percentile=2.0), dict(min_exposure=-1.0), dict(max_exposure=float("nan")),
+                    dict(min_exposure=8.0, max_exposure=4.0), dict(rate=0.0), dict(rate=1.5)):
+            with pytest.raises(ValueError):
+                film.meter(**bad)
+        with pytest.raises(ValueError, match="denoise\\(\\)"):      # the source is what resolve would show: it must exist
+            film.meter(denoised=True)
+        with pytest.raises(ValueError, match="bloom\\(\\)"):
+            film.meter(bloom=True)
+        assert film.d_meter_hist is None and not [c for c in r.calls if c[0] in ("meter", "solve", "h2d")]
+        n = len(r.calls)
+        film.meter()
+        assert r.calls[n:n + 3] == [("malloc", 8 * 323), ("malloc", 32), ("h2d", film.d_meter_state, bytes(32))]
+        assert r.calls[n + 3] == ("meter", film.d_sum, 8, 4, 2, film.d_meter_hist, dict(reset=True, stream=None))
+        assert r.calls[n + 4] == ("solve", film.d_meter_hist, film.d_meter_state, defaults) and len(r.calls) == n + 5
+        film.resolve(auto_exposure=True, white=400.0, exposure=2.0)
+        assert r.calls[-2][:6] == ("resolve_metered", film.d_sum, 8, 4, 2, film.d_meter_state) and r.calls[-1][0] == "free"
+        n = len(r.calls)
+        film.meter(key=10, percentile=0.9, min_exposure=0.5, max_exposure=2, rate=0.25)       # the buffers are there: two launches
+        assert [c[0] for c in r.calls[n:]] == ["meter", "solve"]
+        assert r.calls[-1][3] == dict(key=10.0, percentile=0.9, min_exposure=0.5, max_exposure=2.0, rate=0.25, stream=None)
+        film.denoise()
+        with pytest.raises(ValueError, match="meter\\(\\)"):        # metered on the plain mean, not on the filtered one
+            film.resolve(auto_exposure=True, denoised=True)
+        film.meter(denoised=True)
+        assert r.calls[-2][1:5] == (film.d_denoised, 8, 4, 1)
+        film.resolve(auto_exposure=True, denoised=True)
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.resolve(auto_exposure=True)
+        film.bloom()
+        film.meter(bloom=True)
+        assert r.calls[-2][1:5] == (film.d_bloom, 8, 4, 1)
+        film.resolve(auto_exposure=True, bloom=True)
+        assert [c for c in r.calls if c[0] == "resolve_metered"][-1][1:6] == (film.d_bloom, 8, 4, 1, film.d_meter_state)
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.resolve(auto_exposure=True, denoised=True)
+        film.accumulate(p, 1)                                     # more passes: the metering was that of the earlier mean
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.resolve(auto_exposure=True)
+        state = film.d_meter_state
+        film.clear()                                              # the state survives clear(): the same buffer, not written
+        film.accumulate(p, 3)
+        n = len(r.calls)
+        film.meter(rate=0.25)
+        assert [c[0] for c in r.calls[n:]] == ["meter", "solve"] and film.d_meter_state == state
+        n = len(r.calls)
+        film.reset_meter()
+        assert r.calls[n:] == [("h2d", state, bytes(32))]
+        with pytest.raises(ValueError, match="meter\\(\\)"):
+            film.resolve(auto_exposure=True)
+        held = {film.d_meter_hist, film.d_meter_state}
+    assert held <= {c[1] for c in r.calls if c[0] == "free"}
