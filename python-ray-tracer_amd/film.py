@@ -61,6 +61,11 @@ exposure survives next_frame() and clear(), so rate < 1 adapts along an orbit:
         film.accumulate(params, passes=16)
         film.meter(key=46.0, rate=0.25)               # the median luminance towards 18 % of 255, a quarter of the way per frame
         image, _ = film.resolve(white=400.0, gamma=2, auto_exposure=True)
+
+A derived picture belongs to what it was made from: the temporal mean to the sum, a filtered mean to the mean it filtered, the glow
+and the metering to the source they took.  The film records every write with the writes it read, and a request is refused, before
+any device call, unless that chain is intact: redoing an upstream step (more passes, temporal(), denoise()) means redoing what
+follows it.  Film.current(product) says whether "temporal", "denoised", "bloom" or "meter" still stands.
 """
 import numpy as np
 
@@ -146,6 +151,27 @@ def check_tone(n, exposure, white, gamma, flags=0):
     return n, exposure, white, int(gamma)
 
 
+# Every device buffer a film may own: name -> (bytes per pixel, fixed bytes), in the order close() frees them (the sum last).  The
+# sum, and the sum of squares of a film with moments, come with the film; every other buffer with its first use (Film._buffer)
+BUFFERS = {"d_denoised_var": (8 * VAR_PLANES, 0), "d_work_var": (8 * VAR_PLANES, 0), "d_sq": (24, 0), "d_temporal": (24, 0), "d_temporal_len": (4, 0),
+           "d_temporal_sq": (24, 0), "d_hist": (24, 0), "d_hist_len": (4, 0), "d_hist_sq": (24, 0), "d_hist_guides": (4 * L.RT_GUIDE_PLANES, 0),
+           "d_guides": (4 * L.RT_GUIDE_PLANES, 0), "d_denoised": (24, 0), "d_work": (24, 0), "d_bloom": (24, 0),
+           "d_bloom_work": (8 * L.RT_BLOOM_WORK_PLANES, 0), "d_meter_hist": (0, 8 * L.RT_METER_BINS),
+           "d_meter_state": (0, 8 * L.RT_METER_STATE_DOUBLES), "d_sum": (24, 0)}
+
+# How a product that is missing, made from something else or older than what it reads is refused: the step to run first
+_REFUSALS = {"temporal": "the film has no temporal mean of its current passes: call temporal() first",
+             "denoised": "the film has no filtered mean of its current passes: call denoise() first",
+             "bloom": "the film has no bloom of its current passes and this source: call bloom() with the same denoised and temporal first",
+             "meter": "the film has no metering of its current passes and this source: call meter() with the same denoised, temporal and bloom first"}
+
+
+def products(denoised=False, temporal=False, bloom=False):
+    """The products behind what resolve(denoised=..., temporal=..., bloom=...) shows, upstream first: each is made from the one
+    before it, and the last is the one the request reads."""
+    return ("sum",) + ("temporal",) * bool(temporal) + ("denoised",) * bool(denoised) + ("bloom",) * bool(bloom)
+
+
 class Film:
     """A float64 (3, x1-x0, h) sum of pass frames in the renderer's device memory, and how many passes it holds.  The frame size is
     the renderer's at construction (set_raygen / set_pixel_loc first).  moments: the film also owns a float64 sum of the passes'
@@ -164,40 +190,26 @@ class Film:
         self.renderer, self.x0, self.x1, self.h = renderer, x0, x1, int(h)
         self.ws = x1 - x0
         self.passes = 0
-        self.d_sum = renderer.malloc(24 * self.ws * self.h)
         self.moments = bool(moments)
-        self.d_sq = renderer.malloc(24 * self.ws * self.h) if self.moments else None
-        self.d_denoised_var = self.d_work_var = None              # four planes each: allocated by denoise(variance=True) and variance()
-        self.denoised_variance = False                            # the filtered mean of the current passes is in d_denoised_var
-        self.d_guides = self.d_denoised = self.d_work = None      # allocated by guides() and denoise()
-        self.denoised_passes = 0                                  # the pass count the filtered mean in d_denoised belongs to (0: none)
-        # temporal accumulation: allocated by next_frame() and temporal()
-        self.d_temporal = self.d_temporal_len = None              # the temporal mean of the current passes and its length plane
-        self.d_hist = self.d_hist_len = self.d_hist_guides = None  # the previous frame's mean, lengths and guides
-        self.d_temporal_sq = self.d_hist_sq = None                # with moments: the mean of squares beside d_temporal and d_hist
-        self.temporal_passes = 0                                  # the pass count the mean in d_temporal belongs to (0: none)
+        for name in BUFFERS:
+            setattr(self, name, None)
+        self._buffer("d_sum")
+        if self.moments:
+            self._buffer("d_sq")
+        self.serial = 0                                           # counts the writes of products
+        self.made = {}                                            # product -> (serial of its write, {product it read: that one's serial}, buffer name)
         self.history_camera = None                                # (origin, rotation) the history was rendered with (None: no history)
         self.guides_camera = None                                 # the camera d_guides was last rendered with by this film
         self.guides_stale = False                                 # next_frame() took the guides: d_guides holds an older frame's
-        self.denoised_temporal = False                            # d_denoised is the filtered temporal mean
-        self.d_bloom = self.d_bloom_work = None                   # three and six planes: allocated by bloom()
-        self.bloom_passes = 0                                     # the pass count the mean plus glow in d_bloom belongs to (0: none)
-        self.bloom_source = None                                  # (denoised, temporal) of the source bloom() took
-        self.d_meter_hist = self.d_meter_state = None             # RT_METER_BINS counts and the exposure state: allocated by meter()
-        self.meter_passes = 0                                     # the pass count the histogram in d_meter_hist belongs to (0: none)
-        self.meter_source = None                                  # (denoised, temporal, bloom) of the source meter() took
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
-        d, self.d_sum = getattr(self, "d_sum", None), None
-        names = ("d_denoised_var", "d_work_var", "d_sq", "d_temporal", "d_temporal_len", "d_temporal_sq", "d_hist", "d_hist_len", "d_hist_sq", "d_hist_guides", "d_guides",
-                 "d_denoised", "d_work", "d_bloom", "d_bloom_work", "d_meter_hist", "d_meter_state")
-        extra = [getattr(self, n, None) for n in names]
-        for n in names:
-            setattr(self, n, None)
-        for e in extra + [d]:
-            if e and not self.renderer.closed:
-                self.renderer.free(e)
+        held = [getattr(self, name, None) for name in BUFFERS]
+        for name in BUFFERS:
+            setattr(self, name, None)
+        for d in held:
+            if d and not self.renderer.closed:
+                self.renderer.free(d)
 
     def __enter__(self):
         return self
@@ -215,6 +227,63 @@ class Film:
         if not self.d_sum:
             raise ValueError("the film is closed")
 
+    def _has_pass(self):
+        if self.passes < 1:
+            raise ValueError("the film holds no pass yet")
+
+    def _same_frame(self):
+        if self.renderer.h != self.h or self.x1 > (self.renderer.w or 0):
+            raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
+                             f"[{self.x0}, {self.x1}) of height {self.h}")
+
+    def _buffer(self, name):
+        """The address of the device buffer `name` of BUFFERS, allocated on first use."""
+        if not getattr(self, name):
+            per_pixel, fixed = BUFFERS[name]
+            setattr(self, name, self.renderer.malloc(per_pixel * self.ws * self.h + fixed))
+        return getattr(self, name)
+
+    # -- what was made from what ------------------------------------------------------------
+    def _wrote(self, product, read=None, buffer=None):
+        """Record that `product` has just been written into the buffer named `buffer`, from the product `read` as it stands now."""
+        self.serial += 1
+        self.made[product] = (self.serial, {read: self.made[read][0]} if read else {}, buffer)
+
+    def _stands(self, product, reads=None):
+        """`product` was made from exactly the products `reads` (None: from whatever it was), none of them has been written again
+        since, and each of them stands in the same way."""
+        serial, read, _ = self.made.get(product, (0, {}, None))
+        return serial > 0 and (reads is None or set(read) == set(reads)) and all(
+            self.made[p][0] == s and self._stands(p) for p, s in read.items())
+
+    def current(self, product):
+        """Whether "temporal", "denoised", "bloom" or "meter" is that of the film as it is: made, and nothing it was made from
+        written again since (more passes, or an upstream step redone).  A render loop re-runs the stages that are not."""
+        if product not in ("temporal", "denoised", "bloom", "meter"):
+            raise ValueError(f"product must be 'temporal', 'denoised', 'bloom' or 'meter', not {product!r}")
+        return self._stands(product)
+
+    def _source(self, denoised=False, temporal=False, bloom=False):
+        """(address, n) of what a resolve, a filter, bloom() or meter() with these flags reads: the sum of the passes, the temporal
+        mean, the filtered mean of either, or one of those plus glow; ValueError, naming the step to run first, where a product on
+        the way is missing, was made from something else, or is older than what it was made from."""
+        chain = products(denoised, temporal, bloom)
+        for read, product in zip(chain, chain[1:]):
+            if not self._stands(product, (read,)):
+                raise ValueError(self._refusal(product, read))
+        return getattr(self, self.made[chain[-1]][2]), self.passes if chain[-1] == "sum" else 1
+
+    def _refusal(self, product, read):
+        """Why `product` is not there to be read as made from `read`, and the step to run first.  A filtered mean that exists says
+        which of the two means it is of."""
+        made = self.made.get("denoised")
+        if product != "denoised" or not made:
+            return _REFUSALS[product]
+        if read not in made[1]:
+            return ("the filtered mean is that of the plain passes: call denoise(temporal=True) first" if read == "temporal" else
+                    "the filtered mean is that of the temporal mean, not of the plain passes: call denoise() first")
+        return "the film has no filtered mean of its current temporal mean: call denoise(temporal=True) first" if read == "temporal" else _REFUSALS[product]
+
     # -- passes -----------------------------------------------------------------------------
     def accumulate(self, params, passes=1, stream=None):
         """`passes` more passes of `params` (Renderer.params(...)): pass i is rendered with seed params.seed + i.  A caller who
@@ -223,24 +292,20 @@ class Film:
         passes = int(passes)
         if passes < 1:
             raise ValueError(f"passes must be >= 1, not {passes}")
-        if self.renderer.h != self.h or self.x1 > (self.renderer.w or 0):
-            raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
-                             f"[{self.x0}, {self.x1}) of height {self.h}")
+        self._same_frame()
         if self.moments:
             self.renderer.film_accumulate_moments(params, self.x0, self.x1, passes, self.passes == 0, self.d_sum, self.d_sq,
                                                   self.ws * self.h, self.ws * self.h, stream)
         else:
             self.renderer.film_accumulate(params, self.x0, self.x1, passes, self.passes == 0, self.d_sum, self.ws * self.h, stream)
         self.passes += passes
+        self._wrote("sum", buffer="d_sum")
 
     def clear(self):
-        """Forget every pass: the next accumulate starts from zero.  The guides stay (they do not depend on the passes)."""
+        """Forget every pass, and with them everything made from them: the next accumulate starts from zero.  The guides stay (they
+        do not depend on the passes), and so does the meter's exposure (reset_meter() zeroes it)."""
         self.passes = 0
-        self.denoised_passes = 0
-        self.denoised_variance = False
-        self.temporal_passes = 0
-        self.bloom_passes = 0
-        self.meter_passes = 0                                     # (the exposure state stays: reset_meter() zeroes it)
+        self.made = {}
 
     # -- the denoiser -----------------------------------------------------------------------
     def guides(self, stream=None):
@@ -248,23 +313,17 @@ class Film:
         grid, keep them on the device for denoise(), and return them: float32 (8, ws, h).  clear() does not drop them; a scene,
         camera or grid change is the caller's cue to call this again.  Waits for the stream."""
         self._live()
-        if self.renderer.h != self.h or self.x1 > (self.renderer.w or 0):
-            raise ValueError(f"the renderer's frame is now {self.renderer.w} x {self.renderer.h}; the film holds columns "
-                             f"[{self.x0}, {self.x1}) of height {self.h}")
-        r, n = self.renderer, self.ws * self.h
+        self._same_frame()
         self._render_guides(stream)
-        r.sync(stream)
+        self.renderer.sync(stream)
         out = np.empty((L.RT_GUIDE_PLANES, self.ws, self.h), np.float32)
-        r.d2h(out, self.d_guides)
+        self.renderer.d2h(out, self.d_guides)
         return out
 
     def _render_guides(self, stream=None):
         """The guides of the current scene, camera and grid into d_guides.  Asynchronous."""
-        r, n = self.renderer, self.ws * self.h
-        if not self.d_guides:
-            self.d_guides = r.malloc(4 * L.RT_GUIDE_PLANES * n)
-        r.render_guides(self.x0, self.x1, self.d_guides, n, stream)
-        self.guides_camera = getattr(r, "camera", None)
+        self.renderer.render_guides(self.x0, self.x1, self._buffer("d_guides"), self.ws * self.h, stream)
+        self.guides_camera = getattr(self.renderer, "camera", None)
         self.guides_stale = False
 
     def denoise(self, levels=4, normal_shininess=32, sigma=DENOISE_SIGMA, demodulate=True, stream=None, temporal=False, variance=False,
@@ -288,51 +347,40 @@ class Film:
         self._live()
         if variance:
             return self._denoise_variance(levels, normal_shininess, kappa, var_floor, demodulate, prefilter, temporal, spatial_below, stream)
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
+        self._has_pass()
         levels, shin, sigma, demodulate = check_denoise(levels, normal_shininess, sigma, demodulate)
-        r, n = self.renderer, self.ws * self.h
+        src, n_src = self._source(temporal=temporal)
         if not self.d_guides or self.guides_stale:
             self.guides(stream)
-        if not self.d_denoised:
-            self.d_denoised = r.malloc(24 * n)
-        if levels >= 2 and not self.d_work:
-            self.d_work = r.malloc(24 * n)
-        src, n_src = self._source(False, temporal)
-        r.film_denoise(src, self.ws, self.h, n_src, self.d_guides, self.d_denoised, self.d_work, levels=levels,
-                       normal_shin=shin, sigma=sigma, demodulate=demodulate, stream=stream)
-        self.denoised_passes = self.passes
-        self.denoised_temporal = bool(temporal)
-        self.denoised_variance = False
+        out, work = self._buffer("d_denoised"), self._buffer("d_work") if levels >= 2 else self.d_work
+        self.renderer.film_denoise(src, self.ws, self.h, n_src, self.d_guides, out, work, levels=levels, normal_shin=shin, sigma=sigma,
+                                   demodulate=demodulate, stream=stream)
+        self._wrote("denoised", products(temporal=temporal)[-1], "d_denoised")
 
-    def _variance_buffers(self, d_out, d_work, stream):
-        """What both variance calls need once their own conditions hold: current guides, and the four-plane buffers named d_out and
-        d_work (None: no work buffer), allocated on first use.  Returns their addresses."""
+    def _variance_buffers(self, temporal, d_out, d_work, stream):
+        """What both variance calls need: a film with moments and, first, their own condition (two passes, or the temporal mean of
+        the current passes with its second moment); then current guides, and the four-plane buffers named d_out and d_work (None:
+        no work buffer), allocated on first use.  Returns their addresses."""
+        if not self.moments:
+            raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
+        if temporal and not (self._stands("temporal") and self.d_temporal_sq):
+            raise ValueError("the film has no temporal mean of its current passes, and so no second moment of one: call temporal() first")
+        if not temporal and self.passes < 2:
+            raise ValueError(f"a variance needs at least 2 passes, the film holds {self.passes}")
         if not self.d_guides or self.guides_stale:
             self.guides(stream)
-        for name in (d_out, d_work):
-            if name and not getattr(self, name):
-                setattr(self, name, self.renderer.malloc(8 * VAR_PLANES * self.ws * self.h))
-        return getattr(self, d_out), getattr(self, d_work) if d_work else None
+        return self._buffer(d_out), self._buffer(d_work) if d_work else None
 
     def _variance_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, stream):
         """rt_film_denoise_variance on the film's sums into d_out (four planes), after what it needs is there."""
-        if not self.moments:
-            raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
-        if self.passes < 2:
-            raise ValueError(f"a variance needs at least 2 passes, the film holds {self.passes}")
-        out, work = self._variance_buffers(d_out, d_work, stream)
+        out, work = self._variance_buffers(False, d_out, d_work, stream)
         self.renderer.film_denoise_variance(self.d_sum, self.d_sq, self.ws, self.h, self.passes, self.d_guides, out, work, levels=levels,
                                             normal_shin=shin, kappa=kappa, var_floor=var_floor, demodulate=demodulate, prefilter=prefilter,
                                             stream=stream)
 
     def _variance_temporal_call(self, d_out, d_work, levels, shin, kappa, var_floor, demodulate, prefilter, spatial_below, stream):
         """rt_film_denoise_variance_temporal on the temporal mean, its mean of squares and its lengths into d_out (four planes)."""
-        if not self.moments:
-            raise ValueError("the film keeps no sum of squares: make it with Film(renderer, moments=True)")
-        if not self.temporal_passes or self.temporal_passes != self.passes or not self.d_temporal_sq:
-            raise ValueError("the film has no temporal mean of its current passes, and so no second moment of one: call temporal() first")
-        out, work = self._variance_buffers(d_out, d_work, stream)
+        out, work = self._variance_buffers(True, d_out, d_work, stream)
         self.renderer.film_denoise_variance_temporal(self.d_temporal, self.d_temporal_sq, self.d_temporal_len, self.ws, self.h, self.d_guides,
                                                      out, work, levels=levels, normal_shin=shin, kappa=kappa, var_floor=var_floor,
                                                      demodulate=demodulate, prefilter=prefilter, spatial_below=spatial_below, stream=stream)
@@ -345,9 +393,7 @@ class Film:
                                          check_spatial_below(spatial_below), stream)
         else:
             self._variance_call("d_denoised_var", work, levels, shin, kappa, var_floor, demodulate, prefilter, stream)
-        self.denoised_passes = self.passes
-        self.denoised_temporal = bool(temporal)
-        self.denoised_variance = True
+        self._wrote("denoised", products(temporal=temporal)[-1], "d_denoised_var")
 
     def variance(self, stream=None, temporal=False, spatial_below=SPATIAL_BELOW):
         """The estimated variance of the mean of the passes so far, per pixel, summed over the channels: float64 (ws, h), plane 3 of
@@ -366,18 +412,6 @@ class Film:
         r.d2h(out, self.d_work_var + 8 * 3 * self.ws * self.h)
         return out
 
-    def _source(self, denoised, temporal=False):
-        """(sum or mean, its n) of a resolve or a filter: the sum of the passes, the temporal mean, or the filtered mean of either."""
-        if temporal and (not self.temporal_passes or self.temporal_passes != self.passes):
-            raise ValueError("the film has no temporal mean of its current passes: call temporal() first")
-        if not denoised:
-            return (self.d_temporal, 1) if temporal else (self.d_sum, self.passes)
-        if not self.denoised_passes or self.denoised_passes != self.passes:
-            raise ValueError("the film has no filtered mean of its current passes: call denoise() first")
-        if temporal and not self.denoised_temporal:
-            raise ValueError("the filtered mean is that of the plain passes: call denoise(temporal=True) first")
-        return (self.d_denoised_var if self.denoised_variance else self.d_denoised), 1
-
     # -- bloom ------------------------------------------------------------------------------
     def bloom(self, threshold=BLOOM_THRESHOLD, strength=BLOOM_STRENGTH, levels=BLOOM_LEVELS, stream=None, denoised=False, temporal=False):
         """The mean plus the glow of what is brighter than `threshold` (Renderer.film_bloom) into the film's own buffer, which
@@ -385,37 +419,14 @@ class Film:
         times `strength` added in linear colour.  denoised, temporal: the source, exactly what resolve(denoised=..., temporal=...)
         would show.  The result belongs to the current passes and that source.  Asynchronous."""
         self._live()
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
+        self._has_pass()
         threshold, strength, levels, _ = check_bloom(threshold, strength, levels)
         src, n_src = self._source(denoised, temporal)
-        r, n = self.renderer, self.ws * self.h
-        if not self.d_bloom:
-            self.d_bloom = r.malloc(24 * n)
-        if not self.d_bloom_work:
-            self.d_bloom_work = r.malloc(8 * L.RT_BLOOM_WORK_PLANES * n)
-        r.film_bloom(src, self.ws, self.h, n_src, self.d_bloom, self.d_bloom_work, threshold=threshold, strength=strength, levels=levels,
-                     stream=stream)
-        self.bloom_passes = self.passes
-        self.bloom_source = (bool(denoised), bool(temporal))
-
-    def _bloomed(self, denoised, temporal):
-        """(d_bloom, 1) for a resolve with bloom=True, or ValueError where bloom() has not run for the current passes and source."""
-        self._source(denoised, temporal)
-        if not self.bloom_passes or self.bloom_passes != self.passes or self.bloom_source != (bool(denoised), bool(temporal)):
-            raise ValueError("the film has no bloom of its current passes and this source: call bloom() with the same denoised and temporal first")
-        return self.d_bloom, 1
+        self.renderer.film_bloom(src, self.ws, self.h, n_src, self._buffer("d_bloom"), self._buffer("d_bloom_work"), threshold=threshold,
+                                 strength=strength, levels=levels, stream=stream)
+        self._wrote("bloom", products(denoised, temporal)[-1], "d_bloom")
 
     # -- metering ---------------------------------------------------------------------------
-    def _meter_buffers(self):
-        """The counts and the state, allocated on first use; the state starts as zeros: no history."""
-        r = self.renderer
-        if not self.d_meter_hist:
-            self.d_meter_hist = r.malloc(8 * L.RT_METER_BINS)
-        if not self.d_meter_state:
-            self.d_meter_state = r.malloc(8 * L.RT_METER_STATE_DOUBLES)
-            r.h2d(self.d_meter_state, np.zeros(L.RT_METER_STATE_DOUBLES, np.float64))
-
     def meter(self, key=METER_KEY, percentile=METER_PERCENTILE, min_exposure=MIN_EXPOSURE, max_exposure=MAX_EXPOSURE, rate=METER_RATE,
               stream=None, denoised=False, temporal=False, bloom=False):
         """Meter the source that resolve(denoised=..., temporal=..., bloom=...) would show (Renderer.film_meter: a histogram of its
@@ -425,23 +436,22 @@ class Film:
         resolve(auto_exposure=True) uses them, exposure() and histogram() read them.  The exposure survives next_frame() and clear().
         The defaults are starting points, not measurements: 46 is 18 % of 255.  Asynchronous."""
         self._live()
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
+        self._has_pass()
         key, percentile, min_exposure, max_exposure, rate = check_meter(key, percentile, min_exposure, max_exposure, rate)
-        src, n_src = self._bloomed(denoised, temporal) if bloom else self._source(denoised, temporal)
-        self._meter_buffers()
-        r = self.renderer
-        r.film_meter(src, self.ws, self.h, n_src, self.d_meter_hist, reset=True, stream=stream)
-        r.film_meter_solve(self.d_meter_hist, self.d_meter_state, key=key, percentile=percentile, min_exposure=min_exposure,
-                           max_exposure=max_exposure, rate=rate, stream=stream)
-        self.meter_passes = self.passes
-        self.meter_source = (bool(denoised), bool(temporal), bool(bloom))
+        src, n_src = self._source(denoised, temporal, bloom)
+        r, new = self.renderer, not self.d_meter_state
+        hist, state = self._buffer("d_meter_hist"), self._buffer("d_meter_state")
+        if new:                                                   # the state starts as zeros: no history
+            r.h2d(state, np.zeros(L.RT_METER_STATE_DOUBLES, np.float64))
+        r.film_meter(src, self.ws, self.h, n_src, hist, reset=True, stream=stream)
+        r.film_meter_solve(hist, state, key=key, percentile=percentile, min_exposure=min_exposure, max_exposure=max_exposure, rate=rate,
+                           stream=stream)
+        self._wrote("meter", products(denoised, temporal, bloom)[-1], "d_meter_state")
 
     def _metered(self, denoised, temporal, bloom):
-        """d_meter_state for a resolve with auto_exposure=True, or ValueError where meter() has not run for the current passes and source."""
-        if not self.meter_passes or self.meter_passes != self.passes or self.meter_source != (bool(denoised), bool(temporal), bool(bloom)):
-            raise ValueError("the film has no metering of its current passes and this source: call meter() with the same denoised, temporal "
-                             "and bloom first")
+        """d_meter_state for a resolve with auto_exposure=True, or ValueError where meter() has not run on what that resolve shows."""
+        if not self._stands("meter", products(denoised, temporal, bloom)[-1:]):
+            raise ValueError(_REFUSALS["meter"])
         return self.d_meter_state
 
     def exposure(self, stream=None):
@@ -457,7 +467,7 @@ class Film:
     def histogram(self, stream=None):
         """The counts of the last meter(): uint64 (RT_METER_BINS,); meter.bin_edges() has the bins' edges.  Waits for the stream."""
         self._live()
-        if not self.d_meter_hist or not self.meter_source:
+        if not self.d_meter_hist:                                 # (meter() alone allocates it, after its checks)
             raise ValueError("the film has not metered yet: call meter() first")
         out = np.zeros(L.RT_METER_BINS, np.uint64)
         self.renderer.sync(stream)
@@ -467,7 +477,7 @@ class Film:
     def reset_meter(self):
         """Forget the exposure: the next meter() jumps whatever its rate."""
         self._live()
-        self.meter_passes = 0
+        self.made.pop("meter", None)
         if self.d_meter_state:
             self.renderer.h2d(self.d_meter_state, np.zeros(L.RT_METER_STATE_DOUBLES, np.float64))
 
@@ -497,10 +507,9 @@ class Film:
         Asynchronous."""
         self._live()
         self._full_frame()
-        r, n = self.renderer, self.ws * self.h
         if self.passes < 1:
             return
-        if self.temporal_passes == self.passes:                   # the temporal buffers become the history: a swap
+        if self._stands("temporal"):                              # the temporal buffers become the history: a swap
             self.d_hist, self.d_temporal = self.d_temporal, self.d_hist
             self.d_hist_len, self.d_temporal_len = self.d_temporal_len, self.d_hist_len
             if self.moments:
@@ -508,13 +517,10 @@ class Film:
         else:                                                     # the plain mean: a fresh temporal call writes sum / passes and (float)passes
             if self.guides_camera is None:
                 raise ValueError("the film has no guides of the frame that ends: call guides() or temporal() before the camera moves")
-            if not self.d_hist:
-                self.d_hist, self.d_hist_len = r.malloc(24 * n), r.malloc(4 * n)
-            if self.moments and not self.d_hist_sq:
-                self.d_hist_sq = r.malloc(24 * n)
+            hist, hist_len, hist_sq = self._buffer("d_hist"), self._buffer("d_hist_len"), self._buffer("d_hist_sq") if self.moments else None
             # sum / passes, the length passes and with moments sq / passes: max_history 0 makes every pixel fresh, the history a placeholder
-            self._temporal_call(self.d_sum, self.d_sq, self.d_guides, self.d_guides, self.guides_camera, self.d_hist, self.d_hist_sq,
-                                self.d_hist_len, depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
+            self._temporal_call(self.d_sum, self.d_sq, self.d_guides, self.d_guides, self.guides_camera, hist, hist_sq, hist_len,
+                                depth_tol=0.0, normal_cos=1.0, max_history=0.0, stream=stream)
         self.d_hist_guides, self.d_guides = self.d_guides, self.d_hist_guides
         self.history_camera, self.guides_camera = self.guides_camera, None
         self.guides_stale = True
@@ -530,51 +536,53 @@ class Film:
         A film with moments blends the second moment by the same lengths (Renderer.film_temporal_moments) into d_temporal_sq, which
         denoise(variance=True, temporal=True) takes.  Asynchronous."""
         self._live()
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
+        self._has_pass()
         depth_tol, normal_cos, max_history, _ = check_temporal(depth_tol, normal_cos, max_history, self.passes)
         self._full_frame()
-        r, n = self.renderer, self.ws * self.h
+        r = self.renderer
         if getattr(r, "camera", None) is None:
             raise ValueError("the renderer has no camera yet: call set_camera first")
         if self.guides_camera is None or any(not np.array_equal(a, b) for a, b in zip(self.guides_camera, r.camera)):
             self._render_guides(stream)
-        if not self.d_temporal:
-            self.d_temporal, self.d_temporal_len = r.malloc(24 * n), r.malloc(4 * n)
-        if self.moments and not self.d_temporal_sq:
-            self.d_temporal_sq = r.malloc(24 * n)
-        out = (self.d_temporal, self.d_temporal_sq, self.d_temporal_len)
+        mean, mean_len = self._buffer("d_temporal"), self._buffer("d_temporal_len")
+        out = (mean, self._buffer("d_temporal_sq") if self.moments else None, mean_len)
         kw = dict(depth_tol=depth_tol, normal_cos=normal_cos, stream=stream)
         if self.history_camera is None:                           # no history: every pixel fresh (the inputs are placeholders)
             self._temporal_call(self.d_sum, self.d_sq, self.d_guides, self.d_guides, r.camera, *out, max_history=0.0, **kw)
         else:
             self._temporal_call(self.d_hist, self.d_hist_sq, self.d_hist_len, self.d_hist_guides, self.history_camera, *out,
                                 max_history=max_history, **kw)
-        self.temporal_passes = self.passes
+        self._wrote("temporal", "sum", "d_temporal")
 
     # -- frames -----------------------------------------------------------------------------
+    def _request(self, exposure, white, gamma, flags, denoised, temporal, bloom, auto_exposure):
+        """What both resolves check before they touch the device, and what they then read: (source address, its n, the meter's state
+        or None)."""
+        self._live()
+        self._has_pass()
+        check_tone(self.passes, exposure, white, gamma, flags)
+        return self._source(denoised, temporal, bloom) + (self._metered(denoised, temporal, bloom) if auto_exposure else None,)
+
+    def _resolve_call(self, request, d_u8, d_f32, **tone):
+        src, n, state = request
+        if state:
+            self.renderer.film_resolve_metered(src, self.ws, self.h, n, state, d_u8, d_f32, **tone)
+        else:
+            self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, **tone)
+
     def resolve_device(self, d_u8=None, d_f32=None, exposure=1.0, white=0.0, gamma=1, flags=0, out_stride=None, stream=None,
                        denoised=False, temporal=False, bloom=False, auto_exposure=False):
         """The mean of the passes so far, tone-mapped, into caller-owned device memory (raw addresses), laid out as
         Renderer.render_device's outputs; denoised: the mean that denoise() filtered instead; temporal: the mean that temporal()
         wrote (with denoised: its filtered version, denoise(temporal=True)); bloom: that source with the glow that bloom() added;
         auto_exposure: `exposure` times the exposure that meter() solved for that source (Renderer.film_resolve_metered).
-        Asynchronous."""
-        self._live()
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
-        check_tone(self.passes, exposure, white, gamma, flags)
+        ValueError unless each of those was made from the film as it is now (Film.current).  Asynchronous."""
+        request = self._request(exposure, white, gamma, flags, denoised, temporal, bloom, auto_exposure)
         if not d_u8 and not d_f32:
             raise ValueError("both outputs are None")
         if int(flags) & L.RT_FLAG_U8_HWC and d_f32:
             raise ValueError("RT_FLAG_U8_HWC is a uint8 layout: resolve the float32 frame in a separate call")
-        src, n = self._bloomed(denoised, temporal) if bloom else self._source(denoised, temporal)
-        if auto_exposure:
-            self.renderer.film_resolve_metered(src, self.ws, self.h, n, self._metered(denoised, temporal, bloom), d_u8, d_f32, exposure=exposure,
-                                               white=white, gamma=gamma, flags=flags, out_stride=out_stride, stream=stream)
-            return
-        self.renderer.film_resolve(src, self.ws, self.h, n, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma,
-                                   flags=flags, out_stride=out_stride, stream=stream)
+        self._resolve_call(request, d_u8, d_f32, exposure=exposure, white=white, gamma=gamma, flags=flags, out_stride=out_stride, stream=stream)
 
     def resolve(self, exposure=1.0, white=0.0, gamma=1, u8=True, f32=False, flags=0, denoised=False, temporal=False, bloom=False,
                 auto_exposure=False):
@@ -583,18 +591,9 @@ class Film:
         the glow that bloom() added to that source; auto_exposure: with `exposure` times the exposure that meter() solved for that source
         (ValueError unless meter() ran for the current passes and the same denoised, temporal and bloom).  Waits for the context's
         stream."""
-        self._live()
-        if self.passes < 1:
-            raise ValueError("the film holds no pass yet")
-        check_tone(self.passes, exposure, white, gamma, flags)
+        request = self._request(exposure, white, gamma, flags, denoised, temporal, bloom, auto_exposure)
         if not u8 and not f32:
             raise ValueError("neither u8 nor f32 is asked for")
-        if bloom:
-            self._bloomed(denoised, temporal)
-        else:
-            self._source(denoised, temporal)
-        if auto_exposure:
-            self._metered(denoised, temporal, bloom)
         r, n = self.renderer, self.ws * self.h
         hwc = bool(int(flags) & L.RT_FLAG_U8_HWC)
         out8 = np.empty((self.h, self.ws, 3) if hwc else (3, self.ws, self.h), np.uint8) if u8 else None
@@ -602,17 +601,13 @@ class Film:
         d8 = r.malloc(3 * n) if u8 else None
         d32 = r.malloc(12 * n) if f32 else None
         try:
-            kw = dict(exposure=exposure, white=white, gamma=gamma, denoised=denoised, temporal=temporal)
-            if bloom:
-                kw["bloom"] = True
-            if auto_exposure:
-                kw["auto_exposure"] = True
+            tone = dict(exposure=exposure, white=white, gamma=gamma, out_stride=None, stream=None)
             if hwc:                                             # (the image layout is uint8 only: two calls)
-                self.resolve_device(d8, None, flags=flags, **kw)
+                self._resolve_call(request, d8, None, flags=flags, **tone)
                 if f32:
-                    self.resolve_device(None, d32, flags=int(flags) & ~L.RT_FLAG_U8_HWC, **kw)
+                    self._resolve_call(request, None, d32, flags=int(flags) & ~L.RT_FLAG_U8_HWC, **tone)
             else:
-                self.resolve_device(d8, d32, flags=flags, **kw)
+                self._resolve_call(request, d8, d32, flags=flags, **tone)
             if u8:
                 r.d2h(out8, d8)
             if f32:

@@ -386,8 +386,8 @@ class Renderer:
         if plane_stride is None:
             plane_stride = (int(x1) - int(x0)) * self.h
         self._check(self._lib.rt_render_device(self._ctx, C.byref(params), int(x0), int(x1),
-                                               C.c_void_p(d_u8) if d_u8 else None, C.c_void_p(d_f32) if d_f32 else None,
-                                               int(plane_stride), C.c_void_p(stream) if stream else None))
+                                               _vp(d_u8), _vp(d_f32),
+                                               int(plane_stride), _vp(stream)))
 
     def render_sequence(self, params, x0, x1, n, d_u8=None, d_f32=None, plane_stride=None, frame_stride=None, cameras=None,
                         streams=None, frames_per_launch=0):
@@ -410,7 +410,7 @@ class Renderer:
             self._seq_streams_key = sv
             self._seq_streams = (C.c_void_p * len(sv))(*sv) if sv else None
         self._check(self._lib.rt_render_sequence(self._ctx, C.byref(params), int(x0), int(x1), int(n),
-                                                 C.c_void_p(d_u8) if d_u8 else None, C.c_void_p(d_f32) if d_f32 else None,
+                                                 _vp(d_u8), _vp(d_f32),
                                                  int(plane_stride), int(frame_stride),
                                                  cam.ctypes.data_as(C.POINTER(C.c_double)) if cam is not None else None,
                                                  self._seq_streams, len(sv), int(frames_per_launch)))
@@ -422,8 +422,8 @@ class Renderer:
         if sum_stride is None:
             sum_stride = (int(x1) - int(x0)) * self.h
         self._check(self._lib.rt_film_accumulate(self._ctx, C.byref(params), int(x0), int(x1), int(passes), int(bool(reset)),
-                                                 C.c_void_p(d_sum) if d_sum else None, int(sum_stride),
-                                                 C.c_void_p(stream) if stream else None))
+                                                 _vp(d_sum), int(sum_stride),
+                                                 _vp(stream)))
 
     def film_resolve(self, d_sum, ws, h, n, d_u8=None, d_f32=None, *, exposure=1.0, white=0.0, gamma=1, flags=0, sum_stride=None,
                      out_stride=None, stream=None):
@@ -434,9 +434,9 @@ class Renderer:
         if out_stride is None:
             out_stride = int(ws) if int(flags) & L.RT_FLAG_U8_HWC else int(ws) * int(h)
         tone = L.rt_film_tone(float(exposure), float(white), int(gamma), int(flags))
-        self._check(self._lib.rt_film_resolve(self._ctx, C.c_void_p(d_sum) if d_sum else None, int(sum_stride), int(ws), int(h), int(n),
-                                              C.byref(tone), C.c_void_p(d_u8) if d_u8 else None, C.c_void_p(d_f32) if d_f32 else None,
-                                              int(out_stride), C.c_void_p(stream) if stream else None))
+        self._check(self._lib.rt_film_resolve(self._ctx, _vp(d_sum), int(sum_stride), int(ws), int(h), int(n),
+                                              C.byref(tone), _vp(d_u8), _vp(d_f32),
+                                              int(out_stride), _vp(stream)))
 
     def _later_entry(self, name):
         fn = getattr(self._lib, name, None)
@@ -450,8 +450,8 @@ class Renderer:
         ray (a lens is ignored); plane_stride elements between planes.  Asynchronous.  In numpy: denoise.guides_reference."""
         if plane_stride is None:
             plane_stride = (int(x1) - int(x0)) * (self.h or 0)
-        self._check(self._later_entry("rt_render_guides")(self._ctx, int(x0), int(x1), C.c_void_p(d_guides) if d_guides else None,
-                                                          int(plane_stride), C.c_void_p(stream) if stream else None))
+        self._check(self._later_entry("rt_render_guides")(self._ctx, int(x0), int(x1), _vp(d_guides),
+                                                          int(plane_stride), _vp(stream)))
 
     def film_denoise(self, d_sum, ws, h, n, d_guides, d_out, d_work=None, *, levels=4, normal_shin=32, sigma=0.0, demodulate=1,
                      sum_stride=None, guide_stride=None, out_stride=None, work_stride=None, stream=None, reserved=0):
@@ -588,16 +588,16 @@ class Renderer:
             self._check(self._lib.rt_stream_forget(self._ctx, C.c_void_p(stream)))
 
     def timer_begin(self, stream=None):
-        self._check(self._lib.rt_timer_begin(self._ctx, C.c_void_p(stream) if stream else None))
+        self._check(self._lib.rt_timer_begin(self._ctx, _vp(stream)))
 
     def timer_end(self, stream=None):
         ms = C.c_float()
-        self._check(self._lib.rt_timer_end(self._ctx, C.c_void_p(stream) if stream else None, C.byref(ms)))
+        self._check(self._lib.rt_timer_end(self._ctx, _vp(stream), C.byref(ms)))
         return ms.value
 
     def set_tile_stats(self, dptr):
         """Device buffer (uint32 per 8x8 tile) that later launches fill with per-tile wave cycles; None = off."""
-        self._check(self._lib.rt_set_tile_stats(self._ctx, C.c_void_p(dptr) if dptr else None))
+        self._check(self._lib.rt_set_tile_stats(self._ctx, _vp(dptr)))
 
     def stats(self):
         """rt_stats as a dict: launch counters, and the ray counters of RT_FLAG_COUNT_RAYS launches."""

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from film_stub import NoDevice
 from test_film import same_bits
-from test_denoise import _NoDevice
 import bloom_cases as bc
 
 from python_ray_tracer_amd import Film, bloom as B
@@ -189,22 +189,8 @@ def test_kernel_text_under_sanitizers_matches_numpy(tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # Film's call sequences, before the library sees anything
 
-class _NoDeviceBloom(_NoDevice):
-    def film_resolve(self, *a, **kw):
-        self.calls.append(("resolve",) + a)
-
-    def render_guides(self, *a):
-        self.calls.append(("guides",) + a)
-
-    def film_denoise(self, *a, **kw):
-        self.calls.append(("denoise",) + a + (kw,))
-
-    def film_bloom(self, *a, **kw):
-        self.calls.append(("bloom",) + a + (kw,))
-
-
 def test_film_bloom_call_sequences_and_value_errors():
-    r = _NoDeviceBloom()
+    r = NoDevice()
     p = L.rt_params()
     with Film(r) as film:
         with pytest.raises(ValueError, match="no pass"):

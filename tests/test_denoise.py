@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO, load_frame, raygen_closed_form
+from film_stub import NoDevice
 from test_film import same_bits
 
 from python_ray_tracer_amd import Film, denoise as D, film as F
@@ -316,42 +317,8 @@ def test_check_denoise():
             D.denoise_reference(*args)
 
 
-class _NoDevice:
-    """What Film touches of a Renderer, with every device call recorded."""
-    closed = False
-
-    def __init__(self, w=8, h=4):
-        self.w, self.h, self.calls, self.next = w, h, [], 4096
-
-    def malloc(self, n):
-        self.calls.append(("malloc", n))
-        self.next += 4096
-        return self.next
-
-    def free(self, d):
-        self.calls.append(("free", d))
-
-    def sync(self, stream=None):
-        self.calls.append(("sync", stream))
-
-    def d2h(self, host, d):
-        host[...] = 0
-
-    def film_accumulate(self, *a):
-        self.calls.append(("accumulate",) + a)
-
-    def film_resolve(self, *a, **kw):
-        self.calls.append(("resolve",) + a)
-
-    def render_guides(self, *a):
-        self.calls.append(("guides",) + a)
-
-    def film_denoise(self, *a, **kw):
-        self.calls.append(("denoise",) + a + (kw,))
-
-
 def test_film_denoise_value_errors_and_buffers():
-    r = _NoDevice()
+    r = NoDevice()
     with Film(r, 2, 6) as film:
         assert [c[0] for c in r.calls] == ["malloc"]              # the guides and filter buffers come with their first use
         with pytest.raises(ValueError, match="no pass"):
@@ -384,7 +351,7 @@ def test_film_denoise_value_errors_and_buffers():
         with pytest.raises(ValueError, match="denoise\\(\\) first"):
             film.resolve_device(d_u8=1, denoised=True)
         film.clear()
-        assert film.d_guides and film.denoised_passes == 0        # clear() keeps the guides
+        assert film.d_guides and not film.current("denoised")        # clear() keeps the guides
         r.h = 5
         with pytest.raises(ValueError, match="frame is now"):
             film.guides()

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from film_stub import NoDevice
 
 from python_ray_tracer_amd import Film, film as F
 from python_ray_tracer_amd import _lib as L
@@ -206,36 +207,15 @@ def test_identity_at_n_1():
 # ---------------------------------------------------------------------------------------------------------------------
 # Film's argument checks, before the library sees anything
 
-class _NoDevice:
-    """What Film touches of a Renderer, with every device call recorded."""
-    closed = False
-
-    def __init__(self, w=8, h=4):
-        self.w, self.h, self.calls = w, h, []
-
-    def malloc(self, n):
-        self.calls.append(("malloc", n))
-        return 4096
-
-    def free(self, d):
-        self.calls.append(("free", d))
-
-    def film_accumulate(self, *a):
-        self.calls.append(("accumulate",) + a)
-
-    def film_resolve(self, *a, **kw):
-        self.calls.append(("resolve",) + a)
-
-
 def test_film_value_errors():
     with pytest.raises(ValueError, match="ray grid"):
-        Film(_NoDevice(None, None))
+        Film(NoDevice(None, None))
     for x0, x1 in ((-1, 4), (4, 4), (0, 9), (5, 3)):
         with pytest.raises(ValueError, match="column range"):
-            Film(_NoDevice(), x0, x1)
+            Film(NoDevice(), x0, x1)
     with pytest.raises(ValueError, match="RT_FILM_MAX_PIXELS"):
-        Film(_NoDevice(1, 2 ** 27 + 1))
-    r = _NoDevice()
+        Film(NoDevice(1, 2 ** 27 + 1))
+    r = NoDevice()
     with Film(r, 2, 6) as film:
         assert r.calls == [("malloc", 24 * 4 * 4)] and (film.ws, film.h, film.passes) == (4, 4, 0)
         p = L.rt_params()

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from film_stub import NoDevice
 from test_film import same_bits
-from test_bloom import _NoDeviceBloom
 import meter_cases as mc
 
 from python_ray_tracer_amd import Film, meter as M
@@ -265,22 +265,8 @@ def test_kernel_text_under_sanitizers_matches_numpy(tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # Film's call sequences, before the library sees anything
 
-class _NoDeviceMeter(_NoDeviceBloom):
-    def h2d(self, d, host):
-        self.calls.append(("h2d", d, host.tobytes()))
-
-    def film_meter(self, *a, **kw):
-        self.calls.append(("meter",) + a + (kw,))
-
-    def film_meter_solve(self, *a, **kw):
-        self.calls.append(("solve",) + a + (kw,))
-
-    def film_resolve_metered(self, *a, **kw):
-        self.calls.append(("resolve_metered",) + a)
-
-
 def test_film_meter_call_sequences_and_value_errors():
-    r = _NoDeviceMeter()
+    r = NoDevice()
     p = L.rt_params()
     defaults = dict(key=46.0, percentile=0.5, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, rate=1.0, stream=None)
     with Film(r) as film:

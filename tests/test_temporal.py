@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
-from test_denoise import _NoDevice
+from film_stub import NoDevice
 from test_film import same_bits
 import temporal_cases as tc
 
@@ -296,26 +296,15 @@ def test_check_temporal_and_reference_value_errors():
             T.temporal_reference(**{**ok, **change})
 
 
-class _NoDeviceTemporal(_NoDevice):
-    """_NoDevice with a camera and the temporal call."""
-
-    def __init__(self, w=8, h=4):
-        super().__init__(w, h)
-        self.camera = (np.zeros(3), np.eye(3).reshape(9))
-
-    def film_temporal(self, *a, **kw):
-        self.calls.append(("temporal",) + a + (kw,))
-
-
 def test_film_temporal_value_errors_and_buffers():
-    r = _NoDeviceTemporal()
+    r = NoDevice()
     with Film(r, 2, 6) as slab:                                   # a column slab cannot be reprojected
         slab.accumulate(L.rt_params(), 1)
         with pytest.raises(ValueError, match="full frame"):
             slab.temporal()
         with pytest.raises(ValueError, match="full frame"):
             slab.next_frame()
-    r = _NoDeviceTemporal()
+    r = NoDevice()
     with Film(r) as film:
         with pytest.raises(ValueError, match="no pass"):
             film.temporal()
@@ -354,7 +343,7 @@ def test_film_temporal_value_errors_and_buffers():
         film.next_frame()
         assert len(r.calls) == n                                  # a swap: the temporal mean is the history, no call
         assert (film.d_hist, film.d_hist_len, film.d_hist_guides) == (first_mean, first_len, first_guides)
-        assert film.passes == 0 and film.temporal_passes == 0 and film.history_camera is cam0
+        assert film.passes == 0 and not film.current("temporal") and film.history_camera is cam0
         film.accumulate(L.rt_params(), 2)
         film.temporal(max_history=8, depth_tol=0.5, normal_cos=0.25)
         call = r.calls[-1]

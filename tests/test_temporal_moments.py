@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from film_stub import NoDevice
 from test_denoise import _flat_guides
 from test_film import same_bits
-from test_temporal import CONTRACT as TEMPORAL_CONTRACT, _NoDeviceTemporal
+from test_temporal import CONTRACT as TEMPORAL_CONTRACT
 from test_variance import frame_guides, noisy_passes
 import temporal_cases as tc
 
@@ -393,22 +394,8 @@ def test_reference_value_errors():
 # ---------------------------------------------------------------------------------------------------------------------
 # Film's call sequences, before the library sees anything
 
-class _NoDeviceTemporalMoments(_NoDeviceTemporal):
-    def film_accumulate_moments(self, *a):
-        self.calls.append(("accumulate_moments",) + a)
-
-    def film_denoise_variance(self, *a, **kw):
-        self.calls.append(("denoise_variance",) + a + (kw,))
-
-    def film_temporal_moments(self, *a, **kw):
-        self.calls.append(("temporal_moments",) + a + (kw,))
-
-    def film_denoise_variance_temporal(self, *a, **kw):
-        self.calls.append(("denoise_variance_temporal",) + a + (kw,))
-
-
 def test_film_moments_call_sequences_and_value_errors():
-    r = _NoDeviceTemporalMoments()
+    r = NoDevice()
     p = L.rt_params()
     with Film(r, moments=True) as film:
         film.accumulate(p, 1)
@@ -487,7 +474,7 @@ def test_film_moments_call_sequences_and_value_errors():
 
 def test_a_plain_film_makes_the_calls_it_made():
     """Without moments: no second-moment buffer, the plain temporal calls, and the variance paths refuse before any call."""
-    r = _NoDeviceTemporalMoments()
+    r = NoDevice()
     p = L.rt_params()
     with Film(r) as film:
         film.accumulate(p, 2)

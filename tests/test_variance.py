@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import REPO
-from test_denoise import _NoDevice, _flat_guides, guides_truth
+from film_stub import NoDevice
+from test_denoise import _flat_guides, guides_truth
 from test_film import same_bits
 import variance_cases as vc
 
@@ -332,16 +333,8 @@ def test_quality_beats_the_raw_mean_and_the_fixed_sigma(oracle):
 # ---------------------------------------------------------------------------------------------------------------------
 # Film's argument checks, before the library sees anything
 
-class _NoDeviceMoments(_NoDevice):
-    def film_accumulate_moments(self, *a):
-        self.calls.append(("accumulate_moments",) + a)
-
-    def film_denoise_variance(self, *a, **kw):
-        self.calls.append(("denoise_variance",) + a + (kw,))
-
-
 def test_film_variance_value_errors_and_buffers():
-    r = _NoDeviceMoments()
+    r = NoDevice()
     with Film(r, 2, 6) as plain:                                  # without moments nothing changes, and the variance paths refuse
         assert [c[0] for c in r.calls] == ["malloc"] and not plain.moments and plain.d_sq is None
         plain.accumulate(L.rt_params(), 4)
@@ -352,7 +345,7 @@ def test_film_variance_value_errors_and_buffers():
         with pytest.raises(ValueError, match="moments=True"):
             plain.variance()
         assert len(r.calls) == n
-    r = _NoDeviceMoments()
+    r = NoDevice()
     with Film(r, 2, 6, moments=True) as film:
         assert r.calls == [("malloc", 24 * 16), ("malloc", 24 * 16)] and film.d_sq and film.d_sq != film.d_sum
         p = L.rt_params()
