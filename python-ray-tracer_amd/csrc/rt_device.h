@@ -559,6 +559,25 @@ __device__ __forceinline__ int opaque(int x)
     return x;
 }
 
+// The kernels whose once-per-tile path (render_kernel's prologue, pixel_P, trace_bounce's light base, store_pixel) is compiled in
+// its trimmed form; the others keep the general one, instruction for instruction.  The trims are worth a few dozen scalar
+// instructions per wave, which only a kernel on its instruction-issue bound feels, and every one of them moves the register
+// allocation of the kernels it touches (tools/isa_compare.py: applied everywhere, more than half of the library's kernels
+// gained a spilled scalar or vector register): so they go to the kernels they were measured on and cost nothing anywhere else.
+// RT_TRIM_*: build-time overrides, for measuring a wider choice (profiles/fixed_path_items.txt has the ones tried).
+#ifndef RT_TRIM_PATH
+#define RT_TRIM_PATH(WPW, GROUND, NG) ((NG) > 0)       // prologue (layout, cost words, frame index), light base, facing margin
+#endif
+#ifndef RT_TRIM_RAY
+#define RT_TRIM_RAY(WPW, GROUND, NG) ((NG) > 0)        // pixel_P: px as a scalar value
+#endif
+#ifndef RT_TRIM_STORE
+#define RT_TRIM_STORE(WPW, GROUND, NG) ((NG) > 0)      // store_pixel: the straight-line clip, one address stepped from plane to plane
+#endif
+#ifndef RT_TRIM_RESOLVE
+#define RT_TRIM_RESOLVE false                          // aa_resolve_kernel's store_pixel
+#endif
+
 // What a kernel's scene queries are compiled for, as one type handed down from the kernel (render_kernel's MODE, GROUND and NG;
 // guides_kernel's MODE) through sample and trace_bounce to closest_hit, any_hit, any_hit_masks, plane_code and plane_count: a
 // further axis of specialisation is a member here, not a parameter of each of them.
@@ -567,6 +586,7 @@ struct Query {
     static constexpr int MODE = MODE_;          // 0: wave-uniform cull; 1: the same without float64 sphere records in LDS (sphere_hot); 2: lane-owned traversal of a clustered scene, also without; 3: 2 with re-derived park addresses (Park3)
     static constexpr bool GROUND = GROUND_;     // the one plane is the z-up ground (below)
     static constexpr int NG = NG_;              // > 0: the scene's spheres are that many cull groups of four (cull_mask_t)
+    template <int WPW> static constexpr bool trim() { return RT_TRIM_PATH(WPW, GROUND_, NG_); }   // (above)
     static_assert(NG == 0 || (NG <= 2 && GROUND && MODE == 0), "small-scene kernels are wave-uniform (MODE 0) ground-plane kernels of one or two cull groups");
 };
 
@@ -1586,7 +1606,8 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
         dpark.set(d);
         RT_MARK(4);
 
-        const double *lt = lds.recs() + plb + opaque(P) * PL_STRIDE;
+        constexpr bool TRIM = Q::template trim<WGT / 64>();                  // (RT_TRIM_PATH)
+        const double *lt = lds.recs() + plb + ((TRIM && Q::GROUND) ? 1 : opaque(P)) * PL_STRIDE;   // (TRIM: plane_count, not the opaque argument)
         if constexpr (MS::lit) {
         // LIT (rt_set_scene_lighting, mi355rt.h): light m has a colour e_m and the hit a Blinn-Phong highlight of strength spec / n
         // and exponent shin.  e_m, spec / n and log2(shin) come from the scene's lighting block in global memory (lit_doubles): e_m
@@ -1675,7 +1696,11 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 }
             }
         }
-        } else
+        } else {
+        // (TRIM: the certificate's margin, read from the argument segment once per trace and held in a scalar pair across the
+        // lights: read where it is used, it is loaded again, and waited for, on every light)
+        double ftau = p.facing_tau;
+        if constexpr (FACING_SKIP && TRIM) asm volatile("" : "+s"(ftau));
         for (int m = 0; m < L; ++m) {                                         // :86-102
             const double *g = lt + m * LT_STRIDE;
             const V3 v{g[0] - Pt.x, g[1] - Pt.y, g[2] - Pt.z};
@@ -1686,8 +1711,8 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 // per lane with a material table, folded into facing_tau by the host otherwise), no lane's k will be positive, so
                 // the wave goes to the next light without normalising v.  One lane without the certificate: today's code for all.
                 bool cert;
-                if constexpr (MS::mat) cert = rt_facing_certified_lamb(v.x, v.y, v.z, N.x, N.y, N.z, p.facing_tau, lamb);
-                else cert = rt_facing_certified(v.x, v.y, v.z, N.x, N.y, N.z, p.facing_tau);
+                if constexpr (MS::mat) cert = rt_facing_certified_lamb(v.x, v.y, v.z, N.x, N.y, N.z, TRIM ? ftau : p.facing_tau, lamb);
+                else cert = rt_facing_certified(v.x, v.y, v.z, N.x, N.y, N.z, TRIM ? ftau : p.facing_tau);
                 if (__builtin_amdgcn_ballot_w64(!cert) == 0ull) {
                     cnt.shadow(true, false);
                     RT_MARK(5);
@@ -1705,6 +1730,7 @@ __device__ __forceinline__ void trace_bounce(const Lds &lds, const KParams &p, b
                 const bool occluded = any_hit<Q>(lds, p, Pt, Ld, 1 + m, self, anchor != 0 || p.lanes_primary);
                 if (!occluded) lambert_add(k, V3{1.0, 1.0, 1.0});
             }
+        }
         }
         d = dpark.get();
         if constexpr (MS::scat) {
@@ -1768,13 +1794,19 @@ __device__ __forceinline__ V3 sample(const Lds &lds, const KParams &p, bool aliv
     return acc.get();
 }
 
+template <bool SCALAR_PX = false>
 __device__ __forceinline__ V3 pixel_P(const KParams &p, int x, int y)
 {
+    // (SCALAR_PX, RT_TRIM_RAY: p.px as a value in scalar registers.  Left as a read of the argument segment, it is merged with the
+    // table's first load into one per-lane flat load through a select of the two addresses — a vector memory round trip at the
+    // head of every wave)
+    double px = p.px;
+    if constexpr (SCALAR_PX) asm("" : "+s"(px));
     if (p.pixel_loc) {                                                        // kernels.py:19
         const size_t wh = (size_t)p.w * p.h, o = (size_t)x * p.h + y;
         return V3{p.pixel_loc[o], p.pixel_loc[wh + o], p.pixel_loc[2 * wh + o]};
     }
-    return V3{p.px, (double)x * p.dy + p.y0, (double)y * p.dz + p.z0};        // scene/camera.py:18-26
+    return V3{SCALAR_PX ? px : p.px, (double)x * p.dy + p.y0, (double)y * p.dz + p.z0};   // scene/camera.py:18-26
 }
 
 // Lattice point (i, j) of the half-pixel lattice of the closed-form grid: even indices are pixel centres, odd ones
@@ -1824,10 +1856,15 @@ __device__ __forceinline__ void lens_ray(const KParams &p, unsigned x, unsigned 
 
 // kernels.py:69-73: clip and store one pixel; off = (x - x0) h + y.
 // fo = element offset of this launch's frame (rt_render_sequence; 0 for a single frame)
+// TRIM (RT_TRIM_STORE): the clip as straight-line code (clip_color), and the three planes through one per-lane address stepped by
+// the scalar stride; else the clip with its branches (clip_color_branches: the same bytes) and every plane's base formed with
+// 64-bit scalar adds before the lane's offset goes on.
+template <bool TRIM = false>
 __device__ __forceinline__ void store_pixel(const KParams &p, long long off, long long fo, double R, double G, double B)
 {
     if (p.out_u8) {                                                           // common.py:60-63
-        const uint8_t r8 = clip_color(R), g8 = clip_color(G), b8 = clip_color(B);
+        const uint8_t r8 = TRIM ? clip_color(R) : clip_color_branches(R), g8 = TRIM ? clip_color(G) : clip_color_branches(G),
+                      b8 = TRIM ? clip_color(B) : clip_color_branches(B);
         const uint8_t c1 = p.u8_rgb ? g8 : b8, c2 = p.u8_rgb ? b8 : g8;
         uint8_t *o8 = p.out_u8 + fo;
         if (p.u8_hwc) {                                                       // image layout: row y, column x, 3 bytes
@@ -1835,16 +1872,30 @@ __device__ __forceinline__ void store_pixel(const KParams &p, long long off, lon
             uint8_t *px = o8 + (yy * p.plane_stride + xr) * 3;
             px[0] = r8; px[1] = c1; px[2] = c2;
         } else {
-            o8[off] = r8;
-            o8[p.plane_stride + off] = c1;
-            o8[2 * p.plane_stride + off] = c2;
+            if constexpr (TRIM) {
+                uint8_t *q = o8 + off;
+                q[0] = r8;
+                q += p.plane_stride; q[0] = c1;
+                q += p.plane_stride; q[0] = c2;
+            } else {
+                o8[off] = r8;
+                o8[p.plane_stride + off] = c1;
+                o8[2 * p.plane_stride + off] = c2;
+            }
         }
     }
     if (p.out_f32) {
         float *o32 = p.out_f32 + fo;
-        o32[off] = (float)R;
-        o32[p.plane_stride + off] = (float)G;
-        o32[2 * p.plane_stride + off] = (float)B;
+        if constexpr (TRIM) {
+            float *q = o32 + off;
+            q[0] = (float)R;
+            q += p.plane_stride; q[0] = (float)G;
+            q += p.plane_stride; q[0] = (float)B;
+        } else {
+            o32[off] = (float)R;
+            o32[p.plane_stride + off] = (float)G;
+            o32[2 * p.plane_stride + off] = (float)B;
+        }
     }
 }
 
@@ -1995,6 +2046,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     constexpr bool M2 = MODE >= 2;
     constexpr bool NOREC = MODE >= 1;
     using Q = Query<MODE, GROUND, NG>;        // what the scene queries below are compiled for
+    constexpr bool TRIM = Q::template trim<WPW>(), TRIM_RAY = RT_TRIM_RAY(WPW, GROUND, NG), TRIM_STORE = RT_TRIM_STORE(WPW, GROUND, NG);   // (above Query)
     static_assert(NG == 0 || (WPW == 2 && !COUNT && F == Family::PLAIN), "small-scene twins: of PLAIN's two-wave kernels");
     constexpr bool MAT = has_mat(F), SCAT = has_scat(F), SOFT = has_soft(F), LENS = has_lens(F), TEX = has_tex(F);
     const int nrec = (int)lds_doubles(NOREC ? 0 : p.S, p.P, p.L);             // MODE 1 / 2: planes and lights only (sphere_hot)
@@ -2002,7 +2054,16 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     double *accum = lds_raw + nrec;
     int *offw = reinterpret_cast<int *>(accum + lds_slots(AA, PARK, M2, F) * WG_THREADS);
     float *sph32 = reinterpret_cast<float *>(offw + lds_offset_words(PARK, WG_THREADS));
-    const TableLayout tl = table_layout(p.S, p.NC, p.anchors, p.P);
+    // TRIM: two-wave kernels are sent flat scenes only and are MODE 0 (rt_plan.h: plan_launch), so of the layout they read `tab`
+    // and `total` alone: flat_layout forms those two in a few 32-bit scalar instructions (a small-scene twin: `tab` is a constant
+    // and `total` one multiply-add of L) where table_layout's 64-bit chain through p.NC costs every workgroup about 45.  The
+    // cluster and colour tables are empty there and their pointers never read (Lds::NC is the constant 0).
+    static_assert(WPW != 2 || MODE == 0, "two-wave kernels: wave-uniform cull over float64 records (flat_layout)");
+    TableLayout tl;
+    if constexpr (WPW == 2 && TRIM) {
+        const FlatLayout fl = flat_layout(NG, p.S, p.L, p.anchors);
+        tl = TableLayout{fl.tab, 0, 0, 0, 0, 0, fl.total, fl.total, 0, 0};
+    } else tl = table_layout(p.S, p.NC, p.anchors, p.P);
     // the lane-owned kernels leave the clusters' origin-form spheres in global memory: with anchored tables in place the only
     // rays without an anchor are the reflections, and those test boxes
     const bool LANES = MODE >= 2 && p.anchors > 0;
@@ -2012,7 +2073,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     float *cbox = sph32 + tl.cbox;                     // NCp boxes
     const size_t ntab = MODE == 1 ? tl.total_col : (LANES ? tl.total_lanes : tl.total);
     unsigned *wgstat = reinterpret_cast<unsigned *>(sph32 + ntab);   // {cycles, waves done}
-    if (threadIdx.x == 0) { wgstat[0] = 0u; wgstat[1] = 0u; }
+    if ((!TRIM || p.cost) && threadIdx.x == 0) { wgstat[0] = 0u; wgstat[1] = 0u; }   // (read by measuring launches only, below: TRIM leaves them alone in the others)
     {   // stage the packed scene and its float32 cull tables once per workgroup: two straight copies.  (The tables
         // used to be computed here, by every workgroup: 3 % of the frame's VALU instructions and a second barrier.)
         for (int i = threadIdx.x; i < nrec; i += WG_THREADS) lds_raw[i] = rec_src[i];
@@ -2059,8 +2120,9 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
     // the 128-byte lines they share are completed in that L2 within microseconds.
     int bid = (int)blockIdx.x;
     const unsigned *ord = p.order;
+    int frame = 0;                                                            // of a multi-frame launch (TRIM: one scalar register until the store)
     if (p.nframes > 1) {
-        const int frame = div_by(bid, p.bpf, p.bpf_magic, p.bpf_shift);
+        frame = div_by(bid, p.bpf, p.bpf_magic, p.bpf_shift);
         bid -= frame * p.bpf;
         if (ord && frame < p.nframes - 1) ord += p.seq_offset;
     }
@@ -2107,7 +2169,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         unsigned key = 0u, lkey = 0u;
         if constexpr (SCAT) key = LAT ? scatter_key((unsigned)xc, (unsigned)yc, 0u, sseed) : scatter_key(2u * xc, 2u * yc, 0u, sseed);
         if constexpr (SOFT) lkey = LAT ? soft_key((unsigned)xc, (unsigned)yc, 0u, sseed) : soft_key(2u * xc, 2u * yc, 0u, sseed);
-        const V3 P0 = LAT ? lattice_P(p, xc, yc) : pixel_P(p, xc, yc);
+        const V3 P0 = LAT ? lattice_P(p, xc, yc) : pixel_P<TRIM_RAY>(p, xc, yc);
         V3 ro = o, rd;
         if constexpr (LENS) lens_ray(p, LAT ? (unsigned)xc : 2u * xc, LAT ? (unsigned)yc : 2u * yc, 0u, P0, ro, rd);
         else rd = primary_dir(p, P0);
@@ -2126,7 +2188,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
         Park3<PARK && !M2, WG_THREADS> taps(lds.acc, 2);
 #pragma unroll 1
         for (int tap = 0; tap < ntaps; ++tap) {
-            const V3 Pp = pixel_P(p, xc, yc);                                 // :19
+            const V3 Pp = pixel_P<TRIM_RAY>(p, xc, yc);                       // :19
             V3 Pt = Pp;
             unsigned key = 0u, lkey = 0u;
             unsigned lx = 2u * xc, ly = 2u * yc;                              // LENS: the sample's (X, Y)
@@ -2140,7 +2202,7 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             } else if (tap) {
                 const int k = tap - 1;
                 const int ddx = (int)((NBX >> (2 * k)) & 3u) - 1, ddy = (int)((NBY >> (2 * k)) & 3u) - 1;
-                const V3 Pn = pixel_P(p, interior ? x + ddx : xc, interior ? y + ddy : yc);
+                const V3 Pn = pixel_P<TRIM_RAY>(p, interior ? x + ddx : xc, interior ? y + ddy : yc);
                 Pt = V3{0.5 * Pp.x + 0.5 * Pn.x, 0.5 * Pp.y + 0.5 * Pn.y, 0.5 * Pp.z + 0.5 * Pn.z};   // :43-50
                 if constexpr (SCAT) key = scatter_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
                 if constexpr (SOFT) lkey = soft_key((unsigned)(2 * xc + ddx), (unsigned)(2 * yc + ddy), 0u, sseed);
@@ -2172,9 +2234,12 @@ __global__ __launch_bounds__(64 * WPW, MODE >= 2 ? RT_W_LANES : (AA ? (PARK ? RT
             double *q = p.out_f64 + off * 3;
             q[0] = R; q[1] = G; q[2] = B;
         } else {
-            // the frame index is formed again here (a wave-uniform division) instead of being carried through the trace
-            const long long fo = opaque(p.nframes) > 1 ? (long long)div_by((int)blockIdx.x, p.bpf, p.bpf_magic, p.bpf_shift) * p.frame_stride : 0ll;
-            store_pixel(p, off, fo, R, G, B);
+            // the frame index is formed again here (a wave-uniform division) instead of being carried through the trace, except
+            // by the TRIM kernels, which have the scalar register for it (frame 0 of a single-frame launch: offset 0)
+            long long fo;
+            if constexpr (TRIM) fo = (long long)frame * p.frame_stride;
+            else fo = opaque(p.nframes) > 1 ? (long long)div_by((int)blockIdx.x, p.bpf, p.bpf_magic, p.bpf_shift) * p.frame_stride : 0ll;
+            store_pixel<TRIM_STORE>(p, off, fo, R, G, B);
         }
     }
 #ifdef RT_REGION_STATS
@@ -2227,7 +2292,7 @@ __global__ __launch_bounds__(256) void aa_resolve_kernel(const KParams p)
         }
         R = R / 9; G = G / 9; B = B / 9;                                      // :63-65
     }
-    store_pixel(p, idx, 0ll, R, G, B);
+    store_pixel<RT_TRIM_RESOLVE>(p, idx, 0ll, R, G, B);
 }
 
 // Builds the dispatch order of the following launches from the block costs a measuring launch stored: longest-first WITHIN

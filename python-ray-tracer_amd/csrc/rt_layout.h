@@ -123,6 +123,19 @@ RT_HD inline TableLayout table_layout(int S, int NC, int anchors, int P = 0)
     t.total_col = o;
     return t;
 }
+// What a two-wave render kernel reads of that layout, in 32-bit arithmetic.  The plan sends two-wave workgroups flat scenes only
+// (rt_plan.h: plan_launch, NC == 0) and they are MODE 0 kernels, so the cluster tables and the colour table are empty and never
+// read: what is left is `tab` and `total`, and total == total_lanes.  ng > 0 (the small-scene twins; rt_plan.h: cull_groups
+// guarantees pad4(S) == 4 ng and anchors == L + 1): `tab` is a constant and `total` one multiply-add of L.
+// tests/algo/fixed_path_check.cpp compares both forms with table_layout over every scene the twins are sent, and the plan's
+// case grid for a clustered scene in a two-wave shape.
+struct FlatLayout { unsigned tab, total; };
+RT_HD inline FlatLayout flat_layout(int ng, int S, int L, int anchors)
+{
+    if (ng > 0) return FlatLayout{16u * (unsigned)ng, 16u * (unsigned)ng * (unsigned)L + 32u * (unsigned)ng};
+    const unsigned Sp = (unsigned)pad4(S);
+    return FlatLayout{4u * Sp, 4u * Sp + (unsigned)anchors * Sp * CULL_STRIDE};
+}
 RT_HD inline size_t table_floats(int S, int NC, int anchors, bool lanes = false, bool col = false, int P = 0)
 {
     const TableLayout t = table_layout(S, NC, anchors, P);

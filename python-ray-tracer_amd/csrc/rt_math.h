@@ -183,13 +183,44 @@ RT_MATH_FN unsigned lens_key(unsigned x, unsigned y, unsigned s, unsigned seed) 
 RT_MATH_FN double hash_unit(unsigned key, unsigned t) { return (double)(scatter_hash(key, t) >> 8) * 0x1p-23 + (0x1p-24 - 1.0); }
 
 // common.py:52-57: min(max(0, int(round(c))), 255), round half to even (v_rndne_f64).
-RT_MATH_FN uint8_t clip_color(double c)
+// Straight-line: round, clamp to [0, 255] as a double, convert; four instructions a channel.  The same byte for every double as the
+// rule spelled out with its tests (NaN -> 0, c <= -0.5 -> 0, c >= 255.5 -> 255, else rint(c) clamped to 0..255): that rule clamps
+// the rounded value as an int, this clamps it before the conversion, which then sees an integer of 0..255 whatever c was, a NaN
+// included (clamp_lo sends it to 0).  c in (-0.5, 0) rounds to -0: either zero converts to 0.
+// clamp_lo(c, k) is c > k ? c : k, so a NaN goes to k; clamp_hi(c, k) the same with <.  On the device they are fmax and fmin
+// (v_max_f64 / v_min_f64, one instruction each: rint's result is never a signalling NaN, so the backend adds no canonicalize, as
+// it does when it clamps first).  A host's libm may hand a signalling NaN through rint and fmax, and the conversion to int must
+// never see one, so the host spells the selects out.
+// tests/algo/fixed_path_check.cpp compares the host's text with the rule on the specials, every tie and 10^7 bit patterns;
+// tests/test_gpu_fixed_path.py puts a frame's values on the ties and bounds on the device.
+RT_MATH_FN double clamp_lo(double c, double k)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_fmax(c, k);
+#else
+    return c > k ? c : k;
+#endif
+}
+RT_MATH_FN double clamp_hi(double c, double k)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_fmin(c, k);
+#else
+    return c < k ? c : k;
+#endif
+}
+// The rule as written, with its branches: what every kernel but the trimmed ones (rt_device.h: RT_TRIM_STORE) keeps compiling.
+RT_MATH_FN uint8_t clip_color_branches(double c)
 {
     if (!(c == c)) return 0;
     if (c <= -0.5) return 0;
     if (c >= 255.5) return 255;
     const int i = (int)__builtin_rint(c);
     return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
+}
+RT_MATH_FN uint8_t clip_color(double c)
+{
+    return (uint8_t)(int)clamp_hi(clamp_lo(__builtin_rint(c), 0.0), 255.0);
 }
 
 }  // namespace rt

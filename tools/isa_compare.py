@@ -21,6 +21,8 @@ REFR twin, each SOFT kernel next to its SCAT twin, each LENS and LENS_SOFT kerne
 texture kernel (TEX_SCAT, TEX_SOFT, TEX_LENS, TEX_LENS_SOFT) next to its SCAT, SOFT, LENS and LENS_SOFT twin, and each lighting
 kernel (LIT_SCAT, LIT_SOFT, LIT_LENS, LIT_LENS_SOFT) next to its texture twin, and each sky kernel (SKY_SCAT, SKY_SOFT, SKY_LENS,
 SKY_LENS_SOFT) next to its lighting twin.  Exit status 1 if any kernel differs.
+--tree-asm FILE does the same for the working tree's build.  Under every kernel that differs stands what the change did to its
+line count and resources, and at the end the kernels that now have more scratch, more spills or fewer waves per SIMD.
 --base-asm FILE takes REV's build from an earlier run instead of building it again (a build is minutes of one core): FILE is REV's
 rt_kernel.gfx950.s and FILE.log what its `make asm` wrote to stderr (the resource-usage remarks).  What is compared is the same.
 """
@@ -120,6 +122,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", default="HEAD")
     ap.add_argument("--base-asm", help="REV's rt_kernel.gfx950.s from an earlier build; its stderr in FILE.log")
+    ap.add_argument("--tree-asm", help="the working tree's rt_kernel.gfx950.s from an earlier build; its stderr in FILE.log")
     ap.add_argument("--twins", action="store_true")
     a = ap.parse_args()
     if a.base_asm:
@@ -129,13 +132,15 @@ def main():
             arch = subprocess.run(["git", "-C", REPO, "archive", a.base, CSRC, "include"], capture_output=True, check=True).stdout
             subprocess.run(["tar", "-x", "-C", tmp], input=arch, check=True)
             base_asm, base_log = build(tmp)
-    new_asm, new_log = build(REPO)
+    new_asm, new_log = (open(a.tree_asm).read(), open(a.tree_asm + ".log").read()) if a.tree_asm else build(REPO)
     bf, nf = functions(base_asm), functions(new_asm)
     br, nr = resources(base_log), resources(new_log)
     new_by_key = {}
     for n in nf:
         new_by_key[key(n)] = n
     bad = 0
+    worse = []                                  # kernels with more scratch, more spills or fewer waves per SIMD than in the base
+    WATCH = (("ScratchSize [bytes/lane]", 1), ("VGPRs Spill", 1), ("SGPRs Spill", 1), ("Occupancy [waves/SIMD]", -1))
     for b in sorted(bf):
         n = new_by_key.get(key(b))
         if n is None:
@@ -146,11 +151,19 @@ def main():
         print(f"{'same' if same_isa and same_res else 'DIFF'}  isa={'=' if same_isa else '!'} res={'=' if same_res else '!'} "
               f"{len(bf[b].splitlines()):6d} lines  {key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}{counts}")
         bad += not (same_isa and same_res)
+        if not (same_isa and same_res):         # what the change did to the kernel's resources
+            rb, rn = br.get(b, {}), nr.get(n, {})
+            cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "Occupancy [waves/SIMD]")
+            print(f"      {len(nf[n].splitlines()) - len(bf[b].splitlines()):+5d} lines  " +
+                  "  ".join(f"{c.split(' [')[0]} {rb.get(c, '?')}->{rn.get(c, '?')}" for c in cols))
+            if any(sign * (int(rn.get(c, 0)) - int(rb.get(c, 0))) > 0 for c, sign in WATCH):
+                worse.append(f"{key(b)[0]}{' ' + key(b)[1] if key(b)[1] else ''}")
     base_keys = {key(b) for b in bf}
     new = sorted(n for n in nf if key(n) not in base_keys)
     for n in new:
         print(f"NEW   {key(n)[0]} {key(n)[1]}")
     print(f"{len(bf)} kernels of {a.base} compared, {bad} differ; {len(new)} new")
+    print(f"kernels with more scratch, more spills or fewer waves per SIMD than in {a.base}: {len(worse)}" + "".join(f"\n  {w}" for w in worse))
     if a.twins:
         cols = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "LDS Size [bytes/block]")
         for fam, twin, title in TWINS:
