@@ -12,6 +12,7 @@ import torch
 from conftest import GOLDEN, raygen_closed_form
 import closest_hit_scenes as chs
 import bloom_cases as bc
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_film import same_bits
 
 from python_ray_tracer_amd import Film, bloom as B, film as F
@@ -87,12 +88,6 @@ class _Buffers:
             assert (wk[:, npx:] == WORK_FILL).all(), "the pad of work was written"
             outs.append(np.ascontiguousarray(got[:, :npx]).reshape(3, self.ws, self.h))
         return outs
-
-
-@pytest.fixture
-def rend(renderer):
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -11,8 +11,7 @@ import pytest
 
 from conftest import raygen_closed_form
 import closest_hit_scenes as chs
-from test_gpu_features_vs_oracle import _same
-from test_gpu_launch_plan import KERNEL_LINE
+from feature_gpu import KERNEL_LINE, same as _same
 
 from python_ray_tracer_amd import _lib as L
 

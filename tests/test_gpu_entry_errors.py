@@ -235,7 +235,7 @@ NPX = W * H
 FILM_INPUTS = ("sum", "sq", "guides", "hist", "hist_sq", "hist_len", "hist_guides")
 FILM_OUTPUTS = ("out", "work", "out_sq", "out_len", "o8", "o32", "acc_sum", "acc_sq")
 SENTINEL = 0xA5
-BIG = 1 << 14                          # BIG * BIG = 2^28 pixels: above RT_FILM_MAX_PIXELS, inside rt_set_raygen's limits
+BIG_SIDE = 1 << 14                     # BIG_SIDE^2 = 2^28 pixels: above RT_FILM_MAX_PIXELS, inside rt_set_raygen's limits
 HWC_RESOLVE = "RT_FLAG_U8_HWC re-uses out_stride as the image row pitch: resolve the float32 buffer in a separate call"
 NAN, INF = float("nan"), float("inf")
 
@@ -367,7 +367,7 @@ def _film_refusals(L, mk, e, b):
     add("resolve", "d_sum NULL and tone NULL", "d_sum is NULL", d_sum=None, t=None)
     add("resolve", "ws 0", area, ws=0)
     add("resolve", "h 0", area, h=0)
-    add("resolve", "ws*h 2^28", area, ws=BIG, h=BIG)
+    add("resolve", "ws*h 2^28", area, ws=BIG_SIDE, h=BIG_SIDE)
     add("resolve", "n 0", "n < 1", n=0)
     add("resolve", "ws 0 and n 0", area, ws=0, n=0)
     for x in (0.0, -1.0, INF, NAN):
@@ -416,7 +416,7 @@ def _film_refusals(L, mk, e, b):
         add(ent, "levels 7 and normal_shin 3", "levels outside 0..6", s=st(levels=7, normal_shin=3))
         add(ent, "demodulate 2", "demodulate must be 0 or 1", s=st(demodulate=2))
         add(ent, "demodulate -1", "demodulate must be 0 or 1", s=st(demodulate=-1))
-        for what, kw in (("ws 0", dict(ws=0)), ("h 0", dict(h=0)), ("ws*h 2^28", dict(ws=BIG, h=BIG))):
+        for what, kw in (("ws 0", dict(ws=0)), ("h 0", dict(h=0)), ("ws*h 2^28", dict(ws=BIG_SIDE, h=BIG_SIDE))):
             add(ent, what, area, **kw)
         add(ent, "demodulate 2 and ws 0", "demodulate must be 0 or 1", s=st(demodulate=2), ws=0)
         add(ent, "ws 0 and short strides", area, ws=0, out_stride=-1)
@@ -548,22 +548,22 @@ def test_film_refusals_and_their_texts():
             for o, R in ((np.array([0.0, NAN, 0.0]), CAM_R), (CAM_O, np.diag([1.0, INF, 1.0]))):
                 r.set_camera(o, R)
                 assert (e[ent](), _last_error(r)) == (BAD_ARG, f"{name}: a camera entry is not finite"), (ent, o)
-                r.set_raygen(BIG, BIG, *RAYGEN)
+                r.set_raygen(BIG_SIDE, BIG_SIDE, *RAYGEN)
                 assert (e[ent](), _last_error(r)) == (BAD_ARG, f"{name}: a camera entry is not finite"), (ent, o)
                 r.set_raygen(W, H, *RAYGEN)
             r.set_camera(CAM_O, CAM_R)
         # a frame above RT_FILM_MAX_PIXELS; two at once: with strides far below it, and with an output that is an input
-        r.set_raygen(BIG, BIG, *RAYGEN)
+        r.set_raygen(BIG_SIDE, BIG_SIDE, *RAYGEN)
         for ent, name in (("temporal", "rt_film_temporal"), ("temporal_moments", "rt_film_temporal_moments")):
             assert (e[ent](), _last_error(r)) == (BAD_ARG, f"{name}: w*h above RT_FILM_MAX_PIXELS"), ent
             assert (e[ent](d_out=bufs["sum"]), _last_error(r)) == (BAD_ARG, f"{name}: w*h above RT_FILM_MAX_PIXELS"), ent
             assert (e[ent](t=mk["tp"](prev_origin=(NAN, 0.0, 0.0))), _last_error(r)) == (BAD_ARG, f"{name}: a camera entry is not finite"), ent
         above = "(x1-x0)*h above RT_FILM_MAX_PIXELS"
-        assert (e["moments"](x1=BIG), _last_error(r)) == (BAD_ARG, f"rt_film_accumulate_moments: {above}")
-        assert (e["moments"](x1=BIG, d_sq=bufs["acc_sum"]), _last_error(r)) == (
+        assert (e["moments"](x1=BIG_SIDE), _last_error(r)) == (BAD_ARG, f"rt_film_accumulate_moments: {above}")
+        assert (e["moments"](x1=BIG_SIDE, d_sq=bufs["acc_sum"]), _last_error(r)) == (
             BAD_ARG, "rt_film_accumulate_moments: d_sq and d_sum must be buffers of their own")
         lib, good = r._lib, r.params(0.1, 0.7, 0.5, 2)
-        assert (lib.rt_film_accumulate(r._ctx, C.byref(good), 0, BIG, 1, 1, C.c_void_p(bufs["acc_sum"]), NPX, None), _last_error(r)) == (
+        assert (lib.rt_film_accumulate(r._ctx, C.byref(good), 0, BIG_SIDE, 1, 1, C.c_void_p(bufs["acc_sum"]), NPX, None), _last_error(r)) == (
             BAD_ARG, f"rt_film_accumulate: {above}")
         r.set_raygen(W, H, *RAYGEN)
         # the grid: dy or dz 0

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, raygen_closed_form
-from test_gpu_features_vs_oracle import _same
+from feature_gpu import same as _same
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402

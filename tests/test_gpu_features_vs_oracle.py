@@ -9,136 +9,37 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import REPO, load_frame, raygen_closed_form
+from conftest import REPO, raygen_closed_form
 from closest_hit_scenes import size_limit_arrays
+from feature_gpu import (ENVS, ENVS_IDS, ENVS_KEYS, FAMILIES, IGNORED, MODES, family_scene, oracle_modes, same as _same,
+                         same_pixels as _same_pixels)
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-IGNORED = (7.0, -3.0, 2.0)        # rt_params amb, lamb, refl: a material scene must not read them
-AA_PER_PIXEL = 32
-
-
-def _golden(name):
-    return np.load(os.path.join(REPO, "tests", "golden", f"{name}.npz"))
-
-
-def _same(what, u8, f32, r8, r32):
-    bad8 = (u8 != r8).any(axis=0)
-    assert not bad8.any(), f"{what}: {int(bad8.sum())} of {bad8.size} pixels differ (uint8), e.g. {np.argwhere(bad8)[:4].tolist()}"
-    bad = (f32.view(np.uint32) != r32.view(np.uint32)).any(axis=0)
-    assert not bad.any(), f"{what}: float32 differs at {int(bad.sum())} pixels, e.g. {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same_pixels(what, co, u8, f32, r8, r64, x0=0):
-    """Sampled pixels co (n,2) of frames (3,w,h) against orc.render_pixels' (n,3) outputs."""
-    g8 = u8[:, co[:, 0] - x0, co[:, 1]].T
-    g32 = f32[:, co[:, 0] - x0, co[:, 1]].T
-    e32 = r64.astype(np.float32)
-    bad = (g8 != r8).any(axis=1) | (g32.view(np.uint32) != e32.view(np.uint32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(co)} pixels differ, e.g. {co[bad][:4].tolist()}"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Every feature kernel.  The (scene, environment) pairs of test_gpu_materials.py's table: between them the dispatcher picks every
+# Every feature kernel.  The (scene, environment) pairs of feature_gpu.ENVS: between them the dispatcher picks every
 # instantiation it can pick (flat or clustered, sphere count, LDS image, parked or register state): all 22 MAT kernels and 14 of
-# each REFR, SCAT, SOFT and LENS set (a kernel trace of this module shows the 92).  The parked wave-uniform variants of the
-# latter (MODE 0 and 1) need 13 to 19 per-thread slots, over the parking budget for any scene: the dispatcher never picks them.
-# Each family runs on the scene with a seeded random table, in AA modes 0, 1 (the lattice and RT_FLAG_AA_PER_PIXEL) and 2, and
-# every setting is compared with the oracle.
-_ENVS = [
-    ("c5_s256_d8_sub96", {}),
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_PARK": "0"}),
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000"}),
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"}),
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000"}),
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"}),
-    ("aa_48_d2", {}),
-    ("tiny", {}),
-    ("aa_48_d2", {"MI355RT_WPW2_MAX_IMAGE": "0"}),
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "30"}),
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000", "MI355RT_WPW2_MAX_IMAGE": "0"}),
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000", "MI355RT_WPW2_MAX_IMAGE": "10000000"}),
-]
-_ENV_KEYS = sorted({k for _, e in _ENVS for k in e})
-_FAMILIES = ("mat", "refr", "scat", "soft", "lens_scat", "lens_soft")
-_MODES = ((0, 0, 0), (1, 0, 0), (1, AA_PER_PIXEL, 0), (2, 0, 2))
-_W, _H, _DEPTH, _SEED = 160, 96, 3, 5
-
-
-def _source(case):
-    if case == "tiny":
-        g = load_frame("aa_48_d2")
-        return dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                    cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-    return load_frame(case) if case.startswith("aa_") else _golden(f"lens_{case}")
-
-
-def _family_scene(family, case):
-    """The scene of `case` with a random table for `family` (seeded by both): ids over every row, ids above 7 included.  For
-    scatter, "tiny" gets the floor of aa_48_d2: a lone convex sphere never sees its own reflections, so a rough one renders
-    the bytes of a mirror."""
-    src = dict(_source(case))
-    if case == "tiny" and family == "scat":
-        src["planes"] = load_frame("aa_48_d2")["planes"][:, :1]
-    S, P, NL = src["spheres"].shape[1], src["planes"].shape[1], src["lights"].shape[1]
-    rng = np.random.default_rng(_FAMILIES.index(family) * 101 + len(case))
-    M = 12 if family == "mat" else 5               # (5 rows of 5 or 6 columns leave the LDS room for the parked variants)
-    table = np.zeros((M, 6))
-    table[:, 0] = rng.uniform(-0.05, 0.12, M)
-    table[:, 1] = rng.uniform(0.2, 0.9, M)
-    table[:, 2] = rng.uniform(0.0, 0.9, M)
-    table[:, 4] = 1.0
-    if family != "mat":                            # glass rows 1 and 4 (ior 1.5 and 0.8), rough rows 2 and 3
-        table[1::3, 2], table[1::3, 3], table[1::3, 4] = 0.0, rng.uniform(0.5, 1.0, 2), (1.5, 0.8)
-    if family not in ("mat", "refr"):
-        table[2:4, 5] = (0.3, 1.0)
-    ncols = 3 if family == "mat" else (5 if family == "refr" else 6)
-    table = table[:, :ncols]
-    sid = rng.integers(0, M, S).astype(np.int32)
-    first = [1, 2, 9, 11] if family == "mat" else ([2, 1, 3, 4] if family == "scat" else [1, 2, 3, 4])
-    sid[: min(S, 4)] = first[: min(S, 4)]          # (the one sphere of "tiny")
-    pid = rng.integers(0, M, P).astype(np.int32)
-    radius = np.zeros(NL, np.float32)
-    if family in ("soft", "lens_soft"):
-        radius[:] = np.array([0.5, 0.0, 0.3] * NL, np.float32)[:NL]
-        radius[0] = 0.5
-    lens = (0.08, 3.0) if family.startswith("lens") else (0.0, 1.0)
-    return dict(kind=family, w=_W, h=_H, spheres=src["spheres"], lights=src["lights"], planes=src["planes"], table=table, sid=sid,
-                pid=pid, radius=radius, n=2, lens=lens, cam_origin=np.asarray(src["cam_origin"], np.float64),
-                cam_rot=np.asarray(src["cam_rot"], np.float64), fov=float(src["fov"]),
-                raygen=raygen_closed_form(_W, _H, float(src["fov"])), depth=_DEPTH, aa=0, flags_aa=0, spp=1, hseed=_SEED, typed=0)
-
-
-_FEATURE_OF = dict(mat="materials", refr="glass", scat="rough", soft="soft", lens_scat="lens", lens_soft="lens")
-_ORACLE = {}
-
-
-def _oracle_modes(oracle, family, case):
-    key = (family, case)
-    if key not in _ORACLE:
-        sc = _family_scene(family, case)
-        outs = [fs.oracle_frame(oracle, {**sc, "aa": aa, "spp": max(spp, 1)}) for aa, _, spp in _MODES]
-        off = fs.oracle_frame(oracle, fs.strip(sc, _FEATURE_OF[family]))[0]
-        _ORACLE[key] = (outs, int((off != outs[0][0]).any(axis=0).sum()))
-    return _ORACLE[key]
-
-
-@pytest.mark.parametrize("case, env", _ENVS, ids=[f"{c}-{'-'.join(f'{k[8:]}={v}' for k, v in e.items()) or 'default'}" for c, e in _ENVS])
-@pytest.mark.parametrize("family", _FAMILIES)
+# each REFR, SCAT, SOFT and LENS set (a kernel trace of this module shows the 92).  Each family runs on the scene with a seeded
+# random table (feature_gpu.family_scene), in AA modes 0, 1 (the lattice and RT_FLAG_AA_PER_PIXEL) and 2, and every setting is
+# compared with the oracle.
+@pytest.mark.parametrize("case, env", ENVS, ids=ENVS_IDS)
+@pytest.mark.parametrize("family", FAMILIES)
 def test_every_feature_kernel_vs_oracle(monkeypatch, oracle, family, case, env):
     import python_ray_tracer_amd as pkg
-    for k in _ENV_KEYS:
+    for k in ENVS_KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    sc = _family_scene(family, case)
-    refs, n_live = _oracle_modes(oracle, family, case)
+    sc = family_scene(family, case)
+    refs, n_live = oracle_modes(oracle, family, case)
     assert n_live >= 20, f"{family} on {case}: the feature changes only {n_live} pixels"
     r = pkg.Renderer(0)
     try:
-        for (aa, flags, spp), (r8, r32) in zip(_MODES, refs):
+        for (aa, flags, spp), (r8, r32) in zip(MODES, refs):
             u8, f32 = fs.gpu_frame(r, {**sc, "aa": aa, "flags_aa": flags, "spp": max(spp, 1)})
             _same(f"{family} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
     finally:
@@ -284,7 +185,7 @@ def test_lens_on_a_non_planar_explicit_grid(renderer, oracle, aa, flags):
         renderer.set_camera(sc["cam_origin"], sc["cam_rot"])
         renderer.set_lens(*sc["lens"])
         renderer.set_pixel_loc(grid)
-        u8, f32 = renderer.render(*IGNORED, 3, aa, u8=True, f32=True, flags=flags, seed=sc["hseed"])
+        u8, f32 = renderer.render(*IGNORED.values(), 3, aa, u8=True, f32=True, flags=flags, seed=sc["hseed"])
     finally:
         renderer.set_lens(0.0, 1.0)
     _same(f"explicit non-planar grid aa={aa}", u8, f32, ref["u8"], ref["f32"])
@@ -322,7 +223,7 @@ def test_render_device_and_odd_column_slabs(renderer, oracle):
     w, h = sc["w"], sc["h"]
     try:
         fs.gpu_frame(renderer, sc)
-        p = renderer.params(*IGNORED, sc["depth"], sc["aa"], spp=sc["spp"], seed=sc["hseed"])
+        p = renderer.params(*IGNORED.values(), sc["depth"], sc["aa"], spp=sc["spp"], seed=sc["hseed"])
         d8, d32 = renderer.malloc(3 * w * h), renderer.malloc(12 * w * h)
         try:
             renderer.render_device(p, 0, w, d8, d32, w * h)
@@ -337,7 +238,7 @@ def test_render_device_and_odd_column_slabs(renderer, oracle):
         for aa, spp in ((1, 1), (2, 3), (0, 1)):
             for x0, x1 in ((1, 52), (7, 20), (33, 53), (17, 18)):
                 s8, s32 = fs.oracle_frame(oracle, {**sc, "aa": aa, "spp": spp}, x0=x0, x1=x1)
-                u8, f32 = renderer.render(*IGNORED, sc["depth"], aa, x0=x0, x1=x1, u8=True, f32=True, spp=spp, seed=sc["hseed"])
+                u8, f32 = renderer.render(*IGNORED.values(), sc["depth"], aa, x0=x0, x1=x1, u8=True, f32=True, spp=spp, seed=sc["hseed"])
                 _same(f"slab [{x0}, {x1}) aa={aa}", u8, f32, s8[:, x0:x1], s32[:, x0:x1])
     finally:
         renderer.set_lens(0.0, 1.0)
@@ -357,7 +258,7 @@ def test_render_sequence_per_frame_cameras_with_a_lens(renderer, oracle):
     cams = np.array(cams)
     try:
         fs.gpu_frame(renderer, sc)
-        p = renderer.params(*IGNORED, sc["depth"], 0, seed=sc["hseed"])
+        p = renderer.params(*IGNORED.values(), sc["depth"], 0, seed=sc["hseed"])
         npx = w * h
         d8, d32 = renderer.malloc(n * 3 * npx), renderer.malloc(n * 12 * npx)
         try:

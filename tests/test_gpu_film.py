@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO, load_frame, raygen_closed_form
+from feature_gpu import IGNORED
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_film import EDGE_SUMS, random_sums, same_bits
 from test_oracle_features import _records
 
@@ -19,15 +21,7 @@ from python_ray_tracer_amd import Film, film as F
 from python_ray_tracer_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
 PASS_COUNTS = (1, 2, 4, 5, 9)                  # below a batch of four, one batch, one batch plus one, two batches plus one
-
-
-@pytest.fixture
-def rend(renderer):
-    """The session's renderer, with the pinhole camera restored afterwards (later tests share it)."""
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

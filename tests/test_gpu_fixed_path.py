@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import load_frame, raygen_closed_form
+from feature_gpu import grid as _grid
 import ground_plane_scenes as gps
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +29,6 @@ def _renderer(monkeypatch, small):
     if not small:
         monkeypatch.setenv("MI355RT_SMALL_SCENE", "0")
     return pkg.Renderer(0)
-
-
-def _grid(w, h, fov):
-    """The closed-form grid written out as a pixel table: value = index * step + start, as the kernel forms it."""
-    px, y0, dy, z0, dz = raygen_closed_form(w, h, fov)
-    g = np.empty((3, w, h))
-    g[0] = px
-    g[1] = (np.arange(w) * dy + y0)[:, None]
-    g[2] = (np.arange(h) * dz + z0)[None, :]
-    return g
 
 
 def _reference(oracle, name, sc, w, h, amb, lamb, refl, depth, pixel_loc=None):
@@ -98,7 +89,7 @@ def test_clip_on_its_ties_and_bounds(monkeypatch, oracle, small):
 @SMALL
 def test_clip_of_nan_rays(monkeypatch, oracle, small):
     sc, w, h = _clip_scene(), 37, 29
-    grid = _grid(w, h, sc["fov"])
+    grid = _grid(w, h, raygen_closed_form(w, h, sc["fov"]))
     grid[:, 11:21, 9:19] = 0.0                    # zero vectors: NaN directions (crosses tiles; waves with both kinds of lanes)
     with _renderer(monkeypatch, small) as r:
         r.set_scene(sc["spheres"], sc["lights"], sc["planes"])
@@ -115,7 +106,7 @@ def test_clip_of_nan_rays(monkeypatch, oracle, small):
 def test_pixel_table_and_closed_form(monkeypatch, oracle, small, S):
     sc, w, h = dict(gps.fixture_scene("odd_37x29"), spheres=_spheres(S)), 37, 29
     amb, lamb, refl = sc["shade"]
-    grid = _grid(w, h, sc["fov"])
+    grid = _grid(w, h, raygen_closed_form(w, h, sc["fov"]))
     with _renderer(monkeypatch, small) as r:
         r.set_scene(sc["spheres"], sc["lights"], sc["planes"])
         r.set_camera(sc["cam_origin"], sc["cam_rot"])

@@ -3,16 +3,15 @@ python-ray-tracer_amd/csrc/rt_plan.h on the CPU), taken by their coordinates, re
 render_kernel<...> line the library logs must name the fixture row's family and shape.  This ties the wiring (the KERNELS table's
 indexing, the MI355RT_* knobs reaching the plan) to the table; what the kernels compute is the other GPU tests' business."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, raygen_closed_form
+from feature_gpu import KERNEL_LINE
 from test_algorithms import LAUNCH_PLAN_COORDS, LAUNCH_PLAN_ROW
 
 pytestmark = pytest.mark.gpu
-KERNEL_LINE = re.compile(r"mi355rt: render_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \(rt::Family\)(\d+)>")
 
 PLAIN, MAT, SCAT, SOFT = 0, 1, 3, 4                                      # rt::Family numbers
 KNOB_ENV = ("MI355RT_CLUSTER_MINS", "MI355RT_LANES_MINS", "MI355RT_F32_RECORDS", "MI355RT_LANES_PARK", "MI355RT_WPW2_MAX_IMAGE",

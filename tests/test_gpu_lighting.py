@@ -3,35 +3,18 @@
 lights without a spec row, an unused spec row, doubled lights with lamb halved, a black light, a red light), frames in flight
 across a scene change, column slabs, the error paths and the example."""
 import ctypes as C
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import REPO, load_frame, raygen_closed_form
-# The environment table and helpers are those of the lens and texture tests, imported and not copied, so that the lighting
-# kernels are held to the same tables as their twins.
+# The environment table and helpers are feature_gpu's, so that the lighting kernels are held to the same tables as their twins.
+from feature_gpu import (BIG, IGNORED, KERNEL_LINE, LIT_FAMILIES, TEX_FAMILIES, check as _check, column_slabs_are_the_full_frame,
+                         family_kernels_same_bytes, fixture_lens, frames as _frames, kw as _kw, lit_scene, render_host as _render_host,
+                         run_example, same_frames as _same_frames, set_view, walk_entry_points)
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_lighting import CASES, fixture_textures, load_lighting
-from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
-from test_gpu_textures import _scene_textures
-from test_gpu_features_vs_oracle import _same
-from test_gpu_lit_vs_oracle import kernel_table_refs
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
-BIG = ("c4_s64_d5_sub32", "c5_s256_d8_sub96")
-TEX_FAMILIES = {"scatter": 7, "area_lights": 8, "lens": 9, "both": 10}      # rt::Family numbers of the texture kernels
-LIT_FAMILIES = {"scatter": 11, "area_lights": 12, "lens": 13, "both": 14}   # and of their lighting twins
-KERNEL_LINE = re.compile(r"mi355rt: render_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \(rt::Family\)(\d+)>")
-
-
-@pytest.fixture
-def rend(renderer):
-    """The session's renderer, with the pinhole camera restored afterwards (later tests share it)."""
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 def _mats(g, cols=8):
@@ -45,40 +28,7 @@ def _scene(r, g, materials=None, light_rgb="fixture", **kw):
 
 
 def _setup(r, g, explicit=False, **kw):
-    w, h = int(g["w"]), int(g["h"])
-    _scene(r, g, **kw)
-    r.set_camera(g["cam_origin"], g["cam_rot"])
-    r.set_lens(float(g["aperture"]), float(g["focus_distance"]))
-    rg = raygen_closed_form(w, h, float(g["fov"]))
-    if explicit:
-        r.set_pixel_loc(_grid(w, h, rg))
-    else:
-        r.set_raygen(w, h, *rg)
-    return w, h
-
-
-def _kw(g):
-    return dict(spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]))
-
-
-def _pick(g, a, x0=0):
-    co = g["coords"]
-    return a[:, co[:, 0] - x0, co[:, 1]].T
-
-
-def _check(g, u8, f32=None, what="", x0=0, key="u8"):
-    got = _pick(g, u8, x0)
-    assert np.array_equal(got, g[key]), f"{what}: {(got != g[key]).any(axis=1).sum()} of {len(got)} pixels differ (uint8)"
-    if f32 is not None:
-        a, e = _pick(g, f32, x0), g["rgb64"].astype(np.float32)
-        bad = (a.view(np.uint32) != e.view(np.uint32)).any(axis=1)
-        assert not bad.any(), (f"{what}: float32 differs at {bad.sum()} of {len(bad)} pixels, e.g. {g['coords'][bad][:4].tolist()}: "
-                               f"{a[bad][:4].tolist()} != {e[bad][:4].tolist()}")
-
-
-def _render_host(r, g, flags=0, aa=None, **kw):
-    return r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]) if aa is None else aa, u8=True,
-                    f32=True, flags=flags, **{**_kw(g), **kw})
+    return set_view(r, g, lambda r, g: _scene(r, g, **kw), lens=fixture_lens(g), explicit=explicit)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -86,149 +36,27 @@ def _render_host(r, g, flags=0, aa=None, **kw):
 
 @pytest.mark.parametrize("case", CASES)
 def test_fixture_every_entry_point(rend, case):
-    renderer = rend
     g = load_lighting(case)
-    w, h = _setup(renderer, g)
-    u8, f32 = _render_host(renderer, g)
-    _check(g, u8, f32, "rt_render")
-    big = case in BIG
-    p = renderer.params(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), **_kw(g))
-    n, npx = 3, w * h
-    d8 = renderer.malloc(n * 3 * npx)
-    d32 = None if big else renderer.malloc(n * 12 * npx)
-    try:
-        renderer.render_device(p, 0, w, d8, d32, npx)
-        renderer.sync()
-        got = np.empty((3, w, h), np.uint8)
-        renderer.d2h(got, d8)
-        g32 = None
-        if d32 is not None:
-            g32 = np.empty((3, w, h), np.float32)
-            renderer.d2h(g32, d32)
-        _check(g, got, g32, "rt_render_device")
-        for cams in (None, np.tile(np.concatenate([g["cam_origin"], g["cam_rot"].reshape(9)]), (n, 1))):
-            renderer.h2d(d8, np.zeros(n * 3 * npx, np.uint8))
-            renderer.render_sequence(p, 0, w, n, d8, d32, npx, 3 * npx, cams, None, 2)   # (cameras=None: launches of 2 frames)
-            renderer.sync()
-            seq = np.empty((n, 3, w, h), np.uint8)
-            renderer.d2h(seq, d8)
-            s32 = None
-            if d32 is not None:
-                s32 = np.empty((n, 3, w, h), np.float32)
-                renderer.d2h(s32, d32)
-            for i in range(n):
-                _check(g, seq[i], None if s32 is None else s32[i], f"rt_render_sequence cameras={cams is not None} frame {i}")
-    finally:
-        renderer.free(d8)
-        if d32 is not None:
-            renderer.free(d32)
-    if not big:                                                 # rt_render_begin / rt_render_end
-        o8, o32 = np.empty((3, w, h), np.uint8), np.empty((3, w, h), np.float32)
-        renderer.render_begin(0, IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), o8, o32, **_kw(g))
-        renderer.render_end(0)
-        _check(g, o8, o32, "rt_render_begin/end")
-    if int(g["aa"]) != 2 and case != "c5_s256_d8_sub96":       # stochastic needs the closed-form grid
-        _setup(renderer, g, explicit=True)
-        u8, f32 = _render_host(renderer, g)
-        _check(g, u8, f32, "explicit pixel_loc")
-    if int(g["aa"]) == 1:                                       # the per-pixel 9-tap kernel on the closed-form grid
-        from python_ray_tracer_amd import _lib as L
-        _setup(renderer, g)
-        u8, f32 = _render_host(renderer, g, flags=L.RT_FLAG_AA_PER_PIXEL)
-        _check(g, u8, f32, "RT_FLAG_AA_PER_PIXEL")
-    _setup(renderer, g, materials=_mats(g, 6), light_rgb=None)  # white lights, no spec column: the fixture's u8_plain
-    u8, _ = _render_host(renderer, g)
+    walk_entry_points(rend, g, _setup, case in BIG, cameras=True, begin_end=True, explicit=case != BIG[1])
+    _setup(rend, g, materials=_mats(g, 6), light_rgb=None)      # white lights, no spec column: the fixture's u8_plain
+    u8, _ = _render_host(rend, g)
     _check(g, u8, None, "white lights and no spec", key="u8_plain")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# One scene, the same bytes from every lighting kernel.  test_gpu_lens.py's environment table x the four AA modes reaches all 14
-# shapes of a family; MI355RT_LOG_KERNELS makes every launch name its kernel on stderr.
-
-def _glossy(table):
-    """The 6-column table with spec and shin columns: every row glossy, the exponents 1 .. 1024 in turn."""
-    t = np.zeros((len(table), 8))
-    t[:, :6] = table
-    t[:, 6] = [40.0 + 30.0 * (i % 4) for i in range(len(table))]
-    t[:, 7] = [float(1 << ((3 * i + 1) % 11)) for i in range(len(table))]
-    return t
-
+# One scene, the same bytes from every lighting kernel (feature_gpu.family_kernels_same_bytes): glossy rows and coloured lights
+# against the same textured scene with neither.
 
 @pytest.mark.parametrize("kind", list(LIT_FAMILIES))
 def test_every_lighting_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
-    import python_ray_tracer_amd as pkg
-    from python_ray_tracer_amd import _lib as L
-    soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
-    w, h = 64, 64
-    modes = ((0, 0, 0), (1, 0, 0), (1, L.RT_FLAG_AA_PER_PIXEL, 0), (2, 0, 2))
-    seen = set()
-    for case in _VARIANTS:
-        if case == "tiny":
-            g = load_frame("aa_48_d2")
-            src = dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                       cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-        else:
-            src = load_frame(case) if case.startswith("aa_") else load_lighting(case)
-        S, P, NL = src["spheres"].shape[1], src["planes"].shape[1], src["lights"].shape[1]
-        table, sid, pid = _lens_materials(S, P)
-        mats = (_glossy(table), sid, pid)
-        radius = np.array([0.5, 0.0, 0.3][:NL], np.float32) if soft else np.zeros(NL, np.float32)
-        rgb = np.array([[1.0, 0.7, 0.4], [0.3, 0.5, 1.5], [0.0, 0.3, 0.2]][:NL], np.float32)
-        tex = _scene_textures(src) if case != "tiny" else None    # (tiny: a lit scene without textures)
-        rg = raygen_closed_form(w, h, float(src["fov"]))
-        refs = kernel_table_refs(oracle, src, w, h, modes, "lighting", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
-                                 textures=tex, light_rgb=rgb)
-        first = plain = None
-        for env in _VARIANTS[case]:
-            for k in _VARIANT_KEYS:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            monkeypatch.setenv("MI355RT_LOG_KERNELS", "1")
-            r = pkg.Renderer(0)
-            try:
-                r.set_camera(src["cam_origin"], src["cam_rot"])
-                r.set_raygen(w, h, *rg)
-                r.set_lens(0.08 if lens else 0.0, 3.0)
-                if plain is None:
-                    r.set_scene(src["spheres"], src["lights"], src["planes"], materials=(table, sid, pid), light_radius=radius,
-                                shadow_samples=2, textures=tex)
-                    plain = r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, 0, u8=True, seed=3)[0]
-                    capfd.readouterr()
-                r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats, light_radius=radius, shadow_samples=2,
-                            textures=tex, light_rgb=rgb)
-                outs = [r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, aa, u8=True, f32=True, flags=flags, spp=spp, seed=3)
-                        for aa, flags, spp in modes]
-            finally:
-                r.close()
-            names = KERNEL_LINE.findall(capfd.readouterr().err)
-            assert names and all(int(n[6]) == LIT_FAMILIES[kind] for n in names), (case, env, names)
-            seen.update(names)
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
-                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
-            if first is None:
-                first = outs
-                assert all(u8.any() for u8, _ in outs)
-                assert not np.array_equal(outs[0][0], plain), case      # (the lighting shows)
-                continue
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, first):
-                assert u8.tobytes() == r8.tobytes(), (case, env, aa, flags)
-                assert f32.tobytes() == r32.tobytes(), (case, env, aa, flags)
-    print(f"{kind}: {len(seen)} kernels: {sorted(seen)}")
-    assert len(seen) == 14, f"{kind}: {len(seen)} of the family's 14 kernels ran: {sorted(seen)}"
+    def scenes(src, case):
+        matte, mats, tex, rgb = lit_scene(src, case)            # (tiny: a lit scene without textures)
+        return dict(materials=matte, textures=tex), dict(materials=mats, textures=tex, light_rgb=rgb)
+    family_kernels_same_bytes(monkeypatch, capfd, oracle, kind, LIT_FAMILIES, load_lighting, (64, 64), "lighting", scenes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fixtures against restated scenes
-
-def _frames(r, g):
-    return [_render_host(r, g, aa=aa, spp=spp) for aa, spp in ((0, 0), (1, 0), (2, 2))]
-
-
-def _same_frames(a, b, what):
-    for i, ((u8, f32), (r8, r32)) in enumerate(zip(a, b)):
-        assert u8.tobytes() == r8.tobytes() and f32.tobytes() == r32.tobytes(), (what, i)
-
 
 @pytest.mark.parametrize("case", ["default_64_d4", "everything_48_d4"])
 def test_white_lights_without_spec_is_rt_set_scene_textures(monkeypatch, capfd, case):
@@ -347,12 +175,7 @@ def test_frames_in_flight_keep_their_lights(rend):
 
 @pytest.mark.parametrize("aa, spp", [(0, 0), (1, 0), (2, 2)])
 def test_column_slab_is_the_full_frame(rend, aa, spp):
-    g = load_lighting("everything_48_d4")
-    _setup(rend, g)
-    full8, full32 = _render_host(rend, g, aa=aa, spp=spp)
-    for x0, x1 in ((9, 41), (33, 48)):
-        u8, f32 = _render_host(rend, g, aa=aa, spp=spp, x0=x0, x1=x1)
-        assert np.array_equal(u8, full8[:, x0:x1]) and np.array_equal(f32, full32[:, x0:x1]), (x0, x1)
+    column_slabs_are_the_full_frame(rend, load_lighting("everything_48_d4"), _setup, aa, spp, ((9, 41), (33, 48)))
 
 
 def test_errors_leave_the_previous_scene(rend):
@@ -423,14 +246,5 @@ def test_errors_leave_the_previous_scene(rend):
 
 def test_example_with_lights_writes_png(tmp_path):
     """examples/render_png.py --lights: coloured lights and highlights."""
-    import subprocess
-    from PIL import Image
-    outs = {}
-    for flag in (["--glass"], ["--lights"]):
-        out = str(tmp_path / f"{flag[0].strip('-')}.png")
-        log = subprocess.check_output([sys.executable, os.path.join(REPO, "examples", "render_png.py"), "--size", "64x64", "--depth", "3",
-                                       "--frames", "2", "--out", out] + flag, text=True)
-        assert "wrote" in log
-        outs[flag[0]] = np.asarray(Image.open(out))
-    a, b = outs.values()
+    a, b = (run_example(str(tmp_path / f"{flag.strip('-')}.png"), "64x64", 3, 2, flag)[1] for flag in ("--glass", "--lights"))
     assert b.shape == (64, 64, 3) and b.any() and not np.array_equal(a, b)

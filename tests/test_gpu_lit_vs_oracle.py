@@ -1,7 +1,7 @@
 """The texture, lighting and sky kernels (rt_device.h TEX, LIT and SKY) against the CPU oracle's restatement of include/mi355rt.h
 (oracle/rt_oracle.c orc_render_ex, pinned to every pixel of the texture_*, lighting_* and sky_* fixtures by
-tests/test_oracle_features.py): uint8 and float32, bit for bit, no tolerance anywhere.  kernel_table_refs() gives the three
-test_every_{texture,lighting,sky}_kernel_same_bytes tests the oracle's frames of their scenes; below it, seeded random scenes of
+tests/test_oracle_features.py): uint8 and float32, bit for bit, no tolerance anywhere.  (feature_gpu.kernel_table_refs gives the
+three test_every_{texture,lighting,sky}_kernel_same_bytes tests the oracle's frames of their scenes.)  Here: seeded random scenes of
 tools/feature_scenes.draw_lit, the edges of the texel lookup, of the two lighting terms and of sky(d), and every entry point.
 Each case first checks, on the oracle alone, that its feature is live: the oracle's frame changes when the feature is stripped
 (at least 20 pixels in the kernel table, at least 5 elsewhere)."""
@@ -12,31 +12,13 @@ import numpy as np
 import pytest
 
 from conftest import REPO, raygen_closed_form
-from test_gpu_features_vs_oracle import IGNORED, _same, _same_pixels
+from feature_gpu import IGNORED, same as _same, same_pixels as _same_pixels
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SHININESS = fs.SHININESS
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# The kernel tables of test_gpu_textures.py, test_gpu_lighting.py and test_gpu_sky.py: the oracle's frames of their scenes.
-
-def kernel_table_refs(oracle, src, w, h, modes, feature, *, materials, radius, lens, depth=3, seed=3, textures=None, light_rgb=None,
-                      sky=None):
-    """[(uint8, float32)] per (aa, flags, spp) of `modes`: the oracle's frames of the scene the kernel tables render, after
-    asserting that `feature` ("textures", "lighting" or "sky") changes at least 20 pixels of the first."""
-    sc = dict(kind="table", w=w, h=h, spheres=src["spheres"], lights=src["lights"], planes=src["planes"], table=materials[0],
-              sid=materials[1], pid=materials[2], radius=radius, n=2, lens=lens, cam_origin=np.asarray(src["cam_origin"], np.float64),
-              cam_rot=np.asarray(src["cam_rot"], np.float64), raygen=raygen_closed_form(w, h, float(src["fov"])), depth=depth, aa=0,
-              flags_aa=0, spp=1, hseed=seed, typed=0, textures=textures, light_rgb=light_rgb, sky=sky)
-    refs = [fs.oracle_frame(oracle, {**sc, "aa": aa, "spp": max(spp, 1)}) for aa, _, spp in modes]
-    off = fs.oracle_frame(oracle, fs.strip(sc, feature))[0]
-    n_live = int((off != refs[0][0]).any(axis=0).sum())
-    assert n_live >= 20, f"{feature} changes only {n_live} pixels of the oracle's frame"
-    return refs
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -490,7 +472,7 @@ def test_lit_render_device_and_odd_column_slabs(renderer, oracle):
     w, h = sc["w"], sc["h"]
     try:
         fs.gpu_frame(renderer, sc)
-        p = renderer.params(*IGNORED, sc["depth"], sc["aa"], spp=sc["spp"], seed=sc["hseed"])
+        p = renderer.params(*IGNORED.values(), sc["depth"], sc["aa"], spp=sc["spp"], seed=sc["hseed"])
         d8, d32 = renderer.malloc(3 * w * h), renderer.malloc(12 * w * h)
         try:
             renderer.render_device(p, 0, w, d8, d32, w * h)
@@ -505,7 +487,7 @@ def test_lit_render_device_and_odd_column_slabs(renderer, oracle):
         for aa, spp in ((1, 1), (2, 3), (0, 1)):
             for x0, x1 in ((1, 52), (7, 20), (33, 53), (17, 18)):
                 s8, s32 = fs.oracle_frame(oracle, {**sc, "aa": aa, "spp": spp}, x0=x0, x1=x1)
-                u8, f32 = renderer.render(*IGNORED, sc["depth"], aa, x0=x0, x1=x1, u8=True, f32=True, spp=spp, seed=sc["hseed"])
+                u8, f32 = renderer.render(*IGNORED.values(), sc["depth"], aa, x0=x0, x1=x1, u8=True, f32=True, spp=spp, seed=sc["hseed"])
                 _same(f"slab [{x0}, {x1}) aa={aa}", u8, f32, s8[:, x0:x1], s32[:, x0:x1])
     finally:
         renderer.set_lens(0.0, 1.0)
@@ -542,7 +524,7 @@ def test_lit_render_sequence_per_frame_cameras(renderer, oracle):
         assert i == 0 or (refs[i][0] != refs[i - 1][0]).any(axis=0).sum() >= 20
     try:
         fs.gpu_frame(renderer, sc)
-        p = renderer.params(*IGNORED, sc["depth"], 0, seed=sc["hseed"])
+        p = renderer.params(*IGNORED.values(), sc["depth"], 0, seed=sc["hseed"])
         npx = w * h
         d8, d32 = renderer.malloc(n * 3 * npx), renderer.malloc(n * 12 * npx)
         try:

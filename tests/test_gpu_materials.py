@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_frame, raygen_closed_form
+from feature_gpu import (BIG, ENVS, ENVS_IDS, IGNORED, MODES, aim, check as _check, kw as _kw, large_fixtures_on_a_traversal,
+                         render_host as _render_host, run_example, set_view, variant_source, walk_entry_points)
 from test_materials import material_cases
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
 
 
 def _load(case):
@@ -22,112 +23,21 @@ def _mats(g):
     return g["materials"], g["sphere_material"], g["plane_material"]
 
 
-def _grid(w, h, rg):
-    px, y0, dy, z0, dz = rg
-    grid = np.empty((3, w, h))
-    grid[0] = px
-    grid[1] = (np.arange(w) * dy + y0)[:, None]
-    grid[2] = (np.arange(h) * dz + z0)[None, :]
-    return grid
-
-
 def _setup(r, g, explicit=False, materials=True):
-    w, h = int(g["w"]), int(g["h"])
-    r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g) if materials else None)
-    r.set_camera(g["cam_origin"], g["cam_rot"])
-    rg = raygen_closed_form(w, h, float(g["fov"]))
-    if explicit:
-        r.set_pixel_loc(_grid(w, h, rg))
-    else:
-        r.set_raygen(w, h, *rg)
-    return w, h
-
-
-def _kw(g):
-    return dict(spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]) if "seed" in g else 1)
-
-
-def _check(g, u8, f32=None, what=""):
-    co = g["coords"]
-    got = u8[:, co[:, 0], co[:, 1]].T
-    assert np.array_equal(got, g["u8"]), f"{what}: {(got != g['u8']).any(axis=1).sum()} of {len(co)} pixels differ (uint8)"
-    if f32 is not None:
-        # bit for bit, the sign of zero included (the reference's ambient term is 0.0 + amb*col)
-        assert np.array_equal(f32[:, co[:, 0], co[:, 1]].T.view(np.uint32), g["rgb64"].astype(np.float32).view(np.uint32)), \
-            f"{what}: float32 differs"
-
-
-def _render_host(r, g, flags=0):
-    return r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), u8=True, f32=True, flags=flags, **_kw(g))
-
-
-BIG = ("c4_s64_d5_sub32", "c5_s256_d8_sub96")
+    return set_view(r, g, lambda r, g: r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g) if materials else None),
+                    explicit=explicit)
 
 
 @pytest.mark.parametrize("case", material_cases())
 def test_fixture_every_entry_point(renderer, case):
-    g = _load(case)
-    w, h = _setup(renderer, g)
-    u8, f32 = _render_host(renderer, g)
-    _check(g, u8, f32, "rt_render")
-    # rt_render_device and rt_render_sequence (n = 3, every frame) into device buffers; float32 too for the small frames
-    big = case in BIG
-    p = renderer.params(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), **_kw(g))
-    n, npx = 3, w * h
-    d8 = renderer.malloc(n * 3 * npx)
-    d32 = None if big else renderer.malloc(n * 12 * npx)
-    try:
-        renderer.render_device(p, 0, w, d8, d32, npx)
-        renderer.sync()
-        got = np.empty((3, w, h), np.uint8)
-        renderer.d2h(got, d8)
-        g32 = None
-        if d32 is not None:
-            g32 = np.empty((3, w, h), np.float32)
-            renderer.d2h(g32, d32)
-        _check(g, got, g32, "rt_render_device")
-        renderer.h2d(d8, np.zeros(n * 3 * npx, np.uint8))
-        renderer.render_sequence(p, 0, w, n, d8, d32, npx, 3 * npx, None, None, 2)
-        renderer.sync()
-        seq = np.empty((n, 3, w, h), np.uint8)
-        renderer.d2h(seq, d8)
-        s32 = None
-        if d32 is not None:
-            s32 = np.empty((n, 3, w, h), np.float32)
-            renderer.d2h(s32, d32)
-        for i in range(n):
-            _check(g, seq[i], None if s32 is None else s32[i], f"rt_render_sequence frame {i}")
-    finally:
-        renderer.free(d8)
-        if d32 is not None:
-            renderer.free(d32)
-    if int(g["aa"]) != 2 and case != "c5_s256_d8_sub96":       # stochastic needs the closed-form grid
-        _setup(renderer, g, explicit=True)
-        u8, f32 = _render_host(renderer, g)
-        _check(g, u8, f32, "explicit pixel_loc")
-    if int(g["aa"]) == 1:                                       # the per-pixel 9-tap kernel on the closed-form grid
-        from python_ray_tracer_amd import _lib as L
-        _setup(renderer, g)
-        u8, f32 = _render_host(renderer, g, flags=L.RT_FLAG_AA_PER_PIXEL)
-        _check(g, u8, f32, "RT_FLAG_AA_PER_PIXEL")
+    walk_entry_points(renderer, _load(case), _setup, case in BIG, cameras=False, begin_end=False, explicit=case != BIG[1])
 
 
 @pytest.mark.parametrize("lanes_mins, records", [("30", "1"), ("30", "0"), ("100000", "1"), ("100000", "0")])
 def test_large_fixtures_on_every_traversal(monkeypatch, lanes_mins, records):
     """The 64- and 256-sphere fixtures (clustered scenes) on the lane-owned (MI355RT_LANES_MINS=30) and the wave-uniform
     (=100000) kernels, with and without float64 sphere records in LDS (MI355RT_F32_RECORDS)."""
-    import python_ray_tracer_amd as pkg
-    monkeypatch.setenv("MI355RT_LANES_MINS", lanes_mins)
-    monkeypatch.setenv("MI355RT_F32_RECORDS", records)
-    r = pkg.Renderer(0)
-    try:
-        for case in BIG:
-            g = _load(case)
-            _setup(r, g)
-            u8, f32 = _render_host(r, g)
-            _check(g, u8, f32, f"{case} LANES_MINS={lanes_mins} F32_RECORDS={records}")
-    finally:
-        r.close()
+    large_fixtures_on_a_traversal(monkeypatch, lanes_mins, records, _load, _setup)
 
 
 @pytest.mark.parametrize("case", ["default_128_d3", "fov70_48", "tilted_planes_48", "inside_sphere_32", "aa_48_d2", "stoch_48_spp4"])
@@ -249,17 +159,10 @@ def test_errors_keep_the_previous_scene(renderer):
 
 def test_example_with_materials_writes_png(tmp_path):
     """examples/render_png.py --materials: a mirror floor under matte spheres, through the Renderer API."""
-    import subprocess
-    import sys
-    from PIL import Image
-    from conftest import REPO
     outs = {}
     for flag in ([], ["--materials"]):
-        out = str(tmp_path / f"r{len(flag)}.png")
-        log = subprocess.check_output([sys.executable, os.path.join(REPO, "examples", "render_png.py"), "--size", "160x96", "--depth", "2",
-                                       "--frames", "3", "--out", out] + flag, text=True)
-        assert "wrote" in log and f"materials={bool(flag)}" in log
-        outs[bool(flag)] = np.asarray(Image.open(out))
+        log, outs[bool(flag)] = run_example(str(tmp_path / f"r{len(flag)}.png"), "160x96", 2, 3, *flag)
+        assert f"materials={bool(flag)}" in log
     assert outs[True].shape == (96, 160, 3) and outs[True].any() and not np.array_equal(outs[True], outs[False])
 
 
@@ -304,48 +207,20 @@ def test_negative_ambient_keeps_the_sign_of_zero(renderer, oracle):
     assert np.array_equal(f32.view(np.uint32), ref.view(np.uint32))
 
 
-# Every material kernel (22 instantiations, rt_device.h MAT) is launched by one of these: the dispatcher's choice follows the
-# scene (flat or clustered, sphere count, LDS image) and the overrides read at rt_create.  A uniform power-of-two table must
-# render the global path's bytes in each of them: plain, the AA lattice, per-pixel AA and stochastic.
-_VARIANTS = [
-    ("c5_s256_d8_sub96", {}),                                                 # lane-owned, parked (MODE 2 / 3)
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_PARK": "0"}),                        # lane-owned, registers
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000"}),                    # wave-uniform clusters, 4 waves, parked (MODE 1)
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"}),   # ... MODE 0
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000"}),                   # 4 waves, registers (MODE 1)
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"}),  # ... MODE 0
-    ("aa_48_d2", {}),                                                         # flat, 2 waves, parked (AA: registers)
-    ("tiny", {}),                                                             # one sphere, one light: 2 waves, parked AA too
-    ("aa_48_d2", {"MI355RT_WPW2_MAX_IMAGE": "0"}),                            # flat, 4 waves, parked (MODE 0)
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "30"}),                        # lane-owned on a small image: parked (MODE 2 / 3)
-    ("c4_s64_d5_sub32", {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000",
-                         "MI355RT_WPW2_MAX_IMAGE": "0"}),                     # flat 64 spheres, 4 waves (MODE 1 where it saves LDS)
-    ("c5_s256_d8_sub96", {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000",
-                          "MI355RT_WPW2_MAX_IMAGE": "10000000"}),             # flat 256 spheres, 2 waves, registers
-]
-
-
-@pytest.mark.parametrize("case, env", _VARIANTS, ids=[f"{c}-{'-'.join(f'{k[8:]}={v}' for k, v in e.items()) or 'default'}" for c, e in _VARIANTS])
+# Every material kernel (22 instantiations, rt_device.h MAT) is launched by one row of feature_gpu.ENVS.  A uniform power-of-two
+# table must render the global path's bytes in each of them: plain, the AA lattice, per-pixel AA and stochastic.
+@pytest.mark.parametrize("case, env", ENVS, ids=ENVS_IDS)
 def test_every_material_kernel_is_the_global_path(monkeypatch, case, env):
     import python_ray_tracer_amd as pkg
-    from python_ray_tracer_amd import _lib as L
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    if case == "tiny":
-        g = load_frame("aa_48_d2")
-        src = dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                   cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-    else:
-        src = load_frame(case) if case.startswith("aa_") else _load(case)
+    src = variant_source(case, _load)
     S, P = src["spheres"].shape[1], src["planes"].shape[1]
-    w, h = 160, 96
-    rg = raygen_closed_form(w, h, float(src["fov"]))
     amb, lamb, refl = 0.05, 0.6, 0.5
     r = pkg.Renderer(0)
     try:
-        r.set_camera(src["cam_origin"], src["cam_rot"])
-        r.set_raygen(w, h, *rg)
-        for aa, flags, spp in ((0, 0, 0), (1, 0, 0), (1, L.RT_FLAG_AA_PER_PIXEL, 0), (2, 0, 2)):
+        aim(r, src, 160, 96)
+        for aa, flags, spp in MODES:
             r.set_scene(src["spheres"], src["lights"], src["planes"])
             ref8, ref32 = r.render(amb, lamb, refl, 2, aa, u8=True, f32=True, flags=flags, spp=spp, seed=3)
             r.set_scene(src["spheres"], src["lights"], src["planes"],

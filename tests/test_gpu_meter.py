@@ -11,6 +11,7 @@ import torch
 
 from conftest import GOLDEN, raygen_closed_form
 import meter_cases as mc
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_film import same_bits
 
 from python_ray_tracer_amd import Film, bloom as B, film as F, meter as M
@@ -65,12 +66,6 @@ class _Meter:
         words = _read(self.r, self.d_words, (BINS + 2,), np.uint64)
         assert words[0] == WORD and words[-1] == WORD, "a word beside the counts was written"
         return words[1:-1]
-
-
-@pytest.fixture
-def rend(renderer):
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

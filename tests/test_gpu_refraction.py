@@ -8,12 +8,12 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_frame, raygen_closed_form
+from conftest import GOLDEN, load_frame
+from feature_gpu import (BIG, IGNORED, VARIANTS, aim, check as _check, large_fixtures_on_a_traversal, render_host as _render_host,
+                         render_modes, run_example, same_as_first, set_view, variant_renderers, variant_source, walk_entry_points)
 from test_refraction import refraction_cases
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
-BIG = ("c4_s64_d5_sub32", "c5_s256_d8_sub96")
 
 
 def _load(case):
@@ -24,123 +24,20 @@ def _mats(g):
     return g["materials"], g["sphere_material"], g["plane_material"]
 
 
-def _grid(w, h, rg):
-    px, y0, dy, z0, dz = rg
-    grid = np.empty((3, w, h))
-    grid[0] = px
-    grid[1] = (np.arange(w) * dy + y0)[:, None]
-    grid[2] = (np.arange(h) * dz + z0)[None, :]
-    return grid
-
-
 def _setup(r, g, explicit=False):
-    w, h = int(g["w"]), int(g["h"])
-    r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g))
-    r.set_camera(g["cam_origin"], g["cam_rot"])
-    rg = raygen_closed_form(w, h, float(g["fov"]))
-    if explicit:
-        r.set_pixel_loc(_grid(w, h, rg))
-    else:
-        r.set_raygen(w, h, *rg)
-    return w, h
-
-
-def _kw(g):
-    return dict(spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]) if "seed" in g else 1)
-
-
-def _check(g, u8, f32=None, what=""):
-    co = g["coords"]
-    got = u8[:, co[:, 0], co[:, 1]].T
-    assert np.array_equal(got, g["u8"]), f"{what}: {(got != g['u8']).any(axis=1).sum()} of {len(co)} pixels differ (uint8)"
-    if f32 is not None:
-        assert np.array_equal(f32[:, co[:, 0], co[:, 1]].T.view(np.uint32), g["rgb64"].astype(np.float32).view(np.uint32)), \
-            f"{what}: float32 differs"
-
-
-def _render_host(r, g, flags=0):
-    return r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), u8=True, f32=True, flags=flags, **_kw(g))
+    return set_view(r, g, lambda r, g: r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g)), explicit=explicit)
 
 
 @pytest.mark.parametrize("case", refraction_cases())
 def test_fixture_every_entry_point(renderer, case):
-    g = _load(case)
-    w, h = _setup(renderer, g)
-    u8, f32 = _render_host(renderer, g)
-    _check(g, u8, f32, "rt_render")
-    big = case in BIG
-    p = renderer.params(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), **_kw(g))
-    n, npx = 3, w * h
-    d8 = renderer.malloc(n * 3 * npx)
-    d32 = None if big else renderer.malloc(n * 12 * npx)
-    try:
-        renderer.render_device(p, 0, w, d8, d32, npx)
-        renderer.sync()
-        got = np.empty((3, w, h), np.uint8)
-        renderer.d2h(got, d8)
-        g32 = None
-        if d32 is not None:
-            g32 = np.empty((3, w, h), np.float32)
-            renderer.d2h(g32, d32)
-        _check(g, got, g32, "rt_render_device")
-        renderer.h2d(d8, np.zeros(n * 3 * npx, np.uint8))
-        renderer.render_sequence(p, 0, w, n, d8, d32, npx, 3 * npx, None, None, 2)
-        renderer.sync()
-        seq = np.empty((n, 3, w, h), np.uint8)
-        renderer.d2h(seq, d8)
-        s32 = None
-        if d32 is not None:
-            s32 = np.empty((n, 3, w, h), np.float32)
-            renderer.d2h(s32, d32)
-        for i in range(n):
-            _check(g, seq[i], None if s32 is None else s32[i], f"rt_render_sequence frame {i}")
-    finally:
-        renderer.free(d8)
-        if d32 is not None:
-            renderer.free(d32)
-    if int(g["aa"]) != 2 and case != "c5_s256_d8_sub96":       # stochastic needs the closed-form grid
-        _setup(renderer, g, explicit=True)
-        u8, f32 = _render_host(renderer, g)
-        _check(g, u8, f32, "explicit pixel_loc")
-    if int(g["aa"]) == 1:                                       # the per-pixel 9-tap kernel on the closed-form grid
-        from python_ray_tracer_amd import _lib as L
-        _setup(renderer, g)
-        u8, f32 = _render_host(renderer, g, flags=L.RT_FLAG_AA_PER_PIXEL)
-        _check(g, u8, f32, "RT_FLAG_AA_PER_PIXEL")
+    walk_entry_points(renderer, _load(case), _setup, case in BIG, cameras=False, begin_end=False, explicit=case != BIG[1])
 
 
 @pytest.mark.parametrize("lanes_mins, records", [("30", "1"), ("30", "0"), ("100000", "1"), ("100000", "0")])
 def test_large_fixtures_on_every_traversal(monkeypatch, lanes_mins, records):
     """The 64- and 256-sphere fixtures (every third sphere glass) on the lane-owned and the wave-uniform kernels, with and
     without float64 sphere records in LDS: refracted rays start inside spheres, clusters and boxes."""
-    import python_ray_tracer_amd as pkg
-    monkeypatch.setenv("MI355RT_LANES_MINS", lanes_mins)
-    monkeypatch.setenv("MI355RT_F32_RECORDS", records)
-    r = pkg.Renderer(0)
-    try:
-        for case in BIG:
-            g = _load(case)
-            _setup(r, g)
-            u8, f32 = _render_host(r, g)
-            _check(g, u8, f32, f"{case} LANES_MINS={lanes_mins} F32_RECORDS={records}")
-    finally:
-        r.close()
-
-
-# The environment table of test_gpu_materials.py::test_every_material_kernel_is_the_global_path: between them these launch
-# every one of the 22 refraction kernels (rt_device.h REFR).  With a glass table the frames of one scene must be the same
-# bytes in every variant (there is no global path to compare with).
-_VARIANTS = {
-    "c5_s256_d8_sub96": [{}, {"MI355RT_LANES_PARK": "0"}, {"MI355RT_LANES_MINS": "100000"},
-                         {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"},
-                         {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000", "MI355RT_WPW2_MAX_IMAGE": "10000000"}],
-    "c4_s64_d5_sub32": [{"MI355RT_LANES_MINS": "100000"}, {"MI355RT_LANES_MINS": "100000", "MI355RT_F32_RECORDS": "0"},
-                        {"MI355RT_LANES_MINS": "30"},
-                        {"MI355RT_LANES_MINS": "100000", "MI355RT_CLUSTER_MINS": "100000", "MI355RT_WPW2_MAX_IMAGE": "0"}],
-    "aa_48_d2": [{}, {"MI355RT_WPW2_MAX_IMAGE": "0"}],
-    "tiny": [{}],
-}
-_ENV_KEYS = sorted({k for vs in _VARIANTS.values() for v in vs for k in v})
+    large_fixtures_on_a_traversal(monkeypatch, lanes_mins, records, _load, _setup)
 
 
 def _glass_materials(S, P):
@@ -150,43 +47,17 @@ def _glass_materials(S, P):
     return table, sid, np.full(P, 3, np.int32)
 
 
-@pytest.mark.parametrize("case", list(_VARIANTS))
+@pytest.mark.parametrize("case", list(VARIANTS))
 def test_every_refraction_kernel_same_bytes(monkeypatch, case):
-    import python_ray_tracer_amd as pkg
-    from python_ray_tracer_amd import _lib as L
-    if case == "tiny":
-        g = load_frame("aa_48_d2")
-        src = dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                   cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-    else:
-        src = load_frame(case) if case.startswith("aa_") else _load(case)
-    S, P = src["spheres"].shape[1], src["planes"].shape[1]
-    mats = _glass_materials(S, P)
-    w, h = 160, 96
-    rg = raygen_closed_form(w, h, float(src["fov"]))
-    modes = ((0, 0, 0), (1, 0, 0), (1, L.RT_FLAG_AA_PER_PIXEL, 0), (2, 0, 2))
+    """feature_gpu.VARIANTS launches every one of the 22 refraction kernels (rt_device.h REFR).  With a glass table the frames of
+    one scene must be the same bytes in every variant (there is no global path to compare with)."""
+    src = variant_source(case, _load)
+    mats = _glass_materials(src["spheres"].shape[1], src["planes"].shape[1])
     first = None
-    for env in _VARIANTS[case]:
-        for k in _ENV_KEYS:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        r = pkg.Renderer(0)
-        try:
-            r.set_camera(src["cam_origin"], src["cam_rot"])
-            r.set_raygen(w, h, *rg)
-            r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats)
-            outs = [r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, aa, u8=True, f32=True, flags=flags, spp=spp, seed=3)
-                    for aa, flags, spp in modes]
-        finally:
-            r.close()
-        if first is None:
-            first = outs
-            assert all(u8.any() for u8, _ in outs)
-            continue
-        for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, first):
-            assert u8.tobytes() == r8.tobytes(), (env, aa, flags)
-            assert f32.tobytes() == r32.tobytes(), (env, aa, flags)
+    for env, r in variant_renderers(monkeypatch, case):
+        aim(r, src, 160, 96)
+        r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats)
+        first = same_as_first(first, render_modes(r), env)
 
 
 def test_opaque_five_column_table_is_the_material_path(renderer):
@@ -348,17 +219,9 @@ def test_glass_and_opaque_scenes_in_flight(renderer):
 
 def test_example_with_glass_writes_png(tmp_path):
     """examples/render_png.py --glass: two glass spheres over the mirror floor, through the Renderer API."""
-    import subprocess
-    import sys
-    from PIL import Image
-    from conftest import REPO
     outs = {}
     for flag in (["--materials"], ["--glass"]):
-        out = str(tmp_path / f"{flag[0][2:]}.png")
-        log = subprocess.check_output([sys.executable, os.path.join(REPO, "examples", "render_png.py"), "--size", "160x96", "--depth", "3",
-                                       "--frames", "3", "--out", out] + flag, text=True)
-        assert "wrote" in log
-        outs[flag[0]] = np.asarray(Image.open(out))
+        log, outs[flag[0]] = run_example(str(tmp_path / f"{flag[0][2:]}.png"), "160x96", 3, 3, *flag)
     assert "glass=True" in log
     assert outs["--glass"].shape == (96, 160, 3) and outs["--glass"].any()
     assert not np.array_equal(outs["--glass"], outs["--materials"])

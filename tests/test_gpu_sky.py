@@ -3,33 +3,25 @@ through the dispatcher's environment overrides with the same bytes and the bytes
 unreachable sun, the sun everywhere, a uniform sky over an empty scene, the sky turned upside down), frames in flight across a
 change of sky, column slabs, the error paths and the example."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import REPO, load_frame, raygen_closed_form
-# The environment table and helpers are those of the lens, texture and lighting tests, imported and not copied, so that the sky
-# kernels are held to the same tables as their twins.
+from conftest import raygen_closed_form
+# The environment table and helpers are feature_gpu's, so that the sky kernels are held to the same tables as their twins.
+from feature_gpu import (BIG, IGNORED, KERNEL_LINE, LIT_FAMILIES, check as _check, column_slabs_are_the_full_frame,
+                         family_kernels_same_bytes, fixture_lens, frames as _frames, kw as _kw, lit_scene, render_host as _render_host,
+                         run_example, same_frames as _same_frames, set_view, walk_entry_points)
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_sky import CASES, load_sky, packed
 from test_lighting import fixture_textures, load_lighting
-from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
-from test_gpu_textures import _scene_textures
-from test_gpu_features_vs_oracle import _same
-from test_gpu_lit_vs_oracle import kernel_table_refs
-from test_gpu_lighting import IGNORED, KERNEL_LINE, LIT_FAMILIES, _check, _glossy, _kw, _mats, _render_host, _frames, _same_frames
 
 pytestmark = pytest.mark.gpu
-BIG = ("c4_s64_d5_sub32", "c5_s256_d8_sub96")
 SKY_FAMILIES = {"scatter": 15, "area_lights": 16, "lens": 17, "both": 18}   # rt::Family numbers of the sky kernels
 
 
-@pytest.fixture
-def rend(renderer):
-    """The session's renderer, with the pinhole camera restored afterwards (later tests share it)."""
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
+def _mats(g, cols=8):
+    return np.ascontiguousarray(g["materials"][:, :cols]), g["sphere_material"], g["plane_material"]
 
 
 def _scene(r, g, sky="fixture", **kw):
@@ -40,16 +32,7 @@ def _scene(r, g, sky="fixture", **kw):
 
 
 def _setup(r, g, explicit=False, **kw):
-    w, h = int(g["w"]), int(g["h"])
-    _scene(r, g, **kw)
-    r.set_camera(g["cam_origin"], g["cam_rot"])
-    r.set_lens(float(g["aperture"]), float(g["focus_distance"]))
-    rg = raygen_closed_form(w, h, float(g["fov"]))
-    if explicit:
-        r.set_pixel_loc(_grid(w, h, rg))
-    else:
-        r.set_raygen(w, h, *rg)
-    return w, h
+    return set_view(r, g, lambda r, g: _scene(r, g, **kw), lens=fixture_lens(g), explicit=explicit)
 
 
 def _black(k):
@@ -64,68 +47,21 @@ def _black(k):
 
 @pytest.mark.parametrize("case", CASES)
 def test_fixture_every_entry_point(rend, case):
-    renderer = rend
     g = load_sky(case)
-    w, h = _setup(renderer, g)
-    u8, f32 = _render_host(renderer, g)
-    _check(g, u8, f32, "rt_render")
-    big = case in BIG
-    p = renderer.params(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), **_kw(g))
-    n, npx = 3, w * h
-    d8 = renderer.malloc(n * 3 * npx)
-    d32 = None if big else renderer.malloc(n * 12 * npx)
-    try:
-        renderer.render_device(p, 0, w, d8, d32, npx)
-        renderer.sync()
-        got = np.empty((3, w, h), np.uint8)
-        renderer.d2h(got, d8)
-        g32 = None
-        if d32 is not None:
-            g32 = np.empty((3, w, h), np.float32)
-            renderer.d2h(g32, d32)
-        _check(g, got, g32, "rt_render_device")
-        for cams in (None, np.tile(np.concatenate([g["cam_origin"], g["cam_rot"].reshape(9)]), (n, 1))):
-            renderer.h2d(d8, np.zeros(n * 3 * npx, np.uint8))
-            renderer.render_sequence(p, 0, w, n, d8, d32, npx, 3 * npx, cams, None, 2)   # (cameras=None: launches of 2 frames)
-            renderer.sync()
-            seq = np.empty((n, 3, w, h), np.uint8)
-            renderer.d2h(seq, d8)
-            s32 = None
-            if d32 is not None:
-                s32 = np.empty((n, 3, w, h), np.float32)
-                renderer.d2h(s32, d32)
-            for i in range(n):
-                _check(g, seq[i], None if s32 is None else s32[i], f"rt_render_sequence cameras={cams is not None} frame {i}")
-    finally:
-        renderer.free(d8)
-        if d32 is not None:
-            renderer.free(d32)
-    if not big:                                                 # rt_render_begin / rt_render_end
-        o8, o32 = np.empty((3, w, h), np.uint8), np.empty((3, w, h), np.float32)
-        renderer.render_begin(0, IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), o8, o32, **_kw(g))
-        renderer.render_end(0)
-        _check(g, o8, o32, "rt_render_begin/end")
-    if int(g["aa"]) != 2 and case != "c5_s256_d8_sub96":       # stochastic needs the closed-form grid
-        _setup(renderer, g, explicit=True)
-        u8, f32 = _render_host(renderer, g)
-        _check(g, u8, f32, "explicit pixel_loc")
-    if int(g["aa"]) == 1:                                       # the per-pixel 9-tap kernel on the closed-form grid
-        from python_ray_tracer_amd import _lib as L
-        _setup(renderer, g)
-        u8, f32 = _render_host(renderer, g, flags=L.RT_FLAG_AA_PER_PIXEL)
-        _check(g, u8, f32, "RT_FLAG_AA_PER_PIXEL")
+    walk_entry_points(rend, g, _setup, case in BIG, cameras=True, begin_end=True, explicit=case != BIG[1])
     if "sky_b" in g.files:                                      # the same scene under the fixture's second sky
-        _setup(renderer, g, sky=g["sky_b"])
-        u8, f32 = _render_host(renderer, g)
+        _setup(rend, g, sky=g["sky_b"])
+        u8, f32 = _render_host(rend, g)
         _check(dict(coords=g["coords"], u8=g["u8_b"], rgb64=g["rgb64_b"]), u8, f32, "sky_b")
-    _setup(renderer, g, sky=None)                               # no sky: the fixture's u8_plain
-    u8, _ = _render_host(renderer, g)
+    _setup(rend, g, sky=None)                                   # no sky: the fixture's u8_plain
+    u8, _ = _render_host(rend, g)
     _check(g, u8, None, "without a sky", key="u8_plain")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# One scene, the same bytes from every sky kernel.  test_gpu_lens.py's environment table x the four AA modes reaches all 14
-# shapes of a family; MI355RT_LOG_KERNELS makes every launch name its kernel on stderr.
+# One scene, the same bytes from every sky kernel (feature_gpu.family_kernels_same_bytes): the lighting table's scene under a
+# sky, against its lighting twin without one.
+
 
 SKY = packed(up=(0.0, 0.6, 0.8), zenith=(30.0, 80.0, 210.0), horizon=(230.0, 210.0, 190.0), nadir=(70.0, 60.0, 50.0), sharp=4.0,
              sun_dir=(0.8, 0.0, 0.6), sun_cos=0.97, sun_rgb=(250.0, 230.0, 180.0), halo_rgb=(120.0, 90.0, 40.0), halo_shin=16.0)
@@ -133,67 +69,11 @@ SKY = packed(up=(0.0, 0.6, 0.8), zenith=(30.0, 80.0, 210.0), horizon=(230.0, 210
 
 @pytest.mark.parametrize("kind", list(SKY_FAMILIES))
 def test_every_sky_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
-    import python_ray_tracer_amd as pkg
-    from python_ray_tracer_amd import _lib as L
-    soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
-    w, h = 64, 64
-    modes = ((0, 0, 0), (1, 0, 0), (1, L.RT_FLAG_AA_PER_PIXEL, 0), (2, 0, 2))
-    seen = set()
-    for case in _VARIANTS:
-        if case == "tiny":
-            g = load_frame("aa_48_d2")
-            src = dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                       cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-        else:
-            src = load_frame(case) if case.startswith("aa_") else load_lighting(case)
-        S, P, NL = src["spheres"].shape[1], src["planes"].shape[1], src["lights"].shape[1]
-        table, sid, pid = _lens_materials(S, P)
-        mats = (_glossy(table), sid, pid)
-        radius = np.array([0.5, 0.0, 0.3][:NL], np.float32) if soft else np.zeros(NL, np.float32)
-        rgb = np.array([[1.0, 0.7, 0.4], [0.3, 0.5, 1.5], [0.0, 0.3, 0.2]][:NL], np.float32)
-        tex = _scene_textures(src) if case != "tiny" else None    # (tiny: a sky scene without textures)
-        rg = raygen_closed_form(w, h, float(src["fov"]))
-        refs = kernel_table_refs(oracle, src, w, h, modes, "sky", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
-                                 textures=tex, light_rgb=rgb, sky=SKY)
-        first = plain = None
-        for env in _VARIANTS[case]:
-            for k in _VARIANT_KEYS:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            monkeypatch.setenv("MI355RT_LOG_KERNELS", "1")
-            r = pkg.Renderer(0)
-            try:
-                r.set_camera(src["cam_origin"], src["cam_rot"])
-                r.set_raygen(w, h, *rg)
-                r.set_lens(0.08 if lens else 0.0, 3.0)
-                if plain is None:                                 # the lighting twin: the same scene without a sky
-                    r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats, light_radius=radius, shadow_samples=2,
-                                textures=tex, light_rgb=rgb)
-                    plain = r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, 0, u8=True, seed=3)[0]
-                    names = KERNEL_LINE.findall(capfd.readouterr().err)
-                    assert names and all(int(n[6]) == LIT_FAMILIES[kind] for n in names), (case, env, names)
-                r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats, light_radius=radius, shadow_samples=2,
-                            textures=tex, light_rgb=rgb, sky=SKY)
-                outs = [r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, aa, u8=True, f32=True, flags=flags, spp=spp, seed=3)
-                        for aa, flags, spp in modes]
-            finally:
-                r.close()
-            names = KERNEL_LINE.findall(capfd.readouterr().err)
-            assert names and all(int(n[6]) == SKY_FAMILIES[kind] for n in names), (case, env, names)
-            seen.update(names)
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
-                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
-            if first is None:
-                first = outs
-                assert all(u8.any() for u8, _ in outs)
-                assert not np.array_equal(outs[0][0], plain), case      # (the sky shows)
-                continue
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, first):
-                assert u8.tobytes() == r8.tobytes(), (case, env, aa, flags)
-                assert f32.tobytes() == r32.tobytes(), (case, env, aa, flags)
-    print(f"{kind}: {len(seen)} kernels: {sorted(seen)}")
-    assert len(seen) == 14, f"{kind}: {len(seen)} of the family's 14 kernels ran: {sorted(seen)}"
+    def scenes(src, case):
+        _, mats, tex, rgb = lit_scene(src, case)                # (tiny: a sky scene without textures)
+        lit = dict(materials=mats, textures=tex, light_rgb=rgb)
+        return lit, dict(lit, sky=SKY)
+    family_kernels_same_bytes(monkeypatch, capfd, oracle, kind, SKY_FAMILIES, load_lighting, (64, 64), "sky", scenes, twins=LIT_FAMILIES)
     assert sorted(SKY_FAMILIES.values()) == [15, 16, 17, 18]
 
 
@@ -346,12 +226,7 @@ def test_frames_in_flight_keep_their_sky(rend):
 
 @pytest.mark.parametrize("aa, spp", [(0, 0), (1, 0), (2, 2)])
 def test_column_slab_is_the_full_frame(rend, aa, spp):
-    g = load_sky("everything_48_d4")
-    _setup(rend, g)
-    full8, full32 = _render_host(rend, g, aa=aa, spp=spp)
-    for x0, x1 in ((9, 41), (33, 48)):
-        u8, f32 = _render_host(rend, g, aa=aa, spp=spp, x0=x0, x1=x1)
-        assert np.array_equal(u8, full8[:, x0:x1]) and np.array_equal(f32, full32[:, x0:x1]), (x0, x1)
+    column_slabs_are_the_full_frame(rend, load_sky("everything_48_d4"), _setup, aa, spp, ((9, 41), (33, 48)))
 
 
 def test_errors_leave_the_previous_scene(rend):
@@ -418,11 +293,5 @@ def test_errors_leave_the_previous_scene(rend):
 
 def test_example_with_sky_writes_png(tmp_path):
     """examples/render_png.py --sky: the top row of the picture is sky, not black."""
-    import subprocess
-    from PIL import Image
-    out = str(tmp_path / "sky.png")
-    log = subprocess.check_output([sys.executable, os.path.join(REPO, "examples", "render_png.py"), "--size", "64x64", "--depth", "3",
-                                   "--frames", "2", "--sky", "--out", out], text=True)
-    assert "wrote" in log
-    img = np.asarray(Image.open(out))
+    _, img = run_example(str(tmp_path / "sky.png"), "64x64", 3, 2, "--sky")
     assert img.shape == (64, 64, 3) and img[0].min() > 0 and img[0, :, 2].min() > 100     # blue all along the top row

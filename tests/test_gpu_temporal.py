@@ -18,7 +18,8 @@ from conftest import REPO
 import closest_hit_scenes as chs
 import temporal_cases as tc
 from test_film import same_bits
-from test_gpu_denoise import IGNORED, _read, rend   # noqa: F401  (rend: the session's renderer with the pinhole camera restored)
+from feature_gpu import IGNORED, rend   # noqa: F401  (rend: the session's renderer with the pinhole camera restored)
+from test_gpu_denoise import _read
 
 from python_ray_tracer_amd import Film, denoise as D, film as F, temporal as T
 from python_ray_tracer_amd import _lib as L

@@ -20,7 +20,8 @@ import closest_hit_scenes as chs
 import temporal_cases as tc
 from test_denoise import _flat_guides
 from test_film import same_bits
-from test_gpu_denoise import IGNORED, _read, rend   # noqa: F401  (rend: the session's renderer with the pinhole camera restored)
+from feature_gpu import rend   # noqa: F401  (the session's renderer with the pinhole camera restored)
+from test_gpu_denoise import _read
 from test_gpu_temporal import _orbit_renderer, _pass_sum, _run, _same, _set_view
 from test_temporal_moments import moments_inputs, moments_reference
 from test_variance import noisy_passes

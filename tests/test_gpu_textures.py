@@ -6,38 +6,27 @@ per pixel against the oracle with the texel as the hit object's colour, ids -1 a
 frames in flight across a scene change, column slabs, the error paths and the example."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import REPO, load_frame, raygen_closed_form
-# The environment tables, scenes and comparisons below are those of the lens tests and of the oracle tests, imported and not
-# copied so that the texture kernels are held to the same tables as their twins.  (Those modules stay byte for byte as they
-# are; a rename there shows up here as an import error of this whole module.)
+from conftest import REPO, raygen_closed_form
+# The environment tables, scenes and comparisons are feature_gpu's, so that the texture kernels are held to the same tables as
+# their twins.
+from feature_gpu import (BIG, ENVS, ENVS_IDS, ENVS_KEYS, IGNORED, KERNEL_LINE, MODES, TEX_FAMILIES, check as _check, column_slabs_are_the_full_frame,
+                         family_kernels_same_bytes, family_scene, fixture_lens, kw as _kw, large_fixtures_on_a_traversal, lens_materials,
+                         oracle_modes, render_host as _render_host, run_example, same as _same, same_pixels as _same_pixels,
+                         scene_textures, set_view, walk_entry_points)
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_textures import CASES, fixture_textures, load_texture
-from test_gpu_lens import _VARIANTS, _ENV_KEYS as _VARIANT_KEYS, _grid, _lens_materials
-from test_gpu_features_vs_oracle import _ENVS, _ENV_KEYS, _MODES, _family_scene, _oracle_modes, _same, _same_pixels
-from test_gpu_lit_vs_oracle import kernel_table_refs
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import feature_scenes as fs  # noqa: E402
 
-from python_ray_tracer_amd.scene import Texture, texel_index  # noqa: E402
+from python_ray_tracer_amd.scene import texel_index  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
-BIG = ("c4_s64_d5_sub32", "c5_s256_d8_sub96")
-TEX_FAMILIES = {"scatter": 7, "area_lights": 8, "lens": 9, "both": 10}     # rt::Family numbers of the texture kernels
-KERNEL_LINE = re.compile(r"mi355rt: render_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \(rt::Family\)(\d+)>")
-
-
-@pytest.fixture
-def rend(renderer):
-    """The session's renderer, with the pinhole camera restored afterwards (later tests share it)."""
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 def _mats(g):
@@ -45,41 +34,10 @@ def _mats(g):
 
 
 def _setup(r, g, explicit=False, textured=True):
-    w, h = int(g["w"]), int(g["h"])
-    r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g), light_radius=g["light_radius"],
-                shadow_samples=int(g["shadow_samples"]), textures=fixture_textures(g, textured))
-    r.set_camera(g["cam_origin"], g["cam_rot"])
-    r.set_lens(float(g["aperture"]), float(g["focus_distance"]))
-    rg = raygen_closed_form(w, h, float(g["fov"]))
-    if explicit:
-        r.set_pixel_loc(_grid(w, h, rg))
-    else:
-        r.set_raygen(w, h, *rg)
-    return w, h
-
-
-def _kw(g):
-    return dict(spp=int(g["spp"]) if "spp" in g else 0, seed=int(g["seed"]))
-
-
-def _pick(g, a, x0=0):
-    co = g["coords"]
-    return a[:, co[:, 0] - x0, co[:, 1]].T
-
-
-def _check(g, u8, f32=None, what="", x0=0, key="u8"):
-    got = _pick(g, u8, x0)
-    assert np.array_equal(got, g[key]), f"{what}: {(got != g[key]).any(axis=1).sum()} of {len(got)} pixels differ (uint8)"
-    if f32 is not None:
-        a, e = _pick(g, f32, x0), g["rgb64"].astype(np.float32)
-        bad = (a.view(np.uint32) != e.view(np.uint32)).any(axis=1)
-        assert not bad.any(), (f"{what}: float32 differs at {bad.sum()} of {len(bad)} pixels, e.g. {g['coords'][bad][:4].tolist()}: "
-                               f"{a[bad][:4].tolist()} != {e[bad][:4].tolist()}")
-
-
-def _render_host(r, g, flags=0, aa=None, **kw):
-    return r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]) if aa is None else aa, u8=True,
-                    f32=True, flags=flags, **{**_kw(g), **kw})
+    def scene(r, g):
+        r.set_scene(g["spheres"], g["lights"], g["planes"], materials=_mats(g), light_radius=g["light_radius"],
+                    shadow_samples=int(g["shadow_samples"]), textures=fixture_textures(g, textured))
+    return set_view(r, g, scene, lens=fixture_lens(g), explicit=explicit)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -87,156 +45,29 @@ def _render_host(r, g, flags=0, aa=None, **kw):
 
 @pytest.mark.parametrize("case", CASES)
 def test_fixture_every_entry_point(rend, case):
-    renderer = rend
     g = load_texture(case)
-    w, h = _setup(renderer, g)
-    u8, f32 = _render_host(renderer, g)
-    _check(g, u8, f32, "rt_render")
-    big = case in BIG
-    p = renderer.params(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), **_kw(g))
-    n, npx = 3, w * h
-    d8 = renderer.malloc(n * 3 * npx)
-    d32 = None if big else renderer.malloc(n * 12 * npx)
-    try:
-        renderer.render_device(p, 0, w, d8, d32, npx)
-        renderer.sync()
-        got = np.empty((3, w, h), np.uint8)
-        renderer.d2h(got, d8)
-        g32 = None
-        if d32 is not None:
-            g32 = np.empty((3, w, h), np.float32)
-            renderer.d2h(g32, d32)
-        _check(g, got, g32, "rt_render_device")
-        for cams in (None, np.tile(np.concatenate([g["cam_origin"], g["cam_rot"].reshape(9)]), (n, 1))):
-            renderer.h2d(d8, np.zeros(n * 3 * npx, np.uint8))
-            renderer.render_sequence(p, 0, w, n, d8, d32, npx, 3 * npx, cams, None, 2)   # (cameras=None: launches of 2 frames)
-            renderer.sync()
-            seq = np.empty((n, 3, w, h), np.uint8)
-            renderer.d2h(seq, d8)
-            s32 = None
-            if d32 is not None:
-                s32 = np.empty((n, 3, w, h), np.float32)
-                renderer.d2h(s32, d32)
-            for i in range(n):
-                _check(g, seq[i], None if s32 is None else s32[i], f"rt_render_sequence cameras={cams is not None} frame {i}")
-    finally:
-        renderer.free(d8)
-        if d32 is not None:
-            renderer.free(d32)
-    if not big:                                                 # rt_render_begin / rt_render_end
-        o8, o32 = np.empty((3, w, h), np.uint8), np.empty((3, w, h), np.float32)
-        renderer.render_begin(0, IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], int(g["depth"]), int(g["aa"]), o8, o32, **_kw(g))
-        renderer.render_end(0)
-        _check(g, o8, o32, "rt_render_begin/end")
-    if int(g["aa"]) != 2 and case != "c5_s256_d8_sub96":       # stochastic needs the closed-form grid
-        _setup(renderer, g, explicit=True)
-        u8, f32 = _render_host(renderer, g)
-        _check(g, u8, f32, "explicit pixel_loc")
-    if int(g["aa"]) == 1:                                       # the per-pixel 9-tap kernel on the closed-form grid
-        from python_ray_tracer_amd import _lib as L
-        _setup(renderer, g)
-        u8, f32 = _render_host(renderer, g, flags=L.RT_FLAG_AA_PER_PIXEL)
-        _check(g, u8, f32, "RT_FLAG_AA_PER_PIXEL")
-    _setup(renderer, g, textured=False)                         # every id -1: the fixture's u8_plain
-    u8, _ = _render_host(renderer, g)
+    walk_entry_points(rend, g, _setup, case in BIG, cameras=True, begin_end=True, explicit=case != BIG[1])
+    _setup(rend, g, textured=False)                             # every id -1: the fixture's u8_plain
+    u8, _ = _render_host(rend, g)
     _check(g, u8, None, "every texture id -1", key="u8_plain")
 
 
 @pytest.mark.parametrize("lanes_mins, records", [("30", "1"), ("30", "0"), ("100000", "1"), ("100000", "0")])
 def test_large_fixtures_on_every_traversal(monkeypatch, lanes_mins, records):
-    import python_ray_tracer_amd as pkg
-    monkeypatch.setenv("MI355RT_LANES_MINS", lanes_mins)
-    monkeypatch.setenv("MI355RT_F32_RECORDS", records)
-    r = pkg.Renderer(0)
-    try:
-        for case in BIG:
-            g = load_texture(case)
-            _setup(r, g)
-            u8, f32 = _render_host(r, g)
-            _check(g, u8, f32, f"{case} LANES_MINS={lanes_mins} F32_RECORDS={records}")
-    finally:
-        r.close()
+    large_fixtures_on_a_traversal(monkeypatch, lanes_mins, records, load_texture, _setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# One scene, the same bytes from every texture kernel.  test_gpu_lens.py's environment table x the four AA modes reaches all 14
-# shapes of a family; MI355RT_LOG_KERNELS makes every launch name its kernel on stderr, which is how this test
-# knows.  (A profiler's kernel trace can confirm the list once, but it is not something every test run can take, and it cannot
-# say which launch picked which kernel.)
-
-def _scene_textures(src):
-    """A checkered floor on every plane, a solid checker on every third sphere and a projected image on the ones after them."""
-    S, P = src["spheres"].shape[1], src["planes"].shape[1]
-    rng = np.random.default_rng(S)
-    img = Texture.image(rng.integers(0, 256, (7, 5, 3)), (0.0, -0.3, 0.8), (0.0, 0.9, 0.1), (0.1, 0.0, -0.7))
-    tex = [Texture.checker((240, 240, 240), (20, 20, 20), 0.35), Texture.checker((250, 120, 10), (10, 150, 160), 0.12, solid=True), img]
-    recs, first = [], 0
-    for t in tex:
-        recs.append((t.origin, t.axes, t.dims, first))
-        first += t.texels.shape[0] * t.texels.shape[1] * t.texels.shape[2]
-    st = np.array([1 if i % 3 == 0 else (2 if i % 3 == 1 and i % 2 else -1) for i in range(S)], np.int32)
-    return recs, st, np.zeros(P, np.int32), np.concatenate([t.texels.reshape(-1, 3) for t in tex])
-
+# One scene, the same bytes from every texture kernel (feature_gpu.family_kernels_same_bytes).  (A profiler's kernel trace can
+# confirm the list of kernels once, but it is not something every test run can take, and it cannot say which launch picked which
+# kernel.)
 
 @pytest.mark.parametrize("kind", list(TEX_FAMILIES))
 def test_every_texture_kernel_same_bytes(monkeypatch, capfd, oracle, kind):
-    import python_ray_tracer_amd as pkg
-    from python_ray_tracer_amd import _lib as L
-    soft, lens = kind in ("area_lights", "both"), kind in ("lens", "both")
-    w, h = 160, 96
-    modes = ((0, 0, 0), (1, 0, 0), (1, L.RT_FLAG_AA_PER_PIXEL, 0), (2, 0, 2))
-    seen = set()
-    for case in _VARIANTS:
-        if case == "tiny":
-            g = load_frame("aa_48_d2")
-            src = dict(spheres=g["spheres"][:, :1], lights=g["lights"][:, :1], planes=g["planes"][:, :0], fov=g["fov"],
-                       cam_origin=g["cam_origin"], cam_rot=g["cam_rot"])
-        else:
-            src = load_frame(case) if case.startswith("aa_") else load_texture(case)
-        S, P, NL = src["spheres"].shape[1], src["planes"].shape[1], src["lights"].shape[1]
-        mats = _lens_materials(S, P)
-        radius = np.array([0.5, 0.0, 0.3][:NL], np.float32) if soft else np.zeros(NL, np.float32)
-        tex = _scene_textures(src)
-        rg = raygen_closed_form(w, h, float(src["fov"]))
-        refs = kernel_table_refs(oracle, src, w, h, modes, "textures", materials=mats, radius=radius, lens=(0.08 if lens else 0.0, 3.0),
-                                 textures=tex)
-        first = plain = None
-        for env in _VARIANTS[case]:
-            for k in _VARIANT_KEYS:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            monkeypatch.setenv("MI355RT_LOG_KERNELS", "1")
-            r = pkg.Renderer(0)
-            try:
-                r.set_camera(src["cam_origin"], src["cam_rot"])
-                r.set_raygen(w, h, *rg)
-                r.set_lens(0.08 if lens else 0.0, 3.0)
-                if plain is None:
-                    r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats, light_radius=radius, shadow_samples=2)
-                    plain = r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, 0, u8=True, seed=3)[0]
-                    capfd.readouterr()
-                r.set_scene(src["spheres"], src["lights"], src["planes"], materials=mats, light_radius=radius, shadow_samples=2,
-                            textures=tex)
-                outs = [r.render(IGNORED["amb"], IGNORED["lamb"], IGNORED["refl"], 3, aa, u8=True, f32=True, flags=flags, spp=spp, seed=3)
-                        for aa, flags, spp in modes]
-            finally:
-                r.close()
-            names = KERNEL_LINE.findall(capfd.readouterr().err)
-            assert names and all(int(n[6]) == TEX_FAMILIES[kind] for n in names), (case, env, names)
-            seen.update(names)
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, refs):     # every kernel against the CPU oracle
-                _same(f"{kind} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
-            if first is None:
-                first = outs
-                assert all(u8.any() for u8, _ in outs)
-                assert not np.array_equal(outs[0][0], plain), case      # (the textures show)
-                continue
-            for (aa, flags, _), (u8, f32), (r8, r32) in zip(modes, outs, first):
-                assert u8.tobytes() == r8.tobytes(), (case, env, aa, flags)
-                assert f32.tobytes() == r32.tobytes(), (case, env, aa, flags)
-    print(f"{kind}: {len(seen)} kernels: {sorted(seen)}")
-    assert len(seen) == 14, f"{kind}: {len(seen)} of the family's 14 kernels ran: {sorted(seen)}"
+    def scenes(src, case):
+        mats = lens_materials(src["spheres"].shape[1], src["planes"].shape[1])
+        return dict(materials=mats), dict(materials=mats, textures=scene_textures(src))
+    family_kernels_same_bytes(monkeypatch, capfd, oracle, kind, TEX_FAMILIES, load_texture, (160, 96), "textures", scenes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -282,24 +113,24 @@ def _gpu_frame(r, sc, textures, **kw):
     return r.render(7.0, -3.0, 2.0, sc["depth"], sc["aa"], u8=True, f32=True, flags=sc["flags_aa"], spp=sc["spp"], seed=sc["hseed"], **kw)
 
 
-@pytest.mark.parametrize("case, env", _ENVS, ids=[f"{c}-{'-'.join(f'{k[8:]}={v}' for k, v in e.items()) or 'default'}" for c, e in _ENVS])
+@pytest.mark.parametrize("case, env", ENVS, ids=ENVS_IDS)
 @pytest.mark.parametrize("family", ("mat", "refr", "scat", "soft", "lens_scat", "lens_soft"))
 def test_uniform_texture_every_kernel_vs_oracle(monkeypatch, capfd, oracle, family, case, env):
-    """The (scene, environment) table of test_gpu_features_vs_oracle.py: every shape the dispatcher can pick.  A table of 3 or 5
+    """The (scene, environment) table feature_gpu.ENVS: every shape the dispatcher can pick.  A table of 3 or 5
     columns runs the texture twins of the scatter kernels."""
     import python_ray_tracer_amd as pkg
-    for k in _ENV_KEYS:
+    for k in ENVS_KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     monkeypatch.setenv("MI355RT_LOG_KERNELS", "1")
-    sc = _family_scene(family, case)
-    refs, _ = _oracle_modes(oracle, family, case)
+    sc = family_scene(family, case)
+    refs, _ = oracle_modes(oracle, family, case)
     tex = _uniform_textures(sc["spheres"], sc["planes"], len(case))
     want = {"mat": 7, "refr": 7, "scat": 7, "soft": 8, "lens_scat": 9, "lens_soft": 10}[family]
     r = pkg.Renderer(0)
     try:
-        for (aa, flags, spp), (r8, r32) in zip(_MODES, refs):
+        for (aa, flags, spp), (r8, r32) in zip(MODES, refs):
             u8, f32 = _gpu_frame(r, {**sc, "aa": aa, "flags_aa": flags, "spp": max(spp, 1)}, tex)
             _same(f"{family} {case} {env} aa={aa} flags={flags}", u8, f32, r8, r32)
     finally:
@@ -527,12 +358,7 @@ def test_frames_in_flight_keep_their_textures(rend):
 
 @pytest.mark.parametrize("aa, spp", [(0, 0), (1, 0), (2, 2)])
 def test_column_slab_is_the_full_frame(rend, aa, spp):
-    g = load_texture("everything_48_d4")
-    _setup(rend, g)
-    full8, full32 = _render_host(rend, g, aa=aa, spp=spp)
-    for x0, x1 in ((9, 41), (33, 48)):
-        u8, f32 = _render_host(rend, g, aa=aa, spp=spp, x0=x0, x1=x1)
-        assert np.array_equal(u8, full8[:, x0:x1]) and np.array_equal(f32, full32[:, x0:x1]), (x0, x1)
+    column_slabs_are_the_full_frame(rend, load_texture("everything_48_d4"), _setup, aa, spp, ((9, 41), (33, 48)))
 
 
 def test_errors_leave_the_previous_scene(rend):
@@ -669,17 +495,13 @@ def test_largest_texel_array(rend):
 
 def test_example_with_checker_writes_png(tmp_path):
     """examples/render_png.py --checker [--texture IMAGE]: a checkered floor, and an image on it."""
-    import subprocess
     from PIL import Image
     img = str(tmp_path / "poster.png")
     Image.fromarray(np.random.default_rng(3).integers(0, 256, (12, 16, 3)).astype(np.uint8)).save(img)
     outs = {}
     for flag in (["--materials"], ["--checker"], ["--checker", "--texture", img]):
         out = str(tmp_path / f"{'_'.join(x.strip('-') for x in flag[:2])}{len(flag)}.png")
-        log = subprocess.check_output([sys.executable, os.path.join(REPO, "examples", "render_png.py"), "--size", "160x96", "--depth", "3",
-                                       "--frames", "2", "--out", out] + flag, text=True)
-        assert "wrote" in log
-        outs[" ".join(flag)] = np.asarray(Image.open(out))
+        _, outs[" ".join(flag)] = run_example(out, "160x96", 3, 2, *flag)
     a, b, c = outs.values()
     assert b.shape == (96, 160, 3) and b.any()
     assert not np.array_equal(a, b) and not np.array_equal(b, c)

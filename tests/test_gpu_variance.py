@@ -17,6 +17,8 @@ import torch
 
 from conftest import REPO, raygen_closed_form
 import closest_hit_scenes as chs
+from feature_gpu import IGNORED
+from feature_gpu import rend  # noqa: F401  (the session's renderer with the pinhole camera restored)
 from test_film import same_bits
 from test_variance import FRAMES, frame_guides, noisy_passes
 import variance_cases as vc
@@ -25,14 +27,6 @@ from python_ray_tracer_amd import Film, denoise as D, film as F, variance as V
 from python_ray_tracer_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
-IGNORED = dict(amb=7.0, lamb=-3.0, refl=2.0)   # rt_params shading scalars: a material scene must not read them
-
-
-@pytest.fixture
-def rend(renderer):
-    """The session's renderer, with the pinhole camera restored afterwards (later tests share it)."""
-    yield renderer
-    renderer.set_lens(0.0, 1.0)
 
 
 def _read(r, d, shape, dtype=np.float64):
