@@ -119,10 +119,14 @@ def main():
     ap.add_argument("--auto-exposure", type=float, nargs="?", const=46.0, default=None, metavar="KEY",
                     help="meter the picture on the device: its median luminance maps to KEY (four passes unless --passes)")
     ap.add_argument("--adapt", type=float, default=1.0, metavar="RATE", help="--auto-exposure --orbit: the share of the way the exposure moves per step, (0, 1]")
+    ap.add_argument("--upsample", type=int, default=1, metavar="R",
+                    help="accumulate and filter a film at w/R x h/R and lift it to w x h along full-resolution guides (four passes unless --passes)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "output", "render.png"))
     a = ap.parse_args()
     w, h = (int(v) for v in a.size.lower().split("x"))
-    if (a.denoise or a.temporal or a.denoise_variance or a.bloom is not None or a.auto_exposure is not None) and a.passes <= 0:
+    if a.upsample < 1 or w // a.upsample < 2 or h // a.upsample < 2:
+        ap.error("--upsample takes a ratio R >= 1 that leaves a low-resolution frame of at least 2 x 2")
+    if (a.denoise or a.temporal or a.denoise_variance or a.bloom is not None or a.auto_exposure is not None or a.upsample > 1) and a.passes <= 0:
         a.passes = 4
     if a.denoise_variance and a.denoise:
         ap.error("--denoise-variance stands in place of --denoise")
@@ -203,6 +207,13 @@ def main():
             cam = Camera(resolution=(w, h), position=[-2, 0, 2.0], euler=euler, aperture=a.dof, focus_distance=focus)
             r.set_lens(*cam.lens)
         r.set_raygen(w, h, *cam.raygen())
+        lifter = lambda film: None
+        if a.upsample > 1:                                      # the film runs on the low grid of the same field of view; the picture stays w x h
+            from python_ray_tracer_amd.upsample import Upsampler, hi_raygen
+            fw, fh, full_grid = w, h, tuple(cam.raygen())
+            w, h = fw // a.upsample, fh // a.upsample
+            r.set_raygen(w, h, *hi_raygen(full_grid, fw, fh, w, h))
+            lifter = lambda film: Upsampler(film, fw, fh, raygen=full_grid)
         image = r.host_array((h, w, 3), np.uint8)
         flags = L.RT_FLAG_U8_HWC | L.RT_FLAG_U8_RGB
         aa = 2 if a.spp > 0 else a.aa
@@ -239,7 +250,12 @@ def main():
                 ms = r.timer_end() / (a.orbit * a.passes)
                 if a.bloom is not None and not auto:
                     film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, **src)
-                image = film.resolve(bloom=a.bloom is not None, auto_exposure=auto, **src, **tone)[0]
+                up = lifter(film)
+                if up:                                          # the low-resolution source of that resolve, lifted to the full frame
+                    up.upsample(bloom=a.bloom is not None, **src)
+                image = (up or film).resolve(bloom=a.bloom is not None, auto_exposure=auto, **src, **tone)[0]
+                if up:
+                    up.close()
                 if auto:
                     print("auto-exposure: exposure {:.6g}, metered luminance {:.6g}, {:.0f} pixels, bin {:.0f}".format(*film.exposure()))
         elif a.passes > 0:                                      # a film: the passes summed and resolved on the device
@@ -253,8 +269,13 @@ def main():
                     film.bloom(a.bloom_threshold, a.bloom, a.bloom_levels, denoised=a.denoise or a.denoise_variance)
                 if auto:                                        # the exposure of the source that the resolve shows, solved on the device
                     film.meter(denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None, **meter_kw)
-                image = film.resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags,
-                                     denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None, auto_exposure=auto)[0]
+                up = lifter(film)
+                if up:
+                    up.upsample(denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None)
+                image = (up or film).resolve(exposure=a.exposure, white=a.white, gamma=2 if a.gamma2 else 1, flags=flags,
+                                             denoised=a.denoise or a.denoise_variance, bloom=a.bloom is not None, auto_exposure=auto)[0]
+                if up:
+                    up.close()
                 if auto:
                     print("auto-exposure: exposure {:.6g}, metered luminance {:.6g}, {:.0f} pixels, bin {:.0f}".format(*film.exposure()))
                 r.timer_begin()
@@ -285,6 +306,8 @@ def main():
                 Image.fromarray(np.clip(np.rint(pic), 0, 255).astype(np.uint8).transpose(2, 1, 0)).save(f"{a.guides}_{kind}.png")
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         convert_array_to_image(np.array(image)).save(a.out)
+        if a.upsample > 1:
+            print(f"upsample: the film ran at {w}x{h}, the picture is {fw}x{fh}")
         print(f"{w}x{h} depth {a.depth} aa={a.aa} spp={a.spp} materials={a.materials} glass={a.glass} scatter={a.scatter} soft={a.soft} dof={a.dof} checker={a.checker} lights={a.lights} sky={a.sky} passes={a.passes} denoise={a.denoise} denoise_variance={a.denoise_variance} temporal={a.temporal} orbit={a.orbit}: {ms:.4f} ms per {'pass' if a.passes > 0 else 'frame'} on the device; wrote {a.out}")
 
 

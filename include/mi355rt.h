@@ -929,6 +929,74 @@ int rt_film_resolve_metered(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, 
                             const rt_film_tone *tone, const void *d_state, void *d_u8, void *d_f32, int64_t out_stride,
                             void *stream);
 
+/* Guided upsampling: run the film at low resolution, show it at full.  Accumulate, reproject and filter on a coarse grid, render the
+ * guides alone at display resolution, and lift the filtered mean to the display grid along those guides: edges come from the
+ * full-resolution ids and normals, texture detail from the full-resolution albedo.  RT_ABI_VERSION is unchanged: callers detect
+ * these two entry points by their symbols.
+ *
+ * rt_render_guides_grid: rt_render_guides on the closed-form w x h grid (px, y0, dy, z0, dz) given in the call instead of the
+ * context's grid.  Scene, camera, kernels, table modes, slab splitting and addressing are rt_render_guides': element [g, x, y]
+ * (x0 <= x < x1) is at d_guides[g*plane_stride + (x-x0)*h + y] with this call's h.  The call leaves the context's grid as it is and
+ * does not count as a change of view: a caller alternates low-resolution passes and full-resolution guides every frame, and the
+ * dispatch orders measured for the render launches stay.  The context need not have a grid of its own.  Refusals carry texts
+ * prefixed "rt_render_guides_grid: ", checked in this order: RT_ERR_BAD_ARG for a NULL d_guides and for a frame size that
+ * rt_set_raygen refuses; RT_ERR_STATE without a scene or without a camera; RT_ERR_BAD_ARG unless 0 <= x0 < x1 <= w and for
+ * plane_stride < (x1-x0)*h.  The buffer is then untouched.  Asynchronous on `stream`.
+ *
+ * rt_film_upsample: the lift.  d_lo is a film sum of n passes of the wl x hl frame, or with n = 1 a mean that rt_film_temporal, a
+ * denoiser or rt_film_bloom wrote (planes 0..2 are read, so four-plane buffers work); d_lo_guides and d_hi_guides are the float32
+ * guides of the two frames for the same camera and scene (planes 0..2, 4..6 and 7 are read, plane 3 is not); d_out receives three
+ * float64 planes w x h laid out like a sum, which rt_film_resolve, rt_film_bloom and rt_film_meter take with n = 1; d_out_kind is
+ * NULL or one float32 plane of w*h that says per pixel which stage wrote it (0, 1 or 2).  lo_grid and hi_grid are (px, y0, dy, z0,
+ * dz) of the two frames, as rt_set_raygen and rt_render_guides_grid take them.  The call needs no scene, camera or grid state, and
+ * the library allocates nothing.
+ * Per output pixel p = (X, Y), E = X*h + Y, in float64 without fused multiply-add, in this order; q is a pixel of the low frame,
+ * read at q.x*hl + q.y:
+ *   m[c][q] = lo[c][q] / (double)n;   a_lo[c][q] = max((double)lo_guides[4+c][q], 1.0);   a_hi[c] = max((double)hi_guides[4+c][E], 1.0)
+ *   sc = lo_px / hi_px;   fx = (((double)X*hi_dy + hi_y0) * sc - lo_y0) / lo_dy;   fy = (((double)Y*hi_dz + hi_z0) * sc - lo_z0) / lo_dz
+ *   snap as rt_film_temporal:  rx = floor(fx + 0.5);  |fx - rx| <= 2^-20:  fx = rx        (the same for fy)
+ *   !(fx >= 0):  fx = 0;   fx > wl-1:  fx = wl-1;     the same for fy with hl              (so NaN becomes 0)
+ *   ix = floor(fx); ax = fx - ix;   iy = floor(fy); ay = fy - iy;    idp = hi_guides[7][E]
+ *   stage 0   W = A_c = +0.0;  for a = 0, 1 (outer), b = 0, 1 (inner):  q = (ix+a, iy+b);  bw = (a ? ax : 1.0 - ax) * (b ? ay : 1.0 - ay)
+ *               bw == 0, or q outside [0,wl) x [0,hl):  skip;      lo_guides[7][q] != idp:  skip
+ *               idp >= 0:  cn = ((nx_p*nx_q) + (ny_p*ny_q)) + (nz_p*nz_q)  (float32 normals widened; p from hi_guides, q from lo_guides);
+ *                          !(cn >= normal_cos):  skip
+ *               v_c = demodulate ? m[c][q] / a_lo[c][q] : m[c][q];     W = W + bw;   A_c = A_c + bw * v_c
+ *             W > 0:  out[c][E] = demodulate ? (A_c / W) * a_hi[c] : A_c / W;   kind 0
+ *   stage 1   else W = A_c = +0.0;  for a = -1..2 (outer), b = -1..2 (inner):  q = (ix+a, iy+b)
+ *               q outside the frame:  skip;      lo_guides[7][q] != idp:  skip                (no normal test)
+ *               ex = (double)(ix+a) - fx;  ey = (double)(iy+b) - fy;   wq = 1.0 / (1.0 + (ex*ex + ey*ey))
+ *               v_c as above;     W = W + wq;   A_c = A_c + wq * v_c
+ *             W > 0:  the same output line;   kind 1
+ *   stage 2   else W = A_c = +0.0;  the taps and weights bw of stage 0 (bw == 0 or q outside: skip), no test, no demodulation:
+ *               W = W + bw;   A_c = A_c + bw * m[c][q]
+ *             out[c][E] = A_c / W;   kind 2                 (after the clamp the tap (ix, iy) is inside and its bw > 0, so W > 0)
+ * max(v, 1.0) is v > 1.0 ? v : 1.0.  No exp(), pow() or sqrt: the bytes do not depend on a math library.  With equal grids and
+ * demodulate == 0 every pixel reads one tap of weight 1.0 (the snap), so out is lo / n bit for bit and every kind is 0 (for a
+ * normal_cos that a float32 unit normal passes against itself: its squared length is 1 only to a few 2^-24, so up to 0.999, not 1).
+ * A non-finite mean or guide gives unspecified values but does not fault: every tap index is range-checked before it is read.
+ * The limitations stay where the guides' are: what a mirror or glass shows is interpolated inside the mirror's own id; under a lens
+ * the sharp guides mask a blurred edge; taps do not cross the buffer's edge, so a multi-rank caller upsamples the assembled frame.
+ * RT_ERR_BAD_ARG with texts prefixed "rt_film_upsample: ", checked in this order: a NULL d_lo, d_lo_guides, d_hi_guides, d_out or up;
+ * wl*hl outside 1..RT_FILM_MAX_PIXELS, then w*h; n < 1; lo_stride or lo_guide_stride < wl*hl, hi_guide_stride or out_stride < w*h;
+ * a grid entry that is not finite, or a px, dy or dz of 0 in either grid; normal_cos outside [-1, 1]; a demodulate that is not 0 or 1;
+ * reserved != 0; d_out or d_out_kind equal to an input or to each other.  The outputs are then untouched.  Asynchronous on `stream`. */
+int rt_render_guides_grid(rt_ctx *ctx, int w, int h, double px, double y0, double dy, double z0, double dz,
+                          int x0, int x1, void *d_guides, int64_t plane_stride, void *stream);
+
+typedef struct rt_upsample {
+    double  lo_grid[5];    /* px, y0, dy, z0, dz of the low-resolution frame */
+    double  hi_grid[5];    /* the same of the output frame */
+    double  normal_cos;    /* in [-1, 1]: least cosine between the output pixel's normal and a tap's */
+    int32_t demodulate;    /* 0 or 1: interpolate colour / albedo_lo, multiply by albedo_hi */
+    int32_t reserved;      /* must be 0 */
+} rt_upsample;             /* 96 bytes */
+
+int rt_film_upsample(rt_ctx *ctx, const void *d_lo, int64_t lo_stride, int wl, int hl, int64_t n,
+                     const void *d_lo_guides, int64_t lo_guide_stride,
+                     const void *d_hi_guides, int64_t hi_guide_stride, int w, int h,
+                     const rt_upsample *up, void *d_out, int64_t out_stride, void *d_out_kind, void *stream);
+
 /* Device memory owned by the caller (the DeviceNDArray that `cuda.to_device(np.zeros((3,w,h)))`
  * returns, main.py:32, and `result.copy_to_host()`, main.py:51).  The copies are ordered on the
  * context's stream and return when the bytes have arrived. */

@@ -19,5 +19,7 @@ from . import temporal        # noqa: F401
 from . import variance        # noqa: F401
 from . import bloom           # noqa: F401
 from .film import Film        # noqa: F401
+from . import upsample        # noqa: F401
+from .upsample import Upsampler   # noqa: F401
 
-__all__ = ["bloom", "cuda", "denoise", "film", "temporal", "variance", "Film", "Renderer", "RenderError"]
+__all__ = ["bloom", "cuda", "denoise", "film", "temporal", "upsample", "variance", "Film", "Renderer", "RenderError", "Upsampler"]

@@ -89,6 +89,14 @@ class rt_meter(C.Structure):
                 ("rate", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class rt_upsample(C.Structure):
+    """rt_film_upsample's settings (include/mi355rt.h; the arithmetic in numpy: upsample.upsample_reference): the closed-form grids
+    (px, y0, dy, z0, dz) of the low-resolution and the output frame, finite with px, dy and dz not 0; normal_cos in [-1, 1];
+    demodulate 0 or 1; reserved 0.  96 bytes."""
+    _fields_ = [("lo_grid", C.c_double * 5), ("hi_grid", C.c_double * 5), ("normal_cos", C.c_double), ("demodulate", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function include/mi355rt.h declares.
 _dp, _fp, _vp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p
 PROTOTYPES = {
@@ -145,6 +153,10 @@ PROTOTYPES = {
     "rt_film_meter": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, _vp, _vp]),
     "rt_film_meter_solve": (C.c_int, [_vp, _vp, C.POINTER(rt_meter), _vp, _vp]),
     "rt_film_resolve_metered": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(rt_film_tone), _vp, _vp, _vp, C.c_int64, _vp]),
+    "rt_render_guides_grid": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp,
+                                        C.c_int64, _vp]),
+    "rt_film_upsample": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int,
+                                   C.POINTER(rt_upsample), _vp, C.c_int64, _vp, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_stream_create": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "rt_stream_destroy": (C.c_int, [_vp, _vp]),
@@ -168,7 +180,7 @@ PROTOTYPES = {
 # times such a build beside this one), and Renderer raises where one is called.
 LATER_ENTRIES = ("rt_render_guides", "rt_film_denoise", "rt_film_temporal", "rt_film_accumulate_moments", "rt_film_denoise_variance",
                  "rt_film_temporal_moments", "rt_film_denoise_variance_temporal", "rt_film_bloom", "rt_film_meter", "rt_film_meter_solve",
-                 "rt_film_resolve_metered")
+                 "rt_film_resolve_metered", "rt_render_guides_grid", "rt_film_upsample")
 
 _lib = None
 

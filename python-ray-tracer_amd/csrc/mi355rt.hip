@@ -20,6 +20,7 @@
 #include "rt_scene.h"
 #include "rt_streams.h"
 #include "rt_temporal.h"
+#include "rt_upsample.h"
 
 #include <cmath>
 #include <cstdio>
@@ -861,19 +862,12 @@ int rt_film_resolve(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, 
 // The first-hit guides: one launch of the guides kernel (rt_guides.h) per dispatch the slab needs, in plain tile order.  Scene,
 // camera and grid travel by value as in a render launch (rt_launch.h: frame_part); the cull tables are the stream's own
 // (acquire_tables), built for rays that start at the camera and go no further than the first hit: no lens, depth 0.
-int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream)
+static int guides_launch(rt_ctx *ctx, const rt::View &v, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream)
 {
-    if (!ctx) return RT_ERR_BAD_ARG;
-    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: d_guides is NULL");
-    const rt::View &v = ctx->view;
-    int rc = refuse(ctx, rt::check_state(ctx->have_scene, v));
-    if (rc == RT_OK) rc = refuse(ctx, rt::check_columns(v, x0, x1));
-    if (rc != RT_OK) return rc;
-    if (plane_stride < (int64_t)(x1 - x0) * v.h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_of(ctx, stream);
     StreamRecord *sr = nullptr;
-    rc = stream_record(ctx, st, &sr);
+    int rc = stream_record(ctx, st, &sr);
     if (rc != RT_OK) return rc;
     rt::KParams k;
     rt::guides_part(k, v, ctx->lay, (const double *)ctx->scene[ctx->scene_cur].p, (const double *)ctx->pixel_loc.p,
@@ -898,6 +892,29 @@ int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_
     }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
+}
+
+int rt_render_guides(rt_ctx *ctx, int x0, int x1, void *d_guides, int64_t plane_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    if (!d_guides) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: d_guides is NULL");
+    const rt::View &v = ctx->view;
+    int rc = refuse(ctx, rt::check_state(ctx->have_scene, v));
+    if (rc == RT_OK) rc = refuse(ctx, rt::check_columns(v, x0, x1));
+    if (rc != RT_OK) return rc;
+    if (plane_stride < (int64_t)(x1 - x0) * v.h) return fail(ctx, RT_ERR_BAD_ARG, "rt_render_guides: plane_stride smaller than the slab");
+    return guides_launch(ctx, v, x0, x1, d_guides, plane_stride, stream);
+}
+
+// rt_render_guides on the grid of the call: a copy of the view with that grid goes through the same launch routine; ctx->view and
+// the epoch stay, so the render launches keep their measured dispatch orders.
+int rt_render_guides_grid(rt_ctx *ctx, int w, int h, double px, double y0, double dy, double z0, double dz, int x0, int x1, void *d_guides,
+                          int64_t plane_stride, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_guides_grid(ctx->have_scene, ctx->view.have_cam, w, h, x0, x1, d_guides, plane_stride));
+    if (rc != RT_OK) return rc;
+    return guides_launch(ctx, rt::guides_grid_view(ctx->view, w, h, px, y0, dy, z0, dz), x0, x1, d_guides, plane_stride, stream);
 }
 
 // The film's filter: one launch of the denoise kernel (rt_denoise.h) per level, ping-pong between d_out and d_work so that the last
@@ -1038,6 +1055,25 @@ int rt_film_meter(rt_ctx *ctx, const void *d_sum, int64_t sum_stride, int ws, in
     const rt::MeterHistArgs a = rt::meter_hist_args(d_sum, sum_stride, ws, h, n, d_hist);
     if (reset) hipLaunchKernelGGL(rt::meter_clear_kernel, dim3(1), dim3(rt::METER_THREADS), 0, st, a.hist);
     hipLaunchKernelGGL(rt::meter_hist_kernel, dim3(rt::meter_grid((a.npx + 3) >> 2, ctx->cu_count)), dim3(rt::METER_THREADS), 0, st, a);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// Guided upsampling: one launch of the upsample kernel (rt_upsample.h) over the output frame; both grids travel by value.
+int rt_film_upsample(rt_ctx *ctx, const void *d_lo, int64_t lo_stride, int wl, int hl, int64_t n, const void *d_lo_guides, int64_t lo_guide_stride,
+                     const void *d_hi_guides, int64_t hi_guide_stride, int w, int h, const rt_upsample *up, void *d_out, int64_t out_stride,
+                     void *d_out_kind, void *stream)
+{
+    if (!ctx) return RT_ERR_BAD_ARG;
+    int rc = refuse(ctx, rt::check_film_upsample(d_lo, lo_stride, wl, hl, n, d_lo_guides, lo_guide_stride, d_hi_guides, hi_guide_stride, w, h, up,
+                                                 d_out, out_stride, d_out_kind));
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rt::UpsampleArgs a;
+    rt::upsample_args(a, d_lo, lo_stride, wl, hl, n, d_lo_guides, lo_guide_stride, d_hi_guides, hi_guide_stride, w, h, up, d_out, out_stride,
+                      d_out_kind);
+    hipLaunchKernelGGL(rt::upsample_kernel, dim3(rt::upsample_grid((long long)w * h, ctx->cu_count)), dim3(rt::UPSAMPLE_THREADS), 0,
+                       stream_of(ctx, stream), a);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

@@ -1,4 +1,4 @@
-// rt_film_launch.h — what the film entries (rt_film_accumulate to rt_film_resolve_metered) decide before they touch the device:
+// rt_film_launch.h — what the film entries (rt_film_accumulate to rt_film_upsample) decide before they touch the device:
 //   * the entry checks (check_film_*): each entry's rules in its own order, each shared rule written once (film_*); a film refusal
 //     carries its entry's name, which rt_last_error puts before the text;
 //   * the kernels' arguments: the film's batch plan, the add, resolve and temporal kernels', the filters' (film_batch, *_args);
@@ -16,6 +16,7 @@
 #include "rt_temporal.h"
 #include "rt_bloom.h"
 #include "rt_meter.h"
+#include "rt_upsample.h"
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -475,5 +476,76 @@ inline BloomArgs bloom_args(const BloomLaunch &l, const void *d_sum, int64_t sum
 
 static_assert(BLOOM_MAX_LEVELS == RT_BLOOM_MAX_LEVELS && BLOOM_NO_TILES == RT_BLOOM_NO_TILES, "rt_bloom.h restates the header's constants");
 static_assert(2 * 3 == RT_BLOOM_WORK_PLANES, "the plan uses two sets of three work planes");
+
+// rt_film_upsample and rt_render_guides_grid: their rules in the header's order (the rule macros once more: these entries were added
+// behind bloom's and the meter's arguments).
+#define RT_FILM_RULE(ok, ...) do { if (!(ok)) return film_refusal(e, __VA_ARGS__); } while (0)
+#define RT_FILM_RULES(call) do { const Refusal r_ = (call); if (r_.code != RT_OK) return r_; } while (0)
+
+// A closed-form grid that places pixels: five finite numbers, px, dy and dz not 0.
+inline bool upsample_grid_ok(const double g[5])
+{
+    for (int i = 0; i < 5; ++i) if (!std::isfinite(g[i])) return false;
+    return g[0] != 0.0 && g[2] != 0.0 && g[4] != 0.0;
+}
+
+inline Refusal check_film_upsample(const void *d_lo, int64_t lo_stride, int wl, int hl, int64_t n, const void *d_lo_guides, int64_t lo_guide_stride,
+                                   const void *d_hi_guides, int64_t hi_guide_stride, int w, int h, const rt_upsample *up, const void *d_out,
+                                   int64_t out_stride, const void *d_out_kind)
+{
+    const char *const e = "rt_film_upsample";
+    RT_FILM_RULE(d_lo && d_lo_guides && d_hi_guides && d_out && up, "a buffer or up is NULL");
+    RT_FILM_RULE(wl >= 1 && hl >= 1 && (long long)wl * hl <= RT_FILM_MAX_PIXELS, "wl*hl outside 1..RT_FILM_MAX_PIXELS");
+    RT_FILM_RULE(w >= 1 && h >= 1 && (long long)w * h <= RT_FILM_MAX_PIXELS, "w*h outside 1..RT_FILM_MAX_PIXELS");
+    RT_FILM_RULE(n >= 1, "n < 1");
+    RT_FILM_RULES(film_strides(e, (long long)wl * hl, {lo_stride, lo_guide_stride}, "a plane stride is smaller than its frame"));
+    RT_FILM_RULES(film_strides(e, (long long)w * h, {hi_guide_stride, out_stride}, "a plane stride is smaller than its frame"));
+    RT_FILM_RULE(upsample_grid_ok(up->lo_grid) && upsample_grid_ok(up->hi_grid), "a grid entry is not finite, or a px, dy or dz is 0");
+    RT_FILM_RULE(up->normal_cos >= -1.0 && up->normal_cos <= 1.0, "normal_cos outside [-1, 1]");
+    RT_FILM_RULE(up->demodulate == 0 || up->demodulate == 1, "demodulate must be 0 or 1");
+    RT_FILM_RULE(up->reserved == 0, "reserved must be 0");
+    return film_own(e, {d_out, d_out_kind}, {d_lo, d_lo_guides, d_hi_guides}, "d_out and d_out_kind must be buffers of their own");
+}
+
+static_assert(sizeof(rt_upsample) == 96, "rt_upsample is 96 bytes");
+
+inline void upsample_args(UpsampleArgs &a, const void *d_lo, int64_t lo_stride, int wl, int hl, int64_t n, const void *d_lo_guides,
+                          int64_t lo_guide_stride, const void *d_hi_guides, int64_t hi_guide_stride, int w, int h, const rt_upsample *up,
+                          void *d_out, int64_t out_stride, void *d_out_kind)
+{
+    a.lo = (const double *)d_lo; a.lo_guides = (const float *)d_lo_guides; a.hi_guides = (const float *)d_hi_guides;
+    a.out = (double *)d_out; a.kind = (float *)d_out_kind;
+    a.lo_stride = lo_stride; a.lo_guide_stride = lo_guide_stride; a.hi_guide_stride = hi_guide_stride; a.out_stride = out_stride;
+    a.wl = wl; a.hl = hl; a.w = w; a.h = h; a.n = (double)n;
+    a.lo_px = up->lo_grid[0]; a.lo_y0 = up->lo_grid[1]; a.lo_dy = up->lo_grid[2]; a.lo_z0 = up->lo_grid[3]; a.lo_dz = up->lo_grid[4];
+    a.hi_px = up->hi_grid[0]; a.hi_y0 = up->hi_grid[1]; a.hi_dy = up->hi_grid[2]; a.hi_z0 = up->hi_grid[3]; a.hi_dz = up->hi_grid[4];
+    a.normal_cos = up->normal_cos; a.demod = up->demodulate;
+}
+
+// rt_render_guides_grid: rt_set_raygen's rule for the frame, then rt_render_guides' for state, columns, buffer and stride, measured
+// against the grid of the call.  The context's own grid is not asked for.
+inline Refusal check_guides_grid(bool have_scene, bool have_cam, int w, int h, int x0, int x1, const void *d_guides, int64_t plane_stride)
+{
+    const char *const e = "rt_render_guides_grid";
+    RT_FILM_RULE(d_guides, "d_guides is NULL");
+    RT_FILM_RULE(rt_geo_frame_ok(w, h), "frame size out of range (1 <= w <= 2^31 - 8, 1 <= h <= 2^29 - 32, w*h <= 2^31)");
+    RT_FILM_RULE(have_scene, "rt_set_scene has not been called", RT_ERR_STATE);
+    RT_FILM_RULE(have_cam, "rt_set_camera has not been called", RT_ERR_STATE);
+    RT_FILM_RULE(x0 >= 0 && x1 <= w && x0 < x1, "column range must satisfy 0 <= x0 < x1 <= w");
+    RT_FILM_RULE(plane_stride >= (int64_t)(x1 - x0) * h, "plane_stride smaller than the slab");
+    return {};
+}
+
+// The view of such a call: the context's camera and lens under the closed-form grid given.
+inline View guides_grid_view(const View &ctx_view, int w, int h, double px, double y0, double dy, double z0, double dz)
+{
+    View v = ctx_view;
+    v.w = w; v.h = h; v.px = px; v.y0 = y0; v.dy = dy; v.z0 = z0; v.dz = dz;
+    v.explicit_grid = false; v.have_grid = true;
+    return v;
+}
+
+#undef RT_FILM_RULE
+#undef RT_FILM_RULES
 
 }  // namespace rt

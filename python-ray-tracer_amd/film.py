@@ -273,6 +273,14 @@ class Film:
                 raise ValueError(self._refusal(product, read))
         return getattr(self, self.made[chain[-1]][2]), self.passes if chain[-1] == "sum" else 1
 
+    def source(self, denoised=False, temporal=False, bloom=False, auto_exposure=False):
+        """What resolve() with these flags would read, for a stage outside the film (upsample.Upsampler): (address, n, the serial of
+        the write that made it, the meter's state for it or None); ValueError as resolve()'s where the chain is broken.  A later
+        write of that source, or of anything it was made from, gives another serial."""
+        self._live()
+        src, n = self._source(denoised, temporal, bloom)
+        return src, n, self.made[products(denoised, temporal, bloom)[-1]][0], self._metered(denoised, temporal, bloom) if auto_exposure else None
+
     def _refusal(self, product, read):
         """Why `product` is not there to be read as made from `read`, and the step to run first.  A filtered mean that exists says
         which of the two means it is of."""

@@ -563,6 +563,33 @@ class Renderer:
         self._check(self._later_entry("rt_film_resolve_metered")(self._ctx, _vp(d_sum), sum_stride, int(ws), int(h), int(n), C.byref(tone),
                                                                  _vp(d_state), _vp(d_u8), _vp(d_f32), int(out_stride), _vp(stream)))
 
+    def render_guides_grid(self, w, h, raygen, x0, x1, d_guides, plane_stride=None, stream=None):
+        """render_guides on the closed-form w x h grid raygen = (px, y0, dy, z0, dz) given here instead of the renderer's
+        (rt_render_guides_grid): float32 (RT_GUIDE_PLANES, x1-x0, h) of the current scene and camera.  The renderer's own frame and
+        grid stay as they are, and so do the dispatch orders measured for its render launches.  Asynchronous."""
+        w, h = check_frame(w, h)
+        px, y0, dy, z0, dz = (float(v) for v in raygen)
+        if plane_stride is None:
+            plane_stride = (int(x1) - int(x0)) * h
+        self._check(self._later_entry("rt_render_guides_grid")(self._ctx, w, h, px, y0, dy, z0, dz, int(x0), int(x1), _vp(d_guides),
+                                                               int(plane_stride), _vp(stream)))
+
+    def film_upsample(self, d_lo, wl, hl, n, d_lo_guides, d_hi_guides, w, h, lo_grid, hi_grid, d_out, d_out_kind=None, *, normal_cos=0.95,
+                      demodulate=1, lo_stride=None, lo_guide_stride=None, hi_guide_stride=None, out_stride=None, stream=None, reserved=0):
+        """Guided upsampling (rt_film_upsample): the sum of n passes of the wl x hl frame at d_lo (or a mean, with n = 1) lifted along
+        the guides of both frames (d_lo_guides, d_hi_guides; lo_grid, hi_grid their closed-form grids) into the float64 (3, w, h)
+        buffer d_out; d_out_kind: None, or a float32 (w, h) plane that receives the stage (0, 1, 2) that wrote each pixel.  The
+        result is a mean: resolve it with film_resolve(..., n=1).  Asynchronous.  In numpy: upsample.upsample_reference."""
+        lo_stride, lo_guide_stride = _strides(int(wl) * int(hl), lo_stride, lo_guide_stride)
+        hi_guide_stride, out_stride = _strides(int(w) * int(h), hi_guide_stride, out_stride)
+        up = L.rt_upsample()
+        up.lo_grid[:] = [float(v) for v in lo_grid]
+        up.hi_grid[:] = [float(v) for v in hi_grid]
+        up.normal_cos, up.demodulate, up.reserved = float(normal_cos), int(demodulate), int(reserved)
+        self._check(self._later_entry("rt_film_upsample")(self._ctx, _vp(d_lo), lo_stride, int(wl), int(hl), int(n), _vp(d_lo_guides),
+                                                          lo_guide_stride, _vp(d_hi_guides), hi_guide_stride, int(w), int(h), C.byref(up),
+                                                          _vp(d_out), out_stride, _vp(d_out_kind), _vp(stream)))
+
     def sync(self, stream=None):
         """Wait for the context's stream, or for `stream`(a handle from stream_create / a hipStream_t address)."""
         if stream:
